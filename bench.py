@@ -18,6 +18,12 @@ torch.distributed.run, one rank per GPU, RCCL).  Prints ONE JSON line on rank 0.
               timed region on the engine's stream.
   cpu_baseline = the CPU oracle (oracle/benson_cpu.c: sequential loop, warm-started dense dual
               simplex, 1 core) on the first LPs of the same workload, rank 0, N=1 only.
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds what takes work of
+its own after the timed region: cpu_baseline (with the rounds-1-2 rule on a fresh engine and the
+S-small whole-run pair), long_window and live_vertices; a plain run reports them as null.
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float64, <= 64 MB):
+the inputs are seeded, so two builds run with the same arguments can be compared array for array.
 """
 import argparse
 import ctypes
@@ -28,6 +34,47 @@ import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
+
+DUMP_LIMIT = 64 << 20        # bytes of all arrays of one --dump-outputs
+
+
+def sample_rows(n, k, seed):
+    """indices of a fixed, seeded sample of k of n rows (all of them when n <= k), ascending"""
+    import numpy as np
+    if n <= k:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(seed).choice(n, k, replace=False))
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs DIR: one DIR/<name>.npy per array, float64, at most DUMP_LIMIT bytes in all"""
+    import numpy as np
+    arrays = {k: np.ascontiguousarray(a, np.float64) for k, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit("--dump-outputs: %d bytes, more than the limit of %d" % (total, DUMP_LIMIT))
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), a)
+    print("bench: %d arrays (%d bytes) written to %s" % (len(arrays), total, dirname), file=sys.stderr, flush=True)
+
+
+def poly_outputs(eng, rows=200_000):
+    """the outer approximation after the last step, as --dump-outputs writes it: a fixed, seeded sample of the vertex / direction
+    slots (coordinates, flags used / ideal, slot number) and of the facet slots (coefficients, flags used / ideal, slot number)"""
+    import numpy as np
+    from bensolve_amd._lib import check
+    L, h, d = eng.lib, eng._poly_h, eng.q
+    nv, nf = L.bslv_poly_nprimal(h), L.bslv_poly_ndual(h)
+    pu, pi, ps = (np.zeros(nv, np.uint8) for _ in range(3))
+    X = np.zeros((nv, d))
+    check(L.bslv_poly_get_primal(h, pu.ctypes.data, pi.ctypes.data, ps.ctypes.data, X.ctypes.data))
+    du, di = np.zeros(nf, np.uint8), np.zeros(nf, np.uint8)
+    Y = np.zeros((nf, d))
+    check(L.bslv_poly_get_dual(h, du.ctypes.data, di.ctypes.data, Y.ctypes.data))
+    sv, sf = sample_rows(nv, rows, 1), sample_rows(nf, rows, 2)
+    return {"poly_vertices": X[sv], "poly_vertex_flags": np.stack([pu[sv], pi[sv]], 1), "poly_vertex_slots": sv,
+            "poly_facets": Y[sf], "poly_facet_flags": np.stack([du[sf], di[sf]], 1), "poly_facet_slots": sf}
 
 
 def bench_ex09_lp(args):
@@ -64,6 +111,7 @@ def bench_ex09_lp(args):
     dst = np.arange(1, B + 1, dtype=np.int32)
 
     bad = [0]
+    last = {}
 
     def one_step():
         # every coordinate scaled by itself: a few thousand pivots away from the LP the batch starts from (points on the ray through v0 keep
@@ -72,6 +120,7 @@ def bench_ex09_lp(args):
         V = v0 * rng.uniform(0.6, 0.98, size=(B, prob["q"]))
         stv, itv = eng.solve_batch(src, dst, np.full((B, model.r), -np.inf), model.ub_for(V))
         bad[0] += int((stv != 4).sum())        # (revised form: an LP whose inverse drifted comes back UNDEFINED for the caller's retry)
+        last.update(status=stv, pivots=itv)
         return int(itv.sum()), eng.last_stats()
     for _ in range(warm):
         one_step()
@@ -86,6 +135,11 @@ def bench_ex09_lp(args):
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     eng.set_profile(False)
+    if args.dump_outputs:
+        # the last batch as its caller reads it: status and pivots per LP, objective, the duals w of the q rows -P x + y = 0, y and x
+        dump_outputs(args.dump_outputs, {"lp_status": last["status"], "lp_pivots": last["pivots"], "lp_objective": eng.obj(dst),
+                                         "lp_w": eng.dual(dst, model.w_first, prob["q"]), "lp_y": eng.primal(dst, model.y_first, prob["q"]),
+                                         "lp_x": eng.primal(dst, model.M, model.n)})
     rev = int(eng.lib.bslv_lpq_is_revised(eng.h))
     eng.close()
     ldt = (model.M + 15) // 16 * 16
@@ -123,6 +177,9 @@ def main():
     ap.add_argument("--no-long-window", action="store_true", help="skip the continuation of the run to 5x the steps (reported as long_window, not part of value)")
     ap.add_argument("--no-pair", action="store_true", help="skip the S-small whole-run GPU/CPU pair of cpu_baseline")
     ap.add_argument("--cpu-lps", type=int, default=0, help="LPs of the CPU sample (default by workload)")
+    ap.add_argument("--full", action="store_true", help="also the figures beside the headline: the CPU baseline, the S-small whole-run pair, the rounds-1-2 rule "
+                                                        "on a fresh engine, the long window and the live-vertex count (a plain run measures the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed as DIR/<name>.npy (float64)")
     args = ap.parse_args()
     if args.workload == "ex09-lp":
         return bench_ex09_lp(args)
@@ -202,6 +259,7 @@ def main():
     pipe = None
     phase_ms = [0.0, 0.0, 0.0]          # host wall clock of collect / LP batch / cut application (N=1, unpipelined)
     dist_ms = [0.0, 0.0, 0.0, 0.0]      # N > 1, this rank: collect / its LPs / all-gather (waits for the slowest rank) / application of ALL ranks' cuts
+    last_records = [None]               # cut records of the latest LP batch (N=1, unpipelined; for --dump-outputs)
 
     def one_step():
         if world > 1:
@@ -224,6 +282,7 @@ def main():
         s = eng.apply(rec)
         t3 = time.perf_counter()
         phase_ms[0] += (t1 - t0) * 1e3; phase_ms[1] += (t2 - t1) * 1e3; phase_ms[2] += (t3 - t2) * 1e3
+        last_records[0] = rec
         s.update(n_local=nl, n_total=nt, pivots=piv, lockstep=ls)
         return s
 
@@ -302,20 +361,31 @@ def main():
     # the counters of the timed region, before anything else runs on this engine
     snap = {"counts": eng.poly_call("counts"), "rounds_run": eng.poly_call("rounds_run"), "path_stats": eng.poly_call("path_stats"),
             "health": eng.poly_call("rounds2_health"), "starts": eng.start_stats(), "totals": eng.totals(), "r2": eng.poly_call("rounds2_stats"), "defer": eng.defer_stats()}
-    snap["live"] = int(eng.poly_dump()["pu"].sum()) if snap["counts"]["nprimal"] < 5_000_000 and stopped is None else -1
+    if args.full:
+        snap["live"] = int(eng.poly_dump()["pu"].sum()) if snap["counts"]["nprimal"] < 5_000_000 and stopped is None else -1
+    else:
+        snap["live"] = None
     eng.lib.bslv_poly_largest_facet.argtypes = [ctypes.c_void_p]
     snap["largest_facet"] = int(eng.lib.bslv_poly_largest_facet(eng._poly_h))
     if rank == 0: print("bench: timed region done (%d steps, %.3f s)" % (args.steps, dt), file=sys.stderr, flush=True)
+    if args.dump_outputs and rank == 0:
+        # what the last timed step computed: its counts, the cut records of its LP batch (one row per LP: the records
+        # solve_local hands to apply; N = 1 without --pipeline) and the outer approximation it left (replicated on every rank)
+        outs = {"step_counts": [s.get(k, 0) for k in ("lps", "cuts", "redundant", "confirmed", "failed")]}
+        if last_records[0] is not None and world == 1 and pipe is None:
+            outs["lp_records"] = last_records[0]
+        outs.update(poly_outputs(eng))
+        dump_outputs(args.dump_outputs, outs)
     phase_timed = list(phase_ms)         # (a copy: one_step() keeps adding to phase_ms if the run goes on below)
     lz1 = lazy_stats()
     mat_ms = lz1[2] - lz0[2]             # tableau passes made on request at the end of apply() (lazy tableaux): LP work, booked under "lp_tableaux_on_request", not under the cuts
     dist_timed = list(dist_ms)
-    # Everything the headline needs is measured.  Two more figures for the reader, outside the timed region (rank 0, one GPU):
+    # Everything the headline needs is measured.  With --full, two more figures for the reader, outside the timed region (rank 0, one GPU):
     #  * long_window: the SAME run continued to 5x the steps -- S-mid never terminates, the polyhedron keeps growing, and the rate
     #    of the first steps after the ramp is not the rate of a long run;
     #  * below, after the CPU baseline: the batch selection rule of rounds 1-2 (newest vertices first) on a fresh engine.
     long_window = None
-    if world == 1 and pipe is None and args.workload == "S-mid" and not args.no_long_window:
+    if args.full and world == 1 and pipe is None and args.workload == "S-mid" and not args.no_long_window:
         try:
             extra = 4 * args.steps
             l2 = c2 = f2 = 0
@@ -410,13 +480,13 @@ def main():
                      "cuts_handed_back": snap["defer"]["handed_back"], "cuts_waiting_at_end": snap["defer"]["waiting"], "one_family_batches": snap["defer"]["one_family_batches"],
                      "note": "a round applies a maximal set of mutually independent cuts of the chunk (<= 1024 cuts) in the passes of one cut: ~250 us of dependent small launches, latency-bound (profiles/r03_cut_phase_counters.json: 64-92 % of wave cycles waiting)"}
 
-    cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload.startswith("S-degenerate") and not args.cpu_lps:
+    cpu = None               # (--full only: the CPU oracle on the same workload, the rounds-1-2 rule, the S-small pair)
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload.startswith("S-degenerate") and not args.cpu_lps:
         # the oracle's plain dual simplex does not finish ONE cold LP of this family at full size in minutes (45 k pivots at
         # q=6, n=500): no CPU figure instead of a bench that never returns.  --cpu-lps N forces the attempt.
         cpu = {"value": None, "unit": "LPs/s", "cores": 1, "kind": "port",
                "sample": "not measured: oracle/lp_dense.c needs > 10 minutes for the cold start of one 4000 x 2000 LP of the degenerate family (no bound flipping, no perturbation); --cpu-lps N forces it"}
-    elif rank == 0 and world == 1 and not args.no_cpu_baseline:
+    elif args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import oracle_api
         # same stage on both sides: the CPU oracle first works through `warm` LPs untimed-by-us (its cold solve and the first,

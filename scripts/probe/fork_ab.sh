@@ -5,7 +5,7 @@ out=gpurun_out/fork_ab.log
 : > $out
 BSLV_R2_FORK=1 timeout -k 10 500 python -m pytest tests/test_poly_modes_gpu.py tests/test_benson_gpu.py tests/test_fill_gpu.py -x -q -m gpu > gpurun_out/fork_tests.log 2>&1 || { tail -40 gpurun_out/fork_tests.log; exit 1; }
 tail -4 gpurun_out/fork_tests.log
-run() { echo "== $1" >> $out; env $1 timeout -k 10 200 python bench.py --no-cpu-baseline >> $out 2>> gpurun_out/fork_ab.err || echo "FAILED rc=$?" >> $out; }
+run() { echo "== $1" >> $out; env $1 timeout -k 10 200 python bench.py --full --no-cpu-baseline >> $out 2>> ${out%.log}.err || echo "FAILED rc=$?" >> $out; }
 run BSLV_R2_FORK=0 && run BSLV_R2_FORK=1 && run BSLV_R2_FORK=0 && run BSLV_R2_FORK=1
 python3 - <<PY | tee gpurun_out/fork_ab_summary.txt
 import json

@@ -7,7 +7,7 @@ for cfg in "$@"; do
   envs=""; flags=""
   for w in $cfg; do case $w in *=*) envs="$envs $w";; *) flags="$flags $w";; esac; done
   echo "== $cfg" >> $out
-  env $envs python bench.py --no-cpu-baseline $flags 2>>$out | python -c "
+  env $envs python bench.py --full --no-cpu-baseline $flags 2>>$out | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

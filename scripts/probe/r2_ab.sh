@@ -1,7 +1,7 @@
 #!/bin/bash
 out=gpurun_out/r2_ab.log
 : > $out
-run() { echo "== $*" >> $out; env $1 BSLV_TIMING=1 timeout -k 10 300 python bench.py --no-cpu-baseline "${@:2}" >> $out 2>&1 || echo "FAILED rc=$?" >> $out; }
+run() { echo "== $*" >> $out; env $1 BSLV_TIMING=1 timeout -k 10 300 python bench.py --full --no-cpu-baseline "${@:2}" >> $out 2>&1 || echo "FAILED rc=$?" >> $out; }
 run "BSLV_CHUNK_CUTS=512" --workload S-small --steps 6 --warmup 1
 run "BSLV_CHUNK_CUTS=1024" --workload S-small --steps 6 --warmup 1
 run "BSLV_CHUNK_CUTS=512" --workload S-mid --steps 8 --warmup 2

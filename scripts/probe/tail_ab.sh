@@ -2,7 +2,7 @@
 # the stop rule of the rounds on S-mid: thin tail rounds through the single-cut pipeline instead (BSLV_R2_MIN_CUTS x BSLV_R2_RULE)
 out=gpurun_out/tail_ab.log
 : > $out
-run() { echo "== $*" >> $out; env $* timeout -k 10 200 python bench.py --no-cpu-baseline >> $out 2>> gpurun_out/tail_ab.err || echo "FAILED rc=$?" >> $out; }
+run() { echo "== $*" >> $out; env $* timeout -k 10 200 python bench.py --full --no-cpu-baseline >> $out 2>> ${out%.log}.err || echo "FAILED rc=$?" >> $out; }
 run BSLV_R2_MIN_CUTS=0 && run BSLV_R2_MIN_CUTS=2 BSLV_R2_RULE=1 && run BSLV_R2_MIN_CUTS=3 BSLV_R2_RULE=1 && run BSLV_R2_MIN_CUTS=4 BSLV_R2_RULE=1 && run BSLV_R2_MIN_CUTS=6 BSLV_R2_RULE=1 && run BSLV_R2_MIN_CUTS=0
 python3 - <<PY | tee gpurun_out/tail_ab_summary.txt
 import json

@@ -5,6 +5,7 @@ expected outputs, no reference text.
 
   poly_ref.npz   canonicalised results of the REFERENCE polyhedron engine (bslv_poly.c, unmodified,
                  via oracle/_ref/libref_poly.so) for fixed cut sequences
+  poly_ref_live.npz  the same for the random-tangent sequences the oracle is also checked on live
   lp_highs.json  optimal objective values of P2(v) instances from scipy/HiGHS (independent solver;
                  the reference's own LP solver, GLPK, is not installed: parity unpinned by the reference)
   hybrid_*.npz   outputs of oracle/_ref/bensolve_hybrid (reference driver + reference polyhedron
@@ -257,6 +258,26 @@ def make_poly_large():
     json.dump(meta, open(os.path.join(HERE, "poly_ref_large.json"), "w"), indent=1)
 
 
+LIVE_CASES = [(3, 500, 21), (4, 150, 22), (5, 150, 23)]
+
+
+def make_poly_live():
+    """the reference's results for the random-tangent sequences of tests/test_oracle_poly.py::test_oracle_matches_compiled_reference_live
+    (cuts from ph.tangent_halfspaces(q, N, seed), initialised after q + 2 of them), canonicalised as in poly_ref.npz"""
+    out = {}
+    for q, N, seed in LIVE_CASES:
+        name = "tangent_q%d_N%d_s%d" % (q, N, seed)
+        P = ph.FlatPoly("ref", q)
+        ph.run_sequence(P, ph.tangent_halfspaces(q, N, seed), init_after=q + 2)
+        P.dual_adjacency()
+        can = ph.canonical(P.dump())
+        P.close()
+        for k, v in pack(can).items():
+            out[name + "/" + k] = v
+        print("poly live", name, "primal", len(can["X"]), "dual", len(can["Y"]))
+    np.savez_compressed(os.path.join(HERE, "poly_ref_live.npz"), **out)
+
+
 def make_lp():
     from scipy.optimize import linprog
     rec = []
@@ -326,8 +347,12 @@ if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "snap":
         make_poly_snap()
         sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "live":
+        make_poly_live()
+        sys.exit(0)
     make_poly()
     make_poly_snap()
+    make_poly_live()
     make_poly_large()
     make_lp()
     make_hybrid()

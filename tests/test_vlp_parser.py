@@ -1,5 +1,5 @@
 """CPU: the C .vlp reader (kept file-format contract, bslv_vlp.c:275-588) on the reference's own
-example files (when /root/reference is present) and on generated files; error behaviour."""
+example files (tests/golden/ex) and on generated files; error behaviour."""
 import ctypes
 import os
 import numpy as np
@@ -7,7 +7,7 @@ import pytest
 
 from bensolve_amd import load_library, synth
 
-REF_EX = "/root/reference/ex"
+REF_EX = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ex")      # the example files of the reference's suite
 
 
 class Vlp(ctypes.Structure):
@@ -77,7 +77,6 @@ def py_read(path):
     return d
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_EX), reason="reference examples only exist in the build container")
 @pytest.mark.parametrize("ex", ["ex01", "ex02", "ex03", "ex04", "ex05", "ex06", "ex07", "ex08", "ex10", "ex11"])
 def test_reference_examples_parse(ex):
     path = os.path.join(REF_EX, ex + ".vlp")
