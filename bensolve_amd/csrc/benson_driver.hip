@@ -213,14 +213,6 @@ int bslv_benson_create_ex(bslv_benson **out, int m, int n, int q, const double *
     rc = bslv_poly_create(&h->poly, q, 1 /* lowerV2upperH */, c);
     if (rc) { bslv_benson_destroy(h); return rc; }
     h->pool_slots = pool_slots;
-    if (const char *e = getenv("BSLV_RESERVE")) {        // opt-in: capacity of the polyhedron ahead of need, "elements[:edges[:pool words]]" (bslv_poly_reserve)
-        long a = 0, b = 0, c3 = 0;
-        if (sscanf(e, "%ld:%ld:%ld", &a, &b, &c3) >= 1 && a > 0) {
-            if (b <= 0) b = 4 * a;
-            if (c3 <= 0) c3 = 16 * a;
-            if ((rc = bslv_poly_reserve(h->poly, a, b, c3))) { bslv_benson_destroy(h); return rc; }
-        }
-    }
     if (const char *e = getenv("BSLV_POLICY")) {         // tuning: "policy[:a[:b]]" -- 3:cap:window, 4:fronts:cap, 6:mode:batches
         int pol = 0, a = -1, b = -1, c4 = -1;
         if (sscanf(e, "%d:%d:%d:%d", &pol, &a, &b, &c4) >= 1 && pol >= 1 && pol <= 6) {
@@ -856,11 +848,6 @@ int bslv_benson_apply_ctx(bslv_benson *h, int ctx, int nrec, const double *recor
     // (and the batch is large -- small batches have nothing but thin rounds; every waiting cut also holds a tableau of the pool)
     const int thr = (nrec >= 512 && h->world == 1 && !h->mark_at_collect && ncut - (int)cut_src.size() < std::min(h->defer_max, h->pool_slots / 8)) ? h->defer_thr : 0;
     if ((rc = bslv_poly_set_defer(h->poly, thr))) return rc;
-    if (ncut) {       // the depth of every cut, for the order of the rounds (BSLV_R2_ORDER; unused by default)
-        std::vector<double> zs(ncut);
-        for (int c = 0; c < ncut; c++) zs[c] = info[c].z;
-        if ((rc = bslv_poly_set_cut_priorities(h->poly, ncut, zs.data()))) return rc;
-    }
     if (ncut && (rc = bslv_poly_add_cuts(h->poly, ncut, cuts.data(), nullptr, prc.data()))) return rc;
     // bookkeeping: facet ids f0.. were assigned in this order on every rank
     std::lock_guard<std::mutex> lk(h->slot_mu);

@@ -437,15 +437,6 @@ __device__ __forceinline__ void classify_elem(const PolyView &P, const double *_
     }
     if (TOUCH && i < nv) { tc[i] = touch; t1[i] = first; }
 }
-template <int D, bool TOUCH>
-__device__ __forceinline__ void classify_batch_body(const PolyView &P, const double *__restrict__ hps, int B, int nv,
-                                                    unsigned long long *__restrict__ out, unsigned *__restrict__ anyminus,
-                                                    int *__restrict__ tc, int *__restrict__ t1, const int i)
-{
-    double x[D > 0 ? D : MAXD]; unsigned char fl;
-    classify_load<D>(P, nv, i, x, fl);
-    classify_elem<D, TOUCH>(P, hps, B, nv, out, anyminus, tc, t1, i, x, fl);
-}
 // Grid-stride over the elements with the next element's coordinates requested before the current one is classified.  Measured
 // (scripts/probe/k1_small_b.py, q = 5, 8 M elements): a grid capped at 4..16 workgroups per CU is 3-15 % SLOWER at B = 2..32 than
 // one workgroup per 256 elements, so the launch is not capped and the loop runs once; it stays for nv beyond one grid.  Unrolling
@@ -473,227 +464,14 @@ __global__ __launch_bounds__(PB) void k_classify_batch_t(PolyView P, const doubl
     }
 }
 
-// ---- K1 on the matrix pipe (round 2) -------------------------------------------------------------------------------------
-// The scalar kernel above is VALU-bound from B ~ 16 on: per (element, halfspace) 5 fp64 FMAs, 2 fp64 compares and ~4 integer
-// operations for the bit packing share the vector ALU (24 TFLOP/s useful, 30-36 % of the HBM peak at B = 16..32).  Here the dot
-// products go to v_mfma_f64_16x16x4 -- one tile = 16 elements x 16 halfspaces, K = the coordinates in steps of 4 (zero padded) --
-// and the compares come out of the vector ALU as WAVE MASKS (v_cmp writes an SGPR pair: the "ballot" is free), so no lane packs
-// bits.  (fp64 matrix peak = fp64 vector peak on gfx950: the gain is the vector ALU freed of the FMAs, not a higher peak.)
-//   A[i][k] = X[k][element i]   lane l holds A[l & 15][l >> 4]              (one f64 per lane and K step)
-//   B[k][j] = h_j[k]            lane l holds B[l >> 4][l & 15]
-//   D[i][j] = h_j . x_i         lane l holds rows (l >> 4) + 4 r, r = 0..3, of column l & 15
-// A wave owns 64 elements = 4 tiles and keeps their A operands in registers; per 16 halfspaces it runs 4 independent MFMA chains.
-// Mask (t, r) of tile t, result register r: bits 16 g .. 16 g + 15 are the 16 halfspace bits of element 16 t + 4 r + g.  Read as a
-// string of 16-bit fields in the order (t, r, g) the field number IS the element's lane: the 32 mask dwords are dropped into lanes
-// 0..31 of one register (v_writelane), lane L fetches dword L >> 1 (one ds_bpermute) and keeps half L & 1.
-// Same result bit for bit as the scalar fma chain: the K steps of one MFMA are accumulated in ascending k with one rounding per
-// step, chained MFMAs continue the chain, the padding adds fma(0, 0, s) = s (bslv_k1_mfma_selftest; and the class words against
-// the scalar kernel on random data and inside the +-1e-9 bands: tests/test_poly_gpu.py).
-typedef double d4_t __attribute__((ext_vector_type(4)));
-// The 8 wave masks of one tile (4 result registers x {> alpha + EPS, > alpha - EPS}) and their hand-off into lanes 8 t .. 8 t + 7
-// of mp / mn.  Written as two blocks of assembly so that the ORDER is fixed: v_writelane_b32 fetches its scalar source ahead of the
-// vector pipeline -- issued right behind the v_cmp_f64 that produces the mask it picked up the register's previous content now and
-// then (seen as lost PLUS bits against the scalar kernel).  Here every mask is at least 8 vector instructions old when it is read.
-template <int T0>
-__device__ __forceinline__ void tile_masks(const d4_t &acc, double hi, double lo, int &mp, int &mn)
-{
-    unsigned long long p0, p1, p2, p3, n0, n1, n2, n3;
-    asm volatile("v_cmp_gt_f64 %0, %8, %12\n\tv_cmp_gt_f64 %1, %9, %12\n\tv_cmp_gt_f64 %2, %10, %12\n\tv_cmp_gt_f64 %3, %11, %12\n\t"
-                 "v_cmp_gt_f64 %4, %8, %13\n\tv_cmp_gt_f64 %5, %9, %13\n\tv_cmp_gt_f64 %6, %10, %13\n\tv_cmp_gt_f64 %7, %11, %13"
-                 : "=&s"(p0), "=&s"(p1), "=&s"(p2), "=&s"(p3), "=&s"(n0), "=&s"(n1), "=&s"(n2), "=&s"(n3)
-                 : "v"(acc[0]), "v"(acc[1]), "v"(acc[2]), "v"(acc[3]), "v"(hi), "v"(lo));
-    asm volatile("v_writelane_b32 %0, %2, %18\n\tv_writelane_b32 %0, %3, %19\n\tv_writelane_b32 %0, %4, %20\n\tv_writelane_b32 %0, %5, %21\n\t"
-                 "v_writelane_b32 %0, %6, %22\n\tv_writelane_b32 %0, %7, %23\n\tv_writelane_b32 %0, %8, %24\n\tv_writelane_b32 %0, %9, %25\n\t"
-                 "v_writelane_b32 %1, %10, %18\n\tv_writelane_b32 %1, %11, %19\n\tv_writelane_b32 %1, %12, %20\n\tv_writelane_b32 %1, %13, %21\n\t"
-                 "v_writelane_b32 %1, %14, %22\n\tv_writelane_b32 %1, %15, %23\n\tv_writelane_b32 %1, %16, %24\n\tv_writelane_b32 %1, %17, %25"
-                 : "+v"(mp), "+v"(mn)
-                 : "s"((unsigned)p0), "s"((unsigned)(p0 >> 32)), "s"((unsigned)p1), "s"((unsigned)(p1 >> 32)),
-                   "s"((unsigned)p2), "s"((unsigned)(p2 >> 32)), "s"((unsigned)p3), "s"((unsigned)(p3 >> 32)),
-                   "s"((unsigned)n0), "s"((unsigned)(n0 >> 32)), "s"((unsigned)n1), "s"((unsigned)(n1 >> 32)),
-                   "s"((unsigned)n2), "s"((unsigned)(n2 >> 32)), "s"((unsigned)n3), "s"((unsigned)(n3 >> 32)),
-                   "n"(8 * T0), "n"(8 * T0 + 1), "n"(8 * T0 + 2), "n"(8 * T0 + 3), "n"(8 * T0 + 4), "n"(8 * T0 + 5), "n"(8 * T0 + 6), "n"(8 * T0 + 7));
-}
-template <int I, int N> struct StaticFor {
-    template <class F> static __device__ __forceinline__ void run(F &&f) { f(std::integral_constant<int, I>{}); StaticFor<I + 1, N>::run(f); }
-};
-template <int N> struct StaticFor<N, N> { template <class F> static __device__ __forceinline__ void run(F &&) {} };
-template <int D, bool TOUCH>
-__global__ __launch_bounds__(PB) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_classify_batch_mfma(PolyView P, const double *__restrict__ hps, int B, int nv,
-                                                            unsigned long long *__restrict__ out, unsigned *__restrict__ anyminus,
-                                                            int *__restrict__ tc, int *__restrict__ t1)
-{
-    constexpr int KS = (D + 3) / 4;                                   // K steps
-    constexpr int T = 4;                                              // tiles per wave
-    const int lane = threadIdx.x & 63, col = lane & 15, kq = lane >> 4;
-    const int base = (int)((blockIdx.x * PB + threadIdx.x) >> 6) * 64;
-    if (base >= nv) return;                                           // (wave-uniform)
-    double a[T][KS];
-#pragma unroll
-    for (int t = 0; t < T; t++)
-#pragma unroll
-        for (int ks = 0; ks < KS; ks++) {
-            const int k = 4 * ks + kq, e = base + 16 * t + col;
-            a[t][ks] = (e < nv && k < D) ? P.X[(size_t)k * P.cap + e] : 0.0;
-        }
-    const int e = base + lane;                                        // the element this lane writes
-    const bool mine = e < nv;
-    const unsigned char fl = mine ? P.flag[e] : 0;
-    const bool live = fl & F_USED;
-    // directions are measured against 0 (bslv_poly.c:126), i.e. with thresholds per ROW of a tile: a wave that holds one (rare)
-    // takes the scalar path for its 64 elements
-    if (__ballot(fl & F_IDEAL)) { classify_batch_body<D, TOUCH>(P, hps, B, nv, out, anyminus, tc, t1, e); return; }
-    const int nw = (B + 31) / 32, nh = (B + 15) / 16;
-    // operand B and the thresholds of the first 16 halfspaces (each half is fetched while the previous one is multiplied)
-    double bq[KS], hi, lo;
-    {
-        const bool hv = col < B;
-        const double *h = hps + (size_t)(hv ? col : 0) * (D + 3);
-#pragma unroll
-        for (int ks = 0; ks < KS; ks++) { const int k = 4 * ks + kq; bq[ks] = (hv && k < D) ? h[k] : 0.0; }
-        hi = hv ? h[D + 1] : INFINITY; lo = hv ? h[D + 2] : INFINITY; // alpha +- EPS (an absent halfspace: no bit)
-    }
-    int touch = 0, first = -1;
-    for (int w = 0; w < nw; w++) {
-        unsigned plus32 = 0, nm32 = 0;
-#pragma unroll
-        for (int half = 0; half < 2; half++) {
-            const int hx = 2 * w + half;
-            double bc[KS]; const double chi = hi, clo = lo;
-#pragma unroll
-            for (int ks = 0; ks < KS; ks++) bc[ks] = bq[ks];
-            if (hx + 1 < nh) {                                        // prefetch
-                const int hs = (hx + 1) * 16 + col;
-                const bool hv = hs < B;
-                const double *h = hps + (size_t)(hv ? hs : 0) * (D + 3);
-#pragma unroll
-                for (int ks = 0; ks < KS; ks++) { const int k = 4 * ks + kq; bq[ks] = (hv && k < D) ? h[k] : 0.0; }
-                hi = hv ? h[D + 1] : INFINITY; lo = hv ? h[D + 2] : INFINITY;
-            }
-            if (hx >= nh) break;                                      // (B <= 16 (mod 32): the second half is empty)
-            d4_t acc[T];
-#pragma unroll
-            for (int t = 0; t < T; t++) acc[t] = d4_t{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-            for (int ks = 0; ks < KS; ks++)
-#pragma unroll
-                for (int t = 0; t < T; t++) acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[t][ks], bc[ks], acc[t], 0, 0, 0);
-            int mp = 0, mn = 0;                                       // lanes 0..31: the mask dwords in the order (t, r, low | high)
-            // the compares below are assembly, which the compiler's hazard recogniser does not look into: all MFMAs first, then the
-            // wait states a vector read of a 16-pass MFMA result needs (19), once
-            __builtin_amdgcn_sched_barrier(0);
-            asm volatile("s_nop 15\n\ts_nop 3" ::: "memory");
-            StaticFor<0, T>::run([&](auto ic) { tile_masks<decltype(ic)::value>(acc[decltype(ic)::value], chi, clo, mp, mn); });
-            const unsigned fp = (unsigned)__builtin_amdgcn_ds_bpermute((lane >> 1) << 2, mp), fn = (unsigned)__builtin_amdgcn_ds_bpermute((lane >> 1) << 2, mn);
-            plus32 |= ((fp >> (16 * (lane & 1))) & 0xFFFFu) << (16 * half);
-            nm32 |= ((fn >> (16 * (lane & 1))) & 0xFFFFu) << (16 * half);
-        }
-        const int bend = min(32, B - w * 32);
-        const unsigned valid = bend == 32 ? 0xFFFFFFFFu : ((1u << bend) - 1u);
-        unsigned lowb = (plus32 | ~nm32) & valid, highb = nm32 & valid, minusbits = ~nm32 & valid;
-        if (!live) { lowb = 0; highb = 0; minusbits = 0; }
-        if (mine) out[(size_t)w * P.cap + e] = spread32(lowb) | (spread32(highb) << 1);
-        if (TOUCH) {
-            const unsigned nonplus = live ? (~plus32 & valid) : 0u;
-            if (nonplus) { if (touch == 0) first = w * 32 + (__ffs((int)nonplus) - 1); touch += __popc(nonplus); }
-        }
-        if (anyminus) {
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) minusbits |= __shfl_xor(minusbits, o, WAVE);
-            if (lane == 0 && (minusbits & ~__hip_atomic_load(&anyminus[w], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) atomicOr(&anyminus[w], minusbits);
-        }
-    }
-    if (TOUCH && mine) { tc[e] = touch; t1[e] = first; }
-}
-
-// self-test of the claim above: the dot products of random 16 x 16 tiles by chained MFMAs against the scalar fma chain, bit for bit
-template <int D>
-__global__ void k_k1_mfma_selftest(const double *__restrict__ X /* D x 16 per tile */, const double *__restrict__ H /* 16 x D per tile */, int ntiles, unsigned long long *mismatch)
-{
-    constexpr int KS = (D + 3) / 4;
-    const int lane = threadIdx.x & 63, col = lane & 15, kq = lane >> 4;
-    const int tile = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
-    if (tile >= ntiles) return;
-    const double *x = X + (size_t)tile * D * 16, *h = H + (size_t)tile * 16 * D;
-    d4_t acc = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int ks = 0; ks < KS; ks++) {
-        const int k = 4 * ks + kq;
-        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(k < D ? x[k * 16 + col] : 0.0, k < D ? h[col * D + k] : 0.0, acc, 0, 0, 0);
-    }
-    int bad = 0;
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-        const int i = kq + 4 * r;                       // element row of this result, column = halfspace col
-        double sref = 0.0;
-        for (int k = 0; k < D; k++) sref = fma(h[col * D + k], x[k * 16 + i], sref);
-        bad += __double_as_longlong(sref) != __double_as_longlong(acc[r]);
-    }
-    if (bad) atomicAdd(mismatch, (unsigned long long)bad);
-}
-
-// Which of the two runs: the scalar kernel.  Measured (profiles/r02_f64_pipes.json, scripts/probe/f64_pipes.hip): on gfx950 a wave's
-// v_fma_f64 / v_cmp_f64 make 6-9 % of their stand-alone progress while another wave of the same SIMD issues f64 MFMAs back to back --
-// the f64 MFMA occupies the SIMD's fp64 datapath instead of running beside it, so the dot products cost the same fp64 cycles either
-// way, K padded from 5 to 8 costs 60 % more of them, and the compares + mask hand-off come on top (21.7 against 23.2 TFLOP/s useful
-// at q = 5, B = 512).  BSLV_K1_MFMA=1 or bslv_poly_debug_set key 9 select the matrix kernel (kept: bit-identical, tested).
-static bool g_k1_mfma = getenv("BSLV_K1_MFMA") != nullptr;
+// K1 runs on the vector ALU.  A variant on the matrix pipe (v_mfma_f64_16x16x4, compares as wave masks) was built, measured slower
+// at every B and removed (profiles/r02_f64_pipes.json, scripts/probe/f64_pipes.hip): on gfx950 a wave's v_fma_f64 / v_cmp_f64 make
+// 6-9 % of their stand-alone progress while another wave of the same SIMD issues f64 MFMAs back to back -- the f64 MFMA occupies the
+// SIMD's fp64 datapath instead of running beside it, so the dot products cost the same fp64 cycles either way, K padded from 5 to 8
+// costs 60 % more of them, and the compares + mask hand-off come on top (21.7 against 23.2 TFLOP/s useful at q = 5, B = 512).
 static void launch_classify_batch(hipStream_t s, PolyView P, const double *hps, int B, int nv, unsigned long long *out, unsigned *anyminus,
                                   int *tc, int *t1)
 {
-    if (g_k1_mfma && B >= 16 && P.d >= 2 && P.d <= 10) {
-        dim3 g((unsigned)((nv + PB - 1) / PB)), b(PB);                    // 64 elements per wave
-        static const bool check = getenv("BSLV_K1_CHECK") != nullptr;    // DEBUG: the scalar kernel beside it, outputs compared on the host
-        const int nw = (B + 31) / 32;
-        unsigned long long *out2 = nullptr; unsigned *any2 = nullptr; int *tt2 = nullptr;
-        if (check) {
-            (void)malloc0(&out2, (size_t)nw * P.cap * 8); (void)malloc0(&any2, nw * 4); (void)malloc0(&tt2, (size_t)2 * (nv + 1) * 4);
-            if (anyminus) (void)hipMemcpyAsync(any2, anyminus, nw * 4, hipMemcpyDeviceToDevice, s);
-        }
-        switch (P.d) {
-#define CASE(D) case D: if (tc) hipLaunchKernelGGL((k_classify_batch_mfma<D, true>), g, b, 0, s, P, hps, B, nv, out, anyminus, tc, t1); \
-                       else hipLaunchKernelGGL((k_classify_batch_mfma<D, false>), g, b, 0, s, P, hps, B, nv, out, anyminus, tc, t1); break;
-            CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8) CASE(9) CASE(10)
-#undef CASE
-        }
-        if (check) {
-            g_k1_mfma = false;
-            launch_classify_batch(s, P, hps, B, nv, out2, anyminus ? any2 : nullptr, tc ? tt2 : nullptr, tc ? tt2 + nv : nullptr);
-            g_k1_mfma = true;
-            (void)hipStreamSynchronize(s);
-            std::vector<unsigned long long> wa((size_t)nw * P.cap), wb((size_t)nw * P.cap);
-            std::vector<unsigned> aa(nw), ab(nw); std::vector<int> ta(2 * (size_t)nv), tb(2 * (size_t)nv);
-            (void)hipMemcpy(wa.data(), out, wa.size() * 8, hipMemcpyDeviceToHost); (void)hipMemcpy(wb.data(), out2, wb.size() * 8, hipMemcpyDeviceToHost);
-            if (anyminus) { (void)hipMemcpy(aa.data(), anyminus, nw * 4, hipMemcpyDeviceToHost); (void)hipMemcpy(ab.data(), any2, nw * 4, hipMemcpyDeviceToHost); }
-            if (tc) { (void)hipMemcpy(ta.data(), tc, (size_t)nv * 4, hipMemcpyDeviceToHost); (void)hipMemcpy(ta.data() + nv, t1, (size_t)nv * 4, hipMemcpyDeviceToHost);
-                      (void)hipMemcpy(tb.data(), tt2, (size_t)2 * nv * 4, hipMemcpyDeviceToHost); }
-            long bw = 0, bt = 0, ba = 0; int fw = -1, fi = -1;
-            for (int w = 0; w < nw; w++) for (int i = 0; i < nv; i++) if (wa[(size_t)w * P.cap + i] != wb[(size_t)w * P.cap + i]) { if (!bw) { fw = w; fi = i; } bw++; }
-            if (tc) for (size_t i = 0; i < 2 * (size_t)nv; i++) bt += ta[i] != tb[i];
-            if (anyminus) for (int w = 0; w < nw; w++) ba += aa[w] != ab[w];
-            fprintf(stderr, "K1 check: d %d B %d nv %d cap %d touch %d: words differ %ld (first w %d i %d: %016llx vs %016llx), tc/t1 differ %ld, anyminus differ %ld\n",
-                    P.d, B, nv, P.cap, tc != nullptr, bw, fw, fi, fw >= 0 ? wa[(size_t)fw * P.cap + fi] : 0ull, fw >= 0 ? wb[(size_t)fw * P.cap + fi] : 0ull, bt, ba);
-            if (bw) {
-                std::vector<unsigned char> fl(nv); (void)hipMemcpy(fl.data(), P.flag, nv, hipMemcpyDeviceToHost);
-                std::vector<double> hh((size_t)B * (P.d + 3)); (void)hipMemcpy(hh.data(), hps, hh.size() * 8, hipMemcpyDeviceToHost);
-                fprintf(stderr, "  flags:");
-                for (int i = 0; i < nv && i < 64; i++) fprintf(stderr, " %d:%02x", i, fl[i]);
-                fprintf(stderr, "\n  differing elements:");
-                int shown = 0;
-                for (int i = 0; i < nv && shown < 12; i++) {
-                    bool df = false;
-                    for (int w = 0; w < nw; w++) df |= wa[(size_t)w * P.cap + i] != wb[(size_t)w * P.cap + i];
-                    if (!df) continue;
-                    shown++;
-                    double x[MAXD]; for (int k = 0; k < P.d; k++) (void)hipMemcpy(&x[k], P.X + (size_t)k * P.cap + i, 8, hipMemcpyDeviceToHost);
-                    double s0 = 0; for (int k = 0; k < P.d; k++) s0 = fma(hh[k], x[k], s0);
-                    fprintf(stderr, " [%d fl %02x w0 %016llx vs %016llx s(h0) %.3e alpha0 %.3e]", i, fl[i], wa[i], wb[i], s0, hh[P.d]);
-                }
-                fprintf(stderr, "\n");
-            }
-            (void)hipFree(out2); (void)hipFree(any2); (void)hipFree(tt2);
-        }
-        return;
-    }
     dim3 g(std::min((nv + PB - 1) / PB, K1_MAX_BLOCKS)), b(PB);
     switch (P.d) {
 #define CASE(D) case D: if (tc) hipLaunchKernelGGL((k_classify_batch_t<D, true>), g, b, 0, s, P, hps, B, nv, out, anyminus, tc, t1); \
@@ -2216,7 +1994,7 @@ __device__ __forceinline__ bool k2v2_member(const PolyView &P, int v, int co, in
 }
 __device__ __forceinline__ void k2v2_sizes(const RState *st, int &S, int &go, int &nzero, int &nv0, int &ncross);
 __device__ void k2v2_check_members(const K2V2 &V, int vs, const int *s_mem, int nm, const int *members, int nzero);
-// (a device function: the kernel of the single-cut pipeline, k2_fused_t<false>, and the prune launch of a round, k_r2_k2, call it)
+// (a device function: the kernels of the single-cut pipeline, k2_fused_t<false>, and of a round's prunes, k2_fused_t<true>, call it)
 template <bool V2>
 __device__ void k2_fused_body(PolyView P, int *members, int nzero, int nv0, int ncross, int *fcount, int *flocal,
                               int lds_words, int2 *E, int ebase, int *ne_dev, Tri *totals, Mail *mail, int seq, unsigned long long *dbg,
@@ -2865,11 +2643,8 @@ struct bslv_poly {
     RoundsBuf *rounds = nullptr;      // scratch of the multi-cut path
     Rounds2Buf *rounds2 = nullptr;    // scratch of the device-selected rounds inside a hot chunk (poly_rounds2_host.inc)
     bool rounds2_enabled = true;      // BSLV_NO_ROUNDS2=1 / bslv_poly_debug_set(h, 6, 0): hot chunks go through the single-cut pipeline
-    int r2_fuse = 0;                  // (default 0: measured fastest) 1: the classification of a round's new vertices rides in the launch of its prunes (extra workgroups); 2: and the last prune workgroup to finish writes the adjacent pairs (a ticket; measured slower); 0: three launches (BSLV_R2_FUSE / debug_set key 13)
-    int r2_fork = 0;                  // 1: the classification of a round's new vertices runs on a second stream BESIDE the round's prunes (they are independent until k_r2_k2emit: the prune reads no class words, the classification writes only the class words of the new vertices), joined by an event before k_r2_k2emit (BSLV_R2_FORK / debug_set key 17)
     bool r2_spec = true;              // rounds are queued one ahead of the host (BSLV_R2_SPEC=0 / debug_set key 12: the host reads every round's mailbox before it queues the next)
     long r2_spec_void = 0;            // rounds that were queued ahead and found the device halted (bslv_poly_rounds2_stats)
-    bool r2_share = true;             // (round 4) the cuts of a round may share elements that lie ON their planes: only a MINUS element makes two cuts conflict (poly_rounds2_kernels.inc, "Elements shared by the cuts of a round"); BSLV_R2_SHARE=0 / debug_set key 15: an element belongs to one cut of a round (rounds 2-3)
     bool r2_mis = true;               // rounds take a MAXIMAL independent set from a conflict matrix of the chunk (round 3); BSLV_R2_MIS=0 / debug_set key 11: the local minima of one random order (round 2)
     int chunk_cuts = 1024;             // cuts classified and applied together (bslv_poly_debug_set(h, 7, n); at most 4096)
     int r2_defer = 0;                 // rounds of a chunk stop when one holds fewer cuts than this; what is left is handed BACK to the caller (rc 2) -- see bslv_poly_set_defer
@@ -2878,7 +2653,6 @@ struct bslv_poly {
     bool r2_defer_mark = !(getenv("BSLV_DEFER_MARK") && atoi(getenv("BSLV_DEFER_MARK")) == 0);   // elements a handed-back cut will remove are marked processed
     bool snap = false;                // bslv_poly_set_snap / BSLV_POLY_SNAP: the projection sub-band of poly__cut; cuts are then applied one at a time
     unsigned long long *snapped_d = nullptr;
-    int r2_rule = 0;                  // 0: average over the rounds of the chunk so far, 1: over the last four rounds (BSLV_R2_RULE)
     int r2_min_cuts = 0;              // rounds go on while they hold at least this many cuts on average (debug_set key 8; 0: until the rounds hold one cut each; -1: always)
     long r2_rounds = 0, r2_cuts = 0, r2_fallback_prunes = 0, r2_declined = 0, r2_chunks = 0, shuffle_seq = 0, r2_late_left = 0, r2_torn_reads = 0;
     long r2_fb_reason[5] = {0, 0, 0, 0, 0}, r2_fb_nm[20] = {0};     // fallback prunes by cause and by log2 of the member count (BSLV_R2_REPORT)
@@ -2916,8 +2690,6 @@ struct bslv_poly {
     int *fm_cnt = nullptr, *fm_list = nullptr; size_t fmcap = 0, fmlistcap = 0; int fm_min = 4096; long n_fm = 0; bool member_lists = true;
     // multi-GPU: pair space of large facets dealt to the ranks (k2_multi).  Below ~3e4 elements the two all-gathers cost more than the pair tests
     int largest_facet = 0;            // members of the largest new facet pruned so far (any path)
-    std::vector<double> cut_prio;     // bslv_poly_set_cut_priorities: one number per cut of the NEXT bslv_poly_add_cuts (the rounds prefer small values); cleared by that call
-    int r2_order = getenv("BSLV_R2_ORDER") ? atoi(getenv("BSLV_R2_ORDER")) : 0;      // priority of a chunk's cuts in the rounds: 0 pseudo-random shuffle, 1 ascending / 2 descending cut priority (where the caller gave one)
     bool k2_noflags = getenv("BSLV_K2_NOFLAGS") != nullptr; long n_noflag_prunes = 0;     // large-facet prunes emit by testing the listed pair blocks again instead of keeping a flag per pair
     int shard_min = 32768; long n_sharded = 0; int2 *shard_e = nullptr; size_t shardcap = 0;
     int *nzlist = nullptr; size_t nzcap = 0;         // pair blocks with an adjacent pair (+ their count behind the list)      // facet-major member lists of a large new facet (k_fm_*)       // chunk totals of the two-level scan (k_scan_chunks)
@@ -3752,8 +3524,7 @@ int bslv_poly_create(bslv_poly **out, int dim, int v2h, const double *c)
     // k2_fused keeps the local incidence bit matrix in LDS: ask for most of the CU's 160 KB, settle for 48 KB
     h->k2_lds = 128 * 1024;
     if (hipFuncSetAttribute((const void *)k2_fused_t<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->k2_lds) != hipSuccess ||
-        hipFuncSetAttribute((const void *)k2_fused_t<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->k2_lds) != hipSuccess ||
-        hipFuncSetAttribute((const void *)k_r2_k2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->k2_lds) != hipSuccess) {
+        hipFuncSetAttribute((const void *)k2_fused_t<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->k2_lds) != hipSuccess) {
         (void)hipGetLastError();
         h->k2_lds = 48 * 1024;
     }
@@ -3762,13 +3533,9 @@ int bslv_poly_create(bslv_poly **out, int dim, int v2h, const double *c)
     if (getenv("BSLV_NO_HOT")) h->hot_enabled = false;
     if (getenv("BSLV_NO_ROUNDS2")) h->rounds2_enabled = false;
     if (const char *e = getenv("BSLV_R2_MIS")) h->r2_mis = atoi(e) != 0;
-    if (const char *e = getenv("BSLV_R2_SHARE")) h->r2_share = atoi(e) != 0;
     if (const char *e = getenv("BSLV_R2_SPEC")) h->r2_spec = atoi(e) != 0;
-    if (const char *e = getenv("BSLV_R2_FUSE")) h->r2_fuse = std::min(2, std::max(0, atoi(e)));
-    if (const char *e = getenv("BSLV_R2_FORK")) h->r2_fork = atoi(e) != 0;
     if (const char *e = getenv("BSLV_CHUNK_CUTS")) h->chunk_cuts = std::min(4096, std::max(32, atoi(e)));
     if (const char *e = getenv("BSLV_R2_MIN_CUTS")) h->r2_min_cuts = std::max(-1, atoi(e));
-    if (const char *e = getenv("BSLV_R2_RULE")) h->r2_rule = atoi(e) ? 1 : 0;
     if (const char *e = getenv("BSLV_POLY_SNAP")) h->snap = atoi(e) != 0;
     if (const char *e = getenv("BSLV_CROSS_UB")) h->cross_ub = std::max(0, atoi(e));
     if (const char *e = getenv("BSLV_K2_LDS")) h->k2_lds = (size_t)std::max(64, atoi(e));      // test hook: a small value forces the multi-kernel prune
@@ -3924,15 +3691,12 @@ int bslv_poly_add_cuts(bslv_poly *h, int B, const double *val, const int *ideal,
     for (int b = 0; b < B; b++) fids[b] = new_dual(h, val + (size_t)b * d, ideal ? ideal[b] : 0);
     h->tm_newdual += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tnd).count();
     if (h->snap) {                       // the reference's order exactly: a moved element meets the next cut where the last one left it
-        h->cut_prio.clear();
         for (int b = 0; b < B; b++) { int r, rc = do_cut(h, fids[b], &r, -1); if (rc) return rc; rc_out[b] = r; }
         return settle_k2(h);
     }
     if (h->batch_mode == 1 && B >= 2) {
         auto t0 = std::chrono::steady_clock::now();
-        if ((int)h->cut_prio.size() != B) h->cut_prio.clear();
         int rc = apply_cuts_rounds(h, fids, rc_out);
-        h->cut_prio.clear();
         h->tm_add_cuts += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         return rc;
     }
@@ -4286,13 +4050,9 @@ int bslv_poly_debug_set(bslv_poly *h, int key, long value)
     case 6: h->rounds2_enabled = value != 0; return 0;                  /* device-selected rounds of independent cuts inside a hot chunk */
     case 7: h->chunk_cuts = (int)std::min(4096L, std::max(32L, value)); return 0;    /* cuts classified and applied together */
     case 10: h->shard_min = (int)std::max(2L, value); return 0;           /* multi-GPU: facets from this size on have their pair space dealt to the ranks */
-    case 13: h->r2_fuse = (int)std::min(2L, std::max(0L, value)); return 0;                           /* one launch for a round's prunes + classification + pair emission (1) / three (0) */
-    case 17: h->r2_fork = value != 0; return 0;                           /* rounds: classification of the new vertices on a second stream beside the prunes (1) / one stream (0) */
     case 12: h->r2_spec = value != 0; return 0;                           /* rounds queued one ahead of the host (1) / mailbox read before every round (0) */
     case 16: h->k2_noflags = value != 0; return 0;                        /* multi-kernel prune of large facets without a flag byte per pair (forced; by itself from 4 GiB of flags on) */
-    case 15: h->r2_share = value != 0; return 0;                          /* rounds: cuts may share on-plane elements (1) / every element belongs to one cut of a round (0) */
     case 11: h->r2_mis = value != 0; return 0;                            /* rounds: maximal independent set from the conflict matrix (1) / local minima of one order (0) */
-    case 9: g_k1_mfma = value != 0; return 0;                            /* incidence kernel K1 on the matrix pipe from 16 halfspaces on (1) or the scalar kernel (0, default); process-wide */
     case 14: h->r2_defer = (int)std::max(0L, value); return 0;           /* see bslv_poly_set_defer */
     case 8: h->r2_min_cuts = (int)std::max(-1L, value); return 0;        /* rounds go on while they average at least this many cuts (0: until every round holds one cut, -1: always) */
     case 5: h->member_lists = value != 0; return 0;                     /* edges of large facets confirmed through member lists (1) or against all elements (0) */           /* facets from this size on confirm edges through the facet-major member lists (4096) */
@@ -4300,18 +4060,6 @@ int bslv_poly_debug_set(bslv_poly *h, int key, long value)
     }
 }
 long bslv_poly_sharded_prunes(const bslv_poly *h) { return h ? h->n_sharded : 0; }
-// priorities for the cuts of the NEXT bslv_poly_add_cuts call (prio[b] for cut b; any order-inducing number, e.g. the depth z of the cut):
-// with BSLV_R2_ORDER = 1 / 2 the rounds of independent cuts give the cuts of a chunk their priority in ascending / descending order of it
-int bslv_poly_set_cut_priorities(bslv_poly *h, int n, const double *prio)
-{
-    if (!h || n < 0 || (n && !prio)) return BSLV_E_ARG;
-    h->cut_prio.assign(prio, prio + n);
-    return 0;
-}
-// Capacity ahead of need: element, edge and incidence-pool arrays double when they fill up, and every doubling is a hipMalloc + copy +
-// hipFree with a stream synchronisation in the middle of a batch of cuts (~0.5 ms each, 4.5 % of S-mid's cut phase: DESIGN.md 4e item 10).
-// A caller that knows it is about to run thousands of steps reserves once.  Not while a chunk is open (the rounds hold views of the arrays).
-// Zeros leave that capacity alone; nothing ever shrinks.
 // The projection sub-band of poly__cut (bslv_poly.c:666-674), see k_snap.  Off by default: the rounds of independent cuts classify a chunk's
 // elements against all of its cuts before the first is applied, which a moved element would invalidate; with the band on, cuts are applied
 // one at a time in the order handed in, as the reference applies them.  *moved (may be NULL) receives the elements moved so far.
@@ -4331,18 +4079,6 @@ int bslv_poly_snapped(bslv_poly *h, long *moved)
     unsigned long long v = 0;
     if (h->snapped_d) { HIP_TRY(hipStreamSynchronize(h->stream)); HIP_TRY(hipMemcpy(&v, h->snapped_d, sizeof(v), hipMemcpyDeviceToHost)); }
     *moved = (long)v;
-    return 0;
-}
-int bslv_poly_reserve(bslv_poly *h, long elements, long edges, long pool_words)
-{
-    if (!h || elements < 0 || edges < 0 || pool_words < 0) return BSLV_E_ARG;
-    if (h->hot) { set_error("bslv_poly_reserve: a chunk of cuts is open"); return BSLV_E_ARG; }
-    if (elements > 0x7FFFFF00 / 2 || edges > 0x7FFFFF00 / 2 || (unsigned long)pool_words > 0xF0000000ul) { set_error("bslv_poly_reserve: beyond the 32-bit indices of the engine"); return BSLV_E_CAPACITY; }
-    int rc;
-    if (elements > h->P.cap && (rc = ensure_vcap(h, (int)elements))) return rc;
-    if (edges > h->ecap && (rc = ensure_ecap(h, (int)edges))) return rc;
-    if ((size_t)pool_words > h->poolcap && (rc = ensure_pool(h, (size_t)pool_words))) return rc;
-    HIP_TRY(hipStreamSynchronize(h->stream));
     return 0;
 }
 int bslv_poly_largest_facet(const bslv_poly *h) { return h ? h->largest_facet : 0; }      // members of the largest new facet that went through the multi-kernel prune
@@ -4426,34 +4162,6 @@ int bslv_poly_path_stats(const bslv_poly *h, long out[6])
     return 0;
 }
 long bslv_poly_conflict_pairs(const bslv_poly *h) { return h ? h->conf_pairs : 0; }
-// TEST: ntiles random 16 x 16 tiles of dot products of length dim, chained v_mfma_f64_16x16x4 against the scalar fma chain;
-// *mismatches = results that differ in any bit (0 expected: the MFMA accumulates its K steps in ascending order, one rounding each)
-int bslv_k1_mfma_selftest(int dim, int ntiles, unsigned long long seed, long *mismatches)
-{
-    if (dim < 2 || dim > 10 || ntiles < 1 || !mismatches) return BSLV_E_ARG;
-    std::vector<double> X((size_t)ntiles * dim * 16), H((size_t)ntiles * 16 * dim);
-    unsigned long long z = seed * 0x9E3779B97F4A7C15ull + 1;
-    auto rnd = [&]() { z += 0x9E3779B97F4A7C15ull; unsigned long long t = z; t = (t ^ (t >> 30)) * 0xBF58476D1CE4E5B9ull; t = (t ^ (t >> 27)) * 0x94D049BB133111EBull; t ^= t >> 31;
-                       return ((double)(t >> 11) * (1.0 / 9007199254740992.0) * 2.0 - 1.0) * (1.0 + (double)(t & 7)); };
-    for (double &v : X) v = rnd();
-    for (double &v : H) v = rnd();
-    double *Xd = nullptr, *Hd = nullptr; unsigned long long *md = nullptr;
-    HIP_TRY(malloc0(&Xd, X.size() * 8)); HIP_TRY(malloc0(&Hd, H.size() * 8)); HIP_TRY(malloc0(&md, 8));
-    HIP_TRY(hipMemcpy(Xd, X.data(), X.size() * 8, hipMemcpyHostToDevice)); HIP_TRY(hipMemcpy(Hd, H.data(), H.size() * 8, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemset(md, 0, 8));
-    const dim3 g((unsigned)(((size_t)ntiles * 64 + 255) / 256)), b(256);
-    switch (dim) {
-#define CASE(D) case D: hipLaunchKernelGGL(k_k1_mfma_selftest<D>, g, b, 0, 0, (const double *)Xd, (const double *)Hd, ntiles, md); break;
-        CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8) CASE(9) CASE(10)
-#undef CASE
-    }
-    HIP_TRY(hipGetLastError());
-    unsigned long long m = 0;
-    HIP_TRY(hipMemcpy(&m, md, 8, hipMemcpyDeviceToHost));
-    (void)hipFree(Xd); (void)hipFree(Hd); (void)hipFree(md);
-    *mismatches = (long)m;
-    return 0;
-}
 // device-selected rounds inside hot chunks: out[0] rounds, [1] cuts applied in them, [2] chunks, [3] prunes that went through the
 // multi-kernel path, [4] rounds taken back for want of capacity
 int bslv_poly_rounds2_stats(const bslv_poly *h, long out[5])

@@ -3,7 +3,6 @@
 // poly_rounds2_host.inc -- host side of the device-selected rounds inside a hot chunk (kernels: poly_rounds2_kernels.inc).
 // Included after poly_rounds_host.inc (RoundsBuf) and the single-cut pipeline (do_cut, k2_multi, hot_begin).
 
-constexpr int R2_FORK_EVENTS = 8;
 struct Rounds2Buf {
     RState *st_d = nullptr;
     RState *mail_h = nullptr, *mail_d = nullptr;          // mapped pinned copy of the state, written at the end of every round
@@ -19,11 +18,7 @@ struct Rounds2Buf {
     // conflict-matrix rounds (k_r2_select3): matrix over the cuts of the chunk, live MINUS elements per cut, selected cuts of the
     // round as a bit mask, per element the class words that hold a touch
     unsigned *M = nullptr, *selw = nullptr, *wm = nullptr; int *mcnt = nullptr; int wmcap = 0;
-    int *ticket = nullptr;
     int *fc2 = nullptr, *fl2 = nullptr, *fc_ticket = nullptr; int fc_slices = 0, fc_stride = 0;      // K2V2: counters of prunes with long member lists
-    // r2_fork: the stream the classification of a round's new vertices runs on beside the prunes, and a ring of (fork, join) events --
-    // at most two rounds are in flight, the ring holds eight
-    hipStream_t s2 = nullptr; hipEvent_t ev_fork[R2_FORK_EVENTS] = {}, ev_join[R2_FORK_EVENTS] = {}; unsigned fork_n = 0;
 };
 constexpr int R2_ADJW = (K2_MAXNM * (K2_MAXNM - 1) / 2 + 31) / 32;
 constexpr int R2_MAILS = 4;
@@ -32,27 +27,15 @@ static void rounds2_free(Rounds2Buf &V)
 {
     auto fr = [](void *p) { if (p) (void)hipFree(p); };
     fr(V.st_d); fr(V.alive); fr(V.alive_prev); fr(V.anym); fr(V.bad); fr(V.selmap); fr(V.sel); fr(V.order); fr(V.rcflag); fr(V.own);
-    fr(V.cnt_g); fr(V.nm_g); fr(V.mem_g); fr(V.adj_g); fr(V.gout); fr(V.hw); fr(V.M); fr(V.selw); fr(V.wm); fr(V.mcnt); fr(V.ticket); fr(V.fc2); fr(V.fl2); fr(V.fc_ticket);
+    fr(V.cnt_g); fr(V.nm_g); fr(V.mem_g); fr(V.adj_g); fr(V.gout); fr(V.hw); fr(V.M); fr(V.selw); fr(V.wm); fr(V.mcnt); fr(V.fc2); fr(V.fl2); fr(V.fc_ticket);
     if (V.mail_h) (void)hipHostFree(V.mail_h);
     if (V.gout_h) (void)hipHostFree(V.gout_h);
-    if (V.s2) {
-        (void)hipStreamSynchronize(V.s2);
-        for (int k = 0; k < R2_FORK_EVENTS; k++) { if (V.ev_fork[k]) (void)hipEventDestroy(V.ev_fork[k]); if (V.ev_join[k]) (void)hipEventDestroy(V.ev_join[k]); }
-        (void)hipStreamDestroy(V.s2);
-    }
     V = Rounds2Buf();
 }
 static int rounds2_ensure(bslv_poly *h, Rounds2Buf &V, int Bc)
 {
     hipStream_t s = h->stream;
     int rc;
-    if (h->r2_fork && !V.s2) {
-        HIP_TRY(hipStreamCreate(&V.s2));
-        for (int k = 0; k < R2_FORK_EVENTS; k++) {
-            HIP_TRY(hipEventCreateWithFlags(&V.ev_fork[k], hipEventDisableTiming));
-            HIP_TRY(hipEventCreateWithFlags(&V.ev_join[k], hipEventDisableTiming));
-        }
-    }
     if (!V.st_d) {
         HIP_TRY(malloc0(&V.st_d, sizeof(RState)));
         HIP_TRY(hipHostMalloc(&V.mail_h, R2_MAILS * sizeof(RState), hipHostMallocMapped | hipHostMallocCoherent));       // (a ring: rounds are queued ahead of the host)
@@ -63,8 +46,6 @@ static int rounds2_ensure(bslv_poly *h, Rounds2Buf &V, int Bc)
         HIP_TRY(malloc0(&V.M, (size_t)R2_MAXC * (R2_MAXC / 32) * sizeof(unsigned)));
         HIP_TRY(malloc0(&V.selw, 64 * sizeof(unsigned)));
         HIP_TRY(malloc0(&V.mcnt, (size_t)R2_MAXC * sizeof(int)));
-        HIP_TRY(malloc0(&V.ticket, 4 * sizeof(int)));
-        HIP_TRY(hipMemset(V.ticket, 0, 4 * sizeof(int)));
         if (hipFuncSetAttribute((const void *)k_r2_select3, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((R2_MAXC / 32) * R2_MLD * sizeof(unsigned))) != hipSuccess ||
             hipFuncSetAttribute((const void *)k_r2_minit, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(((size_t)R2_MAXC * (R2_MAXC / 32 + 1) + R2_MAXC + 64) * sizeof(unsigned))) != hipSuccess) {
             (void)hipGetLastError();
@@ -240,7 +221,6 @@ static int run_rounds2(bslv_poly *h, RoundsBuf &R, const std::vector<int> &todo,
     const bool dbg = getenv("BSLV_R2_DEBUG") != nullptr;
     int napplied = 0, nredundant = 0;
     long rounds = 0;
-    int recent[4] = {0, 0, 0, 0};      // cuts of the last four rounds
     int last_ncross = 0, max_S = 0;
     bool stop = false;                 // the element arrays would have to grow
     std::vector<int> order_h;
@@ -332,8 +312,7 @@ static int run_rounds2(bslv_poly *h, RoundsBuf &R, const std::vector<int> &todo,
                     }
                 }
                 hipLaunchKernelGGL(k_r2_minit, dim3(nwg), dim3(1024), ((size_t)Bc * (nw + 1) + Bc + nw) * sizeof(unsigned), s, h->P, (const unsigned long long *)V.hw, (const unsigned *)V.wm, nw, Bc,
-                                   (const RState *)V.st_d, Eold, (const unsigned *)V.alive, V.M, V.mcnt, (const int *)R.tc, V.st_d, std::min(ne, h->ecap), vm_count(h->P, std::min(nv, h->P.cap)),
-                                   h->r2_share ? 1 : 0, probe);
+                                   (const RState *)V.st_d, Eold, (const unsigned *)V.alive, V.M, V.mcnt, (const int *)R.tc, V.st_d, std::min(ne, h->ecap), vm_count(h->P, std::min(nv, h->P.cap)), probe);
                 if (probe) {
                     std::vector<unsigned long long> pr(256 * 16);
                     (void)hipStreamSynchronize(s);
@@ -355,7 +334,7 @@ static int run_rounds2(bslv_poly *h, RoundsBuf &R, const std::vector<int> &todo,
                 }
             }
             hipLaunchKernelGGL(k_r2_select3, dim3(1), dim3(1024), (size_t)nw * R2_MLD * sizeof(unsigned), s, Bc, nw, V.alive, V.alive_prev, V.M, V.mcnt,
-                               V.selmap, V.sel, V.order, V.rcflag, V.st_d, V.selw, depth, h->r2_share ? 1 : 0);
+                               V.selmap, V.sel, V.order, V.rcflag, V.st_d, V.selw, depth);
             hipLaunchKernelGGL(k_r2_assign3, dim3(nbv), dim3(PB), 0, s, h->P, (const unsigned long long *)V.hw, (const unsigned *)V.wm, nw, (const RState *)V.st_d, (const unsigned *)V.selw,
                                (const int *)V.selmap, R.cutof, counters, h->zlist + ZMAX * cslot);
         } else {
@@ -375,35 +354,15 @@ static int run_rounds2(bslv_poly *h, RoundsBuf &R, const std::vector<int> &todo,
         const int S_ub = std::max(1, std::min(Bc - napplied - nredundant, V.scap));
         const K2V2 KV{V.st_d, R.cutof, V.mem_g, V.adj_g, V.cnt_g, V.nm_g, R2_ADJW, &V.st_d->pair_tests, V.fc2, V.fl2, V.fc_ticket, V.fc2 ? V.fc_slices : 0, V.fc_stride};
         const int seq = ++V.seq;
-        if (h->r2_fuse) {
-            // ONE launch: the prunes, the classification of the new vertices (extra workgroups), and -- by the last prune workgroup
-            // to finish -- the ordered emission of the adjacent pairs, the commit of the round and the mailbox
-            const int vpb = K2T / nwp, want = std::max(2048, 2 * last_ncross), ncb = std::max(1, std::min(96, (want + vpb - 1) / vpb));
-            const R2Tail T{(const double *)h->hps_d, Bc, nw, nwp, (const unsigned *)V.alive, V.hw, V.wm, S_ub, h->r2_fuse >= 2 ? V.ticket : (int *)nullptr, Enew, h->EP[1 - cur], h->ecap, V.st_d,
-                           V.mail_d + (seq % R2_MAILS), seq, mis ? 1 : 0};
-            hipLaunchKernelGGL(k_r2_k2, dim3(S_ub + ncb), dim3(K2T), h->k2_lds, s, h->P, h->members, h->fcount, h->flocal, (int)(h->k2_lds / 8), Enew, h->totals + 2, h->k2mail_d, h->abort_d, KV, T);
-            if (h->r2_fuse < 2)
-                hipLaunchKernelGGL(k_r2_k2emit, dim3(S_ub), dim3(K2T), 0, s, V.st_d, (const int *)V.cnt_g, (const int *)V.nm_g, (const unsigned *)V.adj_g, (const int *)V.mem_g,
-                                   R2_ADJW, Enew, h->EP[1 - cur], h->ecap, V.mail_d + (seq % R2_MAILS), seq, (const unsigned long long *)V.hw, (const unsigned *)V.wm, nw, (const unsigned *)V.alive);
-        } else {
-            // the new vertices of the round against the cuts that are still alive: one launch whose grid strides over whatever the round made
-            const int want = std::max(2048, 2 * last_ncross);
-            // r2_fork: the classification on a second stream beside the prunes.  It reads what k_r2_emit wrote (coordinates and flags of
-            // the new vertices, the sizes in the state) and writes the class words of the new vertices, which nothing reads before the
-            // next round's k_r2_minit; the prune reads incidence lists and owners and writes its bitmaps.  Neither raises `halt`.
-            const bool fork = h->r2_fork && V.s2;
-            const unsigned fk = fork ? V.fork_n++ % R2_FORK_EVENTS : 0u;
-            if (fork) { HIP_TRY(hipEventRecord(V.ev_fork[fk], s)); HIP_TRY(hipStreamWaitEvent(V.s2, V.ev_fork[fk], 0)); }
-            launch_r2_classify3(d, dim3(std::max(1, std::min(4096, (want + PB / nwp - 1) / (PB / nwp)))), fork ? V.s2 : s, h->P, (const double *)h->hps_d, Bc, nw, nwp, (const RState *)V.st_d,
-                                (const unsigned *)V.alive, V.hw, V.wm, (int *)nullptr, mis ? 1 : 0);
-            if (fork) HIP_TRY(hipEventRecord(V.ev_join[fk], V.s2));
-            hipLaunchKernelGGL(k2_fused_t<true>, dim3(S_ub), dim3(K2T), h->k2_lds, s, h->P, h->members, 0, 0, 0, h->fcount, h->flocal, (int)(h->k2_lds / 8), Enew, 0,
-                               (int *)nullptr, h->totals + 2, h->k2mail_d, 0, h->k2dbg, (const CutDev *)nullptr, h->abort_d, (int *)nullptr, Hp{}, (int *)nullptr,
-                               (int *)nullptr, KV);
-            if (fork) HIP_TRY(hipStreamWaitEvent(s, V.ev_join[fk], 0));
-            hipLaunchKernelGGL(k_r2_k2emit, dim3(S_ub), dim3(K2T), 0, s, V.st_d, (const int *)V.cnt_g, (const int *)V.nm_g, (const unsigned *)V.adj_g, (const int *)V.mem_g,
-                               R2_ADJW, Enew, h->EP[1 - cur], h->ecap, V.mail_d + (seq % R2_MAILS), seq, (const unsigned long long *)V.hw, (const unsigned *)V.wm, nw, (const unsigned *)V.alive);
-        }
+        // the new vertices of the round against the cuts that are still alive: one launch whose grid strides over whatever the round made
+        const int want = std::max(2048, 2 * last_ncross);
+        launch_r2_classify3(d, dim3(std::max(1, std::min(4096, (want + PB / nwp - 1) / (PB / nwp)))), s, h->P, (const double *)h->hps_d, Bc, nw, nwp, (const RState *)V.st_d,
+                            (const unsigned *)V.alive, V.hw, V.wm, (int *)nullptr, mis ? 1 : 0);
+        hipLaunchKernelGGL(k2_fused_t<true>, dim3(S_ub), dim3(K2T), h->k2_lds, s, h->P, h->members, 0, 0, 0, h->fcount, h->flocal, (int)(h->k2_lds / 8), Enew, 0,
+                           (int *)nullptr, h->totals + 2, h->k2mail_d, 0, h->k2dbg, (const CutDev *)nullptr, h->abort_d, (int *)nullptr, Hp{}, (int *)nullptr,
+                           (int *)nullptr, KV);
+        hipLaunchKernelGGL(k_r2_k2emit, dim3(S_ub), dim3(K2T), 0, s, V.st_d, (const int *)V.cnt_g, (const int *)V.nm_g, (const unsigned *)V.adj_g, (const int *)V.mem_g,
+                           R2_ADJW, Enew, h->EP[1 - cur], h->ecap, V.mail_d + (seq % R2_MAILS), seq, (const unsigned long long *)V.hw, (const unsigned *)V.wm, nw, (const unsigned *)V.alive);
         HIP_TRY(hipGetLastError());
         cur = 1 - cur;
         *seq_out = seq; *sub_out = S_ub;
@@ -588,7 +547,7 @@ static int run_rounds2(bslv_poly *h, RoundsBuf &R, const std::vector<int> &todo,
                 h->r2_fallback_prunes++;
                 const int ne_before = h->ne;
                 if (nm >= 2 && (rc = k2_multi(h, nm, len_ub, (int)(4 * h->cutseq + 3)))) return rc;
-                if (h->r2_share && mis && h->ne > ne_before) {
+                if (mis && h->ne > ne_before) {
                     // pairs of shared on-plane members that a later cut of the round has the final word on (k_r2_dedupe_flags)
                     const int nadd = h->ne - ne_before, nbd = (nadd + PB - 1) / PB, myrank = m.rank_base + sidx;
                     if ((rc = ensure_bsum(h, nbd + 1))) return rc;
@@ -612,15 +571,13 @@ static int run_rounds2(bslv_poly *h, RoundsBuf &R, const std::vector<int> &todo,
         if (h->P.cap - h->nv < 4096) { stop = true; stop_enq = true; continue; }      // (next to no room for another round's vertices; a round already queued is still dealt with)
         // a round costs about two single cuts.  When the cuts of a chunk form one clique (every round holds a single cut) what
         // is left goes through the single-cut pipeline; BSLV_R2_MIN_CUTS / debug key 8 set a stricter rule for experiments
-        recent[rounds & 3] = m.S;
         // thin rounds at the end of a chunk (its cliques: one cut each per round) are not worth their passes: the cuts still alive go
         // back to the caller, who hands them in again with the next batch, where they share rounds with cuts of other regions
         // (thin relative to what the chunk's rounds held at their best: a chunk of one clique has nothing but thin rounds)
         max_S = std::max(max_S, m.S);
         if (h->r2_defer > 0 && m.S < h->r2_defer && m.S * 5 < max_S && m.nalive > 0 && rounds >= 4) { stop = true; stop_enq = true; h->r2_deferred = true; }
         if (h->r2_min_cuts >= 0 && m.nalive >= 8 && rounds >= 16 && napplied * 4 < rounds * 5) { stop = true; stop_enq = true; }
-        if (h->r2_min_cuts > 0 && m.nalive >= 8 && rounds >= 2 &&
-            (h->r2_rule == 0 ? napplied < h->r2_min_cuts * rounds : (rounds >= 4 && recent[0] + recent[1] + recent[2] + recent[3] < 4 * h->r2_min_cuts))) { stop = true; stop_enq = true; }
+        if (h->r2_min_cuts > 0 && m.nalive >= 8 && rounds >= 2 && napplied < h->r2_min_cuts * rounds) { stop = true; stop_enq = true; }
     }
     if (h->r2_deferred && h->r2_defer_mark) {
         // the elements the cuts handed back will remove take no LP in the meantime (k_r2_mark_doomed)

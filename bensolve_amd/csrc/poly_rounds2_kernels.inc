@@ -18,7 +18,7 @@
 //   k_r2_emit     the single-cut emit pass with the halfspace and the facet rank of the OWNER of each crossing edge / on-plane
 //                 element; verdict on the capacities
 //   k_r2_classify the new vertices against every cut of the chunk (batched incidence kernel)
-//   k_r2_k2       one workgroup per selected cut: the adjacency prune of its new facet (k2_fused<true>), result as a bitmap
+//   k2_fused_t<true> one workgroup per selected cut: the adjacency prune of its new facet, result as a bitmap
 //   k_r2_k2emit   ordered emission of the adjacent pairs of all selected cuts, commit of the sizes, mailbox to the host
 //
 // The classes of an element against the cuts of the chunk never change (coordinates are immutable), so the class words of
@@ -33,7 +33,7 @@ struct RState {
     // verdict and sizes of the round (k_r2_emit, workgroup 0)
     int go, declined, nminus, nzero, zero_ub, nsurv, ncross, newlen;
     int nv_next, ne_next; unsigned pool_next, pool_e, pool_z;
-    // adjacency prunes of the round (k_r2_k2 / k_r2_k2emit)
+    // adjacency prunes of the round (k2_fused_t<true> / k_r2_k2emit)
     int epairs, eover, k2abort;
     long long pair_tests;
     // Rounds are queued ahead of the host (round r+1 behind round r before r's mailbox has been read).  Whatever the host would have
@@ -610,18 +610,12 @@ __device__ __forceinline__ void r2_cross4(const unsigned (&a)[4], const int (&aw
         }
     }
 }
-// The conflict relation.  share == 0 (rounds 2-3): two cuts conflict when an element is non-PLUS for both, or an edge joins a
-// non-PLUS element of one to a non-PLUS element of the other (r2_conflicts4 and its _lds / _wave forms below).  share != 0 (round 4):
-// only when a MINUS element is involved -- an element that is MINUS for one and non-PLUS for the other, or an edge from a MINUS element
-// of one to a non-PLUS element of the other (r2_give).  Elements that are merely ON the planes of several cuts (the extreme directions
-// of an upper image for most cuts of a covering problem) and edges between such elements no longer separate cuts: see "Elements shared
-// by the cuts of a round" below.
-__device__ __forceinline__ void r2_conflicts4(const R2T4 &A, const R2T4 &B, bool same, int ld, unsigned *Ml)
-{
-    r2_cross4(A.t, A.w, B.t, B.w, ld, Ml);
-    if (!same) r2_cross4(B.t, B.w, A.t, A.w, ld, Ml);
-}
-// share != 0: the rows of the alive MINUS cuts of element x get the alive non-PLUS cuts of element y (y = x: the element itself, else
+// The conflict relation: two cuts conflict only when a MINUS element is involved -- an element that is MINUS for one and non-PLUS
+// for the other, or an edge from a MINUS element of one to a non-PLUS element of the other (r2_give).  Elements that are merely ON
+// the planes of several cuts (the extreme directions of an upper image for most cuts of a covering problem) and edges between such
+// elements do not separate cuts: see "Elements shared by the cuts of a round" below.  (The strict relation of rounds 2-3 -- any
+// non-PLUS element in common -- was slower on whole runs with the same final sets and has been removed.)
+// The rows of the alive MINUS cuts of element x get the alive non-PLUS cuts of element y (y = x: the element itself, else
 // its neighbour across an edge).  ONE direction only -- the rows of the cuts that own a MINUS element; k_r2_select3 makes the
 // relation symmetric in LDS.  (Writing both directions here cost what the strict relation costs: every edge of an extreme direction
 // that is ON the planes of a hundred cuts touched a hundred rows; this way such an edge costs one row per MINUS cut of its other end.)
@@ -648,42 +642,10 @@ __device__ __forceinline__ void r2_give(const unsigned long long *__restrict__ h
         }
     }
 }
-// the same for items with touches in more than 4 class words, by one thread: rows of the (minus ? MINUS : non-PLUS) cuts of element i get
-// the (minus2 ? MINUS : non-PLUS) cuts of element j
-__device__ __forceinline__ void r2_cross_lds(const unsigned long long *__restrict__ hw, int nw, int i, unsigned wi, bool minus, int j, unsigned wj, bool minus2, const unsigned *alive, unsigned *Ml, int ld)
-{
-    while (wi) {
-        const int wa = __ffs((int)wi) - 1;
-        wi &= wi - 1;
-        const unsigned long long ra = hw[(size_t)i * nw + wa];
-        unsigned ta = (minus ? r2_minus32(ra) : r2_touch32(ra)) & alive[wa];
-        if (!ta) continue;
-        unsigned m = wj;
-        while (m) {
-            const int wb = __ffs((int)m) - 1;
-            m &= m - 1;
-            const unsigned long long rb = hw[(size_t)j * nw + wb];
-            const unsigned tb = (minus2 ? r2_minus32(rb) : r2_touch32(rb)) & alive[wb];
-            if (!tb) continue;
-            unsigned t = ta;
-            while (t) {
-                const int a = wa * 32 + __ffs((int)t) - 1;
-                t &= t - 1;
-                unsigned *w = &Ml[a * ld + wb];
-                if (tb & ~*w) atomicOr(w, tb);
-            }
-        }
-    }
-}
-__device__ __forceinline__ void r2_conflicts_lds(const unsigned long long *__restrict__ hw, int nw, int x, unsigned wx, int y, unsigned wy, const unsigned *alive, unsigned *Ml, int ld)
-{
-    r2_cross_lds(hw, nw, x, wx, false, y, wy, false, alive, Ml, ld);
-    if (x != y) r2_cross_lds(hw, nw, y, wy, false, x, wx, false, alive, Ml, ld);
-}
 constexpr int R2_QCAP = 3072;                          // items of one workgroup that are left to whole waves
 __global__ __launch_bounds__(1024) void k_r2_minit(PolyView P, const unsigned long long *__restrict__ hw, const unsigned *__restrict__ wm, int nw, int Bc, const RState *st,
                                                    const int2 *__restrict__ E, const unsigned *__restrict__ alive_g, unsigned *M, int *mcnt, const int *__restrict__ tc, RState *st_w,
-                                                   int ne_ub, int nel_ub, int share, unsigned long long *probe)
+                                                   int ne_ub, int nel_ub, unsigned long long *probe)
 {
     extern __shared__ unsigned r2_lds[];
     __shared__ int q_item[R2_QCAP];
@@ -717,21 +679,15 @@ __global__ __launch_bounds__(1024) void k_r2_minit(PolyView P, const unsigned lo
             if (!(hu && hv2)) continue;
             const unsigned wu = wm[ed.x], wv = wm[ed.y];
             if (!wu || !wv) continue;
-            if (share && __popc(wu) <= 4 && __popc(wv) <= 4) {          // rows of the MINUS cuts of either end <- the non-PLUS cuts of the other end
+            if (__popc(wu) <= 4 && __popc(wv) <= 4) {          // rows of the MINUS cuts of either end <- the non-PLUS cuts of the other end
                 const R2T4 A = r2_touch4(hw, nw, ed.x, wu, alive), B2 = r2_touch4(hw, nw, ed.y, wv, alive);
                 if (A.m[0] | A.m[1] | A.m[2] | A.m[3]) r2_cross4(A.m, A.w, B2.t, B2.w, ld, Ml);
                 if (B2.m[0] | B2.m[1] | B2.m[2] | B2.m[3]) r2_cross4(B2.m, B2.w, A.t, A.w, ld, Ml);
                 continue;
             }
-            if (__popc(wu) > 4 || __popc(wv) > 4) {
-                const int k = atomicAdd(&q_n, 1);
-                if (k < R2_QCAP) { q_item[k] = it; continue; }
-                if (share) { r2_give(hw, nw, ed.x, wu, ed.y, wv, alive, Ml, ld); r2_give(hw, nw, ed.y, wv, ed.x, wu, alive, Ml, ld); }
-                else r2_conflicts_lds(hw, nw, ed.x, wu, ed.y, wv, alive, Ml, ld);
-                continue;
-            }
-            const R2T4 A = r2_touch4(hw, nw, ed.x, wu, alive), B2 = r2_touch4(hw, nw, ed.y, wv, alive);
-            r2_conflicts4(A, B2, false, ld, Ml);
+            const int k = atomicAdd(&q_n, 1);
+            if (k < R2_QCAP) { q_item[k] = it; continue; }
+            r2_give(hw, nw, ed.x, wu, ed.y, wv, alive, Ml, ld); r2_give(hw, nw, ed.y, wv, ed.x, wu, alive, Ml, ld);
         } else {
             const int i = vm_id(P, it - ne);
             const unsigned wi = wm[i];
@@ -744,17 +700,11 @@ __global__ __launch_bounds__(1024) void k_r2_minit(PolyView P, const unsigned lo
                 anym |= mi;
                 while (mi) { const int b = __ffs((int)mi) - 1; mi &= mi - 1; atomicAdd(&cnt[w * 32 + b], 1u); }
             }
-            if (share && !anym) continue;
-            if (share && __popc(wi) <= 4) { const R2T4 A = r2_touch4(hw, nw, i, wi, alive); r2_cross4(A.m, A.w, A.t, A.w, ld, Ml); continue; }
-            if (__popc(wi) > 4) {
-                const int k = atomicAdd(&q_n, 1);
-                if (k < R2_QCAP) { q_item[k] = -1 - i; continue; }
-                if (share) r2_give(hw, nw, i, wi, i, wi, alive, Ml, ld);
-                else r2_conflicts_lds(hw, nw, i, wi, i, wi, alive, Ml, ld);
-                continue;
-            }
-            const R2T4 A = r2_touch4(hw, nw, i, wi, alive);
-            r2_conflicts4(A, A, true, ld, Ml);
+            if (!anym) continue;
+            if (__popc(wi) <= 4) { const R2T4 A = r2_touch4(hw, nw, i, wi, alive); r2_cross4(A.m, A.w, A.t, A.w, ld, Ml); continue; }
+            const int k = atomicAdd(&q_n, 1);
+            if (k < R2_QCAP) { q_item[k] = -1 - i; continue; }
+            r2_give(hw, nw, i, wi, i, wi, alive, Ml, ld);
         }
     }
     __syncthreads();
@@ -838,13 +788,9 @@ __global__ __launch_bounds__(1024) void k_r2_minit(PolyView P, const unsigned lo
                 if (k + 1 < cntb) fetch(k + 1, nrx, nry);
                 const unsigned long long tg0 = probe ? wall_clock64() : 0ull;
                 const unsigned tx = r2_touch32(rx) & al, ty = r2_touch32(ry) & al;
-                if (share) {          // one direction: the rows of the MINUS cuts (k_r2_select3 mirrors them)
-                    give(r2_minus32(rx) & al, ty);
-                    if (!same) give(r2_minus32(ry) & al, tx);
-                } else {
-                    give(tx, ty);
-                    if (!same) give(ty, tx);
-                }
+                // one direction: the rows of the MINUS cuts (k_r2_select3 mirrors them)
+                give(r2_minus32(rx) & al, ty);
+                if (!same) give(r2_minus32(ry) & al, tx);
                 if (probe) {
                     __builtin_amdgcn_s_waitcnt(0xc07f);      // lgkmcnt(0): the LDS operations are through
                     const unsigned long long tg1 = wall_clock64();
@@ -880,7 +826,7 @@ __global__ __launch_bounds__(1024) void k_r2_minit(PolyView P, const unsigned lo
 // R2_MLD: consecutive cuts in consecutive banks).  Priority = index (the host shuffles the chunk).
 constexpr int R2_MAXC = 1024, R2_MLD = R2_MAXC + 1;
 __global__ __launch_bounds__(1024) void k_r2_select3(int Bc, int nw, unsigned *alive, unsigned *alive_prev, unsigned *M, int *mcnt,
-                                                     int *selmap, int *sel, int *order, int *rcflag, RState *st, unsigned *selw_g, int spec, int share)
+                                                     int *selmap, int *sel, int *order, int *rcflag, RState *st, unsigned *selw_g, int spec)
 {
     extern __shared__ unsigned r2m[];
     __shared__ unsigned s_alive[32], s_cand[32], s_new[32];
@@ -919,18 +865,16 @@ __global__ __launch_bounds__(1024) void k_r2_select3(int Bc, int nw, unsigned *a
         if (lane == 0) { s_cand[2 * wv] = (unsigned)bc; s_cand[2 * wv + 1] = (unsigned)(bc >> 32); }
     }
     __syncthreads();
-    if (share) {
-        // k_r2_minit (share) wrote the relation one way round -- into the rows of the cuts that own a MINUS element: make it symmetric
-        if (a) for (int w = 0; w < nw; w++) {
-            unsigned bits = r2m[w * R2_MLD + k];
-            while (bits) {
-                const int j = w * 32 + __ffs((int)bits) - 1;
-                bits &= bits - 1;
-                atomicOr(&r2m[(k >> 5) * R2_MLD + j], 1u << (k & 31));
-            }
+    // k_r2_minit wrote the relation one way round -- into the rows of the cuts that own a MINUS element: make it symmetric
+    if (a) for (int w = 0; w < nw; w++) {
+        unsigned bits = r2m[w * R2_MLD + k];
+        while (bits) {
+            const int j = w * 32 + __ffs((int)bits) - 1;
+            bits &= bits - 1;
+            atomicOr(&r2m[(k >> 5) * R2_MLD + j], 1u << (k & 31));
         }
-        __syncthreads();
     }
+    __syncthreads();
     bool selected = false;
     const int wk = k >> 5;
     const unsigned below = (1u << (k & 31)) - 1u;
@@ -984,7 +928,7 @@ __global__ __launch_bounds__(1024) void k_r2_select3(int Bc, int nw, unsigned *a
     }
 }
 // ---- Elements shared by the cuts of a round (round 4) -------------------------------------------------------------------------
-// With the relaxed conflict relation (k_r2_minit, share != 0) the selected cuts of a round may have elements in common that are ON
+// With the relaxed conflict relation (k_r2_minit) the selected cuts of a round may have elements in common that are ON
 // the plane of each of them (class ZERO), and edges may join an on-plane element of one cut to an on-plane element of another.  No
 // neighbour of a shared element is MINUS for any of its cuts (that would be a conflict), so every one of its cuts merely TOUCHES the
 // polyhedron there: applied one after the other, in rank order, each would append its facet to the element's list and filter
@@ -1055,7 +999,6 @@ __global__ __launch_bounds__(PB) void k_r2_assign3(PolyView P, const unsigned lo
 // MINUS marks (mcnt).  A workgroup takes PB / nwp vertices at a time (nwp = nw rounded up to a power of two: the lanes of one
 // vertex are neighbours in a wave), the grid strides over all new vertices: whatever a round creates is covered by ONE launch,
 // which the adjacent pairs of the round's prunes rely on (k_r2_k2emit reads these words).
-// (a device function: its own kernel calls it, and so do the extra workgroups of a round's prune launch, k_r2_k2)
 // block / nblocks: this workgroup's number among those that classify; nthr: its threads
 template <int D>
 __device__ __forceinline__ void r2_classify3_body(const PolyView &P, const double *__restrict__ hps, int B, int nw, int nwp, const RState *st, const unsigned *__restrict__ alive,
@@ -1229,108 +1172,6 @@ __global__ __launch_bounds__(K2T) void k_r2_k2emit(RState *st, const int *__rest
         if (tid == 0) s_carry += tot.a;
         __syncthreads();
     }
-}
-
-// ---- the prune launch of a round (round 3): three jobs in one launch instead of three launches.
-//   workgroups 0 .. S_launch-1   one adjacency prune each (k2_fused_body<true>), as k2_fused_t<true> was
-//   workgroups S_launch ..       classify the round's new vertices against the alive cuts (r2_classify3_body): the prunes
-//                                do not read the classes, the two have nothing to wait for in each other
-//   the LAST prune workgroup to finish (a ticket) writes the adjacent pairs of all cuts in order, commits the sizes of the round
-//   and publishes the mailbox -- k_r2_k2emit's job; with at most a few dozen workgroups in the race the agent-scope fence each
-//   of them pays for the ticket costs less than the launch it saves (with ~10^2 workgroups it did not: DESIGN.md 4a).
-struct R2Tail {
-    const double *hps; int B, nw, nwp; const unsigned *alive; unsigned long long *hw; unsigned *wm;      // classification
-    int S_launch; int *ticket; int2 *E; int *EP; int ecap; RState *st_w; RState *mail; int seq;         // emission, commit, mailbox
-    int packed;                                                                                           // class words as two masks (conflict-matrix rounds) / two-bit classes
-};
-// ordered emission of the adjacent pairs of every selected cut by ONE workgroup (cut by cut in selection order, pairs in
-// lexicographic order of the member positions), commit of the round, mailbox: what the workgroups of k_r2_k2emit do side by side
-__device__ void r2_emit_all(RState *st, const int *__restrict__ cnt_g, const int *__restrict__ nm_g, const unsigned *__restrict__ adj_g, const int *__restrict__ mem_g, int adjw_cap,
-                            int2 *E, int *EP, int ecap, RState *mail, int seq)
-{
-    __shared__ Tri lds[16];
-    __shared__ int s_carry;
-    const int S = st->S, tid = threadIdx.x;
-    const int h2 = st->halt2;
-    if (S <= 0 || !st->go || st->halt || (h2 != 0 && h2 != seq)) {
-        if (tid == 0) rstate_publish(st, mail, seq);
-        return;
-    }
-    Tri part{0, 0, 0};
-    for (int k = tid; k < S; k += K2T) { const int c = cnt_g[k]; if (c > 0) part.b += c; if (c < 0) part.c += 1; }
-    part = block_sum(part, lds);
-    const int ebase = st->ne_next, total = part.b;
-    const bool over = (long long)ebase + total > ecap;
-    if (tid == 0) {
-        st->epairs = total; st->eover = over; st->k2abort = part.c;
-        if (over || part.c > 0) st->halt2 = seq;
-        if (!over) { st->nv = st->nv_next; st->ne = ebase + total; st->poolused = st->pool_next; }
-        rstate_publish(st, mail, seq);
-    }
-    if (over) return;
-    int before = 0;
-    for (int s = 0; s < S; s++) {
-        const int cnt = cnt_g[s];
-        if (cnt <= 0) continue;
-        const int nm = nm_g[s];
-        const int nadjw = (int)(((long long)nm * (nm - 1) / 2 + 31) / 32);
-        const unsigned *adj = adj_g + (size_t)s * adjw_cap;
-        const int *mem = mem_g + (size_t)s * K2_MAXNM;
-        __syncthreads();
-        if (tid == 0) s_carry = 0;
-        __syncthreads();
-        for (int w0 = 0; w0 < nadjw; w0 += K2T) {
-            const int ww = w0 + tid;
-            unsigned word = ww < nadjw ? adj[ww] : 0u;
-            Tri t{(int)__popc(word), 0, 0};
-            Tri tot;
-            const Tri ex = block_exscan(t, &tot, lds);
-            int at = ebase + before + s_carry + ex.a;
-            while (word) {
-                const int bbit = __ffs((int)word) - 1;
-                word &= word - 1;
-                int i, j;
-                pair_decode32(ww * 32 + bbit, nm, i, j);
-                E[at] = int2{mem[i], mem[j]};
-                if (EP) EP[at] = -1;
-                at++;
-            }
-            __syncthreads();
-            if (tid == 0) s_carry += tot.a;
-            __syncthreads();
-        }
-        before += cnt;
-    }
-}
-__global__ __launch_bounds__(K2T) void k_r2_k2(PolyView P, int *members, int *fcount, int *flocal, int lds_words, int2 *Enew, Tri *totals, Mail *k2mail, int *abort_flag, K2V2 V, R2Tail T)
-{
-    if ((int)blockIdx.x >= T.S_launch) {
-        const int blk = (int)blockIdx.x - T.S_launch, nblk = (int)gridDim.x - T.S_launch;
-        switch (P.d) {
-#define CASE(D) case D: r2_classify3_body<D>(P, T.hps, T.B, T.nw, T.nwp, V.st, T.alive, T.hw, T.wm, nullptr, blk, nblk, K2T, T.packed); break;
-            CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8) CASE(9) CASE(10)
-#undef CASE
-        default: r2_classify3_body<0>(P, T.hps, T.B, T.nw, T.nwp, V.st, T.alive, T.hw, T.wm, nullptr, blk, nblk, K2T, T.packed); break;
-        }
-        return;
-    }
-    const Hp none{};
-    k2_fused_body<true>(P, members, 0, 0, 0, fcount, flocal, lds_words, Enew, 0, (int *)nullptr, totals, k2mail, 0, (unsigned long long *)nullptr, (const CutDev *)nullptr, abort_flag,
-                        (int *)nullptr, none, (int *)nullptr, (int *)nullptr, V);
-    if (!T.ticket) return;                       // (the pairs are written by a launch of their own: k_r2_k2emit)
-    // the ticket: whoever finds every other prune workgroup done writes the pairs
-    __shared__ int s_last;
-    __threadfence();
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const int t = atomicAdd(T.ticket, 1);
-        s_last = t == T.S_launch - 1;
-        if (s_last) *T.ticket = 0;
-    }
-    __syncthreads();
-    if (!s_last) return;
-    __threadfence();
-    r2_emit_all(T.st_w, V.cnt_g, V.nm_g, V.adj_g, V.mem_g, V.adjw_cap, T.E, T.EP, T.ecap, T.mail, T.seq);
 }
 
 // members of one selected cut, in slot order (on-plane elements, then the new vertices), for the multi-kernel prune

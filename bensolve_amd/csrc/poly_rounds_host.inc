@@ -230,9 +230,6 @@ static int apply_cuts_rounds(bslv_poly *h, const std::vector<int> &fids, int *rc
                 z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull; z = (z ^ (z >> 27)) * 0x94D049BB133111EBull; z ^= z >> 31;
                 std::swap(rem[k], rem[(size_t)(z % (k + 1))]);
             }
-            // (experiment, BSLV_R2_ORDER: priority by a number the caller gave per cut instead -- ties keep the shuffled order)
-            if (h->r2_order && !h->cut_prio.empty())
-                std::stable_sort(rem.begin(), rem.end(), [&](int a, int b) { return h->r2_order == 1 ? h->cut_prio[a] < h->cut_prio[b] : h->cut_prio[a] > h->cut_prio[b]; });
         }
         while (!rem.empty()) {
             const auto tp0 = std::chrono::steady_clock::now();

@@ -173,19 +173,12 @@ int  bslv_poly_path_stats(const bslv_poly *h, long out[6]);
  * key 10 changes the threshold): every rank tests a contiguous share of the rows, the adjacent pairs found are all-gathered and
  * appended in rank order, which is the order a single GPU writes them in */
 long bslv_poly_sharded_prunes(const bslv_poly *h);
-/* one number per cut of the NEXT bslv_poly_add_cuts call (e.g. the depth z of the cut); with BSLV_R2_ORDER=1 / 2 the rounds of independent
- * cuts rank the cuts of a chunk by it, ascending / descending, instead of by a pseudo-random shuffle (an experiment: see DESIGN.md 4e) */
-int  bslv_poly_set_cut_priorities(bslv_poly *h, int n, const double *prio);
 /* the projection sub-band of poly__cut (bslv_poly.c:666-674): with on = 1 an element that lies between 1e-2 POLY_EPS and POLY_EPS above a cut
  * that removes something is moved onto the hyperplane before it is treated as lying on it, exactly as the reference does, and cuts are applied
  * one at a time in the order handed in (the rounds of independent cuts classify ahead and stay off).  Default 0: such an element keeps its
  * coordinates (same index sets, coordinates within 1e-9: tests/test_oracle_poly.py::test_snap_band_*).  Also BSLV_POLY_SNAP=1. */
 int  bslv_poly_set_snap(bslv_poly *h, int on);
 int  bslv_poly_snapped(bslv_poly *h, long *moved);        /* elements moved so far */
-/* capacity ahead of need (elements = vertices + directions, edges, 32-bit words of incidence lists; 0 = leave alone): the arrays otherwise
- * double when they fill up, a hipMalloc + copy + hipFree in the middle of a batch of cuts.  The reference grows its lists the same way
- * in blocks of VRTXBLCK / LSTBLCK (bslv_poly.c:415-440 `add_vrtx`, :452 list blocks).  BSLV_E_ARG while a chunk of cuts is open. */
-int  bslv_poly_reserve(bslv_poly *h, long elements, long edges, long pool_words);
 int  bslv_poly_largest_facet(const bslv_poly *h);     /* members of the largest new facet that went through the multi-kernel prune */
 long bslv_poly_noflag_prunes(const bslv_poly *h);      /* large-facet prunes that kept no flag byte per pair (k_pair_retest_emit) */
 /* cuts that were still untouched when a chunk's rounds ended on "no cut alive" and were handed to the one-cut pipeline instead
@@ -197,7 +190,8 @@ long bslv_poly_rounds2_torn_reads(const bslv_poly *h);
 /* test hook, same switches as the BSLV_* environment variables but at run time: key 0 dynamic LDS bytes of the one-workgroup
  * prune (64 forces the multi-kernel prune), 1 speculative launch on/off, 2 hot mode on/off, 3 CROSS_UB, 4 size of a new facet
  * from which the multi-kernel prune builds facet-major member lists (default 4096), 5 member lists on/off, 6 device-selected
- * rounds of independent cuts inside a hot chunk on/off, 7 cuts per chunk (32..4096, default 512) */
+ * rounds of independent cuts inside a hot chunk on/off, 7 cuts per chunk (32..4096, default 512); keys 8, 10-12, 14 and 16:
+ * bslv_poly_debug_set in poly_engine.hip; any other key is BSLV_E_ARG */
 /* bslv_poly_add_cuts may hand cuts BACK (rc 2: not applied, dual slot left unused) when the rounds of a chunk get thinner than
  * min_cuts cuts -- the tail of a chunk is its cliques, one cut each per pass over the polyhedron; the caller hands the same
  * halfspaces in again with its next batch (phase2_primal has no counterpart: bslv_algs.c:1041-1080 applies one cut per LP).
@@ -225,11 +219,6 @@ int  bslv_poly_classify_batch(bslv_poly *h, int B, const double *hps, unsigned l
 /* TEST: the incidence kernel as the chunked cut application launches it: tc_out[i] = halfspaces element i is not strictly
  * inside, t1_out[i] = the first of them or -1 (nv ints each); words_out as bslv_poly_classify_batch (may be NULL) */
 int  bslv_poly_classify_batch_touch(bslv_poly *h, int B, const double *hps, unsigned long long *words_out, int *tc_out, int *t1_out);
-/* TEST: the incidence kernel has a variant that runs its dot products on v_mfma_f64_16x16x4 (from 16 halfspaces on; selected by
- * bslv_poly_debug_set key 9 = 1 or BSLV_K1_MFMA=1; the scalar kernel is the default because it is faster on gfx950):
- * ntiles random tiles, chained MFMAs against the scalar fma chain, *mismatches = results that differ in any bit (0: same order
- * of accumulation, one rounding per step) */
-int  bslv_k1_mfma_selftest(int dim, int ntiles, unsigned long long seed, long *mismatches);
 /* MEASUREMENT ONLY: replace the polyhedron by nv synthetic live points (for timing the incidence kernel) */
 int  bslv_poly_bench_fill(bslv_poly *h, int nv, unsigned long long seed);
 /* counts and slot-indexed dumps (poly__vrtx2file / adj2file / inc2file write these, :341-414) */
