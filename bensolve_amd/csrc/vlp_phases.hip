@@ -426,6 +426,20 @@ static int dual_benson(const Problem &pb, const Sol &S, int hom, double eps, int
         }
         if (np > 0) {
             if ((rc = bslv_lpq_solve_batch_obj(lp, np, src.data(), dst.data(), nullptr, nullptr, M + n, q, W.data(), stv.data(), itv.data()))) return done(rc);
+            {   // an LP given up (UNDEFINED: in the revised form the pivot cross-check found B^-1 drifted; nothing refactorises it) is solved
+                // once more from slot 0, the first optimal basis -- primal feasible, as every optimal slot -- as the reference retries lp_solve
+                // from the standard basis (bslv_lp.c:222-227)
+                std::vector<int> rt, rsrc, rdst, rst, rit;
+                std::vector<double> rW;
+                for (int t = 0; t < np; t++)
+                    if (stv[t] != BSLV_LP_OPTIMAL && stv[t] != BSLV_LP_UNBOUNDED) { rt.push_back(t); rsrc.push_back(0); rdst.push_back(dst[t]); rW.insert(rW.end(), &W[(size_t)t * q], &W[(size_t)t * q] + q); }
+                const int nr = (int)rt.size();
+                if (nr > 0) {
+                    rst.resize(nr); rit.resize(nr);
+                    if ((rc = bslv_lpq_solve_batch_obj(lp, nr, rsrc.data(), rdst.data(), nullptr, nullptr, M + n, q, rW.data(), rst.data(), rit.data()))) return done(rc);
+                    for (int k = 0; k < nr; k++) { stv[rt[k]] = rst[k]; itv[rt[k]] += rit[k]; }
+                }
+            }
             for (int t = 0; t < np; t++) if (stv[t] != BSLV_LP_OPTIMAL) {
                 if (stv[t] == BSLV_LP_UNBOUNDED) { *status = 2; bslv_poly_destroy(poly); poly = nullptr; return done(0); }      // :1472-1477
                 set_error("phase 2 (dual): LP status %d (the reference asserts unboundedness here, bslv_algs.c:1474)", stv[t]);

@@ -75,8 +75,9 @@ int  bslv_lpq_rows_folded(const bslv_lpq *h);
 /* REVISED FORM (the reference hands A to its solver as COO, bslv_lp.c:60-70 -> glp_load_matrix): for wide sparse
  * problems the engine can keep the BASIS INVERSE of every LP (M x M) instead of its tableau ((M+1) x N) and A once, as CSC and CSR,
  * for the whole pool; tableau rows and columns are sparse products, the delayed update and its pass kernel run on B^-1 (ex09 of the
- * reference's suite: 171 MB per LP instead of 1.36 GB).  Same interface, same slots and warm starts; bslv_lpq_solve_batch_obj is not
- * available in this form, and nothing refactorises B^-1: an LP whose inverse has drifted (the pivot element from its row and from its
+ * reference's suite: 171 MB per LP instead of 1.36 GB).  Same interface, same slots and warm starts, bslv_lpq_solve_batch_obj included
+ * (the new reduced-cost row is one tableau row built from y = sum of c_t times the rows of the parent's B^-1 that hold the basic
+ * cost-carrying variables), and nothing refactorises B^-1: an LP whose inverse has drifted (the pivot element from its row and from its
  * column disagree) comes back BSLV_LP_UNDEFINED for the caller's retry from the standard basis (bslv_lp.c:222-227).  Chosen by itself
  * for N >= 2 M, < 2 % non-zeros and tableaux of 4 GiB and more; BSLV_LP_REV=0 / 1 forces the form.  Returns 1 in the revised form. */
 int  bslv_lpq_is_revised(const bslv_lpq *h);
@@ -106,7 +107,10 @@ int  bslv_lpq_solve_batch(bslv_lpq *h, int B, const int *src, const int *dst,
 /* The LPs of the batch differ in their OBJECTIVE (lp_set_obj_coeffs + lp_solve, bslv_lp.c:141-151, 219-259, as phase2_dual
  * drives them, bslv_algs.c:1469-1477): cost costs[b*cost_cnt + t] on variable cost_first + t, zero elsewhere (the engine must
  * have been created with a zero cost vector).  LP b starts from the basis of slot src[b], which has to be primal feasible
- * (any solved slot is: the bounds do not change) and runs primal simplex steps.  vlo/vup as in solve_batch. */
+ * (any solved slot is: the bounds do not change) and runs primal simplex steps.  vlo/vup as in solve_batch.  Works in both forms
+ * (tableau and revised); src[b] == dst[b] solves in place.  In the revised form an LP can come back BSLV_LP_UNDEFINED (see above):
+ * retry it from a slot known to be accurate.  BSLV_LP_OBJ_UNDEFINED=K:b (test hook, off by default) reports LP b of the K-th call
+ * on an engine as UNDEFINED and changes nothing else. */
 int  bslv_lpq_solve_batch_obj(bslv_lpq *h, int B, const int *src, const int *dst, const double *vlo, const double *vup,
                               int cost_first, int cost_cnt, const double *costs, int *status, int *iters);
 /* getters for solved slots: out[b*cnt + j] = value for variable first+j of slot[b]
