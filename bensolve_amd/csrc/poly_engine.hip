@@ -2,14 +2,18 @@
 //
 // Replaces the polyhedron half of the hot path: poly__add_vrtx / poly__cut / edge_test /
 // poly__intl_apprx / poly__get_vrtx / poly__update_adjacence (bslv_poly.c:104-226, 467-512,
-// 562-787, 992-1010).  One cut = four data-parallel passes with prefix-sum ordering (the same
-// definition as oracle/poly_dd.c, which is checked set-wise against the compiled reference):
+// 562-787, 992-1010).  One cut = data-parallel passes with prefix-sum ordering (the same
+// definition as oracle/poly_dd.c, which is checked set-wise against the compiled reference); do_cut() queues
 //   K1  k_classify      every live element against hp.y >= alpha  -> PLUS / ZERO / MINUS
-//   E   k_edge_flags / k_edge_emit   MINUS-PLUS edges create vertices, survivors are compacted
-//   Z   k_vert_flags / k_vert_emit   ZERO elements join the new facet (incidence rebuilt)
-//   K2  k_pair_flags / k_pair_emit   adjacency prune over all pairs of the new facet:
-//       sorted-list intersection prefilter (|inc_i & inc_j| >= d-1) per lane, then a wave-
-//       cooperative superset scan (ballot over the facet's members) for the surviving pairs.
+//   E+Z k_flags2 / k_scan2 / k_emit2   one grid over edges and elements: MINUS-PLUS edges create vertices and the
+//       survivors are compacted; ZERO elements join the new facet (incidence rebuilt from the keep marks)
+//   K2  k2_fused_t      adjacency prune over all pairs of the new facet in one workgroup (bit matrix in LDS); a facet
+//       too large for it takes k2_multi: k_pair_flags* / k_pair_emit*, sorted-list intersection prefilter
+//       (|inc_i & inc_j| >= d-1) per lane, then a wave-cooperative superset scan for the surviving pairs.
+// A batch of cuts (bslv_poly_add_cuts) is classified at once (k_classify_batch_t) and applied in rounds of independent
+// cuts: poly_rounds_kernels.inc (k_edge_flags / k_edge_emit_m, k_vert_flags / k_vert_emit_m), poly_rounds2_kernels.inc.
+// What runs once per chunk or per step and not per cut -- the hot lists, the vertex selections -- compacts through
+// k_compact_count / k_compact_emit.
 // HBM layout: coordinates SoA X[k*cap + i] (coalesced K1 loads), flags 1 B/element, incidence as
 // sorted facet-id lists in one pool (inc_off/inc_len), edges as int2 pairs (ping-pong buffers).
 #include "common.h"
@@ -107,6 +111,39 @@ __device__ Tri block_exscan(Tri v, Tri *tot, Tri *lds /* >= 16 */)
     Tri ex = tri_add(base, inc);
     ex.a -= v.a; ex.b -= v.b; ex.c -= v.c;
     return ex;
+}
+// Stream compaction outside the per-cut passes, in three launches: k_compact_count leaves one sum per workgroup, k_scan_blocks turns
+// the sums into prefixes (and hands the total to the host, which sizes the output), k_compact_emit scatters in ascending order.
+// Op is a small struct passed by value:
+//   pick(i)           the contribution of element i as a Tri (.a = selected), or a struct derived from Tri that also carries what
+//                     the predicate loaded.  Written once, called by both passes: they cannot disagree about what is selected.
+//   put(i, pos, it)   emit pass, selected elements: element i is number pos of the selection
+//   seen_count(i, it) / seen_emit(i, it)   (CompactOp: nothing) side effect of that pass on every element in range
+struct CompactOp {
+    __device__ __forceinline__ void seen_count(int, const Tri &) const {}
+    __device__ __forceinline__ void seen_emit(int, const Tri &) const {}
+};
+template <class Op>
+__global__ __launch_bounds__(PB) void k_compact_count(Op op, int n, Tri *bsum)
+{
+    __shared__ Tri lds[16];
+    const int i = blockIdx.x * PB + threadIdx.x;
+    Tri t{0, 0, 0};
+    if (i < n) { const auto it = op.pick(i); op.seen_count(i, it); t = it; }
+    Tri tot;
+    (void)block_exscan(t, &tot, lds);
+    if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
+}
+template <class Op>
+__global__ __launch_bounds__(PB) void k_compact_emit(Op op, int n, const Tri *bpre)
+{
+    __shared__ Tri lds[16];
+    const int i = blockIdx.x * PB + threadIdx.x;
+    decltype(op.pick(0)) it{};
+    if (i < n) { it = op.pick(i); op.seen_emit(i, it); }
+    Tri tot;
+    const Tri ex = block_exscan(it, &tot, lds);
+    if (it.a) op.put(i, bpre[blockIdx.x].a + ex.a, it);
 }
 // sum of a Tri over the workgroup (result in every thread)
 __device__ __forceinline__ Tri block_sum(Tri v, Tri *lds /* >= 16 */)
@@ -648,136 +685,6 @@ __global__ __launch_bounds__(PB) void k_edge_flags(PolyView P, const int2 *E, in
     (void)block_exscan(t, &tot, lds);
     if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
 }
-// writes survivors to Enew[0..nsurv), creates vertex nv0+crossidx with its incidence list at
-// pool[pool0 + off), its edge at Enew[nsurv + crossidx], and marks keep[] for ZERO-PLUS edges
-// D = compile-time dimension (0 = run-time P.d): keeps the coordinate arrays in registers -- with a run-time
-// bound they are indexed dynamically and land in scratch memory (the kernel ran 10x slower)
-template <int D>
-__global__ __launch_bounds__(PB) void k_edge_emit(PolyView P, Hp hp, int facet, const int2 *E, int ne, const unsigned char *eflag,
-                                                   const Tri *bpre, const Tri *totals, int2 *Enew, int nv0, unsigned pool0)
-{
-    __shared__ Tri lds[16];
-    int e = blockIdx.x * PB + threadIdx.x;
-    Tri t{0, 0, 0};
-    unsigned char f = 0;
-    int2 ed{0, 0};
-    if (e < ne) {
-        f = eflag[e]; ed = E[e];
-        if (f == 1 || f == 4) t.a = 1;
-        else if (f >= 2) {
-            t.b = 1;
-            t.c = isect_count_fast(P.pool + P.inc_off[ed.x], P.inc_len[ed.x], P.pool + P.inc_off[ed.y], P.inc_len[ed.y]) + 1;
-        }
-    }
-    Tri tot;
-    Tri ex = block_exscan(t, &tot, lds);
-    if (e >= ne) return;
-    ex = tri_add(ex, bpre[blockIdx.x]);
-    const int d = D > 0 ? D : P.d;
-    if (f == 1) Enew[ex.a] = ed;          // plain survivor: a streaming copy, no class lookups
-    else if (f == 4) {
-        Enew[ex.a] = ed;
-        // ZERO element keeps the facets it shares with a PLUS neighbour (bslv_poly.c:634-652)
-        signed char ca = P.cls[ed.x], cb = P.cls[ed.y];
-        int z = -1, pl = -1;
-        if (ca == 0 && cb == 1) { z = ed.x; pl = ed.y; }
-        else if (ca == 1 && cb == 0) { z = ed.y; pl = ed.x; }
-        if (z >= 0) {
-            const int *A = P.pool + P.inc_off[z], *Bp = P.pool + P.inc_off[pl];
-            unsigned char *K = P.keep + P.inc_off[z];
-            int na = P.inc_len[z], nb = P.inc_len[pl];
-            if (na <= LCAP && nb <= LCAP) {
-                int RA[LCAP], RB[LCAP];
-                load_list(A, na, RA); load_list(Bp, nb, RB);
-                unsigned m = match_mask(RA, na, RB);
-                while (m) { int a = __ffs((int)m) - 1; m &= m - 1; K[a] = 1; }
-            } else if (na <= LCAP) {                 // ZERO element short, PLUS neighbour long
-                int RA[LCAP], pos[LCAP];
-                load_list(A, na, RA);
-                unsigned m = match_mask_long(RA, na, Bp, nb, pos);
-                while (m) { int a = __ffs((int)m) - 1; m &= m - 1; K[a] = 1; }
-            } else if (nb <= LCAP) {                 // ZERO element long (a direction), PLUS neighbour short
-                int RB[LCAP], pos[LCAP];
-                load_list(Bp, nb, RB);
-                unsigned m = match_mask_long(RB, nb, A, na, pos);
-#pragma unroll
-                for (int b2 = 0; b2 < LCAP; b2++) if ((m >> b2) & 1u) K[pos[b2]] = 1;
-            } else {
-                int i = 0, j = 0;
-                while (i < na && j < nb) {
-                    int x = A[i], y = Bp[j];
-                    if (x == y) K[i] = 1;
-                    i += (x <= y);
-                    j += (y <= x);
-                }
-            }
-        }
-    } else if (f == 2 || f == 3) {
-        const int mi = (f == 2) ? ed.x : ed.y, pl = (f == 2) ? ed.y : ed.x;
-        const int w = nv0 + ex.b;
-        const bool im = P.flag[mi] & F_IDEAL, ip = P.flag[pl] & F_IDEAL;
-        constexpr int DD = D > 0 ? D : MAXD;
-        double xm[DD], xp[DD], base[DD], dirv[DD];
-#pragma unroll
-        for (int k = 0; k < DD; k++) { xm[k] = k < d ? P.X[(size_t)k * P.cap + mi] : 0.0; xp[k] = k < d ? P.X[(size_t)k * P.cap + pl] : 0.0; }
-        double hb = 0.0, hd = 0.0, a2 = hp.h[d];
-        unsigned char nf = F_USED;
-        // new vertex on the edge (bslv_poly.c:597-627); same operation order as oracle/poly_dd.c:
-        // base + mu * dir with (base, dir) = (minus, plus - minus) for two directions, (plus, minus - plus) for two
-        // points, (the point, the direction) otherwise
-        if (ip && im) {
-            a2 = 0.0; nf |= F_IDEAL;
-#pragma unroll
-            for (int k = 0; k < DD; k++) { base[k] = xm[k]; dirv[k] = xp[k] - xm[k]; }
-        } else if (!ip && !im) {
-#pragma unroll
-            for (int k = 0; k < DD; k++) { base[k] = xp[k]; dirv[k] = xm[k] - xp[k]; }
-        } else {
-#pragma unroll
-            for (int k = 0; k < DD; k++) { base[k] = ip ? xm[k] : xp[k]; dirv[k] = ip ? xp[k] : xm[k]; }
-        }
-#pragma unroll
-        for (int k = 0; k < DD; k++) if (k < d) hd = fma(hp.h[k], dirv[k], hd);
-#pragma unroll
-        for (int k = 0; k < DD; k++) if (k < d) hb = fma(hp.h[k], base[k], hb);
-        const double mu = (a2 - hb) / hd;
-#pragma unroll
-        for (int k = 0; k < DD; k++) if (k < d) P.X[(size_t)k * P.cap + w] = fma(mu, dirv[k], base[k]);
-        P.flag[w] = nf;
-        P.cls[w] = 0;
-        // incidence = inc(minus) & inc(plus) + new facet (bslv_poly.c:634-665)
-        const unsigned off = pool0 + (unsigned)ex.c;
-        int *out = P.pool + off;
-        const int *A = P.pool + P.inc_off[mi], *Bp = P.pool + P.inc_off[pl];
-        int na = P.inc_len[mi], nb = P.inc_len[pl], n = 0;
-        if (na <= LCAP && nb <= LCAP) {
-            int RA[LCAP], RB[LCAP];
-            load_list(A, na, RA); load_list(Bp, nb, RB);
-            const unsigned m = match_mask(RA, na, RB);
-#pragma unroll
-            for (int a = 0; a < LCAP; a++) if ((m >> a) & 1u) out[n++] = RA[a];
-        } else if (na <= LCAP || nb <= LCAP) {       // one end is a direction with a long list
-            const bool ashort = na <= nb;
-            int S[LCAP], pos[LCAP];
-            load_list(ashort ? A : Bp, ashort ? na : nb, S);
-            const unsigned m = match_mask_long(S, ashort ? na : nb, ashort ? Bp : A, ashort ? nb : na, pos);
-#pragma unroll
-            for (int a = 0; a < LCAP; a++) if ((m >> a) & 1u) out[n++] = S[a];
-        } else {
-            int i = 0, j = 0;
-            while (i < na && j < nb) {
-                int x = A[i], y = Bp[j];
-                if (x == y) out[n++] = x;
-                i += (x <= y);
-                j += (y <= x);
-            }
-        }
-        out[n++] = facet;
-        P.inc_off[w] = off;
-        P.inc_len[w] = n;
-        Enew[totals[0].a + ex.b] = int2{w, pl};
-    }
-}
 
 // ---------------- Z: on-plane elements ----------------
 // triple: (is ZERO, 0, new list length = kept + 1)
@@ -819,87 +726,6 @@ __global__ __launch_bounds__(PB) void k_vert_flags(PolyView P, int nv0, Tri *bsu
     Tri tot;
     (void)block_exscan(t, &tot, lds);
     if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
-}
-__global__ __launch_bounds__(PB) void k_vert_emit(PolyView P, int facet, int nv0, const Tri *bpre, int *members, unsigned pool0)
-{
-    __shared__ Tri lds[16];
-    int i = blockIdx.x * PB + threadIdx.x;
-    Tri t{0, 0, 0};
-    signed char c = 2;
-    unsigned keptmask = 0;
-    int lst[LCAP];
-    int n = 0;
-    unsigned off_old = 0;
-    if (i < nv0) {
-        c = P.cls[i];
-        if (c == 0) {
-            off_old = P.inc_off[i];
-            n = P.inc_len[i];
-            const unsigned char *K = P.keep + off_old;
-            int kept = 0;
-            if (n <= LCAP) {
-                load_list(P.pool + off_old, n, lst);
-#pragma unroll
-                for (int j = 0; j < LCAP; j++) { unsigned k = (j < n) ? K[j] : 0; keptmask |= (k & 1u) << j; }
-                kept = __popc(keptmask);
-            } else if (n <= LONGN)
-                for (int j = 0; j < n; j++) kept += K[j];
-            t.a = 1; t.c = kept + 1;
-        }
-    }
-    const int lane = threadIdx.x & 63;
-    const bool longz = (c == 0) && n > LONGN;
-    {   // long lists: kept count by the whole wave (same value k_vert_flags produced)
-        unsigned long long todo = __ballot(longz);
-        while (todo) {
-            const int src = __ffsll((long long)todo) - 1;
-            todo &= todo - 1;
-            const unsigned oo = __shfl(off_old, src, WAVE);
-            const int nn = __shfl(n, src, WAVE);
-            int cnt = 0;
-            for (int j = lane; j < nn; j += WAVE) cnt += P.keep[oo + j];
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, WAVE);
-            if (lane == src) t.c = cnt + 1;
-        }
-    }
-    Tri tot;
-    Tri ex = block_exscan(t, &tot, lds);
-    ex = tri_add(ex, bpre[blockIdx.x]);
-    const unsigned off_new = pool0 + (unsigned)ex.c;
-    {   // long lists: ordered compaction by the whole wave (ballot ranks), then the new facet
-        unsigned long long todo = __ballot(longz);
-        while (todo) {
-            const int src = __ffsll((long long)todo) - 1;
-            todo &= todo - 1;
-            const unsigned oo = __shfl(off_old, src, WAVE), on = __shfl(off_new, src, WAVE);
-            const int nn = __shfl(n, src, WAVE), vv = __shfl(i, src, WAVE);
-            int base = 0;
-            for (int j0 = 0; j0 < nn; j0 += WAVE) {
-                const int j = j0 + lane;
-                const bool k = j < nn && P.keep[oo + j];
-                const unsigned long long bm = __ballot(k);
-                if (k) { P.pool[on + base + __popcll(bm & ((1ull << lane) - 1ull))] = P.pool[oo + j]; P.keep[oo + j] = 0; }
-                base += __popcll(bm);
-            }
-            if (lane == 0) { P.pool[on + base] = facet; P.inc_off[vv] = on; P.inc_len[vv] = base + 1; }
-        }
-    }
-    if (i >= nv0) return;
-    if (c == -1) { P.flag[i] &= ~F_USED; return; }
-    if (c != 0) return;
-    members[ex.a] = i;
-    if (longz) return;
-    int m = 0;
-    if (n <= LCAP) {
-#pragma unroll
-        for (int j = 0; j < LCAP; j++) if ((keptmask >> j) & 1u) { P.pool[off_new + m++] = lst[j]; P.keep[off_old + j] = 0; }
-    } else
-        for (int j = 0; j < n; j++)
-            if (P.keep[off_old + j]) { P.pool[off_new + m++] = P.pool[off_old + j]; P.keep[off_old + j] = 0; }
-    P.pool[off_new + m++] = facet;
-    P.inc_off[i] = off_new;
-    P.inc_len[i] = m;
 }
 __global__ void k_iota_members(int *members, int nzero, int nv0, int ncross)
 {
@@ -1865,17 +1691,6 @@ __global__ __launch_bounds__(PB) void k_emit2(PolyView P, Hp hp, int facet, cons
 // Falls back (mail t.b = 1) when the bit matrix does not fit; the host then runs the multi-kernel path.
 constexpr int K2T = 1024, K2_MAXNM = 512, K2_MAXLONG = 64;
 constexpr int K2_HASH_LOG = 13, K2_HASH = 1 << K2_HASH_LOG;      // LDS hash table of the facets in the member lists (64 KB)
-__device__ __forceinline__ void pair_decode(long long p, int nm, int &i, int &j)
-{
-    const double b2 = 2.0 * nm - 1.0;
-    int ii = (int)((b2 - sqrt(b2 * b2 - 8.0 * (double)p)) * 0.5);
-    ii = ii < 0 ? 0 : (ii > nm - 2 ? nm - 2 : ii);
-    while ((long long)ii * (2 * nm - ii - 1) / 2 > p) ii--;
-    while ((long long)(ii + 1) * (2 * nm - ii - 2) / 2 <= p) ii++;
-    i = ii;
-    j = ii + 1 + (int)(p - (long long)ii * (2 * nm - ii - 1) / 2);
-}
-// same for nm <= K2_MAXNM (p < 2^17): single-precision root, exact integer fix-up
 __device__ __forceinline__ void pair_decode32(int p, int nm, int &i, int &j)
 {
     const float b2 = 2.0f * nm - 1.0f;
@@ -2272,26 +2087,12 @@ __global__ void k_forward_mail(const Mail *src, Mail *dst)
 
 // ---------------- hot mode: set-up and merge (once per chunk of cuts) ----------------
 // elements some cut of the chunk touches (tc > 0, from k_classify_batch) -> hv (ascending); the others are PLUS for all
-__global__ __launch_bounds__(PB) void k_hotv_flags(PolyView P, const int *tc, int nv, Tri *bsum)
-{
-    __shared__ Tri lds[16];
-    const int i = blockIdx.x * PB + threadIdx.x;
-    Tri t{0, 0, 0};
-    if (i < nv) t.a = (P.flag[i] & F_USED) && tc[i] > 0;
-    Tri tot;
-    (void)block_exscan(t, &tot, lds);
-    if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
-}
-__global__ __launch_bounds__(PB) void k_hotv_emit(PolyView P, const int *tc, int nv, const Tri *bpre, int *hv)
-{
-    __shared__ Tri lds[16];
-    const int i = blockIdx.x * PB + threadIdx.x;
-    Tri t{0, 0, 0};
-    if (i < nv) { t.a = (P.flag[i] & F_USED) && tc[i] > 0; if (!t.a) P.cls[i] = 1; }
-    Tri tot;
-    Tri ex = block_exscan(t, &tot, lds);
-    if (t.a) hv[bpre[blockIdx.x].a + ex.a] = i;
-}
+struct HotElems : CompactOp {
+    PolyView P; const int *tc; int *hv;
+    __device__ __forceinline__ Tri pick(int i) const { return Tri{(P.flag[i] & F_USED) && tc[i] > 0, 0, 0}; }
+    __device__ __forceinline__ void seen_emit(int i, const Tri &t) const { if (!t.a) P.cls[i] = 1; }
+    __device__ __forceinline__ void put(int i, int pos, const Tri &) const { hv[pos] = i; }
+};
 // membership bitmaps of the hot elements with long lists: one wave per hot element
 __global__ __launch_bounds__(PB) void k_lbits_build(PolyView P, int nhv, int maxslots, int *nslots)
 {
@@ -2314,93 +2115,30 @@ __global__ void k_lbits_reset(PolyView P, int nhv)
     if (idx < nhv) P.lslot[P.hv[idx]] = -1;
 }
 // edges with a touched end -> EH (order kept) with their position in E; alive[e] = 1 for the others
-__global__ __launch_bounds__(PB) void k_hote_flags(const int2 *E, int ne, const int *tc, Tri *bsum)
-{
-    __shared__ Tri lds[16];
-    const int e = blockIdx.x * PB + threadIdx.x;
-    Tri t{0, 0, 0};
-    if (e < ne) { const int2 ed = E[e]; t.a = tc[ed.x] > 0 || tc[ed.y] > 0; }
-    Tri tot;
-    (void)block_exscan(t, &tot, lds);
-    if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
-}
-__global__ __launch_bounds__(PB) void k_hote_emit(const int2 *E, int ne, const int *tc, const Tri *bpre, int2 *EH, int *EP, unsigned char *alive)
-{
-    __shared__ Tri lds[16];
-    const int e = blockIdx.x * PB + threadIdx.x;
-    Tri t{0, 0, 0};
-    int2 ed{0, 0};
-    if (e < ne) { ed = E[e]; t.a = tc[ed.x] > 0 || tc[ed.y] > 0; alive[e] = t.a ? 0 : 1; }
-    Tri tot;
-    Tri ex = block_exscan(t, &tot, lds);
-    if (t.a) { const int pos = bpre[blockIdx.x].a + ex.a; EH[pos] = ed; EP[pos] = e; }
-}
-// end of the chunk: the hot edges that are still there revive their old positions; (count, 0, 0) = how many
-__global__ __launch_bounds__(PB) void k_hot_revive(const int *EP, int neh, unsigned char *alive, Tri *bsum)
-{
-    __shared__ Tri lds[16];
-    const int k = blockIdx.x * PB + threadIdx.x;
-    Tri t{0, 0, 0};
-    if (k < neh) { const int p = EP[k]; if (p >= 0) { alive[p] = 1; t.a = 1; } }
-    Tri tot;
-    (void)block_exscan(t, &tot, lds);
-    if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
-}
-__global__ __launch_bounds__(PB) void k_alive_flags(const unsigned char *alive, int ne, Tri *bsum)
-{
-    __shared__ Tri lds[16];
-    const int e = blockIdx.x * PB + threadIdx.x;
-    Tri t{0, 0, 0};
-    if (e < ne) t.a = alive[e];
-    Tri tot;
-    (void)block_exscan(t, &tot, lds);
-    if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
-}
-__global__ __launch_bounds__(PB) void k_alive_emit(const int2 *E, const unsigned char *alive, int ne, const Tri *bpre, int2 *Enew)
-{
-    __shared__ Tri lds[16];
-    const int e = blockIdx.x * PB + threadIdx.x;
-    Tri t{0, 0, 0};
-    if (e < ne) t.a = alive[e];
-    Tri tot;
-    Tri ex = block_exscan(t, &tot, lds);
-    if (t.a) Enew[bpre[blockIdx.x].a + ex.a] = E[e];
-}
+struct HotEdge : Tri { int2 ed; };
+struct HotEdges : CompactOp {
+    const int2 *E; const int *tc; int2 *EH; int *EP; unsigned char *alive;
+    __device__ __forceinline__ HotEdge pick(int e) const { const int2 ed = E[e]; return HotEdge{{tc[ed.x] > 0 || tc[ed.y] > 0, 0, 0}, ed}; }
+    __device__ __forceinline__ void seen_emit(int e, const HotEdge &t) const { alive[e] = t.a ? 0 : 1; }
+    __device__ __forceinline__ void put(int e, int pos, const HotEdge &t) const { EH[pos] = t.ed; EP[pos] = e; }
+};
+// end of the chunk: the hot edges that are still there revive their old positions; count pass only: (count, 0, 0) = how many
+struct HotOldPos : Tri { int p; };
+struct HotRevive : CompactOp {
+    const int *EP; unsigned char *alive;
+    __device__ __forceinline__ HotOldPos pick(int k) const { const int p = EP[k]; return HotOldPos{{p >= 0, 0, 0}, p}; }
+    __device__ __forceinline__ void seen_count(int, const HotOldPos &t) const { if (t.a) alive[t.p] = 1; }
+};
+// the edges of the full list that no cut of the chunk could touch, or that came back alive -> Enew (order kept)
+struct AliveEdges : CompactOp {
+    const int2 *E; const unsigned char *alive; int2 *Enew;
+    __device__ __forceinline__ Tri pick(int e) const { return Tri{alive[e], 0, 0}; }
+    __device__ __forceinline__ void put(int e, int pos, const Tri &) const { Enew[pos] = E[e]; }
+};
 
-// unprocessed = used && !sltn (bslv_poly.c:214-216): triple (flag, 0, 0)
-__global__ __launch_bounds__(PB) void k_unproc_flags(PolyView P, int nv, Tri *bsum)
-{
-    __shared__ Tri lds[16];
-    int i = blockIdx.x * PB + threadIdx.x;
-    Tri t{0, 0, 0};
-    if (i < nv) { unsigned char fl = P.flag[i]; t.a = (fl & F_USED) && !(fl & F_SLTN); }
-    Tri tot;
-    (void)block_exscan(t, &tot, lds);
-    if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
-}
-__global__ __launch_bounds__(PB) void k_unproc_emit(PolyView P, int nv, const Tri *bpre, int skip, int maxout, int total, int *idx, double *val,
-                                                     unsigned char *fl_out, int *parent)
-{
-    __shared__ Tri lds[16];
-    int i = blockIdx.x * PB + threadIdx.x;
-    Tri t{0, 0, 0};
-    unsigned char fl = 0;
-    if (i < nv) { fl = P.flag[i]; t.a = (fl & F_USED) && !(fl & F_SLTN); }
-    Tri tot;
-    Tri ex = block_exscan(t, &tot, lds);
-    if (i >= nv || !t.a) return;
-    int pos = bpre[blockIdx.x].a + ex.a;
-    if (total > 0) {              // strided sample: maxout elements spread evenly over the `total` unprocessed ones
-        long long a = (long long)pos * maxout / total, b = (long long)(pos + 1) * maxout / total;
-        if (b == a) return;
-        pos = (int)a;
-    } else pos -= skip;
-    if (pos < 0 || pos >= maxout) return;
-    idx[pos] = i;
-    fl_out[pos] = fl;
-    parent[pos] = P.inc_len[i] > 0 ? P.pool[P.inc_off[i] + P.inc_len[i] - 1] : -1;   // newest facet through it
-    for (int k = 0; k < P.d; k++) val[(size_t)pos * P.d + k] = P.X[(size_t)k * P.cap + i];
-}
+// ---------------- unprocessed elements (vertex selection, once per step) ----------------
+// unprocessed = used && !sltn (bslv_poly.c:214-216)
+__device__ __forceinline__ bool unprocessed(unsigned char fl) { return (fl & F_USED) && !(fl & F_SLTN); }
 // "children of the newest cuts first" (bslv_poly_unprocessed2, from_end == 3): the unprocessed elements are ranked by the dual
 // slot of the cut that created them (the newest facet through them), not by their own slot -- slot numbers follow the order in
 // which the cuts of a batch happened to be applied (chunks, the shuffle of the rounds), facet ids the order in which they were found.
@@ -2439,70 +2177,53 @@ __global__ __launch_bounds__(1024) void k_unproc_threshold(const int *__restrict
     }
     if (threadIdx.x == 0) { out[0] = 0; out[1] = s_carry; }  // fewer than `want` in all
 }
-__global__ __launch_bounds__(PB) void k_unproc_flags_f(PolyView P, int nv, const int *__restrict__ r2f, const int *__restrict__ thr, Tri *bsum)
+// what the three selections below know about an element: .a selected, .b unprocessed at all, its flag byte and the dual slot of its
+// parent facet (.b and pf: the two selections by parent facet)
+struct Unproc : Tri { unsigned char fl; int pf; };
+__device__ __forceinline__ Unproc unproc_child(const PolyView &P, int i, const int *r2f)      // (.a is the caller's to set)
 {
-    __shared__ Tri lds[16];
-    const int i = blockIdx.x * PB + threadIdx.x, fmin = thr[0];
-    Tri t{0, 0, 0};
-    if (i < nv) { const unsigned char fl = P.flag[i]; t.b = (fl & F_USED) && !(fl & F_SLTN); t.a = t.b && parent_facet(P, i, r2f) >= fmin; }      // (.b: all unprocessed elements)
-    Tri tot;
-    (void)block_exscan(t, &tot, lds);
-    if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
+    const unsigned char fl = P.flag[i];
+    const bool u = unprocessed(fl);
+    return Unproc{{0, u, 0}, fl, u ? parent_facet(P, i, r2f) : -1};
 }
-// the newest maxout (by slot) of the elements with a parent facet >= thr[0], ascending slot order; parent[] = FACET ids
-__global__ __launch_bounds__(PB) void k_unproc_emit_f(PolyView P, int nv, const int *__restrict__ r2f, const int *__restrict__ thr, const Tri *bpre, int skip, int maxout,
-                                                       int *idx, double *val, unsigned char *fl_out, int *parent)
-{
-    __shared__ Tri lds[16];
-    const int i = blockIdx.x * PB + threadIdx.x, fmin = thr[0];
-    Tri t{0, 0, 0};
-    unsigned char fl = 0;
-    int pf = -1;
-    if (i < nv) { fl = P.flag[i]; if ((fl & F_USED) && !(fl & F_SLTN)) { pf = parent_facet(P, i, r2f); t.a = pf >= fmin; } }
-    Tri tot;
-    const Tri ex = block_exscan(t, &tot, lds);
-    if (i >= nv || !t.a) return;
-    const int pos = bpre[blockIdx.x].a + ex.a - skip;
-    if (pos < 0 || pos >= maxout) return;
-    idx[pos] = i;
-    fl_out[pos] = fl;
-    parent[pos] = P.inc_len[i] > 0 ? pf : -1;
-    for (int k = 0; k < P.d; k++) val[(size_t)pos * P.d + k] = P.X[(size_t)k * P.cap + i];
-}
-// the unprocessed elements whose parent facet is marked in chosen[] (one byte per dual slot >= f0; older facets: not chosen)
-__global__ __launch_bounds__(PB) void k_unproc_flags_c(PolyView P, int nv, const int *__restrict__ r2f, const unsigned char *__restrict__ chosen, int f0, Tri *bsum)
-{
-    __shared__ Tri lds[16];
-    const int i = blockIdx.x * PB + threadIdx.x;
-    Tri t{0, 0, 0};
-    if (i < nv) {
-        const unsigned char fl = P.flag[i];
-        t.b = (fl & F_USED) && !(fl & F_SLTN);
-        if (t.b) { const int f = parent_facet(P, i, r2f); t.a = f >= f0 && chosen[f - f0]; }
+// their common sink: a window of maxout of the selected elements -- behind the first `skip`, or (total > 0) spread evenly over all
+// `total` of them -- with slot, flag byte, parent (par(), asked only for an element inside the window) and coordinates of each
+struct UnprocOut {
+    int skip, maxout, total;
+    int *idx; double *val; unsigned char *fl_out; int *parent;
+    template <class F>
+    __device__ __forceinline__ void put(const PolyView &P, int i, int pos, unsigned char fl, F par) const
+    {
+        if (total > 0) {              // strided sample: maxout elements spread evenly over the `total` selected ones
+            const long long a = (long long)pos * maxout / total, b = (long long)(pos + 1) * maxout / total;
+            if (b == a) return;
+            pos = (int)a;
+        } else pos -= skip;
+        if (pos < 0 || pos >= maxout) return;
+        idx[pos] = i;
+        fl_out[pos] = fl;
+        parent[pos] = par();
+        for (int k = 0; k < P.d; k++) val[(size_t)pos * P.d + k] = P.X[(size_t)k * P.cap + i];
     }
-    Tri tot;
-    (void)block_exscan(t, &tot, lds);
-    if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
-}
-__global__ __launch_bounds__(PB) void k_unproc_emit_c(PolyView P, int nv, const int *__restrict__ r2f, const unsigned char *__restrict__ chosen, int f0, const Tri *bpre, int skip, int maxout,
-                                                       int *idx, double *val, unsigned char *fl_out, int *parent)
-{
-    __shared__ Tri lds[16];
-    const int i = blockIdx.x * PB + threadIdx.x;
-    Tri t{0, 0, 0};
-    unsigned char fl = 0;
-    int pf = -1;
-    if (i < nv) { fl = P.flag[i]; if ((fl & F_USED) && !(fl & F_SLTN)) { pf = parent_facet(P, i, r2f); t.a = pf >= f0 && chosen[pf - f0]; } }
-    Tri tot;
-    const Tri ex = block_exscan(t, &tot, lds);
-    if (i >= nv || !t.a) return;
-    const int pos = bpre[blockIdx.x].a + ex.a - skip;
-    if (pos < 0 || pos >= maxout) return;
-    idx[pos] = i;
-    fl_out[pos] = fl;
-    parent[pos] = pf;
-    for (int k = 0; k < P.d; k++) val[(size_t)pos * P.d + k] = P.X[(size_t)k * P.cap + i];
-}
+};
+// all of them; parent[] = RANK of the newest facet through the element, -1 if none
+struct UnprocAll : CompactOp {
+    PolyView P; UnprocOut out;
+    __device__ __forceinline__ Unproc pick(int i) const { const unsigned char fl = P.flag[i]; return Unproc{{unprocessed(fl), 0, 0}, fl, 0}; }
+    __device__ __forceinline__ void put(int i, int pos, const Unproc &u) const { out.put(P, i, pos, u.fl, [&] { return P.inc_len[i] > 0 ? P.pool[P.inc_off[i] + P.inc_len[i] - 1] : -1; }); }
+};
+// those with a parent facet >= thr[0] (k_unproc_threshold); parent[] = dual slot of the parent, -1 for an element with an empty list
+struct UnprocNewest : CompactOp {
+    PolyView P; const int *r2f, *thr; UnprocOut out;
+    __device__ __forceinline__ Unproc pick(int i) const { Unproc u = unproc_child(P, i, r2f); u.a = u.b && u.pf >= thr[0]; return u; }
+    __device__ __forceinline__ void put(int i, int pos, const Unproc &u) const { out.put(P, i, pos, u.fl, [&] { return P.inc_len[i] > 0 ? u.pf : -1; }); }
+};
+// those whose parent facet is marked in chosen[] (one byte per dual slot >= f0; older facets: not chosen); parent[] = dual slot of the parent
+struct UnprocChosen : CompactOp {
+    PolyView P; const int *r2f; const unsigned char *chosen; int f0; UnprocOut out;
+    __device__ __forceinline__ Unproc pick(int i) const { Unproc u = unproc_child(P, i, r2f); u.a = u.b && u.pf >= f0 && chosen[u.pf - f0]; return u; }
+    __device__ __forceinline__ void put(int i, int pos, const Unproc &u) const { out.put(P, i, pos, u.fl, [&] { return u.pf; }); }
+};
 __global__ void k_mark(PolyView P, const int *idx, int n, unsigned char bit)
 {
     int k = blockIdx.x * blockDim.x + threadIdx.x;
@@ -2736,8 +2457,7 @@ struct bslv_poly {
     double *hps_d = nullptr; int hpscap = 0; std::vector<double> hps_stage;
     unsigned long long *clsw = nullptr; size_t clswcap = 0;
     unsigned *anyminus = nullptr; int anycap = 0;      // bit b%32 of word b/32: some element violates halfspace b
-    int *idx_d = nullptr; double *val_d = nullptr; unsigned char *fl_d = nullptr; int outcap = 0;
-    int *par_d = nullptr; int parcap = 0;
+    int *idx_d = nullptr; double *val_d = nullptr; unsigned char *fl_d = nullptr; int *par_d = nullptr; int outcap = 0;
     int *r2f_d = nullptr; int r2fcap = 0, r2f_n = 0;   // dual slot of every facet rank (device copy of facet_of_rank, extended on demand)
     int *fhist_d = nullptr; int fhistcap = 0;           // unprocessed elements per parent facet + 4 ints of threshold
     unsigned char *chosen_d = nullptr; size_t chosencap = 0;   // bslv_poly_children_of: one byte per dual slot from the oldest chosen one on
@@ -2871,6 +2591,24 @@ static int scan_totals(bslv_poly *h, int nb, Tri *tot_out)
     HIP_TRY(hipMemcpyAsync(h->totals_h, h->totals, sizeof(Tri), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     *tot_out = h->totals_h[0];
+    return 0;
+}
+// the two passes of a compaction over n elements (k_compact_count / k_compact_emit); the caller sizes the output from *tot in between
+static inline int compact_blocks(int n) { return std::max(1, (n + PB - 1) / PB); }
+template <class Op>
+static int compact_count(bslv_poly *h, const Op &op, int n, Tri *tot)
+{
+    const int nb = compact_blocks(n);
+    int rc;
+    if ((rc = ensure_bsum(h, nb + 1))) return rc;
+    hipLaunchKernelGGL(k_compact_count<Op>, dim3(nb), dim3(PB), 0, h->stream, op, n, h->bsum);
+    return scan_totals(h, nb, tot);
+}
+template <class Op>
+static int compact_emit(bslv_poly *h, const Op &op, int n)
+{
+    hipLaunchKernelGGL(k_compact_emit<Op>, dim3(compact_blocks(n)), dim3(PB), 0, h->stream, op, n, (const Tri *)h->bsum);
+    HIP_TRY(hipGetLastError());
     return 0;
 }
 
@@ -3353,17 +3091,17 @@ static int hot_begin(bslv_poly *h, const int *tc)
 {
     if (h->hot || h->pend_k2) { set_error("internal: hot_begin in the wrong state"); return BSLV_E_STATE; }
     hipStream_t s = h->stream;
-    const int nv = h->nv, ne = h->ne, nbv = (nv + PB - 1) / PB, nbe = std::max(1, (ne + PB - 1) / PB);
+    const int nv = h->nv, ne = h->ne;
     int rc;
-    if ((rc = ensure_bsum(h, std::max(nbv, nbe) + 1))) return rc;
     Tri t;
-    hipLaunchKernelGGL(k_hotv_flags, dim3(nbv), dim3(PB), 0, s, h->P, tc, nv, h->bsum);
-    if ((rc = scan_totals(h, nbv, &t))) return rc;
+    HotElems hv{{}, h->P, tc, nullptr};
+    if ((rc = compact_count(h, hv, nv, &t))) return rc;
     const int nhv = t.a;
     if (nhv > h->hvcap) { int nc = std::max(nhv, std::max(4096, h->hvcap * 2)); if ((rc = grow(&h->hv_d, 0, (size_t)nc, s))) return rc; h->hvcap = nc; }
-    hipLaunchKernelGGL(k_hotv_emit, dim3(nbv), dim3(PB), 0, s, h->P, tc, nv, h->bsum, h->hv_d);
-    hipLaunchKernelGGL(k_hote_flags, dim3(nbe), dim3(PB), 0, s, (const int2 *)h->E[h->ecur], ne, tc, h->bsum);
-    if ((rc = scan_totals(h, nbe, &t))) return rc;
+    hv.hv = h->hv_d;
+    if ((rc = compact_emit(h, hv, nv))) return rc;
+    HotEdges he{{}, h->E[h->ecur], tc, nullptr, nullptr, nullptr};
+    if ((rc = compact_count(h, he, ne, &t))) return rc;
     const int neh = t.a;
     bslv_poly::EdgeSet &H = h->hotbuf;
     const int need = neh + K2_MAXNM * (K2_MAXNM - 1) / 2 + 1;
@@ -3374,8 +3112,8 @@ static int hot_begin(bslv_poly *h, const int *tc)
         H.ecap = nc;
     }
     if (ne > h->alivecap) { int nc = std::max(ne, std::max(1 << 16, h->alivecap * 2)); if ((rc = grow(&h->alive, 0, (size_t)nc, s))) return rc; h->alivecap = nc; }
-    hipLaunchKernelGGL(k_hote_emit, dim3(nbe), dim3(PB), 0, s, (const int2 *)h->E[h->ecur], ne, tc, (const Tri *)h->bsum, H.E[0], H.EP[0], h->alive);
-    HIP_TRY(hipGetLastError());
+    he.EH = H.E[0]; he.EP = H.EP[0]; he.alive = h->alive;
+    if ((rc = compact_emit(h, he, ne))) return rc;
     // the full list steps aside
     bslv_poly::EdgeSet &F = h->full;
     F.E[0] = h->E[0]; F.E[1] = h->E[1]; F.eflag = h->eflag; F.ecap = h->ecap; F.ne = ne; F.ecur = h->ecur;
@@ -3417,18 +3155,16 @@ static int hot_end(bslv_poly *h)
     h->P.hv = nullptr; h->P.nhv = 0; h->P.nv_base = 0;
     h->hot = false;
     h->pre_f = -1;
-    const int ne = h->ne, nbe = std::max(1, (ne + PB - 1) / PB), nbh = std::max(1, (neh + PB - 1) / PB);
-    if ((rc = ensure_bsum(h, std::max(nbe, nbh) + 1))) return rc;
+    const int ne = h->ne;
     Tri t;
-    hipLaunchKernelGGL(k_hot_revive, dim3(nbh), dim3(PB), 0, s, EPc, neh, h->alive, h->bsum);
-    if ((rc = scan_totals(h, nbh, &t))) return rc;
+    if ((rc = compact_count(h, HotRevive{{}, EPc, h->alive}, neh, &t))) return rc;
     const int nold = t.a;                          // hot edges of the old list that are still there: a prefix of EH
-    hipLaunchKernelGGL(k_alive_flags, dim3(nbe), dim3(PB), 0, s, (const unsigned char *)h->alive, ne, h->bsum);
-    if ((rc = scan_totals(h, nbe, &t))) return rc;
+    AliveEdges al{{}, h->E[h->ecur], h->alive, nullptr};
+    if ((rc = compact_count(h, al, ne, &t))) return rc;
     const int nalive = t.a, nnew = neh - nold;
     if ((rc = ensure_ecap(h, nalive + nnew + 1))) return rc;
-    hipLaunchKernelGGL(k_alive_emit, dim3(nbe), dim3(PB), 0, s, (const int2 *)h->E[h->ecur], (const unsigned char *)h->alive, ne, (const Tri *)h->bsum, h->E[1 - h->ecur]);
-    HIP_TRY(hipGetLastError());
+    al.E = h->E[h->ecur]; al.Enew = h->E[1 - h->ecur];
+    if ((rc = compact_emit(h, al, ne))) return rc;
     if (nnew > 0) HIP_TRY(hipMemcpyAsync(h->E[1 - h->ecur] + nalive, EH + nold, (size_t)nnew * sizeof(int2), hipMemcpyDeviceToDevice, s));
     h->ecur = 1 - h->ecur;
     h->ne = nalive + nnew;
@@ -3800,10 +3536,57 @@ int bslv_poly_classify_batch_touch(bslv_poly *h, int B, const double *hps, unsig
 // all unprocessed elements (used && !sltn) in ascending slot order: the set poly__get_vrtx
 // iterates (bslv_poly.c:214-216).  *count = how many exist; at most max_out are written.
 int bslv_poly_unprocessed2(bslv_poly *h, int max_out, int from_end, int *idx, double *val, int *ideal, int *parent, int *count);
-static int sync_r2f(bslv_poly *h);
 int bslv_poly_unprocessed(bslv_poly *h, int max_out, int *idx, double *val, int *ideal, int *count)
 {
     return bslv_poly_unprocessed2(h, max_out, 0, idx, val, ideal, nullptr, count);
+}
+// room for n elements in the output arrays of the selections (idx_d, val_d, fl_d, par_d)
+static int ensure_out(bslv_poly *h, int n)
+{
+    if (n <= h->outcap) return 0;
+    const int nc = std::max(n, h->outcap * 2);
+    int rc;
+    if ((rc = grow(&h->idx_d, 0, (size_t)nc, h->stream))) return rc;
+    if ((rc = grow(&h->val_d, 0, (size_t)nc * h->d, h->stream))) return rc;
+    if ((rc = grow(&h->fl_d, 0, (size_t)nc, h->stream))) return rc;
+    if ((rc = grow(&h->par_d, 0, (size_t)nc, h->stream))) return rc;
+    h->outcap = nc;
+    return 0;
+}
+// the n elements an emit pass wrote -> host (val, parent, ideal: or nullptr), one synchronise; fl: n flag bytes, ideal[] follows from them
+static int fetch_out(bslv_poly *h, int n, int *idx, double *val, int *parent, unsigned char *fl, int *ideal)
+{
+    hipStream_t s = h->stream;
+    HIP_TRY(hipMemcpyAsync(idx, h->idx_d, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
+    if (parent) HIP_TRY(hipMemcpyAsync(parent, h->par_d, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
+    if (val) HIP_TRY(hipMemcpyAsync(val, h->val_d, (size_t)n * h->d * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(fl, h->fl_d, (size_t)n, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (ideal) for (int k = 0; k < n; k++) ideal[k] = (fl[k] & F_IDEAL) ? 1 : 0;
+    return 0;
+}
+static int sync_r2f(bslv_poly *h)
+{
+    hipStream_t s = h->stream;
+    int rc;
+    const int nr = (int)h->facet_of_rank.size();
+    if (nr > h->r2fcap) { const int nc = std::max(nr + 4096, h->r2fcap * 2); if ((rc = grow(&h->r2f_d, (size_t)h->r2f_n, (size_t)nc, s))) return rc; h->r2fcap = nc; }
+    if (nr > h->r2f_n) { HIP_TRY(hipMemcpyAsync(h->r2f_d + h->r2f_n, h->facet_of_rank.data() + h->r2f_n, (size_t)(nr - h->r2f_n) * sizeof(int), hipMemcpyHostToDevice, s)); h->r2f_n = nr; }
+    return 0;
+}
+// queues fhist_d[f] = unprocessed elements whose parent is dual slot f, f < nf; the rest of fhist_d -- the four ints of threshold
+// at its end among it -- is zero
+static int unproc_hist(bslv_poly *h)
+{
+    hipStream_t s = h->stream;
+    int rc;
+    const int nv = h->nv, nf = h->nf;
+    if ((rc = sync_r2f(h))) return rc;
+    if (nf + 4 > h->fhistcap) { const int nc = std::max(nf + 4 + 4096, h->fhistcap * 2); if ((rc = grow(&h->fhist_d, 0, (size_t)nc, s))) return rc; h->fhistcap = nc; }
+    HIP_TRY(hipMemsetAsync(h->fhist_d, 0, (size_t)h->fhistcap * sizeof(int), s));
+    hipLaunchKernelGGL(k_unproc_hist, dim3((nv + PB - 1) / PB), dim3(PB), 0, s, h->P, nv, (const int *)h->r2f_d, h->fhist_d);
+    HIP_TRY(hipGetLastError());
+    return 0;
 }
 // from_end == 1: the max_out NEWEST unprocessed elements (highest slots); == 2: max_out elements spread
 // evenly over all unprocessed ones (every total/max_out-th); == 3: the children of the newest cuts first (by the
@@ -3816,45 +3599,28 @@ int bslv_poly_unprocessed2(bslv_poly *h, int max_out, int from_end, int *idx, do
     *count = 0;
     if (!h->initialised || h->nv == 0) return 0;
     int rc;
-    const int nv = h->nv, nb = (nv + PB - 1) / PB;
-    if ((rc = ensure_bsum(h, nb + 1))) return rc;
+    const int nv = h->nv;
+    Tri t;
     if (from_end == 3) {
         // children of the newest cuts first: at most max_out elements, those whose parent facet is newest (whole families of
         // siblings; of the oldest family taken, the newest members by slot).  *count = all unprocessed elements, as in the other modes.
-        hipStream_t s = h->stream;
-        const int nf = h->nf;
-        if ((rc = sync_r2f(h))) return rc;
-        if (nf + 4 > h->fhistcap) { const int nc = std::max(nf + 4 + 4096, h->fhistcap * 2); if ((rc = grow(&h->fhist_d, 0, (size_t)nc, s))) return rc; h->fhistcap = nc; }
+        if ((rc = unproc_hist(h))) return rc;
         int *thr = h->fhist_d + h->fhistcap - 4;
-        HIP_TRY(hipMemsetAsync(h->fhist_d, 0, (size_t)h->fhistcap * sizeof(int), s));
-        hipLaunchKernelGGL(k_unproc_hist, dim3(nb), dim3(PB), 0, s, h->P, nv, (const int *)h->r2f_d, h->fhist_d);
         // (max_out == 0: only the count is wanted -- the threshold facet 0 covers everything)
-        hipLaunchKernelGGL(k_unproc_threshold, dim3(1), dim3(1024), 0, s, (const int *)h->fhist_d, nf, max_out > 0 ? max_out : (1 << 30), thr);
-        hipLaunchKernelGGL(k_unproc_flags_f, dim3(nb), dim3(PB), 0, s, h->P, nv, (const int *)h->r2f_d, (const int *)thr, h->bsum);
-        Tri t;
-        if ((rc = scan_totals(h, nb, &t))) return rc;
+        hipLaunchKernelGGL(k_unproc_threshold, dim3(1), dim3(1024), 0, h->stream, (const int *)h->fhist_d, h->nf, max_out > 0 ? max_out : (1 << 30), thr);
+        UnprocNewest op{{}, h->P, h->r2f_d, thr, {}};
+        if ((rc = compact_count(h, op, nv, &t))) return rc;
         *count = t.b;
         if (max_out == 0 || !idx) return 0;
         // everything from the threshold facet up, capped at 2 max_out + 4096 (newest slots); the host keeps the max_out best
         const int cap = 2 * max_out + 4096, n = std::min(t.a, cap);
-        if (n > h->outcap) {
-            int nc = std::max(n, h->outcap * 2);
-            if ((rc = grow(&h->idx_d, 0, (size_t)nc, s))) return rc;
-            if ((rc = grow(&h->val_d, 0, (size_t)nc * h->d, s))) return rc;
-            if ((rc = grow(&h->fl_d, 0, (size_t)nc, s))) return rc;
-            h->outcap = nc;
-        }
-        if (n > h->parcap) { if ((rc = grow(&h->par_d, 0, (size_t)std::max(n, h->parcap * 2), s))) return rc; h->parcap = std::max(n, h->parcap * 2); }
-        hipLaunchKernelGGL(k_unproc_emit_f, dim3(nb), dim3(PB), 0, s, h->P, nv, (const int *)h->r2f_d, (const int *)thr, (const Tri *)h->bsum, t.a - n, n, h->idx_d, h->val_d, h->fl_d, h->par_d);
-        HIP_TRY(hipGetLastError());
+        if ((rc = ensure_out(h, n))) return rc;
+        op.out = UnprocOut{t.a - n, n, 0, h->idx_d, h->val_d, h->fl_d, h->par_d};
+        if ((rc = compact_emit(h, op, nv))) return rc;
         std::vector<int> ti(n), tp(n);
         std::vector<double> tv((size_t)n * h->d);
         std::vector<unsigned char> fl(n);
-        HIP_TRY(hipMemcpyAsync(ti.data(), h->idx_d, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(tp.data(), h->par_d, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(tv.data(), h->val_d, (size_t)n * h->d * sizeof(double), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(fl.data(), h->fl_d, (size_t)n, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
+        if ((rc = fetch_out(h, n, ti.data(), tv.data(), tp.data(), fl.data(), nullptr))) return rc;
         std::vector<int> ord(n);
         for (int k = 0; k < n; k++) ord[k] = k;
         // newest parent facet first, within a family the newest slot first; ideal elements first of all (they cost no LP)
@@ -3876,43 +3642,20 @@ int bslv_poly_unprocessed2(bslv_poly *h, int max_out, int from_end, int *idx, do
         }
         return 0;
     }
-    hipLaunchKernelGGL(k_unproc_flags, dim3(nb), dim3(PB), 0, h->stream, h->P, nv, h->bsum);
-    Tri t;
-    if ((rc = scan_totals(h, nb, &t))) return rc;
+    UnprocAll op{{}, h->P, {}};
+    if ((rc = compact_count(h, op, nv, &t))) return rc;
     *count = t.a;
-    int n = std::min(t.a, max_out);
+    const int n = std::min(t.a, max_out);
     if (n == 0 || !idx) return 0;
-    if (n > h->outcap) {
-        int nc = std::max(n, h->outcap * 2);
-        if ((rc = grow(&h->idx_d, 0, (size_t)nc, h->stream))) return rc;
-        if ((rc = grow(&h->val_d, 0, (size_t)nc * h->d, h->stream))) return rc;
-        if ((rc = grow(&h->fl_d, 0, (size_t)nc, h->stream))) return rc;
-        h->outcap = nc;
-    }
-    if (n > h->parcap) { if ((rc = grow(&h->par_d, 0, (size_t)std::max(n, h->parcap * 2), h->stream))) return rc; h->parcap = std::max(n, h->parcap * 2); }
-    hipLaunchKernelGGL(k_unproc_emit, dim3(nb), dim3(PB), 0, h->stream, h->P, nv, h->bsum, from_end == 1 ? t.a - n : 0, n, from_end == 2 ? t.a : 0,
-                       h->idx_d, h->val_d, h->fl_d, h->par_d);
-    HIP_TRY(hipGetLastError());
+    if ((rc = ensure_out(h, n))) return rc;
+    op.out = UnprocOut{from_end == 1 ? t.a - n : 0, n, from_end == 2 ? t.a : 0, h->idx_d, h->val_d, h->fl_d, h->par_d};
+    if ((rc = compact_emit(h, op, nv))) return rc;
     std::vector<unsigned char> fl(n);
-    if (parent) HIP_TRY(hipMemcpyAsync(parent, h->par_d, n * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(idx, h->idx_d, n * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    if (val) HIP_TRY(hipMemcpyAsync(val, h->val_d, (size_t)n * h->d * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(fl.data(), h->fl_d, n, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (ideal) for (int k = 0; k < n; k++) ideal[k] = (fl[k] & F_IDEAL) ? 1 : 0;
+    if ((rc = fetch_out(h, n, idx, val, parent, fl.data(), ideal))) return rc;
     if (parent) for (int k = 0; k < n; k++) if (parent[k] >= 0) parent[k] = h->facet_of_rank[parent[k]];
     return 0;
 }
 
-static int sync_r2f(bslv_poly *h)
-{
-    hipStream_t s = h->stream;
-    int rc;
-    const int nr = (int)h->facet_of_rank.size();
-    if (nr > h->r2fcap) { const int nc = std::max(nr + 4096, h->r2fcap * 2); if ((rc = grow(&h->r2f_d, (size_t)h->r2f_n, (size_t)nc, s))) return rc; h->r2fcap = nc; }
-    if (nr > h->r2f_n) { HIP_TRY(hipMemcpyAsync(h->r2f_d + h->r2f_n, h->facet_of_rank.data() + h->r2f_n, (size_t)(nr - h->r2f_n) * sizeof(int), hipMemcpyHostToDevice, s)); h->r2f_n = nr; }
-    return 0;
-}
 // Batch selection by FAMILIES (the unprocessed children of one cut; bslv_benson policy 6).  counts[k] = unprocessed elements whose
 // parent -- the newest facet through them -- is dual slot first_facet + k, k < n; *total = all unprocessed elements,
 // *older = those whose parent is older than first_facet.
@@ -3925,12 +3668,8 @@ int bslv_poly_children_hist(bslv_poly *h, int first_facet, int n, int *counts, i
     if (!h->initialised || h->nv == 0) return 0;
     hipStream_t s = h->stream;
     int rc;
-    const int nv = h->nv, nb = (nv + PB - 1) / PB, nf = h->nf;
-    if ((rc = sync_r2f(h))) return rc;
-    if (nf + 4 > h->fhistcap) { const int nc = std::max(nf + 4 + 4096, h->fhistcap * 2); if ((rc = grow(&h->fhist_d, 0, (size_t)nc, s))) return rc; h->fhistcap = nc; }
-    HIP_TRY(hipMemsetAsync(h->fhist_d, 0, (size_t)nf * sizeof(int), s));
-    hipLaunchKernelGGL(k_unproc_hist, dim3(nb), dim3(PB), 0, s, h->P, nv, (const int *)h->r2f_d, h->fhist_d);
-    HIP_TRY(hipGetLastError());
+    const int nf = h->nf;
+    if ((rc = unproc_hist(h))) return rc;
     const int m = std::max(0, std::min(n, nf - first_facet));
     if (m > 0) HIP_TRY(hipMemcpyAsync(counts, h->fhist_d + first_facet, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, s));
     if (total || older) {
@@ -3954,7 +3693,7 @@ int bslv_poly_children_of(bslv_poly *h, int nfacets, const int *facets, int max_
     if (!h->initialised || h->nv == 0 || nfacets == 0 || max_out == 0) return 0;
     hipStream_t s = h->stream;
     int rc;
-    const int nv = h->nv, nb = (nv + PB - 1) / PB, nf = h->nf;
+    const int nv = h->nv, nf = h->nf;
     int f0 = nf;
     for (int k = 0; k < nfacets; k++) { if (facets[k] < 0 || facets[k] >= nf) { set_error("bslv_poly_children_of: facet %d out of range", facets[k]); return BSLV_E_ARG; } f0 = std::min(f0, facets[k]); }
     std::vector<unsigned char> chosen((size_t)(nf - f0), 0);
@@ -3962,30 +3701,16 @@ int bslv_poly_children_of(bslv_poly *h, int nfacets, const int *facets, int max_
     if ((rc = sync_r2f(h))) return rc;
     if ((size_t)(nf - f0) > h->chosencap) { const size_t nc = std::max((size_t)(nf - f0) + 4096, h->chosencap * 2); if ((rc = grow(&h->chosen_d, 0, nc, s))) return rc; h->chosencap = nc; }
     HIP_TRY(hipMemcpyAsync(h->chosen_d, chosen.data(), chosen.size(), hipMemcpyHostToDevice, s));
-    if ((rc = ensure_bsum(h, nb + 1))) return rc;
-    hipLaunchKernelGGL(k_unproc_flags_c, dim3(nb), dim3(PB), 0, s, h->P, nv, (const int *)h->r2f_d, (const unsigned char *)h->chosen_d, f0, h->bsum);
+    UnprocChosen op{{}, h->P, h->r2f_d, h->chosen_d, f0, {}};
     Tri t;
-    if ((rc = scan_totals(h, nb, &t))) return rc;          // (synchronises: `chosen` may go)
+    if ((rc = compact_count(h, op, nv, &t))) return rc;          // (synchronises: `chosen` may go)
     const int n = std::min(t.a, max_out);
     if (n == 0) return 0;
-    if (n > h->outcap) {
-        int nc = std::max(n, h->outcap * 2);
-        if ((rc = grow(&h->idx_d, 0, (size_t)nc, s))) return rc;
-        if ((rc = grow(&h->val_d, 0, (size_t)nc * h->d, s))) return rc;
-        if ((rc = grow(&h->fl_d, 0, (size_t)nc, s))) return rc;
-        h->outcap = nc;
-    }
-    if (n > h->parcap) { if ((rc = grow(&h->par_d, 0, (size_t)std::max(n, h->parcap * 2), s))) return rc; h->parcap = std::max(n, h->parcap * 2); }
-    hipLaunchKernelGGL(k_unproc_emit_c, dim3(nb), dim3(PB), 0, s, h->P, nv, (const int *)h->r2f_d, (const unsigned char *)h->chosen_d, f0, (const Tri *)h->bsum, t.a - n, n,
-                       h->idx_d, h->val_d, h->fl_d, h->par_d);
-    HIP_TRY(hipGetLastError());
+    if ((rc = ensure_out(h, n))) return rc;
+    op.out = UnprocOut{t.a - n, n, 0, h->idx_d, h->val_d, h->fl_d, h->par_d};
+    if ((rc = compact_emit(h, op, nv))) return rc;
     std::vector<unsigned char> fl(n);
-    if (parent) HIP_TRY(hipMemcpyAsync(parent, h->par_d, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(idx, h->idx_d, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
-    if (val) HIP_TRY(hipMemcpyAsync(val, h->val_d, (size_t)n * h->d * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(fl.data(), h->fl_d, (size_t)n, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (ideal) for (int k = 0; k < n; k++) ideal[k] = (fl[k] & F_IDEAL) ? 1 : 0;
+    if ((rc = fetch_out(h, n, idx, val, parent, fl.data(), ideal))) return rc;
     *n_out = n;
     return 0;
 }
@@ -4008,13 +3733,7 @@ int bslv_poly_mark(bslv_poly *h, int n, const int *idx)
     if (n == 0) return 0;
     for (int k = 0; k < n; k++) if (idx[k] < 0 || idx[k] >= h->nv) { set_error("bslv_poly_mark: slot %d out of range", idx[k]); return BSLV_E_ARG; }
     int rc;
-    if (n > h->outcap) {
-        int nc = std::max(n, h->outcap * 2);
-        if ((rc = grow(&h->idx_d, 0, (size_t)nc, h->stream))) return rc;
-        if ((rc = grow(&h->val_d, 0, (size_t)nc * h->d, h->stream))) return rc;
-        if ((rc = grow(&h->fl_d, 0, (size_t)nc, h->stream))) return rc;
-        h->outcap = nc;
-    }
+    if ((rc = ensure_out(h, n))) return rc;
     HIP_TRY(hipMemcpyAsync(h->idx_d, idx, n * sizeof(int), hipMemcpyHostToDevice, h->stream));
     hipLaunchKernelGGL(k_mark, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->P, h->idx_d, n, F_SLTN);
     HIP_TRY(hipGetLastError());

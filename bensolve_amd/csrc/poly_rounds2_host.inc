@@ -92,16 +92,6 @@ static void launch_r2_classify3(int d, dim3 grid, hipStream_t s, A... a)
     default: hipLaunchKernelGGL(k_r2_classify3<0>, grid, dim3(PB), 0, s, a...); break;
     }
 }
-template <class... A>
-static void launch_r2_classify(int d, dim3 grid, hipStream_t s, A... a)
-{
-    switch (d) {
-#define CASE(D) case D: hipLaunchKernelGGL(k_r2_classify<D>, grid, dim3(PB), 0, s, a...); break;
-        CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8) CASE(9) CASE(10)
-#undef CASE
-    default: hipLaunchKernelGGL(k_r2_classify<0>, grid, dim3(PB), 0, s, a...); break;
-    }
-}
 // host: one attempt to take the round state for `seq` (as mail_try_read does for a Mail)
 static inline bool rstate_try_read(const volatile RState *m, int seq, RState *out, long *torn)
 {

@@ -17,7 +17,7 @@
 //   k_flags2      (the single-cut kernel, unchanged) flags, list lengths, keep marks
 //   k_r2_emit     the single-cut emit pass with the halfspace and the facet rank of the OWNER of each crossing edge / on-plane
 //                 element; verdict on the capacities
-//   k_r2_classify the new vertices against every cut of the chunk (batched incidence kernel)
+//   k_r2_classify3 the new vertices against the alive cuts of the chunk, which of their words hold a touch, their MINUS marks
 //   k2_fused_t<true> one workgroup per selected cut: the adjacency prune of its new facet, result as a bitmap
 //   k_r2_k2emit   ordered emission of the adjacent pairs of all selected cuts, commit of the sizes, mailbox to the host
 //
@@ -69,20 +69,12 @@ __device__ __forceinline__ void rstate_publish(RState *st, RState *mail, int seq
 }
 
 __device__ __forceinline__ bool r2_halted(const RState *st) { return st->halt != 0 || st->halt2 != 0; }
-// even bits of the cuts of word w that are alive and for which element i is not PLUS (classes 01 MINUS, 10 ZERO)
 // PRIORITY = INDEX: the host shuffles the cuts of a chunk (pseudo-random, the same on every rank) before they are
 // classified, so the index order of the class words is the priority order.  The owner candidate of an element is then the
 // LOWEST set bit of (its non-PLUS cuts & alive), and "every cut of lower priority that touches this element" is a bit mask:
 // the prep pass has no loop over touches at all (with a priority table it spent 60 us walking the ~90 touches of the most
 // crowded elements).
 // hw: ELEMENT-major copy of the class words, hw[i * nw + w] (the words of one element are two cache lines).
-__device__ __forceinline__ unsigned long long r2_touch(const unsigned long long *hw, int nw, int i, const unsigned *alive, int w)
-{
-    const unsigned a = alive[w];
-    if (a == 0u) return 0ull;
-    const unsigned long long word = hw[(size_t)i * nw + w];
-    return (word ^ (word >> 1)) & 0x5555555555555555ull & spread32(a);
-}
 // The class words of an element are fetched R2B at a time with independent loads: a loop that stops at the first non-zero
 // word is a chain of dependent memory latencies (it cost 30 us per pass).
 constexpr int R2B = 8;
@@ -1050,40 +1042,6 @@ __global__ __launch_bounds__(PB) void k_r2_classify3(PolyView P, const double *_
     r2_classify3_body<D>(P, hps, B, nw, nwp, st, alive, hw, wm, mcnt, (int)blockIdx.x, (int)gridDim.x, PB, packed);
 }
 
-// classes of the vertices a round created against the cuts of the chunk that are still alive: thread = (vertex, word of 32
-// cuts), grid.y = words.  Words without an alive cut are skipped (their bits are masked wherever they are read).  Same
-// arithmetic as the batched incidence kernel (k_classify_batch_t): fma chain in coordinate order, thresholds alpha +- EPS
-// precomputed on the host.  first: offset into the new vertices (the catch-up launch of a round that made more than the grid
-// of the first launch covered).
-template <int D>
-__global__ __launch_bounds__(PB) void k_r2_classify(PolyView P, const double *__restrict__ hps, int B, int nw, const RState *st, const unsigned *__restrict__ alive,
-                                                    unsigned long long *__restrict__ hw, int first)
-{
-    const int w = blockIdx.y;
-    if (alive[w] == 0u) return;
-    // (st->nv: before the commit of the round the first new vertex, after it -- catch-up launch -- one past the last)
-    const int i = (first >= 0 ? st->nv_next - st->ncross + first : st->nv) + (int)blockIdx.x * PB + (int)threadIdx.x;
-    if (!st->go || i >= st->nv_next) return;
-    const int d = D > 0 ? D : P.d;
-    double x[D > 0 ? D : MAXD];
-#pragma unroll
-    for (int k = 0; k < (D > 0 ? D : MAXD); k++) x[k] = k < d ? P.X[(size_t)k * P.cap + i] : 0.0;
-    const bool ideal = P.flag[i] & F_IDEAL;
-    const int bend = min(32, B - w * 32);
-    unsigned plus = 0, notminus = 0;
-    for (int bb = 0; bb < bend; bb++) {
-        const double *h = hps + (size_t)(w * 32 + bb) * (d + 3);
-        double s = 0.0;
-#pragma unroll
-        for (int k = 0; k < (D > 0 ? D : MAXD); k++) if (k < d) s = fma(h[k], x[k], s);
-        const double hi = ideal ? 0.0 + POLY_EPS : h[d + 1], lo = ideal ? 0.0 - POLY_EPS : h[d + 2];
-        plus |= (unsigned)(s > hi) << bb;
-        notminus |= (unsigned)(s > lo) << bb;
-    }
-    const unsigned valid = bend == 32 ? 0xFFFFFFFFu : ((1u << bend) - 1u);
-    const unsigned lowb = (plus | ~notminus) & valid, highb = notminus & valid;
-    hw[(size_t)i * nw + w] = spread32(lowb) | (spread32(highb) << 1);
-}
 // The cuts still alive when a chunk hands them back (bslv_poly_set_defer) WILL be applied, with a later batch: every element that is
 // MINUS for one of them will be removed then.  It is marked as processed now, so that no batch in between spends an LP on it
 // (whose cut would be a valid but needless refinement next to the waiting one).

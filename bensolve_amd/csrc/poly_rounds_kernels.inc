@@ -102,7 +102,7 @@ struct SelView {
     const int *self;        // per selected cut: global facet id
 };
 
-// multi-cut twin of k_edge_emit: halfspace and facet id come from the cut that owns the MINUS end
+// multi-cut edge emit pass (survivors compacted, one vertex per crossing edge): halfspace and facet id come from the cut that owns the MINUS end
 __global__ __launch_bounds__(PB) void k_edge_emit_m(PolyView P, SelView S, int *cutof, const int2 *E, int ne, const unsigned char *eflag,
                                                      const Tri *bpre, const Tri *totals, int2 *Enew, int nv0, unsigned pool0, int *err)
 {
@@ -193,7 +193,7 @@ __global__ __launch_bounds__(PB) void k_edge_emit_m(PolyView P, SelView S, int *
     }
 }
 
-// multi-cut twin of k_vert_emit: ZERO elements join the facet of their owner cut; zlist = ZERO elements in slot order
+// multi-cut on-plane pass (incidence lists rebuilt from the keep marks): ZERO elements join the facet of their owner cut; zlist = ZERO elements in slot order
 __global__ __launch_bounds__(PB) void k_vert_emit_m(PolyView P, SelView S, const int *cutof, int nv0, const Tri *bpre, int *zlist, unsigned pool0)
 {
     __shared__ Tri lds[16];
