@@ -391,22 +391,51 @@ __device__ __forceinline__ void shift_in_gt(unsigned &acc, double s, double t)
 {
     asm("v_cmp_lt_f64 vcc, %2, %1\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(acc) : "v"(s), "s"(t) : "vcc");
 }
+// The live slots of [0, nv), for the batched classification: live[0 .. *nlive) in no particular order (every output of the
+// classification is indexed by slot).  One wave looks at LIVE_G * 64 consecutive slots -- a ballot per 64 -- and appends its
+// live ones with ONE atomic.  The dead slots get here what the classification used to leave on them: tc 0, t1 -1 (tc != nullptr).
+constexpr int LIVE_G = 8;
+__global__ __launch_bounds__(PB) void k_live_list(PolyView P, int nv, int *__restrict__ live, int *__restrict__ nlive, int *__restrict__ tc, int *__restrict__ t1)
+{
+    const int lane = (int)(threadIdx.x & 63);
+    const int base = ((int)blockIdx.x * (PB / WAVE) + (int)(threadIdx.x >> 6)) * (LIVE_G * WAVE);      // (wave-uniform; < nv + PB * LIVE_G: no overflow, nv <= 2^30)
+    if (base >= nv) return;
+    unsigned long long m[LIVE_G];
+    int total = 0;
+#pragma unroll
+    for (int g = 0; g < LIVE_G; g++) {
+        const int i = base + g * WAVE + lane;
+        m[g] = __ballot(i < nv && (P.flag[i] & F_USED));
+        total += __popcll(m[g]);
+    }
+    int pos = 0;
+    if (lane == 0 && total > 0) pos = atomicAdd(nlive, total);
+    pos = __shfl(pos, 0, WAVE);
+#pragma unroll
+    for (int g = 0; g < LIVE_G; g++) {
+        const int i = base + g * WAVE + lane;
+        if ((m[g] >> lane) & 1ull) live[pos + __popcll(m[g] & ((1ull << lane) - 1ull))] = i;
+        else if (tc && i < nv) { tc[i] = 0; t1[i] = -1; }
+        pos += __popcll(m[g]);
+    }
+}
 // one element per lane: coordinates and flag byte in registers (classify_load), then its classes against the B halfspaces
+// (i < 0: a lane past the end of the live list -- it computes along with its wave and writes nothing)
 template <int D>
-__device__ __forceinline__ void classify_load(const PolyView &P, int nv, int i, double (&x)[D > 0 ? D : MAXD], unsigned char &fl)
+__device__ __forceinline__ void classify_load(const PolyView &P, int i, double (&x)[D > 0 ? D : MAXD], unsigned char &fl)
 {
     const int d = D > 0 ? D : P.d;
     fl = 0;
 #pragma unroll
     for (int k = 0; k < (D > 0 ? D : MAXD); k++) x[k] = 0.0;
-    if (i < nv) {
+    if (i >= 0) {
         fl = P.flag[i];
 #pragma unroll
         for (int k = 0; k < (D > 0 ? D : MAXD); k++) if (k < d) x[k] = P.X[(size_t)k * P.cap + i];
     }
 }
 template <int D, bool TOUCH>
-__device__ __forceinline__ void classify_elem(const PolyView &P, const double *__restrict__ hps, int B, int nv,
+__device__ __forceinline__ void classify_elem(const PolyView &P, const double *__restrict__ hps, int B,
                                               unsigned long long *__restrict__ out, unsigned *__restrict__ anyminus,
                                               int *__restrict__ tc, int *__restrict__ t1, const int i,
                                               const double (&x)[D > 0 ? D : MAXD], const unsigned char fl)
@@ -459,7 +488,7 @@ __device__ __forceinline__ void classify_elem(const PolyView &P, const double *_
         unsigned lowb = (plus | ~notminus) & valid, highb = notminus & valid;
         unsigned minusbits = ~notminus & valid;
         if (!live) { lowb = 0; highb = 0; minusbits = 0; }
-        if (i < nv) out[(size_t)w * P.cap + i] = spread32(lowb) | (spread32(highb) << 1);
+        if (i >= 0) out[(size_t)w * P.cap + i] = spread32(lowb) | (spread32(highb) << 1);
         if (TOUCH) {
             const unsigned nonplus = live ? (~plus & valid) : 0u;
             if (nonplus) { if (touch == 0) first = w * 32 + (__ffs((int)nonplus) - 1); touch += __popc(nonplus); }
@@ -472,33 +501,26 @@ __device__ __forceinline__ void classify_elem(const PolyView &P, const double *_
                 atomicOr(&anyminus[w], minusbits);
         }
     }
-    if (TOUCH && i < nv) { tc[i] = touch; t1[i] = first; }
+    if (TOUCH && i >= 0) { tc[i] = touch; t1[i] = first; }
 }
-// Grid-stride over the elements with the next element's coordinates requested before the current one is classified.  Measured
-// (scripts/probe/k1_small_b.py, q = 5, 8 M elements): a grid capped at 4..16 workgroups per CU is 3-15 % SLOWER at B = 2..32 than
-// one workgroup per 256 elements, so the launch is not capped and the loop runs once; it stays for nv beyond one grid.  Unrolling
-// the partial-word loop by 2, 4 or 8 changes nothing (same box, +-2 %).
-constexpr int K1_MAX_BLOCKS = 1 << 22;
+// Lane t of the grid classifies slot live[t] (k_live_list): dead slots cost nothing, and they are most of a polyhedron that has
+// been cut for a while -- slots are never reused.  The grid is sized from nv on the host, the count is read here, and the
+// workgroups past it return.  One element per lane and no grid-stride loop: 2^30 elements at most (ensure_vcap) are 2^22
+// workgroups, and a grid capped at 4..16 workgroups per CU measured 3-15 % slower (scripts/probe/k1_small_b.py).  Unrolling the
+// partial-word loop by 2, 4 or 8 changes nothing (same box, +-2 %).
 template <int D, bool TOUCH>
-__global__ __launch_bounds__(PB) void k_classify_batch_t(PolyView P, const double *__restrict__ hps, int B, int nv,
+__global__ __launch_bounds__(PB) void k_classify_batch_t(PolyView P, const double *__restrict__ hps, int B,
+                                                         const int *__restrict__ live, const int *__restrict__ nlive,
                                                          unsigned long long *__restrict__ out, unsigned *__restrict__ anyminus,
                                                          int *__restrict__ tc, int *__restrict__ t1)
 {
-    const int stride = (int)gridDim.x * PB;
-    int i = (int)(blockIdx.x * PB + threadIdx.x);
-    if (i - (int)(threadIdx.x & 63) >= nv) return;                     // (wave-uniform)
+    const int n = *nlive;
+    const int t = (int)(blockIdx.x * PB + threadIdx.x);
+    if (t - (int)(threadIdx.x & 63) >= n) return;                      // (wave-uniform)
+    const int i = t < n ? live[t] : -1;
     double x[D > 0 ? D : MAXD]; unsigned char fl;
-    classify_load<D>(P, nv, i, x, fl);
-    for (;;) {
-        const int inext = i + stride;
-        const bool more = inext - (int)(threadIdx.x & 63) < nv;       // (wave-uniform; no overflow: nv + stride < 2^31 by the launch)
-        double xn[D > 0 ? D : MAXD]; unsigned char fln = 0;
-        if (more) classify_load<D>(P, nv, inext, xn, fln);
-        classify_elem<D, TOUCH>(P, hps, B, nv, out, anyminus, tc, t1, i, x, fl);
-        if (!more) break;
-        i = inext; fl = fln;
-        for (int k = 0; k < (D > 0 ? D : MAXD); k++) x[k] = xn[k];
-    }
+    classify_load<D>(P, i, x, fl);
+    classify_elem<D, TOUCH>(P, hps, B, out, anyminus, tc, t1, i, x, fl);
 }
 
 // K1 runs on the vector ALU.  A variant on the matrix pipe (v_mfma_f64_16x16x4, compares as wave masks) was built, measured slower
@@ -506,19 +528,6 @@ __global__ __launch_bounds__(PB) void k_classify_batch_t(PolyView P, const doubl
 // 6-9 % of their stand-alone progress while another wave of the same SIMD issues f64 MFMAs back to back -- the f64 MFMA occupies the
 // SIMD's fp64 datapath instead of running beside it, so the dot products cost the same fp64 cycles either way, K padded from 5 to 8
 // costs 60 % more of them, and the compares + mask hand-off come on top (21.7 against 23.2 TFLOP/s useful at q = 5, B = 512).
-static void launch_classify_batch(hipStream_t s, PolyView P, const double *hps, int B, int nv, unsigned long long *out, unsigned *anyminus,
-                                  int *tc, int *t1)
-{
-    dim3 g(std::min((nv + PB - 1) / PB, K1_MAX_BLOCKS)), b(PB);
-    switch (P.d) {
-#define CASE(D) case D: if (tc) hipLaunchKernelGGL((k_classify_batch_t<D, true>), g, b, 0, s, P, hps, B, nv, out, anyminus, tc, t1); \
-                       else hipLaunchKernelGGL((k_classify_batch_t<D, false>), g, b, 0, s, P, hps, B, nv, out, anyminus, tc, t1); break;
-        CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8) CASE(9) CASE(10)
-#undef CASE
-    default: if (tc) hipLaunchKernelGGL((k_classify_batch_t<0, true>), g, b, 0, s, P, hps, B, nv, out, anyminus, tc, t1);
-             else hipLaunchKernelGGL((k_classify_batch_t<0, false>), g, b, 0, s, P, hps, B, nv, out, anyminus, tc, t1); break;
-    }
-}
 
 // ---------------- sorted-list helpers ----------------
 __device__ __forceinline__ int isect_count(const int *a, int na, const int *b, int nb)
@@ -2456,6 +2465,7 @@ struct bslv_poly {
     // scratch for batched classify
     double *hps_d = nullptr; int hpscap = 0; std::vector<double> hps_stage;
     unsigned long long *clsw = nullptr; size_t clswcap = 0;
+    int *live_d = nullptr; int livecap = 0;             // [0]: number of live slots, [1 ..]: the slots (k_live_list, once per batched classification)
     unsigned *anyminus = nullptr; int anycap = 0;      // bit b%32 of word b/32: some element violates halfspace b
     int *idx_d = nullptr; double *val_d = nullptr; unsigned char *fl_d = nullptr; int *par_d = nullptr; int outcap = 0;
     int *r2f_d = nullptr; int r2fcap = 0, r2f_n = 0;   // dual slot of every facet rank (device copy of facet_of_rank, extended on demand)
@@ -2627,6 +2637,42 @@ static int upload_hps(bslv_poly *h, const double *hp_host, int B)
         dst[d + 2] = src[d] - POLY_EPS;
     }
     HIP_TRY(hipMemcpyAsync(h->hps_d, h->hps_stage.data(), h->hps_stage.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    return 0;
+}
+
+// Classes of the live elements of [0, nv) against the B halfspaces in h->hps_d: class words out[w * cap + i], anyminus bits, and
+// with tc != nullptr the touch counts (tc, t1).  The list of live slots is built on the device and its length stays there.
+// Dead slots: tc = 0 and t1 = -1 are written every time; their class words are NOT (whatever an earlier batch or the allocation
+// left).  Readers of the class words, checked: k_conflict_v (tc >= 2 only), k_conflict_e (both ends tc > 0), k_assign (F_USED and
+// tc > 0), k_r2_words / k_r2_words3 (the hot list: F_USED and tc > 0; nothing beyond nv_base at the start of a chunk), the
+// BSLV_R2_DEBUG dump in run_rounds2 (an element a round kernel complained about: hot), and the two test entry points below, which
+// copy all nv slots out and therefore zero the words first.  Readers of tc / t1 on dead slots: HotElems, HotEdges, k_conflict_*.
+static int launch_classify_batch(bslv_poly *h, int B, int nv, unsigned long long *out, unsigned *anyminus, int *tc, int *t1)
+{
+    hipStream_t s = h->stream;
+    int rc;
+    if (nv > h->livecap) { const int nc = std::max(nv, h->P.cap); if ((rc = grow(&h->live_d, 0, (size_t)nc + 1, s))) return rc; h->livecap = nc; }
+    int *nlive = h->live_d, *live = h->live_d + 1;
+    HIP_TRY(hipMemsetAsync(nlive, 0, sizeof(int), s));
+    const PolyView &P = h->P;
+    const double *hps = h->hps_d;
+    hipLaunchKernelGGL(k_live_list, dim3(std::max(1, (nv + PB * LIVE_G - 1) / (PB * LIVE_G))), dim3(PB), 0, s, P, nv, live, nlive, tc, t1);
+    dim3 g(std::max(1, (nv + PB - 1) / PB)), b(PB);
+    switch (P.d) {
+#define CASE(D) case D: if (tc) hipLaunchKernelGGL((k_classify_batch_t<D, true>), g, b, 0, s, P, hps, B, (const int *)live, (const int *)nlive, out, anyminus, tc, t1); \
+                       else hipLaunchKernelGGL((k_classify_batch_t<D, false>), g, b, 0, s, P, hps, B, (const int *)live, (const int *)nlive, out, anyminus, tc, t1); break;
+        CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8) CASE(9) CASE(10)
+#undef CASE
+    default: if (tc) hipLaunchKernelGGL((k_classify_batch_t<0, true>), g, b, 0, s, P, hps, B, (const int *)live, (const int *)nlive, out, anyminus, tc, t1);
+             else hipLaunchKernelGGL((k_classify_batch_t<0, false>), g, b, 0, s, P, hps, B, (const int *)live, (const int *)nlive, out, anyminus, tc, t1); break;
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+// (test entry points) zero class words for all nv slots, so that the dead ones read zero on the host
+static int zero_class_words(bslv_poly *h, int B, int nv)
+{
+    for (int w = 0; w < (B + 31) / 32; w++) HIP_TRY(hipMemsetAsync(h->clsw + (size_t)w * h->P.cap, 0, (size_t)nv * sizeof(unsigned long long), h->stream));
     return 0;
 }
 
@@ -3316,7 +3362,7 @@ void bslv_poly_destroy(bslv_poly *h)
     for (int k = 0; k < 2; k++) { fr(h->hotbuf.E[k]); fr(h->hotbuf.EP[k]); }
     fr(h->snapped_d);
     fr(h->hotbuf.eflag); fr(h->alive); fr(h->hv_d); fr(h->ecount); fr(h->lslot_d); fr(h->lbits_d); fr(h->lnslots_d);
-    fr(h->shard_e); fr(h->blks); fr(h->pflag); fr(h->fstamp); fr(h->flocal); fr(h->nlocal); fr(h->bits); fr(h->hps_d); fr(h->clsw); fr(h->anyminus); fr(h->idx_d); fr(h->val_d); fr(h->fl_d); fr(h->par_d); fr(h->r2f_d); fr(h->fhist_d); fr(h->chosen_d);
+    fr(h->shard_e); fr(h->blks); fr(h->pflag); fr(h->fstamp); fr(h->flocal); fr(h->nlocal); fr(h->bits); fr(h->hps_d); fr(h->clsw); fr(h->live_d); fr(h->anyminus); fr(h->idx_d); fr(h->val_d); fr(h->fl_d); fr(h->par_d); fr(h->r2f_d); fr(h->fhist_d); fr(h->chosen_d);
     if (h->rounds) { rounds_free(*h->rounds); delete h->rounds; }
     if (h->rounds2) { rounds2_free(*h->rounds2); delete h->rounds2; }
     if (h->totals_h) (void)hipHostFree(h->totals_h);
@@ -3448,8 +3494,7 @@ int bslv_poly_add_cuts(bslv_poly *h, int B, const double *val, const int *ideal,
             size_t need = (size_t)((nb_ + 31) / 32) * h->P.cap;
             if (need > h->clswcap) { if ((rc = grow(&h->clsw, 0, need, h->stream))) return rc; h->clswcap = need; }
             HIP_TRY(hipMemsetAsync(h->anyminus, 0, ((nb_ + 31) / 32) * sizeof(unsigned), h->stream));
-            launch_classify_batch(h->stream, h->P, h->hps_d, nb_, nv, h->clsw, h->anyminus, nullptr, nullptr);
-            HIP_TRY(hipGetLastError());
+            if ((rc = launch_classify_batch(h, nb_, nv, h->clsw, h->anyminus, nullptr, nullptr))) return rc;
             std::vector<unsigned> bits((nb_ + 31) / 32);
             HIP_TRY(hipMemcpy(bits.data(), h->anyminus, bits.size() * sizeof(unsigned), hipMemcpyDeviceToHost));
             for (int k = 0; k < nb_; k++) anym[b0 + k] = (bits[k >> 5] >> (k & 31)) & 1u;
@@ -3481,13 +3526,14 @@ int bslv_poly_classify_batch(bslv_poly *h, int B, const double *hps, unsigned lo
     size_t need = (size_t)((B + 31) / 32) * h->P.cap;
     if (need > h->clswcap) { if ((rc = grow(&h->clsw, 0, need, h->stream))) return rc; h->clswcap = need; }
     HIP_TRY(hipMemsetAsync(h->anyminus, 0, ((B + 31) / 32) * sizeof(unsigned), h->stream));
+    if ((rc = zero_class_words(h, B, nv))) return rc;
     hipEvent_t e0, e1;
     HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
     if (repeats < 1) repeats = 1;
     // one untimed launch, then `repeats` timed ones
     for (int it = 0; it <= repeats; it++) {
         if (it == 1) HIP_TRY(hipEventRecord(e0, h->stream));
-        launch_classify_batch(h->stream, h->P, h->hps_d, B, nv, h->clsw, h->anyminus, nullptr, nullptr);
+        if ((rc = launch_classify_batch(h, B, nv, h->clsw, h->anyminus, nullptr, nullptr))) return rc;
     }
     HIP_TRY(hipEventRecord(e1, h->stream));
     HIP_TRY(hipGetLastError());
@@ -3521,8 +3567,7 @@ int bslv_poly_classify_batch_touch(bslv_poly *h, int B, const double *hps, unsig
     int *tt = nullptr;
     HIP_TRY(malloc0s(&tt, (size_t)2 * std::max(nv, 1) * sizeof(int), h->stream));
     HIP_TRY(hipMemsetAsync(h->anyminus, 0, ((B + 31) / 32) * sizeof(unsigned), h->stream));
-    launch_classify_batch(h->stream, h->P, h->hps_d, B, nv, h->clsw, h->anyminus, tt, tt + nv);
-    HIP_TRY(hipGetLastError());
+    if ((rc = zero_class_words(h, B, nv)) || (rc = launch_classify_batch(h, B, nv, h->clsw, h->anyminus, tt, tt + nv))) { (void)hipFree(tt); return rc; }
     HIP_TRY(hipStreamSynchronize(h->stream));
     HIP_TRY(hipMemcpy(tc_out, tt, (size_t)nv * sizeof(int), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(t1_out, tt + nv, (size_t)nv * sizeof(int), hipMemcpyDeviceToHost));

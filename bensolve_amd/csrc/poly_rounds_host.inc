@@ -258,7 +258,7 @@ static int apply_cuts_rounds(bslv_poly *h, const std::vector<int> &fids, int *rc
                 if (need > h->clswcap) { if ((rc = grow(&h->clsw, 0, need, s))) return rc; h->clswcap = need; }
                 if ((rc = rounds_ensure(h, R, chunkB))) return rc;
             }
-            launch_classify_batch(s, h->P, h->hps_d, Bc, nv, h->clsw, R.nminus, R.tc, R.t1);      // (touch counts: conflict pass and hot mode)
+            if ((rc = launch_classify_batch(h, Bc, nv, h->clsw, R.nminus, R.tc, R.t1))) return rc;      // (touch counts: conflict pass and hot mode)
             ConfBuf C{R.conf, R.ints + 0, R.confcap, R.ints + 1};
             if (Bc > 1 && probe) {
                 hipLaunchKernelGGL(k_conflict_v, dim3(nbv), dim3(PB), 0, s, h->P, h->clsw, nw, nv, R.tc, C);
