@@ -1101,6 +1101,260 @@ __device__ bool select_once(const LpView &L, const BatchView &Bv, const int b, c
     if ((L.probe & 8) && b == 0) { __syncthreads(); if (tid == 0) { Bv.dbg[6] += wall_clock64() - tk2; Bv.dbg[7] += 1; } }
     return true;
 }
+// ---- select_once<false> of the tableau form with a pivot's row and column state kept on chip (k_select_cached) ----
+// A selection by select_once is a chain of dependent trips to global memory for data that never leaves the workgroup: the pivot row is
+// written to prow and read back by pass 0, both Harris passes and the reduced-cost update, each with nstat and the reduced costs again;
+// virt_entry loads a pending pivot's descriptor, branches on it and only then loads the row / multiplier entry, pivot after pivot, for
+// every entry of the row and of the entering column.  Here
+//  * thread tid owns the columns tid + u NT, u < CPT, from the row fetch to the reduced-cost update: row entry, reduced cost and status
+//    stay in registers; whether a column is a candidate (status, sign, pivot tolerance) is decided once; the row goes to prow once
+//    (k_flush reads it there) and the reduced costs to dcur once;
+//  * the pending descriptors are staged in LDS once per selection, the multipliers that are the same for the whole workgroup
+//    (pcol[s][r] for the row, prow[s][q] for the column) as soon as r / q is known, and the per-entry loads of ALL pending pivots
+//    (and of all owned columns / four rows) are issued before the first is used;
+//  * the entering column's loads are in flight while thread 0 writes the descriptor and the basis heads.
+// Every entry goes through the same operations in the same order as virt_entry applies them, every reduction is the same min or
+// (value, index) arg-max: no pivot and no bit of a result differs from select_once (tests/test_lp_select_cache_gpu.py).
+// For workgroups of NT threads and N <= CPT * NT; everything else (1024 threads, extended selection, revised form) stays with select_once.
+template <int CPT>
+__device__ bool select_once_cached(const LpView &L, const BatchView &Bv, const int b)
+{
+    __shared__ double sv[NT / WAVE];
+    __shared__ int si[NT / WAVE];
+    __shared__ PivDesc s_pd[KP];             // the pending pivots
+    __shared__ double s_mul[KP];             // of pending pivot s: pcol[s][r] while the row is built, prow[s][q] for the column
+    __shared__ PivDesc s_d;
+    __shared__ double s_fM;
+    constexpr int RU = 4;                    // rows per thread in flight
+    const int tid = threadIdx.x;
+    // (one trip for everything the LP's state decides)
+    const int status = Bv.status[b], mode = Bv.mode[b], np = Bv.npend[b], slot = Bv.dst[b], srcslot = Bv.src[b], flushed = Bv.flushed[b];
+    const int iters = Bv.iters[b], verified = Bv.verified[b];
+    if (status != ST_RUNNING || mode == MODE_REFRESH) return false;
+    if (np >= KP) return false;                // waits for the pass over its tableau
+    const double *T0 = L.T + (size_t)(flushed ? slot : srcslot) * L.slotT;
+    double *beta = L.beta + (size_t)slot * L.Mp1p;
+    double *xN = L.xN + (size_t)slot * L.ld;
+    int *bh = L.bh + (size_t)slot * L.M, *nh = L.nh + (size_t)slot * L.N;
+    int *nstat = L.nstat + (size_t)slot * L.N, *pos = L.pos + (size_t)slot * (L.M + L.N);
+    const int M = L.M, N = L.N, ld = L.ld, Mp1p = L.Mp1p;
+    const double *prow0 = Bv.prow + (size_t)b * KP * ld;
+    const double *pcol0 = Bv.pcol + (size_t)b * KP * Mp1p;
+    double *drow = Bv.dcur + (size_t)b * ld;
+    double *row = Bv.prow + (size_t)b * KP * ld + (size_t)np * ld;
+    double *pc = Bv.pcol + (size_t)b * KP * Mp1p + (size_t)np * Mp1p;
+    if (tid < np) s_pd[tid] = Bv.desc[(size_t)b * KP + tid];       // (read after the barriers of Phase A's reduction)
+    const bool bland = iters >= L.bland_after;
+    unsigned long long tk = (L.probe & 8) ? wall_clock64() : 0ull;
+
+    // Phase A: leaving row = largest bound violation; id = 2*i + (below ? 1 : 0)
+    ValIdx best{0.0, -1};
+    for (int i0 = tid; i0 < M; i0 += RU * NT) {
+        int kv[RU]; double lov[RU], upv[RU], btv[RU];
+#pragma unroll
+        for (int u = 0; u < RU; u++) { const int i = i0 + u * NT; kv[u] = i < M ? bh[i] : -1; btv[u] = i < M ? beta[i] : 0.0; }
+#pragma unroll
+        for (int u = 0; u < RU; u++) { lov[u] = kv[u] >= 0 ? LO(L, Bv, b, kv[u]) : -INFINITY; upv[u] = kv[u] >= 0 ? UP(L, Bv, b, kv[u]) : INFINITY; }
+#pragma unroll
+        for (int u = 0; u < RU; u++) {
+            const int i = i0 + u * NT, k = kv[u];
+            const double lo = lov[u], up = upv[u], bt = btv[u];
+            if (!isinf(lo)) { double v = lo - bt; if (v > btol(lo)) best = better_max(best, ValIdx{bland ? (double)(M + N - k) : v, 2 * i + 1}); }
+            if (!isinf(up)) { double v = bt - up; if (v > btol(up)) best = better_max(best, ValIdx{bland ? (double)(M + N - k) : v, 2 * i}); }
+        }
+    }
+    best = block_argmax(best, sv, si);
+    if (best.i < 0) {
+        // (as select_once: beta recomputed before concluding unless it is fresh; optimal, or unbounded on an active artificial bound)
+        if (!(verified & 1) && (iters > REFRESH_AFTER || (verified & 2))) {
+            if (tid == 0) Bv.mode[b] = MODE_REFRESH;
+            return true;
+        }
+        double flag = 0.0;
+        for (int j = tid; j < N; j += NT) {
+            int st = nstat[j];
+            unsigned char a = L.art[nh[j]];
+            if (((st == NS_L && (a & 1)) || (st == NS_U && (a & 2))) && fabs(drow[j]) > TOL_DJ) flag = 1.0;
+        }
+        flag = block_max(flag, sv);
+        if (tid == 0) { Bv.status[b] = flag > 0.0 ? BSLV_LP_UNBOUNDED : BSLV_LP_OPTIMAL; Bv.mode[b] = MODE_NONE; }
+        return true;
+    }
+    if (iters >= L.maxit) {
+        if (tid == 0) { Bv.status[b] = BSLV_LP_UNDEFINED; Bv.mode[b] = MODE_NONE; }
+        return true;
+    }
+    const int r = best.i >> 1;
+    const bool below = best.i & 1;
+    const double sgn = below ? 1.0 : -1.0;
+    SEL_PHASE(0);
+
+    // the pivot row as it is after the pending pivots: stored entry, the pending rows' entries, status and reduced cost of every owned
+    // column in one round of loads
+    double rowv[CPT], dv[CPT];
+    int stv[CPT];
+    {
+        double t0v[CPT], pr[KP - 1][CPT];
+#pragma unroll
+        for (int u = 0; u < CPT; u++) {
+            const int j = tid + u * NT;
+            const bool in = j < N;
+            t0v[u] = in ? T0[(size_t)r * ld + j] : 0.0;
+            stv[u] = in ? nstat[j] : NS_S;
+            dv[u] = in ? drow[j] : 0.0;
+#pragma unroll
+            for (int s = 0; s < KP - 1; s++) pr[s][u] = (in && s < np) ? prow0[(size_t)s * ld + j] : 0.0;
+        }
+        if (tid < np) s_mul[tid] = pcol0[(size_t)tid * Mp1p + r];
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < CPT; u++) {
+            const int j = tid + u * NT;
+            double v = t0v[u];
+#pragma unroll
+            for (int s = 0; s < KP - 1; s++) {
+                if (s < np) {
+                    const PivDesc d = s_pd[s];
+                    if (r == d.r) v = j == d.q ? d.p : -pr[s][u] * d.p;
+                    else { const double f = s_mul[s]; v = j == d.q ? f : fma(-f, pr[s][u], v); }
+                }
+            }
+            rowv[u] = j < N ? v : 0.0;
+            if (j < ld) row[j] = rowv[u];
+        }
+    }
+    SEL_PHASE(1);
+
+    // pass 0: row scale for the relative pivot tolerance
+    double rmax = 0.0;
+#pragma unroll
+    for (int u = 0; u < CPT; u++) if (tid + u * NT < N) rmax = fmax(rmax, fabs(rowv[u]));
+    rmax = block_max(rmax, sv);             // (its barriers also order the reads of s_mul above before the next write below)
+    const double ptol = TOL_PIV * (1.0 + rmax);
+    SEL_PHASE(2);
+    // the candidates, decided once; pass 1: Harris bound on the dual step
+    bool cand[CPT];
+    double th = INFINITY;
+#pragma unroll
+    for (int u = 0; u < CPT; u++) {
+        const int st = stv[u];
+        const double a = sgn * rowv[u];
+        cand[u] = tid + u * NT < N && st != NS_S && !(fabs(a) < ptol) && ((a > 0 && (st == NS_L || st == NS_F)) || (a < 0 && (st == NS_U || st == NS_F)));
+        if (cand[u]) th = fmin(th, (fabs(dv[u]) + (bland ? 0.0 : TOL_DJ)) / fabs(a));
+    }
+    th = block_min(th, sv);
+    SEL_PHASE(3);
+    if (isinf(th)) {                      // no entering candidate: primal infeasible ...
+        if (!(verified & 1)) {            // ... unless the violation is rounding debris in beta: recompute it first
+            if (tid == 0) Bv.mode[b] = MODE_REFRESH;
+            return true;
+        }
+        if (tid == 0) { Bv.status[b] = BSLV_LP_INFEASIBLE; Bv.mode[b] = MODE_NONE; }
+        return true;
+    }
+    // pass 2: largest |pivot| within the bound
+    ValIdx piv{0.0, -1};
+    if (bland) {
+#pragma unroll
+        for (int u = 0; u < CPT; u++) {
+            const int j = tid + u * NT;
+            const double a = sgn * rowv[u];
+            if (cand[u] && fabs(dv[u]) / fabs(a) <= th) piv = better_max(piv, ValIdx{(double)(M + N - nh[j]), j});
+        }
+    } else {
+#pragma unroll
+        for (int u = 0; u < CPT; u++) {
+            const double a = sgn * rowv[u];
+            if (cand[u] && fabs(dv[u]) / fabs(a) <= th) piv = better_max(piv, ValIdx{fabs(a), tid + u * NT});
+        }
+    }
+    piv = block_argmax(piv, sv, si);
+    SEL_PHASE(4);
+    const int q = piv.i;
+    unsigned long long tk2 = (L.probe & 8) ? wall_clock64() : 0ull;
+
+    // Phase D's loads first -- the entering column of the stored tableau, the pending multipliers of its rows, beta -- so that they
+    // are in flight while thread 0 is in Phase C
+    double c0[RU], btd[RU], pcl[KP - 1][RU];
+    auto load_rows = [&](const int i0) {
+#pragma unroll
+        for (int u = 0; u < RU; u++) {
+            const int i = i0 + u * NT;
+            c0[u] = i < M ? T0[(size_t)i * ld + q] : (i == M ? drow[q] : 0.0);
+            btd[u] = i <= M ? beta[i] : 0.0;
+#pragma unroll
+            for (int s = 0; s < KP - 1; s++) pcl[s][u] = (i < M && s < np) ? pcol0[(size_t)s * Mp1p + i] : 0.0;
+        }
+    };
+    load_rows(tid);
+    if (tid < np) s_mul[tid] = prow0[(size_t)tid * ld + q];
+    // Phase C: the descriptor, the basis heads
+    if (tid == 0) {
+        int kb = bh[r], kn = nh[q];
+        double lo = LO(L, Bv, b, kb), up = UP(L, Bv, b, kb);
+        double target = below ? lo : up;
+        double trq = row[q];
+        double br = beta[r];
+        PivDesc d;
+        d.r = r; d.q = q; d.p = 1.0 / trq;
+        d.pbeta = br - target;
+        d.enter_val = xN[q] + (target - br) / trq;
+        Bv.desc[(size_t)b * KP + np] = d;
+        s_d = d;
+        bh[r] = kn; nh[q] = kb;
+        pos[kn] = r; pos[kb] = -1 - q;
+        if (lo == up) { nstat[q] = NS_S; xN[q] = lo; }
+        else if (below) { nstat[q] = NS_L; xN[q] = lo; }
+        else { nstat[q] = NS_U; xN[q] = up; }
+        if (L.trace == b && (iters < 300 || iters % 997 == 0)) printf("lp %d it %d r %d (var %d, %s by %.3e) q %d (var %d) alpha %.3e d %.3e step %.3e flips 0 obj %.12g%s\n", b, iters, r, kb, below ? "below" : "above",
+                                 below ? lo - br : br - up, q, kn, trq, drow[q], fabs(drow[q] / trq), beta[M], bland ? " bland" : "");
+        Bv.mode[b] = MODE_PIVOT;
+        Bv.verified[b] = verified & 2;
+        Bv.iters[b] = iters + 1;
+    }
+    __syncthreads();
+    const PivDesc d = s_d;
+    if ((L.probe & 8) && b == 0) { __syncthreads(); if (tid == 0) { const unsigned long long tn = wall_clock64(); Bv.dbg[5] += tn - tk2; tk2 = tn; } }
+    // Phase D: the entering column as it is after the pending pivots -> multipliers of all rows, beta; the reduced-cost row
+    for (int i0 = tid; ; ) {
+#pragma unroll
+        for (int u = 0; u < RU; u++) {
+            const int i = i0 + u * NT;
+            if (i > M) continue;
+            if (i == r) { pc[i] = 0.0; beta[i] = d.enter_val; continue; }
+            double v = c0[u];
+            if (i < M) {
+#pragma unroll
+                for (int s = 0; s < KP - 1; s++) {
+                    if (s < np) {
+                        const PivDesc ds = s_pd[s];
+                        if (i == ds.r) v = q == ds.q ? ds.p : -s_mul[s] * ds.p;
+                        else { const double f = pcl[s][u]; v = q == ds.q ? f : fma(-f, s_mul[s], v); }
+                    }
+                }
+            }
+            const double f = v * d.p;
+            pc[i] = f;
+            beta[i] = fma(-f, d.pbeta, btd[u]);
+            if (i == M) s_fM = f;
+        }
+        i0 += RU * NT;
+        if (i0 > M) break;
+        load_rows(i0);
+    }
+    __syncthreads();
+    {
+        const double fM = s_fM;
+#pragma unroll
+        for (int u = 0; u < CPT; u++) {
+            const int j = tid + u * NT;
+            if (j < N) drow[j] = j == q ? fM : fma(-fM, rowv[u], dv[u]);
+        }
+    }
+    if (tid == 0) Bv.npend[b] = np + 1;
+    if ((L.probe & 8) && b == 0) { __syncthreads(); if (tid == 0) { Bv.dbg[6] += wall_clock64() - tk2; Bv.dbg[7] += 1; } }
+    return true;
+}
 // One launch selects up to nsel pivots per LP, one after the other, by the same workgroup: the KP selections between two passes
 // over the tableau depend only on the LP's own vectors (beta, the reduced-cost row, the pending pivot rows and multipliers) -- no
 // grid-wide dependency asks for a launch each (rounds 1-3 launched this kernel KP times per pass, 17 % of all GPU time in
@@ -1121,6 +1375,19 @@ __global__ __launch_bounds__(NT_BIG) void k_select(LpView L, BatchView Bv, const
     }
 }
 
+// k_select<false> for the tableau form in workgroups of NT threads and rows of at most CPT * NT columns (CPT = 2, 4, 6: every row
+// length below the 1536 columns from which a selection takes NT_BIG threads).  A kernel of its own: k_select is compiled for 1024
+// threads, 128 registers, and carries the revised form's sparse products; this one holds its state in registers without spilling.
+template <int CPT>
+__global__ __launch_bounds__(NT) void k_select_cached(LpView L, BatchView Bv, const int *active, int nact, int nsel)
+{
+    if ((int)blockIdx.x >= nact) return;
+    const int b = active[blockIdx.x];
+    for (int sdx = 0; sdx < nsel; sdx++) {
+        if (sdx) __syncthreads();
+        if (!select_once_cached<CPT>(L, Bv, b)) break;
+    }
+}
 
 // ---- which LPs need a pass over their tableau: pending pivots to apply, or beta to recompute ----
 __global__ void k_list_pending(BatchView Bv, const int *active, int nact, int it)
@@ -1963,6 +2230,9 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
     h->last_update_ms = 0;
     static const int max_rounds = getenv("BSLV_LP_MAXROUNDS") ? atoi(getenv("BSLV_LP_MAXROUNDS")) : 0;      // (timing experiments)
     L.probe = getenv("BSLV_REV_PROBE") ? atoi(getenv("BSLV_REV_PROBE")) : 0;
+    const bool sel_cache = !(getenv("BSLV_SELECT_CACHE") && atoi(getenv("BSLV_SELECT_CACHE")) == 0);      // 0: k_select<false> where k_select_cached would run (same results bit for bit, tests/test_lp_select_cache_gpu.py)
+    // columns per thread of k_select_cached (plain dual selection, tableau form, NT threads), 0: k_select
+    const int sel_cpt = (sel_cache && !bfrt && !L.rev && sel_nt == NT && L.N <= 6 * NT) ? (L.N <= 2 * NT ? 2 : (L.N <= 4 * NT ? 4 : 6)) : 0;
     while (running > 0 && it < L.maxit + 8 && !(max_rounds && it >= max_rounds)) {
         for (int c = 0; c < chunk; c++, it++) {
             for (int lev = 0; lev < KP; lev += sel_per_launch) {
@@ -1975,7 +2245,10 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
                 }
                 L.helpers = helpers;
                 L.launch_id = (++h->launch_seq) & 0x3FFFFF;
-                if (bfrt) hipLaunchKernelGGL(k_select<true>, dim3(running, helpers), dim3(sel_nt), sel_lds_launch, s, L, bv, h->active_d, running, cap2, sel_per_launch);
+                if (sel_cpt == 2) hipLaunchKernelGGL(k_select_cached<2>, dim3(running), dim3(NT), 0, s, L, bv, h->active_d, running, sel_per_launch);
+                else if (sel_cpt == 4) hipLaunchKernelGGL(k_select_cached<4>, dim3(running), dim3(NT), 0, s, L, bv, h->active_d, running, sel_per_launch);
+                else if (sel_cpt == 6) hipLaunchKernelGGL(k_select_cached<6>, dim3(running), dim3(NT), 0, s, L, bv, h->active_d, running, sel_per_launch);
+                else if (bfrt) hipLaunchKernelGGL(k_select<true>,dim3(running, helpers), dim3(sel_nt), sel_lds_launch, s, L, bv, h->active_d, running, cap2, sel_per_launch);
                 else hipLaunchKernelGGL(k_select<false>, dim3(running, helpers), dim3(sel_nt), sel_lds_launch, s, L, bv, h->active_d, running, 0, sel_per_launch);
             }
             hipLaunchKernelGGL(k_list_pending, dim3((running + 255) / 256), dim3(256), 0, s, bv, h->active_d, running, it);
