@@ -89,7 +89,7 @@ struct LpView {
     // ex09: 171 MB per slot instead of 1.36 GB.  rev == 0: ldt = ld, mrows = M + 1 and everything is as before.
     int rho_off;                // rev: byte offset of the LDS copy of rho (row of B^-1 the tableau row is built from) in k_select's dynamic LDS, or -1 (does not fit: gathers from global memory)
     int helpers, launch_id;      // revised form: workgroups per LP in k_select (1 = none besides the LP's own) that share the sparse products of a tableau row; a number per launch for their mailbox
-    int rev, ldt, mrows, probe;  // probe: BSLV_REV_PROBE, timing experiments only (parts of the revised selection skipped: results are WRONG)
+    int rev, ldt, mrows, probe;  // probe: BSLV_REV_PROBE, timing experiments only (8: phase clocks of the selection, see phase_mark; 16: rev_take_slices without its release fence)
     double *dsl;                // rev: [slots][ld] reduced costs of each slot (the tableau form keeps them as row M of T)
     const int *cptr, *cidx; const double *cval;   // rev: CSC of A
     const int *rptr, *ridx; const double *rval;   // rev: CSR of A
@@ -287,14 +287,33 @@ __device__ __forceinline__ double block_min(double v, double *sv)
 // ---- k_select: dual simplex choice of (leaving row r, entering column q) for each running LP.
 //      Same rules as oracle/lp_dense.c dual_simplex(): largest bound violation, Harris two-pass
 //      ratio test with the largest |pivot| among the ties. ----
+// THE RULES, each stated once for select_once and select_once_cached (below): the two differ in where a pivot's row and column state
+// lives and in how loads are issued, never in a rule -- same pivots, same bits (tests/test_lp_select_cache_gpu.py).
+// One pending pivot (1 / pivot element p, multiplier f of the entry's row, entry of the pivot row in its column) applied to one entry, as k_flush does
+__device__ __forceinline__ double apply_pending(double v, bool is_pivot_row, bool is_pivot_col, double p, double f, double rowentry)
+{
+    if (is_pivot_row) return is_pivot_col ? p : -rowentry * p;
+    return is_pivot_col ? f : fma(-f, rowentry, v);
+}
+// leaving row: largest bound violation (smallest variable id under Bland's rule); id = 2*i + (below ? 1 : 0)
+__device__ __forceinline__ ValIdx leave_candidate(ValIdx best, double lo, double up, double bt, int k, int i, bool bland, int nvar)
+{
+    if (!isinf(lo)) { double v = lo - bt; if (v > btol(lo)) best = better_max(best, ValIdx{bland ? (double)(nvar - k) : v, 2 * i + 1}); }
+    if (!isinf(up)) { double v = bt - up; if (v > btol(up)) best = better_max(best, ValIdx{bland ? (double)(nvar - k) : v, 2 * i}); }
+    return best;
+}
+// may a column of status st with the (signed) row entry a enter?
+__device__ __forceinline__ bool is_candidate(int st, double a, double ptol) { return st != NS_S && !(fabs(a) < ptol) && ((a > 0 && (st == NS_L || st == NS_F)) || (a < 0 && (st == NS_U || st == NS_F))); }
+__device__ __forceinline__ double harris_key(double d, double a, bool bland) { return (fabs(d) + (bland ? 0.0 : TOL_DJ)) / fabs(a); }
+__device__ __forceinline__ bool within_bound(double d, double a, double th) { return fabs(d) / fabs(a) <= th; }
+
 // entry (i, j) of the tableau as it is after the pending pivots 0..np-1, given its value v0 in the stored tableau
-// (same operations, in the same order, as k_flush applies them -- and as one rank-1 update per pivot did)
 __device__ __forceinline__ double virt_entry(double v, int i, int j, int np, const PivDesc *pd, const double *prow, const double *pcol, int ld, int Mp1p)
 {
     for (int s = 0; s < np; s++) {
         const PivDesc d = pd[s];
-        if (i == d.r) v = j == d.q ? d.p : -prow[(size_t)s * ld + j] * d.p;
-        else { const double f = pcol[(size_t)s * Mp1p + i]; v = j == d.q ? f : fma(-f, prow[(size_t)s * ld + j], v); }
+        const bool pr = i == d.r, pq = j == d.q;
+        v = apply_pending(v, pr, pq, d.p, pr ? 0.0 : pcol[(size_t)s * Mp1p + i], pq ? 0.0 : prow[(size_t)s * ld + j]);
     }
     return v;
 }
@@ -304,8 +323,8 @@ __device__ __forceinline__ double virt_entry_b(double v, int i, int c, int np, c
 {
     for (int s = 0; s < np; s++) {
         const PivDesc d = pd[s];
-        if (i == d.r) v = -prow[(size_t)s * ldt + c] * d.p;
-        else v = fma(-pcol[(size_t)s * Mp1p + i], prow[(size_t)s * ldt + c], v);
+        const bool pr = i == d.r;
+        v = apply_pending(v, pr, false, d.p, pr ? 0.0 : pcol[(size_t)s * Mp1p + i], prow[(size_t)s * ldt + c]);
     }
     return v;
 }
@@ -529,7 +548,7 @@ __device__ void rev_take_slices(const LpView &L, int *mb, const int n, const dou
         if (threadIdx.x == 0) __hip_atomic_fetch_add(&mb[1], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
-__device__ void rev_helper(const LpView &L, const BatchView &Bv, const int b)
+__device__ __forceinline__ void rev_helper(const LpView &L, const BatchView &Bv, const int b)
 {
     extern __shared__ unsigned char dyn_sel[];
     __shared__ int s_req;
@@ -547,25 +566,419 @@ __device__ void rev_helper(const LpView &L, const BatchView &Bv, const int b)
         if ((req >> 8) != L.launch_id || req == last) { __builtin_amdgcn_s_sleep(8); continue; }
         if ((req & 0xFF) == 0xFF) return;
         last = req;
-        if (!(L.probe & 32)) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");      // (once per request: rho, the pending count and the heads as the LP's workgroup left them)
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");      // (once per request: rho, the pending count and the heads as the LP's workgroup left them)
         const int np = __hip_atomic_load(&mb[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         const double *brow_g = Bv.prow + (size_t)b * KP * L.ldt + (size_t)np * L.ldt;
         if (srho) { for (int c = tid; c < L.ldt; c += NT) srho[c] = brow_g[c]; __syncthreads(); }
-        if (!(L.probe & 64)) rev_take_slices(L, mb, req & 0xFF, srho ? srho : brow_g, nh, Bv.trow + (size_t)b * L.ld);
+        rev_take_slices(L, mb, req & 0xFF, srho ? srho : brow_g, nh, Bv.trow + (size_t)b * L.ld);
     }
 }
+// BSLV_REV_PROBE & 8: 100 MHz clock ticks per phase of the selections of LP 0, summed in Bv.dbg[k] (solve_batch_impl prints them)
+__device__ __forceinline__ void phase_mark(const LpView &L, const BatchView &Bv, int b, int k, unsigned long long &t)
+{
+    if ((L.probe & 8) && b == 0) { __syncthreads(); if (threadIdx.x == 0) { const unsigned long long tn = wall_clock64(); Bv.dbg[k] += tn - t; t = tn; } }
+}
+// The vectors of LP b as one selection sees them
+struct SelCtx {
+    const double *T0;            // the stored tableau of this solve: the parent's slot until the first pass has written its own (see k_init)
+    double *beta, *xN; int *bh, *nh, *nstat, *pos;
+    double *prow0, *pcol0;       // the pending pivots' rows and multipliers
+    double *drow;                // the reduced costs (the true ones: a perturbation has a row of its own, dper)
+    double *row;                 // the pivot row as it is after the pending pivots, where k_flush will read it (revised form: k_flush reads the row of B^-1 from there, and the tableau row lives in a scratch vector of the LP)
+    double *pc;                  // the multipliers of the rows (primal selection: first the entering column itself)
+    const PivDesc *pd; int np, b;
+};
+__device__ __forceinline__ SelCtx sel_ctx(const LpView &L, const BatchView &Bv, int b, int np, int slot, int stored_slot)
+{
+    SelCtx c;
+    c.T0 = L.T + (size_t)stored_slot * L.slotT;
+    c.beta = L.beta + (size_t)slot * L.Mp1p; c.xN = L.xN + (size_t)slot * L.ld;
+    c.bh = L.bh + (size_t)slot * L.M; c.nh = L.nh + (size_t)slot * L.N;
+    c.nstat = L.nstat + (size_t)slot * L.N; c.pos = L.pos + (size_t)slot * (L.M + L.N);
+    c.prow0 = Bv.prow + (size_t)b * KP * L.ldt; c.pcol0 = Bv.pcol + (size_t)b * KP * L.Mp1p;
+    c.drow = Bv.dcur + (size_t)b * L.ld; c.row = L.rev ? Bv.trow + (size_t)b * L.ld : c.prow0 + (size_t)np * L.ld;
+    c.pc = c.pcol0 + (size_t)np * L.Mp1p; c.pd = Bv.desc + (size_t)b * KP;
+    c.np = np; c.b = b; return c;
+}
+// No row violates a bound: optimal, or unbounded on an active artificial bound.  Beta is recomputed first (a full read of the tableau) unless
+// it is fresh or this solve made only a few pivots since k_init computed it (rank-1 updates: ~1e-15 against tolerances of 1e-9; not after a start on an artificial bound, 1e7 leaves debris of 1e-9)
+__device__ __forceinline__ void conclude_optimal(const LpView &L, const BatchView &Bv, const SelCtx &c, const int iters, const int verified, const int nt, double *sv)
+{
+    const int tid = threadIdx.x, b = c.b;
+    if (!(verified & 1) && (iters > REFRESH_AFTER || (verified & 2))) { if (tid == 0) Bv.mode[b] = MODE_REFRESH; return; }      // k_flush applies what is pending and recomputes beta
+    double flag = 0.0;
+    for (int j = tid; j < L.N; j += nt) {
+        int st = c.nstat[j];
+        unsigned char a = L.art[c.nh[j]];
+        if (((st == NS_L && (a & 1)) || (st == NS_U && (a & 2))) && fabs(c.drow[j]) > TOL_DJ) flag = 1.0;
+    }
+    flag = block_max(flag, sv);
+    if (tid == 0) { Bv.status[b] = flag > 0.0 ? BSLV_LP_UNBOUNDED : BSLV_LP_OPTIMAL; Bv.mode[b] = MODE_NONE; }
+}
+// No entering candidate: primal infeasible -- unless the violation is rounding debris in beta: recompute it first
+__device__ __forceinline__ void conclude_infeasible(const BatchView &Bv, const int b, const int verified)
+{
+    if (threadIdx.x == 0) { if (!(verified & 1)) Bv.mode[b] = MODE_REFRESH; else { Bv.status[b] = BSLV_LP_INFEASIBLE; Bv.mode[b] = MODE_NONE; } }
+}
+__device__ __noinline__ void trace_pivot(int b, int iters, bool primal, int r, int kb, bool below, double viol, int q, int kn, double trq, double dq, int nflip, double obj, bool bland, bool perturbed)
+{
+    printf("lp %d it %d%s r %d (var %d, %s by %.3e) q %d (var %d) alpha %.3e d %.3e step %.3e flips %d obj %.12g%s%s\n", b, iters, primal ? " primal" : "", r, kb, below ? "below" : "above", viol, q, kn, trq, dq, fabs(dq / trq), nflip, obj, bland ? " bland" : "", perturbed ? " perturbed" : "");
+}
+// Phase C, by ONE thread: descriptor of the pivot (r, q), basis heads, the leaving variable's new status (dwork, primal, nflip, perturbed: trace line only)
+__device__ __forceinline__ PivDesc commit_pivot(const LpView &L, const BatchView &Bv, const SelCtx &c, const int r, const int q, const bool below, const bool bland,
+                                                const int iters, const int verified, const int mode, const double *dwork, const bool primal, const int nflip, const bool perturbed)
+{
+    const int b = c.b;
+    int kb = c.bh[r], kn = c.nh[q];
+    double lo = LO(L, Bv, b, kb), up = UP(L, Bv, b, kb);
+    double target = below ? lo : up, trq = c.row[q], br = c.beta[r];
+    PivDesc d;
+    d.r = r; d.q = q; d.p = 1.0 / trq; d.pbeta = br - target; d.enter_val = c.xN[q] + (target - br) / trq;
+    Bv.desc[(size_t)b * KP + c.np] = d;
+    c.bh[r] = kn; c.nh[q] = kb;
+    c.pos[kn] = r; c.pos[kb] = -1 - q;
+    if (lo == up) { c.nstat[q] = NS_S; c.xN[q] = lo; }
+    else if (below) { c.nstat[q] = NS_L; c.xN[q] = lo; }
+    else { c.nstat[q] = NS_U; c.xN[q] = up; }
+    if (L.trace == b && (iters < 300 || iters % 997 == 0)) trace_pivot(b, iters, primal, r, kb, below, below ? lo - br : br - up, q, kn, trq, dwork[q], nflip, c.beta[L.M], bland, perturbed);
+    Bv.mode[b] = mode; Bv.verified[b] = verified & 2; Bv.iters[b] = iters + 1;
+    return d;
+}
+
+// ---- row r / column q of the tableau as it is after the pending pivots, by the whole workgroup (barriers inside) ----
+__device__ __forceinline__ void fetch_row_tableau(const LpView &L, const SelCtx &c, const int r)
+{
+    for (int j = threadIdx.x; j < L.ld; j += (int)blockDim.x) c.row[j] = j < L.N ? virt_entry(c.T0[(size_t)r * L.ld + j], r, j, c.np, c.pd, c.prow0, c.pcol0, L.ld, L.Mp1p) : 0.0;
+}
+// revised form: rho = row r of B^-1, then one sparse product per column -- by this workgroup, or dealt in slices to it and its helpers
+__device__ __forceinline__ void fetch_row_revised(const LpView &L, const BatchView &Bv, const SelCtx &c, const int r)
+{
+    extern __shared__ unsigned char dyn_sel[];
+    __shared__ int s_n, s_late;
+    const int tid = threadIdx.x, NT = (int)blockDim.x, b = c.b, np = c.np, ldt = L.ldt;
+    double *brow_g = c.prow0 + (size_t)np * ldt;
+    // rho also goes to LDS when it fits (ex09: 37 KB): the sparse products below gather from it ~200 000 times per selection
+    double *srho = L.rho_off >= 0 ? reinterpret_cast<double *>(dyn_sel + L.rho_off) : nullptr;
+    for (int i = tid; i < ldt; i += NT) {
+        const double v = i < L.M ? virt_entry_b(c.T0[(size_t)r * ldt + i], r, i, np, c.pd, c.prow0, c.pcol0, ldt, L.Mp1p) : 0.0;
+        brow_g[i] = v;
+        if (srho) srho[i] = v;
+    }
+    __syncthreads();
+    const double *brow = srho ? srho : brow_g;
+    if (L.helpers <= 1) { rev_row_slice(L, brow, c.nh, c.row, 0, 1); return; }
+    // hand the row out in slices (rev_take_slices): rho is in global memory (brow_g), the request goes out, this workgroup takes
+    // slices like everyone else and then waits for the ones others took
+    unsigned long long tf = ((L.probe & 8) && b == 0) ? wall_clock64() : 0ull;
+    int *mb = Bv.hmail + (size_t)b * 8;
+    __threadfence();
+    __syncthreads();
+    phase_mark(L, Bv, b, 8, tf);
+    if (tid == 0) {
+        const int old = __hip_atomic_load(&mb[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int n = ((old >> 8) == L.launch_id ? (old & 0xFF) : 0) + 1;      // (at most 2 * KP requests per launch: far from 0xFF)
+        s_n = n;
+        __hip_atomic_store(&mb[1], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&mb[2], np, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&mb[3], n << 16, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&mb[0], (L.launch_id << 8) | n, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __syncthreads();
+    phase_mark(L, Bv, b, 9, tf);
+    rev_take_slices(L, mb, s_n, brow, c.nh, c.row, ((L.probe & 8) && b == 0) ? &Bv.dbg[13] : nullptr);
+    phase_mark(L, Bv, b, 10, tf);
+    if (tid == 0) {
+        const int ns = rev_nslices(L);
+        long w = 0;
+        while (__hip_atomic_load(&mb[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < ns && ++w < 50000000L) __builtin_amdgcn_s_sleep(2);      // (every slice counted here was taken by a workgroup that is running)
+        s_late = w >= 50000000L;
+    }
+    __syncthreads();
+    phase_mark(L, Bv, b, 11, tf);
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");      // (the slices the others wrote)
+    phase_mark(L, Bv, b, 12, tf);
+    if (s_late) { rev_row_slice(L, brow, c.nh, c.row, 0, 1); __syncthreads(); }      // (never seen; the row is this workgroup's to deliver either way)
+}
+__device__ __forceinline__ void fetch_row(const LpView &L, const BatchView &Bv, const SelCtx &c, const int r)
+{
+    if (!L.rev) fetch_row_tableau(L, c, r); else fetch_row_revised(L, Bv, c, r); __syncthreads();
+}
+__device__ __forceinline__ void fetch_col_tableau(const LpView &L, const SelCtx &c, const int q)
+{
+    for (int i = threadIdx.x; i < L.M; i += (int)blockDim.x) c.pc[i] = virt_entry(c.T0[(size_t)i * L.ld + q], i, q, c.np, c.pd, c.prow0, c.pcol0, L.ld, L.Mp1p);
+}
+// revised form: T[:, q] = -B^-1 K_kq
+__device__ __forceinline__ void fetch_col_revised(const LpView &L, const SelCtx &c, const int q)
+{
+    const int tid = threadIdx.x, NT = (int)blockDim.x, M = L.M, ldt = L.ldt;
+    double *pc = c.pc;
+    const int kq = c.nh[q];
+    const int cb = kq >= M ? L.cptr[kq - M] : 0, ce = kq >= M ? L.cptr[kq - M + 1] : 0;
+    for (int i0 = tid; i0 < M; i0 += 2 * NT) {    // (B^-1 as stored) K_kq: two rows per thread, the gathers of eight non-zeros of each in flight together
+        const int i1 = i0 + NT;
+        const double *B0 = c.T0 + (size_t)i0 * ldt, *B1 = c.T0 + (size_t)(i1 < M ? i1 : i0) * ldt;
+        double v0 = 0.0, v1 = 0.0;
+        if (kq < M) { v0 = B0[kq]; v1 = B1[kq]; }
+        else for (int t0 = cb; t0 < ce; t0 += 8) {
+            double g0[8], g1[8], cv[8];
+#pragma unroll
+            for (int u = 0; u < 8; u++) { const bool in = t0 + u < ce; const int k = in ? L.cidx[t0 + u] : 0; cv[u] = in ? L.cval[t0 + u] : 0.0; g0[u] = B0[k]; g1[u] = B1[k]; }
+#pragma unroll
+            for (int u = 0; u < 8; u++) { v0 = fma(-cv[u], g0[u], v0); v1 = fma(-cv[u], g1[u], v1); }
+        }
+        pc[i0] = v0;
+        if (i1 < M) pc[i1] = v1;
+    }
+    for (int sp = 0; sp < c.np; sp++) {              // ... through the pending pivots, in order
+        __syncthreads();
+        const PivDesc d = c.pd[sp];
+        const double vr = pc[d.r];
+        __syncthreads();
+        for (int i = tid; i < M; i += NT) pc[i] = i == d.r ? -d.p * vr : fma(-c.pcol0[(size_t)sp * L.Mp1p + i], vr, pc[i]);
+    }
+    __syncthreads();
+    for (int i = tid; i < M; i += NT) pc[i] = -pc[i];
+}
+__device__ __forceinline__ void fetch_col(const LpView &L, const SelCtx &c, const int q)
+{
+    if (!L.rev) fetch_col_tableau(L, c, q); else fetch_col_revised(L, c, q); __syncthreads();
+}
+
+// the perturbed reduced costs dp, from the true ones
+__device__ __forceinline__ void apply_perturbation(const LpView &L, const SelCtx &c, double *dp)
+{
+    const int NT = (int)blockDim.x;
+    for (int j = threadIdx.x; j < L.ld; j += NT) {
+        double v = j < L.N ? c.drow[j] : 0.0;
+        if (j < L.N) {
+            const int st = c.nstat[j];
+            const double eps = 5e-7 * L.pert_scale * (1.0 + hash01(c.nh[j]));
+            if (st == NS_L) v = fmax(v, 0.0) + eps;
+            else if (st == NS_U) v = fmin(v, 0.0) - eps;
+        }
+        dp[j] = v;
+    }
+    __syncthreads();
+}
+// The perturbed problem is solved: perturbation off (pf); true when wrong signs of the true reduced costs end this selection (primal steps or bound switches repair them)
+__device__ __forceinline__ bool perturbation_off(const LpView &L, const BatchView &Bv, const SelCtx &c, int &pf)
+{
+    const int tid = threadIdx.x, NT = (int)blockDim.x, b = c.b, N = L.N;
+    int wrong1 = 0, wrongb = 0;
+    for (int j = tid; j < N; j += NT) {
+        const int st = c.nstat[j];
+        const double v = c.drow[j];
+        if ((st == NS_L && v < -TOL_DJ) || (st == NS_U && v > TOL_DJ) || (st == NS_F && fabs(v) > TOL_DJ)) {
+            const int k = c.nh[j];
+            if (st != NS_F && !isinf(LO(L, Bv, b, k)) && !isinf(UP(L, Bv, b, k)) && !L.art[k]) wrongb = 1; else wrong1 = 1;
+        }
+    }
+    wrong1 = __syncthreads_or(wrong1);
+    wrongb = __syncthreads_or(wrongb);
+    pf &= ~PF_PERT;
+    if (tid == 0 && (wrong1 || wrongb)) atomicAdd(&Bv.xstat[3], 1);
+    if (wrong1) {
+        if (tid == 0) { Bv.pflags[b] = pf | PF_PRIMAL; Bv.stall[b] = 0; if (L.trace == b) printf("lp %d it %d perturbation off -> primal clean-up\n", b, Bv.iters[b]); }
+        return true;
+    }
+    if (tid == 0) Bv.pflags[b] = pf;
+    if (wrongb) {
+        for (int j = tid; j < N; j += NT) {
+            const int st = c.nstat[j], k = c.nh[j];
+            const double v = c.drow[j];
+            if (st == NS_L && v < -TOL_DJ) { c.nstat[j] = NS_U; c.xN[j] = UP(L, Bv, b, k); }
+            else if (st == NS_U && v > TOL_DJ) { c.nstat[j] = NS_L; c.xN[j] = LO(L, Bv, b, k); }
+        }
+        if (tid == 0) { Bv.mode[b] = MODE_REFRESH; Bv.verified[b] &= 2; if (L.trace == b) printf("lp %d it %d perturbation off -> bound switches\n", b, Bv.iters[b]); }
+        return true;
+    }
+    return false;
+}
+// Primal simplex step on the true reduced costs (clean-up after a perturbation): true with the pivot (r, q), column in pc, row fetched; false: no pivot
+__device__ __forceinline__ bool primal_step(const LpView &L, const BatchView &Bv, const SelCtx &c, const int pf, const bool bland, double *sv, int *si,
+                                            int &r, int &q, bool &below, double &pstep)
+{
+    const int tid = threadIdx.x, NT = (int)blockDim.x, b = c.b, M = L.M, N = L.N;
+    const double *pc = c.pc;
+    double *beta = c.beta;
+    ValIdx ent{0.0, -1};
+    for (int j = tid; j < N; j += NT) {
+        const int st = c.nstat[j];
+        if (st == NS_S) continue;
+        const double v = c.drow[j];
+        double sc = 0.0;
+        if (st == NS_L) { if (v < -TOL_DJ) sc = -v; }
+        else if (st == NS_U) { if (v > TOL_DJ) sc = v; }
+        else if (fabs(v) > TOL_DJ) sc = fabs(v);
+        if (sc > 0.0) ent = better_max(ent, ValIdx{bland ? (double)(L.M + L.N - c.nh[j]) : sc, j});
+    }
+    ent = block_argmax(ent, sv, si);
+    if (ent.i < 0) {
+        // dual feasible: the dual selection takes over again (it concludes, or repairs what rounding left infeasible)
+        if (tid == 0) { Bv.pflags[b] = pf & ~PF_PRIMAL; Bv.stall[b] = 0; }
+        return false;
+    }
+    if (Bv.iters[b] >= L.maxit) { if (tid == 0) { Bv.status[b] = BSLV_LP_UNDEFINED; Bv.mode[b] = MODE_NONE; } return false; }
+    q = ent.i;
+    const int stq = c.nstat[q], kq = c.nh[q];
+    const double dq = c.drow[q];
+    const double dir = (stq == NS_U || (stq == NS_F && dq > 0.0)) ? -1.0 : 1.0;
+    fetch_col(L, c, q);
+    double cmax = 0.0;
+    for (int i = tid; i < M; i += NT) cmax = fmax(cmax, fabs(pc[i]));
+    cmax = block_max(cmax, sv);
+    const double ptol = TOL_PIV * (1.0 + cmax);
+    const double gap = UP(L, Bv, b, kq) - LO(L, Bv, b, kq);     // inf unless both bounds are finite
+    double tmax = gap;
+    for (int i = tid; i < M; i += NT) {
+        const double a = pc[i] * dir;
+        if (fabs(a) < ptol) continue;
+        const int k = c.bh[i];
+        const double bt = beta[i];
+        if (a > 0) { const double up = UP(L, Bv, b, k); if (!isinf(up)) tmax = fmin(tmax, fmax(up + (bland ? 0.0 : btol(up)) - bt, 0.0) / a); }
+        else { const double lo = LO(L, Bv, b, k); if (!isinf(lo)) tmax = fmin(tmax, fmax(bt - lo + (bland ? 0.0 : btol(lo)), 0.0) / -a); }
+    }
+    tmax = block_min(tmax, sv);
+    if (isinf(tmax)) {
+        if (tid == 0) { Bv.status[b] = BSLV_LP_UNBOUNDED; Bv.mode[b] = MODE_NONE; }
+        return false;
+    }
+    ValIdx lv{0.0, -1};
+    for (int i = tid; i < M; i += NT) {
+        const double a = pc[i] * dir;
+        if (fabs(a) < ptol) continue;
+        const int k = c.bh[i];
+        const double bt = beta[i];
+        if (a > 0) { const double up = UP(L, Bv, b, k); if (!isinf(up) && (up - bt) / a <= tmax) lv = better_max(lv, ValIdx{bland ? (double)(L.M + L.N - k) : a, 2 * i + 1}); }
+        else { const double lo = LO(L, Bv, b, k); if (!isinf(lo) && (bt - lo) / -a <= tmax) lv = better_max(lv, ValIdx{bland ? (double)(L.M + L.N - k) : -a, 2 * i}); }
+    }
+    lv = block_argmax(lv, sv, si);
+    double tstep = INFINITY;
+    if (lv.i >= 0) {
+        const int i = lv.i >> 1, k = c.bh[i];
+        const double a = pc[i] * dir;
+        tstep = fmax(((lv.i & 1) ? UP(L, Bv, b, k) - beta[i] : beta[i] - LO(L, Bv, b, k)) / fabs(a), 0.0);
+    }
+    if (lv.i < 0 || gap <= tstep) {
+        // the entering variable reaches its own other bound first: no pivot
+        __syncthreads();
+        for (int i = tid; i < M; i += NT) beta[i] = fma(pc[i], dir * gap, beta[i]);
+        if (tid == 0) {
+            beta[M] = fma(dq, dir * gap, beta[M]);
+            if (stq == NS_L) { c.nstat[q] = NS_U; c.xN[q] = UP(L, Bv, b, kq); } else { c.nstat[q] = NS_L; c.xN[q] = LO(L, Bv, b, kq); }
+            if (L.trace == b) printf("lp %d it %d primal: column %d (var %d) d %.3e switches bound\n", b, Bv.iters[b], q, kq, dq);
+            Bv.verified[b] &= 2;
+            Bv.iters[b] += 1;
+            atomicAdd(&Bv.xstat[2], 1);
+        }
+        return false;
+    }
+    r = lv.i >> 1;
+    below = !(lv.i & 1);                   // the leaving variable goes to its lower bound
+    pstep = fabs(dq) * tstep / (1.0 + fabs(beta[M]));      // (what the step moves the objective by, relative: the ratio test's tolerance gives a degenerate step a length of 1e-9, not 0)
+    fetch_row(L, Bv, c, r);
+    return true;
+}
+// Bound flipping ratio test: sorted breakpoints of row r; a boxed candidate switches bound (sflag) while the row stays infeasible.  Returns the number of switches (the first of sidx)
+__device__ __forceinline__ int flip_breakpoints(const LpView &L, const BatchView &Bv, const SelCtx &c, const int r, const bool below, const double sgn, const double ptol,
+                                                const double *dwork, const int cap2, double *skey, int *sidx, unsigned char *sflag)
+{
+    __shared__ int s_cnt, s_nboxed, s_stop;
+    const int tid = threadIdx.x, NT = (int)blockDim.x, b = c.b, N = L.N;
+    const double *row = c.row;
+    if (tid == 0) { s_cnt = 0; s_nboxed = 0; s_stop = 0; }
+    for (int j = tid; j < N; j += NT) sflag[j] = 0;
+    __syncthreads();
+    if (cap2 > 0) for (int j = tid; j < N; j += NT) {
+        int st = c.nstat[j];
+        double a = sgn * row[j];
+        if (is_candidate(st, a, ptol)) {
+            const int at = atomicAdd(&s_cnt, 1);
+            skey[at] = fabs(dwork[j]) / fabs(a);
+            sidx[at] = j;
+            const int k = c.nh[j];
+            const double lo = LO(L, Bv, b, k), up = UP(L, Bv, b, k);
+            if (st != NS_F && !isinf(lo) && !isinf(up) && !L.art[k]) atomicAdd(&s_nboxed, 1);
+        }
+    }
+    __syncthreads();
+    const int C = s_cnt;
+    if (s_nboxed == 0) return 0;              // nothing to flip at all
+    int n2 = 2;
+    while (n2 < C) n2 <<= 1;
+    for (int i = C + tid; i < n2; i += NT) { skey[i] = INFINITY; sidx[i] = 0x7fffffff; }
+    __syncthreads();
+    // bitonic sort by (breakpoint, column): the order, and with it every decision below, is unique
+    for (int kk = 2; kk <= n2; kk <<= 1)
+        for (int jj = kk >> 1; jj > 0; jj >>= 1) {
+            for (int i = tid; i < n2; i += NT) {
+                const int x = i ^ jj;
+                if (x > i) {
+                    const double ka = skey[i], kb2 = skey[x];
+                    const int ia = sidx[i], ib = sidx[x];
+                    const bool gt = ka > kb2 || (ka == kb2 && ia > ib);
+                    if (((i & kk) == 0) == gt) { skey[i] = kb2; skey[x] = ka; sidx[i] = ib; sidx[x] = ia; }
+                }
+            }
+            __syncthreads();
+        }
+    if (tid == 0) {
+        // walk the breakpoints
+        const int kb0 = c.bh[r];
+        double slope = below ? LO(L, Bv, b, kb0) - c.beta[r] : c.beta[r] - UP(L, Bv, b, kb0);
+        int k = 0;
+        for (; k < C; k++) {
+            const int j = sidx[k], kv = c.nh[j];
+            const double lo = LO(L, Bv, b, kv), up = UP(L, Bv, b, kv);
+            if (c.nstat[j] == NS_F || isinf(lo) || isinf(up) || L.art[kv]) break;
+            const double dec = (up - lo) * fabs(row[j]);
+            if (slope - dec < 0.0) break;
+            slope -= dec;
+            sflag[j] = 1;
+        }
+        s_stop = k;
+    }
+    __syncthreads();
+    return s_stop;
+}
+// The switches: other bound, other status.  A few: beta follows as a vector update over the nflip columns of the tableau as it is after the pending
+// pivots, and the LP keeps selecting (true).  Many, or the revised form (a column is a product, not a gather): false, the caller asks for MODE_REFRESH.
+// beta is recomputed from the tableau before any status is reported (verified), so the update cannot end in a result.
+__device__ __forceinline__ bool switch_bounds(const LpView &L, const BatchView &Bv, const SelCtx &c, const int r, const int nflip, double *skey, const int *sidx)
+{
+    const int tid = threadIdx.x, NT = (int)blockDim.x, b = c.b, M = L.M;
+    for (int k = tid; k < nflip; k += NT) {
+        const int j = sidx[k], kv = c.nh[j];
+        const double lo = LO(L, Bv, b, kv), up = UP(L, Bv, b, kv);
+        if (c.nstat[j] == NS_L) { c.nstat[j] = NS_U; c.xN[j] = up; skey[k] = up - lo; }
+        else { c.nstat[j] = NS_L; c.xN[j] = lo; skey[k] = lo - up; }
+    }
+    if (!(nflip > 0 && nflip <= FLIP_INCR_MAX && !L.rev)) return false;
+    __syncthreads();
+    for (int i = tid; i <= M; i += NT) {
+        double acc = 0.0;
+        for (int k = 0; k < nflip; k++) {
+            const int j = sidx[k];
+            const double t = i == M ? c.drow[j] : (i == r ? c.row[j] : virt_entry(c.T0[(size_t)i * L.ld + j], i, j, c.np, c.pd, c.prow0, c.pcol0, L.ld, L.Mp1p));
+            acc = fma(t, skey[k], acc);
+        }
+        c.beta[i] += acc;
+    }
+    __syncthreads();
+    return true;
+}
+
 // Workgroup: NT threads; NT_BIG for rows of 1536 columns and more (S-degenerate: 2011, ex09: 36 939) -- an LP's selection is a chain
 // of passes over N entries by ONE workgroup, and four times the threads shorten every pass.
 // ONE selection of LP b by the calling workgroup (every `return` below is taken by the whole workgroup).  Returns false when the LP
 // cannot select again before the next pass over its tableau (finished, waiting for a refresh, KP pivots pending).
 template <bool EXT>
-__device__ bool select_once(const LpView &L, const BatchView &Bv, const int b, const int cap2)
+__device__ __forceinline__ bool select_once(const LpView &L, const BatchView &Bv, const int b, const int cap2)
 {
     __shared__ double sv[NT_BIG / WAVE];
     __shared__ int si[NT_BIG / WAVE];
     const int NT = (int)blockDim.x;
     __shared__ PivDesc s_d;
-    __shared__ int s_cnt, s_nboxed, s_stop;
     extern __shared__ unsigned char dyn_sel[];
     double *skey = reinterpret_cast<double *>(dyn_sel);          // [cap2] breakpoints |d_j| / |alpha_j| of the candidates
     int *sidx = reinterpret_cast<int *>(skey + cap2);             // [cap2] their columns
@@ -574,128 +987,17 @@ __device__ bool select_once(const LpView &L, const BatchView &Bv, const int b, c
     const int np = Bv.npend[b];
     if (np >= KP) return false;                // waits for the pass over its tableau
     const int tid = threadIdx.x;
-    int slot = Bv.dst[b];
-    // the stored tableau of this solve: the parent's slot until the first pass has written its own (see k_init)
-    const double *T0 = L.T + (size_t)(Bv.flushed[b] ? slot : Bv.src[b]) * L.slotT;
-    double *beta = L.beta + (size_t)slot * L.Mp1p;
-    double *xN = L.xN + (size_t)slot * L.ld;
-    int *bh = L.bh + (size_t)slot * L.M, *nh = L.nh + (size_t)slot * L.N;
-    int *nstat = L.nstat + (size_t)slot * L.N, *pos = L.pos + (size_t)slot * (L.M + L.N);
+    const int slot = Bv.dst[b];
+    const SelCtx c = sel_ctx(L, Bv, b, np, slot, Bv.flushed[b] ? slot : Bv.src[b]);
     const int M = L.M, N = L.N, ld = L.ld;
-    const PivDesc *pd = Bv.desc + (size_t)b * KP;
-    const int ldt = L.ldt;
-    double *prow0 = Bv.prow + (size_t)b * KP * ldt;
-    double *pcol0 = Bv.pcol + (size_t)b * KP * L.Mp1p;
-    double *drow = Bv.dcur + (size_t)b * ld;
+    double *const beta = c.beta, *const drow = c.drow, *const row = c.row, *const pc = c.pc;
     double *dwork = drow;                      // the reduced costs the dual ratio test works with
-    // the pivot row as it is after the pending pivots, where k_flush will read it (revised form: k_flush reads the row of B^-1, brow,
-    // from there, and the tableau row lives in a scratch vector of the LP)
-    double *row = L.rev ? Bv.trow + (size_t)b * ld : prow0 + (size_t)np * ld;
-    double *pc = pcol0 + (size_t)np * L.Mp1p;  // the multipliers of the rows (primal selection: first the entering column itself)
-    // row r / column q of the tableau as it is after the pending pivots, by the whole workgroup (barriers inside)
-    auto fetch_row = [&](const int r) {
-        if (!L.rev) {
-            for (int j = tid; j < ld; j += NT) row[j] = j < N ? virt_entry(T0[(size_t)r * ld + j], r, j, np, pd, prow0, pcol0, ld, L.Mp1p) : 0.0;
-        } else {
-            double *brow_g = prow0 + (size_t)np * ldt;
-            // rho also goes to LDS when it fits (ex09: 37 KB): the sparse products below gather from it ~200 000 times per selection
-            double *srho = L.rho_off >= 0 ? reinterpret_cast<double *>(dyn_sel + L.rho_off) : nullptr;
-            for (int c = tid; c < ldt; c += NT) {
-                const double v = c < M ? ((L.probe & 4) ? T0[(size_t)r * ldt + c] : virt_entry_b(T0[(size_t)r * ldt + c], r, c, np, pd, prow0, pcol0, ldt, L.Mp1p)) : 0.0;
-                brow_g[c] = v;
-                if (srho) srho[c] = v;
-            }
-            __syncthreads();
-            const double *brow = srho ? srho : brow_g;
-            if (L.probe & 1) { for (int j = tid; j < ld; j += NT) row[j] = (j < N && nh[j] < M) ? -brow[nh[j]] : (j < N ? 1e-3 : 0.0); __syncthreads(); return; }
-            unsigned long long tf = ((L.probe & 8) && b == 0) ? wall_clock64() : 0ull;
-#define ROW_PHASE(k) do { if ((L.probe & 8) && b == 0) { __syncthreads(); if (tid == 0) { const unsigned long long tn = wall_clock64(); Bv.dbg[k] += tn - tf; tf = tn; } } } while (0)
-            if (L.helpers > 1) {
-                // hand the row out in slices (rev_take_slices): rho is in global memory (brow_g), the request goes out, this workgroup takes
-                // slices like everyone else and then waits for the ones others took
-                int *mb = Bv.hmail + (size_t)b * 8;
-                __threadfence();
-                __syncthreads();
-                ROW_PHASE(8);
-                __shared__ int s_n, s_late;
-                if (tid == 0) {
-                    const int old = __hip_atomic_load(&mb[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    const int n = ((old >> 8) == L.launch_id ? (old & 0xFF) : 0) + 1;      // (at most 2 * KP requests per launch: far from 0xFF)
-                    s_n = n;
-                    __hip_atomic_store(&mb[1], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __hip_atomic_store(&mb[2], np, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __hip_atomic_store(&mb[3], n << 16, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __hip_atomic_store(&mb[0], (L.launch_id << 8) | n, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-                }
-                __syncthreads();
-                ROW_PHASE(9);
-                rev_take_slices(L, mb, s_n, brow, nh, row, ((L.probe & 8) && b == 0) ? &Bv.dbg[13] : nullptr);
-                ROW_PHASE(10);
-                if (tid == 0) {
-                    const int ns = rev_nslices(L);
-                    long w = 0;
-                    while (__hip_atomic_load(&mb[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < ns && ++w < 50000000L) __builtin_amdgcn_s_sleep(2);      // (every slice counted here was taken by a workgroup that is running)
-                    s_late = w >= 50000000L;
-                }
-                __syncthreads();
-                ROW_PHASE(11);
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");      // (the slices the others wrote)
-                ROW_PHASE(12);
-                if (s_late) { rev_row_slice(L, brow, nh, row, 0, 1); __syncthreads(); }      // (never seen; the row is this workgroup's to deliver either way)
-            } else rev_row_slice(L, brow, nh, row, 0, 1);
-        }
-        __syncthreads();
-    };
-    auto fetch_col = [&](const int q) {
-        if (!L.rev) {
-            for (int i = tid; i < M; i += NT) pc[i] = virt_entry(T0[(size_t)i * ld + q], i, q, np, pd, prow0, pcol0, ld, L.Mp1p);
-        } else {
-            const int kq = nh[q];
-            if (L.probe & 2) { for (int i = tid; i < M; i += NT) pc[i] = i == 0 ? 1.0 : 1e-3; __syncthreads(); return; }
-            const int cb = kq >= M ? L.cptr[kq - M] : 0, ce = kq >= M ? L.cptr[kq - M + 1] : 0;
-            for (int i0 = tid; i0 < M; i0 += 2 * NT) {    // (B^-1 as stored) K_kq: two rows per thread, the gathers of eight non-zeros of each in flight together
-                const int i1 = i0 + NT;
-                const double *B0 = T0 + (size_t)i0 * ldt, *B1 = T0 + (size_t)(i1 < M ? i1 : i0) * ldt;
-                double v0 = 0.0, v1 = 0.0;
-                if (kq < M) { v0 = B0[kq]; v1 = B1[kq]; }
-                else for (int t0 = cb; t0 < ce; t0 += 8) {
-                    double g0[8], g1[8], cv[8];
-#pragma unroll
-                    for (int u = 0; u < 8; u++) { const bool in = t0 + u < ce; const int c = in ? L.cidx[t0 + u] : 0; cv[u] = in ? L.cval[t0 + u] : 0.0; g0[u] = B0[c]; g1[u] = B1[c]; }
-#pragma unroll
-                    for (int u = 0; u < 8; u++) { v0 = fma(-cv[u], g0[u], v0); v1 = fma(-cv[u], g1[u], v1); }
-                }
-                pc[i0] = v0;
-                if (i1 < M) pc[i1] = v1;
-            }
-            for (int sp = 0; sp < np; sp++) {              // ... through the pending pivots, in order
-                __syncthreads();
-                const PivDesc d = pd[sp];
-                const double vr = pc[d.r];
-                __syncthreads();
-                for (int i = tid; i < M; i += NT) pc[i] = i == d.r ? -d.p * vr : fma(-pcol0[(size_t)sp * L.Mp1p + i], vr, pc[i]);
-            }
-            __syncthreads();
-            for (int i = tid; i < M; i += NT) pc[i] = -pc[i];      // T[:, q] = -B^-1 K_kq
-        }
-        __syncthreads();
-    };
     int pf = 0;
     if constexpr (EXT) {
         pf = Bv.pflags[b];
         double *dp = Bv.dper + (size_t)b * ld;
         if (pf & PF_PERT_PENDING) {
-            for (int j = tid; j < ld; j += NT) {
-                double v = j < N ? drow[j] : 0.0;
-                if (j < N) {
-                    const int st = nstat[j];
-                    const double eps = 5e-7 * L.pert_scale * (1.0 + hash01(nh[j]));
-                    if (st == NS_L) v = fmax(v, 0.0) + eps;
-                    else if (st == NS_U) v = fmin(v, 0.0) - eps;
-                }
-                dp[j] = v;
-            }
-            __syncthreads();
+            apply_perturbation(L, c, dp);
             pf = (pf & ~PF_PERT_PENDING) | PF_PERT;
             if (tid == 0) { Bv.pflags[b] = pf; atomicAdd(&Bv.xstat[1], 1); }
         }
@@ -708,235 +1010,45 @@ __device__ bool select_once(const LpView &L, const BatchView &Bv, const int b, c
     //  answer -- 2 M pivots, it crawls while there is progress to be made -- so it holds only as long as the steps have length zero)
     const bool bland = (Bv.iters[b] >= L.bland_after || (EXT && (pf & PF_PRIMAL) && Bv.stall[b] >= PRIMAL_STALL)) && !(pf & PF_PERT);     // (perturbed costs break the ties themselves)
     int r = -1, q = -1, nflip = 0;
-    bool incr = false;                       // bound switches of this iteration already carried into beta
-    bool below = false, have_col = false;
+    bool below = false, incr = false;        // incr: bound switches of this iteration already carried into beta
+    const bool primal = EXT && (pf & PF_PRIMAL);
     double pstep = 1.0;                      // length of a primal step (clean-up)
 
-    if (EXT && (pf & PF_PRIMAL)) {
-        // ---- primal simplex step on the true reduced costs (clean-up after a perturbation) ----
-        ValIdx ent{0.0, -1};
-        for (int j = tid; j < N; j += NT) {
-            const int st = nstat[j];
-            if (st == NS_S) continue;
-            const double v = drow[j];
-            double sc = 0.0;
-            if (st == NS_L) { if (v < -TOL_DJ) sc = -v; }
-            else if (st == NS_U) { if (v > TOL_DJ) sc = v; }
-            else if (fabs(v) > TOL_DJ) sc = fabs(v);
-            if (sc > 0.0) ent = better_max(ent, ValIdx{bland ? (double)(L.M + L.N - nh[j]) : sc, j});
-        }
-        ent = block_argmax(ent, sv, si);
-        if (ent.i < 0) {
-            // dual feasible: the dual selection takes over again (it concludes, or repairs what rounding left infeasible)
-            if (tid == 0) { Bv.pflags[b] = pf & ~PF_PRIMAL; Bv.stall[b] = 0; }
-            return true;
-        }
-        if (Bv.iters[b] >= L.maxit) {
-            if (tid == 0) { Bv.status[b] = BSLV_LP_UNDEFINED; Bv.mode[b] = MODE_NONE; }
-            return true;
-        }
-        q = ent.i;
-        const int stq = nstat[q], kq = nh[q];
-        const double dq = drow[q];
-        const double dir = (stq == NS_U || (stq == NS_F && dq > 0.0)) ? -1.0 : 1.0;
-        fetch_col(q);
-        double cmax = 0.0;
-        for (int i = tid; i < M; i += NT) cmax = fmax(cmax, fabs(pc[i]));
-        cmax = block_max(cmax, sv);
-        const double ptol = TOL_PIV * (1.0 + cmax);
-        const double gap = UP(L, Bv, b, kq) - LO(L, Bv, b, kq);     // inf unless both bounds are finite
-        double tmax = gap;
-        for (int i = tid; i < M; i += NT) {
-            const double a = pc[i] * dir;
-            if (fabs(a) < ptol) continue;
-            const int k = bh[i];
-            const double bt = beta[i];
-            if (a > 0) { const double up = UP(L, Bv, b, k); if (!isinf(up)) tmax = fmin(tmax, fmax(up + (bland ? 0.0 : btol(up)) - bt, 0.0) / a); }
-            else { const double lo = LO(L, Bv, b, k); if (!isinf(lo)) tmax = fmin(tmax, fmax(bt - lo + (bland ? 0.0 : btol(lo)), 0.0) / -a); }
-        }
-        tmax = block_min(tmax, sv);
-        if (isinf(tmax)) {
-            if (tid == 0) { Bv.status[b] = BSLV_LP_UNBOUNDED; Bv.mode[b] = MODE_NONE; }
-            return true;
-        }
-        ValIdx lv{0.0, -1};
-        for (int i = tid; i < M; i += NT) {
-            const double a = pc[i] * dir;
-            if (fabs(a) < ptol) continue;
-            const int k = bh[i];
-            const double bt = beta[i];
-            if (a > 0) { const double up = UP(L, Bv, b, k); if (!isinf(up) && (up - bt) / a <= tmax) lv = better_max(lv, ValIdx{bland ? (double)(L.M + L.N - k) : a, 2 * i + 1}); }
-            else { const double lo = LO(L, Bv, b, k); if (!isinf(lo) && (bt - lo) / -a <= tmax) lv = better_max(lv, ValIdx{bland ? (double)(L.M + L.N - k) : -a, 2 * i}); }
-        }
-        lv = block_argmax(lv, sv, si);
-        double tstep = INFINITY;
-        if (lv.i >= 0) {
-            const int i = lv.i >> 1, k = bh[i];
-            const double a = pc[i] * dir;
-            tstep = fmax(((lv.i & 1) ? UP(L, Bv, b, k) - beta[i] : beta[i] - LO(L, Bv, b, k)) / fabs(a), 0.0);
-        }
-        if (lv.i < 0 || gap <= tstep) {
-            // the entering variable reaches its own other bound first: no pivot
-            __syncthreads();
-            for (int i = tid; i < M; i += NT) beta[i] = fma(pc[i], dir * gap, beta[i]);
-            if (tid == 0) {
-                beta[M] = fma(dq, dir * gap, beta[M]);
-                if (stq == NS_L) { nstat[q] = NS_U; xN[q] = UP(L, Bv, b, kq); } else { nstat[q] = NS_L; xN[q] = LO(L, Bv, b, kq); }
-                if (L.trace == b) printf("lp %d it %d primal: column %d (var %d) d %.3e switches bound\n", b, Bv.iters[b], q, kq, dq);
-                Bv.verified[b] &= 2;
-                Bv.iters[b] += 1;
-                atomicAdd(&Bv.xstat[2], 1);
-            }
-            return true;
-        }
-        r = lv.i >> 1;
-        below = !(lv.i & 1);                   // the leaving variable goes to its lower bound
-        pstep = fabs(dq) * tstep / (1.0 + fabs(beta[M]));      // (what the step moves the objective by, relative: the ratio test's tolerance gives a degenerate step a length of 1e-9, not 0)
-        fetch_row(r);
-        have_col = true;
+    if (primal) {
+        if (!primal_step(L, Bv, c, pf, bland, sv, si, r, q, below, pstep)) return true;
     } else {
     // ---- dual simplex step ----
     unsigned long long tk = (L.probe & 8) ? wall_clock64() : 0ull;
-#define SEL_PHASE(k) do { if ((L.probe & 8) && b == 0) { __syncthreads(); if (tid == 0) { const unsigned long long tn = wall_clock64(); Bv.dbg[k] += tn - tk; tk = tn; } } } while (0)
-    // Phase A: leaving row = largest bound violation; id = 2*i + (below ? 1 : 0)
+    // Phase A: the leaving row
     ValIdx best{0.0, -1};
     for (int i = tid; i < M; i += NT) {
-        int k = bh[i];
-        double lo = LO(L, Bv, b, k), up = UP(L, Bv, b, k), bt = beta[i];
-        if (!isinf(lo)) { double v = lo - bt; if (v > btol(lo)) best = better_max(best, ValIdx{bland ? (double)(L.M + L.N - k) : v, 2 * i + 1}); }
-        if (!isinf(up)) { double v = bt - up; if (v > btol(up)) best = better_max(best, ValIdx{bland ? (double)(L.M + L.N - k) : v, 2 * i}); }
+        int k = c.bh[i];
+        best = leave_candidate(best, LO(L, Bv, b, k), UP(L, Bv, b, k), beta[i], k, i, bland, L.M + L.N);
     }
     best = block_argmax(best, sv, si);
     if (best.i < 0) {
         if (EXT && (pf & PF_PERT)) {
-            // the perturbed problem is solved: take the perturbation away and look at the true reduced costs
-            int wrong1 = 0, wrongb = 0;
-            for (int j = tid; j < N; j += NT) {
-                const int st = nstat[j];
-                const double v = drow[j];
-                if ((st == NS_L && v < -TOL_DJ) || (st == NS_U && v > TOL_DJ) || (st == NS_F && fabs(v) > TOL_DJ)) {
-                    const int k = nh[j];
-                    if (st != NS_F && !isinf(LO(L, Bv, b, k)) && !isinf(UP(L, Bv, b, k)) && !L.art[k]) wrongb = 1; else wrong1 = 1;
-                }
-            }
-            wrong1 = __syncthreads_or(wrong1);
-            wrongb = __syncthreads_or(wrongb);
-            pf &= ~PF_PERT;
-            if (tid == 0 && (wrong1 || wrongb)) atomicAdd(&Bv.xstat[3], 1);
-            if (wrong1) {
-                if (tid == 0) { Bv.pflags[b] = pf | PF_PRIMAL; Bv.stall[b] = 0; if (L.trace == b) printf("lp %d it %d perturbation off -> primal clean-up\n", b, Bv.iters[b]); }
-                return true;
-            }
-            if (tid == 0) Bv.pflags[b] = pf;
-            if (wrongb) {
-                for (int j = tid; j < N; j += NT) {
-                    const int st = nstat[j], k = nh[j];
-                    const double v = drow[j];
-                    if (st == NS_L && v < -TOL_DJ) { nstat[j] = NS_U; xN[j] = UP(L, Bv, b, k); }
-                    else if (st == NS_U && v > TOL_DJ) { nstat[j] = NS_L; xN[j] = LO(L, Bv, b, k); }
-                }
-                if (tid == 0) { Bv.mode[b] = MODE_REFRESH; Bv.verified[b] &= 2; if (L.trace == b) printf("lp %d it %d perturbation off -> bound switches\n", b, Bv.iters[b]); }
-                return true;
-            }
+            if (perturbation_off(L, Bv, c, pf)) return true;
             dwork = drow;
         }
-        // recompute beta from scratch before concluding -- unless this solve made only a few pivots since k_init computed
-        // it from scratch: the rank-1 updates of beta then carry ~1e-15 of error against tolerances of 1e-9, and the
-        // refresh is a full read of the tableau (4 MB per LP on S-mid)
-        // (Not when the solve started on an artificial bound: values of 1e7 leave rounding debris of 1e-9 in beta.)
-        if (!(Bv.verified[b] & 1) && (Bv.iters[b] > REFRESH_AFTER || (Bv.verified[b] & 2))) {
-            if (tid == 0) Bv.mode[b] = MODE_REFRESH;          // k_flush applies what is pending and recomputes beta
-            return true;
-        }
-        // optimal for the bounded problem; unbounded if an artificial bound is active
-        double flag = 0.0;
-        for (int j = tid; j < N; j += NT) {
-            int st = nstat[j];
-            unsigned char a = L.art[nh[j]];
-            if (((st == NS_L && (a & 1)) || (st == NS_U && (a & 2))) && fabs(drow[j]) > TOL_DJ) flag = 1.0;
-        }
-        flag = block_max(flag, sv);
-        if (tid == 0) { Bv.status[b] = flag > 0.0 ? BSLV_LP_UNBOUNDED : BSLV_LP_OPTIMAL; Bv.mode[b] = MODE_NONE; }
+        conclude_optimal(L, Bv, c, Bv.iters[b], Bv.verified[b], NT, sv);
         return true;
     }
-    if (Bv.iters[b] >= L.maxit) {
-        if (tid == 0) { Bv.status[b] = BSLV_LP_UNDEFINED; Bv.mode[b] = MODE_NONE; }
-        return true;
-    }
-    r = best.i >> 1;
-    below = best.i & 1;
+    if (Bv.iters[b] >= L.maxit) { if (tid == 0) { Bv.status[b] = BSLV_LP_UNDEFINED; Bv.mode[b] = MODE_NONE; } return true; }
+    r = best.i >> 1; below = best.i & 1;
     const double sgn = below ? 1.0 : -1.0;
-    SEL_PHASE(0);
-    fetch_row(r);
-    SEL_PHASE(1);
+    phase_mark(L, Bv, b, 0, tk);
+    fetch_row(L, Bv, c, r);
+    phase_mark(L, Bv, b, 1, tk);
 
     // pass 0: row scale for the relative pivot tolerance
     double rmax = 0.0;
     for (int j = tid; j < N; j += NT) rmax = fmax(rmax, fabs(row[j]));
     rmax = block_max(rmax, sv);
     const double ptol = TOL_PIV * (1.0 + rmax);
-    if constexpr (EXT) {
-        // candidates with their breakpoints; anything to flip at all?
-        if (tid == 0) { s_cnt = 0; s_nboxed = 0; s_stop = 0; }
-        for (int j = tid; j < N; j += NT) sflag[j] = 0;
-        __syncthreads();
-        if (cap2 > 0) for (int j = tid; j < N; j += NT) {
-            int st = nstat[j];
-            if (st == NS_S) continue;
-            double a = sgn * row[j];
-            if (fabs(a) < ptol) continue;
-            if ((a > 0 && (st == NS_L || st == NS_F)) || (a < 0 && (st == NS_U || st == NS_F))) {
-                const int at = atomicAdd(&s_cnt, 1);
-                skey[at] = fabs(dwork[j]) / fabs(a);
-                sidx[at] = j;
-                const int k = nh[j];
-                const double lo = LO(L, Bv, b, k), up = UP(L, Bv, b, k);
-                if (st != NS_F && !isinf(lo) && !isinf(up) && !L.art[k]) atomicAdd(&s_nboxed, 1);
-            }
-        }
-        __syncthreads();
-        const int C = s_cnt;
-        if (s_nboxed > 0) {
-            int n2 = 2;
-            while (n2 < C) n2 <<= 1;
-            for (int i = C + tid; i < n2; i += NT) { skey[i] = INFINITY; sidx[i] = 0x7fffffff; }
-            __syncthreads();
-            // bitonic sort by (breakpoint, column): the order, and with it every decision below, is unique
-            for (int kk = 2; kk <= n2; kk <<= 1)
-                for (int jj = kk >> 1; jj > 0; jj >>= 1) {
-                    for (int i = tid; i < n2; i += NT) {
-                        const int x = i ^ jj;
-                        if (x > i) {
-                            const double ka = skey[i], kb2 = skey[x];
-                            const int ia = sidx[i], ib = sidx[x];
-                            const bool gt = ka > kb2 || (ka == kb2 && ia > ib);
-                            if (((i & kk) == 0) == gt) { skey[i] = kb2; skey[x] = ka; sidx[i] = ib; sidx[x] = ia; }
-                        }
-                    }
-                    __syncthreads();
-                }
-            if (tid == 0) {
-                // walk the breakpoints: a boxed candidate switches bound while the row stays infeasible after its switch
-                const int kb0 = bh[r];
-                double slope = below ? LO(L, Bv, b, kb0) - beta[r] : beta[r] - UP(L, Bv, b, kb0);
-                int k = 0;
-                for (; k < C; k++) {
-                    const int j = sidx[k], kv = nh[j];
-                    const double lo = LO(L, Bv, b, kv), up = UP(L, Bv, b, kv);
-                    if (nstat[j] == NS_F || isinf(lo) || isinf(up) || L.art[kv]) break;
-                    const double dec = (up - lo) * fabs(row[j]);
-                    if (slope - dec < 0.0) break;
-                    slope -= dec;
-                    sflag[j] = 1;
-                }
-                s_stop = k;
-            }
-            __syncthreads();
-            nflip = s_stop;
-        }
-    }
+    if constexpr (EXT) nflip = flip_breakpoints(L, Bv, c, r, below, sgn, ptol, dwork, cap2, skey, sidx, sflag);
     // pass 1: Harris bound on the dual step
-    SEL_PHASE(2);
+    phase_mark(L, Bv, b, 2, tk);
     // (both passes fetch FOUR columns per thread and iteration with all loads issued first: on wide problems -- ex09: 37 000 columns,
     // 36 per thread -- a column after the other, its reduced cost loaded behind two branches, was a chain of ~100 memory latencies;
     // min and the (value, index) arg-max do not depend on the order)
@@ -948,28 +1060,16 @@ __device__ bool select_once(const LpView &L, const BatchView &Bv, const int b, c
         for (int u = 0; u < PU; u++) {
             const int j = j0 + u * NT;
             const bool in = j < N;
-            stv[u] = in ? nstat[j] : NS_S; av[u] = in ? sgn * row[j] : 0.0; dv[u] = in ? dwork[j] : 0.0;
+            stv[u] = in ? c.nstat[j] : NS_S; av[u] = in ? sgn * row[j] : 0.0; dv[u] = in ? dwork[j] : 0.0;
             skip[u] = !in || (EXT && sflag[in ? j : 0]);
         }
 #pragma unroll
-        for (int u = 0; u < PU; u++) {
-            const int st = stv[u];
-            const double a = av[u];
-            if (skip[u] || st == NS_S || fabs(a) < ptol) continue;
-            if ((a > 0 && (st == NS_L || st == NS_F)) || (a < 0 && (st == NS_U || st == NS_F)))
-                th = fmin(th, (fabs(dv[u]) + (bland ? 0.0 : TOL_DJ)) / fabs(a));
-        }
+        for (int u = 0; u < PU; u++)
+            if (!skip[u] && is_candidate(stv[u], av[u], ptol)) th = fmin(th, harris_key(dv[u], av[u], bland));
     }
     th = block_min(th, sv);
-    SEL_PHASE(3);
-    if (isinf(th)) {                      // no entering candidate: primal infeasible ...
-        if (!(Bv.verified[b] & 1)) {      // ... unless the violation is rounding debris in beta: recompute it first
-            if (tid == 0) Bv.mode[b] = MODE_REFRESH;
-            return true;
-        }
-        if (tid == 0) { Bv.status[b] = BSLV_LP_INFEASIBLE; Bv.mode[b] = MODE_NONE; }
-        return true;
-    }
+    phase_mark(L, Bv, b, 3, tk);
+    if (isinf(th)) { conclude_infeasible(Bv, b, Bv.verified[b]); return true; }
     // pass 2: largest |pivot| within the bound
     ValIdx piv{0.0, -1};
     for (int j0 = tid; j0 < N; j0 += PU * NT) {
@@ -978,62 +1078,28 @@ __device__ bool select_once(const LpView &L, const BatchView &Bv, const int b, c
         for (int u = 0; u < PU; u++) {
             const int j = j0 + u * NT;
             const bool in = j < N;
-            stv[u] = in ? nstat[j] : NS_S; av[u] = in ? sgn * row[j] : 0.0; dv[u] = in ? dwork[j] : 0.0;
+            stv[u] = in ? c.nstat[j] : NS_S; av[u] = in ? sgn * row[j] : 0.0; dv[u] = in ? dwork[j] : 0.0;
             skip[u] = !in || (EXT && sflag[in ? j : 0]);
         }
 #pragma unroll
         for (int u = 0; u < PU; u++) {
-            const int st = stv[u], j = j0 + u * NT;
-            const double a = av[u];
-            if (skip[u] || st == NS_S || fabs(a) < ptol) continue;
-            if ((a > 0 && (st == NS_L || st == NS_F)) || (a < 0 && (st == NS_U || st == NS_F)))
-                if (fabs(dv[u]) / fabs(a) <= th) piv = better_max(piv, ValIdx{bland ? (double)(L.M + L.N - nh[j]) : fabs(a), j});
+            const int j = j0 + u * NT;
+            if (!skip[u] && is_candidate(stv[u], av[u], ptol) && within_bound(dv[u], av[u], th))
+                piv = better_max(piv, ValIdx{bland ? (double)(L.M + L.N - c.nh[j]) : fabs(av[u]), j});
         }
     }
     piv = block_argmax(piv, sv, si);
-    SEL_PHASE(4);
+    phase_mark(L, Bv, b, 4, tk);
     q = piv.i;
-    if constexpr (EXT) {
-        // the switches: other bound, other status.  beta no longer matches xN: this pivot is applied at once and beta
-        // recomputed from the new tableau (MODE_REFRESH below), before the LP selects again
-        for (int k = tid; k < nflip; k += NT) {
-            const int j = sidx[k], kv = nh[j];
-            const double lo = LO(L, Bv, b, kv), up = UP(L, Bv, b, kv);
-            if (nstat[j] == NS_L) { nstat[j] = NS_U; xN[j] = up; skey[k] = up - lo; }
-            else { nstat[j] = NS_L; xN[j] = lo; skey[k] = lo - up; }
-        }
-        // A few switches: beta follows them as a vector update, beta_i += sum_k T_i,j(k) * delta_k over the columns j(k) of the
-        // tableau as it is after the pending pivots (row M = the reduced costs, row r = the row at hand) -- nflip strided column
-        // reads instead of a pass over the whole tableau, and the LP keeps selecting (up to KP pivots per pass as without
-        // switches).  Many switches (a cold start walks hundreds of breakpoints): the pass with MODE_REFRESH as before.
-        // beta is recomputed from the tableau before any status is reported (verified), so the update cannot end in a result.
-        if (nflip > 0 && nflip <= FLIP_INCR_MAX && !L.rev) {      // (revised form: a column of the tableau is a product, not a gather -- the refresh pass)
-            __syncthreads();
-            for (int i = tid; i <= M; i += NT) {
-                double acc = 0.0;
-                for (int k = 0; k < nflip; k++) {
-                    const int j = sidx[k];
-                    const double t = i == M ? drow[j] : (i == r ? row[j] : virt_entry(T0[(size_t)i * ld + j], i, j, np, pd, prow0, pcol0, ld, L.Mp1p));
-                    acc = fma(t, skey[k], acc);
-                }
-                beta[i] += acc;
-            }
-            incr = true;
-            __syncthreads();
-        }
+    if constexpr (EXT) incr = switch_bounds(L, Bv, c, r, nflip, skey, sidx);
     }
-    }
-    bool col_ready = have_col;                                       // pc[] holds the entering column (primal steps fetch it first)
+    bool col_ready = primal;                                         // pc[] holds the entering column (primal steps fetch it first)
     unsigned long long tk2 = (L.probe & 8) ? wall_clock64() : 0ull;
-    if (L.rev && !col_ready) { fetch_col(q); col_ready = true; }    // (the tableau form gathers its column in Phase D)
-    if ((L.probe & 8) && b == 0) { __syncthreads(); if (tid == 0) { const unsigned long long tn = wall_clock64(); Bv.dbg[5] += tn - tk2; tk2 = tn; } }
+    if (L.rev && !col_ready) { fetch_col(L, c, q); col_ready = true; }    // (the tableau form gathers its column in Phase D)
+    phase_mark(L, Bv, b, 5, tk2);
     // Phase C: the descriptor, the basis heads
     if (tid == 0) {
-        int kb = bh[r], kn = nh[q];
-        double lo = LO(L, Bv, b, kb), up = UP(L, Bv, b, kb);
-        double target = below ? lo : up;
-        double trq = row[q];
-        double br = beta[r];
+        const double trq = row[q];
         // revised form: the pivot element comes out of TWO products -- rho K_q (the row) and the column B^-1 K_q -- which agree as long as
         // B^-1 is accurate.  Nothing refactorises it; when the two drift apart the LP is given up as UNDEFINED and the caller's retry
         // (bslv_lp.c:222-227: from the standard basis, an exact identity) takes over instead of a solve on a corrupted inverse
@@ -1042,36 +1108,17 @@ __device__ bool select_once(const LpView &L, const BatchView &Bv, const int b, c
             if (L.trace == b) printf("lp %d it %d: pivot element from the row %.17g, from the column %.17g: B^-1 has drifted\n", b, Bv.iters[b], trq, pc[r]);
             s_d.r = -1;
         } else {
-        PivDesc d;
-        d.r = r; d.q = q; d.p = 1.0 / trq;
-        d.pbeta = br - target;
-        d.enter_val = xN[q] + (target - br) / trq;
-        Bv.desc[(size_t)b * KP + np] = d;
-        s_d = d;
-        bh[r] = kn; nh[q] = kb;
-        pos[kn] = r; pos[kb] = -1 - q;
-        if (lo == up) { nstat[q] = NS_S; xN[q] = lo; }
-        else if (below) { nstat[q] = NS_L; xN[q] = lo; }
-        else { nstat[q] = NS_U; xN[q] = up; }
-        if (L.trace == b && (Bv.iters[b] < 300 || Bv.iters[b] % 997 == 0)) printf("lp %d it %d%s r %d (var %d, %s by %.3e) q %d (var %d) alpha %.3e d %.3e step %.3e flips %d obj %.12g%s%s\n", b, Bv.iters[b], have_col ? " primal" : "", r, kb, below ? "below" : "above",
-                                 below ? lo - br : br - up, q, kn, trq, dwork[q], fabs(dwork[q] / trq), nflip, beta[M], bland ? " bland" : "", (pf & PF_PERT) ? " perturbed" : "");
-        if constexpr (EXT) {
-            if (nflip > 0) atomicAdd(&Bv.xstat[0], 1);
-            if (incr) atomicAdd(&Bv.xstat[4], 1);
-            if (have_col) { atomicAdd(&Bv.xstat[2], 1); Bv.stall[b] = pstep <= 1e-7 ? Bv.stall[b] + 1 : 0; }      // (streak of degenerate steps of this primal clean-up)
-            if (!have_col) {
-                // dual degenerate stalling: perturb the costs from the next selection on
-                int stl = fabs(dwork[q] / trq) <= 1e-11 ? Bv.stall[b] + 1 : 0;
-                if (stl >= L.stall_limit && !(pf & PF_PERT) && (pf >> PF_USES_SHIFT) < PERT_MAX_USES) {
-                    Bv.pflags[b] = (pf | PF_PERT_PENDING) + (1 << PF_USES_SHIFT);
-                    stl = 0;
+            s_d = commit_pivot(L, Bv, c, r, q, below, bland, Bv.iters[b], Bv.verified[b], (nflip > 0 && !incr) ? MODE_REFRESH : MODE_PIVOT, dwork, primal, nflip, pf & PF_PERT);
+            if constexpr (EXT) {
+                if (nflip > 0) atomicAdd(&Bv.xstat[0], 1);
+                if (incr) atomicAdd(&Bv.xstat[4], 1);
+                if (primal) { atomicAdd(&Bv.xstat[2], 1); Bv.stall[b] = pstep <= 1e-7 ? Bv.stall[b] + 1 : 0; }      // (streak of degenerate steps of this primal clean-up)
+                else {      // dual degenerate stalling: perturb the costs from the next selection on
+                    int stl = fabs(dwork[q] / trq) <= 1e-11 ? Bv.stall[b] + 1 : 0;
+                    if (stl >= L.stall_limit && !(pf & PF_PERT) && (pf >> PF_USES_SHIFT) < PERT_MAX_USES) { Bv.pflags[b] = (pf | PF_PERT_PENDING) + (1 << PF_USES_SHIFT); stl = 0; }
+                    Bv.stall[b] = stl;
                 }
-                Bv.stall[b] = stl;
             }
-        }
-        Bv.mode[b] = (nflip > 0 && !incr) ? MODE_REFRESH : MODE_PIVOT;
-        Bv.verified[b] &= 2;
-        Bv.iters[b] += 1;
         }
     }
     __syncthreads();
@@ -1080,7 +1127,7 @@ __device__ bool select_once(const LpView &L, const BatchView &Bv, const int b, c
     // Phase D: the entering column as it is after the pending pivots -> multipliers of all rows, beta; the reduced-cost row
     for (int i = tid; i <= M; i += NT) {
         if (i == r) { pc[i] = 0.0; beta[i] = d.enter_val; continue; }
-        const double f = (i == M ? drow[q] : (col_ready ? pc[i] : virt_entry(T0[(size_t)i * ld + q], i, q, np, pd, prow0, pcol0, ld, L.Mp1p))) * d.p;
+        const double f = (i == M ? drow[q] : (col_ready ? pc[i] : virt_entry(c.T0[(size_t)i * ld + q], i, q, np, c.pd, c.prow0, c.pcol0, ld, L.Mp1p))) * d.p;
         pc[i] = f;
         beta[i] = fma(-f, d.pbeta, beta[i]);
     }
@@ -1098,14 +1145,12 @@ __device__ bool select_once(const LpView &L, const BatchView &Bv, const int b, c
         }
     }
     if (tid == 0) Bv.npend[b] = np + 1;
-    if ((L.probe & 8) && b == 0) { __syncthreads(); if (tid == 0) { Bv.dbg[6] += wall_clock64() - tk2; Bv.dbg[7] += 1; } }
+    phase_mark(L, Bv, b, 6, tk2);
+    if ((L.probe & 8) && b == 0 && tid == 0) Bv.dbg[7] += 1;
     return true;
 }
 // ---- select_once<false> of the tableau form with a pivot's row and column state kept on chip (k_select_cached) ----
-// A selection by select_once is a chain of dependent trips to global memory for data that never leaves the workgroup: the pivot row is
-// written to prow and read back by pass 0, both Harris passes and the reduced-cost update, each with nstat and the reduced costs again;
-// virt_entry loads a pending pivot's descriptor, branches on it and only then loads the row / multiplier entry, pivot after pivot, for
-// every entry of the row and of the entering column.  Here
+// (select_once goes to global memory for every row entry, status and reduced cost in each pass, and per pending pivot in virt_entry: DESIGN 4e, 4b.)  Here
 //  * thread tid owns the columns tid + u NT, u < CPT, from the row fetch to the reduced-cost update: row entry, reduced cost and status
 //    stay in registers; whether a column is a candidate (status, sign, pivot tolerance) is decided once; the row goes to prow once
 //    (k_flush reads it there) and the reduced costs to dcur once;
@@ -1113,18 +1158,15 @@ __device__ bool select_once(const LpView &L, const BatchView &Bv, const int b, c
 //    (pcol[s][r] for the row, prow[s][q] for the column) as soon as r / q is known, and the per-entry loads of ALL pending pivots
 //    (and of all owned columns / four rows) are issued before the first is used;
 //  * the entering column's loads are in flight while thread 0 writes the descriptor and the basis heads.
-// Every entry goes through the same operations in the same order as virt_entry applies them, every reduction is the same min or
-// (value, index) arg-max: no pivot and no bit of a result differs from select_once (tests/test_lp_select_cache_gpu.py).
+// Same helpers, same order of operations, same reductions as select_once: no pivot and no bit differs (tests/test_lp_select_cache_gpu.py).
 // For workgroups of NT threads and N <= CPT * NT; everything else (1024 threads, extended selection, revised form) stays with select_once.
 template <int CPT>
-__device__ bool select_once_cached(const LpView &L, const BatchView &Bv, const int b)
+__device__ __forceinline__ bool select_once_cached(const LpView &L, const BatchView &Bv, const int b)
 {
-    __shared__ double sv[NT / WAVE];
-    __shared__ int si[NT / WAVE];
+    __shared__ double sv[NT / WAVE]; __shared__ int si[NT / WAVE];
     __shared__ PivDesc s_pd[KP];             // the pending pivots
     __shared__ double s_mul[KP];             // of pending pivot s: pcol[s][r] while the row is built, prow[s][q] for the column
-    __shared__ PivDesc s_d;
-    __shared__ double s_fM;
+    __shared__ PivDesc s_d; __shared__ double s_fM;
     constexpr int RU = 4;                    // rows per thread in flight
     const int tid = threadIdx.x;
     // (one trip for everything the LP's state decides)
@@ -1132,67 +1174,35 @@ __device__ bool select_once_cached(const LpView &L, const BatchView &Bv, const i
     const int iters = Bv.iters[b], verified = Bv.verified[b];
     if (status != ST_RUNNING || mode == MODE_REFRESH) return false;
     if (np >= KP) return false;                // waits for the pass over its tableau
-    const double *T0 = L.T + (size_t)(flushed ? slot : srcslot) * L.slotT;
-    double *beta = L.beta + (size_t)slot * L.Mp1p;
-    double *xN = L.xN + (size_t)slot * L.ld;
-    int *bh = L.bh + (size_t)slot * L.M, *nh = L.nh + (size_t)slot * L.N;
-    int *nstat = L.nstat + (size_t)slot * L.N, *pos = L.pos + (size_t)slot * (L.M + L.N);
+    const SelCtx c = sel_ctx(L, Bv, b, np, slot, flushed ? slot : srcslot);
     const int M = L.M, N = L.N, ld = L.ld, Mp1p = L.Mp1p;
-    const double *prow0 = Bv.prow + (size_t)b * KP * ld;
-    const double *pcol0 = Bv.pcol + (size_t)b * KP * Mp1p;
-    double *drow = Bv.dcur + (size_t)b * ld;
-    double *row = Bv.prow + (size_t)b * KP * ld + (size_t)np * ld;
-    double *pc = Bv.pcol + (size_t)b * KP * Mp1p + (size_t)np * Mp1p;
-    if (tid < np) s_pd[tid] = Bv.desc[(size_t)b * KP + tid];       // (read after the barriers of Phase A's reduction)
+    const double *const T0 = c.T0, *const prow0 = c.prow0, *const pcol0 = c.pcol0;
+    double *const beta = c.beta, *const drow = c.drow, *const row = c.row, *const pc = c.pc;
+    if (tid < np) s_pd[tid] = c.pd[tid];       // (read after the barriers of Phase A's reduction)
     const bool bland = iters >= L.bland_after;
     unsigned long long tk = (L.probe & 8) ? wall_clock64() : 0ull;
 
-    // Phase A: leaving row = largest bound violation; id = 2*i + (below ? 1 : 0)
+    // Phase A: the leaving row
     ValIdx best{0.0, -1};
     for (int i0 = tid; i0 < M; i0 += RU * NT) {
         int kv[RU]; double lov[RU], upv[RU], btv[RU];
 #pragma unroll
-        for (int u = 0; u < RU; u++) { const int i = i0 + u * NT; kv[u] = i < M ? bh[i] : -1; btv[u] = i < M ? beta[i] : 0.0; }
+        for (int u = 0; u < RU; u++) { const int i = i0 + u * NT; kv[u] = i < M ? c.bh[i] : -1; btv[u] = i < M ? beta[i] : 0.0; }
 #pragma unroll
         for (int u = 0; u < RU; u++) { lov[u] = kv[u] >= 0 ? LO(L, Bv, b, kv[u]) : -INFINITY; upv[u] = kv[u] >= 0 ? UP(L, Bv, b, kv[u]) : INFINITY; }
 #pragma unroll
-        for (int u = 0; u < RU; u++) {
-            const int i = i0 + u * NT, k = kv[u];
-            const double lo = lov[u], up = upv[u], bt = btv[u];
-            if (!isinf(lo)) { double v = lo - bt; if (v > btol(lo)) best = better_max(best, ValIdx{bland ? (double)(M + N - k) : v, 2 * i + 1}); }
-            if (!isinf(up)) { double v = bt - up; if (v > btol(up)) best = better_max(best, ValIdx{bland ? (double)(M + N - k) : v, 2 * i}); }
-        }
+        for (int u = 0; u < RU; u++) best = leave_candidate(best, lov[u], upv[u], btv[u], kv[u], i0 + u * NT, bland, M + N);
     }
     best = block_argmax(best, sv, si);
-    if (best.i < 0) {
-        // (as select_once: beta recomputed before concluding unless it is fresh; optimal, or unbounded on an active artificial bound)
-        if (!(verified & 1) && (iters > REFRESH_AFTER || (verified & 2))) {
-            if (tid == 0) Bv.mode[b] = MODE_REFRESH;
-            return true;
-        }
-        double flag = 0.0;
-        for (int j = tid; j < N; j += NT) {
-            int st = nstat[j];
-            unsigned char a = L.art[nh[j]];
-            if (((st == NS_L && (a & 1)) || (st == NS_U && (a & 2))) && fabs(drow[j]) > TOL_DJ) flag = 1.0;
-        }
-        flag = block_max(flag, sv);
-        if (tid == 0) { Bv.status[b] = flag > 0.0 ? BSLV_LP_UNBOUNDED : BSLV_LP_OPTIMAL; Bv.mode[b] = MODE_NONE; }
-        return true;
-    }
-    if (iters >= L.maxit) {
-        if (tid == 0) { Bv.status[b] = BSLV_LP_UNDEFINED; Bv.mode[b] = MODE_NONE; }
-        return true;
-    }
-    const int r = best.i >> 1;
-    const bool below = best.i & 1;
+    if (best.i < 0) { conclude_optimal(L, Bv, c, iters, verified, NT, sv); return true; }
+    if (iters >= L.maxit) { if (tid == 0) { Bv.status[b] = BSLV_LP_UNDEFINED; Bv.mode[b] = MODE_NONE; } return true; }
+    const int r = best.i >> 1; const bool below = best.i & 1;
     const double sgn = below ? 1.0 : -1.0;
-    SEL_PHASE(0);
+    phase_mark(L, Bv, b, 0, tk);
 
     // the pivot row as it is after the pending pivots: stored entry, the pending rows' entries, status and reduced cost of every owned
     // column in one round of loads
-    double rowv[CPT], dv[CPT];
-    int stv[CPT];
+    double rowv[CPT], dv[CPT]; int stv[CPT];
     {
         double t0v[CPT], pr[KP - 1][CPT];
 #pragma unroll
@@ -1200,7 +1210,7 @@ __device__ bool select_once_cached(const LpView &L, const BatchView &Bv, const i
             const int j = tid + u * NT;
             const bool in = j < N;
             t0v[u] = in ? T0[(size_t)r * ld + j] : 0.0;
-            stv[u] = in ? nstat[j] : NS_S;
+            stv[u] = in ? c.nstat[j] : NS_S;
             dv[u] = in ? drow[j] : 0.0;
 #pragma unroll
             for (int s = 0; s < KP - 1; s++) pr[s][u] = (in && s < np) ? prow0[(size_t)s * ld + j] : 0.0;
@@ -1215,15 +1225,14 @@ __device__ bool select_once_cached(const LpView &L, const BatchView &Bv, const i
             for (int s = 0; s < KP - 1; s++) {
                 if (s < np) {
                     const PivDesc d = s_pd[s];
-                    if (r == d.r) v = j == d.q ? d.p : -pr[s][u] * d.p;
-                    else { const double f = s_mul[s]; v = j == d.q ? f : fma(-f, pr[s][u], v); }
+                    v = apply_pending(v, r == d.r, j == d.q, d.p, s_mul[s], pr[s][u]);
                 }
             }
             rowv[u] = j < N ? v : 0.0;
             if (j < ld) row[j] = rowv[u];
         }
     }
-    SEL_PHASE(1);
+    phase_mark(L, Bv, b, 1, tk);
 
     // pass 0: row scale for the relative pivot tolerance
     double rmax = 0.0;
@@ -1231,27 +1240,19 @@ __device__ bool select_once_cached(const LpView &L, const BatchView &Bv, const i
     for (int u = 0; u < CPT; u++) if (tid + u * NT < N) rmax = fmax(rmax, fabs(rowv[u]));
     rmax = block_max(rmax, sv);             // (its barriers also order the reads of s_mul above before the next write below)
     const double ptol = TOL_PIV * (1.0 + rmax);
-    SEL_PHASE(2);
+    phase_mark(L, Bv, b, 2, tk);
     // the candidates, decided once; pass 1: Harris bound on the dual step
     bool cand[CPT];
     double th = INFINITY;
 #pragma unroll
     for (int u = 0; u < CPT; u++) {
-        const int st = stv[u];
         const double a = sgn * rowv[u];
-        cand[u] = tid + u * NT < N && st != NS_S && !(fabs(a) < ptol) && ((a > 0 && (st == NS_L || st == NS_F)) || (a < 0 && (st == NS_U || st == NS_F)));
-        if (cand[u]) th = fmin(th, (fabs(dv[u]) + (bland ? 0.0 : TOL_DJ)) / fabs(a));
+        cand[u] = tid + u * NT < N && is_candidate(stv[u], a, ptol);
+        if (cand[u]) th = fmin(th, harris_key(dv[u], a, bland));
     }
     th = block_min(th, sv);
-    SEL_PHASE(3);
-    if (isinf(th)) {                      // no entering candidate: primal infeasible ...
-        if (!(verified & 1)) {            // ... unless the violation is rounding debris in beta: recompute it first
-            if (tid == 0) Bv.mode[b] = MODE_REFRESH;
-            return true;
-        }
-        if (tid == 0) { Bv.status[b] = BSLV_LP_INFEASIBLE; Bv.mode[b] = MODE_NONE; }
-        return true;
-    }
+    phase_mark(L, Bv, b, 3, tk);
+    if (isinf(th)) { conclude_infeasible(Bv, b, verified); return true; }
     // pass 2: largest |pivot| within the bound
     ValIdx piv{0.0, -1};
     if (bland) {
@@ -1259,17 +1260,17 @@ __device__ bool select_once_cached(const LpView &L, const BatchView &Bv, const i
         for (int u = 0; u < CPT; u++) {
             const int j = tid + u * NT;
             const double a = sgn * rowv[u];
-            if (cand[u] && fabs(dv[u]) / fabs(a) <= th) piv = better_max(piv, ValIdx{(double)(M + N - nh[j]), j});
+            if (cand[u] && within_bound(dv[u], a, th)) piv = better_max(piv, ValIdx{(double)(M + N - c.nh[j]), j});
         }
     } else {
 #pragma unroll
         for (int u = 0; u < CPT; u++) {
             const double a = sgn * rowv[u];
-            if (cand[u] && fabs(dv[u]) / fabs(a) <= th) piv = better_max(piv, ValIdx{fabs(a), tid + u * NT});
+            if (cand[u] && within_bound(dv[u], a, th)) piv = better_max(piv, ValIdx{fabs(a), tid + u * NT});
         }
     }
     piv = block_argmax(piv, sv, si);
-    SEL_PHASE(4);
+    phase_mark(L, Bv, b, 4, tk);
     const int q = piv.i;
     unsigned long long tk2 = (L.probe & 8) ? wall_clock64() : 0ull;
 
@@ -1289,32 +1290,10 @@ __device__ bool select_once_cached(const LpView &L, const BatchView &Bv, const i
     load_rows(tid);
     if (tid < np) s_mul[tid] = prow0[(size_t)tid * ld + q];
     // Phase C: the descriptor, the basis heads
-    if (tid == 0) {
-        int kb = bh[r], kn = nh[q];
-        double lo = LO(L, Bv, b, kb), up = UP(L, Bv, b, kb);
-        double target = below ? lo : up;
-        double trq = row[q];
-        double br = beta[r];
-        PivDesc d;
-        d.r = r; d.q = q; d.p = 1.0 / trq;
-        d.pbeta = br - target;
-        d.enter_val = xN[q] + (target - br) / trq;
-        Bv.desc[(size_t)b * KP + np] = d;
-        s_d = d;
-        bh[r] = kn; nh[q] = kb;
-        pos[kn] = r; pos[kb] = -1 - q;
-        if (lo == up) { nstat[q] = NS_S; xN[q] = lo; }
-        else if (below) { nstat[q] = NS_L; xN[q] = lo; }
-        else { nstat[q] = NS_U; xN[q] = up; }
-        if (L.trace == b && (iters < 300 || iters % 997 == 0)) printf("lp %d it %d r %d (var %d, %s by %.3e) q %d (var %d) alpha %.3e d %.3e step %.3e flips 0 obj %.12g%s\n", b, iters, r, kb, below ? "below" : "above",
-                                 below ? lo - br : br - up, q, kn, trq, drow[q], fabs(drow[q] / trq), beta[M], bland ? " bland" : "");
-        Bv.mode[b] = MODE_PIVOT;
-        Bv.verified[b] = verified & 2;
-        Bv.iters[b] = iters + 1;
-    }
+    if (tid == 0) s_d = commit_pivot(L, Bv, c, r, q, below, bland, iters, verified, MODE_PIVOT, drow, false, 0, false);
     __syncthreads();
     const PivDesc d = s_d;
-    if ((L.probe & 8) && b == 0) { __syncthreads(); if (tid == 0) { const unsigned long long tn = wall_clock64(); Bv.dbg[5] += tn - tk2; tk2 = tn; } }
+    phase_mark(L, Bv, b, 5, tk2);
     // Phase D: the entering column as it is after the pending pivots -> multipliers of all rows, beta; the reduced-cost row
     for (int i0 = tid; ; ) {
 #pragma unroll
@@ -1328,8 +1307,7 @@ __device__ bool select_once_cached(const LpView &L, const BatchView &Bv, const i
                 for (int s = 0; s < KP - 1; s++) {
                     if (s < np) {
                         const PivDesc ds = s_pd[s];
-                        if (i == ds.r) v = q == ds.q ? ds.p : -s_mul[s] * ds.p;
-                        else { const double f = pcl[s][u]; v = q == ds.q ? f : fma(-f, s_mul[s], v); }
+                        v = apply_pending(v, i == ds.r, q == ds.q, ds.p, pcl[s][u], s_mul[s]);
                     }
                 }
             }
@@ -1352,9 +1330,12 @@ __device__ bool select_once_cached(const LpView &L, const BatchView &Bv, const i
         }
     }
     if (tid == 0) Bv.npend[b] = np + 1;
-    if ((L.probe & 8) && b == 0) { __syncthreads(); if (tid == 0) { Bv.dbg[6] += wall_clock64() - tk2; Bv.dbg[7] += 1; } }
+    phase_mark(L, Bv, b, 6, tk2);
+    if ((L.probe & 8) && b == 0 && tid == 0) Bv.dbg[7] += 1;
     return true;
 }
+// (the extended instance is a function of its own, as the compiler always had it: inlined into the 1024-thread kernel it spills 300 registers, called none)
+__device__ __noinline__ bool select_once_ext(const LpView &L, const BatchView &Bv, const int b, const int cap2) { return select_once<true>(L, Bv, b, cap2); }
 // One launch selects up to nsel pivots per LP, one after the other, by the same workgroup: the KP selections between two passes
 // over the tableau depend only on the LP's own vectors (beta, the reduced-cost row, the pending pivot rows and multipliers) -- no
 // grid-wide dependency asks for a launch each (rounds 1-3 launched this kernel KP times per pass, 17 % of all GPU time in
@@ -1367,7 +1348,7 @@ __global__ __launch_bounds__(NT_BIG) void k_select(LpView L, BatchView Bv, const
     if (blockIdx.y > 0) { rev_helper(L, Bv, b); return; }      // (revised form: helps with the sparse products of LP b's tableau rows until told to leave)
     for (int sdx = 0; sdx < nsel; sdx++) {
         if (sdx) __syncthreads();              // (what thread 0 / every thread wrote for the LP -- status, mode, pending count, beta, reduced costs -- is read by all)
-        if (!select_once<EXT>(L, Bv, b, cap2)) break;
+        if (!(EXT ? select_once_ext(L, Bv, b, cap2) : select_once<false>(L, Bv, b, cap2))) break;
     }
     if (L.helpers > 1) {                       // every path of the LP's own workgroup ends here: the helpers may go
         __syncthreads();
@@ -2049,6 +2030,72 @@ static int materialise_indices(bslv_lpq *h, const int *list, int n)
     HIP_TRY(hipGetLastError());
     return 0;
 }
+// How the selections of a batch are launched: plan_select decides once per solve_batch (every environment switch is read at every
+// solve: the tests change them between solves of one process), launch_select launches once per round
+struct SelectPlan {
+    bool ext; int cap2;     // the extended selection k_select<true>; its candidate arrays in LDS (0: rows too long for the in-LDS sort, no long-step part)
+    int nt, per_launch; size_t lds;     // threads per workgroup; selections per launch; dynamic LDS of a k_select launch
+    int cpt;                // columns per thread of k_select_cached (plain dual selection, tableau form, NT threads), 0: k_select
+};
+static int plan_select(bslv_lpq *h, int B, const double *vlo, const double *vup, SelectPlan *plan)
+{
+    LpView &L = h->L;
+    // bound flipping ratio test only where a variable has two finite, non-artificial bounds
+    bool bfrt = h->has_boxed || L.objmode || h->force_ext;        // (the primal steps live in the extended selection)
+    if (!bfrt && L.vcnt > 0)
+        for (size_t k = 0; k < (size_t)B * L.vcnt && !bfrt; k++) bfrt = std::isfinite(vlo[k]) && std::isfinite(vup[k]) && vlo[k] < vup[k];
+    if (getenv("BSLV_LP_EXT")) bfrt = atoi(getenv("BSLV_LP_EXT")) != 0;      // test hook: force the extended selection on / off
+    int cap2 = 2;
+    while (cap2 < L.N) cap2 <<= 1;
+    size_t sel_lds = (size_t)cap2 * (sizeof(double) + sizeof(int)) + (size_t)L.N;
+    if (bfrt && sel_lds > 144 * 1024) { cap2 = 0; sel_lds = (size_t)L.N; }     // rows too long for the in-LDS sort: extended selection without the long-step part
+    if (bfrt && sel_lds > h->select_lds_max) {
+        if (sel_lds <= 144 * 1024 && hipFuncSetAttribute((const void *)k_select<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sel_lds) == hipSuccess) h->select_lds_max = sel_lds;
+        else bfrt = false;
+    }
+    if (L.objmode && !bfrt) { set_error("bslv_lpq_solve_batch_obj: rows too long for the extended selection (N=%d)", L.N); return BSLV_E_CAPACITY; }
+    // revised form: rho (a row of B^-1) in LDS behind the selection's own arrays, when there is room
+    plan->lds = bfrt ? sel_lds : 0;
+    L.rho_off = -1;
+    if (L.rev) {
+        const size_t off = bfrt ? (sel_lds + 15) / 16 * 16 : 0, want = off + (size_t)L.ldt * sizeof(double);
+        size_t &lim = bfrt ? h->select_lds_max : h->select0_lds_max;
+        bool ok = want <= lim;
+        if (!ok && want <= 144 * 1024) {
+            ok = hipFuncSetAttribute(bfrt ? (const void *)k_select<true> : (const void *)k_select<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)want) == hipSuccess;
+            if (ok) lim = want; else (void)hipGetLastError();
+        }
+        if (ok) { L.rho_off = (int)off; plan->lds = want; }
+    }
+    plan->ext = bfrt; plan->cap2 = bfrt ? cap2 : 0;
+    // (measured, BSLV_SELECT_NT: S-degenerate, 2011 columns, 64 LPs per step: LP phase 67.6 / 52.0 / 46.6 ms with 256 / 512 / 1024 threads;
+    //  S-degenerate-q4 to termination with 256 LPs per step 12.1 -> 10.4 s; same pivots)
+    plan->nt = getenv("BSLV_SELECT_NT") ? atoi(getenv("BSLV_SELECT_NT")) : (L.N >= 1536 ? NT_BIG : NT);
+    plan->per_launch = (getenv("BSLV_SELECT_FUSE") && atoi(getenv("BSLV_SELECT_FUSE")) == 0) ? 1 : KP;
+    const bool cache = !(getenv("BSLV_SELECT_CACHE") && atoi(getenv("BSLV_SELECT_CACHE")) == 0);      // 0: k_select<false> where k_select_cached would run (same results bit for bit, tests/test_lp_select_cache_gpu.py)
+    plan->cpt = (cache && !bfrt && !L.rev && plan->nt == NT && L.N <= 6 * NT) ? (L.N <= 2 * NT ? 2 : (L.N <= 4 * NT ? 4 : 6)) : 0;
+    return 0;
+}
+// the KP selections of one round for the `running` LPs of the active list
+static void launch_select(bslv_lpq *h, const SelectPlan &p, const BatchView &bv, int running)
+{
+    LpView &L = h->L; hipStream_t s = h->stream;
+    for (int lev = 0; lev < KP; lev += p.per_launch) {
+        // revised form: helper workgroups for the sparse products of a tableau row (rev_helper), as many per LP as the chip holds
+        // beside the LPs' own workgroups without anyone waiting for a place
+        int helpers = 1;
+        if (L.rev && p.nt == NT_BIG) {
+            static const int hmax = getenv("BSLV_REV_HELPERS") ? std::max(1, atoi(getenv("BSLV_REV_HELPERS"))) : 32;
+            helpers = std::max(1, std::min(std::min(hmax, (L.ld + 2047) / 2048), 256 / std::max(1, running)));
+        }
+        L.helpers = helpers; L.launch_id = (++h->launch_seq) & 0x3FFFFF;
+        if (p.cpt == 2) hipLaunchKernelGGL(k_select_cached<2>, dim3(running), dim3(NT), 0, s, L, bv, h->active_d, running, p.per_launch);
+        else if (p.cpt == 4) hipLaunchKernelGGL(k_select_cached<4>, dim3(running), dim3(NT), 0, s, L, bv, h->active_d, running, p.per_launch);
+        else if (p.cpt == 6) hipLaunchKernelGGL(k_select_cached<6>, dim3(running), dim3(NT), 0, s, L, bv, h->active_d, running, p.per_launch);
+        else if (p.ext) hipLaunchKernelGGL(k_select<true>, dim3(running, helpers), dim3(p.nt), p.lds, s, L, bv, h->active_d, running, p.cap2, p.per_launch);
+        else hipLaunchKernelGGL(k_select<false>, dim3(running, helpers), dim3(p.nt), p.lds, s, L, bv, h->active_d, running, 0, p.per_launch);
+    }
+}
 static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, const double *vlo, const double *vup,
                             int cfirst, int ccnt, const double *cvals, int *status, int *iters);
 int bslv_lpq_set_lazy(bslv_lpq *h, int on)
@@ -2186,43 +2233,13 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
     const size_t lds = wide ? 0 : (size_t)KP * L.ldt * sizeof(double);
     // (160 KB of LDS per CU: three workgroups of NT threads need lds <= ~53 KB)
     const bool big_flush = getenv("BSLV_FLUSH_NT") ? atoi(getenv("BSLV_FLUSH_NT")) > NT : lds > 53 * 1024;
-    // bound flipping ratio test only where a variable has two finite, non-artificial bounds
-    bool bfrt = h->has_boxed || L.objmode || h->force_ext;        // (the primal steps live in the extended selection)
-    if (!bfrt && L.vcnt > 0)
-        for (size_t k = 0; k < (size_t)B * L.vcnt && !bfrt; k++) bfrt = std::isfinite(vlo[k]) && std::isfinite(vup[k]) && vlo[k] < vup[k];
-    if (getenv("BSLV_LP_EXT")) bfrt = atoi(getenv("BSLV_LP_EXT")) != 0;      // test hook: force the extended selection on / off
-    int cap2 = 2;
-    while (cap2 < L.N) cap2 <<= 1;
-    size_t sel_lds = (size_t)cap2 * (sizeof(double) + sizeof(int)) + (size_t)L.N;
-    if (bfrt && sel_lds > 144 * 1024) { cap2 = 0; sel_lds = (size_t)L.N; }     // rows too long for the in-LDS sort: extended selection without the long-step part
-    if (bfrt && sel_lds > h->select_lds_max) {
-        if (sel_lds <= 144 * 1024 && hipFuncSetAttribute((const void *)k_select<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sel_lds) == hipSuccess) h->select_lds_max = sel_lds;
-        else bfrt = false;
-    }
-    if (L.objmode && !bfrt) { set_error("bslv_lpq_solve_batch_obj: rows too long for the extended selection (N=%d)", L.N); return BSLV_E_CAPACITY; }
-    // revised form: rho (a row of B^-1) in LDS behind the selection's own arrays, when there is room
-    size_t sel_lds_launch = bfrt ? sel_lds : 0;
-    L.rho_off = -1;
-    if (L.rev) {
-        const size_t off = bfrt ? (sel_lds + 15) / 16 * 16 : 0, want = off + (size_t)L.ldt * sizeof(double);
-        size_t &lim = bfrt ? h->select_lds_max : h->select0_lds_max;
-        bool ok = want <= lim;
-        if (!ok && want <= 144 * 1024) {
-            ok = (bfrt ? hipFuncSetAttribute((const void *)k_select<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)want)
-                       : hipFuncSetAttribute((const void *)k_select<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)want)) == hipSuccess;
-            if (ok) lim = want; else (void)hipGetLastError();
-        }
-        if (ok) { L.rho_off = (int)off; sel_lds_launch = want; }
-    }
+    SelectPlan plan;
+    if ((rc = plan_select(h, B, vlo, vup, &plan))) return rc;
     L.trace = getenv("BSLV_LP_TRACE") ? atoi(getenv("BSLV_LP_TRACE")) : -1;
     L.stall_limit = getenv("BSLV_STALL_LIMIT") ? atoi(getenv("BSLV_STALL_LIMIT")) : STALL_LIMIT;
     L.pert_scale = getenv("BSLV_PERT_SCALE") ? atof(getenv("BSLV_PERT_SCALE")) : 1.0;
-    // One ROUND = KP lock-step selections on vectors, then one pass over the tableaux of the LPs that have something
+    // One ROUND = KP lock-step selections on vectors (launch_select), then one pass over the tableaux of the LPs that have something
     // pending (k_flush).  The status vector is read back every 1, 2, 4, ... rounds.
-    // (measured, BSLV_SELECT_NT: S-degenerate, 2011 columns, 64 LPs per step: LP phase 67.6 / 52.0 / 46.6 ms with 256 / 512 / 1024 threads;
-    //  S-degenerate-q4 to termination with 256 LPs per step 12.1 -> 10.4 s; same pivots)
-    const int sel_nt = getenv("BSLV_SELECT_NT") ? atoi(getenv("BSLV_SELECT_NT")) : (L.N >= 1536 ? NT_BIG : NT);
-    const int sel_per_launch = (getenv("BSLV_SELECT_FUSE") && atoi(getenv("BSLV_SELECT_FUSE")) == 0) ? 1 : KP;     // selections per k_select launch
     int it = 0, chunk = 1, running = B;
     for (int b = 0; b < B; b++) h->active_h[b] = b;
     HIP_TRY(hipMemcpyAsync(h->active_d, h->active_h, B * sizeof(int), hipMemcpyHostToDevice, s));
@@ -2230,27 +2247,9 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
     h->last_update_ms = 0;
     static const int max_rounds = getenv("BSLV_LP_MAXROUNDS") ? atoi(getenv("BSLV_LP_MAXROUNDS")) : 0;      // (timing experiments)
     L.probe = getenv("BSLV_REV_PROBE") ? atoi(getenv("BSLV_REV_PROBE")) : 0;
-    const bool sel_cache = !(getenv("BSLV_SELECT_CACHE") && atoi(getenv("BSLV_SELECT_CACHE")) == 0);      // 0: k_select<false> where k_select_cached would run (same results bit for bit, tests/test_lp_select_cache_gpu.py)
-    // columns per thread of k_select_cached (plain dual selection, tableau form, NT threads), 0: k_select
-    const int sel_cpt = (sel_cache && !bfrt && !L.rev && sel_nt == NT && L.N <= 6 * NT) ? (L.N <= 2 * NT ? 2 : (L.N <= 4 * NT ? 4 : 6)) : 0;
     while (running > 0 && it < L.maxit + 8 && !(max_rounds && it >= max_rounds)) {
         for (int c = 0; c < chunk; c++, it++) {
-            for (int lev = 0; lev < KP; lev += sel_per_launch) {
-                // revised form: helper workgroups for the sparse products of a tableau row (rev_helper), as many per LP as the chip holds
-                // beside the LPs' own workgroups without anyone waiting for a place
-                int helpers = 1;
-                if (L.rev && sel_nt == NT_BIG) {
-                    static const int hmax = getenv("BSLV_REV_HELPERS") ? std::max(1, atoi(getenv("BSLV_REV_HELPERS"))) : 32;
-                    helpers = std::max(1, std::min(std::min(hmax, (L.ld + 2047) / 2048), 256 / std::max(1, running)));
-                }
-                L.helpers = helpers;
-                L.launch_id = (++h->launch_seq) & 0x3FFFFF;
-                if (sel_cpt == 2) hipLaunchKernelGGL(k_select_cached<2>, dim3(running), dim3(NT), 0, s, L, bv, h->active_d, running, sel_per_launch);
-                else if (sel_cpt == 4) hipLaunchKernelGGL(k_select_cached<4>, dim3(running), dim3(NT), 0, s, L, bv, h->active_d, running, sel_per_launch);
-                else if (sel_cpt == 6) hipLaunchKernelGGL(k_select_cached<6>, dim3(running), dim3(NT), 0, s, L, bv, h->active_d, running, sel_per_launch);
-                else if (bfrt) hipLaunchKernelGGL(k_select<true>,dim3(running, helpers), dim3(sel_nt), sel_lds_launch, s, L, bv, h->active_d, running, cap2, sel_per_launch);
-                else hipLaunchKernelGGL(k_select<false>, dim3(running, helpers), dim3(sel_nt), sel_lds_launch, s, L, bv, h->active_d, running, 0, sel_per_launch);
-            }
+            launch_select(h, plan, bv, running);
             hipLaunchKernelGGL(k_list_pending, dim3((running + 255) / 256), dim3(256), 0, s, bv, h->active_d, running, it);
             if (h->profile) {
                 if (nev == h->evpool.size()) {

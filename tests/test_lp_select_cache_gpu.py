@@ -83,3 +83,50 @@ def test_select_cache_is_bit_identical_to_the_plain_selection(monkeypatch, case)
     assert a[1].sum() > B, "the batch needs pivots for this to mean anything"
     for x, y in zip(a[2:], b[2:]):
         assert np.array_equal(x.view(np.uint64), y.view(np.uint64))
+
+
+def _infeasible_lp():
+    # x1 + x2 >= 2 and x1 + x2 <= 1, x >= 0, min x1 + x2: the second row finds no entering candidate
+    A = np.array([[1.0, 1.0], [1.0, 1.0]])
+    lo = np.array([2.0, -np.inf, 0.0, 0.0])
+    up = np.array([np.inf, 1.0, np.inf, np.inf])
+    return A, lo, up, np.array([0.0, 1.0, 1.0]), 0
+
+
+def _unbounded_lp():
+    # min -x1 with x1 free above (the second LP of test_lp_gpu.test_infeasible_and_unbounded_status): optimal on an artificial bound
+    A = np.array([[1.0, 1.0]])
+    lo = np.array([-np.inf, 0.0, 0.0])
+    up = np.array([np.inf, np.inf, np.inf])
+    return A, lo, up, np.array([0.0, -1.0, 0.0]), 1
+
+
+@pytest.mark.parametrize("make", [_infeasible_lp, _unbounded_lp])
+def test_select_cache_ends_infeasible_and_unbounded_lps_as_the_plain_selection(monkeypatch, make):
+    """The cases above all end OPTIMAL.  Two LPs without a boxed variable (no variable has two finite bounds, so the plain dual
+    selection runs and k_select_cached takes it) that end the other ways: no entering candidate for a violated row (INFEASIBLE, 0) and an
+    active artificial bound at the optimum of the bounded problem (UNBOUNDED, 1).  Same status and same pivot count through both
+    kernels, and the status of the CPU oracle."""
+    import oracle_api
+    A, lo, up, cost, expected = make()
+    M, N = A.shape
+    olp = oracle_api.OracleLP(A, lo, up, cost)
+    ost = olp.solve(1)
+    olp.close()
+    assert ost == expected
+    res = {}
+    for cache in ("0", "1"):
+        for k in SWITCHES:
+            monkeypatch.delenv(k, raising=False)
+        if cache == "0":
+            monkeypatch.setenv("BSLV_SELECT_CACHE", "0")
+        eng = LpEngine(M, N, A, lo, up, cost, 0, 0, 2)
+        eng.reset_slot(0)
+        st, it = eng.solve_batch([0], [0], np.zeros((1, 0)), np.zeros((1, 0)))
+        stats = eng.last_stats()
+        eng.close()
+        print("%s cache %s: status %d, %d pivots, %s" % (make.__name__, cache, st[0], it[0], stats))
+        assert stats["perturbations"] == 0 and stats["flip_iterations"] == 0 and stats["primal_steps"] == 0      # (not the extended selection)
+        res[cache] = (int(st[0]), int(it[0]))
+    assert res["0"][0] == expected and res["1"][0] == expected
+    assert res["0"] == res["1"], "status or pivot count differs"
