@@ -214,7 +214,9 @@ __global__ __launch_bounds__(NT) void k_prep(LpView L, BatchView Bv, int B)
     }
 }
 
-// ---- k_init: beta_dst = T_src . xN_dst, one wave per row, and the reduced-cost row T_dst[M] = T_src[M].  The rest of the
+// ---- k_init: beta_dst = T_src . xN_dst, one wave per row, and the reduced-cost row T_dst[M] = T_src[M].  It starts the batches
+//      k_init_grouped (below) has no instance for -- new objectives, rows of more than 2048 columns -- and every batch under
+//      BSLV_INIT_GROUP=0; plan_init decides.  The rest of the
 //      parent's tableau is NOT copied here: the first pivot of the solve reads the parent and writes the new slot
 //      (k_flush), which saves one write and one read of the tableau per LP; solves without a pivot are copied by
 //      k_copy_unpivoted at the end. ----
@@ -246,6 +248,107 @@ __global__ __launch_bounds__(NT) void k_init(LpView L, BatchView Bv, int B)
         }
         acc = wave_sum(acc);
         if (lane == 0) beta[i] = acc;
+    }
+}
+
+// wave_sum of R values at once: on return a[0] of lane l holds the sum of value init_row_of_lane<R>(l), added up in wave_sum's own
+// order.  The lanes l and l ^ o hold the same sum after wave_sum's step o, so each of the first log2(R) steps halves the number
+// of values instead: a lane keeps the even value of a pair if its bit o is clear and the odd one if it is set, and gets the
+// partner's half of the value it keeps.  8 values: 4 + 2 + 1 + 3 shuffles instead of 8 x 6.
+template <int R>
+__device__ __forceinline__ void wave_sum_rows(double (&a)[R], int lane)
+{
+    static_assert(R == 2 || R == 4 || R == 8, "two, four or eight values");
+    auto halve = [&](auto n, int o) {
+        const bool odd = (lane & o) != 0;
+#pragma unroll
+        for (int k = 0; k < decltype(n)::value / 2; k++) {
+            const double keep = odd ? a[2 * k + 1] : a[2 * k], give = odd ? a[2 * k] : a[2 * k + 1];
+            a[k] = keep + __shfl_xor(give, o, WAVE);
+        }
+    };
+    if constexpr (R == 8) { halve(std::integral_constant<int, 8>{}, 32); halve(std::integral_constant<int, 4>{}, 16); halve(std::integral_constant<int, 2>{}, 8); }
+    if constexpr (R == 4) { halve(std::integral_constant<int, 4>{}, 32); halve(std::integral_constant<int, 2>{}, 16); }
+    if constexpr (R == 2) halve(std::integral_constant<int, 2>{}, 32);
+#pragma unroll
+    for (int o = 32 / R; o > 0; o >>= 1) a[0] += __shfl_xor(a[0], o, WAVE);
+}
+template <int R>
+__device__ __forceinline__ int init_row_of_lane(int lane)      // (step o = 32 chose bit 0 of the value's index, o = 16 bit 1, o = 8 bit 2)
+{
+    int r = (lane >> 5) & 1;
+    if (R >= 4) r |= ((lane >> 4) & 1) << 1;
+    if (R >= 8) r |= ((lane >> 3) & 1) << 2;
+    return r;
+}
+
+// ---- k_init_grouped: k_init for a batch whose LPs share a few parents (plan_init says which of the two runs).  The host has
+//      sorted the batch by parent and cut every family into chunks of children (InitChunk); a workgroup takes one chunk and
+//      4 x R rows of the parent, a wave R of them.  The wave reads its rows ONCE into registers -- lane l holds the entries
+//      j2 = l, l + 64, ... of each row, the ones it touches in k_init -- and then walks the children of the chunk: x_N of the
+//      child, the same fma chain per row as k_init, the same wave reduction (wave_sum_rows), beta of the child; row M goes
+//      to the child's slot from the registers.  Per LP it reads and writes what k_init reads and writes, bit for bit; the
+//      parent's tableau is read once per chunk instead of once per child.  EPL: double2 entries of a row per lane. ----
+struct InitChunk { int first, cnt; };      // children order[first .. first + cnt) of the batch, all of one parent
+template <int EPL, int R>
+__global__ __launch_bounds__(NT) void k_init_grouped(LpView L, BatchView Bv, const int *__restrict__ order, const InitChunk *__restrict__ chunks)
+{
+    const InitChunk ch = chunks[blockIdx.y];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int i0 = (blockIdx.x * (NT / WAVE) + wave) * R;      // first row of this wave
+    if (i0 >= L.mrows) return;
+    const int ld2 = L.ldt >> 1;
+    const int src = Bv.src[order[ch.first]];
+    const double *Ts = L.T + (size_t)src * L.slotT;
+    double2 v[R][EPL];
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+        const double2 *s = reinterpret_cast<const double2 *>(Ts + (size_t)min(i0 + r, L.mrows - 1) * L.ldt);      // (rows past the last: loaded again, never written)
+#pragma unroll
+        for (int e = 0; e < EPL; e++) { const int j2 = lane + e * WAVE; v[r][e] = j2 < ld2 ? s[j2] : make_double2(0.0, 0.0); }
+    }
+    const int rowM = (!L.rev && L.M >= i0 && L.M < i0 + R) ? L.M - i0 : -1;      // the reduced-cost row is one of this wave's
+    const int myrow = init_row_of_lane<R>(lane);
+    const bool writer = (lane & (WAVE / R - 1)) == 0 && i0 + myrow < L.mrows;
+    auto x_of = [&](int c) -> const double2 * {
+        const int b = order[ch.first + c];
+        return reinterpret_cast<const double2 *>(L.rev ? Bv.uvec + (size_t)b * L.ldt : L.xN + (size_t)Bv.dst[b] * L.ld);
+    };
+    double2 x[EPL], xn[EPL];
+    {
+        const double2 *x2 = x_of(0);
+#pragma unroll
+        for (int e = 0; e < EPL; e++) { const int j2 = lane + e * WAVE; xn[e] = j2 < ld2 ? x2[j2] : make_double2(0.0, 0.0); }
+    }
+    for (int c = 0; c < ch.cnt; c++) {
+        const int dst = Bv.dst[order[ch.first + c]];
+#pragma unroll
+        for (int e = 0; e < EPL; e++) x[e] = xn[e];
+        if (c + 1 < ch.cnt) {      // the next child's x_N is on its way while this one is multiplied
+            const double2 *x2 = x_of(c + 1);
+#pragma unroll
+            for (int e = 0; e < EPL; e++) { const int j2 = lane + e * WAVE; xn[e] = j2 < ld2 ? x2[j2] : make_double2(0.0, 0.0); }
+        }
+        double acc[R];
+#pragma unroll
+        for (int r = 0; r < R; r++) acc[r] = 0.0;
+#pragma unroll
+        for (int e = 0; e < EPL; e++)
+            if (lane + e * WAVE < ld2) {      // (k_init's loop bound: a lane past the row's end adds nothing)
+#pragma unroll
+                for (int r = 0; r < R; r++) { acc[r] = fma(v[r][e].x, x[e].x, acc[r]); acc[r] = fma(v[r][e].y, x[e].y, acc[r]); }
+            }
+        wave_sum_rows<R>(acc, lane);
+        if (writer) L.beta[(size_t)dst * L.Mp1p + i0 + myrow] = acc[0];
+        if (rowM >= 0 && src != dst) {      // only the reduced-cost row: the first pass streams the rest from the parent (k_flush)
+            double2 *d = reinterpret_cast<double2 *>(L.T + (size_t)dst * L.slotT + (size_t)L.M * L.ldt);
+#pragma unroll
+            for (int r = 0; r < R; r++)
+                if (r == rowM) {
+#pragma unroll
+                    for (int e = 0; e < EPL; e++) { const int j2 = lane + e * WAVE; if (j2 < ld2) d[j2] = v[r][e]; }
+                }
+        }
     }
 }
 
@@ -1578,6 +1681,9 @@ struct bslv_lpq {
     size_t flush_lds_max = 64 * 1024;  // dynamic LDS k_flush may use (raised to 144 KB at create when the runtime allows)
     int upd_grid = 32768;             // workgroups of the persistent k_flush (BSLV_UPD_GRID; 1024..32768 measured equal within 2 %)
     int *active_d = nullptr, *active_h = nullptr;       // compacted indices of the LPs still running (device / pinned)
+    int *init_d = nullptr, *init_h = nullptr;           // the batch ordered by parent and its chunks for k_init_grouped: [B] order, [B] InitChunk (device / pinned, plan_init)
+    std::vector<int> init_at, init_seen;                // plan_init's scratch: per slot a count / write position (zero between calls), the parents of the batch
+    int last_init_parents = 0, last_init_family = 0, last_init_chunks = 0;      // distinct src slots of the last batch, its largest family; chunks k_init_grouped ran on (0: k_init ran)
     double *vlo_d = nullptr, *vup_d = nullptr, *prow_d = nullptr, *out_d = nullptr;
     size_t out_cap = 0;
     PivDesc *desc_d = nullptr;
@@ -1615,11 +1721,12 @@ static int ensure_batch(bslv_lpq *h, int B)
     // every pointer is cleared as it is freed: when one of the allocations below fails, destroy() and a later ensure_batch()
     // see nullptr for what is gone instead of freeing it a second time
     auto fr = [](auto *&p) { if (p) (void)hipFree(p); p = nullptr; };
-    fr(h->src_d); fr(h->dst_d); fr(h->status_d); fr(h->iters_d); fr(h->mode_d); fr(h->ver_d); fr(h->active_d); fr(h->work_d); fr(h->qslot_d);
+    fr(h->src_d); fr(h->dst_d); fr(h->status_d); fr(h->iters_d); fr(h->mode_d); fr(h->ver_d); fr(h->active_d); fr(h->work_d); fr(h->qslot_d); fr(h->init_d);
     fr(h->vlo_d); fr(h->vup_d); fr(h->prow_d); fr(h->desc_d); fr(h->npend_d); fr(h->flushed_d); fr(h->pcol_d); fr(h->dcur_d); fr(h->dper_d); fr(h->pflags_d); fr(h->stall_d);
     fr(h->trow_d); fr(h->uvec_d); fr(h->xfull_d); fr(h->hmail_d);
     if (h->status_h) { (void)hipHostFree(h->status_h); h->status_h = nullptr; }
     if (h->active_h) { (void)hipHostFree(h->active_h); h->active_h = nullptr; }
+    if (h->init_h) { (void)hipHostFree(h->init_h); h->init_h = nullptr; }
     h->Bcap = 0;
     HIP_TRY(malloc0(&h->src_d, cap * sizeof(int)));
     HIP_TRY(malloc0(&h->qslot_d, cap * sizeof(int)));
@@ -1652,6 +1759,8 @@ static int ensure_batch(bslv_lpq *h, int B)
     HIP_TRY(hipHostMalloc(&h->status_h, cap * sizeof(int)));
     HIP_TRY(malloc0(&h->active_d, cap * sizeof(int)));
     HIP_TRY(hipHostMalloc(&h->active_h, cap * sizeof(int)));
+    HIP_TRY(malloc0(&h->init_d, (size_t)cap * 3 * sizeof(int)));
+    HIP_TRY(hipHostMalloc(&h->init_h, (size_t)cap * 3 * sizeof(int)));
     h->Bcap = cap;
     return 0;
 }
@@ -1838,10 +1947,11 @@ void bslv_lpq_destroy(bslv_lpq *h)
     fr(h->L.T); fr(h->L.beta); fr(h->L.xN); fr(h->L.bh); fr(h->L.nh); fr(h->L.nstat); fr(h->L.pos);
     fr(h->Tstd); fr(h->lb_d); fr(h->ub_d); fr(h->art_d);
     fr(h->dbg_d); fr(h->list_d); fr(h->cptr_d); fr(h->cidx_d); fr(h->rptr_d); fr(h->ridx_d); fr(h->cval_d); fr(h->rval_d); fr(h->cost_d); fr(h->dsl_d); fr(h->trow_d); fr(h->uvec_d); fr(h->xfull_d); fr(h->hmail_d);
-    fr(h->src_d); fr(h->dst_d); fr(h->status_d); fr(h->iters_d); fr(h->mode_d); fr(h->ver_d); fr(h->qslot_d);
+    fr(h->src_d); fr(h->dst_d); fr(h->status_d); fr(h->iters_d); fr(h->mode_d); fr(h->ver_d); fr(h->qslot_d); fr(h->init_d);
     fr(h->vlo_d); fr(h->vup_d); fr(h->prow_d); fr(h->desc_d); fr(h->out_d); fr(h->active_d); fr(h->work_d); fr(h->nwork_d); fr(h->npend_d); fr(h->flushed_d); fr(h->pcol_d); fr(h->dcur_d); fr(h->dper_d); fr(h->pflags_d); fr(h->stall_d); fr(h->xstat_d); fr(h->cvals_d);
     if (h->status_h) (void)hipHostFree(h->status_h);
     if (h->active_h) (void)hipHostFree(h->active_h);
+    if (h->init_h) (void)hipHostFree(h->init_h);
     for (auto &e : h->evpool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
@@ -2029,6 +2139,44 @@ static int materialise_indices(bslv_lpq *h, const int *list, int n)
     hipLaunchKernelGGL(k_store_d, dim3((h->L.ld + 255) / 256, B), dim3(256), 0, s, h->L, bv, B);
     HIP_TRY(hipGetLastError());
     return 0;
+}
+// Which kernel starts the LPs of a batch (beta = T_parent x_N, row M): k_init_grouped where it has an instance -- rows of at most
+// 16 x 64 double2 (2048 columns: S-degenerate's 2011 are in, ex09's revised form with ldt ~ 4 600 is not), the reduced-cost row
+// not rebuilt per child (objmode: k_prep wrote it into the child's own slot) -- and BSLV_INIT_GROUP is not 0; k_init otherwise.
+// Same results bit for bit (tests/test_lp_init_group_gpu.py).  For k_init_grouped the batch is ordered by parent here (stable) and
+// every family cut into chunks of children, short enough that the chunks x row tiles fill the chip when the parents are few.
+struct InitPlan {
+    int epl, rows;          // k_init_grouped<epl, rows>: double2 entries of a row per lane, rows per wave; epl 0: k_init
+    int tiles, chunks;      // its grid
+};
+static void plan_init(bslv_lpq *h, int B, const int *src, InitPlan *plan)
+{
+    const LpView &L = h->L;
+    int *order = h->init_h;
+    InitChunk *chunks = reinterpret_cast<InitChunk *>(h->init_h + B);
+    // counting sort by parent slot, the families in the order of their first LP: O(B), and it runs while k_prep does
+    std::vector<int> &at = h->init_at, &seen = h->init_seen;
+    at.resize(h->slots, 0); seen.clear();
+    for (int b = 0; b < B; b++) if (at[src[b]]++ == 0) seen.push_back(src[b]);
+    { int off = 0; for (int p : seen) { const int n = at[p]; at[p] = off; off += n; } }
+    for (int b = 0; b < B; b++) order[at[src[b]]++] = b;
+    for (int p : seen) at[p] = 0;
+    const int ld2 = L.ldt >> 1;
+    const bool on = !(getenv("BSLV_INIT_GROUP") && atoi(getenv("BSLV_INIT_GROUP")) == 0);
+    plan->epl = (!on || L.objmode || ld2 > 16 * WAVE) ? 0 : ld2 <= WAVE ? 1 : ld2 <= 2 * WAVE ? 2 : ld2 <= 4 * WAVE ? 4 : ld2 <= 8 * WAVE ? 8 : 16;
+    plan->rows = plan->epl == 16 ? 2 : plan->epl == 8 ? 4 : 8;       // (32 double2 of the parent per lane)
+    plan->tiles = (L.mrows + plan->rows * (NT / WAVE) - 1) / (plan->rows * (NT / WAVE));
+    const int per_chunk = std::max(4, std::min(32, (int)((long)B * plan->tiles / 4096)));      // (S-mid: 2048 LPs x 32 tiles: 16 children)
+    int parents = 0, family = 0, n = 0;
+    for (int a = 0; a < B;) {
+        int e = a;
+        while (e < B && src[order[e]] == src[order[a]]) e++;
+        parents++; family = std::max(family, e - a);
+        for (int c = a; c < e; c += per_chunk) chunks[n++] = InitChunk{c, std::min(per_chunk, e - c)};
+        a = e;
+    }
+    plan->chunks = n;
+    h->last_init_parents = parents; h->last_init_family = family; h->last_init_chunks = plan->epl ? n : 0;
 }
 // How the selections of a batch are launched: plan_select decides once per solve_batch (every environment switch is read at every
 // solve: the tests change them between solves of one process), launch_select launches once per round
@@ -2228,7 +2376,19 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
         hipLaunchKernelGGL(k_list_unpivoted, dim3((B + 255) / 256), dim3(256), 0, s, bv, B, -cnt_slot);
         hipLaunchKernelGGL(k_copy_unpivoted, dim3(std::min(B * tiles, 2048)), dim3(NT), 0, s, L, bv, cnt_slot, tiles);
     }
-    hipLaunchKernelGGL(k_init, dim3(tiles, B), dim3(NT), 0, s, L, bv, B);
+    InitPlan ip;
+    plan_init(h, B, src, &ip);
+    if (ip.epl) {
+        HIP_TRY(hipMemcpyAsync(h->init_d, h->init_h, ((size_t)B + 2 * (size_t)ip.chunks) * sizeof(int), hipMemcpyHostToDevice, s));
+        const int *order = h->init_d;
+        const InitChunk *chunks = reinterpret_cast<const InitChunk *>(h->init_d + B);
+        const dim3 grid(ip.tiles, ip.chunks);
+        if (ip.epl == 1) hipLaunchKernelGGL((k_init_grouped<1, 8>), grid, dim3(NT), 0, s, L, bv, order, chunks);
+        else if (ip.epl == 2) hipLaunchKernelGGL((k_init_grouped<2, 8>), grid, dim3(NT), 0, s, L, bv, order, chunks);
+        else if (ip.epl == 4) hipLaunchKernelGGL((k_init_grouped<4, 8>), grid, dim3(NT), 0, s, L, bv, order, chunks);
+        else if (ip.epl == 8) hipLaunchKernelGGL((k_init_grouped<8, 4>), grid, dim3(NT), 0, s, L, bv, order, chunks);
+        else hipLaunchKernelGGL((k_init_grouped<16, 2>), grid, dim3(NT), 0, s, L, bv, order, chunks);
+    } else hipLaunchKernelGGL(k_init, dim3(tiles, B), dim3(NT), 0, s, L, bv, B);
     HIP_TRY(hipGetLastError());
     const size_t lds = wide ? 0 : (size_t)KP * L.ldt * sizeof(double);
     // (160 KB of LDS per CU: three workgroups of NT threads need lds <= ~53 KB)
@@ -2331,7 +2491,7 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
     }
     {
         static const bool tm = getenv("BSLV_LP_TIMING") != nullptr;
-        if (tm) fprintf(stderr, "lp solve_batch: %s form %d x %d, B %d, %d lock-step rounds, %ld pivots, %ld passes, %.1f ms\n", L.rev ? "revised" : "tableau", L.M, L.N, B, it, h->last_pivots, h->last_passes, h->last_total_ms);
+        if (tm) fprintf(stderr, "lp solve_batch: %s form %d x %d, B %d, %d lock-step rounds, %ld pivots, %ld passes, %.1f ms; %d parents, largest family %d, %s\n", L.rev ? "revised" : "tableau", L.M, L.N, B, it, h->last_pivots, h->last_passes, h->last_total_ms, h->last_init_parents, h->last_init_family, h->last_init_chunks ? "k_init_grouped" : "k_init");
     }
     return 0;
 }
@@ -2442,6 +2602,7 @@ int bslv_lpq_get_obj(bslv_lpq *h, int B, const int *slot, double *out)
 long bslv_lpq_last_passes(const bslv_lpq *h) { return h ? h->last_passes : 0; }
 long bslv_lpq_last_launches(const bslv_lpq *h) { return h ? h->last_launches : 0; }
 long bslv_lpq_last_flip_updates(const bslv_lpq *h) { return h ? h->last_ext[4] : 0; }
+long bslv_lpq_last_init_chunks(const bslv_lpq *h) { return h ? h->last_init_chunks : 0; }
 // The extended selection for every LP of this engine from now on (on != 0) or only where a variable is boxed (0, the default
 // below 1 GiB per tableau).  It changes the pivots taken, not the optimal value: used by the callers' retry when the plain
 // dual simplex runs into its iteration limit on a degenerate LP.

@@ -137,6 +137,9 @@ int  bslv_lpq_last_ext_stats(const bslv_lpq *h, long out[4]);
 /* of the iterations with bound switches (out[0] above): those whose switches were carried into beta by a vector update, i.e.
  * without a pass over the tableau (at most 48 switches in the iteration) */
 long bslv_lpq_last_flip_updates(const bslv_lpq *h);
+/* how the last solve_batch started its LPs: the number of (parent, range of children) chunks k_init_grouped ran on, 0 when k_init
+ * ran (a new objective, rows of more than 2048 columns, BSLV_INIT_GROUP=0) */
+long bslv_lpq_last_init_chunks(const bslv_lpq *h);
 /* The extended selection (bound flipping where variables are boxed, cost perturbation against dual-degenerate stalling, primal
  * clean-up) is compiled in for LPs with a boxed variable and, by itself, for tableaux of 1 GiB and more (ex09 of the reference's
  * suite: the plain dual simplex stalls there until the iteration limit).  on != 0 switches it on for every later solve of this
