@@ -53,6 +53,9 @@ constexpr int ST_RUNNING = -1;
 constexpr int MODE_NONE = 0, MODE_PIVOT = 1, MODE_REFRESH = 2;
 constexpr int PRIMAL_STALL = 500;           // consecutive degenerate steps of a primal clean-up before Bland's rule takes over (until a step has a length again)
 constexpr int PF_PERT = 1, PF_PRIMAL = 2, PF_PERT_PENDING = 4, PF_USES_SHIFT = 8;   // BatchView::pflags
+// primal phase 1 (bits 4..7 of pflags; the perturbations of the solve are counted from bit PF_USES_SHIFT up): the LP is in phase 1 and dper
+// holds its pricing vector d1; it has been there in this solve; d1 has to be rebuilt from the rows; d1 is current although nothing is pending
+constexpr int PF_PHASE1 = 16, PF_P1_SEEN = 32, PF_P1_STALE = 64, PF_P1_KEEP = 128;
 constexpr int STALL_LIMIT = 3;         // consecutive degenerate pivots (dual step <= 1e-11) after which the costs are perturbed
 constexpr int PERT_MAX_USES = 3;       // perturbations per solve
 #ifndef BSLV_KP
@@ -107,10 +110,10 @@ struct BatchView {
     double *pcol;               // [B][KP][Mp1p] multipliers f_i = (entering column)_i * p of every row i (0 for the pivot row)
     double *dcur;               // [B][ld]       reduced-cost row of the LP, up to date
     // Extended selection (k_select<true>): cost perturbation against dual degenerate stalling, primal clean-up afterwards
-    double *dper;               // [B][ld]       perturbed reduced costs (the ratio tests use them while PF_PERT is set)
+    double *dper;               // [B][ld]       perturbed reduced costs (the ratio tests use them while PF_PERT is set); while PF_PHASE1 is set: the phase-1 pricing vector d1
     int *pflags, *stall;        // PF_* bits; consecutive degenerate pivots
     const double *cvals;        // [B][ccnt] objective coefficients (objmode)
-    int *xstat;                 // [5] of the batch: iterations with bound switches, perturbations, primal steps, removals that left wrong signs, switch iterations carried into beta without a pass
+    int *xstat;                 // [8] of the batch: iterations with bound switches, perturbations, primal steps, removals that left wrong signs, switch iterations carried into beta without a pass; phase 1: LPs that entered it, its iterations, rebuilds of d1
     int *work, *nwork;      // LPs whose tableau k_flush passes over in a round (k_list_pending), their number per round
     // revised form
     double *trow;           // [B][ld]   the tableau row of the selection at hand (prow then holds rows of B^-1: [B][KP][ldt])
@@ -135,6 +138,38 @@ __device__ __forceinline__ double btol(double bnd) { return TOL_BND * (1.0 + fab
 
 // ---- k_prep: copy the small per-slot arrays src -> dst, sanitise nonbasic statuses against the
 //      new bounds and set the nonbasic values (oracle/lp_dense.c sanitize()) ----
+// The nonbasic status a DUAL start gives a variable (lo .. up) that the parent held at st with the reduced cost dj, and whether
+// the dual simplex can start from it
+__device__ __forceinline__ int dual_start_status(int st, double lo, double up, const double *drow, int j, int objmode)
+{
+    if (lo == up) st = NS_S;
+    else if (isinf(lo) && isinf(up)) st = NS_F;
+    else if (isinf(lo)) st = NS_U;
+    else if (isinf(up)) st = NS_L;
+    else {
+        // boxed: sit at the bound that keeps the reduced cost dual feasible
+        double dj = objmode ? 0.0 : drow[j];       // (new objective: stay where the parent was, that is primal feasible)
+        if (dj < -TOL_DJ) st = NS_U;
+        else if (dj > TOL_DJ) st = NS_L;
+        else if (st != NS_L && st != NS_U) st = NS_L;
+    }
+    return st;
+}
+__device__ __forceinline__ bool dual_start_infeasible(int st, double dj) { return (st == NS_F && fabs(dj) > 1e-7) || (st == NS_L && dj < -1e-7) || (st == NS_U && dj > 1e-7); }
+// ... and a PRIMAL start (bslv_lpq_set_method): the parent's side where the bounds still have it; an artificial bound is no place to
+// start from (1e7 in x_N leaves 1e-9 of debris in beta), the variable starts on its own bound or, without one, free at zero
+__device__ __forceinline__ int primal_start_status(int st, double lo, double up, unsigned char art)
+{
+    const bool nlo = isinf(lo) || (art & 1), nup = isinf(up) || (art & 2);
+    if (lo == up) return NS_S;
+    if (nlo && nup) return NS_F;
+    if (nlo) return NS_U;
+    if (nup) return NS_L;
+    return (st == NS_L || st == NS_U) ? st : NS_L;
+}
+// METHOD: bslv_lpq_set_method's (objective batches: DUAL).  DUAL is the kernel as it always was; PRIMAL starts every LP as it stands,
+// REPAIR the ones a DUAL start reports UNDEFINED -- both with PF_PRIMAL, the selection's phase 1 takes it from there.
+template <int METHOD>
 __global__ __launch_bounds__(NT) void k_prep(LpView L, BatchView Bv, int B)
 {
     int b = blockIdx.x;
@@ -151,11 +186,22 @@ __global__ __launch_bounds__(NT) void k_prep(LpView L, BatchView Bv, int B)
         for (int i = threadIdx.x; i < L.M + L.N; i += NT) pos_d[i] = pos_s[i];
     }
     int dual_infeasible = 0, bigm = 0;     // bigm: a nonbasic variable sits on an artificial (+-1e7) bound
+    bool primal_start = METHOD == BSLV_LP_METHOD_PRIMAL;
+    if constexpr (METHOD == BSLV_LP_METHOD_REPAIR) {      // would the dual start below fail?  (asked first: in place, the loop below overwrites the parent's statuses)
+        int bad = 0;
+        for (int j = threadIdx.x; j < L.N; j += NT) {
+            const int k = nh_s[j];
+            if (dual_start_infeasible(dual_start_status(ns_s[j], LO(L, Bv, b, k), UP(L, Bv, b, k), drow_s, j, 0), drow_s[j])) bad = 1;
+        }
+        primal_start = __syncthreads_or(bad);
+    }
     for (int j = threadIdx.x; j < L.ld; j += NT) {
         if (j >= L.N) { xN_d[j] = 0.0; continue; }
         int k = nh_s[j];
         double lo = LO(L, Bv, b, k), up = UP(L, Bv, b, k);
         int st = ns_s[j];
+        if (METHOD != BSLV_LP_METHOD_DUAL && primal_start) st = primal_start_status(st, lo, up, L.art[k]);
+        else {      // (dual_start_status and dual_start_infeasible, in the words the DUAL kernel was compiled from: its code stays what it was)
         if (lo == up) st = NS_S;
         else if (isinf(lo) && isinf(up)) st = NS_F;
         else if (isinf(lo)) st = NS_U;
@@ -172,6 +218,7 @@ __global__ __launch_bounds__(NT) void k_prep(LpView L, BatchView Bv, int B)
         {
             double dj = drow_s[j];
             if (!L.objmode && ((st == NS_F && fabs(dj) > 1e-7) || (st == NS_L && dj < -1e-7) || (st == NS_U && dj > 1e-7))) dual_infeasible = 1;
+        }
         }
         { const unsigned char a = L.art[k]; if ((st == NS_L && (a & 1)) || (st == NS_U && (a & 2))) bigm = 1; }
         nh_d[j] = k;
@@ -208,7 +255,7 @@ __global__ __launch_bounds__(NT) void k_prep(LpView L, BatchView Bv, int B)
         Bv.mode[b] = MODE_NONE;
         Bv.verified[b] = 1 | (bigm ? 2 : 0);   // k_init recomputes beta from scratch
         Bv.npend[b] = 0;
-        Bv.pflags[b] = L.objmode ? PF_PRIMAL : 0;       // a new objective on a primal feasible basis: primal simplex steps
+        Bv.pflags[b] = (L.objmode || (METHOD != BSLV_LP_METHOD_DUAL && primal_start)) ? PF_PRIMAL : 0;       // a new objective on a primal feasible basis: primal simplex steps (a primal start: phase 1 first where it is not feasible)
         Bv.stall[b] = 0;
         Bv.flushed[b] = (src == dst) || (L.objmode && !L.rev);      // (in place: the slot already holds the tableau; tableau form with a new objective: it is copied up front, see solve_batch; revised form: the first pass streams B^-1 from the parent, as for solve_batch)
     }
@@ -802,9 +849,11 @@ __device__ __forceinline__ void fetch_row_revised(const LpView &L, const BatchVi
     phase_mark(L, Bv, b, 12, tf);
     if (s_late) { rev_row_slice(L, brow, c.nh, c.row, 0, 1); __syncthreads(); }      // (never seen; the row is this workgroup's to deliver either way)
 }
+// (TABLEAU: an instance that never sees the revised form -- k_select_p1 -- leaves its code, and the LDS it declares, out)
+template <bool TABLEAU = false>
 __device__ __forceinline__ void fetch_row(const LpView &L, const BatchView &Bv, const SelCtx &c, const int r)
 {
-    if (!L.rev) fetch_row_tableau(L, c, r); else fetch_row_revised(L, Bv, c, r); __syncthreads();
+    if (TABLEAU || !L.rev) fetch_row_tableau(L, c, r); else fetch_row_revised(L, Bv, c, r); __syncthreads();
 }
 __device__ __forceinline__ void fetch_col_tableau(const LpView &L, const SelCtx &c, const int q)
 {
@@ -842,9 +891,10 @@ __device__ __forceinline__ void fetch_col_revised(const LpView &L, const SelCtx 
     __syncthreads();
     for (int i = tid; i < M; i += NT) pc[i] = -pc[i];
 }
+template <bool TABLEAU = false>
 __device__ __forceinline__ void fetch_col(const LpView &L, const SelCtx &c, const int q)
 {
-    if (!L.rev) fetch_col_tableau(L, c, q); else fetch_col_revised(L, c, q); __syncthreads();
+    if (TABLEAU || !L.rev) fetch_col_tableau(L, c, q); else fetch_col_revised(L, c, q); __syncthreads();
 }
 
 // the perturbed reduced costs dp, from the true ones
@@ -864,7 +914,9 @@ __device__ __forceinline__ void apply_perturbation(const LpView &L, const SelCtx
     __syncthreads();
 }
 // The perturbed problem is solved: perturbation off (pf); true when wrong signs of the true reduced costs end this selection (primal steps or bound switches repair them)
-__device__ __forceinline__ bool perturbation_off(const LpView &L, const BatchView &Bv, const SelCtx &c, int &pf)
+// (P1: k_select_p1's instance reduces through sv -- __syncthreads_or keeps its word in LDS of its own, see SelShared)
+template <bool P1 = false>
+__device__ __forceinline__ bool perturbation_off(const LpView &L, const BatchView &Bv, const SelCtx &c, int &pf, double *sv = nullptr)
 {
     const int tid = threadIdx.x, NT = (int)blockDim.x, b = c.b, N = L.N;
     int wrong1 = 0, wrongb = 0;
@@ -876,8 +928,8 @@ __device__ __forceinline__ bool perturbation_off(const LpView &L, const BatchVie
             if (st != NS_F && !isinf(LO(L, Bv, b, k)) && !isinf(UP(L, Bv, b, k)) && !L.art[k]) wrongb = 1; else wrong1 = 1;
         }
     }
-    wrong1 = __syncthreads_or(wrong1);
-    wrongb = __syncthreads_or(wrongb);
+    if constexpr (P1) { wrong1 = block_max(wrong1 ? 1.0 : 0.0, sv) > 0.0; wrongb = block_max(wrongb ? 1.0 : 0.0, sv) > 0.0; }
+    else { wrong1 = __syncthreads_or(wrong1); wrongb = __syncthreads_or(wrongb); }
     pf &= ~PF_PERT;
     if (tid == 0 && (wrong1 || wrongb)) atomicAdd(&Bv.xstat[3], 1);
     if (wrong1) {
@@ -897,18 +949,84 @@ __device__ __forceinline__ bool perturbation_off(const LpView &L, const BatchVie
     }
     return false;
 }
-// Primal simplex step on the true reduced costs (clean-up after a perturbation): true with the pivot (r, q), column in pc, row fetched; false: no pivot
-__device__ __forceinline__ bool primal_step(const LpView &L, const BatchView &Bv, const SelCtx &c, const int pf, const bool bland, double *sv, int *si,
-                                            int &r, int &q, bool &below, double &pstep)
+// -1: the basic value bt is below its lower bound, +1: above its upper bound, 0: inside (oracle/lp_dense.c infeas_sign)
+__device__ __forceinline__ int infeas_sign(double lo, double up, double bt)
+{
+    if (!isinf(lo) && bt < lo - btol(lo)) return -1;
+    if (!isinf(up) && bt > up + btol(up)) return +1;
+    return 0;
+}
+// Phase 1 of LP b, before a step: sg[i] = infeas_sign of row i (as a double; sg is the entering column's place, free until the column
+// is fetched).  With an infeasible row the LP is in phase 1 (true) and d1[j] = sum_i sg_i T[i][j] prices it -- T as it is after the pending
+// pivots.  d1 is rebuilt from the rows on entry, after a pass over the tableau (nothing pending) and when the last step moved a row
+// other than the leaving one across a bound (PF_P1_STALE); between those it follows every pivot like the reduced costs do (select_once).
+__device__ __forceinline__ bool phase1_prepare(const LpView &L, const BatchView &Bv, const SelCtx &c, int &pf, double *sg, double *d1, double *sv)
+{
+    const int tid = threadIdx.x, NT = (int)blockDim.x, b = c.b, M = L.M;
+    int ninf = 0;
+    for (int i = tid; i < M; i += NT) {
+        const int k = c.bh[i];
+        const int s = infeas_sign(LO(L, Bv, b, k), UP(L, Bv, b, k), c.beta[i]);
+        sg[i] = (double)s;
+        ninf |= s != 0;
+    }
+    ninf = block_max(ninf ? 1.0 : 0.0, sv) > 0.0;      // (its barriers also put sg in front of the whole workgroup)
+    const int pf0 = pf;
+    if (!ninf) {
+        if (pf & PF_PHASE1) {      // feasible: phase 2, on the true reduced costs
+            pf &= ~(PF_PHASE1 | PF_P1_STALE | PF_P1_KEEP);
+            if (tid == 0) { Bv.pflags[b] = pf; Bv.stall[b] = 0; if (L.trace == b) printf("lp %d it %d phase 1 ends: primal feasible\n", b, Bv.iters[b]); }
+        }
+        return false;
+    }
+    const bool enter = !(pf & PF_PHASE1);
+    if (enter || (pf & PF_P1_STALE) || (c.np == 0 && !(pf & PF_P1_KEEP))) {
+        for (int j = tid; j < L.ld; j += NT) {
+            double acc = 0.0;
+            if (j < L.N)
+                for (int i = 0; i < M; i++) {
+                    const double s = sg[i];
+                    if (s != 0.0) acc += s * virt_entry(c.T0[(size_t)i * L.ld + j], i, j, c.np, c.pd, c.prow0, c.pcol0, L.ld, L.Mp1p);
+                }
+            d1[j] = acc;
+        }
+        if (tid == 0) {
+            atomicAdd(&Bv.xstat[7], 1);
+            if (!(pf & PF_P1_SEEN)) atomicAdd(&Bv.xstat[5], 1);
+            if (enter && L.trace == b) printf("lp %d it %d phase 1 starts\n", b, Bv.iters[b]);
+        }
+        pf = (pf & ~(PF_PERT | PF_PERT_PENDING | PF_P1_STALE)) | PF_PHASE1 | PF_P1_SEEN;      // (phase 1 and a cost perturbation exclude each other: they share dper)
+        if (enter && tid == 0) Bv.stall[b] = 0;
+    }
+    pf &= ~PF_P1_KEEP;
+    if (pf != pf0 && tid == 0) Bv.pflags[b] = pf;
+    __syncthreads();
+    return true;
+}
+// Primal simplex step: true with the pivot (r, q), column in pc, row fetched; false: no pivot.  On the true reduced costs from a primal
+// feasible basis (clean-up after a perturbation, new objectives) -- and, P1 (bslv_lpq_set_method), from any basis: while a basic variable
+// is outside its bounds the step is one of PHASE 1, priced by d1 (phase1_prepare), with the SAME ratio test except that an infeasible
+// basic variable blocks where it reaches the bound it violates and nowhere else (oracle/lp_dense.c primal_simplex).  rsig: infeas_sign
+// the leaving variable had.
+template <bool P1>
+__device__ __forceinline__ bool primal_step(const LpView &L, const BatchView &Bv, const SelCtx &c, int &pf, const bool bland, double *sv, int *si,
+                                            int &r, int &q, bool &below, double &pstep, int &rsig)
 {
     const int tid = threadIdx.x, NT = (int)blockDim.x, b = c.b, M = L.M, N = L.N;
     const double *pc = c.pc;
     double *beta = c.beta;
+    const double *dj = c.drow;               // what prices the step
+    bool ph1 = false;
+    if constexpr (P1) {
+        double *d1 = Bv.dper + (size_t)b * L.ld;
+        ph1 = phase1_prepare(L, Bv, c, pf, c.pc, d1, sv);
+        if (ph1) dj = d1;
+    }
     ValIdx ent{0.0, -1};
     for (int j = tid; j < N; j += NT) {
         const int st = c.nstat[j];
         if (st == NS_S) continue;
-        const double v = c.drow[j];
+        const double v = dj[j];
         double sc = 0.0;
         if (st == NS_L) { if (v < -TOL_DJ) sc = -v; }
         else if (st == NS_U) { if (v > TOL_DJ) sc = v; }
@@ -917,6 +1035,14 @@ __device__ __forceinline__ bool primal_step(const LpView &L, const BatchView &Bv
     }
     ent = block_argmax(ent, sv, si);
     if (ent.i < 0) {
+        if (P1 && ph1) {
+            // nothing lowers the sum of infeasibilities: primal infeasible -- on a recomputed beta (the pass leaves nothing pending: d1 is rebuilt too)
+            if (tid == 0) {
+                if (!(Bv.verified[b] & 1)) { Bv.mode[b] = MODE_REFRESH; Bv.pflags[b] = pf | PF_P1_STALE; }
+                else { Bv.status[b] = BSLV_LP_INFEASIBLE; Bv.mode[b] = MODE_NONE; }
+            }
+            return false;
+        }
         // dual feasible: the dual selection takes over again (it concludes, or repairs what rounding left infeasible)
         if (tid == 0) { Bv.pflags[b] = pf & ~PF_PRIMAL; Bv.stall[b] = 0; }
         return false;
@@ -924,9 +1050,9 @@ __device__ __forceinline__ bool primal_step(const LpView &L, const BatchView &Bv
     if (Bv.iters[b] >= L.maxit) { if (tid == 0) { Bv.status[b] = BSLV_LP_UNDEFINED; Bv.mode[b] = MODE_NONE; } return false; }
     q = ent.i;
     const int stq = c.nstat[q], kq = c.nh[q];
-    const double dq = c.drow[q];
+    const double dq = dj[q];
     const double dir = (stq == NS_U || (stq == NS_F && dq > 0.0)) ? -1.0 : 1.0;
-    fetch_col(L, c, q);
+    fetch_col<P1>(L, c, q);
     double cmax = 0.0;
     for (int i = tid; i < M; i += NT) cmax = fmax(cmax, fabs(pc[i]));
     cmax = block_max(cmax, sv);
@@ -938,12 +1064,19 @@ __device__ __forceinline__ bool primal_step(const LpView &L, const BatchView &Bv
         if (fabs(a) < ptol) continue;
         const int k = c.bh[i];
         const double bt = beta[i];
-        if (a > 0) { const double up = UP(L, Bv, b, k); if (!isinf(up)) tmax = fmin(tmax, fmax(up + (bland ? 0.0 : btol(up)) - bt, 0.0) / a); }
-        else { const double lo = LO(L, Bv, b, k); if (!isinf(lo)) tmax = fmin(tmax, fmax(bt - lo + (bland ? 0.0 : btol(lo)), 0.0) / -a); }
+        int sg = 0;                          // (phase 1: below its lower bound it blocks there, coming from below, and not at the upper one; above likewise)
+        if constexpr (P1) if (ph1) sg = infeas_sign(LO(L, Bv, b, k), UP(L, Bv, b, k), bt);
+        if (a > 0) {
+            if (P1 && sg < 0) { const double lo = LO(L, Bv, b, k); tmax = fmin(tmax, (lo + (bland ? 0.0 : btol(lo)) - bt) / a); }
+            else if (!(P1 && sg > 0)) { const double up = UP(L, Bv, b, k); if (!isinf(up)) tmax = fmin(tmax, fmax(up + (bland ? 0.0 : btol(up)) - bt, 0.0) / a); }
+        } else {
+            if (P1 && sg > 0) { const double up = UP(L, Bv, b, k); tmax = fmin(tmax, (bt - up + (bland ? 0.0 : btol(up))) / -a); }
+            else if (!(P1 && sg < 0)) { const double lo = LO(L, Bv, b, k); if (!isinf(lo)) tmax = fmin(tmax, fmax(bt - lo + (bland ? 0.0 : btol(lo)), 0.0) / -a); }
+        }
     }
     tmax = block_min(tmax, sv);
     if (isinf(tmax)) {
-        if (tid == 0) { Bv.status[b] = BSLV_LP_UNBOUNDED; Bv.mode[b] = MODE_NONE; }
+        if (tid == 0) { Bv.status[b] = (P1 && ph1) ? BSLV_LP_UNEXPECTED : BSLV_LP_UNBOUNDED; Bv.mode[b] = MODE_NONE; }      // (phase 1 has a bounded objective: the oracle says UNEXPECTED too)
         return false;
     }
     ValIdx lv{0.0, -1};
@@ -952,22 +1085,44 @@ __device__ __forceinline__ bool primal_step(const LpView &L, const BatchView &Bv
         if (fabs(a) < ptol) continue;
         const int k = c.bh[i];
         const double bt = beta[i];
-        if (a > 0) { const double up = UP(L, Bv, b, k); if (!isinf(up) && (up - bt) / a <= tmax) lv = better_max(lv, ValIdx{bland ? (double)(L.M + L.N - k) : a, 2 * i + 1}); }
-        else { const double lo = LO(L, Bv, b, k); if (!isinf(lo) && (bt - lo) / -a <= tmax) lv = better_max(lv, ValIdx{bland ? (double)(L.M + L.N - k) : -a, 2 * i}); }
+        int sg = 0;
+        if constexpr (P1) if (ph1) sg = infeas_sign(LO(L, Bv, b, k), UP(L, Bv, b, k), bt);
+        if (a > 0) {
+            if (P1 && sg < 0) { const double lo = LO(L, Bv, b, k); if ((lo - bt) / a <= tmax) lv = better_max(lv, ValIdx{bland ? (double)(L.M + L.N - k) : a, 2 * i}); }
+            else if (!(P1 && sg > 0)) { const double up = UP(L, Bv, b, k); if (!isinf(up) && (up - bt) / a <= tmax) lv = better_max(lv, ValIdx{bland ? (double)(L.M + L.N - k) : a, 2 * i + 1}); }
+        } else {
+            if (P1 && sg > 0) { const double up = UP(L, Bv, b, k); if ((bt - up) / -a <= tmax) lv = better_max(lv, ValIdx{bland ? (double)(L.M + L.N - k) : -a, 2 * i + 1}); }
+            else if (!(P1 && sg < 0)) { const double lo = LO(L, Bv, b, k); if (!isinf(lo) && (bt - lo) / -a <= tmax) lv = better_max(lv, ValIdx{bland ? (double)(L.M + L.N - k) : -a, 2 * i}); }
+        }
     }
     lv = block_argmax(lv, sv, si);
     double tstep = INFINITY;
+    rsig = 0;
     if (lv.i >= 0) {
         const int i = lv.i >> 1, k = c.bh[i];
         const double a = pc[i] * dir;
         tstep = fmax(((lv.i & 1) ? UP(L, Bv, b, k) - beta[i] : beta[i] - LO(L, Bv, b, k)) / fabs(a), 0.0);
+        if constexpr (P1) if (ph1) {
+            rsig = infeas_sign(LO(L, Bv, b, k), UP(L, Bv, b, k), beta[i]);
+            if (rsig) tstep = ((lv.i & 1) ? beta[i] - UP(L, Bv, b, k) : LO(L, Bv, b, k) - beta[i]) / fabs(a);      // (from outside to the bound it violates)
+        }
     }
     if (lv.i < 0 || gap <= tstep) {
         // the entering variable reaches its own other bound first: no pivot
         __syncthreads();
-        for (int i = tid; i < M; i += NT) beta[i] = fma(pc[i], dir * gap, beta[i]);
+        int moved = 0;                       // phase 1: a row crossed a bound (under the ratio test above none should)
+        for (int i = tid; i < M; i += NT) {
+            const double bn = fma(pc[i], dir * gap, beta[i]);
+            if constexpr (P1) if (ph1) { const int k = c.bh[i]; const double lo = LO(L, Bv, b, k), up = UP(L, Bv, b, k); moved |= infeas_sign(lo, up, beta[i]) != infeas_sign(lo, up, bn); }
+            beta[i] = bn;
+        }
+        if constexpr (P1) if (ph1) {
+            moved = block_max(moved ? 1.0 : 0.0, sv) > 0.0;
+            pf = (pf | PF_P1_KEEP) | (moved ? PF_P1_STALE : 0);      // (no pivot: d1 stands as it is)
+            if (tid == 0) { Bv.pflags[b] = pf; atomicAdd(&Bv.xstat[6], 1); }
+        }
         if (tid == 0) {
-            beta[M] = fma(dq, dir * gap, beta[M]);
+            beta[M] = fma((P1 && ph1) ? c.drow[q] : dq, dir * gap, beta[M]);      // (the objective moves by the TRUE reduced cost)
             if (stq == NS_L) { c.nstat[q] = NS_U; c.xN[q] = UP(L, Bv, b, kq); } else { c.nstat[q] = NS_L; c.xN[q] = LO(L, Bv, b, kq); }
             if (L.trace == b) printf("lp %d it %d primal: column %d (var %d) d %.3e switches bound\n", b, Bv.iters[b], q, kq, dq);
             Bv.verified[b] &= 2;
@@ -979,14 +1134,20 @@ __device__ __forceinline__ bool primal_step(const LpView &L, const BatchView &Bv
     r = lv.i >> 1;
     below = !(lv.i & 1);                   // the leaving variable goes to its lower bound
     pstep = fabs(dq) * tstep / (1.0 + fabs(beta[M]));      // (what the step moves the objective by, relative: the ratio test's tolerance gives a degenerate step a length of 1e-9, not 0)
-    fetch_row(L, Bv, c, r);
+    if constexpr (P1) if (ph1) { pstep = fabs(dq) * tstep; if (tid == 0) atomicAdd(&Bv.xstat[6], 1); }      // (phase 1: by how much the sum of infeasibilities falls)
+    fetch_row<P1>(L, Bv, c, r);
     return true;
 }
 // Bound flipping ratio test: sorted breakpoints of row r; a boxed candidate switches bound (sflag) while the row stays infeasible.  Returns the number of switches (the first of sidx)
+// (P1: the instance of k_select_p1, which hands in its counters -- see SelShared)
+template <bool P1 = false>
 __device__ __forceinline__ int flip_breakpoints(const LpView &L, const BatchView &Bv, const SelCtx &c, const int r, const bool below, const double sgn, const double ptol,
-                                                const double *dwork, const int cap2, double *skey, int *sidx, unsigned char *sflag)
+                                                const double *dwork, const int cap2, double *skey, int *sidx, unsigned char *sflag, int *cnt3 = nullptr)
 {
-    __shared__ int s_cnt, s_nboxed, s_stop;
+    int *p_cnt, *p_nboxed, *p_stop;
+    if constexpr (P1) { p_cnt = cnt3; p_nboxed = cnt3 + 1; p_stop = cnt3 + 2; }
+    else { __shared__ int l_cnt, l_nboxed, l_stop; p_cnt = &l_cnt; p_nboxed = &l_nboxed; p_stop = &l_stop; }
+    int &s_cnt = *p_cnt, &s_nboxed = *p_nboxed, &s_stop = *p_stop;
     const int tid = threadIdx.x, NT = (int)blockDim.x, b = c.b, N = L.N;
     const double *row = c.row;
     if (tid == 0) { s_cnt = 0; s_nboxed = 0; s_stop = 0; }
@@ -1075,15 +1236,28 @@ __device__ __forceinline__ bool switch_bounds(const LpView &L, const BatchView &
 // of passes over N entries by ONE workgroup, and four times the threads shorten every pass.
 // ONE selection of LP b by the calling workgroup (every `return` below is taken by the whole workgroup).  Returns false when the LP
 // cannot select again before the next pass over its tableau (finished, waiting for a refresh, KP pivots pending).
-template <bool EXT>
-__device__ __forceinline__ bool select_once(const LpView &L, const BatchView &Bv, const int b, const int cap2)
+// P1 (with EXT): the primal steps include phase 1 (bslv_lpq_set_method; k_select_p1) -- an instance of its own, so that the kernels of
+// the default method stay what they were.
+// The LDS of a selection is declared where it is used, in select_once and flip_breakpoints, for the kernels that always were.  A device
+// function that is not inlined and declares LDS is laid out per MODULE, though: one more kernel calling one (select_once_p1) would
+// move the others' variables into a table looked up by kernel.  So k_select_p1 declares everything itself and hands it down.
+struct SelShared { double sv[NT_BIG / WAVE]; int si[NT_BIG / WAVE]; PivDesc d; int cnt3[3]; unsigned char *dyn; };
+template <bool EXT, bool P1 = false>
+__device__ __forceinline__ bool select_once(const LpView &L, const BatchView &Bv, const int b, const int cap2, SelShared *xs = nullptr)
 {
-    __shared__ double sv[NT_BIG / WAVE];
-    __shared__ int si[NT_BIG / WAVE];
+    static_assert(EXT || !P1, "phase 1 lives in the extended selection");
+    double *sv; int *si; PivDesc *p_d; unsigned char *dyn;
+    if constexpr (P1) { sv = xs->sv; si = xs->si; p_d = &xs->d; dyn = xs->dyn; }
+    else {
+        __shared__ double l_sv[NT_BIG / WAVE];
+        __shared__ int l_si[NT_BIG / WAVE];
+        __shared__ PivDesc l_d;
+        extern __shared__ unsigned char dyn_sel[];
+        sv = l_sv; si = l_si; p_d = &l_d; dyn = dyn_sel;
+    }
+    PivDesc &s_d = *p_d;
     const int NT = (int)blockDim.x;
-    __shared__ PivDesc s_d;
-    extern __shared__ unsigned char dyn_sel[];
-    double *skey = reinterpret_cast<double *>(dyn_sel);          // [cap2] breakpoints |d_j| / |alpha_j| of the candidates
+    double *skey = reinterpret_cast<double *>(dyn);          // [cap2] breakpoints |d_j| / |alpha_j| of the candidates
     int *sidx = reinterpret_cast<int *>(skey + cap2);             // [cap2] their columns
     unsigned char *sflag = reinterpret_cast<unsigned char *>(sidx + cap2);   // [N] 1 = column switches bound in this iteration
     if (Bv.status[b] != ST_RUNNING || Bv.mode[b] == MODE_REFRESH) return false;
@@ -1116,9 +1290,10 @@ __device__ __forceinline__ bool select_once(const LpView &L, const BatchView &Bv
     bool below = false, incr = false;        // incr: bound switches of this iteration already carried into beta
     const bool primal = EXT && (pf & PF_PRIMAL);
     double pstep = 1.0;                      // length of a primal step (clean-up)
+    int rsig = 0;                            // phase 1: which bound the leaving variable violated
 
     if (primal) {
-        if (!primal_step(L, Bv, c, pf, bland, sv, si, r, q, below, pstep)) return true;
+        if (!primal_step<P1>(L, Bv, c, pf, bland, sv, si, r, q, below, pstep, rsig)) return true;
     } else {
     // ---- dual simplex step ----
     unsigned long long tk = (L.probe & 8) ? wall_clock64() : 0ull;
@@ -1131,7 +1306,7 @@ __device__ __forceinline__ bool select_once(const LpView &L, const BatchView &Bv
     best = block_argmax(best, sv, si);
     if (best.i < 0) {
         if (EXT && (pf & PF_PERT)) {
-            if (perturbation_off(L, Bv, c, pf)) return true;
+            if (perturbation_off<P1>(L, Bv, c, pf, sv)) return true;
             dwork = drow;
         }
         conclude_optimal(L, Bv, c, Bv.iters[b], Bv.verified[b], NT, sv);
@@ -1141,7 +1316,7 @@ __device__ __forceinline__ bool select_once(const LpView &L, const BatchView &Bv
     r = best.i >> 1; below = best.i & 1;
     const double sgn = below ? 1.0 : -1.0;
     phase_mark(L, Bv, b, 0, tk);
-    fetch_row(L, Bv, c, r);
+    fetch_row<P1>(L, Bv, c, r);
     phase_mark(L, Bv, b, 1, tk);
 
     // pass 0: row scale for the relative pivot tolerance
@@ -1149,7 +1324,7 @@ __device__ __forceinline__ bool select_once(const LpView &L, const BatchView &Bv
     for (int j = tid; j < N; j += NT) rmax = fmax(rmax, fabs(row[j]));
     rmax = block_max(rmax, sv);
     const double ptol = TOL_PIV * (1.0 + rmax);
-    if constexpr (EXT) nflip = flip_breakpoints(L, Bv, c, r, below, sgn, ptol, dwork, cap2, skey, sidx, sflag);
+    if constexpr (EXT) nflip = flip_breakpoints<P1>(L, Bv, c, r, below, sgn, ptol, dwork, cap2, skey, sidx, sflag, P1 ? xs->cnt3 : nullptr);
     // pass 1: Harris bound on the dual step
     phase_mark(L, Bv, b, 2, tk);
     // (both passes fetch FOUR columns per thread and iteration with all loads issued first: on wide problems -- ex09: 37 000 columns,
@@ -1198,7 +1373,7 @@ __device__ __forceinline__ bool select_once(const LpView &L, const BatchView &Bv
     }
     bool col_ready = primal;                                         // pc[] holds the entering column (primal steps fetch it first)
     unsigned long long tk2 = (L.probe & 8) ? wall_clock64() : 0ull;
-    if (L.rev && !col_ready) { fetch_col(L, c, q); col_ready = true; }    // (the tableau form gathers its column in Phase D)
+    if (!P1 && L.rev && !col_ready) { fetch_col(L, c, q); col_ready = true; }    // (the tableau form gathers its column in Phase D)
     phase_mark(L, Bv, b, 5, tk2);
     // Phase C: the descriptor, the basis heads
     if (tid == 0) {
@@ -1206,7 +1381,7 @@ __device__ __forceinline__ bool select_once(const LpView &L, const BatchView &Bv
         // revised form: the pivot element comes out of TWO products -- rho K_q (the row) and the column B^-1 K_q -- which agree as long as
         // B^-1 is accurate.  Nothing refactorises it; when the two drift apart the LP is given up as UNDEFINED and the caller's retry
         // (bslv_lp.c:222-227: from the standard basis, an exact identity) takes over instead of a solve on a corrupted inverse
-        if (L.rev && !(fabs(trq - pc[r]) <= 1e-8 * (1.0 + fabs(trq)))) {
+        if (!P1 && L.rev && !(fabs(trq - pc[r]) <= 1e-8 * (1.0 + fabs(trq)))) {
             Bv.status[b] = BSLV_LP_UNDEFINED; Bv.mode[b] = MODE_NONE;
             if (L.trace == b) printf("lp %d it %d: pivot element from the row %.17g, from the column %.17g: B^-1 has drifted\n", b, Bv.iters[b], trq, pc[r]);
             s_d.r = -1;
@@ -1232,6 +1407,13 @@ __device__ __forceinline__ bool select_once(const LpView &L, const BatchView &Bv
         if (i == r) { pc[i] = 0.0; beta[i] = d.enter_val; continue; }
         const double f = (i == M ? drow[q] : (col_ready ? pc[i] : virt_entry(c.T0[(size_t)i * ld + q], i, q, np, c.pd, c.prow0, c.pcol0, ld, L.Mp1p))) * d.p;
         pc[i] = f;
+        if constexpr (P1) {      // phase 1: did the step move a row other than the leaving one across a bound?  (d1 is then rebuilt)
+            if ((pf & PF_PHASE1) && i < M) {
+                const int k = c.bh[i];
+                const double lo = LO(L, Bv, b, k), up = UP(L, Bv, b, k);
+                if (infeas_sign(lo, up, beta[i]) != infeas_sign(lo, up, fma(-f, d.pbeta, beta[i]))) Bv.pflags[b] = pf | PF_P1_STALE;      // (every writer writes the same word)
+            }
+        }
         beta[i] = fma(-f, d.pbeta, beta[i]);
     }
     __syncthreads();
@@ -1239,11 +1421,12 @@ __device__ __forceinline__ bool select_once(const LpView &L, const BatchView &Bv
         const double fM = pc[M];
         for (int j = tid; j < N; j += NT) drow[j] = j == q ? fM : fma(-fM, row[j], drow[j]);
         if constexpr (EXT) {
-            if (pf & PF_PERT) {
+            if (pf & (PF_PERT | (P1 ? PF_PHASE1 : 0))) {
                 double *dp = Bv.dper + (size_t)b * ld;
                 const double fP = dp[q] * d.p;
                 __syncthreads();
-                for (int j = tid; j < N; j += NT) dp[j] = j == q ? fP : fma(-fP, row[j], dp[j]);
+                // (phase 1: d1 follows the pivot as the reduced costs do; the leaving variable's phase-1 cost drops to zero, which is its own entry's alone)
+                for (int j = tid; j < N; j += NT) dp[j] = j == q ? ((P1 && (pf & PF_PHASE1)) ? fP - (double)rsig : fP) : fma(-fP, row[j], dp[j]);
             }
         }
     }
@@ -1439,6 +1622,7 @@ __device__ __forceinline__ bool select_once_cached(const LpView &L, const BatchV
 }
 // (the extended instance is a function of its own, as the compiler always had it: inlined into the 1024-thread kernel it spills 300 registers, called none)
 __device__ __noinline__ bool select_once_ext(const LpView &L, const BatchView &Bv, const int b, const int cap2) { return select_once<true>(L, Bv, b, cap2); }
+__device__ __noinline__ bool select_once_p1(const LpView &L, const BatchView &Bv, const int b, const int cap2, SelShared *xs) { return select_once<true, true>(L, Bv, b, cap2, xs); }
 // One launch selects up to nsel pivots per LP, one after the other, by the same workgroup: the KP selections between two passes
 // over the tableau depend only on the LP's own vectors (beta, the reduced-cost row, the pending pivot rows and multipliers) -- no
 // grid-wide dependency asks for a launch each (rounds 1-3 launched this kernel KP times per pass, 17 % of all GPU time in
@@ -1456,6 +1640,22 @@ __global__ __launch_bounds__(NT_BIG) void k_select(LpView L, BatchView Bv, const
     if (L.helpers > 1) {                       // every path of the LP's own workgroup ends here: the helpers may go
         __syncthreads();
         if (threadIdx.x == 0) __hip_atomic_store(&Bv.hmail[(size_t)b * 8], (L.launch_id << 8) | 0xFF, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+// k_select<true> with phase 1 in its primal steps: what the PRIMAL and REPAIR methods launch (tableau form; the LPs of a batch that
+// are in phase 1, in phase 2 and in the dual simplex share the launch)
+__global__ __launch_bounds__(NT_BIG) void k_select_p1(LpView L, BatchView Bv, const int *active, int nact, int cap2, int nsel)
+{
+    __shared__ SelShared xs;
+    extern __shared__ unsigned char dyn_p1[];
+    if ((int)blockIdx.x >= nact) return;
+    const int b = active[blockIdx.x];
+    if (threadIdx.x == 0) xs.dyn = dyn_p1;
+    __syncthreads();
+    for (int sdx = 0; sdx < nsel; sdx++) {
+        if (sdx) __syncthreads();
+        if (!select_once_p1(L, Bv, b, cap2, &xs)) break;
     }
 }
 
@@ -1669,10 +1869,13 @@ struct bslv_lpq {
     double *dper_d = nullptr; int *pflags_d = nullptr, *stall_d = nullptr, *xstat_d = nullptr;
     double *cvals_d = nullptr; size_t cvals_cap = 0;     // objective coefficients of solve_batch_obj
     long last_ext[5] = {0, 0, 0, 0, 0};
+    int method = BSLV_LP_METHOD_DUAL;  // bslv_lpq_set_method (BSLV_LP_METHOD at create)
+    long last_p1[3] = {0, 0, 0};       // phase 1 of the last batch: LPs that entered it, its iterations, rebuilds of its pricing vector
     long last_passes = 0;              // (LP, pass) pairs of the last batch: how many tableaux k_flush read and wrote
     long last_launches = 0;            // k_flush launches of the last batch: one per lock-step round + one per pass made on request (bslv_lpq_materialise)
     size_t select_lds_max = 64 * 1024; // dynamic LDS of k_select<true> (candidate sort of the bound flipping ratio test)
     size_t select0_lds_max = 64 * 1024; // ... of k_select<false> (revised form: rho)
+    size_t select1_lds_max = 64 * 1024; // ... of k_select_p1
     size_t price_lds_max = 64 * 1024;  // ... of k_rev_price (revised form, new objective: y)
     int obj_batches = 0;               // solve_batch_obj calls so far (BSLV_LP_OBJ_UNDEFINED counts them)
     bool has_boxed = false;            // some variable outside the per-LP range has two finite, non-artificial bounds
@@ -1936,6 +2139,10 @@ static int raw_create(bslv_lpq **out, int M, int N, const double *A, const doubl
             else (void)hipGetLastError();
         }
     }
+    // BSLV_LP_METHOD=dual|primal|repair: the method the engine starts with (bslv_lpq_set_method); the revised form has the dual one only
+    if (const char *e = getenv("BSLV_LP_METHOD")) {
+        if (!rev) h->method = !strcmp(e, "primal") ? BSLV_LP_METHOD_PRIMAL : !strcmp(e, "repair") ? BSLV_LP_METHOD_REPAIR : BSLV_LP_METHOD_DUAL;
+    }
     *out = h;
     return 0;
 }
@@ -2182,6 +2389,7 @@ static void plan_init(bslv_lpq *h, int B, const int *src, InitPlan *plan)
 // solve: the tests change them between solves of one process), launch_select launches once per round
 struct SelectPlan {
     bool ext; int cap2;     // the extended selection k_select<true>; its candidate arrays in LDS (0: rows too long for the in-LDS sort, no long-step part)
+    bool p1;                // ... with phase 1 in its primal steps (k_select_p1): the PRIMAL and REPAIR methods
     int nt, per_launch; size_t lds;     // threads per workgroup; selections per launch; dynamic LDS of a k_select launch
     int cpt;                // columns per thread of k_select_cached (plain dual selection, tableau form, NT threads), 0: k_select
 };
@@ -2189,18 +2397,20 @@ static int plan_select(bslv_lpq *h, int B, const double *vlo, const double *vup,
 {
     LpView &L = h->L;
     // bound flipping ratio test only where a variable has two finite, non-artificial bounds
-    bool bfrt = h->has_boxed || L.objmode || h->force_ext;        // (the primal steps live in the extended selection)
+    const bool p1 = h->method != BSLV_LP_METHOD_DUAL && !L.objmode && !L.rev;      // (objective batches keep their own start)
+    bool bfrt = h->has_boxed || L.objmode || h->force_ext || p1;        // (the primal steps live in the extended selection)
     if (!bfrt && L.vcnt > 0)
         for (size_t k = 0; k < (size_t)B * L.vcnt && !bfrt; k++) bfrt = std::isfinite(vlo[k]) && std::isfinite(vup[k]) && vlo[k] < vup[k];
-    if (getenv("BSLV_LP_EXT")) bfrt = atoi(getenv("BSLV_LP_EXT")) != 0;      // test hook: force the extended selection on / off
+    if (getenv("BSLV_LP_EXT")) bfrt = p1 || atoi(getenv("BSLV_LP_EXT")) != 0;      // test hook: force the extended selection on / off
     int cap2 = 2;
     while (cap2 < L.N) cap2 <<= 1;
     size_t sel_lds = (size_t)cap2 * (sizeof(double) + sizeof(int)) + (size_t)L.N;
     if (bfrt && sel_lds > 144 * 1024) { cap2 = 0; sel_lds = (size_t)L.N; }     // rows too long for the in-LDS sort: extended selection without the long-step part
-    if (bfrt && sel_lds > h->select_lds_max) {
-        if (sel_lds <= 144 * 1024 && hipFuncSetAttribute((const void *)k_select<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sel_lds) == hipSuccess) h->select_lds_max = sel_lds;
+    if (bfrt && sel_lds > (p1 ? h->select1_lds_max : h->select_lds_max)) {
+        if (sel_lds <= 144 * 1024 && hipFuncSetAttribute(p1 ? (const void *)k_select_p1 : (const void *)k_select<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sel_lds) == hipSuccess) (p1 ? h->select1_lds_max : h->select_lds_max) = sel_lds;
         else bfrt = false;
     }
+    if (p1 && !bfrt) { set_error("bslv_lpq_solve_batch: rows too long for the extended selection the primal method needs (N=%d)", L.N); return BSLV_E_CAPACITY; }
     if (L.objmode && !bfrt) { set_error("bslv_lpq_solve_batch_obj: rows too long for the extended selection (N=%d)", L.N); return BSLV_E_CAPACITY; }
     // revised form: rho (a row of B^-1) in LDS behind the selection's own arrays, when there is room
     plan->lds = bfrt ? sel_lds : 0;
@@ -2215,7 +2425,7 @@ static int plan_select(bslv_lpq *h, int B, const double *vlo, const double *vup,
         }
         if (ok) { L.rho_off = (int)off; plan->lds = want; }
     }
-    plan->ext = bfrt; plan->cap2 = bfrt ? cap2 : 0;
+    plan->ext = bfrt; plan->cap2 = bfrt ? cap2 : 0; plan->p1 = p1;
     // (measured, BSLV_SELECT_NT: S-degenerate, 2011 columns, 64 LPs per step: LP phase 67.6 / 52.0 / 46.6 ms with 256 / 512 / 1024 threads;
     //  S-degenerate-q4 to termination with 256 LPs per step 12.1 -> 10.4 s; same pivots)
     plan->nt = getenv("BSLV_SELECT_NT") ? atoi(getenv("BSLV_SELECT_NT")) : (L.N >= 1536 ? NT_BIG : NT);
@@ -2240,6 +2450,7 @@ static void launch_select(bslv_lpq *h, const SelectPlan &p, const BatchView &bv,
         if (p.cpt == 2) hipLaunchKernelGGL(k_select_cached<2>, dim3(running), dim3(NT), 0, s, L, bv, h->active_d, running, p.per_launch);
         else if (p.cpt == 4) hipLaunchKernelGGL(k_select_cached<4>, dim3(running), dim3(NT), 0, s, L, bv, h->active_d, running, p.per_launch);
         else if (p.cpt == 6) hipLaunchKernelGGL(k_select_cached<6>, dim3(running), dim3(NT), 0, s, L, bv, h->active_d, running, p.per_launch);
+        else if (p.p1) hipLaunchKernelGGL(k_select_p1, dim3(running), dim3(p.nt), p.lds, s, L, bv, h->active_d, running, p.cap2, p.per_launch);
         else if (p.ext) hipLaunchKernelGGL(k_select<true>, dim3(running, helpers), dim3(p.nt), p.lds, s, L, bv, h->active_d, running, p.cap2, p.per_launch);
         else hipLaunchKernelGGL(k_select<false>, dim3(running, helpers), dim3(p.nt), p.lds, s, L, bv, h->active_d, running, 0, p.per_launch);
     }
@@ -2314,6 +2525,7 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
     if (h && h->ps.empty_box && B > 0 && status) {        // (bslv_lpq_set_bounds left a folded row no room: fold_bounds)
         for (int b = 0; b < B; b++) { status[b] = BSLV_LP_INFEASIBLE; if (iters) iters[b] = 0; }
         h->last_iters = 0; h->last_pivots = 0; h->last_passes = 0; h->last_launches = 0;
+        for (int k = 0; k < 3; k++) h->last_p1[k] = 0;
         return 0;
     }
     if (!h || B < 0 || (B > 0 && (!src || !dst)) || (B > 0 && h->L.vcnt > 0 && (!vlo || !vup))) {
@@ -2358,7 +2570,12 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
     BatchView bv = bview(h);
     bv.cvals = h->cvals_d;
     const int tiles = (L.mrows + TR - 1) / TR;
-    hipLaunchKernelGGL(k_prep, dim3(B), dim3(NT), 0, s, L, bv, B);
+    {   // (objective batches keep their own start; the revised form knows the dual method only: bslv_lpq_set_method)
+        const int method = (L.objmode || L.rev) ? BSLV_LP_METHOD_DUAL : h->method;
+        if (method == BSLV_LP_METHOD_PRIMAL) hipLaunchKernelGGL(k_prep<BSLV_LP_METHOD_PRIMAL>, dim3(B), dim3(NT), 0, s, L, bv, B);
+        else if (method == BSLV_LP_METHOD_REPAIR) hipLaunchKernelGGL(k_prep<BSLV_LP_METHOD_REPAIR>, dim3(B), dim3(NT), 0, s, L, bv, B);
+        else hipLaunchKernelGGL(k_prep<BSLV_LP_METHOD_DUAL>, dim3(B), dim3(NT), 0, s, L, bv, B);
+    }
     if (L.rev && L.objmode) {      // new objective: the reduced-cost row from the parent's B^-1 (k_rev_u takes beta[M] = d . x_N from it)
         const size_t ylds = (size_t)L.ldt * sizeof(double);
         bool in_lds = ylds <= h->price_lds_max;
@@ -2473,7 +2690,7 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
     }
     h->last_iters = it;
     h->last_launches = it;
-    { int xs[5]; HIP_TRY(hipMemcpy(xs, h->xstat_d, sizeof xs, hipMemcpyDeviceToHost)); for (int k = 0; k < 5; k++) h->last_ext[k] = xs[k]; }
+    { int xs[8]; HIP_TRY(hipMemcpy(xs, h->xstat_d, sizeof xs, hipMemcpyDeviceToHost)); for (int k = 0; k < 5; k++) h->last_ext[k] = xs[k]; for (int k = 0; k < 3; k++) h->last_p1[k] = xs[5 + k]; }
     if (h->profile) {
         double ms = 0;
         for (size_t e = 0; e < nev; e++) { float t = 0; (void)hipEventElapsedTime(&t, h->evpool[e].first, h->evpool[e].second); ms += t; }
@@ -2555,7 +2772,9 @@ static int get_mapped(bslv_lpq *h, int B, const int *slot, int first, int cnt, i
         auto on_row_bound = [&](int j) -> int {            // folded row whose bound column j sits on, or -1
             if (!(d[Mi + j] != 0.0)) return -1;
             const double xl = std::fabs(x[Mi + j] - P.clo[j]), xu = std::fabs(x[Mi + j] - P.cup[j]);
-            const bool at_lo = !(xu < xl);
+            // (on both at once -- the folded rows left the column no room, lower bound from one source, upper from another: the
+            // reduced cost belongs to the bound of its sign, d > 0 to the lower one)
+            const bool at_lo = xl == xu ? d[Mi + j] > 0.0 : !(xu < xl);
             const int src = at_lo ? P.lo_src[j] : P.up_src[j];
             if (src < 0) return -1;
             // (the row's bound and the column's own may coincide: then the column keeps the reduced cost -- either split is a dual solution)
@@ -2613,6 +2832,21 @@ int bslv_lpq_set_extended(bslv_lpq *h, int on)
     return 0;
 }
 int bslv_lpq_get_extended(const bslv_lpq *h) { return h && h->force_ext; }
+// The simplex method of every later solve_batch (lp_set_options, bslv_lp.c:153-217, is where the reference chooses GLPK's): see bslv_hip.h
+int bslv_lpq_set_method(bslv_lpq *h, int method)
+{
+    if (!h || method < BSLV_LP_METHOD_DUAL || method > BSLV_LP_METHOD_REPAIR) { set_error("bslv_lpq_set_method: bad argument (method %d)", method); return BSLV_E_ARG; }
+    if (h->L.rev && method != BSLV_LP_METHOD_DUAL) { set_error("bslv_lpq_set_method: the revised form solves by the dual simplex only (method %d asked for)", method); return BSLV_E_ARG; }
+    h->method = method;
+    return 0;
+}
+int bslv_lpq_get_method(const bslv_lpq *h) { return h ? h->method : BSLV_LP_METHOD_DUAL; }
+int bslv_lpq_last_phase1_stats(const bslv_lpq *h, long out[3])
+{
+    if (!h || !out) return BSLV_E_ARG;
+    for (int k = 0; k < 3; k++) out[k] = h->last_p1[k];
+    return 0;
+}
 int bslv_lpq_last_ext_stats(const bslv_lpq *h, long out[4])
 {
     if (!h || !out) return BSLV_E_ARG;

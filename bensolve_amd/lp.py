@@ -185,6 +185,17 @@ class LpEngine:
         self.lib.bslv_lpq_set_extended.argtypes = [ctypes.c_void_p, ctypes.c_int]
         check(self.lib.bslv_lpq_set_extended(self.h, int(bool(on))))
 
+    def set_method(self, m):
+        """the simplex method of every later solve_batch: 0 dual (default), 1 primal with a phase 1, 2 dual with a primal start
+        for the LPs the dual simplex cannot start (bslv_lpq_set_method, include/bslv_hip.h).  Returns the library's code (0, or
+        BSLV_E_ARG for an unknown method or the revised form)."""
+        self.lib.bslv_lpq_set_method.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        return int(self.lib.bslv_lpq_set_method(self.h, int(m)))
+
+    def get_method(self):
+        self.lib.bslv_lpq_get_method.argtypes = [ctypes.c_void_p]
+        return int(self.lib.bslv_lpq_get_method(self.h))
+
     def last_stats(self):
         it = ctypes.c_int()
         piv = ctypes.c_long()
@@ -202,6 +213,9 @@ class LpEngine:
         self.lib.bslv_lpq_last_flip_updates.argtypes = [ctypes.c_void_p]
         self.lib.bslv_lpq_last_init_chunks.restype = ctypes.c_long
         self.lib.bslv_lpq_last_init_chunks.argtypes = [ctypes.c_void_p]
-        return dict(init_chunks=self.lib.bslv_lpq_last_init_chunks(self.h), lockstep_iters=it.value, pivots=piv.value, update_ms=ums.value, total_ms=tms.value, passes=self.lib.bslv_lpq_last_passes(self.h), launches=self.lib.bslv_lpq_last_launches(self.h),
+        p1 = (ctypes.c_long * 3)()
+        self.lib.bslv_lpq_last_phase1_stats.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        self.lib.bslv_lpq_last_phase1_stats(self.h, p1)
+        return dict(phase1_lps=int(p1[0]), phase1_iterations=int(p1[1]), phase1_rebuilds=int(p1[2]), init_chunks=self.lib.bslv_lpq_last_init_chunks(self.h), lockstep_iters=it.value, pivots=piv.value, update_ms=ums.value, total_ms=tms.value, passes=self.lib.bslv_lpq_last_passes(self.h), launches=self.lib.bslv_lpq_last_launches(self.h),
                     flip_iterations=ext[0], perturbations=ext[1], primal_steps=ext[2], wrong_sign_removals=ext[3],
                     flip_vector_updates=self.lib.bslv_lpq_last_flip_updates(self.h))

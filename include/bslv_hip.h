@@ -147,6 +147,26 @@ long bslv_lpq_last_init_chunks(const bslv_lpq *h);
  * (bslv_lp.c:222-227 is the reference's two-stage retry).  Same optimal values, other pivots. */
 int  bslv_lpq_set_extended(bslv_lpq *h, int on);
 int  bslv_lpq_get_extended(const bslv_lpq *h);
+/* THE SIMPLEX METHOD of every later solve_batch of this engine (the reference hands its choice to GLPK: lp_set_options,
+ * bslv_lp.c:153-217 -- PRIMAL_SIMPLEX / DUAL_SIMPLEX / DUAL_PRIMAL_SIMPLEX become GLP_PRIMAL / GLP_DUAL / GLP_DUALP, and GLPK's
+ * primal simplex has a phase 1 of its own).
+ *   DUAL    the default, and the engine as it was: LP b needs a dual feasible start in slot src[b], else BSLV_LP_UNDEFINED.
+ *   PRIMAL  LP b starts from the basis of src[b] as it stands: the nonbasic variables keep their side where the new bounds allow it,
+ *           a dual infeasible start is not an error.  While a basic variable is outside its bounds the LP runs a primal PHASE 1
+ *           (sum of infeasibilities, Dantzig pricing, Harris ratio test in which an infeasible basic variable blocks at the bound
+ *           it violates: oracle/lp_dense.c primal_simplex), then primal simplex steps on the true reduced costs.  The only dual
+ *           simplex steps are the ones that conclude a primal clean-up today (rounding left a bound violated).
+ *   REPAIR  the dual simplex, except that an LP whose start is dual infeasible is started as under PRIMAL instead of coming back
+ *           UNDEFINED (GLP_DUALP: "dual, and primal if it fails").
+ * Both imply the extended selection (the primal steps live there).  Objective batches (solve_batch_obj) keep their own start.
+ * Not for the revised form: there a method other than DUAL is BSLV_E_ARG.  BSLV_LP_METHOD=dual|primal|repair sets the method an
+ * engine is created with (ignored by an engine that comes up in the revised form).
+ * bslv_lpq_last_phase1_stats, of the last solve_batch: [0] LPs that entered phase 1, [1] phase-1 iterations (pivots + bound
+ * switches), [2] rebuilds of the phase-1 pricing vector from the tableau rows (it is otherwise updated with every pivot). */
+enum { BSLV_LP_METHOD_DUAL = 0, BSLV_LP_METHOD_PRIMAL = 1, BSLV_LP_METHOD_REPAIR = 2 };
+int  bslv_lpq_set_method(bslv_lpq *h, int method);
+int  bslv_lpq_get_method(const bslv_lpq *h);
+int  bslv_lpq_last_phase1_stats(const bslv_lpq *h, long out[3]);
 
 /* ------------------------------------------------------------------------------------------
  * 2. Polyhedron engine  (replaces bslv_poly.h:90-118)
