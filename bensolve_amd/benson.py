@@ -134,7 +134,26 @@ class BensonEngine:
         keys = ("lps", "cuts", "redundant", "confirmed", "failed", "pivots", "lockstep", "left")
         out = dict(zip(keys, list(stats)))
         out.update(ms_lp=ms[0], ms_poly=ms[1], ms_total=ms[2])
+        if self.get_canonical():
+            out["tie_pivots"] = self.canonical_stats()["last"]["tie_pivots"]
         return out
+
+    def set_canonical(self, on):
+        """cuts from the canonical optimal duals (bslv_benson_set_canonical, include/bslv_hip.h); off by default"""
+        self.lib.bslv_benson_set_canonical.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        check(self.lib.bslv_benson_set_canonical(self.h, int(bool(on))))
+
+    def get_canonical(self):
+        self.lib.bslv_benson_get_canonical.argtypes = [ctypes.c_void_p]
+        return int(self.lib.bslv_benson_get_canonical(self.h))
+
+    def canonical_stats(self):
+        """tie phase of the LPs of the last solve_local and of all so far (bslv_benson_canonical_stats)"""
+        last, tot = (ctypes.c_long * 4)(), (ctypes.c_long * 4)()
+        self.lib.bslv_benson_canonical_stats.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        check(self.lib.bslv_benson_canonical_stats(self.h, last, tot))
+        keys = ("entered", "tie_pivots", "no_candidate", "capped")
+        return dict(last=dict(zip(keys, list(last))), total=dict(zip(keys, list(tot))))
 
     def set_pipelined(self, on):
         check(self.lib.bslv_benson_set_pipelined(self.h, int(on)))

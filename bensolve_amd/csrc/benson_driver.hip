@@ -93,6 +93,10 @@ struct bslv_benson {
     std::vector<char> slot_valid;
     std::vector<int> slot_gen;                        // generations of warm starts between the root tableau and this slot
     std::vector<int> last_src, last_piv, last_gen;    // per LP of the last solve_local (tuning: bslv_benson_last_local)
+    // canonical duals (bslv_benson_set_canonical): the switch, dir_j = R_j . d for the LP engine's tie phase, its counters
+    bool canonical = false;
+    std::vector<double> canon_dir;                    // r
+    long last_canon[4] = {0, 0, 0, 0}, tot_canon[4] = {0, 0, 0, 0};     // of the last solve_local / of all: bslv_lpq_last_canonical_stats
     // totals
     long tot_lps = 0, tot_cuts = 0, tot_pivots = 0;
 };
@@ -226,7 +230,36 @@ int bslv_benson_create_ex(bslv_benson **out, int m, int n, int q, const double *
     h->slot_src.assign((size_t)pool_slots * q, 0.0);
     h->slot_valid.assign(pool_slots, 0);
     h->slot_gen.assign(pool_slots, 0);
+    // BSLV_CANONICAL_DUAL=1: every cut from the canonical dual (bslv_benson_set_canonical).  The homogeneous problems of phases 0 and 1
+    // take no part: their cut has another normal cone.
+    if (const char *e = getenv("BSLV_CANONICAL_DUAL")) {
+        if (atoi(e) != 0 && !h->hom && (rc = bslv_benson_set_canonical(h, 1))) { bslv_benson_destroy(h); return rc; }
+    }
     *out = h;
+    return 0;
+}
+
+// Canonical duals: w of every P2(v) is the dual that P2(v + t d) would have for small t > 0, d_k = 1 + hash01(k) a fixed generic
+// direction of R^q -- for generic d a facet normal of the image at y = v + z c, whatever basis the pivoting reached (the cut is built
+// from w, bslv_algs.c:1050).  The bound of row j of P2 is R_j . v (:1041-1046), so it moves by dir_j = R_j . d.
+int bslv_benson_set_canonical(bslv_benson *h, int on)
+{
+    if (!h) { set_error("bslv_benson_set_canonical: bad argument"); return BSLV_E_ARG; }
+    if (on && h->hom) { set_error("bslv_benson_set_canonical: a homogeneous engine cuts with (w + alpha eta, alpha), which has another normal cone"); return BSLV_E_ARG; }
+    if (!on) { h->canonical = false; return bslv_lpq_set_canonical(h->lp, 0, nullptr); }
+    if (bslv_lpq_is_revised(h->lp)) return bslv_lpq_set_canonical(h->lp, 1, h->c.data());      // (answers BSLV_E_ARG with its message)
+    const int q = h->q, r = h->r;
+    h->canon_dir.assign(r, 0.0);
+    for (int j = 0; j < r; j++) for (int k = 0; k < q; k++) h->canon_dir[j] += h->R[(size_t)k * r + j] * (1.0 + hash01(k));
+    h->canonical = true;      // (the LP engine gets the switch with the first batch of P2 LPs: the weighted-sum LPs of PART 1 are not P2(v))
+    return 0;
+}
+int bslv_benson_get_canonical(const bslv_benson *h) { return h && h->canonical; }
+// tie phase of the LPs of the last solve_local (retries included) / of all so far: bslv_lpq_last_canonical_stats
+int bslv_benson_canonical_stats(const bslv_benson *h, long last[4], long total[4])
+{
+    if (!h) return BSLV_E_ARG;
+    for (int k = 0; k < 4; k++) { if (last) last[k] = h->last_canon[k]; if (total) total[k] = h->tot_canon[k]; }
     return 0;
 }
 
@@ -698,7 +731,11 @@ int bslv_benson_solve_local_ctx(bslv_benson *h, int ctx, double *records, int *p
         static const bool lazy_ok = !(getenv("BSLV_LP_LAZY") && atoi(getenv("BSLV_LP_LAZY")) == 0);
         if ((rc = bslv_lpq_set_lazy(h->lp, (lazy_ok && !h->mark_at_collect) ? 1 : 0))) return rc;
     }
+    for (int k = 0; k < 4; k++) h->last_canon[k] = 0;
+    auto count_canonical = [h]() { long cs[4]; if (bslv_lpq_last_canonical_stats(h->lp, cs) == 0) for (int k = 0; k < 4; k++) { h->last_canon[k] += cs[k]; h->tot_canon[k] += cs[k]; } };
+    if (h->canonical && !bslv_lpq_get_canonical(h->lp) && (rc = bslv_lpq_set_canonical(h->lp, 1, h->canon_dir.data()))) return rc;      // (stays on: the retries below solve with it too)
     if ((rc = bslv_lpq_solve_batch(h->lp, nl, src.data(), dst.data(), vlo.data(), vup.data(), st.data(), it.data()))) return rc;
+    count_canonical();
     {
         // The reference's retry (bslv_lp.c:222-227: undefined -> standard basis -> solve again), in two stages.  A tableau is
         // handed down from parent to child without ever being refactorised; after hundreds of generations (ex07: 3400 outer
@@ -723,6 +760,7 @@ int bslv_benson_solve_local_ctx(bslv_benson *h, int ctx, double *records, int *p
                 if (stage >= 1 && (rc = bslv_lpq_reset_slot(h->lp, d2[t]))) return rc;
             }
             if ((rc = bslv_lpq_solve_batch(h->lp, nr, s2.data(), d2.data(), lo2.data(), up2.data(), st2.data(), it2.data()))) return rc;
+            count_canonical();
             std::vector<int> still;
             for (int t = 0; t < nr; t++) {
                 st[redo[t]] = st2[t]; it[redo[t]] += it2[t];

@@ -85,4 +85,12 @@ __device__ __forceinline__ ValIdx wave_argmax(ValIdx x)
     return x;
 }
 
+// a value in [0, 1) per index, the same on the host and on the device (cost perturbation of the LP engine; direction of the canonical duals)
+__host__ __device__ __forceinline__ double hash01(int k)
+{
+    unsigned x = (unsigned)k * 2654435761u;
+    x ^= x >> 16; x *= 0x85ebca6bu; x ^= x >> 13;
+    return (double)(x >> 8) * (1.0 / 16777216.0);
+}
+
 }  // namespace bslv

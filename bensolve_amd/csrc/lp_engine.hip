@@ -540,12 +540,7 @@ __global__ void k_rev_identity(LpView L, int slot, const double *cost)
 //    feasible basis at hand (Dantzig pricing, Harris ratio test on the entering column) -- oracle/lp_dense.c does the same
 //    with its primal_simplex().
 // cap2 = capacity of the candidate arrays in dynamic LDS.
-__device__ __forceinline__ double hash01(int k)
-{
-    unsigned x = (unsigned)k * 2654435761u;
-    x ^= x >> 16; x *= 0x85ebca6bu; x ^= x >> 13;
-    return (double)(x >> 8) * (1.0 / 16777216.0);
-}
+// (hash01: common.h)
 // ---- revised form: the tableau row as sparse products, by slices that several workgroups take ----
 // One sparse dot product per nonbasic column j in [j0, j1): row[j] = -rho[k] for a slack k = nh[j] < M, else -(rho . A_k) ... as the
 // caller's sign convention has it (K = [I | -A]: the column of structural k is -A_k; cval holds -A).  The non-zeros of a column are fetched
@@ -1673,6 +1668,152 @@ __global__ __launch_bounds__(NT) void k_select_cached(LpView L, BatchView Bv, co
     }
 }
 
+// ---- TIE PHASE (bslv_lpq_set_canonical): the canonical optimal basis of a primal degenerate LP ----
+// An LP whose optimum lies on several bounds at once (beta_i on a bound for basic i) has a whole face of optimal duals, and the basis the
+// pivoting happened to end in names one of its vertices.  The canonical one is the basis that STAYS optimal when the per-LP bounds move
+// to vlo + t dir, vup + t dir for every small t > 0 -- applied symbolically, no t is ever formed: beta(t) = beta + t g with
+//   g_i = sum over the nonbasic per-LP variables j that sit on a (finite, hence shifted) bound of T[i][j] dir_j,
+// a basic per-LP variable's own bounds move by its dir, and a TIED row (beta_i within btol of a bound) is WRONG when it would cross that
+// bound for t > 0: g_i - shift_i < -tol at the lower bound, > tol at the upper one.  The phase is the dual simplex on that second level:
+// the wrong tied row with the largest |g_i - shift_i| leaves (Bland's rule after PRIMAL_STALL steps), the entering column comes from the
+// Harris ratio test of the dual selection (same helpers, the true reduced costs, no long steps), and the step has length ZERO: beta, the
+// objective and every primal value stay what they were bit for bit (the leaving variable keeps its value, within btol of the bound it
+// now sits on); the reduced costs, g and the pivot descriptor follow the pivot as always, so k_flush, lazy tableaux and warm starts see
+// an ordinary pivot.  The phase ends OPTIMAL in every case: no wrong tied row (canonical), no entering candidate (the shifted LP is
+// infeasible for t > 0), or the cap on its pivots.  It runs as kernel instances of its own after the rounds of the batch are over, on
+// the LPs that ended OPTIMAL (an LP is ST_RUNNING again while it is in the phase, so that the pass kernels treat it as they treat any LP
+// that still pivots) -- the kernels of a solve without the switch are not touched.
+constexpr int TIE_NEW = 0, TIE_RUN = 1, TIE_DONE = 2;      // TieView::state
+struct TieView {
+    const double *dir;      // [vcnt] direction of the shift, per variable of the per-LP range
+    double *g;              // [B][Mp1p] d beta / d t
+    int *state, *iters;     // [B] TIE_*; tie pivots of the LP
+    int *stat;              // [4] LPs that entered the phase, tie pivots, LPs that ended without an entering candidate, LPs that gave up at the cap
+    int cap;                // tie pivots per LP
+};
+__device__ __forceinline__ double tie_shift(const LpView &L, const TieView &Tv, int k)
+{
+    const int j = k - L.vfirst;
+    return (j >= 0 && j < L.vcnt) ? Tv.dir[j] : 0.0;
+}
+// the phase of LP b is over (why: the counter of Tv.stat that says so, or -1)
+__device__ __forceinline__ void tie_finish(const BatchView &Bv, const TieView &Tv, const int b, const int why)
+{
+    if (threadIdx.x == 0) {
+        Tv.state[b] = TIE_DONE; Bv.status[b] = BSLV_LP_OPTIMAL; Bv.mode[b] = MODE_NONE;
+        if (why >= 0) atomicAdd(&Tv.stat[why], 1);
+    }
+}
+// One tie pivot of LP b by the calling workgroup; false when the LP cannot select again before the next pass (finished, KP pivots pending).
+// sv, si, p_d, s_g: LDS of the kernel (see SelShared for why it is handed down).
+__device__ __forceinline__ bool tie_once(const LpView &L, const BatchView &Bv, const TieView &Tv, const int b, double *sv, int *si, PivDesc *p_d, double *s_g)
+{
+    const int tid = threadIdx.x, NT = (int)blockDim.x;
+    const int state = Tv.state[b], np = Bv.npend[b], titer = Tv.iters[b];
+    if (state == TIE_DONE || np >= KP) return false;
+    const int slot = Bv.dst[b];
+    const SelCtx c = sel_ctx(L, Bv, b, np, slot, Bv.flushed[b] ? slot : Bv.src[b]);
+    const int M = L.M, N = L.N, ld = L.ld;
+    double *const g = Tv.g + (size_t)b * L.Mp1p;
+    double *const beta = c.beta, *const drow = c.drow, *const row = c.row, *const pc = c.pc;
+    __syncthreads();                           // (everyone has read the LP's state before thread 0 changes it)
+    if (state == TIE_NEW) {
+        // entry: g through the pending pivots, one column gather per nonbasic per-LP variable
+        for (int i = tid; i < M; i += NT) {
+            double acc = 0.0;
+            for (int t = 0; t < L.vcnt; t++) {
+                const int p = c.pos[L.vfirst + t];
+                if (p >= 0) continue;
+                const int j = -1 - p;
+                if (c.nstat[j] == NS_F) continue;      // (free at zero: no bound to move with)
+                acc = fma(virt_entry(c.T0[(size_t)i * ld + j], i, j, np, c.pd, c.prow0, c.pcol0, ld, L.Mp1p), Tv.dir[t], acc);
+            }
+            g[i] = acc;
+        }
+        if (tid == 0) { Tv.state[b] = TIE_RUN; Bv.status[b] = ST_RUNNING; atomicAdd(&Tv.stat[0], 1); }
+        __syncthreads();
+    }
+    const bool bland = titer >= PRIMAL_STALL;
+    // Phase A: the leaving row -- the wrong tied row with the largest rate; id = 2*i + (below ? 1 : 0) as in leave_candidate
+    ValIdx best{0.0, -1};
+    for (int i = tid; i < M; i += NT) {
+        const int k = c.bh[i];
+        const double lo = LO(L, Bv, b, k), up = UP(L, Bv, b, k), bt = beta[i], gi = g[i], sh = tie_shift(L, Tv, k);
+        const double rate = gi - sh, tol = TOL_BND * (1.0 + fabs(gi) + fabs(sh));
+        if (!isinf(lo) && fabs(bt - lo) <= btol(lo) && rate < -tol) best = better_max(best, ValIdx{bland ? (double)(M + N - k) : -rate, 2 * i + 1});
+        if (!isinf(up) && fabs(bt - up) <= btol(up) && rate > tol) best = better_max(best, ValIdx{bland ? (double)(M + N - k) : rate, 2 * i});
+    }
+    best = block_argmax(best, sv, si);
+    if (best.i < 0) { tie_finish(Bv, Tv, b, -1); return false; }          // the basis is canonical
+    if (titer >= Tv.cap) { tie_finish(Bv, Tv, b, 3); return false; }
+    const int r = best.i >> 1; const bool below = best.i & 1;
+    const double sgn = below ? 1.0 : -1.0;
+    fetch_row<true>(L, Bv, c, r);
+    // the dual ratio test of select_once, on the true reduced costs
+    double rmax = 0.0;
+    for (int j = tid; j < N; j += NT) rmax = fmax(rmax, fabs(row[j]));
+    rmax = block_max(rmax, sv);
+    const double ptol = TOL_PIV * (1.0 + rmax);
+    double th = INFINITY;
+    for (int j = tid; j < N; j += NT) {
+        const double a = sgn * row[j];
+        if (is_candidate(c.nstat[j], a, ptol)) th = fmin(th, harris_key(drow[j], a, bland));
+    }
+    th = block_min(th, sv);
+    if (isinf(th)) { tie_finish(Bv, Tv, b, 2); return false; }           // the shifted LP is infeasible for t > 0: the basis reached stays
+    ValIdx piv{0.0, -1};
+    for (int j = tid; j < N; j += NT) {
+        const double a = sgn * row[j];
+        if (is_candidate(c.nstat[j], a, ptol) && within_bound(drow[j], a, th)) piv = better_max(piv, ValIdx{bland ? (double)(M + N - c.nh[j]) : fabs(a), j});
+    }
+    piv = block_argmax(piv, sv, si);
+    const int q = piv.i;
+    // Phase C: the descriptor, the basis heads -- and the step of length zero
+    if (tid == 0) {
+        const double sk = tie_shift(L, Tv, c.bh[r]), sq = c.nstat[q] == NS_F ? 0.0 : tie_shift(L, Tv, c.nh[q]);
+        const double br = beta[r], xq = c.xN[q], gr = g[r];
+        PivDesc d = commit_pivot(L, Bv, c, r, q, below, bland, Bv.iters[b], Bv.verified[b], MODE_PIVOT, drow, false, 0, false);
+        d.pbeta = 0.0; d.enter_val = xq;       // nothing moves at t = 0: the entering variable keeps its value ...
+        c.xN[q] = br;                          // ... and so does the leaving one, on its bound within btol
+        Bv.desc[(size_t)b * KP + np] = d;
+        *p_d = d;
+        s_g[0] = gr - sk; s_g[1] = sq;
+        Tv.iters[b] = titer + 1;
+        atomicAdd(&Tv.stat[1], 1);
+    }
+    __syncthreads();
+    const PivDesc d = *p_d;
+    const double gp = s_g[0], sq = s_g[1];     // rate at which the leaving row crosses its bound; shift of the entering variable's own bound
+    // Phase D: the multipliers of all rows; g follows the pivot as beta does in select_once (beta itself: a step of length zero)
+    for (int i = tid; i <= M; i += NT) {
+        if (i == r) { pc[i] = 0.0; beta[i] = d.enter_val; g[i] = fma(-gp, d.p, sq); continue; }
+        const double f = (i == M ? drow[q] : virt_entry(c.T0[(size_t)i * ld + q], i, q, np, c.pd, c.prow0, c.pcol0, ld, L.Mp1p)) * d.p;
+        pc[i] = f;
+        if (i < M) g[i] = fma(-f, gp, g[i]);
+    }
+    __syncthreads();
+    {
+        const double fM = pc[M];
+        for (int j = tid; j < N; j += NT) drow[j] = j == q ? fM : fma(-fM, row[j], drow[j]);
+    }
+    if (tid == 0) Bv.npend[b] = np + 1;
+    return true;
+}
+// Launched only while the switch is on (tableau form), with the workgroup size of the batch's selections
+__global__ __launch_bounds__(NT_BIG) void k_select_tie(LpView L, BatchView Bv, TieView Tv, const int *active, int nact, int nsel)
+{
+    __shared__ double sv[NT_BIG / WAVE];
+    __shared__ int si[NT_BIG / WAVE];
+    __shared__ PivDesc s_d;
+    __shared__ double s_g[2];
+    if ((int)blockIdx.x >= nact) return;
+    const int b = active[blockIdx.x];
+    for (int sdx = 0; sdx < nsel; sdx++) {
+        if (sdx) __syncthreads();
+        if (!tie_once(L, Bv, Tv, b, sv, si, &s_d, s_g)) break;
+    }
+}
+
 // ---- which LPs need a pass over their tableau: pending pivots to apply, or beta to recompute ----
 __global__ void k_list_pending(BatchView Bv, const int *active, int nact, int it)
 {
@@ -1871,6 +2012,11 @@ struct bslv_lpq {
     long last_ext[5] = {0, 0, 0, 0, 0};
     int method = BSLV_LP_METHOD_DUAL;  // bslv_lpq_set_method (BSLV_LP_METHOD at create)
     long last_p1[3] = {0, 0, 0};       // phase 1 of the last batch: LPs that entered it, its iterations, rebuilds of its pricing vector
+    // tie phase (bslv_lpq_set_canonical): the switch, the direction (host / device), per-LP state of a batch, the counters of the last batch
+    bool canonical = false;
+    std::vector<double> canon_dir;
+    double *tdir_d = nullptr, *tg_d = nullptr; int *tstate_d = nullptr, *titers_d = nullptr, *tstat_d = nullptr; int tie_Bcap = 0;
+    long last_canon[4] = {0, 0, 0, 0};
     long last_passes = 0;              // (LP, pass) pairs of the last batch: how many tableaux k_flush read and wrote
     long last_launches = 0;            // k_flush launches of the last batch: one per lock-step round + one per pass made on request (bslv_lpq_materialise)
     size_t select_lds_max = 64 * 1024; // dynamic LDS of k_select<true> (candidate sort of the bound flipping ratio test)
@@ -2155,6 +2301,7 @@ void bslv_lpq_destroy(bslv_lpq *h)
     fr(h->Tstd); fr(h->lb_d); fr(h->ub_d); fr(h->art_d);
     fr(h->dbg_d); fr(h->list_d); fr(h->cptr_d); fr(h->cidx_d); fr(h->rptr_d); fr(h->ridx_d); fr(h->cval_d); fr(h->rval_d); fr(h->cost_d); fr(h->dsl_d); fr(h->trow_d); fr(h->uvec_d); fr(h->xfull_d); fr(h->hmail_d);
     fr(h->src_d); fr(h->dst_d); fr(h->status_d); fr(h->iters_d); fr(h->mode_d); fr(h->ver_d); fr(h->qslot_d); fr(h->init_d);
+    fr(h->tdir_d); fr(h->tg_d); fr(h->tstate_d); fr(h->titers_d); fr(h->tstat_d);
     fr(h->vlo_d); fr(h->vup_d); fr(h->prow_d); fr(h->desc_d); fr(h->out_d); fr(h->active_d); fr(h->work_d); fr(h->nwork_d); fr(h->npend_d); fr(h->flushed_d); fr(h->pcol_d); fr(h->dcur_d); fr(h->dper_d); fr(h->pflags_d); fr(h->stall_d); fr(h->xstat_d); fr(h->cvals_d);
     if (h->status_h) (void)hipHostFree(h->status_h);
     if (h->active_h) (void)hipHostFree(h->active_h);
@@ -2457,6 +2604,24 @@ static void launch_select(bslv_lpq *h, const SelectPlan &p, const BatchView &bv,
 }
 static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, const double *vlo, const double *vup,
                             int cfirst, int ccnt, const double *cvals, int *status, int *iters);
+// tie phase: pivots an LP may spend in it (Bland's rule holds from PRIMAL_STALL on), and the rounds that leaves a batch at most --
+// every round an LP of the phase is in makes a pivot or ends it, except the one it waits in for a pass with KP pivots pending
+static int tie_cap(const LpView &L) { return 2 * PRIMAL_STALL + 2 * (L.M + L.N); }
+static int tie_rounds_max(const LpView &L) { return tie_cap(L) + 8; }
+// the per-LP vectors of the tie phase, for batches as large as the batch buffers
+static int ensure_tie(bslv_lpq *h)
+{
+    if (h->tie_Bcap >= h->Bcap && h->tg_d) return 0;
+    auto fr = [](auto *&p) { if (p) (void)hipFree(p); p = nullptr; };
+    fr(h->tg_d); fr(h->tstate_d); fr(h->titers_d);
+    h->tie_Bcap = 0;
+    HIP_TRY(malloc0s(&h->tg_d, (size_t)h->Bcap * h->L.Mp1p * sizeof(double), h->stream));
+    HIP_TRY(malloc0s(&h->tstate_d, (size_t)h->Bcap * sizeof(int), h->stream));
+    HIP_TRY(malloc0s(&h->titers_d, (size_t)h->Bcap * sizeof(int), h->stream));
+    if (!h->tstat_d) HIP_TRY(malloc0s(&h->tstat_d, 4 * sizeof(int), h->stream));
+    h->tie_Bcap = h->Bcap;
+    return 0;
+}
 int bslv_lpq_set_lazy(bslv_lpq *h, int on)
 {
     if (!h) return BSLV_E_ARG;
@@ -2526,6 +2691,7 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
         for (int b = 0; b < B; b++) { status[b] = BSLV_LP_INFEASIBLE; if (iters) iters[b] = 0; }
         h->last_iters = 0; h->last_pivots = 0; h->last_passes = 0; h->last_launches = 0;
         for (int k = 0; k < 3; k++) h->last_p1[k] = 0;
+        for (int k = 0; k < 4; k++) h->last_canon[k] = 0;
         return 0;
     }
     if (!h || B < 0 || (B > 0 && (!src || !dst)) || (B > 0 && h->L.vcnt > 0 && (!vlo || !vup))) {
@@ -2562,7 +2728,7 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
     }
     if (const char *e = getenv("BSLV_UPD_GRID")) h->upd_grid = std::max(64, atoi(e));
     {   // one work-list length per lock-step iteration, zeroed here: no reset between iterations
-        const int need = L.maxit + 64;
+        const int need = L.maxit + 64 + (h->canonical ? tie_rounds_max(L) : 0);      // (the rounds of a tie phase count on behind the others')
         if (need > h->nworkcap) { if (h->nwork_d) (void)hipFree(h->nwork_d); h->nwork_d = nullptr; HIP_TRY(malloc0s(&h->nwork_d, need * sizeof(int), s)); h->nworkcap = need; }
         HIP_TRY(hipMemsetAsync(h->nwork_d, 0, need * sizeof(int), s));
     }
@@ -2624,31 +2790,36 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
     h->last_update_ms = 0;
     static const int max_rounds = getenv("BSLV_LP_MAXROUNDS") ? atoi(getenv("BSLV_LP_MAXROUNDS")) : 0;      // (timing experiments)
     L.probe = getenv("BSLV_REV_PROBE") ? atoi(getenv("BSLV_REV_PROBE")) : 0;
+    // the pass of round `it` over the tableaux of the `running` LPs of the active list that have something pending
+    auto pass_round = [&](const int running, const int it) -> int {
+        hipLaunchKernelGGL(k_list_pending, dim3((running + 255) / 256), dim3(256), 0, s, bv, h->active_d, running, it);
+        if (h->profile) {
+            if (nev == h->evpool.size()) {
+                hipEvent_t a, b2;
+                HIP_TRY(hipEventCreate(&a)); HIP_TRY(hipEventCreate(&b2));
+                h->evpool.emplace_back(a, b2);
+            }
+            HIP_TRY(hipEventRecord(h->evpool[nev].first, s));
+        }
+        // few LPs left: smaller row tiles keep >= ~2k workgroups in flight
+        int tr = running * tiles >= 2048 ? 32 : (running * tiles * 2 >= 2048 ? 16 : (running * tiles * 4 >= 2048 ? 8 : 4));      // (4: one row per wave -- a single LP of a few thousand rows)
+        if (big_flush) {                                            // 16 waves per workgroup: at least one row per wave, more where the batch still fills the chip
+            const long rows = (long)running * L.mrows;
+            tr = rows >= 2048L * 128 ? 128 : rows >= 2048L * 64 ? 64 : rows >= 2048L * 32 ? 32 : 16;
+        }
+        const int ntile = (L.mrows + tr - 1) / tr;
+        const int fnt = big_flush ? NT_BIG : NT;
+        if (L.rev) hipLaunchKernelGGL(k_rev_u, dim3(running), dim3(NT), 0, s, L, bv, B, (const int *)h->work_d, it);      // (only the LPs that asked for a refresh of beta)
+        if (wide) hipLaunchKernelGGL(k_flush<true>, dim3(std::min(running * ntile, h->upd_grid)), dim3(fnt), 0, s, L, bv, it, ntile, tr);
+        else hipLaunchKernelGGL(k_flush<false>, dim3(std::min(running * ntile, h->upd_grid)), dim3(fnt), lds, s, L, bv, it, ntile, tr);
+        if (h->profile) { HIP_TRY(hipEventRecord(h->evpool[nev].second, s)); nev++; }
+        hipLaunchKernelGGL(k_after_flush, dim3((running + 255) / 256), dim3(256), 0, s, bv, it);
+        return 0;
+    };
     while (running > 0 && it < L.maxit + 8 && !(max_rounds && it >= max_rounds)) {
         for (int c = 0; c < chunk; c++, it++) {
             launch_select(h, plan, bv, running);
-            hipLaunchKernelGGL(k_list_pending, dim3((running + 255) / 256), dim3(256), 0, s, bv, h->active_d, running, it);
-            if (h->profile) {
-                if (nev == h->evpool.size()) {
-                    hipEvent_t a, b2;
-                    HIP_TRY(hipEventCreate(&a)); HIP_TRY(hipEventCreate(&b2));
-                    h->evpool.emplace_back(a, b2);
-                }
-                HIP_TRY(hipEventRecord(h->evpool[nev].first, s));
-            }
-            // few LPs left: smaller row tiles keep >= ~2k workgroups in flight
-            int tr = running * tiles >= 2048 ? 32 : (running * tiles * 2 >= 2048 ? 16 : (running * tiles * 4 >= 2048 ? 8 : 4));      // (4: one row per wave -- a single LP of a few thousand rows)
-            if (big_flush) {                                            // 16 waves per workgroup: at least one row per wave, more where the batch still fills the chip
-                const long rows = (long)running * L.mrows;
-                tr = rows >= 2048L * 128 ? 128 : rows >= 2048L * 64 ? 64 : rows >= 2048L * 32 ? 32 : 16;
-            }
-            const int ntile = (L.mrows + tr - 1) / tr;
-            const int fnt = big_flush ? NT_BIG : NT;
-            if (L.rev) hipLaunchKernelGGL(k_rev_u, dim3(running), dim3(NT), 0, s, L, bv, B, (const int *)h->work_d, it);      // (only the LPs that asked for a refresh of beta)
-            if (wide) hipLaunchKernelGGL(k_flush<true>, dim3(std::min(running * ntile, h->upd_grid)), dim3(fnt), 0, s, L, bv, it, ntile, tr);
-            else hipLaunchKernelGGL(k_flush<false>, dim3(std::min(running * ntile, h->upd_grid)), dim3(fnt), lds, s, L, bv, it, ntile, tr);
-            if (h->profile) { HIP_TRY(hipEventRecord(h->evpool[nev].second, s)); nev++; }
-            hipLaunchKernelGGL(k_after_flush, dim3((running + 255) / 256), dim3(256), 0, s, bv, it);
+            if ((rc = pass_round(running, it))) return rc;
         }
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(h->status_h, h->status_d, B * sizeof(int), hipMemcpyDeviceToHost, s));
@@ -2658,11 +2829,56 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
         if (running) HIP_TRY(hipMemcpyAsync(h->active_d, h->active_h, running * sizeof(int), hipMemcpyHostToDevice, s));
         if (chunk < 16) chunk *= 2;
     }
+    // TIE PHASE (bslv_lpq_set_canonical): the LPs that ended OPTIMAL go on to their canonical basis, in rounds of the same shape --
+    // KP tie pivots on vectors (k_select_tie), one pass.  Their work lists count on from L.maxit + 64.
+    int tie_rounds = 0;
+    const int tie_base = L.maxit + 64;
+    for (int k = 0; k < 4; k++) h->last_canon[k] = 0;
+    if (h->canonical && !L.objmode && !L.rev && L.vcnt > 0 && !max_rounds) {
+        if ((rc = ensure_tie(h))) return rc;
+        TieView tv;
+        tv.dir = h->tdir_d; tv.g = h->tg_d; tv.state = h->tstate_d; tv.iters = h->titers_d; tv.stat = h->tstat_d; tv.cap = tie_cap(L);
+        HIP_TRY(hipMemsetAsync(h->tstate_d, 0, (size_t)B * sizeof(int), s));
+        HIP_TRY(hipMemsetAsync(h->titers_d, 0, (size_t)B * sizeof(int), s));
+        HIP_TRY(hipMemsetAsync(h->tstat_d, 0, 4 * sizeof(int), s));
+        int nt = 0;
+        for (int b = 0; b < B; b++) if (h->status_h[b] == BSLV_LP_OPTIMAL) h->active_h[nt++] = b;
+        if (nt) HIP_TRY(hipMemcpyAsync(h->active_d, h->active_h, nt * sizeof(int), hipMemcpyHostToDevice, s));
+        std::vector<int> tstate(B);
+        const int rounds_max = tie_rounds_max(L);
+        int tchunk = 1;
+        while (nt > 0 && tie_rounds < rounds_max) {
+            for (int c = 0; c < tchunk && tie_rounds < rounds_max; c++, tie_rounds++) {
+                hipLaunchKernelGGL(k_select_tie, dim3(nt), dim3(plan.nt), 0, s, L, bv, tv, h->active_d, nt, KP);
+                if ((rc = pass_round(nt, tie_base + tie_rounds))) return rc;
+            }
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(tstate.data(), h->tstate_d, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+            int left = 0;
+            for (int k = 0; k < nt; k++) { const int b = h->active_h[k]; if (tstate[b] != TIE_DONE) h->active_h[left++] = b; }
+            nt = left;
+            if (nt) HIP_TRY(hipMemcpyAsync(h->active_d, h->active_h, nt * sizeof(int), hipMemcpyHostToDevice, s));
+            if (tchunk < 16) tchunk *= 2;
+        }
+        HIP_TRY(hipMemcpyAsync(h->status_h, h->status_d, B * sizeof(int), hipMemcpyDeviceToHost, s));
+        int ts[4];
+        HIP_TRY(hipMemcpyAsync(ts, h->tstat_d, sizeof ts, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        for (int k = 0; k < 4; k++) h->last_canon[k] = ts[k];
+        // (the cap on the pivots of an LP ends every phase long before the rounds run out; an LP still in it would keep the basis reached)
+        for (int k = 0; k < nt; k++) { const int b = h->active_h[k]; if (h->status_h[b] == ST_RUNNING) { h->status_h[b] = BSLV_LP_OPTIMAL; h->last_canon[3]++; HIP_TRY(hipMemcpy(h->status_d + b, h->status_h + b, sizeof(int), hipMemcpyHostToDevice)); } }
+    }
     {   // tableau passes of this batch: sum of the work-list lengths of the rounds
         std::vector<int> nw(std::max(it, 1), 0);
         if (it > 0) HIP_TRY(hipMemcpy(nw.data(), h->nwork_d, (size_t)it * sizeof(int), hipMemcpyDeviceToHost));
         long passes = 0;
         for (int k = 0; k < it; k++) passes += nw[k];
+        if (tie_rounds > 0) {
+            nw.assign(tie_rounds, 0);
+            HIP_TRY(hipMemcpy(nw.data(), h->nwork_d + tie_base, (size_t)tie_rounds * sizeof(int), hipMemcpyDeviceToHost));
+            for (int k = 0; k < tie_rounds; k++) passes += nw[k];
+        }
         h->last_passes = passes;
     }
     if (L.rev) hipLaunchKernelGGL(k_rev_store_d, dim3((L.ld + 255) / 256, B), dim3(256), 0, s, L, bv, B);       // the reduced costs of every LP go to its slot
@@ -2688,8 +2904,8 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
         h->last_pivots = piv;
         if (iters) memcpy(iters, itv.data(), B * sizeof(int));
     }
-    h->last_iters = it;
-    h->last_launches = it;
+    h->last_iters = it + tie_rounds;
+    h->last_launches = it + tie_rounds;
     { int xs[8]; HIP_TRY(hipMemcpy(xs, h->xstat_d, sizeof xs, hipMemcpyDeviceToHost)); for (int k = 0; k < 5; k++) h->last_ext[k] = xs[k]; for (int k = 0; k < 3; k++) h->last_p1[k] = xs[5 + k]; }
     if (h->profile) {
         double ms = 0;
@@ -2845,6 +3061,30 @@ int bslv_lpq_last_phase1_stats(const bslv_lpq *h, long out[3])
 {
     if (!h || !out) return BSLV_E_ARG;
     for (int k = 0; k < 3; k++) out[k] = h->last_p1[k];
+    return 0;
+}
+// The canonical optimal basis (tie phase) for every later solve_batch: see bslv_hip.h; the cut of a vertex is built from these duals (bslv_algs.c:1050)
+int bslv_lpq_set_canonical(bslv_lpq *h, int on, const double *dir)
+{
+    if (!h || (on && !dir)) { set_error("bslv_lpq_set_canonical: bad argument"); return BSLV_E_ARG; }
+    if (h->L.rev && on) { set_error("bslv_lpq_set_canonical: the revised form has no tie phase (the canonical dual is the tableau form's)"); return BSLV_E_ARG; }
+    if (!on) { h->canonical = false; return 0; }
+    const int vc = h->L.vcnt;
+    for (int j = 0; j < vc; j++) if (!std::isfinite(dir[j])) { set_error("bslv_lpq_set_canonical: dir[%d] is not finite", j); return BSLV_E_ARG; }
+    if (!h->tdir_d) HIP_TRY(malloc0(&h->tdir_d, (size_t)std::max(1, vc) * sizeof(double)));
+    h->canon_dir.assign(dir, dir + vc);
+    if (vc > 0) {
+        HIP_TRY(hipMemcpyAsync(h->tdir_d, h->canon_dir.data(), (size_t)vc * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+    }
+    h->canonical = true;
+    return 0;
+}
+int bslv_lpq_get_canonical(const bslv_lpq *h) { return h && h->canonical; }
+int bslv_lpq_last_canonical_stats(const bslv_lpq *h, long out[4])
+{
+    if (!h || !out) return BSLV_E_ARG;
+    for (int k = 0; k < 4; k++) out[k] = h->last_canon[k];
     return 0;
 }
 int bslv_lpq_last_ext_stats(const bslv_lpq *h, long out[4])

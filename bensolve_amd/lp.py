@@ -196,6 +196,27 @@ class LpEngine:
         self.lib.bslv_lpq_get_method.argtypes = [ctypes.c_void_p]
         return int(self.lib.bslv_lpq_get_method(self.h))
 
+    def set_canonical(self, on, dir=None):
+        """canonical optimal duals for every later solve_batch: the basis that stays optimal when the per-LP bounds move by
+        t * dir (var_cnt values) for small t > 0, found by a tie phase after optimality (bslv_lpq_set_canonical, include/bslv_hip.h).
+        Returns the library's code (0, or BSLV_E_ARG for the revised form or a missing direction)."""
+        self.lib.bslv_lpq_set_canonical.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+        d = None if dir is None else np.ascontiguousarray(dir, np.float64)
+        if on and d is not None and getattr(self, "vcnt", None) is not None:      # (a borrowed view of a driver's engine does not know its range)
+            assert d.shape == (self.vcnt,)
+        return int(self.lib.bslv_lpq_set_canonical(self.h, int(bool(on)), None if d is None else d.ctypes.data))
+
+    def get_canonical(self):
+        self.lib.bslv_lpq_get_canonical.argtypes = [ctypes.c_void_p]
+        return int(self.lib.bslv_lpq_get_canonical(self.h))
+
+    def last_canonical_stats(self):
+        """tie phase of the last solve_batch (bslv_lpq_last_canonical_stats)"""
+        o = (ctypes.c_long * 4)()
+        self.lib.bslv_lpq_last_canonical_stats.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        check(self.lib.bslv_lpq_last_canonical_stats(self.h, o))
+        return dict(entered=int(o[0]), tie_pivots=int(o[1]), no_candidate=int(o[2]), capped=int(o[3]))
+
     def last_stats(self):
         it = ctypes.c_int()
         piv = ctypes.c_long()

@@ -167,6 +167,22 @@ enum { BSLV_LP_METHOD_DUAL = 0, BSLV_LP_METHOD_PRIMAL = 1, BSLV_LP_METHOD_REPAIR
 int  bslv_lpq_set_method(bslv_lpq *h, int method);
 int  bslv_lpq_get_method(const bslv_lpq *h);
 int  bslv_lpq_last_phase1_stats(const bslv_lpq *h, long out[3]);
+/* CANONICAL OPTIMAL DUALS.  Benson's cut is built from the dual solution of P2(v) (w = lp_dual_solution_rows, bslv_algs.c:1050).  Where
+ * the optimum is primal degenerate -- y = v + z c on an edge or a vertex of the image -- every w of the normal cone at y is optimal and
+ * the basis the pivoting ended in names one of them, which need not be a facet normal.  With on != 0 every later solve_batch ends in the
+ * CANONICAL optimal basis instead: the one that stays optimal for the per-LP bounds vlo + t dir, vup + t dir (dir: var_cnt values, one
+ * per variable of the per-LP range; infinite bounds stay infinite) for all small enough t > 0.  Status, objective and primal values are
+ * those of t = 0, bit for bit; only the basis may differ, and with it bslv_lpq_get_dual (:1050).  No t is ever formed: an LP that ends
+ * OPTIMAL goes on into a TIE PHASE -- dual simplex pivots of length zero among the rows that sit on a bound, chosen by the derivative
+ * of the basic values with respect to t (lp_engine.hip, k_select_tie) -- when the rounds of its batch are over.  The phase keeps the
+ * status OPTIMAL however it ends; its pivots are counted in iters[].  Works with every method and with the extended selection on or
+ * off (it does not need it); objective batches (solve_batch_obj) ignore the switch; the revised form answers BSLV_E_ARG.  With on = 0
+ * (dir may be NULL) the engine computes what it always did.
+ * bslv_lpq_last_canonical_stats, of the last solve_batch: [0] LPs that entered the tie phase (all that ended OPTIMAL), [1] tie pivots,
+ * [2] LPs whose phase ended without an entering candidate (the shifted LP is infeasible for t > 0), [3] LPs that gave up at the cap. */
+int  bslv_lpq_set_canonical(bslv_lpq *h, int on, const double *dir /* var_cnt, NULL with on = 0 */);
+int  bslv_lpq_get_canonical(const bslv_lpq *h);
+int  bslv_lpq_last_canonical_stats(const bslv_lpq *h, long out[4]);
 
 /* ------------------------------------------------------------------------------------------
  * 2. Polyhedron engine  (replaces bslv_poly.h:90-118)
@@ -313,6 +329,17 @@ int  bslv_benson_collect_ctx(bslv_benson *h, int ctx, int max_batch, int rank, i
 int  bslv_benson_solve_local_ctx(bslv_benson *h, int ctx, double *records, int *pivots_out, int *lockstep_out);
 int  bslv_benson_apply_ctx(bslv_benson *h, int ctx, int nrec, const double *records, long *stats);
 int  bslv_benson_unprocessed_left(const bslv_benson *h);
+/* CANONICAL DUALS: with on != 0 the cut of every vertex v is built from the dual that P2(v + t d) would have for small t > 0 instead
+ * of the dual the pivoting happened to reach (w of bslv_algs.c:1050), d_k = 1 + hash01(k) a fixed generic direction -- a facet normal
+ * of the image at y = v + z c also where y lies on an edge or a vertex.  The driver hands dir_j = R_j . d to bslv_lpq_set_canonical on
+ * its LP engine (the bound of row j is R_j . v, :1041-1046); the LPs of the retry ladder are solved with it too, the weighted-sum LPs
+ * of PART 1 are not.  Off by default; BSLV_CANONICAL_DUAL=1 switches it on when an engine is created.  A homogeneous engine (hom != 0)
+ * answers BSLV_E_ARG: its cut (w + alpha eta, alpha) has another normal cone (the environment switch leaves such engines alone).  The
+ * dual-variant entry points do not know the switch.  bslv_benson_canonical_stats: the four counts of bslv_lpq_last_canonical_stats
+ * summed over the LPs of the last solve_local, retries included (last), and over all of them (total); either may be NULL. */
+int  bslv_benson_set_canonical(bslv_benson *h, int on);
+int  bslv_benson_get_canonical(const bslv_benson *h);
+int  bslv_benson_canonical_stats(const bslv_benson *h, long last[4], long total[4]);
 /* batch selection: 1 = newest vertices first (default), 2 = spread evenly over the unprocessed queue, 3 = newest first but at
  * most `cap` children of one cut per batch, chosen from a window of `window` batches (set_sibling_rule; default 1, 8): the
  * children of one cut mostly see the same facet of the upper image, so their LPs return the same cut -- the reference's
