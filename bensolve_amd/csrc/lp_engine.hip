@@ -96,6 +96,10 @@ struct LpView {
     double *dsl;                // rev: [slots][ld] reduced costs of each slot (the tableau form keeps them as row M of T)
     const int *cptr, *cidx; const double *cval;   // rev: CSC of A
     const int *rptr, *ridx; const double *rval;   // rev: CSR of A
+    // rev, refactorisation (bslv_lpq_set_refactor): rfx != 0 = an LP the pivot cross-check gives up is marked in BatchView::rmark (the call
+    // rebuilds its inverse and solves it again); drift_b / drift_p: test hook BSLV_LP_REV_DRIFT, the cross-check of LP drift_b is taken as
+    // failed at its drift_p-th pivot (-1: off)
+    int rfx, drift_b, drift_p;
 };
 struct BatchView {
     const int *src, *dst;
@@ -119,6 +123,7 @@ struct BatchView {
     double *trow;           // [B][ld]   the tableau row of the selection at hand (prow then holds rows of B^-1: [B][KP][ldt])
     double *uvec;           // [B][ldt]  -K_N x_N: beta = B^-1 uvec (k_rev_u; k_init and the refresh pass of k_flush multiply by it)
     double *xfull;          // [B][N]    scratch of k_rev_u: values of the nonbasic structurals by column
+    int *rmark;             // [B]       revised form with LpView::rfx: 1 = given up by the pivot cross-check (zeroed per solve only while the switch is on)
     int *hmail;             // [B][8]    revised form, helper workgroups of k_select: request word, slices done, pending count, slice ticket
     int lazy;               // bslv_lpq_set_lazy: an LP that is finished when its pass would be due keeps its pending pivots; its slot gets the tableau only when asked for (bslv_lpq_materialise)
     unsigned long long *dbg; // BSLV_REV_PROBE & 8: 100 MHz clock ticks per phase of the dual selection of LP 0 (timing experiments)
@@ -1374,10 +1379,13 @@ __device__ __forceinline__ bool select_once(const LpView &L, const BatchView &Bv
     if (tid == 0) {
         const double trq = row[q];
         // revised form: the pivot element comes out of TWO products -- rho K_q (the row) and the column B^-1 K_q -- which agree as long as
-        // B^-1 is accurate.  Nothing refactorises it; when the two drift apart the LP is given up as UNDEFINED and the caller's retry
-        // (bslv_lp.c:222-227: from the standard basis, an exact identity) takes over instead of a solve on a corrupted inverse
-        if (!P1 && L.rev && !(fabs(trq - pc[r]) <= 1e-8 * (1.0 + fabs(trq)))) {
+        // B^-1 is accurate.  Within a solve nothing refactorises it; when the two drift apart the LP is given up as UNDEFINED and the caller's
+        // retry (bslv_lp.c:222-227: from the standard basis, an exact identity) takes over instead of a solve on a corrupted inverse -- or,
+        // with bslv_lpq_set_refactor, the LP is marked and the call itself rebuilds the inverse from the heads and solves it again
+        // (BSLV_LP_REV_DRIFT: the test hook that takes the check as failed at a given pivot of a given LP)
+        if (!P1 && L.rev && (!(fabs(trq - pc[r]) <= 1e-8 * (1.0 + fabs(trq))) || (b == L.drift_b && Bv.iters[b] + 1 == L.drift_p))) {
             Bv.status[b] = BSLV_LP_UNDEFINED; Bv.mode[b] = MODE_NONE;
+            if (L.rfx) Bv.rmark[b] = 1;
             if (L.trace == b) printf("lp %d it %d: pivot element from the row %.17g, from the column %.17g: B^-1 has drifted\n", b, Bv.iters[b], trq, pc[r]);
             s_d.r = -1;
         } else {
@@ -1976,6 +1984,161 @@ __global__ void k_std_heads(LpView L, int slot)
     if (i < L.Mp1p) L.beta[(size_t)slot * L.Mp1p + i] = 0.0;
 }
 
+// ---- REFACTORISATION of the revised form (bslv_lpq_refactor): B^-1 of a slot rebuilt from its basis heads alone ----
+// The target X satisfies X K[:, bh] = I with K = [I | -A] (see LpView).  It is reached by REPLAYING the basis on the engine's own
+// machinery: the slot starts as the identity (the all-slack basis, row i <-> auxiliary variable i), the structural basic variables of
+// the target enter one after the other in ascending variable id, each on the row partial pivoting chooses -- the largest |v_i| of the
+// column v = X K_k (fetch_col_revised, through the pending steps) among the rows whose auxiliary variable is nonbasic in the target and
+// that have not been pivoted yet, ties to the smallest i -- and every step is recorded as an ordinary pending pivot (PivDesc, rho = row
+// r of X as virt_entry_b sees it, multipliers v_i / v_r), KP of them between two passes of k_flush.  Nothing numeric in the slot is
+// read before the identity is written, no atomics enter the arithmetic and every reduction has a fixed order: the result is a function
+// of the heads and the model.  One workgroup per LP and selection; no helper workgroups, no mailbox, no polling loop: a replay step
+// needs the column only.
+// cnt: [B][4] = structural basics to enter, entered so far, state (RFX_*), unused; enter / rowvar / elig: [B][M]
+constexpr int RFX_RUN = 0, RFX_SINGULAR = 2, RFX_HEADS = 3;
+struct RfxView { int *enter, *rowvar, *elig, *cnt; const double *cost; };
+__global__ __launch_bounds__(NT) void k_rfx_setup(LpView L, BatchView Bv, RfxView R, int n)
+{
+    __shared__ int s_cnt[NT];
+    __shared__ int s_ne;
+    const int b = blockIdx.x, tid = threadIdx.x, M = L.M, N = L.N;
+    if (b >= n) return;
+    const int slot = Bv.dst[b];
+    const int *pos = L.pos + (size_t)slot * (M + N);
+    int *enter = R.enter + (size_t)b * M, *rowvar = R.rowvar + (size_t)b * M, *elig = R.elig + (size_t)b * M;
+    // the structural basic variables in ascending id: thread t counts its stretch of the columns, a scan places it
+    const int chunk = (N + NT - 1) / NT, j0 = min(N, tid * chunk), j1 = min(N, j0 + chunk);
+    int c = 0;
+    for (int j = j0; j < j1; j++) c += pos[M + j] >= 0;
+    s_cnt[tid] = c;
+    if (tid == 0) s_ne = 0;
+    __syncthreads();
+    if (tid == 0) { int o = 0; for (int t = 0; t < NT; t++) { const int v = s_cnt[t]; s_cnt[t] = o; o += v; } }
+    __syncthreads();
+    int o = s_cnt[tid];
+    for (int j = j0; j < j1; j++) if (pos[M + j] >= 0) { if (o < M) enter[o] = M + j; o++; }
+    __shared__ int s_k;
+    if (tid == NT - 1) s_k = o;                 // (the last stretch ends where the list does)
+    // the eligible rows: the auxiliary variable is nonbasic in the target basis
+    int ne = 0;
+    for (int i = tid; i < M; i += NT) { const int e = pos[i] < 0; elig[i] = e; rowvar[i] = i; ne += e; }
+    if (ne) atomicAdd(&s_ne, ne);
+    __syncthreads();
+    if (tid == 0) {
+        int *cnt = R.cnt + (size_t)b * 4;
+        cnt[0] = s_k; cnt[1] = 0; cnt[2] = (s_k == s_ne && s_k <= M) ? RFX_RUN : RFX_HEADS; cnt[3] = 0;
+        Bv.status[b] = ST_RUNNING; Bv.iters[b] = 0; Bv.mode[b] = MODE_NONE; Bv.verified[b] = 0;
+        Bv.npend[b] = 0; Bv.pflags[b] = 0; Bv.stall[b] = 0; Bv.flushed[b] = 1;      // (in place: every pass reads and writes the slot itself)
+    }
+}
+__global__ void k_rfx_identity(LpView L, BatchView Bv, RfxView R, int n)
+{
+    const int b = blockIdx.y;
+    if (b >= n || R.cnt[(size_t)b * 4 + 2] != RFX_RUN) return;
+    double *X = L.T + (size_t)Bv.dst[b] * L.slotT;
+    const size_t total = (size_t)L.M * L.ldt;
+    for (size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x; k < total; k += (size_t)gridDim.x * blockDim.x) X[k] = (int)(k / L.ldt) == (int)(k % L.ldt) ? 1.0 : 0.0;
+}
+// up to nsel replay steps of LP b by one workgroup (256 or 1024 threads)
+__global__ __launch_bounds__(NT_BIG) void k_rfx_select(LpView L, BatchView Bv, RfxView R, int n, int nsel)
+{
+    __shared__ double sv[NT_BIG / WAVE];
+    __shared__ int si[NT_BIG / WAVE];
+    const int b = blockIdx.x, tid = threadIdx.x, NT = (int)blockDim.x, M = L.M, ldt = L.ldt;
+    if (b >= n) return;
+    int *cnt = R.cnt + (size_t)b * 4, *elig = R.elig + (size_t)b * M;
+    const int slot = Bv.dst[b];
+    for (int sdx = 0; sdx < nsel; sdx++) {
+        if (sdx) __syncthreads();              // (what thread 0 wrote for the LP in the last step is read by all)
+        const int np = Bv.npend[b], t = cnt[1];
+        if (cnt[2] != RFX_RUN || np >= KP || t >= cnt[0]) break;
+        SelCtx c = sel_ctx(L, Bv, b, np, slot, slot);
+        c.nh = R.enter + (size_t)b * M;        // (fetch_col_revised takes the variable of "column" t from here: the t-th to enter)
+        const int kq = c.nh[t];
+        fetch_col_revised(L, c, t);            // pc = -(X K_kq) through the pending steps: the tableau column, as a pivot of the engine has it
+        __syncthreads();
+        double *pc = c.pc;
+        ValIdx best{-1.0, -1};
+        double cmax = 0.0;
+        for (int i = tid; i < M; i += NT) {
+            const double a = fabs(pc[i]);
+            cmax = fmax(cmax, a);
+            if (elig[i]) best = better_max(best, ValIdx{a, i});
+        }
+        best = block_argmax(best, sv, si);
+        cmax = block_max(cmax, sv);
+        const int r = best.i;
+        if (r < 0 || !(best.v > TOL_PIV * (1.0 + cmax))) { if (tid == 0) cnt[2] = RFX_SINGULAR; break; }
+        const double p = 1.0 / pc[r];
+        double *rho = c.prow0 + (size_t)np * ldt;
+        for (int i = tid; i < ldt; i += NT) rho[i] = i < M ? virt_entry_b(c.T0[(size_t)r * ldt + i], r, i, np, c.pd, c.prow0, c.pcol0, ldt, L.Mp1p) : 0.0;
+        __syncthreads();                       // (everyone has read pc[r])
+        for (int i = tid; i <= M; i += NT) pc[i] = (i == r || i == M) ? 0.0 : pc[i] * p;
+        if (tid == 0) {
+            PivDesc d;
+            d.r = r; d.q = -1; d.p = p; d.pbeta = 0.0; d.enter_val = 0.0;
+            Bv.desc[(size_t)b * KP + np] = d;
+            elig[r] = 0; R.rowvar[(size_t)b * M + r] = kq;
+            cnt[1] = t + 1; Bv.npend[b] = np + 1; Bv.mode[b] = MODE_PIVOT;
+        }
+    }
+}
+// after the last pass: the heads of the basic variables follow the rows they ended in; a slot that is done asks for the refresh pass
+__global__ __launch_bounds__(NT) void k_rfx_finish(LpView L, BatchView Bv, RfxView R, int n)
+{
+    const int b = blockIdx.x, M = L.M;
+    if (b >= n) return;
+    int *cnt = R.cnt + (size_t)b * 4;
+    const bool ok = cnt[2] == RFX_RUN && cnt[1] == cnt[0] && Bv.npend[b] == 0;
+    __syncthreads();
+    if (!ok) { if (threadIdx.x == 0) { if (cnt[2] == RFX_RUN) cnt[2] = RFX_SINGULAR; Bv.npend[b] = 0; Bv.mode[b] = MODE_NONE; Bv.status[b] = BSLV_LP_UNDEFINED; } return; }
+    const int slot = Bv.dst[b];
+    int *bh = L.bh + (size_t)slot * M, *pos = L.pos + (size_t)slot * (M + L.N);
+    const int *rowvar = R.rowvar + (size_t)b * M;
+    for (int i = threadIdx.x; i < M; i += NT) { const int k = rowvar[i]; bh[i] = k; pos[k] = i; }
+    if (threadIdx.x == 0) Bv.mode[b] = MODE_REFRESH;
+}
+// y = sum over the rows i of c[bh_i] X[i, :] for the engine's own cost vector (cost[0] is the constant, auxiliary variables cost nothing)
+// into the LP's scratch vector uvec (free until k_rev_u): what rev_price_y does for the cost range of an objective batch
+__global__ void k_rfx_y(LpView L, BatchView Bv, RfxView R, int n)
+{
+    const int b = blockIdx.y, c = blockIdx.x * blockDim.x + threadIdx.x, M = L.M;
+    if (b >= n || c >= L.ldt) return;
+    double v = 0.0;
+    if (c < M && Bv.mode[b] == MODE_REFRESH) {
+        const int slot = Bv.dst[b];
+        const int *bh = L.bh + (size_t)slot * M;
+        const double *X = L.T + (size_t)slot * L.slotT;
+        for (int i = 0; i < M; i++) {
+            const int k = bh[i];
+            const double ck = k >= M ? R.cost[k - M + 1] : 0.0;
+            if (ck != 0.0) v = fma(ck, X[(size_t)i * L.ldt + c], v);
+        }
+    }
+    Bv.uvec[(size_t)b * L.ldt + c] = v;
+}
+// d_j = c[nh_j] - y . K[nh_j] into dcur, by column slices as k_rev_price has them
+__global__ __launch_bounds__(NT) void k_rfx_price(LpView L, BatchView Bv, RfxView R, int n)
+{
+    const int b = blockIdx.y, M = L.M;
+    if (b >= n) return;
+    const int *nh = L.nh + (size_t)Bv.dst[b] * L.N;
+    double *dc = Bv.dcur + (size_t)b * L.ld;
+    rev_row_slice(L, Bv.uvec + (size_t)b * L.ldt, nh, dc, blockIdx.x, gridDim.x);        // dc[j] = -(y . K[nh_j]), 0 on the padding (barrier at its end)
+    for (int j = blockIdx.x + gridDim.x * threadIdx.x; j < L.N; j += gridDim.x * blockDim.x) {
+        const int k = nh[j];
+        if (k >= M) dc[j] += R.cost[k - M + 1];
+    }
+}
+// test support (bslv_lpq_debug_perturb_inverse): a deterministic stand-in for drift
+__global__ void k_rfx_perturb(LpView L, int slot, double rel)
+{
+    const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= (size_t)L.M * L.M) return;
+    const int i = (int)(k / L.M), c = (int)(k % L.M);
+    L.T[(size_t)slot * L.slotT + (size_t)i * L.ldt + c] *= 1.0 + rel * (1.0 + hash01(i * L.M + c));
+}
+
 }  // namespace bslv
 
 using namespace bslv;
@@ -2017,6 +2180,12 @@ struct bslv_lpq {
     std::vector<double> canon_dir;
     double *tdir_d = nullptr, *tg_d = nullptr; int *tstate_d = nullptr, *titers_d = nullptr, *tstat_d = nullptr; int tie_Bcap = 0;
     long last_canon[4] = {0, 0, 0, 0};
+    // refactorisation of the revised form (bslv_lpq_refactor, bslv_lpq_set_refactor): the switch, the marks of the last batch (device / host),
+    // the replay's per-LP lists, the counters of the last solve call or explicit refactor
+    bool refactor_on = false;
+    int *rmark_d = nullptr; std::vector<int> rmark_h; bool rmark_valid = false;
+    int *rfx_i_d = nullptr, *rfx_c_d = nullptr; int rfx_Bcap = 0;
+    long last_rfx[4] = {0, 0, 0, 0};
     long last_passes = 0;              // (LP, pass) pairs of the last batch: how many tableaux k_flush read and wrote
     long last_launches = 0;            // k_flush launches of the last batch: one per lock-step round + one per pass made on request (bslv_lpq_materialise)
     size_t select_lds_max = 64 * 1024; // dynamic LDS of k_select<true> (candidate sort of the bound flipping ratio test)
@@ -2072,7 +2241,7 @@ static int ensure_batch(bslv_lpq *h, int B)
     auto fr = [](auto *&p) { if (p) (void)hipFree(p); p = nullptr; };
     fr(h->src_d); fr(h->dst_d); fr(h->status_d); fr(h->iters_d); fr(h->mode_d); fr(h->ver_d); fr(h->active_d); fr(h->work_d); fr(h->qslot_d); fr(h->init_d);
     fr(h->vlo_d); fr(h->vup_d); fr(h->prow_d); fr(h->desc_d); fr(h->npend_d); fr(h->flushed_d); fr(h->pcol_d); fr(h->dcur_d); fr(h->dper_d); fr(h->pflags_d); fr(h->stall_d);
-    fr(h->trow_d); fr(h->uvec_d); fr(h->xfull_d); fr(h->hmail_d);
+    fr(h->trow_d); fr(h->uvec_d); fr(h->xfull_d); fr(h->hmail_d); fr(h->rmark_d);
     if (h->status_h) { (void)hipHostFree(h->status_h); h->status_h = nullptr; }
     if (h->active_h) { (void)hipHostFree(h->active_h); h->active_h = nullptr; }
     if (h->init_h) { (void)hipHostFree(h->init_h); h->init_h = nullptr; }
@@ -2094,6 +2263,7 @@ static int ensure_batch(bslv_lpq *h, int B)
         HIP_TRY(malloc0(&h->uvec_d, (size_t)cap * h->L.ldt * sizeof(double)));
         HIP_TRY(malloc0(&h->xfull_d, (size_t)cap * h->L.N * sizeof(double)));
         HIP_TRY(malloc0(&h->hmail_d, (size_t)cap * 8 * sizeof(int)));
+        HIP_TRY(malloc0(&h->rmark_d, (size_t)cap * sizeof(int)));
     }
     HIP_TRY(malloc0(&h->desc_d, (size_t)cap * KP * sizeof(PivDesc)));
     HIP_TRY(malloc0(&h->pcol_d, (size_t)cap * KP * h->L.Mp1p * sizeof(double)));
@@ -2122,7 +2292,7 @@ static BatchView bview(bslv_lpq *h)
     v.desc = h->desc_d; v.prow = h->prow_d; v.pcol = h->pcol_d; v.dcur = h->dcur_d; v.npend = h->npend_d; v.flushed = h->flushed_d;
     v.work = h->work_d; v.nwork = h->nwork_d;
     v.dper = h->dper_d; v.pflags = h->pflags_d; v.stall = h->stall_d; v.xstat = h->xstat_d;
-    v.trow = h->trow_d; v.uvec = h->uvec_d; v.xfull = h->xfull_d; v.dbg = h->dbg_d; v.hmail = h->hmail_d;
+    v.trow = h->trow_d; v.uvec = h->uvec_d; v.xfull = h->xfull_d; v.dbg = h->dbg_d; v.hmail = h->hmail_d; v.rmark = h->rmark_d;
     v.lazy = (h->lazy && !h->L.rev) ? 1 : 0;
     return v;
 }
@@ -2289,6 +2459,9 @@ static int raw_create(bslv_lpq **out, int M, int N, const double *A, const doubl
     if (const char *e = getenv("BSLV_LP_METHOD")) {
         if (!rev) h->method = !strcmp(e, "primal") ? BSLV_LP_METHOD_PRIMAL : !strcmp(e, "repair") ? BSLV_LP_METHOD_REPAIR : BSLV_LP_METHOD_DUAL;
     }
+    // BSLV_LP_REFACTOR=1: the in-call rescue of bslv_lpq_set_refactor, for an engine in the revised form (the tableau form has no inverse to rebuild)
+    L.rfx = 0; L.drift_b = -1; L.drift_p = -1;
+    if (const char *e = getenv("BSLV_LP_REFACTOR")) { if (rev) h->refactor_on = atoi(e) != 0; }
     *out = h;
     return 0;
 }
@@ -2301,7 +2474,7 @@ void bslv_lpq_destroy(bslv_lpq *h)
     fr(h->Tstd); fr(h->lb_d); fr(h->ub_d); fr(h->art_d);
     fr(h->dbg_d); fr(h->list_d); fr(h->cptr_d); fr(h->cidx_d); fr(h->rptr_d); fr(h->ridx_d); fr(h->cval_d); fr(h->rval_d); fr(h->cost_d); fr(h->dsl_d); fr(h->trow_d); fr(h->uvec_d); fr(h->xfull_d); fr(h->hmail_d);
     fr(h->src_d); fr(h->dst_d); fr(h->status_d); fr(h->iters_d); fr(h->mode_d); fr(h->ver_d); fr(h->qslot_d); fr(h->init_d);
-    fr(h->tdir_d); fr(h->tg_d); fr(h->tstate_d); fr(h->titers_d); fr(h->tstat_d);
+    fr(h->tdir_d); fr(h->tg_d); fr(h->tstate_d); fr(h->titers_d); fr(h->tstat_d); fr(h->rmark_d); fr(h->rfx_i_d); fr(h->rfx_c_d);
     fr(h->vlo_d); fr(h->vup_d); fr(h->prow_d); fr(h->desc_d); fr(h->out_d); fr(h->active_d); fr(h->work_d); fr(h->nwork_d); fr(h->npend_d); fr(h->flushed_d); fr(h->pcol_d); fr(h->dcur_d); fr(h->dper_d); fr(h->pflags_d); fr(h->stall_d); fr(h->xstat_d); fr(h->cvals_d);
     if (h->status_h) (void)hipHostFree(h->status_h);
     if (h->active_h) (void)hipHostFree(h->active_h);
@@ -2442,7 +2615,7 @@ int bslv_lpq_reset_slot(bslv_lpq *h, int slot)
 // caller names the slots it will use as parents: bslv_lpq_materialise(h, n, slots) gives those their tableau -- the same pass, the
 // same arithmetic -- and bslv_lpq_discard_pending(h) drops the rest.  A batch that is started while slots are still open gives all
 // of them their tableau first (the retry batches of the driver).  Slots that were not materialised must not be used as `src`.
-static int flush_list(bslv_lpq *h, int cnt_slot, int upper)
+static int flush_list(bslv_lpq *h, int cnt_slot, int upper, bool account = true)      // (account: the pass counts in the statistics of the lazy tableaux and of the last batch)
 {
     LpView &L = h->L;
     hipStream_t s = h->stream;
@@ -2464,9 +2637,7 @@ static int flush_list(bslv_lpq *h, int cnt_slot, int upper)
     int n = 0;
     HIP_TRY(hipMemcpyAsync(&n, h->nwork_d + cnt_slot, sizeof(int), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    h->last_passes += n;
-    h->last_launches += 1;
-    h->lazy_materialised += n;
+    if (account) { h->last_passes += n; h->last_launches += 1; h->lazy_materialised += n; }
     if (h->profile) { float t = 0; (void)hipEventElapsedTime(&t, e0, e1); h->last_update_ms += t; (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); }
     return 0;
 }
@@ -2604,6 +2775,8 @@ static void launch_select(bslv_lpq *h, const SelectPlan &p, const BatchView &bv,
 }
 static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, const double *vlo, const double *vup,
                             int cfirst, int ccnt, const double *cvals, int *status, int *iters);
+static int solve_batch_rescue(bslv_lpq *h, int B, const int *src, const int *dst, const double *vlo, const double *vup,
+                              int cfirst, int ccnt, const double *cvals, int *status, int *iters);
 // tie phase: pivots an LP may spend in it (Bland's rule holds from PRIMAL_STALL on), and the rounds that leaves a batch at most --
 // every round an LP of the phase is in makes a pivot or ends it, except the one it waits in for a pass with KP pivots pending
 static int tie_cap(const LpView &L) { return 2 * PRIMAL_STALL + 2 * (L.M + L.N); }
@@ -2658,7 +2831,7 @@ int bslv_lpq_lazy_stats(const bslv_lpq *h, long out[3])
 int bslv_lpq_solve_batch(bslv_lpq *h, int B, const int *src, const int *dst, const double *vlo,
                          const double *vup, int *status, int *iters)
 {
-    return solve_batch_impl(h, B, src, dst, vlo, vup, 0, 0, nullptr, status, iters);
+    return solve_batch_rescue(h, B, src, dst, vlo, vup, 0, 0, nullptr, status, iters);
 }
 // The LPs of the batch differ in their OBJECTIVE (lp_set_obj_coeffs + lp_solve, bslv_lp.c:141-151,219: what phase2_dual
 // does per vertex, bslv_algs.c:1469-1477): cost costs[b*cost_cnt + t] on variable cost_first + t, 0 elsewhere (the engine's
@@ -2674,7 +2847,7 @@ int bslv_lpq_solve_batch_obj(bslv_lpq *h, int B, const int *src, const int *dst,
         cost_first = h->ps.map_var(cost_first);
     }
     for (size_t j = 0; j < h->cost.size(); j++) if (h->cost[j] != 0.0) { set_error("bslv_lpq_solve_batch_obj: the engine was created with a non-zero cost vector"); return BSLV_E_STATE; }
-    const int rc = solve_batch_impl(h, B, src, dst, vlo, vup, cost_first, cost_cnt, costs, status, iters);
+    const int rc = solve_batch_rescue(h, B, src, dst, vlo, vup, cost_first, cost_cnt, costs, status, iters);
     ++h->obj_batches;
     // test hook BSLV_LP_OBJ_UNDEFINED=K:b -- LP b of the K-th objective batch of this engine is REPORTED as UNDEFINED (as when the pivot
     // cross-check of the revised form gives it up): the callers' retry runs.  Only the status changes; the slot keeps what the solve left.
@@ -2733,6 +2906,7 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
         HIP_TRY(hipMemsetAsync(h->nwork_d, 0, need * sizeof(int), s));
     }
     HIP_TRY(hipMemsetAsync(h->xstat_d, 0, 8 * sizeof(int), s));
+    if (L.rfx) HIP_TRY(hipMemsetAsync(h->rmark_d, 0, (size_t)B * sizeof(int), s));
     BatchView bv = bview(h);
     bv.cvals = h->cvals_d;
     const int tiles = (L.mrows + TR - 1) / TR;
@@ -2896,6 +3070,7 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
         HIP_TRY(hipGetLastError());
     }
     if (status) for (int b = 0; b < B; b++) status[b] = h->status_h[b] == ST_RUNNING ? BSLV_LP_UNDEFINED : h->status_h[b];
+    if (L.rfx) { h->rmark_h.resize(B); HIP_TRY(hipMemcpy(h->rmark_h.data(), h->rmark_d, (size_t)B * sizeof(int), hipMemcpyDeviceToHost)); h->rmark_valid = true; }      // (the LPs the pivot cross-check gave up: solve_batch_rescue)
     {
         std::vector<int> itv(B);
         HIP_TRY(hipMemcpy(itv.data(), h->iters_d, B * sizeof(int), hipMemcpyDeviceToHost));
@@ -2926,6 +3101,201 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
         static const bool tm = getenv("BSLV_LP_TIMING") != nullptr;
         if (tm) fprintf(stderr, "lp solve_batch: %s form %d x %d, B %d, %d lock-step rounds, %ld pivots, %ld passes, %.1f ms; %d parents, largest family %d, %s\n", L.rev ? "revised" : "tableau", L.M, L.N, B, it, h->last_pivots, h->last_passes, h->last_total_ms, h->last_init_parents, h->last_init_family, h->last_init_chunks ? "k_init_grouped" : "k_init");
     }
+    return 0;
+}
+
+// ---- refactorisation of the revised form: host side (the kernels: k_rfx_*) ----
+static int ensure_rfx(bslv_lpq *h)
+{
+    if (h->rfx_Bcap >= h->Bcap && h->rfx_i_d) return 0;
+    auto fr = [](auto *&p) { if (p) (void)hipFree(p); p = nullptr; };
+    fr(h->rfx_i_d); fr(h->rfx_c_d);
+    h->rfx_Bcap = 0;
+    HIP_TRY(malloc0s(&h->rfx_i_d, (size_t)h->Bcap * 3 * h->L.M * sizeof(int), h->stream));
+    HIP_TRY(malloc0s(&h->rfx_c_d, (size_t)h->Bcap * 4 * sizeof(int), h->stream));
+    h->rfx_Bcap = h->Bcap;
+    return 0;
+}
+// B^-1 of the n slots (distinct, in range) rebuilt in place from their heads, in lock step; status_out[b]: 0, or BSLV_LP_UNDEFINED for a
+// slot whose basis is singular or whose heads are inconsistent (it is reset to the standard basis).  ok / pivots / failed: the counters.
+static int refactor_impl(bslv_lpq *h, int n, const int *slots, int *status_out, long *ok_out, long *pivots_out, long *failed_out)
+{
+    LpView &L = h->L;
+    hipStream_t s = h->stream;
+    int rc;
+    if ((rc = ensure_batch(h, n))) return rc;
+    if ((rc = ensure_rfx(h))) return rc;
+    const int M = L.M;
+    const int rounds_max = (M + KP - 1) / KP + 2;
+    {   // the work lists of the rounds and of the refresh pass behind them
+        const int need = std::max(L.maxit + 64, rounds_max + 2);
+        if (need > h->nworkcap) { if (h->nwork_d) (void)hipFree(h->nwork_d); h->nwork_d = nullptr; HIP_TRY(malloc0s(&h->nwork_d, need * sizeof(int), s)); h->nworkcap = need; }
+        HIP_TRY(hipMemsetAsync(h->nwork_d, 0, (size_t)(rounds_max + 2) * sizeof(int), s));
+    }
+    L.objmode = 0;
+    for (int b = 0; b < n; b++) h->active_h[b] = b;
+    HIP_TRY(hipMemcpyAsync(h->active_d, h->active_h, n * sizeof(int), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(h->src_d, slots, n * sizeof(int), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(h->dst_d, slots, n * sizeof(int), hipMemcpyHostToDevice, s));
+    BatchView bv = bview(h);
+    RfxView R;
+    R.enter = h->rfx_i_d; R.rowvar = h->rfx_i_d + (size_t)h->Bcap * M; R.elig = h->rfx_i_d + (size_t)h->Bcap * 2 * M; R.cnt = h->rfx_c_d; R.cost = h->cost_d;
+    hipLaunchKernelGGL(k_rfx_setup, dim3(n), dim3(NT), 0, s, L, bv, R, n);
+    {
+        const size_t total = (size_t)M * L.ldt;
+        hipLaunchKernelGGL(k_rfx_identity, dim3((unsigned)std::min<size_t>((total + 255) / 256, 4096), n), dim3(256), 0, s, L, bv, R, n);
+    }
+    HIP_TRY(hipGetLastError());
+    std::vector<int> cnt((size_t)n * 4);
+    HIP_TRY(hipMemcpyAsync(cnt.data(), h->rfx_c_d, cnt.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    int kmax = 0;
+    for (int b = 0; b < n; b++) if (cnt[(size_t)b * 4 + 2] == RFX_RUN) kmax = std::max(kmax, cnt[(size_t)b * 4]);
+    // one round = KP replay steps on vectors, one pass; an LP with fewer structural basics is done earlier and is passed over
+    const int rounds = std::min((kmax + KP - 1) / KP, rounds_max);
+    const int snt = M >= 1536 ? NT_BIG : NT;
+    for (int it = 0; it < rounds; it++) {
+        hipLaunchKernelGGL(k_rfx_select, dim3(n), dim3(snt), 0, s, L, bv, R, n, KP);
+        hipLaunchKernelGGL(k_list_pending, dim3((n + 255) / 256), dim3(256), 0, s, bv, h->active_d, n, it);
+        if ((rc = flush_list(h, it, n, false))) return rc;
+    }
+    hipLaunchKernelGGL(k_rfx_finish, dim3(n), dim3(NT), 0, s, L, bv, R, n);
+    // the reduced costs of the engine's own cost vector -> dsl, then uvec = -K_N x_N and beta[M], then one refresh pass for beta
+    hipLaunchKernelGGL(k_rfx_y, dim3((L.ldt + 255) / 256, n), dim3(256), 0, s, L, bv, R, n);
+    hipLaunchKernelGGL(k_rfx_price, dim3((L.ld + REV_PRICE_SLICE - 1) / REV_PRICE_SLICE, n), dim3(NT), 0, s, L, bv, R, n);
+    hipLaunchKernelGGL(k_rev_store_d, dim3((L.ld + 255) / 256, n), dim3(256), 0, s, L, bv, n);
+    hipLaunchKernelGGL(k_rev_u, dim3(n), dim3(NT), 0, s, L, bv, n, (const int *)nullptr, 0);
+    hipLaunchKernelGGL(k_list_pending, dim3((n + 255) / 256), dim3(256), 0, s, bv, h->active_d, n, rounds_max + 1);
+    HIP_TRY(hipGetLastError());
+    if ((rc = flush_list(h, rounds_max + 1, n, false))) return rc;
+    HIP_TRY(hipMemcpy(cnt.data(), h->rfx_c_d, cnt.size() * sizeof(int), hipMemcpyDeviceToHost));
+    for (int b = 0; b < n; b++) {
+        const bool ok = cnt[(size_t)b * 4 + 2] == RFX_RUN;
+        if (status_out) status_out[b] = ok ? 0 : BSLV_LP_UNDEFINED;
+        if (ok) { *ok_out += 1; *pivots_out += cnt[(size_t)b * 4 + 1]; }
+        else { *failed_out += 1; if ((rc = bslv_lpq_reset_slot(h, slots[b]))) return rc; }      // (nothing can read a half-built inverse)
+    }
+    return 0;
+}
+// solve_batch_impl, and with bslv_lpq_set_refactor the rescue behind it: every LP the pivot cross-check gave up has its slot refactorised
+// in place (the slot's heads, statuses and values are current: they follow every committed pivot; what is pending for its matrix is
+// dropped) and is solved again in place with its own bounds and costs by the ordinary batch path, at most RESCUE_MAX times per call.
+constexpr int RESCUE_MAX = 3;
+static int solve_batch_rescue(bslv_lpq *h, int B, const int *src, const int *dst, const double *vlo, const double *vup,
+                              int cfirst, int ccnt, const double *cvals, int *status, int *iters)
+{
+    if (h) {
+        LpView &L = h->L;
+        for (int k = 0; k < 4; k++) h->last_rfx[k] = 0;
+        h->rmark_valid = false;
+        L.rfx = (h->refactor_on && L.rev) ? 1 : 0;
+        L.drift_b = -1; L.drift_p = -1;
+        if (L.rev) if (const char *e = getenv("BSLV_LP_REV_DRIFT")) { int lp = -1, p = -1; if (sscanf(e, "%d:%d", &lp, &p) == 2 && lp >= 0 && p >= 1) { L.drift_b = lp; L.drift_p = p; } }
+    }
+    int rc = solve_batch_impl(h, B, src, dst, vlo, vup, cfirst, ccnt, cvals, status, iters);
+    if (!h) return rc;
+    LpView &L = h->L;
+    L.drift_b = -1; L.drift_p = -1;             // (once per call: not again in the rescue)
+    if (rc || !L.rfx || !h->rmark_valid || B <= 0) return rc;
+    std::vector<int> todo;
+    {
+        std::vector<char> taken(h->slots, 0);
+        for (int b = 0; b < B; b++) if (h->rmark_h[b]) { if (taken[dst[b]]) h->last_rfx[3]++; else { taken[dst[b]] = 1; todo.push_back(b); } }
+    }
+    if (todo.empty()) return 0;
+    int tot_iters = h->last_iters; long tot_pivots = h->last_pivots, tot_passes = h->last_passes, tot_launches = h->last_launches;
+    double tot_upd = h->last_update_ms, tot_ms = h->last_total_ms;
+    long ext[5], p1[3];
+    for (int k = 0; k < 5; k++) ext[k] = h->last_ext[k];
+    for (int k = 0; k < 3; k++) p1[k] = h->last_p1[k];
+    const int vc = L.vcnt;
+    for (int attempt = 0; attempt < RESCUE_MAX && !todo.empty(); attempt++) {
+        const auto t0 = std::chrono::steady_clock::now();
+        const int n = (int)todo.size();
+        std::vector<int> slots(n), rst(n);
+        for (int k = 0; k < n; k++) slots[k] = dst[todo[k]];
+        if ((rc = refactor_impl(h, n, slots.data(), rst.data(), &h->last_rfx[0], &h->last_rfx[1], &h->last_rfx[3]))) return rc;
+        tot_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        std::vector<int> lps, sl;
+        for (int k = 0; k < n; k++) if (rst[k] == 0) { lps.push_back(todo[k]); sl.push_back(slots[k]); }
+        todo.clear();
+        const int m = (int)lps.size();
+        if (m == 0) break;
+        std::vector<double> lo2((size_t)m * std::max(vc, 1)), up2((size_t)m * std::max(vc, 1)), cv2((size_t)m * std::max(ccnt, 1));
+        for (int k = 0; k < m; k++) {
+            if (vc > 0) { memcpy(&lo2[(size_t)k * vc], vlo + (size_t)lps[k] * vc, vc * sizeof(double)); memcpy(&up2[(size_t)k * vc], vup + (size_t)lps[k] * vc, vc * sizeof(double)); }
+            if (cvals) memcpy(&cv2[(size_t)k * ccnt], cvals + (size_t)lps[k] * ccnt, ccnt * sizeof(double));
+        }
+        std::vector<int> st2(m), it2(m);
+        h->rmark_valid = false;
+        if ((rc = solve_batch_impl(h, m, sl.data(), sl.data(), vc > 0 ? lo2.data() : nullptr, vc > 0 ? up2.data() : nullptr, cfirst, ccnt, cvals ? cv2.data() : nullptr, st2.data(), it2.data()))) return rc;
+        tot_iters += h->last_iters; tot_pivots += h->last_pivots; tot_passes += h->last_passes; tot_launches += h->last_launches;
+        tot_upd += h->last_update_ms; tot_ms += h->last_total_ms;
+        for (int k = 0; k < 5; k++) ext[k] += h->last_ext[k];
+        for (int k = 0; k < 3; k++) p1[k] += h->last_p1[k];
+        for (int k = 0; k < m; k++) {
+            const int b = lps[k];
+            if (iters) iters[b] += it2[k];
+            if (st2[k] != BSLV_LP_UNDEFINED) { if (status) status[b] = st2[k]; h->last_rfx[2]++; }
+            else if (h->rmark_valid && h->rmark_h[k] && attempt + 1 < RESCUE_MAX) todo.push_back(b);      // (drifted again: once more)
+            else h->last_rfx[3]++;                 // (k_prep refused the restart, or the cap: the LP stays UNDEFINED, as without the switch)
+        }
+    }
+    h->last_iters = tot_iters; h->last_pivots = tot_pivots; h->last_passes = tot_passes; h->last_launches = tot_launches;
+    h->last_update_ms = tot_upd; h->last_total_ms = tot_ms;
+    for (int k = 0; k < 5; k++) h->last_ext[k] = ext[k];
+    for (int k = 0; k < 3; k++) h->last_p1[k] = p1[k];
+    return 0;
+}
+int bslv_lpq_refactor(bslv_lpq *h, int n, const int *slots, int *status_out)
+{
+    if (!h) { set_error("bslv_lpq_refactor: no engine"); return BSLV_E_ARG; }
+    if (!h->L.rev) { set_error("bslv_lpq_refactor: the engine is in the tableau form, which keeps no basis inverse to rebuild"); return BSLV_E_ARG; }
+    if (n < 0 || (n > 0 && !slots)) { set_error("bslv_lpq_refactor: bad argument (n = %d)", n); return BSLV_E_ARG; }
+    std::vector<char> taken(h->slots, 0);
+    for (int b = 0; b < n; b++) {
+        if (slots[b] < 0 || slots[b] >= h->slots) { set_error("bslv_lpq_refactor: bad slot %d at %d (pool %d)", slots[b], b, h->slots); return BSLV_E_ARG; }
+        if (taken[slots[b]]) { set_error("bslv_lpq_refactor: bad slot %d at %d: named twice", slots[b], b); return BSLV_E_ARG; }
+        taken[slots[b]] = 1;
+    }
+    for (int k = 0; k < 4; k++) h->last_rfx[k] = 0;
+    if (n == 0) return 0;
+    return refactor_impl(h, n, slots, status_out, &h->last_rfx[0], &h->last_rfx[1], &h->last_rfx[3]);
+}
+int bslv_lpq_set_refactor(bslv_lpq *h, int on)
+{
+    if (!h) { set_error("bslv_lpq_set_refactor: no engine"); return BSLV_E_ARG; }
+    if (on && !h->L.rev) { set_error("bslv_lpq_set_refactor: the engine is in the tableau form, which keeps no basis inverse to rebuild"); return BSLV_E_ARG; }
+    h->refactor_on = on != 0;
+    return 0;
+}
+int bslv_lpq_get_refactor(const bslv_lpq *h) { return h && h->refactor_on; }
+int bslv_lpq_last_refactor_stats(const bslv_lpq *h, long out[4])
+{
+    if (!h || !out) return BSLV_E_ARG;
+    for (int k = 0; k < 4; k++) out[k] = h->last_rfx[k];
+    return 0;
+}
+int bslv_lpq_get_inverse(bslv_lpq *h, int slot, int *heads, double *X)
+{
+    if (!h || !heads) { set_error("bslv_lpq_get_inverse: bad argument"); return BSLV_E_ARG; }
+    if (!h->L.rev) { set_error("bslv_lpq_get_inverse: the engine is in the tableau form, which keeps no basis inverse"); return BSLV_E_ARG; }
+    if (slot < 0 || slot >= h->slots) { set_error("bslv_lpq_get_inverse: bad slot %d", slot); return BSLV_E_ARG; }
+    const LpView &L = h->L;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpy(heads, L.bh + (size_t)slot * L.M, (size_t)L.M * sizeof(int), hipMemcpyDeviceToHost));
+    if (X) HIP_TRY(hipMemcpy2D(X, (size_t)L.M * sizeof(double), L.T + (size_t)slot * L.slotT, (size_t)L.ldt * sizeof(double), (size_t)L.M * sizeof(double), (size_t)L.M, hipMemcpyDeviceToHost));
+    return 0;
+}
+int bslv_lpq_debug_perturb_inverse(bslv_lpq *h, int slot, double rel)
+{
+    if (!h) { set_error("bslv_lpq_debug_perturb_inverse: no engine"); return BSLV_E_ARG; }
+    if (!h->L.rev) { set_error("bslv_lpq_debug_perturb_inverse: the engine is in the tableau form, which keeps no basis inverse"); return BSLV_E_ARG; }
+    if (slot < 0 || slot >= h->slots) { set_error("bslv_lpq_debug_perturb_inverse: bad slot %d", slot); return BSLV_E_ARG; }
+    const size_t nk = (size_t)h->L.M * h->L.M;
+    hipLaunchKernelGGL(k_rfx_perturb, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, h->stream, h->L, slot, rel);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(h->stream));
     return 0;
 }
 

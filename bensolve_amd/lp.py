@@ -217,6 +217,48 @@ class LpEngine:
         check(self.lib.bslv_lpq_last_canonical_stats(self.h, o))
         return dict(entered=int(o[0]), tie_pivots=int(o[1]), no_candidate=int(o[2]), capped=int(o[3]))
 
+    def refactor(self, slots):
+        """revised form: rebuild the basis inverse of the slots in place from their heads (bslv_lpq_refactor); returns the
+        per-slot statuses (0, or 3 = UNDEFINED for a singular basis: the slot is then reset to the standard basis)"""
+        slots = np.ascontiguousarray(slots, np.int32)
+        st = np.empty(len(slots), np.int32)
+        self.lib.bslv_lpq_refactor.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+        check(self.lib.bslv_lpq_refactor(self.h, len(slots), slots.ctypes.data, st.ctypes.data))
+        return st
+
+    def set_refactor(self, on):
+        """the in-call rescue of LPs the pivot cross-check gives up (bslv_lpq_set_refactor).  Returns the library's code (0, or
+        BSLV_E_ARG for the tableau form)."""
+        self.lib.bslv_lpq_set_refactor.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        return int(self.lib.bslv_lpq_set_refactor(self.h, int(bool(on))))
+
+    def get_refactor(self):
+        self.lib.bslv_lpq_get_refactor.argtypes = [ctypes.c_void_p]
+        return int(self.lib.bslv_lpq_get_refactor(self.h))
+
+    def last_refactor_stats(self):
+        """of the last solve call or explicit refactor (bslv_lpq_last_refactor_stats)"""
+        o = (ctypes.c_long * 4)()
+        self.lib.bslv_lpq_last_refactor_stats.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        check(self.lib.bslv_lpq_last_refactor_stats(self.h, o))
+        return dict(refactorised=int(o[0]), replay_pivots=int(o[1]), rescued=int(o[2]), failed=int(o[3]))
+
+    def get_inverse(self, slot, matrix=True):
+        """revised form: (basis heads, stored matrix M x M or None) of a slot, in the engine's own indices (bslv_lpq_get_inverse)"""
+        self.lib.bslv_lpq_is_revised.argtypes = [ctypes.c_void_p]
+        self.lib.bslv_lpq_rows_folded.argtypes = [ctypes.c_void_p]
+        M = self.M - int(self.lib.bslv_lpq_rows_folded(self.h))
+        heads = np.empty(M, np.int32)
+        X = np.empty((M, M), np.float64) if matrix else None
+        self.lib.bslv_lpq_get_inverse.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+        check(self.lib.bslv_lpq_get_inverse(self.h, int(slot), heads.ctypes.data, X.ctypes.data if matrix else None))
+        return heads, X
+
+    def debug_perturb_inverse(self, slot, rel):
+        """tests only: a deterministic stand-in for drift in the stored inverse of a slot (bslv_lpq_debug_perturb_inverse)"""
+        self.lib.bslv_lpq_debug_perturb_inverse.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_double]
+        check(self.lib.bslv_lpq_debug_perturb_inverse(self.h, int(slot), float(rel)))
+
     def last_stats(self):
         it = ctypes.c_int()
         piv = ctypes.c_long()

@@ -77,10 +77,41 @@ int  bslv_lpq_rows_folded(const bslv_lpq *h);
  * for the whole pool; tableau rows and columns are sparse products, the delayed update and its pass kernel run on B^-1 (ex09 of the
  * reference's suite: 171 MB per LP instead of 1.36 GB).  Same interface, same slots and warm starts, bslv_lpq_solve_batch_obj included
  * (the new reduced-cost row is one tableau row built from y = sum of c_t times the rows of the parent's B^-1 that hold the basic
- * cost-carrying variables), and nothing refactorises B^-1: an LP whose inverse has drifted (the pivot element from its row and from its
- * column disagree) comes back BSLV_LP_UNDEFINED for the caller's retry from the standard basis (bslv_lp.c:222-227).  Chosen by itself
+ * cost-carrying variables).  Within a solve B^-1 is only ever updated, and children inherit it from their parents: an LP whose inverse
+ * has drifted (the pivot element from its row and from its column disagree) comes back BSLV_LP_UNDEFINED for the caller's retry from the
+ * standard basis (bslv_lp.c:222-227) -- unless the refactorisation below is switched on, which is off by default.  Chosen by itself
  * for N >= 2 M, < 2 % non-zeros and tableaux of 4 GiB and more; BSLV_LP_REV=0 / 1 forces the form.  Returns 1 in the revised form. */
 int  bslv_lpq_is_revised(const bslv_lpq *h);
+/* REFACTORISATION (revised form only; the tableau form answers BSLV_E_ARG, its message names the tableau form).
+ * bslv_lpq_refactor rebuilds B^-1 of the n named slots (distinct) in place from their basis heads alone -- nothing numeric in the
+ * slot's matrix is read: the slot is set to the identity and the structural basic variables enter one after the other in ascending
+ * variable id, each on the row partial pivoting chooses among the rows whose auxiliary variable is nonbasic, as ordinary pending
+ * pivots of the engine (KP steps per pass, at most ceil(M / KP) + 2 rounds for all slots in lock step).  The result is a function of
+ * the heads and the model.  Afterwards the heads of the basic variables name the rows they ended in (the basis as a set, the nonbasic
+ * heads, statuses and values stay), the reduced costs are rebuilt for the ENGINE'S OWN cost vector -- a slot that an objective batch
+ * produced gets the own-cost (zero) row, bslv_lpq_solve_batch_obj rebuilds its row from y anyway -- and the basic values are
+ * recomputed.  status_out[b] (may be NULL): 0, or BSLV_LP_UNDEFINED for a singular basis (a pivot with |v_r| <= 1e-9 (1 + max |v|))
+ * or inconsistent heads; such a slot is reset to the standard basis as by bslv_lpq_reset_slot.  Errors: tableau form, bad slot (out of
+ * range or named twice), n < 0.
+ * bslv_lpq_set_refactor(h, 1) (BSLV_LP_REFACTOR=1 when an engine comes up in the revised form; the tableau form ignores the variable
+ * and answers BSLV_E_ARG to on = 1): an LP that the pivot cross-check gives up is, after the rounds of the batch and inside the same
+ * solve_batch / solve_batch_obj call, refactorised in its dst slot and solved again in place with its own bounds (and costs), at
+ * most 3 times per LP and call; iters[] add up and bslv_lpq_last_stats covers the whole call.  It stays BSLV_LP_UNDEFINED, as without
+ * the switch, when the restart is refused or it fails again at the cap.  With the switch off nothing changes.
+ * bslv_lpq_last_refactor_stats, of the last solve call or explicit refactor: [0] slots refactorised, [1] replay pivots, [2] LPs
+ * rescued (they ended with a status other than UNDEFINED), [3] refactorisations that failed or rescues that stayed UNDEFINED. */
+int  bslv_lpq_refactor(bslv_lpq *h, int n, const int *slots, int *status_out);
+int  bslv_lpq_set_refactor(bslv_lpq *h, int on);
+int  bslv_lpq_get_refactor(const bslv_lpq *h);
+int  bslv_lpq_last_refactor_stats(const bslv_lpq *h, long out[4]);
+/* Test and diagnostic support of the revised form, plain C ABI like everything here.  bslv_lpq_get_inverse: the basis heads (M
+ * variable ids: 0..M-1 auxiliary, M.. structural) and, unless X is NULL, the stored matrix of a slot, M x M row-major, in the indices
+ * of the engine's own model (M = rows given minus bslv_lpq_rows_folded).  bslv_lpq_debug_perturb_inverse multiplies entry (i, c) of
+ * the stored matrix by 1 + rel (1 + hash01(i M + c)): a deterministic stand-in for drift, for tests only.  BSLV_LP_REV_DRIFT=b:p
+ * (test hook, read per solve call, off by default): the pivot cross-check of LP b of the batch is taken as failed at the LP's p-th
+ * pivot (p >= 1), once per call and not again in the in-call rescue; nothing else changes. */
+int  bslv_lpq_get_inverse(bslv_lpq *h, int slot, int *heads /* M */, double *X /* M x M row-major, may be NULL */);
+int  bslv_lpq_debug_perturb_inverse(bslv_lpq *h, int slot, double rel);
 int  bslv_lpq_pool_slots(const bslv_lpq *h);
 size_t bslv_lpq_slot_bytes(const bslv_lpq *h);
 /* LAZY TABLEAUX.  The first pass of a solve writes the LP's tableau into its own slot -- the largest memory item of a batch, and

@@ -1,0 +1,455 @@
+"""GPU: the revised form of the LP engine rebuilds a slot's basis inverse on the device (bslv_lpq_refactor), and with
+bslv_lpq_set_refactor an LP that the pivot cross-check gives up is refactorised and solved again inside the same call.
+
+Models: the sparse P2(v) of tests/test_lp_gpu.py (_sparse_covering, copied): 47 x 304 -- neither M nor N a multiple of the padding,
+the replay takes several groups of KP steps -- and 127 x 6004 with six dense columns (the 1024-thread selection, wide rows).  Neither
+has a single-entry row, so nothing is folded and K = [I | -L] in the indices as given.  Every run: BSLV_LP_REV=1, a cold solve into
+slot 0, a warm batch into slots 1..B, a second generation from those slots with shifted right-hand sides."""
+import contextlib
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from bensolve_amd import synth
+from bensolve_amd.lp import P2Model, LpEngine, bounds_from_types
+
+pytestmark = pytest.mark.gpu
+RTOL = 1e-9
+OPTIMAL, UNDEFINED = 4, 3
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+#        m,   n,    q, seed, dense_cols, B
+CASES = {"main": (40, 300, 3, 5, 0, 24), "wide": (120, 6000, 3, 11, 6, 8)}
+
+
+def _sparse_covering(m, n, q, seed, per_col=4, dense_cols=0):
+    """covering VLP with a sparse A (per_col non-zeros per column, every row hit) and sparse objectives (tests/test_lp_gpu.py)"""
+    rng = np.random.default_rng(seed)
+    prob = synth.covering_vlp(m, n, q, seed)
+    A = np.zeros((m, n))
+    for j in range(n):
+        k = m // 2 if j < dense_cols else per_col
+        rows = rng.choice(m, size=k, replace=False)
+        A[rows, j] = rng.uniform(0.5, 1.5, size=k) * (0.2 if j < dense_cols else 1.0)
+    for i in range(m):
+        if not A[i].any():
+            A[i, rng.integers(n)] = 1.0
+    P = prob["P"] * (rng.random((q, n)) < 0.3)
+    P[:, 0] = prob["P"][:, 0]
+    prob = dict(prob, A=A, P=P)
+    return prob
+
+
+def _random_V(model, prob, rng, B):
+    n = prob["n"]
+    X = rng.random((B, n)) * (3.0 / n) + 1.0 / n
+    Y = X @ prob["P"].T
+    return Y * rng.uniform(0.2, 1.2, size=(B, 1)) + rng.normal(scale=0.05, size=Y.shape)
+
+
+@contextlib.contextmanager
+def _env(**kv):
+    old = {k: os.environ.get(k) for k in kv}
+    try:
+        for k, v in kv.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+        yield
+    finally:
+        for k, v in old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+
+
+_PROBLEMS = {}
+
+
+def _problem(case):
+    if case not in _PROBLEMS:
+        m, n, q, seed, dense, B = CASES[case]
+        prob = _sparse_covering(m, n, q, seed, dense_cols=dense)
+        model = P2Model(prob)
+        assert not np.any((model.L != 0).sum(axis=1) == 1), "a single-entry row would be folded into a column bound"
+        rng = np.random.default_rng(seed)
+        V = _random_V(model, prob, rng, B)
+        K = np.hstack([np.eye(model.M), -model.L])
+        _PROBLEMS[case] = dict(prob=prob, model=model, B=B, ub=model.ub_for(V), ub2=model.ub_for(V * 1.07 + 0.01), K=K,
+                               dst=np.arange(1, B + 1, dtype=np.int32), dst2=np.arange(B + 1, 2 * B + 1, dtype=np.int32))
+    return _PROBLEMS[case]
+
+
+def _read(eng, model, slots):
+    return dict(obj=eng.obj(slots).copy(), w=eng.dual(slots, model.w_first, model.q).copy(), y=eng.primal(slots, model.y_first, model.q).copy())
+
+
+def _first_generation(case, rev="1", hook=None, switch=None):
+    """engine with the cold solve in slot 0 and the warm batch in slots 1..B; the hook (BSLV_LP_REV_DRIFT) covers the warm batch only"""
+    p = _problem(case)
+    model, B = p["model"], p["B"]
+    with _env(BSLV_LP_REV=rev, BSLV_LP_REFACTOR=None, BSLV_LP_REV_DRIFT=None):
+        eng = LpEngine.from_model(model, pool_slots=2 * B + 4)
+        assert eng.rows_folded() == 0
+        assert eng.lib.bslv_lpq_is_revised(eng.h) == int(rev)
+        if switch is not None:
+            assert eng.set_refactor(switch) == 0
+        eng.reset_slot(0)
+        st0, _ = eng.solve_batch([0], [0], np.full((1, model.r), -np.inf), p["ub"][:1])
+        assert st0[0] == OPTIMAL, st0
+        with _env(BSLV_LP_REV_DRIFT=hook):
+            st, it = eng.solve_batch(np.zeros(B, np.int32), p["dst"], np.full((B, model.r), -np.inf), p["ub"])
+    return eng, st, it
+
+
+def _second_generation(eng, case):
+    p = _problem(case)
+    model, B = p["model"], p["B"]
+    with _env(BSLV_LP_REV_DRIFT=None):
+        st2, it2 = eng.solve_batch(p["dst"], p["dst2"], np.full((B, model.r), -np.inf), p["ub2"])
+    assert np.all(st2 == OPTIMAL), st2
+    return _read(eng, model, p["dst2"]), it2
+
+
+_REFERENCE = {}
+
+
+def _reference(case):
+    """the run that never touches the new entry points: first and second generation, computed once per case"""
+    if case not in _REFERENCE:
+        p = _problem(case)
+        eng, st, it = _first_generation(case)
+        assert np.all(st == OPTIMAL), st
+        first = _read(eng, p["model"], p["dst"])
+        second, it2 = _second_generation(eng, case)
+        eng.close()
+        _REFERENCE[case] = dict(first=first, it=it.copy(), second=second, it2=it2.copy())
+    return _REFERENCE[case]
+
+
+def _basis(p, heads):
+    return p["K"][:, heads]
+
+
+def _residual(p, heads, X):
+    return float(np.abs(X @ _basis(p, heads) - np.eye(len(heads))).max())
+
+
+def _rho_ref(p, heads):
+    Bm = _basis(p, heads)
+    return float(np.abs(np.linalg.inv(Bm) @ Bm - np.eye(len(heads))).max())
+
+
+def _bound(rho_ref):
+    # 64: the replay's k rank-1 steps against LAPACK's blocked LU; five orders below anything a wrong step produces
+    return max(1e-12, 64.0 * rho_ref)
+
+
+def _keyed(heads, X):
+    """rows of X by the variable that is basic in them"""
+    return {int(k): X[i].copy() for i, k in enumerate(heads)}
+
+
+def _same_bits(a, b):
+    return a.shape == b.shape and np.array_equal(np.ascontiguousarray(a).view(np.uint8), np.ascontiguousarray(b).view(np.uint8))
+
+
+def _close(got, ref, b=None):
+    sel = slice(None) if b is None else b
+    np.testing.assert_allclose(got["obj"][sel], ref["obj"][sel], rtol=RTOL, atol=1e-9)
+    np.testing.assert_allclose(got["w"][sel], ref["w"][sel], rtol=0, atol=1e-7)
+    np.testing.assert_allclose(got["y"][sel], ref["y"][sel], rtol=0, atol=1e-7)
+
+
+@pytest.mark.parametrize("case", ["main", "wide"])
+def test_rebuilt_inverse_against_the_host(case):
+    """X K[:, heads] = I: the rebuilt inverse of four first-generation slots against numpy's inverse of the same basis.  The basis set
+    and the solution of the slot (objective, w, y: reduced costs and basic values are rebuilt too) stay what they were."""
+    p = _problem(case)
+    model = p["model"]
+    eng, st, _ = _first_generation(case)
+    assert np.all(st == OPTIMAL), st
+    slots = p["dst"][:4]
+    before = _read(eng, model, slots)
+    old = [eng.get_inverse(s) for s in slots]
+    assert all(len(set(h.tolist())) == model.M and h.min() >= 0 and h.max() < model.M + model.N for h, _ in old)
+    status = eng.refactor(slots)
+    assert list(status) == [0] * 4, status
+    stats = eng.last_refactor_stats()
+    assert stats["refactorised"] == 4 and stats["failed"] == 0 and stats["rescued"] == 0
+    assert stats["replay_pivots"] == sum(int((h >= model.M).sum()) for h, _ in old)
+    for s, (h0, X0) in zip(slots, old):
+        h1, X1 = eng.get_inverse(s)
+        assert set(h1.tolist()) == set(h0.tolist())
+        rho_ref, res, res_old = _rho_ref(p, h0), _residual(p, h1, X1), _residual(p, h0, X0)
+        print("lp_refactor_residual case %s M %d N %d slot %d structural_basics %d rho_ref %.3e rebuilt %.3e updated_only %.3e" % (
+            case, model.M, model.N, s, int((h0 >= model.M).sum()), rho_ref, res, res_old))
+        assert res <= _bound(rho_ref), (case, s, res, rho_ref)
+    _close(_read(eng, model, slots), before)
+    eng.close()
+
+
+@pytest.mark.parametrize("case", ["main", "wide"])
+def test_refactor_repairs_a_perturbed_inverse(case):
+    """a drifted inverse (debug_perturb_inverse, never solved from) is rebuilt from the heads; the children of the repaired slots equal
+    the children of an untouched engine at the revised-vs-tableau tolerances"""
+    p = _problem(case)
+    ref = _reference(case)
+    eng, st, _ = _first_generation(case)
+    assert np.all(st == OPTIMAL), st
+    slots = p["dst"]
+    rho = {}
+    for s in slots:
+        eng.debug_perturb_inverse(s, 1e-6)
+        h, X = eng.get_inverse(s)
+        assert _residual(p, h, X) >= 1e-7, "the perturbation hook did not change the stored inverse"
+        rho[int(s)] = _rho_ref(p, h)
+    assert list(eng.refactor(slots)) == [0] * len(slots)
+    for s in slots:
+        h, X = eng.get_inverse(s)
+        assert _residual(p, h, X) <= _bound(rho[int(s)]), (case, s)
+    _close(_read(eng, p["model"], slots), ref["first"])
+    second, _ = _second_generation(eng, case)
+    _close(second, ref["second"])
+    eng.close()
+
+
+def test_refactor_is_deterministic_and_handles_the_edges():
+    case = "main"
+    p = _problem(case)
+    model, M = p["model"], p["model"].M
+    eng, st, _ = _first_generation(case)
+    assert eng.get_refactor() == 0                      # off unless asked for
+    # twice: bit-identical by head variable
+    slots = p["dst"][:3]
+    eng.refactor(slots)
+    first = [eng.get_inverse(s) for s in slots]
+    eng.refactor(slots)
+    for s, (h1, X1) in zip(slots, first):
+        h2, X2 = eng.get_inverse(s)
+        k1, k2 = _keyed(h1, X1), _keyed(h2, X2)
+        assert k1.keys() == k2.keys() and all(_same_bits(k1[k], k2[k]) for k in k1), s
+    # the all-slack basis: the exact identity, no replay pivot
+    fresh = 2 * p["B"] + 1
+    eng.reset_slot(fresh)
+    assert list(eng.refactor([fresh])) == [0]
+    assert eng.last_refactor_stats() == dict(refactorised=1, replay_pivots=0, rescued=0, failed=0)
+    h, X = eng.get_inverse(fresh)
+    assert np.array_equal(h, np.arange(M)) and _same_bits(X, np.eye(M))
+    # slots with different numbers of structural basics in one batch = one slot at a time
+    mixed = [fresh, 0] + [int(s) for s in p["dst"][3:9]]
+    ks = [int((eng.get_inverse(s, matrix=False)[0] >= M).sum()) for s in mixed]
+    assert len(set(ks)) >= 2, ks
+    assert list(eng.refactor(mixed)) == [0] * len(mixed)
+    assert eng.last_refactor_stats()["replay_pivots"] == sum(ks)
+    together = [eng.get_inverse(s) for s in mixed]
+    for s, (ht, Xt) in zip(mixed, together):
+        assert list(eng.refactor([s])) == [0]
+        hs, Xs = eng.get_inverse(s)
+        assert np.array_equal(hs, ht) and _same_bits(Xs, Xt), s
+    # errors: a slot out of range, a slot named twice, n < 0
+    for bad in ([eng.pool_slots], [-1], [1, 1]):
+        with pytest.raises(Exception, match="bad slot"):
+            eng.refactor(bad)
+    import ctypes
+    eng.lib.bslv_lpq_refactor.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+    assert eng.lib.bslv_lpq_refactor(eng.h, -1, None, None) == 2
+    assert b"n = -1" in eng.lib.bslv_last_error()
+    eng.close()
+
+
+def test_tableau_form_refuses():
+    eng, st, _ = _first_generation("main", rev="0")
+    import ctypes
+    slots = np.array([1], np.int32)
+    eng.lib.bslv_lpq_refactor.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+    assert eng.lib.bslv_lpq_refactor(eng.h, 1, slots.ctypes.data, None) == 2          # BSLV_E_ARG
+    assert b"tableau" in eng.lib.bslv_last_error()
+    assert eng.set_refactor(1) == 2 and b"tableau" in eng.lib.bslv_last_error()
+    assert eng.get_refactor() == 0
+    with pytest.raises(Exception, match="tableau"):
+        eng.get_inverse(1)
+    with _env(BSLV_LP_REV="0", BSLV_LP_REFACTOR="1"):      # (the tableau form ignores the variable)
+        e2 = LpEngine.from_model(_problem("main")["model"], pool_slots=2)
+        assert e2.get_refactor() == 0
+        e2.close()
+    with _env(BSLV_LP_REV="1", BSLV_LP_REFACTOR="1"):
+        e3 = LpEngine.from_model(_problem("main")["model"], pool_slots=2)
+        assert e3.get_refactor() == 1
+        e3.close()
+    eng.close()
+
+
+def test_switch_off_changes_nothing():
+    """the read-only entry points and a switch that stays off: the second generation is what it is without them, bit for bit"""
+    case = "main"
+    p = _problem(case)
+    ref = _reference(case)
+    eng, st, it = _first_generation(case, switch=0)
+    assert np.array_equal(it, ref["it"])
+    for s in p["dst"][:3]:
+        eng.get_inverse(s)
+    eng.last_refactor_stats()
+    assert eng.get_refactor() == 0
+    second, it2 = _second_generation(eng, case)
+    assert np.array_equal(it2, ref["it2"])
+    for k in ("obj", "w", "y"):
+        assert _same_bits(second[k], ref["second"][k]), k
+    assert eng.last_refactor_stats() == dict(refactorised=0, replay_pivots=0, rescued=0, failed=0)
+    eng.close()
+
+
+@pytest.mark.parametrize("case", ["main", "wide"])
+def test_rescue_of_an_lp_the_cross_check_gives_up(case):
+    """BSLV_LP_REV_DRIFT=b:p takes the cross-check of LP b as failed at its p-th pivot.  Switch off: the LP comes back UNDEFINED, as
+    it always did.  Switch on: its slot is refactorised and the LP solved again inside the call; every other LP is untouched."""
+    p = _problem(case)
+    model = p["model"]
+    ref = _reference(case)
+    cand = np.nonzero(ref["it"] >= 4)[0]
+    assert len(cand) > 0, ref["it"]
+    b = int(cand[0])
+    hook = "%d:%d" % (b, int(ref["it"][b]) // 2)
+    others = np.array([k for k in range(p["B"]) if k != b])
+    # hook on, switch off
+    eng, st, it = _first_generation(case, hook=hook)
+    assert st[b] == UNDEFINED and np.all(st[others] == OPTIMAL), st
+    got = _read(eng, model, p["dst"])
+    for k in ("obj", "w", "y"):
+        assert _same_bits(got[k][others], ref["first"][k][others]), k
+    assert eng.last_refactor_stats() == dict(refactorised=0, replay_pivots=0, rescued=0, failed=0)
+    eng.close()
+    # hook on, switch on
+    eng, st, it = _first_generation(case, hook=hook, switch=1)
+    assert eng.get_refactor() == 1
+    assert np.all(st == OPTIMAL), st
+    stats = eng.last_refactor_stats()
+    assert stats["refactorised"] == 1 and stats["rescued"] == 1 and stats["failed"] == 0, stats
+    assert np.array_equal(it[others], ref["it"][others])
+    assert eng.last_stats()["pivots"] == int(it.sum())
+    got = _read(eng, model, p["dst"])
+    _close(got, ref["first"], b=[b])
+    for k in ("obj", "w", "y"):
+        assert _same_bits(got[k][others], ref["first"][k][others]), k
+    # the rescued slot is a parent like any other
+    second, _ = _second_generation(eng, case)
+    _close(second, ref["second"])
+    eng.close()
+
+
+class _P1Model:
+    """P1(w) of the dual variant (tests/test_lp_rev_obj_gpu.py): rows [A 0; -P I], zero engine cost, w as the cost of the columns y"""
+
+    def __init__(self, prob):
+        m, n, q = prob["m"], prob["n"], prob["q"]
+        M, N = m + q, n + q
+        L = np.zeros((M, N))
+        L[:m, :n] = prob["A"]
+        L[m:, :n] = -prob["P"]
+        L[m:, n:] = np.eye(q)
+        rlo, rup = bounds_from_types(prob["rtype"], prob["rlb"], prob["rub"])
+        clo, cup = bounds_from_types(prob["ctype"], prob["clb"], prob["cub"])
+        self.lo = np.concatenate([rlo, np.zeros(q), clo, np.full(q, -np.inf)])
+        self.up = np.concatenate([rup, np.zeros(q), cup, np.full(q, np.inf)])
+        self.m, self.n, self.q, self.M, self.N, self.L = m, n, q, M, N, L
+        self.y_first = M + n
+
+
+def _obj_chain(model, W, hook=None, switch=None):
+    B = len(W)
+    with _env(BSLV_LP_REV="1", BSLV_LP_REFACTOR=None, BSLV_LP_REV_DRIFT=None):
+        eng = LpEngine(model.M, model.N, model.L, model.lo, model.up, np.zeros(model.N + 1), 0, 0, B + 2)
+        assert eng.lib.bslv_lpq_is_revised(eng.h) == 1
+        if switch is not None:
+            assert eng.set_refactor(switch) == 0
+        eng.reset_slot(0)
+        st, _ = eng.solve_batch([0], [0], np.zeros((1, 0)), np.zeros((1, 0)))
+        assert st[0] == OPTIMAL
+        st, _ = eng.solve_batch_obj([0], [0], model.y_first, np.full((1, model.q), 1.0 / model.q))
+        assert st[0] == OPTIMAL
+        dst = np.arange(1, B + 1, dtype=np.int32)
+        with _env(BSLV_LP_REV_DRIFT=hook):
+            st, it = eng.solve_batch_obj(np.zeros(B, np.int32), dst, model.y_first, W)
+    out = dict(st=st.copy(), it=it.copy(), obj=eng.obj(dst).copy(), y=eng.primal(dst, model.y_first, model.q).copy(),
+               u=eng.dual(dst, 0, model.m).copy(), stats=eng.last_refactor_stats())
+    eng.close()
+    return out
+
+
+def test_rescue_in_an_objective_batch():
+    """the same through solve_batch_obj: one batch of P1(w) LPs as the dual variant of Benson's algorithm builds them"""
+    m, n, q, seed = 40, 300, 3, 5
+    rng = np.random.default_rng(seed)
+    base = synth.covering_vlp(m, n, q, seed)
+    prob = _sparse_covering(m, n, q, seed)
+    mask = prob["P"] != 0
+    mask[rng.integers(q, size=n), np.arange(n)] = True      # (a column of P without a non-zero would make y = 0 optimal for every w >= 0)
+    model = _P1Model(dict(prob, P=base["P"] * mask))
+    B = 16
+    W = rng.uniform(0.1, 1.0, size=(B, q))
+    W /= W.sum(axis=1, keepdims=True)
+    ref = _obj_chain(model, W)
+    assert np.all(ref["st"] == OPTIMAL), ref["st"]
+    cand = np.nonzero(ref["it"] >= 4)[0]
+    assert len(cand) > 0, ref["it"]
+    b = int(cand[0])
+    hook = "%d:%d" % (b, int(ref["it"][b]) // 2)
+    others = np.array([k for k in range(B) if k != b])
+    off = _obj_chain(model, W, hook=hook)
+    assert off["st"][b] == UNDEFINED and np.all(off["st"][others] == OPTIMAL), off["st"]
+    on = _obj_chain(model, W, hook=hook, switch=1)
+    assert np.all(on["st"] == OPTIMAL), on["st"]
+    assert on["stats"]["refactorised"] == 1 and on["stats"]["rescued"] == 1 and on["stats"]["failed"] == 0, on["stats"]
+    np.testing.assert_allclose(on["obj"][b], ref["obj"][b], rtol=RTOL, atol=1e-9)
+    np.testing.assert_allclose(on["y"][b], ref["y"][b], rtol=0, atol=1e-7)
+    np.testing.assert_allclose(W[b] @ on["y"][b], on["obj"][b], rtol=RTOL, atol=1e-9)
+    for res in (off, on):
+        for k in ("obj", "y", "u"):
+            assert _same_bits(res[k][others], ref[k][others]), k
+
+
+# ---- end to end: the Benson driver and the command line with a rescue in every batch ----
+RESCUE_ENV = dict(BSLV_LP_REV="1", BSLV_LP_REFACTOR="1", BSLV_LP_REV_DRIFT="0:1")
+
+
+@pytest.mark.parametrize("alg", ["primal", "dual"])
+def test_benson_run_with_a_rescue_in_every_batch(alg):
+    """LP 0 of every batch is given up at its first pivot and rescued in the call: the images are those of the default run"""
+    import poly_harness as ph
+    from bensolve_amd.vlp import solve_primal
+    prob = synth.covering_vlp(30, 15, 3, 5)
+    with _env(BSLV_LP_REV=None, BSLV_LP_REFACTOR=None, BSLV_LP_REV_DRIFT=None):
+        a = solve_primal(prob, bounded=True, batch=32, eps_benson_phase2=1e-9, alg_phase2=alg)
+    with _env(**RESCUE_ENV):
+        b = solve_primal(prob, bounded=True, batch=32, eps_benson_phase2=1e-9, alg_phase2=alg)
+    assert a["status"] == b["status"] == "optimal", (a["message"], b["message"])
+    ph.assert_benson_results_agree(ph.canonical(b["dump"], decimals=6), ph.canonical(a["dump"], decimals=6))
+
+
+def _read_img(t, X):
+    X = X.copy()
+    for i in np.nonzero(t == 0)[0]:
+        X[i] /= np.abs(X[i]).max()
+    key = np.round(X, 6) + 0.0
+    o = np.lexsort([key[:, j] for j in range(X.shape[1] - 1, -1, -1)] + [1 - t])
+    return t[o], X[o]
+
+
+@pytest.mark.parametrize("alg", ["primal", "dual"])
+@pytest.mark.parametrize("ex", ["ex01", "ex05"])
+def test_cli_with_a_rescue_in_every_batch_matches_hybrid_goldens(tmp_path, ex, alg):
+    cli = os.path.join(ROOT, "bensolve_amd", "csrc", "bensolve_hip")
+    gold = np.load(os.path.join(ROOT, "tests", "golden", "hybrid.npz"))
+    base = os.path.join(tmp_path, ex)
+    r = subprocess.run([cli, os.path.join(ROOT, "tests", "golden", "ex", ex + ".vlp"), "-m", "2", "-B", "64", "-a", alg, "-o", base],
+                       capture_output=True, text=True, timeout=600, env=dict(os.environ, **RESCUE_ENV))
+    assert r.returncode == 0, r.stdout + r.stderr
+    for side in ("p", "d"):
+        a = np.array([[float(x) for x in l.split()] for l in open(base + "_img_%s.sol" % side).read().strip().splitlines()])
+        t, X = _read_img(a[:, 0].astype(int), a[:, 1:])
+        gt, gX = _read_img(gold["%s/%s_type" % (ex, side)], gold["%s/%s" % (ex, side)])
+        assert np.array_equal(t, gt), (ex, side, r.stdout)
+        np.testing.assert_allclose(X, gX, rtol=1e-9, atol=1e-9)
