@@ -122,6 +122,17 @@ class BensonEngine:
         check(self.lib.bslv_benson_pool_stats(self.h, out))
         return dict(zip(("free", "resident", "held", "pool"), list(out)))
 
+    def set_park(self, on):
+        """apply() parks the tableau passes of the slots it keeps (default) or makes them at once (bslv_benson_set_park)"""
+        self.lib.bslv_benson_set_park.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        check(self.lib.bslv_benson_set_park(self.h, int(bool(on))))
+
+    def park_stats(self):
+        out = (ctypes.c_long * 5)()
+        self.lib.bslv_benson_park_stats.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        check(self.lib.bslv_benson_park_stats(self.h, out))
+        return dict(zip(("parked", "for_child", "forced", "dropped", "live"), [int(v) for v in out]))
+
     def start(self):
         st = ctypes.c_int()
         check(self.lib.bslv_benson_start(self.h, ctypes.byref(st)))

@@ -49,6 +49,8 @@ struct bslv_benson {
     int batch_cap = 1 << 30;            // LPs per outer iteration and rank the pool of tableaux can serve
     // tableau slots: 0 = root (kept).  facet -> slot of the LP that produced the cut
     std::vector<int> free_slots;
+    std::vector<int> freed_slots;                     // slots that went back to free_slots and may hold a tableau pass the LP engine has parked (bslv_lpq_park): it is told before the next batch (bslv_lpq_drop_parked)
+    bool park = true;                                 // apply() parks the passes of the slots it keeps (bslv_benson_set_park; BSLV_LP_PARK=0: it makes them at once)
     std::deque<std::pair<int, int>> parents;          // (facet, slot) in creation order
     std::unordered_map<int, int> facet_slot;
     std::vector<int> facet_owner;                     // by facet id: rank that solved its LP (-1 unknown)
@@ -226,6 +228,7 @@ int bslv_benson_create_ex(bslv_benson **out, int m, int n, int q, const double *
             if (pol == 6 && a >= 0 && a <= 5) { h->fam_mode = a; if (b > 0) h->fam_batches = b; if (c4 >= 0) h->fam_cap = c4; }
         }
     }
+    if (const char *e = getenv("BSLV_LP_PARK")) h->park = atoi(e) != 0;      // (the LP engine reads it too)
     for (int s = pool_slots - 1; s >= 1; s--) h->free_slots.push_back(s);
     h->slot_src.assign((size_t)pool_slots * q, 0.0);
     h->slot_valid.assign(pool_slots, 0);
@@ -626,9 +629,9 @@ static int take_slot(bslv_benson *h)      // caller holds slot_mu
             h->parents.pop_front();
             // (-2, s): a slot that was evicted while it still served as a warm-start source of a batch (solve_local re-queues
             // it under this key); nothing refers to it any more, so it goes back to the free list unconditionally
-            if (pr.first == -2) { h->free_slots.push_back(pr.second); continue; }
+            if (pr.first == -2) { h->free_slots.push_back(pr.second); h->freed_slots.push_back(pr.second); continue; }
             auto it = h->facet_slot.find(pr.first);
-            if (it != h->facet_slot.end() && it->second == pr.second) { h->facet_slot.erase(it); h->free_slots.push_back(pr.second); }
+            if (it != h->facet_slot.end() && it->second == pr.second) { h->facet_slot.erase(it); h->free_slots.push_back(pr.second); h->freed_slots.push_back(pr.second); }
         }
         if (h->free_slots.empty()) return -1;
     }
@@ -723,9 +726,15 @@ int bslv_benson_solve_local_ctx(bslv_benson *h, int ctx, double *records, int *p
             vup[(size_t)k * r + j] = ub;
         }
     }
+    // evicted parents never start an LP again: the LP engine forgets the passes it has parked for them (not for one that still
+    // serves this batch as a source: it is back in the queue, see above)
+    std::vector<int> gone;
+    for (int s : h->freed_slots) if (!is_src[s]) gone.push_back(s);
+    h->freed_slots.clear();
     lk.unlock();
     std::vector<int> st(nl), it(nl);
     int rc;
+    if ((rc = bslv_lpq_drop_parked(h->lp, (int)gone.size(), gone.data()))) return rc;
     {   // lazy tableaux (bslv_lpq_set_lazy): the slots of this batch get their tableau only where apply() keeps them as parents.  Not in
         // the pipelined mode, where the next batch is solved before this one's cuts are known.  BSLV_LP_LAZY=0: every LP writes its tableau
         static const bool lazy_ok = !(getenv("BSLV_LP_LAZY") && atoi(getenv("BSLV_LP_LAZY")) == 0);
@@ -941,11 +950,12 @@ int bslv_benson_apply_ctx(bslv_benson *h, int ctx, int nrec, const double *recor
             handed_back++;
             if (ci.slot >= 0) keep_slots.push_back(ci.slot);
             h->deferred.push_back(bslv_benson::Deferred{std::vector<double>(&cuts[(size_t)c * q], &cuts[(size_t)(c + 1) * q]), ci.z, ci.owner, ci.slot, ci.front});
-        } else if (ci.slot >= 0) h->free_slots.push_back(ci.slot);
+        } else if (ci.slot >= 0) { h->free_slots.push_back(ci.slot); h->freed_slots.push_back(ci.slot); }      // (a cut handed back earlier holds a parked slot)
     }
     h->tot_deferred += handed_back;
-    // (lazy tableaux) the parents-to-be get their tableau now, the slots of every other LP of the batch never do
-    if ((rc = bslv_lpq_materialise(h->lp, (int)keep_slots.size(), keep_slots.data()))) return rc;
+    // (lazy tableaux) the parents-to-be keep what their tableau pass needs -- the LP engine makes it when one of them starts an LP
+    // (bslv_lpq_park; with the switch off they get their tableau now) --, the slots of every other LP of the batch never get theirs
+    if ((rc = h->park ? bslv_lpq_park(h->lp, (int)keep_slots.size(), keep_slots.data()) : bslv_lpq_materialise(h->lp, (int)keep_slots.size(), keep_slots.data()))) return rc;
     if ((rc = bslv_lpq_discard_pending(h->lp))) return rc;
     for (auto &kv : slot_of_src) h->free_slots.push_back(kv.second);    // confirmed vertices: tableau not needed again
     B.l_pos.clear(); B.l_slot.clear();
@@ -984,6 +994,18 @@ int bslv_benson_set_pipelined(bslv_benson *h, int on)
     if (!h) return BSLV_E_ARG;
     h->mark_at_collect = on ? 1 : 0;
     return 0;
+}
+// off: apply() gives the slots it keeps their tableau at once (bslv_lpq_materialise) instead of parking the pass (bslv_lpq_park)
+int bslv_benson_set_park(bslv_benson *h, int on)
+{
+    if (!h) return BSLV_E_ARG;
+    h->park = on != 0;
+    return bslv_lpq_set_park(h->lp, on);
+}
+int bslv_benson_park_stats(const bslv_benson *h, long out[5])
+{
+    if (!h || !out) return BSLV_E_ARG;
+    return bslv_lpq_park_stats(h->lp, out);
 }
 int bslv_benson_set_policy(bslv_benson *h, int policy)
 {

@@ -1859,6 +1859,35 @@ __global__ void k_after_flush(BatchView Bv, int it)
     Bv.flushed[b] = 1;
     if (Bv.mode[b] == MODE_REFRESH) { Bv.verified[b] |= 1; Bv.mode[b] = MODE_NONE; }
 }
+// parked passes (bslv_lpq_park): what the pass of LP pairs[2k] of the batch needs goes to record pairs[2k+1] of the store -- its
+// counters, the descriptors, pivot rows and multiplier columns of its pending pivots, its reduced-cost row.  One workgroup per LP.
+__global__ __launch_bounds__(NT) void k_park_copy(LpView L, BatchView Bv, BatchView Pv, const int *pairs, int n)
+{
+    if ((int)blockIdx.x >= n) return;
+    const int b = pairs[2 * blockIdx.x], rec = pairs[2 * blockIdx.x + 1];
+    const int np = Bv.npend[b];
+    if (threadIdx.x == 0) {
+        Pv.npend[rec] = np; Pv.flushed[rec] = Bv.flushed[b]; Pv.mode[rec] = Bv.mode[b]; Pv.verified[rec] = Bv.verified[b];
+        const_cast<int *>(Pv.src)[rec] = Bv.src[b]; const_cast<int *>(Pv.dst)[rec] = Bv.dst[b];
+    }
+    if ((int)threadIdx.x < np) Pv.desc[(size_t)rec * KP + threadIdx.x] = Bv.desc[(size_t)b * KP + threadIdx.x];
+    const int ld2 = L.ldt >> 1, mp2 = L.Mp1p >> 1, d2 = L.ld >> 1;
+    const double2 *pr = reinterpret_cast<const double2 *>(Bv.prow + (size_t)b * KP * L.ldt), *pc = reinterpret_cast<const double2 *>(Bv.pcol + (size_t)b * KP * L.Mp1p);
+    const double2 *dc = reinterpret_cast<const double2 *>(Bv.dcur + (size_t)b * L.ld);
+    double2 *qr = reinterpret_cast<double2 *>(Pv.prow + (size_t)rec * KP * L.ldt), *qc = reinterpret_cast<double2 *>(Pv.pcol + (size_t)rec * KP * L.Mp1p);
+    double2 *qd = reinterpret_cast<double2 *>(Pv.dcur + (size_t)rec * L.ld);
+    for (int k = threadIdx.x; k < np * ld2; k += NT) qr[k] = pr[k];
+    for (int k = threadIdx.x; k < np * mp2; k += NT) qc[k] = pc[k];
+    for (int k = threadIdx.x; k < d2; k += NT) qd[k] = dc[k];
+}
+// k_store_d for the LPs list[0..n) of a view (the records of an unpark pass)
+__global__ void k_store_d_list(LpView L, BatchView Bv, const int *list, int n)
+{
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if ((int)blockIdx.y >= n || j >= L.ld) return;
+    const int b = list[blockIdx.y];
+    L.T[(size_t)Bv.dst[b] * L.slotT + (size_t)L.M * L.ld + j] = Bv.dcur[(size_t)b * L.ld + j];
+}
 
 // ---- k_flush: the HBM-bound kernel.  Persistent grid over (LP of the work list x row tile).  Every row of the stored
 //      tableau (the parent's slot on the first pass of a solve) is read once, the pending pivots are applied to it in order
@@ -2157,7 +2186,26 @@ struct bslv_lpq {
     std::vector<int> last_dst;                     // dst slots of the last batch (host copy)
     int *list_d = nullptr; int listcap = 0;
     long lazy_skipped = 0, lazy_materialised = 0;  // LPs whose pass was skipped / asked for afterwards (totals)
-    double lazy_ms = 0;                            // host wall clock spent in bslv_lpq_materialise (total)
+    double lazy_ms = 0;                            // host wall clock spent in bslv_lpq_materialise and bslv_lpq_park (total)
+    std::vector<int> park_src, last_npend;         // src and npend of the last batch as the solve left them (host copies, lazy with park on), behind npend ...
+    size_t last_flushed_at = 0;                    // ... from this index on: flushed
+    // PARKED passes (bslv_lpq_park): see the comment above park_alloc
+    struct Park {
+        bool on = true, failed = false;            // the switch (bslv_lpq_set_park, BSLV_LP_PARK); the store could not be allocated: park() materialises
+        int cap = 0;                               // records of the store (one per pool slot), 0: not allocated yet
+        int *src = nullptr, *dst = nullptr, *npend = nullptr, *flushed = nullptr, *mode = nullptr, *ver = nullptr, *work = nullptr, *nwork = nullptr;
+        PivDesc *desc = nullptr; double *prow = nullptr, *pcol = nullptr, *dcur = nullptr;
+        int *pairs_d = nullptr, *pairs_h = nullptr;      // (batch index, record) of a park call (device / pinned)
+        int *list_d = nullptr, *list_h = nullptr;        // records of an unpark pass (device / pinned)
+        std::vector<int> free_recs, live, pos_in_live;   // free records; records in use, and where each of them stands in `live`
+        std::vector<int> rec_of_slot;                    // slot -> its record, or -1
+        std::vector<int> slot_of, src_of, flushed_of;    // per record: its slot, the slot its pass reads when flushed_of is 0
+        std::vector<char> mark, listed;                  // scratch per slot / per record (zero between calls)
+        bool list_inflight = false, pairs_inflight = false;      // the pinned lists may still be read by a copy on the stream (cleared where a batch has waited for it)
+        long stats[4] = {0, 0, 0, 0};                    // parked, unparked for a child, unparked because their source was about to be overwritten, dropped unused
+        long pre_passes = 0, pre_launches = 0;           // unpark passes since the last batch: they count in the statistics of the batch they precede
+        std::vector<std::pair<hipEvent_t, hipEvent_t>> pre_ev;      // ... and their events (set_profile)
+    } park;
     double *trow_d = nullptr, *uvec_d = nullptr, *xfull_d = nullptr;
     int *hmail_d = nullptr; int launch_seq = 0;      // revised form: mailboxes of k_select's helper workgroups; launches so far
     long nnzA = 0;
@@ -2231,6 +2279,9 @@ struct bslv_lpq {
 };
 
 static int materialise_indices(bslv_lpq *h, const int *list, int n);
+static void park_release(bslv_lpq *h, int rec);
+static int park_before(bslv_lpq *h, int nuse, const int *use, int nover, const int *over);
+static void park_free(bslv_lpq *h);
 static int ensure_batch(bslv_lpq *h, int B)
 {
     if (B <= h->Bcap) return 0;
@@ -2240,7 +2291,7 @@ static int ensure_batch(bslv_lpq *h, int B)
     // see nullptr for what is gone instead of freeing it a second time
     auto fr = [](auto *&p) { if (p) (void)hipFree(p); p = nullptr; };
     fr(h->src_d); fr(h->dst_d); fr(h->status_d); fr(h->iters_d); fr(h->mode_d); fr(h->ver_d); fr(h->active_d); fr(h->work_d); fr(h->qslot_d); fr(h->init_d);
-    fr(h->vlo_d); fr(h->vup_d); fr(h->prow_d); fr(h->desc_d); fr(h->npend_d); fr(h->flushed_d); fr(h->pcol_d); fr(h->dcur_d); fr(h->dper_d); fr(h->pflags_d); fr(h->stall_d);
+    fr(h->vlo_d); fr(h->vup_d); fr(h->prow_d); fr(h->desc_d); fr(h->npend_d); h->flushed_d = nullptr; fr(h->pcol_d); fr(h->dcur_d); fr(h->dper_d); fr(h->pflags_d); fr(h->stall_d);
     fr(h->trow_d); fr(h->uvec_d); fr(h->xfull_d); fr(h->hmail_d); fr(h->rmark_d);
     if (h->status_h) { (void)hipHostFree(h->status_h); h->status_h = nullptr; }
     if (h->active_h) { (void)hipHostFree(h->active_h); h->active_h = nullptr; }
@@ -2273,8 +2324,8 @@ static int ensure_batch(bslv_lpq *h, int B)
     HIP_TRY(malloc0(&h->stall_d, cap * sizeof(int)));
     if (!h->xstat_d) HIP_TRY(malloc0(&h->xstat_d, 8 * sizeof(int)));
     if (!h->dbg_d) HIP_TRY(malloc0(&h->dbg_d, 16 * sizeof(unsigned long long)));
-    HIP_TRY(malloc0(&h->npend_d, cap * sizeof(int)));
-    HIP_TRY(malloc0(&h->flushed_d, cap * sizeof(int)));
+    HIP_TRY(malloc0(&h->npend_d, (size_t)2 * cap * sizeof(int)));      // (npend and flushed in one piece: bslv_lpq_park's copy of both is one readback)
+    h->flushed_d = h->npend_d + cap;
     HIP_TRY(hipHostMalloc(&h->status_h, cap * sizeof(int)));
     HIP_TRY(malloc0(&h->active_d, cap * sizeof(int)));
     HIP_TRY(hipHostMalloc(&h->active_h, cap * sizeof(int)));
@@ -2462,6 +2513,8 @@ static int raw_create(bslv_lpq **out, int M, int N, const double *A, const doubl
     // BSLV_LP_REFACTOR=1: the in-call rescue of bslv_lpq_set_refactor, for an engine in the revised form (the tableau form has no inverse to rebuild)
     L.rfx = 0; L.drift_b = -1; L.drift_p = -1;
     if (const char *e = getenv("BSLV_LP_REFACTOR")) { if (rev) h->refactor_on = atoi(e) != 0; }
+    // BSLV_LP_PARK=0: bslv_lpq_park makes the passes at once, as bslv_lpq_materialise does (bslv_lpq_set_park)
+    if (const char *e = getenv("BSLV_LP_PARK")) h->park.on = atoi(e) != 0;
     *out = h;
     return 0;
 }
@@ -2469,13 +2522,14 @@ static int raw_create(bslv_lpq **out, int M, int N, const double *A, const doubl
 void bslv_lpq_destroy(bslv_lpq *h)
 {
     if (!h) return;
+    park_free(h);
     auto fr = [](void *p) { if (p) (void)hipFree(p); };
     fr(h->L.T); fr(h->L.beta); fr(h->L.xN); fr(h->L.bh); fr(h->L.nh); fr(h->L.nstat); fr(h->L.pos);
     fr(h->Tstd); fr(h->lb_d); fr(h->ub_d); fr(h->art_d);
     fr(h->dbg_d); fr(h->list_d); fr(h->cptr_d); fr(h->cidx_d); fr(h->rptr_d); fr(h->ridx_d); fr(h->cval_d); fr(h->rval_d); fr(h->cost_d); fr(h->dsl_d); fr(h->trow_d); fr(h->uvec_d); fr(h->xfull_d); fr(h->hmail_d);
     fr(h->src_d); fr(h->dst_d); fr(h->status_d); fr(h->iters_d); fr(h->mode_d); fr(h->ver_d); fr(h->qslot_d); fr(h->init_d);
     fr(h->tdir_d); fr(h->tg_d); fr(h->tstate_d); fr(h->titers_d); fr(h->tstat_d); fr(h->rmark_d); fr(h->rfx_i_d); fr(h->rfx_c_d);
-    fr(h->vlo_d); fr(h->vup_d); fr(h->prow_d); fr(h->desc_d); fr(h->out_d); fr(h->active_d); fr(h->work_d); fr(h->nwork_d); fr(h->npend_d); fr(h->flushed_d); fr(h->pcol_d); fr(h->dcur_d); fr(h->dper_d); fr(h->pflags_d); fr(h->stall_d); fr(h->xstat_d); fr(h->cvals_d);
+    fr(h->vlo_d); fr(h->vup_d); fr(h->prow_d); fr(h->desc_d); fr(h->out_d); fr(h->active_d); fr(h->work_d); fr(h->nwork_d); fr(h->npend_d); fr(h->pcol_d); fr(h->dcur_d); fr(h->dper_d); fr(h->pflags_d); fr(h->stall_d); fr(h->xstat_d); fr(h->cvals_d);
     if (h->status_h) (void)hipHostFree(h->status_h);
     if (h->active_h) (void)hipHostFree(h->active_h);
     if (h->init_h) (void)hipHostFree(h->init_h);
@@ -2594,6 +2648,7 @@ int bslv_lpq_reset_slot(bslv_lpq *h, int slot)
 {
     if (!h || slot < 0 || slot >= h->slots) { set_error("bslv_lpq_reset_slot: bad slot %d", slot); return BSLV_E_ARG; }
     if (h->lazy_open) { const int rc = materialise_indices(h, nullptr, 0); if (rc) return rc; h->lazy_open = false; }      // (a pending pass must not land on the slot after it has been reset)
+    { const int rc = park_before(h, 0, nullptr, 1, &slot); if (rc) return rc; }      // (nor may a parked pass read it afterwards)
     LpView &L = h->L;
     if (L.rev) {
         const size_t nk = std::max((size_t)L.M * L.ldt, (size_t)L.ld);
@@ -2614,12 +2669,12 @@ int bslv_lpq_reset_slot(bslv_lpq *h, int slot)
 // an LP that is finished when its pass would be due keeps its pending pivots (<= KP; one that needs more passes as before), and the
 // caller names the slots it will use as parents: bslv_lpq_materialise(h, n, slots) gives those their tableau -- the same pass, the
 // same arithmetic -- and bslv_lpq_discard_pending(h) drops the rest.  A batch that is started while slots are still open gives all
-// of them their tableau first (the retry batches of the driver).  Slots that were not materialised must not be used as `src`.
-static int flush_list(bslv_lpq *h, int cnt_slot, int upper, bool account = true)      // (account: the pass counts in the statistics of the lazy tableaux and of the last batch)
+// of them their tableau first (the retry batches of the driver).  Slots that were neither materialised nor parked (below) must not be used as `src`.
+// one pass over the work list of counter slot cnt_slot of a view (at most `upper` LPs); ev: events around k_flush (set_profile), or nullptr
+static int flush_launch(bslv_lpq *h, const BatchView &bv, int cnt_slot, int upper, std::pair<hipEvent_t, hipEvent_t> *ev)
 {
     LpView &L = h->L;
     hipStream_t s = h->stream;
-    BatchView bv = bview(h);
     const int wide = (size_t)KP * L.ldt * sizeof(double) > h->flush_lds_max;
     const size_t lds = wide ? 0 : (size_t)KP * L.ldt * sizeof(double);
     const bool big_flush = getenv("BSLV_FLUSH_NT") ? atoi(getenv("BSLV_FLUSH_NT")) > NT : lds > 53 * 1024;
@@ -2627,18 +2682,25 @@ static int flush_list(bslv_lpq *h, int cnt_slot, int upper, bool account = true)
     int tr = upper * tiles >= 2048 ? 32 : (upper * tiles * 2 >= 2048 ? 16 : (upper * tiles * 4 >= 2048 ? 8 : 4));
     if (big_flush) { const long rows = (long)upper * L.mrows; tr = rows >= 2048L * 128 ? 128 : rows >= 2048L * 64 ? 64 : rows >= 2048L * 32 ? 32 : 16; }
     const int ntile = (L.mrows + tr - 1) / tr, fnt = big_flush ? NT_BIG : NT;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (h->profile) { HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1)); HIP_TRY(hipEventRecord(e0, s)); }
+    if (ev) { HIP_TRY(hipEventCreate(&ev->first)); HIP_TRY(hipEventCreate(&ev->second)); HIP_TRY(hipEventRecord(ev->first, s)); }
     if (wide) hipLaunchKernelGGL(k_flush<true>, dim3(std::min(upper * ntile, h->upd_grid)), dim3(fnt), 0, s, L, bv, cnt_slot, ntile, tr);
     else hipLaunchKernelGGL(k_flush<false>, dim3(std::min(upper * ntile, h->upd_grid)), dim3(fnt), lds, s, L, bv, cnt_slot, ntile, tr);
-    if (h->profile) HIP_TRY(hipEventRecord(e1, s));
+    if (ev) HIP_TRY(hipEventRecord(ev->second, s));
     hipLaunchKernelGGL(k_after_flush, dim3((upper + 255) / 256), dim3(256), 0, s, bv, cnt_slot);
     HIP_TRY(hipGetLastError());
+    return 0;
+}
+static int flush_list(bslv_lpq *h, int cnt_slot, int upper, bool account = true)      // (account: the pass counts in the statistics of the lazy tableaux and of the last batch)
+{
+    hipStream_t s = h->stream;
+    std::pair<hipEvent_t, hipEvent_t> ev{nullptr, nullptr};
+    const int rc = flush_launch(h, bview(h), cnt_slot, upper, h->profile ? &ev : nullptr);
+    if (rc) return rc;
     int n = 0;
     HIP_TRY(hipMemcpyAsync(&n, h->nwork_d + cnt_slot, sizeof(int), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     if (account) { h->last_passes += n; h->last_launches += 1; h->lazy_materialised += n; }
-    if (h->profile) { float t = 0; (void)hipEventElapsedTime(&t, e0, e1); h->last_update_ms += t; (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); }
+    if (h->profile) { float t = 0; (void)hipEventElapsedTime(&t, ev.first, ev.second); h->last_update_ms += t; (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
     return 0;
 }
 // batch indices list[0..n) of the last batch (nullptr: all of it): their slots get their tableau
@@ -2663,6 +2725,111 @@ static int materialise_indices(bslv_lpq *h, const int *list, int n)
     // with pivots pending that was ALREADY the final row (k_store_d at the end of the solve), now updated twice; the vector is the truth
     hipLaunchKernelGGL(k_store_d, dim3((h->L.ld + 255) / 256, B), dim3(256), 0, s, h->L, bv, B);
     HIP_TRY(hipGetLastError());
+    // (a slot of this batch that was parked has its tableau now: its record must not make the pass a second time)
+    if (h->park.cap) for (int k = 0; k < n; k++) { const int r = h->park.rec_of_slot[h->last_dst[list[k]]]; if (r >= 0) { park_release(h, r); h->park.stats[3]++; } }
+    return 0;
+}
+// ---- parked passes -----------------------------------------------------------------------------------------------------------
+// bslv_lpq_materialise gives every slot the driver keeps its tableau at once, because any of them MAY become a parent; most never do
+// (a batch takes the children of a few of them, the pool evicts the others first).  bslv_lpq_park(h, n, slots) postpones the pass
+// instead: what it needs -- npend, flushed, src, dst, the descriptors, pivot rows and multiplier columns of the pending pivots, the
+// reduced-cost row -- is copied to a record of a store beside the pool (k_park_copy, ~2 % of the pool's bytes), shaped like the batch
+// arrays, so that k_flush and k_after_flush run on a BatchView that points into the store.  The pass is made (unparked: park_pass,
+// the same arithmetic on the same inputs) when a batch names the slot as `src`, and, for a record that has not passed before and so
+// still reads its parent's slot, before that slot is overwritten; a record whose own slot is overwritten or that the caller gives
+// up (bslv_lpq_drop_parked) is dropped without a pass.  The host knows what is parked (rec_of_slot and, per record, slot, source and
+// flushed): no readback, no host wait.  Tableau form only; the revised form and an engine whose store does not fit materialise.
+static void park_free(bslv_lpq *h)
+{
+    bslv_lpq::Park &P = h->park;
+    auto fr = [](auto *&p) { if (p) (void)hipFree(p); p = nullptr; };
+    fr(P.src); fr(P.dst); fr(P.npend); fr(P.flushed); fr(P.mode); fr(P.ver); fr(P.work); fr(P.nwork); fr(P.desc); fr(P.prow); fr(P.pcol); fr(P.dcur); fr(P.pairs_d); fr(P.list_d);
+    if (P.pairs_h) (void)hipHostFree(P.pairs_h);
+    if (P.list_h) (void)hipHostFree(P.list_h);
+    P.pairs_h = P.list_h = nullptr;
+    for (auto &e : P.pre_ev) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
+    P.pre_ev.clear();
+    P.cap = 0;
+}
+static bool park_alloc(bslv_lpq *h)
+{
+    bslv_lpq::Park &P = h->park;
+    if (P.cap) return true;
+    if (P.failed) return false;
+    const LpView &L = h->L;
+    const size_t n = (size_t)h->slots;
+    hipStream_t s = h->stream;
+    const bool ok = malloc0s(&P.src, n * sizeof(int), s) == hipSuccess && malloc0s(&P.dst, n * sizeof(int), s) == hipSuccess && malloc0s(&P.npend, n * sizeof(int), s) == hipSuccess &&
+                    malloc0s(&P.flushed, n * sizeof(int), s) == hipSuccess && malloc0s(&P.mode, n * sizeof(int), s) == hipSuccess && malloc0s(&P.ver, n * sizeof(int), s) == hipSuccess &&
+                    malloc0s(&P.work, n * sizeof(int), s) == hipSuccess && malloc0s(&P.nwork, sizeof(int), s) == hipSuccess && malloc0s(&P.pairs_d, 2 * n * sizeof(int), s) == hipSuccess &&
+                    malloc0s(&P.list_d, n * sizeof(int), s) == hipSuccess && malloc0s(&P.desc, n * KP * sizeof(PivDesc), s) == hipSuccess && malloc0s(&P.dcur, n * L.ld * sizeof(double), s) == hipSuccess &&
+                    malloc0s(&P.prow, n * KP * L.ldt * sizeof(double), s) == hipSuccess && malloc0s(&P.pcol, n * KP * L.Mp1p * sizeof(double), s) == hipSuccess &&
+                    hipHostMalloc(&P.pairs_h, 2 * n * sizeof(int)) == hipSuccess && hipHostMalloc(&P.list_h, n * sizeof(int)) == hipSuccess;
+    if (!ok) { (void)hipGetLastError(); park_free(h); P.failed = true; return false; }      // (park() materialises from now on)
+    P.cap = (int)n;
+    P.free_recs.resize(n); for (size_t k = 0; k < n; k++) P.free_recs[k] = (int)(n - 1 - k);
+    P.live.clear(); P.pos_in_live.assign(n, -1); P.rec_of_slot.assign(n, -1);
+    P.slot_of.assign(n, -1); P.src_of.assign(n, -1); P.flushed_of.assign(n, 0);
+    P.mark.assign(n, 0); P.listed.assign(n, 0);
+    return true;
+}
+static void park_release(bslv_lpq *h, int rec)
+{
+    bslv_lpq::Park &P = h->park;
+    const int at = P.pos_in_live[rec], last = P.live.back();
+    P.live[at] = last; P.pos_in_live[last] = at; P.live.pop_back(); P.pos_in_live[rec] = -1;
+    P.rec_of_slot[P.slot_of[rec]] = -1; P.slot_of[rec] = -1;
+    P.free_recs.push_back(rec);
+}
+static BatchView park_view(bslv_lpq *h)
+{
+    const bslv_lpq::Park &P = h->park;
+    BatchView v = bview(h);
+    v.src = P.src; v.dst = P.dst; v.npend = P.npend; v.flushed = P.flushed; v.mode = P.mode; v.verified = P.ver; v.work = P.work; v.nwork = P.nwork;
+    v.desc = P.desc; v.prow = P.prow; v.pcol = P.pcol; v.dcur = P.dcur;
+    return v;
+}
+// The pass of the records recs[0..n) (distinct, live), then they are free: one k_flush launch, row M again from the record's reduced
+// costs (as materialise_indices does).  No host wait: the pass counts in the statistics of the batch that follows (pre_*).
+static int park_pass(bslv_lpq *h, const int *recs, int n)
+{
+    if (n == 0) return 0;
+    bslv_lpq::Park &P = h->park;
+    hipStream_t s = h->stream;
+    const BatchView pv = park_view(h);
+    if (P.list_inflight) HIP_TRY(hipStreamSynchronize(s));      // (the pinned list of the last pass may not have been read yet: only where two passes follow each other without a batch between them)
+    P.list_inflight = true;
+    memcpy(P.list_h, recs, (size_t)n * sizeof(int));
+    HIP_TRY(hipMemcpyAsync(P.list_d, P.list_h, (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(P.nwork, 0, sizeof(int), s));
+    hipLaunchKernelGGL(k_list_given, dim3((n + 255) / 256), dim3(256), 0, s, pv, (const int *)P.list_d, n, 0);
+    std::pair<hipEvent_t, hipEvent_t> ev{nullptr, nullptr};
+    const int rc = flush_launch(h, pv, 0, n, h->profile ? &ev : nullptr);
+    if (rc) return rc;
+    if (h->profile) P.pre_ev.push_back(ev);
+    hipLaunchKernelGGL(k_store_d_list, dim3((h->L.ld + 255) / 256, n), dim3(256), 0, s, h->L, pv, (const int *)P.list_d, n);
+    HIP_TRY(hipGetLastError());
+    P.pre_passes += n; P.pre_launches += 1; h->lazy_materialised += n;      // (every record needs its pass: that is why it was parked)
+    for (int k = 0; k < n; k++) park_release(h, recs[k]);
+    return 0;
+}
+// Before the slots over[0..nover) are overwritten and the slots use[0..nuse) are read as parents: the records of `use` make their
+// pass, so do the records that have not passed before and read one of `over`; then the records of `over` themselves are dropped.
+static int park_before(bslv_lpq *h, int nuse, const int *use, int nover, const int *over)
+{
+    bslv_lpq::Park &P = h->park;
+    if (!P.cap || P.live.empty()) return 0;
+    std::vector<int> recs;
+    for (int k = 0; k < nuse; k++) { const int r = P.rec_of_slot[use[k]]; if (r >= 0 && !P.listed[r]) { P.listed[r] = 1; recs.push_back(r); } }
+    const size_t for_child = recs.size();
+    for (int k = 0; k < nover; k++) P.mark[over[k]] = 1;
+    for (int r : P.live) if (!P.listed[r] && !P.flushed_of[r] && P.mark[P.src_of[r]] && !P.mark[P.slot_of[r]]) { P.listed[r] = 1; recs.push_back(r); }
+    for (int k = 0; k < nover; k++) P.mark[over[k]] = 0;
+    for (int r : recs) P.listed[r] = 0;
+    P.stats[1] += (long)for_child; P.stats[2] += (long)(recs.size() - for_child);
+    const int rc = park_pass(h, recs.data(), (int)recs.size());
+    if (rc) return rc;
+    for (int k = 0; k < nover; k++) { const int r = P.rec_of_slot[over[k]]; if (r >= 0) { park_release(h, r); P.stats[3]++; } }
     return 0;
 }
 // Which kernel starts the LPs of a batch (beta = T_parent x_N, row M): k_init_grouped where it has an instance -- rows of at most
@@ -2795,6 +2962,8 @@ static int ensure_tie(bslv_lpq *h)
     h->tie_Bcap = h->Bcap;
     return 0;
 }
+// host wall clock of the calls an apply() makes for its tableaux (bslv_lpq_materialise, bslv_lpq_park): lazy_stats[2]
+struct LazyClock { bslv_lpq *h; std::chrono::steady_clock::time_point t; ~LazyClock() { h->lazy_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); } };
 int bslv_lpq_set_lazy(bslv_lpq *h, int on)
 {
     if (!h) return BSLV_E_ARG;
@@ -2805,17 +2974,90 @@ int bslv_lpq_set_lazy(bslv_lpq *h, int on)
 int bslv_lpq_materialise(bslv_lpq *h, int n, const int *slots)
 {
     if (!h || n < 0 || (n && !slots)) { set_error("bslv_lpq_materialise: bad argument"); return BSLV_E_ARG; }
-    if (!h->lazy_open || n == 0) return 0;
-    std::vector<int> idx;
-    const auto t0 = std::chrono::steady_clock::now();
-    struct Clock { bslv_lpq *h; std::chrono::steady_clock::time_point t; ~Clock() { h->lazy_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); } } clock{h, t0};
+    if (n == 0 || (!h->lazy_open && h->park.live.empty())) return 0;
+    std::vector<int> idx, parked;
+    LazyClock clock{h, std::chrono::steady_clock::now()};
     {
         std::vector<int> where(h->slots, -1);
-        for (size_t b = 0; b < h->last_dst.size(); b++) where[h->last_dst[b]] = (int)b;
-        for (int k = 0; k < n; k++) if (slots[k] >= 0 && slots[k] < h->slots && where[slots[k]] >= 0) idx.push_back(where[slots[k]]);      // (slots of earlier batches have theirs)
+        if (h->lazy_open) for (size_t b = 0; b < h->last_dst.size(); b++) where[h->last_dst[b]] = (int)b;
+        for (int k = 0; k < n; k++) {
+            if (slots[k] < 0 || slots[k] >= h->slots) continue;
+            if (where[slots[k]] >= 0) idx.push_back(where[slots[k]]);      // (a slot of the open batch, parked or not: materialise_indices)
+            else if (h->park.cap && h->park.rec_of_slot[slots[k]] >= 0) parked.push_back(slots[k]);      // (parked by an earlier batch; the other slots of earlier batches have their tableau)
+        }
+    }
+    if (!parked.empty()) {
+        const int rc = park_before(h, (int)parked.size(), parked.data(), 0, nullptr);
+        if (rc) return rc;
+        HIP_TRY(hipStreamSynchronize(h->stream));
     }
     return materialise_indices(h, idx.data(), (int)idx.size());
 }
+int bslv_lpq_park(bslv_lpq *h, int n, const int *slots)
+{
+    if (!h || n < 0 || (n && !slots)) { set_error("bslv_lpq_park: bad argument"); return BSLV_E_ARG; }
+    if (!h->lazy_open || n == 0) return 0;
+    if (!h->park.on || h->L.rev || h->last_npend.size() != h->last_flushed_at + h->last_dst.size() || !park_alloc(h)) return bslv_lpq_materialise(h, n, slots);
+    bslv_lpq::Park &P = h->park;
+    LazyClock clock{h, std::chrono::steady_clock::now()};
+    hipStream_t s = h->stream;
+    if (P.pairs_inflight) HIP_TRY(hipStreamSynchronize(s));      // (a second park call for one batch: the pinned list of the first may not have been read yet)
+    std::vector<int> where(h->slots, -1);
+    for (size_t b = 0; b < h->last_dst.size(); b++) where[h->last_dst[b]] = (int)b;
+    const int *npend = h->last_npend.data(), *flushed = npend + h->last_flushed_at;
+    int m = 0;
+    for (int k = 0; k < n; k++) {
+        if (slots[k] < 0 || slots[k] >= h->slots || where[slots[k]] < 0 || P.rec_of_slot[slots[k]] >= 0) continue;
+        const int b = where[slots[k]];
+        if (!(npend[b] > 0 || !flushed[b])) continue;      // (k_list_given's condition: this slot has its tableau)
+        const int rec = P.free_recs.back();
+        P.free_recs.pop_back();
+        P.rec_of_slot[slots[k]] = rec; P.slot_of[rec] = slots[k]; P.src_of[rec] = h->park_src[b]; P.flushed_of[rec] = flushed[b];
+        P.pos_in_live[rec] = (int)P.live.size(); P.live.push_back(rec);
+        P.pairs_h[2 * m] = b; P.pairs_h[2 * m + 1] = rec; m++;
+    }
+    if (m == 0) return 0;
+    P.pairs_inflight = true;
+    HIP_TRY(hipMemcpyAsync(P.pairs_d, P.pairs_h, (size_t)2 * m * sizeof(int), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_park_copy, dim3(m), dim3(NT), 0, s, h->L, bview(h), park_view(h), (const int *)P.pairs_d, m);
+    HIP_TRY(hipGetLastError());
+    P.stats[0] += m;
+    return 0;
+}
+int bslv_lpq_drop_parked(bslv_lpq *h, int n, const int *slots)
+{
+    if (!h || n < 0 || (n && !slots)) { set_error("bslv_lpq_drop_parked: bad argument"); return BSLV_E_ARG; }
+    bslv_lpq::Park &P = h->park;
+    if (!P.cap) return 0;
+    for (int k = 0; k < n; k++) {
+        if (slots[k] < 0 || slots[k] >= h->slots) continue;
+        const int r = P.rec_of_slot[slots[k]];
+        if (r >= 0) { park_release(h, r); P.stats[3]++; }
+    }
+    return 0;
+}
+int bslv_lpq_park_stats(const bslv_lpq *h, long out[5])
+{
+    if (!h || !out) return BSLV_E_ARG;
+    for (int k = 0; k < 4; k++) out[k] = h->park.stats[k];
+    out[4] = (long)h->park.live.size();
+    return 0;
+}
+int bslv_lpq_set_park(bslv_lpq *h, int on)
+{
+    if (!h) return BSLV_E_ARG;
+    bslv_lpq::Park &P = h->park;
+    if (!on && !P.live.empty()) {      // what is parked gets its tableau now, as if it had never been parked
+        const std::vector<int> recs(P.live);
+        P.stats[1] += (long)recs.size();
+        const int rc = park_pass(h, recs.data(), (int)recs.size());
+        if (rc) return rc;
+        HIP_TRY(hipStreamSynchronize(h->stream));
+    }
+    P.on = on != 0;
+    return 0;
+}
+int bslv_lpq_get_park(const bslv_lpq *h) { return h && h->park.on; }
 int bslv_lpq_discard_pending(bslv_lpq *h)
 {
     if (!h) return BSLV_E_ARG;
@@ -2883,6 +3125,9 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
         h->lazy_open = false;
     }
     if ((rc = ensure_batch(h, B))) return rc;
+    // parked passes: the parents of this batch get their tableau, and so does whoever still reads a slot this batch overwrites
+    // (before k_prep: the pass reads and writes slots the batch touches)
+    if ((rc = park_before(h, B, src, B, dst))) return rc;
     LpView &L = h->L;
     const int wide = (size_t)KP * L.ldt * sizeof(double) > h->flush_lds_max;      // pivot rows from global memory in k_flush
     auto t0 = std::chrono::steady_clock::now();
@@ -3061,7 +3306,14 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
         hipLaunchKernelGGL(k_store_d, dim3((L.ld + 255) / 256, B), dim3(256), 0, s, L, bv, B);
         HIP_TRY(hipGetLastError());
         h->last_dst.assign(dst, dst + B);
+        h->park_src.assign(src, src + B);
         h->lazy_open = true;
+        h->last_npend.clear();
+        if (h->park.on) {      // which LPs still need a pass, and whether it reads their parent's slot: bslv_lpq_park decides on the host
+            h->last_flushed_at = (size_t)h->Bcap;
+            h->last_npend.resize(h->last_flushed_at + B);
+            HIP_TRY(hipMemcpy(h->last_npend.data(), h->npend_d, h->last_npend.size() * sizeof(int), hipMemcpyDeviceToHost));
+        }
         h->lazy_skipped += B - std::min<long>(B, h->last_passes);
     } else {   // tableaux of the solves that made no pivot
         const int cnt_slot = L.maxit + 40;
@@ -3081,12 +3333,21 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
     }
     h->last_iters = it + tie_rounds;
     h->last_launches = it + tie_rounds;
+    {   // the unpark passes made since the last batch count with this one (they ran on the stream before its first kernel)
+        bslv_lpq::Park &P = h->park;
+        h->last_passes += P.pre_passes; h->last_launches += P.pre_launches;
+        P.pre_passes = 0; P.pre_launches = 0;
+        P.list_inflight = false; P.pairs_inflight = false;      // (the readbacks above have waited for the stream)
+    }
     { int xs[8]; HIP_TRY(hipMemcpy(xs, h->xstat_d, sizeof xs, hipMemcpyDeviceToHost)); for (int k = 0; k < 5; k++) h->last_ext[k] = xs[k]; for (int k = 0; k < 3; k++) h->last_p1[k] = xs[5 + k]; }
     if (h->profile) {
         double ms = 0;
         for (size_t e = 0; e < nev; e++) { float t = 0; (void)hipEventElapsedTime(&t, h->evpool[e].first, h->evpool[e].second); ms += t; }
+        for (auto &e : h->park.pre_ev) { float t = 0; (void)hipEventElapsedTime(&t, e.first, e.second); ms += t; }
         h->last_update_ms = ms;
     }
+    for (auto &e : h->park.pre_ev) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
+    h->park.pre_ev.clear();
     h->last_total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     if (L.probe & 8) {
         unsigned long long dg[16];
@@ -3100,6 +3361,7 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
     {
         static const bool tm = getenv("BSLV_LP_TIMING") != nullptr;
         if (tm) fprintf(stderr, "lp solve_batch: %s form %d x %d, B %d, %d lock-step rounds, %ld pivots, %ld passes, %.1f ms; %d parents, largest family %d, %s\n", L.rev ? "revised" : "tableau", L.M, L.N, B, it, h->last_pivots, h->last_passes, h->last_total_ms, h->last_init_parents, h->last_init_family, h->last_init_chunks ? "k_init_grouped" : "k_init");
+        if (tm && h->park.cap) fprintf(stderr, "lp park (totals): %ld parked, %ld unparked for a child, %ld because their source was about to be overwritten, %ld dropped unused, %zu live\n", h->park.stats[0], h->park.stats[1], h->park.stats[2], h->park.stats[3], h->park.live.size());
     }
     return 0;
 }

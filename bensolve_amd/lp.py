@@ -130,6 +130,27 @@ class LpEngine:
         check(self.lib.bslv_lpq_lazy_stats(self.h, o))
         return dict(skipped=int(o[0]), on_request=int(o[1]), ms=o[2] / 1000.0)
 
+    def park(self, slots):
+        """in place of materialise: the slots keep what their tableau pass needs, the engine makes it when they are used (bslv_lpq_park)"""
+        slots = np.ascontiguousarray(slots, np.int32)
+        self.lib.bslv_lpq_park.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+        check(self.lib.bslv_lpq_park(self.h, len(slots), slots.ctypes.data))
+
+    def drop_parked(self, slots):
+        slots = np.ascontiguousarray(slots, np.int32)
+        self.lib.bslv_lpq_drop_parked.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+        check(self.lib.bslv_lpq_drop_parked(self.h, len(slots), slots.ctypes.data))
+
+    def set_park(self, on):
+        self.lib.bslv_lpq_set_park.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        check(self.lib.bslv_lpq_set_park(self.h, int(bool(on))))
+
+    def park_stats(self):
+        o = (ctypes.c_long * 5)()
+        self.lib.bslv_lpq_park_stats.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        check(self.lib.bslv_lpq_park_stats(self.h, o))
+        return dict(zip(("parked", "for_child", "forced", "dropped", "live"), [int(v) for v in o]))
+
     def set_bounds(self, lo, up):
         lo = np.ascontiguousarray(lo, np.float64)
         up = np.ascontiguousarray(up, np.float64)

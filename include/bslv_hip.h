@@ -120,12 +120,29 @@ size_t bslv_lpq_slot_bytes(const bslv_lpq *h);
  * pass would be due keeps its pending pivots; values, duals and objective are served from its vectors as always.  The caller then
  * names the slots it will start later LPs from: bslv_lpq_materialise gives those their tableau (the same pass), and
  * bslv_lpq_discard_pending drops the rest.  A slot that was not materialised must not be passed as `src`.  A solve_batch that finds
- * slots still open materialises all of them first.  bslv_lpq_lazy_stats: [0] LP passes skipped, [1] passes made on request, [2] host
- * microseconds spent in bslv_lpq_materialise (totals). */
+ * slots still open materialises all of them first.  bslv_lpq_lazy_stats: [0] LP passes skipped, [1] passes made on request
+ * (those of parked slots included, when they are made), [2] host microseconds spent in bslv_lpq_materialise and bslv_lpq_park (totals).
+ * PARKED PASSES.  Most slots a caller keeps never become a parent after all.  bslv_lpq_park(h, n, slots) takes the place of
+ * bslv_lpq_materialise for slots that MAY be used as `src` later: what the pass of such a slot needs (its pending pivots and its
+ * reduced-cost row, ~2 % of a slot) is copied to a store beside the pool, without a pass and without a host wait, and the slot may
+ * be used like a materialised one.  The engine makes the pass by itself -- same arithmetic, same result bit for bit -- at the start
+ * of the solve_batch / solve_batch_obj that names the slot as `src`, in bslv_lpq_materialise, and, where the pass still reads the
+ * slot's own parent, before that parent is overwritten (as `dst` of a batch, by bslv_lpq_reset_slot).  A parked slot that is itself
+ * overwritten loses its record; bslv_lpq_drop_parked tells the engine which slots the caller will never read again.  The getters
+ * answer for a parked slot what they answer after bslv_lpq_materialise.  The pass of a parked slot counts in lazy_stats[1] and in
+ * the statistics of the batch it precedes (bslv_lpq_last_passes / _last_launches, update_ms).  bslv_lpq_set_park(h, 0) (or
+ * BSLV_LP_PARK=0 at create) makes bslv_lpq_park materialise at once, as it does in the revised form and where the store does not
+ * fit; switching off gives every parked slot its tableau.  bslv_lpq_park_stats: [0] slots parked, [1] passes made for a child (or
+ * on request), [2] passes made because the parent was about to be overwritten, [3] records dropped unused, [4] records live now. */
 int  bslv_lpq_set_lazy(bslv_lpq *h, int on);
 int  bslv_lpq_materialise(bslv_lpq *h, int n, const int *slots);
 int  bslv_lpq_discard_pending(bslv_lpq *h);
 int  bslv_lpq_lazy_stats(const bslv_lpq *h, long out[3]);
+int  bslv_lpq_park(bslv_lpq *h, int n, const int *slots);
+int  bslv_lpq_drop_parked(bslv_lpq *h, int n, const int *slots);
+int  bslv_lpq_park_stats(const bslv_lpq *h, long out[5]);
+int  bslv_lpq_set_park(bslv_lpq *h, int on);
+int  bslv_lpq_get_park(const bslv_lpq *h);
 /* replace the shared bounds (lp_set_rows / lp_set_cols, bslv_lp.c:112-134) */
 int  bslv_lpq_set_bounds(bslv_lpq *h, const double *lb, const double *ub);
 /* put the standard basis (all aux basic; glp_std_basis, bslv_lp.c:101,225) into a slot */
@@ -158,7 +175,8 @@ int  bslv_lpq_last_stats(const bslv_lpq *h, int *lockstep_iters, long *pivots, d
  * update_ms = time in k_flush (HIP events, with set_profile).  Tableau passes of the last batch, i.e. how many (LP, round)
  * pairs k_flush read and wrote: */
 long bslv_lpq_last_passes(const bslv_lpq *h);
-/* k_flush launches behind those passes: one per lock-step round, plus one per bslv_lpq_materialise that had something to do
+/* k_flush launches behind those passes: one per lock-step round, plus one per bslv_lpq_materialise that had something to do and
+ * one per pass over parked slots made since the batch before
  * (what a kernel trace counts; update_ms / this = the average launch) */
 long bslv_lpq_last_launches(const bslv_lpq *h);
 /* extended selection of the last solve_batch (LPs with boxed variables): out[0] iterations in which boxed columns switched
@@ -398,6 +416,11 @@ int  bslv_benson_collect_given(bslv_benson *h, int n, const int *idx, const doub
 int  bslv_benson_last_local(bslv_benson *h, int max_out, int *src, int *pivots, int *gen);
 /* tableau pool: out[0] free slots, [1] resident warm-start sources, [2] held by a batch in flight, [3] pool size */
 int  bslv_benson_pool_stats(bslv_benson *h, long out[4]);
+/* apply() parks the tableau passes of the slots it keeps (bslv_lpq_park) and tells the LP engine which parked slots the pool has
+ * evicted (bslv_lpq_drop_parked); set_park(h, 0), or BSLV_LP_PARK=0 at create, makes the passes at the end of apply() instead
+ * (bslv_lpq_materialise).  Same LPs, same cuts, same slots either way.  park_stats: as bslv_lpq_park_stats. */
+int  bslv_benson_set_park(bslv_benson *h, int on);
+int  bslv_benson_park_stats(const bslv_benson *h, long out[5]);
 int  bslv_benson_totals(const bslv_benson *h, long *lps, long *cuts, long *pivots);
 /* warm starts: LPs whose parent's tableau was not resident on this rank (evicted, or solved on another rank) and that started
  * from the root tableau / from the resident tableau whose own vertex is nearest */
