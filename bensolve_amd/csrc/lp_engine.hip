@@ -3560,6 +3560,35 @@ int bslv_lpq_debug_perturb_inverse(bslv_lpq *h, int slot, double rel)
     HIP_TRY(hipStreamSynchronize(h->stream));
     return 0;
 }
+// test support: another basis in the heads of a slot, for bslv_lpq_refactor to build (or to refuse).  A host-side edit of the slot's
+// small arrays: the matrix, the reduced costs and the basic values stay what they were and belong to the old basis.
+int bslv_lpq_debug_swap_heads(bslv_lpq *h, int slot, int r, int q)
+{
+    if (!h) { set_error("bslv_lpq_debug_swap_heads: no engine"); return BSLV_E_ARG; }
+    if (!h->L.rev) { set_error("bslv_lpq_debug_swap_heads: the engine is in the tableau form, whose heads cannot change without their tableau"); return BSLV_E_ARG; }
+    const LpView &L = h->L;
+    if (slot < 0 || slot >= h->slots) { set_error("bslv_lpq_debug_swap_heads: bad slot %d", slot); return BSLV_E_ARG; }
+    if (r < 0 || r >= L.M || q < 0 || q >= L.N) { set_error("bslv_lpq_debug_swap_heads: row %d of %d, position %d of %d", r, L.M, q, L.N); return BSLV_E_ARG; }
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    int *bh = L.bh + (size_t)slot * L.M + r, *nh = L.nh + (size_t)slot * L.N + q, *pos = L.pos + (size_t)slot * (L.M + L.N);
+    int leave = -1, enter = -1;
+    HIP_TRY(hipMemcpy(&leave, bh, sizeof(int), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&enter, nh, sizeof(int), hipMemcpyDeviceToHost));
+    if (leave < 0 || leave >= L.M + L.N || enter < 0 || enter >= L.M + L.N) { set_error("bslv_lpq_debug_swap_heads: slot %d holds no basis", slot); return BSLV_E_ARG; }
+    double lo = 0.0, up = 0.0;              // the model's own bounds (the artificial ones included): a per-LP range gets its bounds with the next solve
+    HIP_TRY(hipMemcpy(&lo, h->lb_d + leave, sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&up, h->ub_d + leave, sizeof(double), hipMemcpyDeviceToHost));
+    const int st = lo == up ? NS_S : (std::isinf(lo) && std::isinf(up)) ? NS_F : std::isinf(lo) ? NS_U : NS_L;
+    const double x = st == NS_F ? 0.0 : (st == NS_U ? up : lo);
+    const int prow = r, pnb = -1 - q;
+    HIP_TRY(hipMemcpy(bh, &enter, sizeof(int), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(nh, &leave, sizeof(int), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(pos + enter, &prow, sizeof(int), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(pos + leave, &pnb, sizeof(int), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(L.nstat + (size_t)slot * L.N + q, &st, sizeof(int), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(L.xN + (size_t)slot * L.ld + q, &x, sizeof(double), hipMemcpyHostToDevice));
+    return 0;
+}
 
 static int ensure_out(bslv_lpq *h, size_t n)
 {

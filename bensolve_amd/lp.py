@@ -280,6 +280,12 @@ class LpEngine:
         self.lib.bslv_lpq_debug_perturb_inverse.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_double]
         check(self.lib.bslv_lpq_debug_perturb_inverse(self.h, int(slot), float(rel)))
 
+    def debug_swap_heads(self, slot, r, q):
+        """tests only: the basic variable of row r and the nonbasic variable at position q of a slot change places in its heads; the
+        stored matrix stays the old basis' until refactor (bslv_lpq_debug_swap_heads)"""
+        self.lib.bslv_lpq_debug_swap_heads.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int]
+        check(self.lib.bslv_lpq_debug_swap_heads(self.h, int(slot), int(r), int(q)))
+
     def last_stats(self):
         it = ctypes.c_int()
         piv = ctypes.c_long()

@@ -109,9 +109,13 @@ int  bslv_lpq_last_refactor_stats(const bslv_lpq *h, long out[4]);
  * of the engine's own model (M = rows given minus bslv_lpq_rows_folded).  bslv_lpq_debug_perturb_inverse multiplies entry (i, c) of
  * the stored matrix by 1 + rel (1 + hash01(i M + c)): a deterministic stand-in for drift, for tests only.  BSLV_LP_REV_DRIFT=b:p
  * (test hook, read per solve call, off by default): the pivot cross-check of LP b of the batch is taken as failed at the LP's p-th
- * pivot (p >= 1), once per call and not again in the in-call rescue; nothing else changes. */
+ * pivot (p >= 1), once per call and not again in the in-call rescue; nothing else changes.  bslv_lpq_debug_swap_heads, for tests only:
+ * the basic variable of row r and the nonbasic variable at position q (0 .. N-1 of the slot's nonbasic list; position j of a reset slot
+ * holds structural j) change places in the heads of the slot; the variable that leaves gets the nonbasic status and value of its
+ * bounds in the model.  The stored matrix is not touched and belongs to the old basis until bslv_lpq_refactor rebuilds it. */
 int  bslv_lpq_get_inverse(bslv_lpq *h, int slot, int *heads /* M */, double *X /* M x M row-major, may be NULL */);
 int  bslv_lpq_debug_perturb_inverse(bslv_lpq *h, int slot, double rel);
+int  bslv_lpq_debug_swap_heads(bslv_lpq *h, int slot, int r, int q);
 int  bslv_lpq_pool_slots(const bslv_lpq *h);
 size_t bslv_lpq_slot_bytes(const bslv_lpq *h);
 /* LAZY TABLEAUX.  The first pass of a solve writes the LP's tableau into its own slot -- the largest memory item of a batch, and

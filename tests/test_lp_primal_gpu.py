@@ -21,7 +21,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-from bensolve_amd.lp import LpEngine, bounds_from_types
+from bensolve_amd.lp import LpEngine
+from lp_cases import random_lp, highs, oracle_primal, check_optimality_conditions
 
 pytestmark = pytest.mark.gpu
 
@@ -35,86 +36,11 @@ E_ARG = 2
 NONE = np.zeros((1, 0))
 
 
-# ---- the LPs -------------------------------------------------------------------------------------------------------------
-def _bounds(types, lb, ub):
-    lo, up = bounds_from_types(np.array(list(types)), lb, ub)
-    return lo, up
-
-
-def random_lp(M, N, rng, kind):
-    """(A, lo, up, cost) of one LP: lo / up over the M row variables then the N columns, cost[0] the constant shift."""
-    A = np.round(rng.normal(size=(M, N)) * 3) / 2
-    A[rng.random((M, N)) < 0.4] = 0.0
-    for i in range(M):                      # no empty row
-        if not A[i].any():
-            A[i, rng.integers(N)] = 1.0
-    x0 = np.round(rng.normal(size=N) * 2)
-    tr = rng.choice(list("fluds"), size=M, p=[.1, .3, .3, .2, .1])
-    tc = rng.choice(list("fluds"), size=N, p=[.15, .4, .1, .25, .1])
-    cost = np.concatenate([[float(rng.integers(-2, 3))], np.round(rng.normal(size=N) * 3)])
-    if kind == "wild":                      # bounds that know nothing of each other: feasible, infeasible or unbounded as it comes
-        rl = np.round(rng.normal(size=M) * 2)
-        cl = np.round(rng.normal(size=N) * 2)
-        ru, cu = rl + rng.integers(0, 4, size=M), cl + rng.integers(0, 4, size=N)
-    else:                                   # feasible: x0 lies within all of them
-        if kind == "unbounded":
-            A[:, 0] = 0.0
-            for i in range(M):
-                if not A[i].any():
-                    A[i, 1 + rng.integers(N - 1)] = 1.0
-        r0 = A @ x0
-        rl, cl = r0 - rng.integers(0, 3, size=M), x0 - rng.integers(0, 3, size=N)
-        ru, cu = r0 + rng.integers(0, 3, size=M), x0 + rng.integers(0, 3, size=N)
-        rl, cl = np.where(tr == "s", r0, rl), np.where(tc == "s", x0, cl)
-        ru, cu = np.where((tr == "d") & (ru == rl), rl + 1, ru), np.where((tc == "d") & (cu == cl), cl + 1, cu)
-    if kind == "feasible" and rng.random() < 0.7:      # most of them bounded as well: no cost pulls a column where it has no bound
-        c = cost[1:]
-        c[:] = np.where(tc == "f", 0.0, np.where(tc == "l", np.abs(c), np.where(tc == "u", -np.abs(c), c)))
-    rlo, rup = _bounds(tr, rl, ru)
-    clo, cup = _bounds(tc, cl, cu)
-    if kind == "unbounded":                 # a free column with a cost and no row
-        clo[0], cup[0], cost[1] = -np.inf, np.inf, 1.0
-    if kind == "infeasible":                # two rows that contradict each other
-        A[1] = A[0]
-        rlo[0], rup[0] = 5.0, np.inf
-        rlo[1], rup[1] = -np.inf, 4.0
-    return A, np.concatenate([rlo, clo]), np.concatenate([rup, cup]), cost
-
-
+# ---- the LPs (random_lp and the yardsticks: tests/lp_cases.py) ----------------------------------------------------------
 def lp_set(M, N):
     rng = np.random.default_rng(SEEDS[(M, N)])
     kinds = ["infeasible", "unbounded"] + ["wild" if t % 5 == 4 else "feasible" for t in range(2, NLP)]
     return [random_lp(M, N, rng, k) for k in kinds]
-
-
-def highs(A, lo, up, cost):
-    """(status in the engine's numbering, optimal value) from scipy's HiGHS"""
-    from scipy.optimize import linprog
-    M, N = A.shape
-    Aub, bub, Aeq, beq = [], [], [], []
-    for i in range(M):
-        if lo[i] == up[i]:
-            Aeq.append(A[i]); beq.append(lo[i])
-        else:
-            if np.isfinite(up[i]): Aub.append(A[i]); bub.append(up[i])
-            if np.isfinite(lo[i]): Aub.append(-A[i]); bub.append(-lo[i])
-    kw = dict(A_ub=np.array(Aub) if Aub else None, b_ub=bub if Aub else None, A_eq=np.array(Aeq) if Aeq else None, b_eq=beq if Aeq else None,
-              bounds=[(None if np.isinf(l) else l, None if np.isinf(u) else u) for l, u in zip(lo[M:], up[M:])])
-    res = linprog(cost[1:], method="highs", **kw)
-    if res.status != 0:                     # HiGHS' presolve reports 'infeasible' for 'infeasible or unbounded'
-        res = linprog(cost[1:], method="highs", options={"presolve": False}, **kw)
-    st = {0: OPTIMAL, 2: INFEASIBLE, 3: UNBOUNDED}.get(res.status, UNDEFINED)
-    return st, (res.fun + cost[0]) if st == OPTIMAL else None
-
-
-def oracle_primal(A, lo, up, cost):
-    """the oracle's primal method from the standard basis: (status, optimal value)"""
-    import oracle_api
-    olp = oracle_api.OracleLP(A, lo, up, cost)
-    st = olp.solve(0)
-    z = olp.obj() if st == OPTIMAL else None
-    olp.close()
-    return st, z
 
 
 _REF = {}
@@ -145,21 +71,6 @@ def cold_solve(A, lo, up, cost, method, details=False):
         out["dual"] = eng.dual([0], 0, M + N)[0]
     eng.close()
     return out
-
-
-def check_optimality_conditions(A, lo, up, cost, z, prim, dual, tag):
-    """of the model as given (tests/test_lp_gpu.py test_presolve_keeps_the_model_of_the_caller_primal_and_dual): r = A x within the
-    bounds, d = c - A' lambda, every non-zero dual on a bound of the matching sign"""
-    M, N = A.shape
-    x, r, lam, d = prim[M:], prim[:M], dual[:M], dual[M:]
-    np.testing.assert_allclose(r, A @ x, atol=1e-9, err_msg=str(tag))
-    np.testing.assert_allclose(z, cost[0] + cost[1:] @ x, atol=1e-9, err_msg=str(tag))
-    np.testing.assert_allclose(d, cost[1:] - A.T @ lam, atol=1e-8, err_msg=str(tag))
-    assert np.all(prim >= lo - 1e-8) and np.all(prim <= up + 1e-8), tag
-    for k in range(M + N):
-        if abs(dual[k]) > 1e-9:
-            at_lo, at_up = abs(prim[k] - lo[k]) < 1e-7, abs(prim[k] - up[k]) < 1e-7
-            assert (dual[k] > 0 and at_lo) or (dual[k] < 0 and at_up) or (at_lo and at_up), (tag, k, dual[k], prim[k], lo[k], up[k])
 
 
 # ---- 1. cold start under PRIMAL --------------------------------------------------------------------------------------------

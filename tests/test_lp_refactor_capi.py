@@ -5,7 +5,7 @@ import re
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ["bslv_lpq_refactor", "bslv_lpq_set_refactor", "bslv_lpq_get_refactor", "bslv_lpq_last_refactor_stats",
-       "bslv_lpq_get_inverse", "bslv_lpq_debug_perturb_inverse"]
+       "bslv_lpq_get_inverse", "bslv_lpq_debug_perturb_inverse", "bslv_lpq_debug_swap_heads"]
 
 
 def test_refactor_symbols_exported():
@@ -28,7 +28,7 @@ def test_refactor_symbols_declared():
 
 def test_python_mirror_has_the_methods():
     from bensolve_amd.lp import LpEngine
-    for name in ("refactor", "set_refactor", "get_refactor", "last_refactor_stats", "get_inverse", "debug_perturb_inverse"):
+    for name in ("refactor", "set_refactor", "get_refactor", "last_refactor_stats", "get_inverse", "debug_perturb_inverse", "debug_swap_heads"):
         assert callable(getattr(LpEngine, name)), name
 
 
@@ -43,9 +43,11 @@ def test_entry_points_refuse_a_missing_engine():
     lib.bslv_lpq_get_inverse.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
     lib.bslv_lpq_debug_perturb_inverse.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_double]
     lib.bslv_lpq_last_refactor_stats.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+    lib.bslv_lpq_debug_swap_heads.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int]
     assert lib.bslv_lpq_refactor(None, 0, None, None) == 2          # BSLV_E_ARG
     assert lib.bslv_lpq_set_refactor(None, 1) == 2
     assert lib.bslv_lpq_get_refactor(None) == 0
     assert lib.bslv_lpq_get_inverse(None, 0, None, None) == 2
     assert lib.bslv_lpq_debug_perturb_inverse(None, 0, 1e-6) == 2
     assert lib.bslv_lpq_last_refactor_stats(None, None) == 2
+    assert lib.bslv_lpq_debug_swap_heads(None, 0, 0, 0) == 2

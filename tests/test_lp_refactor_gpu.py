@@ -340,6 +340,159 @@ def test_rescue_of_an_lp_the_cross_check_gives_up(case):
     eng.close()
 
 
+# ---- other heads than a solve leaves: bslv_lpq_debug_swap_heads ----
+def _heads(eng, slot):
+    return eng.get_inverse(slot, matrix=False)[0]
+
+
+def test_refactor_of_a_basis_no_solve_produced():
+    """swap_heads puts another basis into the heads of a slot -- of a solved slot, three exchanges that numpy finds well conditioned;
+    of a reset slot, five structurals on rows where they have an entry -- and refactor builds its inverse: against numpy's inverse of
+    K[:, heads], at the bound of test_rebuilt_inverse_against_the_host"""
+    case = "main"
+    p = _problem(case)
+    model, M, N = p["model"], p["model"].M, p["model"].N
+    eng, st, _ = _first_generation(case)
+    assert np.all(st == OPTIMAL), st
+    # a solved slot: exchange row r with nonbasic position q, keep the exchange if the basis stays well conditioned, else undo it
+    slot, kept = int(p["dst"][0]), 0
+    h0 = _heads(eng, slot)
+    for r, q in zip(range(3, M, 5), range(1, N, 7)):
+        before = _heads(eng, slot)
+        eng.debug_swap_heads(slot, r, q)
+        h = _heads(eng, slot)
+        assert np.array_equal(np.delete(h, r), np.delete(before, r)) and h[r] not in before
+        if np.linalg.cond(_basis(p, h)) < 1e6:
+            kept += 1
+        else:
+            eng.debug_swap_heads(slot, r, q)              # (position q holds the variable that left: the same exchange undoes it)
+            assert np.array_equal(_heads(eng, slot), before)
+        if kept == 3:
+            break
+    assert kept == 3
+    # a reset slot: position j holds structural j
+    fresh = 2 * p["B"] + 1
+    eng.reset_slot(fresh)
+    rows, cols = [], []
+    for j in range(0, N, 11):
+        i = next((int(i) for i in np.nonzero(model.L[:, j])[0] if i not in rows), None)
+        if i is not None and np.linalg.cond(model.L[np.ix_(rows + [i], cols + [j])]) < 1e4:
+            rows.append(i); cols.append(j)
+        if len(rows) == 5:
+            break
+    assert len(rows) == 5
+    for i, j in zip(rows, cols):
+        eng.debug_swap_heads(fresh, i, j)
+    hf = _heads(eng, fresh)
+    assert all(hf[i] == M + j for i, j in zip(rows, cols)) and len(set(hf.tolist())) == M
+    assert list(eng.refactor([slot, fresh])) == [0, 0]
+    stats = eng.last_refactor_stats()
+    assert stats["refactorised"] == 2 and stats["failed"] == 0
+    for s_ in (slot, fresh):
+        h1, X1 = eng.get_inverse(s_)
+        assert set(h1.tolist()) == set(_heads(eng, s_).tolist()) and (s_ != slot or set(h1.tolist()) != set(h0.tolist()))
+        rho_ref, res = _rho_ref(p, h1), _residual(p, h1, X1)
+        print("lp_refactor_residual swapped heads M %d N %d slot %d structural_basics %d rho_ref %.3e rebuilt %.3e" % (M, N, s_, int((h1 >= M).sum()), rho_ref, res))
+        assert res <= _bound(rho_ref), (s_, res, rho_ref)
+    eng.close()
+
+
+def _singular_swap(model):
+    """(row i, column j) with L[i][j] = 0: auxiliary i out and structural j in makes the standard basis K[:, heads] singular"""
+    i = 2
+    j = int(np.nonzero(model.L[i] == 0)[0][0])
+    return i, j
+
+
+def test_refactor_of_a_singular_basis_resets_the_slot():
+    """the failure path: UNDEFINED, counted as failed, the slot as after reset_slot -- and a solve from it is a cold solve"""
+    case = "main"
+    p = _problem(case)
+    ref = _reference(case)
+    model, M = p["model"], p["model"].M
+    eng, st, _ = _first_generation(case)
+    fresh = 2 * p["B"] + 1
+    eng.reset_slot(fresh)
+    i, j = _singular_swap(model)
+    eng.debug_swap_heads(fresh, i, j)
+    h = _heads(eng, fresh)
+    assert h[i] == M + j and np.linalg.matrix_rank(_basis(p, h)) == M - 1
+    assert list(eng.refactor([fresh])) == [UNDEFINED]
+    assert eng.last_refactor_stats() == dict(refactorised=0, replay_pivots=0, rescued=0, failed=1)
+    h, X = eng.get_inverse(fresh)
+    assert np.array_equal(h, np.arange(M)) and _same_bits(X, np.eye(M))
+    other = fresh + 1
+    eng.reset_slot(other)
+    n = M + model.N
+    assert _same_bits(eng.primal([fresh], 0, n), eng.primal([other], 0, n)) and _same_bits(eng.dual([fresh], 0, n), eng.dual([other], 0, n))
+    st1, it1 = eng.solve_batch([fresh], [fresh], np.full((1, model.r), -np.inf), p["ub"][:1])
+    assert st1[0] == OPTIMAL and it1[0] > 0, (st1, it1)
+    _close(_read(eng, model, [fresh]), ref["first"], b=[0])
+    eng.close()
+
+
+def test_a_singular_slot_beside_healthy_ones():
+    """one singular slot between two healthy ones in one call: it keeps going through the rounds beside them and leaves no trace in
+    their matrices"""
+    case = "main"
+    p = _problem(case)
+    model, M = p["model"], p["model"].M
+    eng, st, _ = _first_generation(case)
+    good = [int(p["dst"][0]), int(p["dst"][1])]
+    assert all(int((_heads(eng, s_) >= M).sum()) > KP_STEPS for s_ in good)      # (several rounds, so the failed slot is passed over more than once)
+    assert list(eng.refactor(good)) == [0, 0]
+    without = [eng.get_inverse(s_) for s_ in good]
+    bad = 2 * p["B"] + 1
+    eng.reset_slot(bad)
+    eng.debug_swap_heads(bad, *_singular_swap(model))
+    assert list(eng.refactor([good[0], bad, good[1]])) == [0, UNDEFINED, 0]
+    stats = eng.last_refactor_stats()
+    assert stats["refactorised"] == 2 and stats["failed"] == 1, stats
+    for s_, (h0, X0) in zip(good, without):
+        h1, X1 = eng.get_inverse(s_)
+        assert np.array_equal(h1, h0) and _same_bits(X1, X0), s_
+    assert np.array_equal(_heads(eng, bad), np.arange(M))
+    eng.close()
+
+
+KP_STEPS = 6         # replay steps between two passes of a refactorisation (KP of lp_engine.hip)
+
+
+def test_refactor_with_the_1024_thread_selection():
+    """M = 1536: k_rfx_select runs with 1024 threads from there ("snt = M >= 1536 ? NT_BIG : NT").  A sparse covering model of that
+    height; its cold solve takes far longer than a test may, so 40 structurals are put on rows where they have an entry with
+    swap_heads, and the one rebuild is checked against numpy at the bound of test_rebuilt_inverse_against_the_host."""
+    q = 3
+    m, n = 1536 - 2 * q - 1, 1600
+    model = P2Model(_sparse_covering(m, n, q, 21))
+    M, N = model.M, model.N
+    assert M == 1536
+    p = dict(K=np.hstack([np.eye(M), -model.L]))
+    rng = np.random.default_rng(21)
+    rows, cols = [], []
+    for j in rng.permutation(N):
+        i = next((int(i) for i in np.nonzero(model.L[:, j])[0] if i not in rows), None)
+        if i is not None and np.linalg.cond(model.L[np.ix_(rows + [i], cols + [int(j)])]) < 1e4:
+            rows.append(i); cols.append(int(j))
+        if len(rows) == 40:
+            break
+    assert len(rows) == 40
+    with _env(BSLV_LP_REV="1", BSLV_LP_REFACTOR=None, BSLV_LP_REV_DRIFT=None, BSLV_NO_PRESOLVE="1"):      # (rows with one entry stay rows: K as given)
+        eng = LpEngine.from_model(model, pool_slots=2)
+    assert eng.rows_folded() == 0 and eng.lib.bslv_lpq_is_revised(eng.h) == 1
+    eng.reset_slot(0)
+    for i, j in zip(rows, cols):
+        eng.debug_swap_heads(0, i, j)
+    assert list(eng.refactor([0])) == [0]
+    assert eng.last_refactor_stats() == dict(refactorised=1, replay_pivots=40, rescued=0, failed=0)
+    h, X = eng.get_inverse(0)
+    assert set(h.tolist()) == (set(range(M)) - set(rows)) | {M + j for j in cols}
+    rho_ref, res = _rho_ref(p, h), _residual(p, h, X)
+    print("lp_refactor_residual M %d N %d structural_basics 40 rho_ref %.3e rebuilt %.3e" % (M, N, rho_ref, res))
+    assert res <= _bound(rho_ref), (res, rho_ref)
+    eng.close()
+
+
 class _P1Model:
     """P1(w) of the dual variant (tests/test_lp_rev_obj_gpu.py): rows [A 0; -P I], zero engine cost, w as the cost of the columns y"""
 
