@@ -2168,6 +2168,128 @@ __global__ void k_rfx_perturb(LpView L, int slot, double rel)
     L.T[(size_t)slot * L.slotT + (size_t)i * L.ldt + c] *= 1.0 + rel * (1.0 + hash01(i * L.M + c));
 }
 
+// ---- the AGE of a slot's matrix, and the PERIODIC refactorisation (bslv_lpq_set_refactor_period) ----
+// age[slot]: rank-1 steps applied to the slot's B^-1 since it was last built from the identity.  A solve carries, per LP of its batch,
+// age0[b] = (age of the matrix the LP stands on when it was last built or inherited) - (the LP's pivots at that moment), so that the age
+// of the LP's matrix is age0[b] + iters[b] wherever nothing is pending: k_age_begin takes it from the parent, a refactorisation inside
+// the solve sets it to -iters[b] (k_per_resume), k_age_end leaves the sum in the LP's own slot.  Maintained in every solve of the revised
+// form, period or not; the default kernels do not know about it.  (iters[] is what the selection counts: a primal step in which the entering
+// variable only switches bound counts as well, although no step is applied -- the age never underestimates.)
+__global__ void k_age_begin(BatchView Bv, const long long *age, long long *age0, int B)
+{
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b < B) age0[b] = age[Bv.src[b]];
+}
+__global__ void k_age_end(BatchView Bv, long long *age, const long long *age0, int B)
+{
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b < B) age[Bv.dst[b]] = age0[b] + Bv.iters[b];
+}
+__global__ void k_age_zero(const int *slots, int n, long long *age)
+{
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k < n) age[slots[k]] = 0;
+}
+// The LPs of the active list that are DUE: running, nothing pending, age >= K -- in the order of the list (ONE workgroup, a scan: the
+// replay index of an LP is a function of the batch).  stat[0] = their number; stat[1] = the largest age met so far among the LPs of the
+// list that a selection saw or will see at that age (at the start of a call the due ones and the ones k_prep refused are left out: no
+// selection is made on them as they stand).  Called where the host reads the status vector, after the pass of the round.
+__global__ __launch_bounds__(NT) void k_per_due(BatchView Bv, const int *active, int nact, const long long *age0, long long K, int at_start, int *due, long long *stat)
+{
+    __shared__ int s_cnt[NT];
+    __shared__ long long s_max[NT];
+    const int tid = threadIdx.x;
+    const int chunk = (nact + NT - 1) / NT, k0 = min(nact, tid * chunk), k1 = min(nact, k0 + chunk);
+    int c = 0;
+    long long mx = 0;
+    for (int k = k0; k < k1; k++) {
+        const int b = active[k];
+        const long long a = age0[b] + Bv.iters[b];
+        const bool run = Bv.status[b] == ST_RUNNING, is_due = run && Bv.npend[b] == 0 && a >= K;
+        c += is_due;
+        if (!at_start || (run && !is_due)) mx = max(mx, a);
+    }
+    s_cnt[tid] = c; s_max[tid] = mx;
+    __syncthreads();
+    if (tid == 0) {
+        int o = 0;
+        long long m = stat[1];
+        for (int t = 0; t < NT; t++) { const int v = s_cnt[t]; s_cnt[t] = o; o += v; m = max(m, s_max[t]); }
+        stat[0] = o; stat[1] = m;
+    }
+    __syncthreads();
+    int o = s_cnt[tid];
+    for (int k = k0; k < k1; k++) {
+        const int b = active[k];
+        if (Bv.status[b] == ST_RUNNING && Bv.npend[b] == 0 && age0[b] + Bv.iters[b] >= K) due[o++] = b;
+    }
+}
+// The replay (k_rfx_*) runs on a view of its own, Rv, whose LP k is LP due[k] of the batch: in place on that LP's dst slot.  Everything
+// else of Rv's LP k is k_rfx_setup's to set.
+__global__ void k_per_setup(BatchView Bv, BatchView Rv, const int *due, int n)
+{
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const int slot = Bv.dst[due[k]];
+    const_cast<int *>(Rv.src)[k] = slot; const_cast<int *>(Rv.dst)[k] = slot;
+}
+// the cost of variable k in LP b of the batch: the engine's vector, in an objective batch with the LP's own values on their range
+__device__ __forceinline__ double per_cost(const LpView &L, const BatchView &Bv, const double *cost, const int b, const int k)
+{
+    if (L.objmode) { const int t = k - L.cfirst; if (t >= 0 && t < L.ccnt) return Bv.cvals[(size_t)b * L.ccnt + t]; }
+    return k >= L.M ? cost[k - L.M + 1] : 0.0;
+}
+// y = sum over the rows i of c[bh_i] X[i, :] for the LP's OWN cost (k_rfx_y knows the engine's only), rows in ascending order, into
+// Rv's scratch vector uvec (free until k_rev_u).  Grid (column blocks, n).
+__global__ void k_per_y(LpView L, BatchView Bv, BatchView Rv, const int *due, const double *cost, int n)
+{
+    const int k = blockIdx.y, c = blockIdx.x * blockDim.x + threadIdx.x, M = L.M;
+    if (k >= n || c >= L.ldt) return;
+    double v = 0.0;
+    if (c < M && Rv.mode[k] == MODE_REFRESH) {
+        const int slot = Rv.dst[k], b = due[k];
+        const int *bh = L.bh + (size_t)slot * M;
+        const double *X = L.T + (size_t)slot * L.slotT;
+        for (int i = 0; i < M; i++) {
+            const double ck = per_cost(L, Bv, cost, b, bh[i]);
+            if (ck != 0.0) v = fma(ck, X[(size_t)i * L.ldt + c], v);
+        }
+    }
+    Rv.uvec[(size_t)k * L.ldt + c] = v;
+}
+// The LP goes on: its TRUE reduced costs d_j = c[nh_j] - y . K[nh_j] from the rebuilt inverse, by column slices as k_rfx_price has
+// them, into the batch's dcur; a perturbed row keeps its offsets to the true one, dper_new = d_new + (dper_old - d_old).  Rv's dcur
+// gets the row too: k_rev_u, which runs on Rv next, takes beta[M] = d . x_N from there.  A replay that failed leaves the LP's vectors alone.
+__global__ __launch_bounds__(NT) void k_per_price(LpView L, BatchView Bv, BatchView Rv, const int *due, const double *cost, int n)
+{
+    const int k = blockIdx.y;
+    if (k >= n || Rv.mode[k] != MODE_REFRESH) return;
+    const int b = due[k];
+    const int *nh = L.nh + (size_t)Rv.dst[k] * L.N;
+    double *dn = Rv.dcur + (size_t)k * L.ld;
+    rev_row_slice(L, Rv.uvec + (size_t)k * L.ldt, nh, dn, blockIdx.x, gridDim.x);        // dn[j] = -(y . K[nh_j]), 0 on the padding (barrier at its end)
+    double *dc = Bv.dcur + (size_t)b * L.ld, *dp = Bv.dper + (size_t)b * L.ld;
+    const bool pert = Bv.pflags[b] & PF_PERT;
+    for (int j = blockIdx.x + gridDim.x * threadIdx.x; j < L.N; j += gridDim.x * blockDim.x) {
+        const double d = dn[j] + per_cost(L, Bv, cost, b, nh[j]);
+        if (pert) dp[j] = d + (dp[j] - dc[j]);
+        dc[j] = d; dn[j] = d;
+    }
+}
+// after the refresh pass of the replay: LP due[k] has its own, fresh matrix and a fresh beta, or ends UNDEFINED (singular basis; the
+// host resets its slot when the call is over).  res[k]: the replay's pivots, or -1.
+__global__ void k_per_resume(BatchView Bv, BatchView Rv, RfxView R, const int *due, int n, long long *age0, int *res)
+{
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const int b = due[k];
+    if (R.cnt[(size_t)k * 4 + 2] == RFX_RUN && Rv.status[k] == ST_RUNNING) {
+        Bv.flushed[b] = 1; Bv.verified[b] = (Bv.verified[b] & 2) | 1;
+        age0[b] = -(long long)Bv.iters[b];
+        res[k] = R.cnt[(size_t)k * 4 + 1];
+    } else { Bv.status[b] = BSLV_LP_UNDEFINED; Bv.mode[b] = MODE_NONE; res[k] = -1; }
+}
+
 }  // namespace bslv
 
 using namespace bslv;
@@ -2234,6 +2356,21 @@ struct bslv_lpq {
     int *rmark_d = nullptr; std::vector<int> rmark_h; bool rmark_valid = false;
     int *rfx_i_d = nullptr, *rfx_c_d = nullptr; int rfx_Bcap = 0;
     long last_rfx[4] = {0, 0, 0, 0};
+    // age of the slots' matrices (revised form: [slots], and per LP of a batch, see k_age_begin) and the periodic refactorisation
+    // (bslv_lpq_set_refactor_period): the period, the replay's own batch view (see period_view), the counters of the last solve call
+    long long *age_d = nullptr, *age0_d = nullptr;
+    int period = 0;
+    struct Period {
+        int cap = 0, nwcap = 0;
+        int *src = nullptr, *dst = nullptr, *status = nullptr, *iters = nullptr, *mode = nullptr, *ver = nullptr, *npend = nullptr, *flushed = nullptr, *pflags = nullptr, *stall = nullptr;
+        int *work = nullptr, *nwork = nullptr, *iota = nullptr, *due = nullptr, *res = nullptr;
+        long long *stat = nullptr;                   // [2]: k_per_due's count and largest age
+        PivDesc *desc = nullptr; double *prow = nullptr, *pcol = nullptr, *dcur = nullptr, *uvec = nullptr, *xfull = nullptr;
+        long passes = 0, launches = 0; double ms = 0;      // of the call at hand: the replay's (LP, pass) pairs, its k_flush launches, host wall clock
+        std::vector<int> failed;                     // batch indices whose replay found the basis singular (their slots are reset when the call is over)
+        std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;      // events around the replay's passes (set_profile)
+    } per;
+    long last_per[4] = {0, 0, 0, 0};
     long last_passes = 0;              // (LP, pass) pairs of the last batch: how many tableaux k_flush read and wrote
     long last_launches = 0;            // k_flush launches of the last batch: one per lock-step round + one per pass made on request (bslv_lpq_materialise)
     size_t select_lds_max = 64 * 1024; // dynamic LDS of k_select<true> (candidate sort of the bound flipping ratio test)
@@ -2282,6 +2419,7 @@ static int materialise_indices(bslv_lpq *h, const int *list, int n);
 static void park_release(bslv_lpq *h, int rec);
 static int park_before(bslv_lpq *h, int nuse, const int *use, int nover, const int *over);
 static void park_free(bslv_lpq *h);
+static void period_free(bslv_lpq *h);
 static int ensure_batch(bslv_lpq *h, int B)
 {
     if (B <= h->Bcap) return 0;
@@ -2292,7 +2430,7 @@ static int ensure_batch(bslv_lpq *h, int B)
     auto fr = [](auto *&p) { if (p) (void)hipFree(p); p = nullptr; };
     fr(h->src_d); fr(h->dst_d); fr(h->status_d); fr(h->iters_d); fr(h->mode_d); fr(h->ver_d); fr(h->active_d); fr(h->work_d); fr(h->qslot_d); fr(h->init_d);
     fr(h->vlo_d); fr(h->vup_d); fr(h->prow_d); fr(h->desc_d); fr(h->npend_d); h->flushed_d = nullptr; fr(h->pcol_d); fr(h->dcur_d); fr(h->dper_d); fr(h->pflags_d); fr(h->stall_d);
-    fr(h->trow_d); fr(h->uvec_d); fr(h->xfull_d); fr(h->hmail_d); fr(h->rmark_d);
+    fr(h->trow_d); fr(h->uvec_d); fr(h->xfull_d); fr(h->hmail_d); fr(h->rmark_d); fr(h->age0_d);
     if (h->status_h) { (void)hipHostFree(h->status_h); h->status_h = nullptr; }
     if (h->active_h) { (void)hipHostFree(h->active_h); h->active_h = nullptr; }
     if (h->init_h) { (void)hipHostFree(h->init_h); h->init_h = nullptr; }
@@ -2315,6 +2453,7 @@ static int ensure_batch(bslv_lpq *h, int B)
         HIP_TRY(malloc0(&h->xfull_d, (size_t)cap * h->L.N * sizeof(double)));
         HIP_TRY(malloc0(&h->hmail_d, (size_t)cap * 8 * sizeof(int)));
         HIP_TRY(malloc0(&h->rmark_d, (size_t)cap * sizeof(int)));
+        HIP_TRY(malloc0(&h->age0_d, (size_t)cap * sizeof(long long)));
     }
     HIP_TRY(malloc0(&h->desc_d, (size_t)cap * KP * sizeof(PivDesc)));
     HIP_TRY(malloc0(&h->pcol_d, (size_t)cap * KP * h->L.Mp1p * sizeof(double)));
@@ -2459,6 +2598,8 @@ static int raw_create(bslv_lpq **out, int M, int N, const double *A, const doubl
     if (!rev) TRYF(malloc0(&h->Tstd, L.slotT * sizeof(double)));
     else {
         TRYF(malloc0(&h->dsl_d, (size_t)pool_slots * L.ld * sizeof(double)));
+        TRYF(malloc0(&h->age_d, (size_t)pool_slots * sizeof(long long)));
+        TRYF(hipMemset(h->age_d, 0, (size_t)pool_slots * sizeof(long long)));      // (whatever malloc0 fills with: a slot nobody has built yet has no age)
         TRYF(malloc0(&h->cost_d, (size_t)(N + 1) * sizeof(double)));
         TRYF(malloc0(&h->cptr_d, (size_t)(N + 1) * sizeof(int)));
         TRYF(malloc0(&h->rptr_d, (size_t)(M + 1) * sizeof(int)));
@@ -2513,6 +2654,8 @@ static int raw_create(bslv_lpq **out, int M, int N, const double *A, const doubl
     // BSLV_LP_REFACTOR=1: the in-call rescue of bslv_lpq_set_refactor, for an engine in the revised form (the tableau form has no inverse to rebuild)
     L.rfx = 0; L.drift_b = -1; L.drift_p = -1;
     if (const char *e = getenv("BSLV_LP_REFACTOR")) { if (rev) h->refactor_on = atoi(e) != 0; }
+    // BSLV_LP_REFACTOR_EVERY=K: the period of bslv_lpq_set_refactor_period, for an engine in the revised form (the tableau form ignores it)
+    if (const char *e = getenv("BSLV_LP_REFACTOR_EVERY")) { if (rev) h->period = std::max(0, atoi(e)); }
     // BSLV_LP_PARK=0: bslv_lpq_park makes the passes at once, as bslv_lpq_materialise does (bslv_lpq_set_park)
     if (const char *e = getenv("BSLV_LP_PARK")) h->park.on = atoi(e) != 0;
     *out = h;
@@ -2523,7 +2666,9 @@ void bslv_lpq_destroy(bslv_lpq *h)
 {
     if (!h) return;
     park_free(h);
+    period_free(h);
     auto fr = [](void *p) { if (p) (void)hipFree(p); };
+    fr(h->age_d); fr(h->age0_d);
     fr(h->L.T); fr(h->L.beta); fr(h->L.xN); fr(h->L.bh); fr(h->L.nh); fr(h->L.nstat); fr(h->L.pos);
     fr(h->Tstd); fr(h->lb_d); fr(h->ub_d); fr(h->art_d);
     fr(h->dbg_d); fr(h->list_d); fr(h->cptr_d); fr(h->cidx_d); fr(h->rptr_d); fr(h->ridx_d); fr(h->cval_d); fr(h->rval_d); fr(h->cost_d); fr(h->dsl_d); fr(h->trow_d); fr(h->uvec_d); fr(h->xfull_d); fr(h->hmail_d);
@@ -2657,6 +2802,7 @@ int bslv_lpq_reset_slot(bslv_lpq *h, int slot)
     int n = std::max(std::max(L.M, L.N), std::max(L.ld, L.Mp1p));
     hipLaunchKernelGGL(k_std_heads, dim3((n + 255) / 256), dim3(256), 0, h->stream, L, slot);
     HIP_TRY(hipGetLastError());
+    if (L.rev) HIP_TRY(hipMemsetAsync(h->age_d + slot, 0, sizeof(long long), h->stream));      // (the identity: no step applied)
     HIP_TRY(hipStreamSynchronize(h->stream));
     return 0;
 }
@@ -2944,6 +3090,120 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
                             int cfirst, int ccnt, const double *cvals, int *status, int *iters);
 static int solve_batch_rescue(bslv_lpq *h, int B, const int *src, const int *dst, const double *vlo, const double *vup,
                               int cfirst, int ccnt, const double *cvals, int *status, int *iters);
+// ---- periodic refactorisation inside a solve (bslv_lpq_set_refactor_period): host side (the kernels: k_per_*, k_rfx_*) ----
+// The replay of k_rfx_* overwrites, for the batch indices it runs on, everything a batch keeps per LP.  In the middle of a batch those
+// belong to running LPs, so it gets a BatchView of its own, as the parked passes have (park_view): its LP k is LP due[k] of the batch,
+// in place on that LP's slot, with its own counters, pending pivots, reduced-cost row and work lists (so its passes do not count into
+// the work lists of the rounds).  Sized with the batch buffers BEFORE the rounds start: nothing is allocated while a batch is in flight.
+static int ensure_rfx(bslv_lpq *h);
+static void period_free(bslv_lpq *h)
+{
+    bslv_lpq::Period &P = h->per;
+    auto fr = [](auto *&p) { if (p) (void)hipFree(p); p = nullptr; };
+    fr(P.src); fr(P.dst); fr(P.status); fr(P.iters); fr(P.mode); fr(P.ver); fr(P.npend); fr(P.flushed); fr(P.pflags); fr(P.stall);
+    fr(P.work); fr(P.nwork); fr(P.iota); fr(P.due); fr(P.res); fr(P.stat); fr(P.desc); fr(P.prow); fr(P.pcol); fr(P.dcur); fr(P.uvec); fr(P.xfull);
+    for (auto &e : P.ev) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
+    P.ev.clear();
+    P.cap = 0; P.nwcap = 0;
+}
+static int period_rounds_max(const LpView &L) { return (L.M + KP - 1) / KP + 2; }
+static int ensure_period(bslv_lpq *h)
+{
+    bslv_lpq::Period &P = h->per;
+    const LpView &L = h->L;
+    int rc;
+    if ((rc = ensure_rfx(h))) return rc;
+    if (P.cap >= h->Bcap && P.src) return 0;
+    period_free(h);
+    const size_t cap = (size_t)h->Bcap;
+    for (int **p : {&P.src, &P.dst, &P.status, &P.iters, &P.mode, &P.ver, &P.npend, &P.flushed, &P.pflags, &P.stall, &P.work, &P.iota, &P.due, &P.res}) HIP_TRY(malloc0(p, cap * sizeof(int)));
+    P.nwcap = period_rounds_max(L) + 2;
+    HIP_TRY(malloc0(&P.nwork, (size_t)P.nwcap * sizeof(int)));
+    HIP_TRY(malloc0(&P.stat, 2 * sizeof(long long)));
+    HIP_TRY(malloc0(&P.desc, cap * KP * sizeof(PivDesc)));
+    HIP_TRY(malloc0(&P.prow, cap * KP * L.ldt * sizeof(double)));
+    HIP_TRY(malloc0(&P.pcol, cap * KP * L.Mp1p * sizeof(double)));
+    HIP_TRY(malloc0(&P.dcur, cap * L.ld * sizeof(double)));
+    HIP_TRY(malloc0(&P.uvec, cap * L.ldt * sizeof(double)));
+    HIP_TRY(malloc0(&P.xfull, cap * L.N * sizeof(double)));
+    std::vector<int> iota(cap);
+    for (size_t k = 0; k < cap; k++) iota[k] = (int)k;
+    HIP_TRY(hipMemcpy(P.iota, iota.data(), cap * sizeof(int), hipMemcpyHostToDevice));
+    P.cap = h->Bcap;
+    return 0;
+}
+static BatchView period_view(bslv_lpq *h, const BatchView &bv)
+{
+    const bslv_lpq::Period &P = h->per;
+    BatchView v = bv;      // (bounds, costs and the selection's scratch stay the batch's: the replay reads none of them)
+    v.src = P.src; v.dst = P.dst; v.status = P.status; v.iters = P.iters; v.mode = P.mode; v.verified = P.ver; v.npend = P.npend; v.flushed = P.flushed;
+    v.pflags = P.pflags; v.stall = P.stall; v.work = P.work; v.nwork = P.nwork;
+    v.desc = P.desc; v.prow = P.prow; v.pcol = P.pcol; v.dcur = P.dcur; v.uvec = P.uvec; v.xfull = P.xfull;
+    v.lazy = 0;
+    return v;
+}
+// The n LPs of the batch that k_per_due listed (per.due, batch indices in the order of the active list) are refactorised in their dst
+// slots and go on -- bounds, nonbasic statuses and values, iteration count, pflags, stall and Bland state and their place in the batch are
+// not touched; the matrix, the heads of the basic variables, beta and the true reduced costs are rebuilt before the next selection.  An
+// LP whose basis the replay finds singular ends UNDEFINED (status_h follows).  at_start: counts in out[0], else in out[1].
+static int period_refactor(bslv_lpq *h, const BatchView &bv, int n, bool at_start)
+{
+    bslv_lpq::Period &P = h->per;
+    LpView &L = h->L;
+    hipStream_t s = h->stream;
+    const auto t0 = std::chrono::steady_clock::now();
+    const int M = L.M, rounds_max = period_rounds_max(L);
+    int rc;
+    BatchView rv = period_view(h, bv);
+    RfxView R;
+    R.enter = h->rfx_i_d; R.rowvar = h->rfx_i_d + (size_t)h->Bcap * M; R.elig = h->rfx_i_d + (size_t)h->Bcap * 2 * M; R.cnt = h->rfx_c_d; R.cost = h->cost_d;
+    HIP_TRY(hipMemsetAsync(P.nwork, 0, (size_t)P.nwcap * sizeof(int), s));
+    hipLaunchKernelGGL(k_per_setup, dim3((n + 255) / 256), dim3(256), 0, s, bv, rv, (const int *)P.due, n);
+    hipLaunchKernelGGL(k_rfx_setup, dim3(n), dim3(NT), 0, s, L, rv, R, n);
+    {
+        const size_t total = (size_t)M * L.ldt;
+        hipLaunchKernelGGL(k_rfx_identity, dim3((unsigned)std::min<size_t>((total + 255) / 256, 4096), n), dim3(256), 0, s, L, rv, R, n);
+    }
+    HIP_TRY(hipGetLastError());
+    std::vector<int> cnt((size_t)n * 4);
+    HIP_TRY(hipMemcpyAsync(cnt.data(), h->rfx_c_d, cnt.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    int kmax = 0;
+    for (int k = 0; k < n; k++) if (cnt[(size_t)k * 4 + 2] == RFX_RUN) kmax = std::max(kmax, cnt[(size_t)k * 4]);
+    const int rounds = std::min((kmax + KP - 1) / KP, rounds_max);
+    const int snt = M >= 1536 ? NT_BIG : NT;
+    auto pass = [&](int cnt_slot) -> int {
+        hipLaunchKernelGGL(k_list_pending, dim3((n + 255) / 256), dim3(256), 0, s, rv, (const int *)P.iota, n, cnt_slot);
+        if (h->profile) P.ev.emplace_back(nullptr, nullptr);
+        return flush_launch(h, rv, cnt_slot, n, h->profile ? &P.ev.back() : nullptr);
+    };
+    for (int it = 0; it < rounds; it++) {
+        hipLaunchKernelGGL(k_rfx_select, dim3(n), dim3(snt), 0, s, L, rv, R, n, KP);
+        if ((rc = pass(it))) return rc;
+    }
+    hipLaunchKernelGGL(k_rfx_finish, dim3(n), dim3(NT), 0, s, L, rv, R, n);
+    // the LP's own costs on the rebuilt inverse -> its reduced costs (and the perturbed row's offsets), then uvec = -K_N x_N and beta[M],
+    // then the refresh pass for beta: all of it before the next selection
+    hipLaunchKernelGGL(k_per_y, dim3((L.ldt + 255) / 256, n), dim3(256), 0, s, L, bv, rv, (const int *)P.due, (const double *)h->cost_d, n);
+    hipLaunchKernelGGL(k_per_price, dim3((L.ld + REV_PRICE_SLICE - 1) / REV_PRICE_SLICE, n), dim3(NT), 0, s, L, bv, rv, (const int *)P.due, (const double *)h->cost_d, n);
+    hipLaunchKernelGGL(k_rev_u, dim3(n), dim3(NT), 0, s, L, rv, n, (const int *)nullptr, 0);
+    if ((rc = pass(rounds_max + 1))) return rc;
+    hipLaunchKernelGGL(k_per_resume, dim3((n + 255) / 256), dim3(256), 0, s, bv, rv, R, (const int *)P.due, n, h->age0_d, P.res);
+    HIP_TRY(hipGetLastError());
+    std::vector<int> due(n), res(n), nw(P.nwcap);
+    HIP_TRY(hipMemcpyAsync(due.data(), P.due, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(res.data(), P.res, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(nw.data(), P.nwork, (size_t)P.nwcap * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int k = 0; k < n; k++) {
+        if (res[k] >= 0) { h->last_per[at_start ? 0 : 1] += 1; h->last_per[2] += res[k]; }
+        else { P.failed.push_back(due[k]); h->status_h[due[k]] = BSLV_LP_UNDEFINED; }
+    }
+    for (int k = 0; k < P.nwcap; k++) P.passes += nw[k];
+    P.launches += rounds + 1;
+    P.ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return 0;
+}
 // tie phase: pivots an LP may spend in it (Bland's rule holds from PRIMAL_STALL on), and the rounds that leaves a batch at most --
 // every round an LP of the phase is in makes a pivot or ends it, except the one it waits in for a pass with KP pivots pending
 static int tie_cap(const LpView &L) { return 2 * PRIMAL_STALL + 2 * (L.M + L.N); }
@@ -3125,6 +3385,10 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
         h->lazy_open = false;
     }
     if ((rc = ensure_batch(h, B))) return rc;
+    // periodic refactorisation: the replay's buffers are sized now, nothing is allocated once the batch is in flight
+    const int period = h->L.rev ? h->period : 0;
+    if (period > 0 && (rc = ensure_period(h))) return rc;
+    h->per.passes = 0; h->per.launches = 0; h->per.ms = 0; h->per.failed.clear();
     // parked passes: the parents of this batch get their tableau, and so does whoever still reads a slot this batch overwrites
     // (before k_prep: the pass reads and writes slots the batch touches)
     if ((rc = park_before(h, B, src, B, dst))) return rc;
@@ -3155,6 +3419,7 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
     BatchView bv = bview(h);
     bv.cvals = h->cvals_d;
     const int tiles = (L.mrows + TR - 1) / TR;
+    if (L.rev) hipLaunchKernelGGL(k_age_begin, dim3((B + 255) / 256), dim3(256), 0, s, bv, (const long long *)h->age_d, h->age0_d, B);      // the age of every LP's matrix: its parent's
     {   // (objective batches keep their own start; the revised form knows the dual method only: bslv_lpq_set_method)
         const int method = (L.objmode || L.rev) ? BSLV_LP_METHOD_DUAL : h->method;
         if (method == BSLV_LP_METHOD_PRIMAL) hipLaunchKernelGGL(k_prep<BSLV_LP_METHOD_PRIMAL>, dim3(B), dim3(NT), 0, s, L, bv, B);
@@ -3209,6 +3474,21 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
     h->last_update_ms = 0;
     static const int max_rounds = getenv("BSLV_LP_MAXROUNDS") ? atoi(getenv("BSLV_LP_MAXROUNDS")) : 0;      // (timing experiments)
     L.probe = getenv("BSLV_REV_PROBE") ? atoi(getenv("BSLV_REV_PROBE")) : 0;
+    // PERIODIC REFACTORISATION (bslv_lpq_set_refactor_period): the LPs of the active list that are due are listed on the stream
+    // (period_list, before a readback) and, once the host knows their number, refactorised in their slots and go on (period_refactor).
+    // At the start of the call that is every LP k_prep accepted whose parent's matrix is old enough: it is rebuilt from the heads
+    // k_prep left in dst before the first selection, and nothing of the parent's matrix enters what the LP computes.
+    auto period_list = [&](const int nact, const bool at_start) {
+        hipLaunchKernelGGL(k_per_due, dim3(1), dim3(NT), 0, s, bv, (const int *)h->active_d, nact, (const long long *)h->age0_d, (long long)period, at_start ? 1 : 0, h->per.due, h->per.stat);
+    };
+    long long per_stat[2] = {0, 0};
+    if (period > 0) {
+        HIP_TRY(hipMemsetAsync(h->per.stat, 0, sizeof per_stat, s));
+        period_list(B, true);
+        HIP_TRY(hipMemcpyAsync(per_stat, h->per.stat, sizeof per_stat, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (per_stat[0] > 0 && (rc = period_refactor(h, bv, (int)per_stat[0], true))) return rc;
+    }
     // the pass of round `it` over the tableaux of the `running` LPs of the active list that have something pending
     auto pass_round = [&](const int running, const int it) -> int {
         hipLaunchKernelGGL(k_list_pending, dim3((running + 255) / 256), dim3(256), 0, s, bv, h->active_d, running, it);
@@ -3241,12 +3521,18 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
             if ((rc = pass_round(running, it))) return rc;
         }
         HIP_TRY(hipGetLastError());
+        if (period > 0) { period_list(running, false); HIP_TRY(hipMemcpyAsync(per_stat, h->per.stat, sizeof per_stat, hipMemcpyDeviceToHost, s)); }
         HIP_TRY(hipMemcpyAsync(h->status_h, h->status_d, B * sizeof(int), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
+        // (the pass of the round has just been made: nothing is pending for any running LP)
+        if (period > 0 && per_stat[0] > 0 && (rc = period_refactor(h, bv, (int)per_stat[0], false))) return rc;
         running = 0;
         for (int b = 0; b < B; b++) if (h->status_h[b] == ST_RUNNING) h->active_h[running++] = b;
         if (running) HIP_TRY(hipMemcpyAsync(h->active_d, h->active_h, running * sizeof(int), hipMemcpyHostToDevice, s));
         if (chunk < 16) chunk *= 2;
+        // with a period the status vector is read at least every max(1, K / KP) rounds: an LP below K at one readback has made at most
+        // max(KP, K) pivots more at the next, so no selection is made on a matrix older than 2 K + KP
+        if (period > 0) chunk = std::min(chunk, std::max(1, period / KP));
     }
     // TIE PHASE (bslv_lpq_set_canonical): the LPs that ended OPTIMAL go on to their canonical basis, in rounds of the same shape --
     // KP tie pivots on vectors (k_select_tie), one pass.  Their work lists count on from L.maxit + 64.
@@ -3298,7 +3584,7 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
             HIP_TRY(hipMemcpy(nw.data(), h->nwork_d + tie_base, (size_t)tie_rounds * sizeof(int), hipMemcpyDeviceToHost));
             for (int k = 0; k < tie_rounds; k++) passes += nw[k];
         }
-        h->last_passes = passes;
+        h->last_passes = passes + h->per.passes;      // (the replay's passes count in work lists of their own)
     }
     if (L.rev) hipLaunchKernelGGL(k_rev_store_d, dim3((L.ld + 255) / 256, B), dim3(256), 0, s, L, bv, B);       // the reduced costs of every LP go to its slot
     if (bv.lazy) {
@@ -3321,6 +3607,13 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
         hipLaunchKernelGGL(k_copy_unpivoted, dim3(std::min(B * tiles, 2048)), dim3(NT), 0, s, L, bv, cnt_slot, tiles);
         HIP_TRY(hipGetLastError());
     }
+    if (L.rev) hipLaunchKernelGGL(k_age_end, dim3((B + 255) / 256), dim3(256), 0, s, bv, h->age_d, (const long long *)h->age0_d, B);
+    if (period > 0) {
+        HIP_TRY(hipMemcpy(per_stat, h->per.stat, sizeof per_stat, hipMemcpyDeviceToHost));
+        h->last_per[3] = std::max(h->last_per[3], (long)per_stat[1]);
+        // a slot whose replay failed holds a half-built matrix: it is reset, as bslv_lpq_refactor does (now: the solve has left its vectors in it)
+        for (int b : h->per.failed) if ((rc = bslv_lpq_reset_slot(h, dst[b]))) return rc;
+    }
     if (status) for (int b = 0; b < B; b++) status[b] = h->status_h[b] == ST_RUNNING ? BSLV_LP_UNDEFINED : h->status_h[b];
     if (L.rfx) { h->rmark_h.resize(B); HIP_TRY(hipMemcpy(h->rmark_h.data(), h->rmark_d, (size_t)B * sizeof(int), hipMemcpyDeviceToHost)); h->rmark_valid = true; }      // (the LPs the pivot cross-check gave up: solve_batch_rescue)
     {
@@ -3332,7 +3625,7 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
         if (iters) memcpy(iters, itv.data(), B * sizeof(int));
     }
     h->last_iters = it + tie_rounds;
-    h->last_launches = it + tie_rounds;
+    h->last_launches = it + tie_rounds + h->per.launches;
     {   // the unpark passes made since the last batch count with this one (they ran on the stream before its first kernel)
         bslv_lpq::Park &P = h->park;
         h->last_passes += P.pre_passes; h->last_launches += P.pre_launches;
@@ -3344,8 +3637,11 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
         double ms = 0;
         for (size_t e = 0; e < nev; e++) { float t = 0; (void)hipEventElapsedTime(&t, h->evpool[e].first, h->evpool[e].second); ms += t; }
         for (auto &e : h->park.pre_ev) { float t = 0; (void)hipEventElapsedTime(&t, e.first, e.second); ms += t; }
+        for (auto &e : h->per.ev) { float t = 0; (void)hipEventElapsedTime(&t, e.first, e.second); ms += t; }
         h->last_update_ms = ms;
     }
+    for (auto &e : h->per.ev) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
+    h->per.ev.clear();
     for (auto &e : h->park.pre_ev) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
     h->park.pre_ev.clear();
     h->last_total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -3361,6 +3657,7 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
     {
         static const bool tm = getenv("BSLV_LP_TIMING") != nullptr;
         if (tm) fprintf(stderr, "lp solve_batch: %s form %d x %d, B %d, %d lock-step rounds, %ld pivots, %ld passes, %.1f ms; %d parents, largest family %d, %s\n", L.rev ? "revised" : "tableau", L.M, L.N, B, it, h->last_pivots, h->last_passes, h->last_total_ms, h->last_init_parents, h->last_init_family, h->last_init_chunks ? "k_init_grouped" : "k_init");
+        if (tm && period > 0) fprintf(stderr, "lp period %d: %ld refactorisations at the start, %ld during the rounds, %ld replay pivots, largest age at a selection %ld, %ld replay passes, %.1f ms in refactorisations\n", period, h->last_per[0], h->last_per[1], h->last_per[2], h->last_per[3], h->per.passes, h->per.ms);
         if (tm && h->park.cap) fprintf(stderr, "lp park (totals): %ld parked, %ld unparked for a child, %ld because their source was about to be overwritten, %ld dropped unused, %zu live\n", h->park.stats[0], h->park.stats[1], h->park.stats[2], h->park.stats[3], h->park.live.size());
     }
     return 0;
@@ -3430,6 +3727,7 @@ static int refactor_impl(bslv_lpq *h, int n, const int *slots, int *status_out, 
     hipLaunchKernelGGL(k_list_pending, dim3((n + 255) / 256), dim3(256), 0, s, bv, h->active_d, n, rounds_max + 1);
     HIP_TRY(hipGetLastError());
     if ((rc = flush_list(h, rounds_max + 1, n, false))) return rc;
+    hipLaunchKernelGGL(k_age_zero, dim3((n + 255) / 256), dim3(256), 0, s, (const int *)h->dst_d, n, h->age_d);      // built from the identity (a failed slot is reset below)
     HIP_TRY(hipMemcpy(cnt.data(), h->rfx_c_d, cnt.size() * sizeof(int), hipMemcpyDeviceToHost));
     for (int b = 0; b < n; b++) {
         const bool ok = cnt[(size_t)b * 4 + 2] == RFX_RUN;
@@ -3449,6 +3747,7 @@ static int solve_batch_rescue(bslv_lpq *h, int B, const int *src, const int *dst
     if (h) {
         LpView &L = h->L;
         for (int k = 0; k < 4; k++) h->last_rfx[k] = 0;
+        for (int k = 0; k < 4; k++) h->last_per[k] = 0;      // (solve_batch_impl adds to them: the rescue's solves count with the call)
         h->rmark_valid = false;
         L.rfx = (h->refactor_on && L.rev) ? 1 : 0;
         L.drift_b = -1; L.drift_p = -1;
@@ -3536,6 +3835,33 @@ int bslv_lpq_last_refactor_stats(const bslv_lpq *h, long out[4])
 {
     if (!h || !out) return BSLV_E_ARG;
     for (int k = 0; k < 4; k++) out[k] = h->last_rfx[k];
+    return 0;
+}
+int bslv_lpq_set_refactor_period(bslv_lpq *h, int pivots)
+{
+    if (!h) { set_error("bslv_lpq_set_refactor_period: no engine"); return BSLV_E_ARG; }
+    if (pivots < 0) { set_error("bslv_lpq_set_refactor_period: bad argument (pivots = %d)", pivots); return BSLV_E_ARG; }
+    if (pivots > 0 && !h->L.rev) { set_error("bslv_lpq_set_refactor_period: the engine is in the tableau form, which keeps no basis inverse to rebuild"); return BSLV_E_ARG; }
+    h->period = pivots;
+    return 0;
+}
+int bslv_lpq_get_refactor_period(const bslv_lpq *h) { return h ? h->period : 0; }
+int bslv_lpq_slot_age(const bslv_lpq *h, int slot, long *age)
+{
+    if (!h || !age) { set_error("bslv_lpq_slot_age: bad argument"); return BSLV_E_ARG; }
+    if (slot < 0 || slot >= h->slots) { set_error("bslv_lpq_slot_age: bad slot %d", slot); return BSLV_E_ARG; }
+    *age = 0;
+    if (!h->L.rev) return 0;               // (the tableau form keeps no inverse: nothing ages)
+    long long a = 0;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpy(&a, h->age_d + slot, sizeof a, hipMemcpyDeviceToHost));
+    *age = (long)a;
+    return 0;
+}
+int bslv_lpq_last_period_stats(const bslv_lpq *h, long out[4])
+{
+    if (!h || !out) return BSLV_E_ARG;
+    for (int k = 0; k < 4; k++) out[k] = h->last_per[k];
     return 0;
 }
 int bslv_lpq_get_inverse(bslv_lpq *h, int slot, int *heads, double *X)

@@ -264,6 +264,30 @@ class LpEngine:
         check(self.lib.bslv_lpq_last_refactor_stats(self.h, o))
         return dict(refactorised=int(o[0]), replay_pivots=int(o[1]), rescued=int(o[2]), failed=int(o[3]))
 
+    def set_refactor_period(self, pivots):
+        """revised form: refactorise an LP's basis inverse inside a solve once it is `pivots` rank-1 steps old, 0 = off
+        (bslv_lpq_set_refactor_period).  Returns the library's code (0, or BSLV_E_ARG for a negative period or the tableau form)."""
+        self.lib.bslv_lpq_set_refactor_period.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        return int(self.lib.bslv_lpq_set_refactor_period(self.h, int(pivots)))
+
+    def get_refactor_period(self):
+        self.lib.bslv_lpq_get_refactor_period.argtypes = [ctypes.c_void_p]
+        return int(self.lib.bslv_lpq_get_refactor_period(self.h))
+
+    def slot_age(self, slot):
+        """rank-1 steps applied to the slot's basis inverse since it was last built from the identity (bslv_lpq_slot_age; tableau form: 0)"""
+        a = ctypes.c_long()
+        self.lib.bslv_lpq_slot_age.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+        check(self.lib.bslv_lpq_slot_age(self.h, int(slot), ctypes.byref(a)))
+        return int(a.value)
+
+    def last_period_stats(self):
+        """periodic refactorisation of the last solve call (bslv_lpq_last_period_stats)"""
+        o = (ctypes.c_long * 4)()
+        self.lib.bslv_lpq_last_period_stats.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        check(self.lib.bslv_lpq_last_period_stats(self.h, o))
+        return dict(at_start=int(o[0]), in_rounds=int(o[1]), replay_pivots=int(o[2]), max_age=int(o[3]))
+
     def get_inverse(self, slot, matrix=True):
         """revised form: (basis heads, stored matrix M x M or None) of a slot, in the engine's own indices (bslv_lpq_get_inverse)"""
         self.lib.bslv_lpq_is_revised.argtypes = [ctypes.c_void_p]

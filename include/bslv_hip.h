@@ -104,6 +104,35 @@ int  bslv_lpq_refactor(bslv_lpq *h, int n, const int *slots, int *status_out);
 int  bslv_lpq_set_refactor(bslv_lpq *h, int on);
 int  bslv_lpq_get_refactor(const bslv_lpq *h);
 int  bslv_lpq_last_refactor_stats(const bslv_lpq *h, long out[4]);
+/* PERIODIC REFACTORISATION inside a solve (revised form only; off by default, and with the period at 0 every launch and every result
+ * is what it is without it).  Every slot has an AGE: the rank-1 steps applied to its matrix since it was last built from the identity.
+ * bslv_lpq_reset_slot, a successful bslv_lpq_refactor, a refactorisation of the rescue above and one made by the period set it to 0; a
+ * solve leaves age[dst] = age[src] + the LP's own steps since its last refactorisation inside the solve (in place too).  The ages live
+ * beside the pool (bslv_lpq_slot_bytes is what it was) and are kept whether a period is set or not; bslv_lpq_slot_age reads one (the
+ * tableau form reports 0).  The steps of a solve are counted as its iterations: a primal step in which the entering variable only switches
+ * bound counts too, so the age never underestimates.
+ * bslv_lpq_set_refactor_period(h, K): 0 = off; K < 0 is BSLV_E_ARG; the tableau form answers BSLV_E_ARG to K > 0 (its message names the
+ * tableau form) and accepts 0.  BSLV_LP_REFACTOR_EVERY=K sets the period when an engine comes up in the revised form; the tableau form
+ * ignores the variable.  Independent of bslv_lpq_set_refactor: both may be on, the pivot cross-check and the rescue stay as they are.
+ * With K > 0, in bslv_lpq_solve_batch and bslv_lpq_solve_batch_obj alike:
+ *  - at the START of a call an LP that was accepted and whose parent's age is >= K is refactorised in its dst slot, from the heads it
+ *    inherited, before its first selection; it then has its own matrix, and no number of the parent's matrix enters what it computes;
+ *  - during the ROUNDS the ages are checked where the host reads the status vector back, which with a period happens at least every
+ *    max(1, K / KP) rounds (KP = 6 pivots per round): a running LP whose age is >= K there is refactorised and GOES ON.  It keeps its
+ *    bounds, nonbasic statuses and values, iteration count, perturbation, stall and Bland state and its place in the batch; the matrix,
+ *    the heads of the basic variables (they follow the rows the replay put them in), the basic values and the TRUE reduced costs
+ *    d_j = c_j - y K_j, y = sum_i c[bh_i] X[i, :] -- c being the LP's own cost in an objective batch -- are rebuilt before its next
+ *    selection; a perturbed cost row keeps its offsets to the true one.  No selection is made on an inverse older than 2 K + KP: a
+ *    bound that follows from the readback rule (derived, not measured); the statistics report the largest age met;
+ *  - a replay that finds the basis singular ends that LP BSLV_LP_UNDEFINED and its slot is reset as by bslv_lpq_reset_slot; the rescue,
+ *    if on, and the callers' retries see it like any other UNDEFINED.
+ * bslv_lpq_last_period_stats, summed over the last solve call: [0] refactorisations made at the start, [1] during the rounds, [2] replay
+ * pivots, [3] the largest age at which any selection was made.  bslv_lpq_last_refactor_stats does not count these; bslv_lpq_last_stats
+ * (total_ms, and update_ms with the profile on) and bslv_lpq_last_passes cover the replay's passes. */
+int  bslv_lpq_set_refactor_period(bslv_lpq *h, int pivots);
+int  bslv_lpq_get_refactor_period(const bslv_lpq *h);
+int  bslv_lpq_slot_age(const bslv_lpq *h, int slot, long *age);
+int  bslv_lpq_last_period_stats(const bslv_lpq *h, long out[4]);
 /* Test and diagnostic support of the revised form, plain C ABI like everything here.  bslv_lpq_get_inverse: the basis heads (M
  * variable ids: 0..M-1 auxiliary, M.. structural) and, unless X is NULL, the stored matrix of a slot, M x M row-major, in the indices
  * of the engine's own model (M = rows given minus bslv_lpq_rows_folded).  bslv_lpq_debug_perturb_inverse multiplies entry (i, c) of
