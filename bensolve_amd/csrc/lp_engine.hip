@@ -1822,6 +1822,184 @@ __global__ __launch_bounds__(NT_BIG) void k_select_tie(LpView L, BatchView Bv, T
     }
 }
 
+// ---- TIE PHASE OF AN OBJECTIVE BATCH (bslv_lpq_set_canonical_obj): the canonical optimal POINT of a dual degenerate LP ----
+// The transposed case: an LP of solve_batch_obj whose costs are normal to a whole face of the feasible set's image has a face of optimal
+// points, and the vertex the pivoting ended in is whichever it reached.  The canonical one is the vertex that STAYS optimal for the costs
+// c + t ddir (ddir: ccnt values on the variables of the cost range) for every small t > 0 -- the lexicographic minimum of (c . x, ddir . x)
+// -- again without ever forming t: the engine keeps g, the reduced-cost row of ddir at the current basis,
+//   g_j = ddir_{nh[j]} + sum over the basic variables k of the cost range of ddir_k T[row of k][j]
+// (built on entry through the pending pivots, as k_prep builds the reduced costs of a new objective; afterwards it follows every pivot by
+// the pivot row, as the reduced costs do).  A nonbasic column is TIED when |d_j| <= TOL_DJ on the true reduced costs and WRONG when g_j
+// has the sign primal_step's optimality test rejects for its status.  The phase is the primal simplex on that second level: the wrong
+// tied column with the largest |g_j| enters (Bland's rule after PRIMAL_STALL steps), the leaving row comes from primal_step's Harris
+// two-pass ratio test (phase 2's: restated here, so that the kernels that inline primal_step stay what they were), the entering variable
+// switches bound without a pivot where its own box is the tightest ratio.  Unlike the tie phase above the steps HAVE A LENGTH: x moves
+// along the optimal face, beta, x_N and the objective (by at most TOL_DJ x step) follow as in any primal step, and the step is an
+// ordinary PivDesc for k_flush, lazy tableaux, parked passes and warm starts.  The phase ends OPTIMAL in every case: no wrong tied
+// column (canonical), an entering column without a blocking row (ddir . x is unbounded on the optimal face: the basis reached stays), or
+// the cap on its iterations -- after conclude_optimal's recomputation of beta where the solve has made that many pivots.
+struct TieObjView {
+    const double *dir;      // [ccnt] ddir, per variable of the cost range
+    double *g;              // [B][ld] reduced-cost row of ddir
+    int *state, *iters;     // [B] TIE_*; tie iterations (pivots + bound switches) of the LP
+    int *stat;              // [4] LPs that entered the phase, tie iterations, LPs that ended on a column without a blocking row, LPs that gave up at the cap
+    int cap;                // tie iterations per LP
+};
+// the phase of LP b ends (why: the counter of Tv.stat that says so, or -1) -- on a recomputed beta by conclude_optimal's rule: false when
+// the LP waits for that pass first (the selection after it comes to the same end)
+__device__ __forceinline__ bool tie_obj_finish(const BatchView &Bv, const TieObjView &Tv, const int b, const int why)
+{
+    const int verified = Bv.verified[b], iters = Bv.iters[b];
+    __syncthreads();
+    if (!(verified & 1) && (iters > REFRESH_AFTER || (verified & 2))) { if (threadIdx.x == 0) Bv.mode[b] = MODE_REFRESH; return false; }
+    if (threadIdx.x == 0) {
+        Tv.state[b] = TIE_DONE; Bv.status[b] = BSLV_LP_OPTIMAL; Bv.mode[b] = MODE_NONE;
+        if (why >= 0) atomicAdd(&Tv.stat[why], 1);
+    }
+    return true;
+}
+// One tie iteration of LP b by the calling workgroup; false when the LP cannot select again before the next pass (finished, waiting for
+// a refresh, KP pivots pending).  sv, si, p_d: LDS of the kernel (see SelShared for why it is handed down).
+__device__ __forceinline__ bool tie_obj_once(const LpView &L, const BatchView &Bv, const TieObjView &Tv, const int b, double *sv, int *si, PivDesc *p_d)
+{
+    const int tid = threadIdx.x, NT = (int)blockDim.x;
+    const int state = Tv.state[b], np = Bv.npend[b], titer = Tv.iters[b], mode = Bv.mode[b];
+    if (state == TIE_DONE || mode == MODE_REFRESH || np >= KP) return false;
+    const int slot = Bv.dst[b];
+    const SelCtx c = sel_ctx(L, Bv, b, np, slot, Bv.flushed[b] ? slot : Bv.src[b]);
+    const int M = L.M, N = L.N, ld = L.ld;
+    double *const g = Tv.g + (size_t)b * ld;
+    double *const beta = c.beta, *const drow = c.drow, *const row = c.row, *const pc = c.pc;
+    __syncthreads();                           // (everyone has read the LP's state before thread 0 changes it)
+    if (state == TIE_NEW) {
+        // entry: g through the pending pivots, at most ccnt tableau rows
+        for (int j = tid; j < ld; j += NT) {
+            double v = 0.0;
+            if (j < N) {
+                const int kj = c.nh[j] - L.cfirst;
+                if (kj >= 0 && kj < L.ccnt) v = Tv.dir[kj];
+                for (int t = 0; t < L.ccnt; t++) {
+                    const int pr = c.pos[L.cfirst + t];
+                    if (pr >= 0) v = fma(Tv.dir[t], virt_entry(c.T0[(size_t)pr * ld + j], pr, j, np, c.pd, c.prow0, c.pcol0, ld, L.Mp1p), v);
+                }
+            }
+            g[j] = v;
+        }
+        if (tid == 0) { Tv.state[b] = TIE_RUN; Bv.status[b] = ST_RUNNING; atomicAdd(&Tv.stat[0], 1); }
+        __syncthreads();
+    }
+    const bool bland = titer >= PRIMAL_STALL;
+    // the entering column: the wrong tied column with the largest rate
+    ValIdx ent{0.0, -1};
+    for (int j = tid; j < N; j += NT) {
+        const int st = c.nstat[j];
+        if (st == NS_S || fabs(drow[j]) > TOL_DJ) continue;
+        const double v = g[j], tol = TOL_DJ * (1.0 + fabs(v));
+        double sc = 0.0;
+        if (st == NS_L) { if (v < -tol) sc = -v; }
+        else if (st == NS_U) { if (v > tol) sc = v; }
+        else if (fabs(v) > tol) sc = fabs(v);
+        if (sc > 0.0) ent = better_max(ent, ValIdx{bland ? (double)(M + N - c.nh[j]) : sc, j});
+    }
+    ent = block_argmax(ent, sv, si);
+    if (ent.i < 0) { tie_obj_finish(Bv, Tv, b, -1); return false; }      // the point is canonical
+    if (titer >= Tv.cap) { tie_obj_finish(Bv, Tv, b, 3); return false; }
+    const int q = ent.i;
+    const int stq = c.nstat[q], kq = c.nh[q];
+    const double gq = g[q], dq = drow[q];
+    const double dir = (stq == NS_U || (stq == NS_F && gq > 0.0)) ? -1.0 : 1.0;
+    fetch_col<true>(L, c, q);
+    // primal_step's ratio test (phase 2), on the entering column
+    double cmax = 0.0;
+    for (int i = tid; i < M; i += NT) cmax = fmax(cmax, fabs(pc[i]));
+    cmax = block_max(cmax, sv);
+    const double ptol = TOL_PIV * (1.0 + cmax);
+    const double gap = UP(L, Bv, b, kq) - LO(L, Bv, b, kq);     // inf unless both bounds are finite
+    double tmax = gap;
+    for (int i = tid; i < M; i += NT) {
+        const double a = pc[i] * dir;
+        if (fabs(a) < ptol) continue;
+        const int k = c.bh[i];
+        const double bt = beta[i];
+        if (a > 0) { const double up = UP(L, Bv, b, k); if (!isinf(up)) tmax = fmin(tmax, fmax(up + (bland ? 0.0 : btol(up)) - bt, 0.0) / a); }
+        else { const double lo = LO(L, Bv, b, k); if (!isinf(lo)) tmax = fmin(tmax, fmax(bt - lo + (bland ? 0.0 : btol(lo)), 0.0) / -a); }
+    }
+    tmax = block_min(tmax, sv);
+    if (isinf(tmax)) { tie_obj_finish(Bv, Tv, b, 2); return false; }     // no blocking row: ddir . x is unbounded on the optimal face
+    ValIdx lv{0.0, -1};
+    for (int i = tid; i < M; i += NT) {
+        const double a = pc[i] * dir;
+        if (fabs(a) < ptol) continue;
+        const int k = c.bh[i];
+        const double bt = beta[i];
+        if (a > 0) { const double up = UP(L, Bv, b, k); if (!isinf(up) && (up - bt) / a <= tmax) lv = better_max(lv, ValIdx{bland ? (double)(M + N - k) : a, 2 * i + 1}); }
+        else { const double lo = LO(L, Bv, b, k); if (!isinf(lo) && (bt - lo) / -a <= tmax) lv = better_max(lv, ValIdx{bland ? (double)(M + N - k) : -a, 2 * i}); }
+    }
+    lv = block_argmax(lv, sv, si);
+    double tstep = INFINITY;
+    if (lv.i >= 0) {
+        const int i = lv.i >> 1, k = c.bh[i];
+        tstep = fmax(((lv.i & 1) ? UP(L, Bv, b, k) - beta[i] : beta[i] - LO(L, Bv, b, k)) / fabs(pc[i] * dir), 0.0);
+    }
+    if (lv.i < 0 || gap <= tstep) {
+        // the entering variable reaches its own other bound first: no pivot, g stands as it is
+        __syncthreads();
+        for (int i = tid; i < M; i += NT) beta[i] = fma(pc[i], dir * gap, beta[i]);
+        if (tid == 0) {
+            beta[M] = fma(dq, dir * gap, beta[M]);
+            if (stq == NS_L) { c.nstat[q] = NS_U; c.xN[q] = UP(L, Bv, b, kq); } else { c.nstat[q] = NS_L; c.xN[q] = LO(L, Bv, b, kq); }
+            if (L.trace == b) printf("lp %d it %d tie: column %d (var %d) g %.3e switches bound\n", b, Bv.iters[b], q, kq, gq);
+            Bv.verified[b] &= 2;
+            Bv.iters[b] += 1;
+            Tv.iters[b] = titer + 1;
+            atomicAdd(&Tv.stat[1], 1);
+        }
+        return true;
+    }
+    const int r = lv.i >> 1;
+    const bool below = !(lv.i & 1);          // the leaving variable goes to its lower bound
+    fetch_row<true>(L, Bv, c, r);
+    // the descriptor, the basis heads
+    if (tid == 0) {
+        *p_d = commit_pivot(L, Bv, c, r, q, below, bland, Bv.iters[b], Bv.verified[b], MODE_PIVOT, g, true, 0, false);
+        Tv.iters[b] = titer + 1;
+        atomicAdd(&Tv.stat[1], 1);
+    }
+    __syncthreads();
+    const PivDesc d = *p_d;
+    // the multipliers of all rows, beta; the reduced-cost row and g follow the pivot (select_once, Phase D)
+    for (int i = tid; i <= M; i += NT) {
+        if (i == r) { pc[i] = 0.0; beta[i] = d.enter_val; continue; }
+        const double f = (i == M ? dq : pc[i]) * d.p;
+        pc[i] = f;
+        beta[i] = fma(-f, d.pbeta, beta[i]);
+    }
+    __syncthreads();
+    {
+        const double fM = pc[M], fG = gq * d.p;
+        for (int j = tid; j < N; j += NT) {
+            const double rj = row[j];
+            drow[j] = j == q ? fM : fma(-fM, rj, drow[j]);
+            g[j] = j == q ? fG : fma(-fG, rj, g[j]);
+        }
+    }
+    if (tid == 0) Bv.npend[b] = np + 1;
+    return true;
+}
+// Launched only while the switch is on (tableau form, objective batches), with the workgroup size of the batch's selections
+__global__ __launch_bounds__(NT_BIG) void k_select_tie_obj(LpView L, BatchView Bv, TieObjView Tv, const int *active, int nact, int nsel)
+{
+    __shared__ double sv[NT_BIG / WAVE];
+    __shared__ int si[NT_BIG / WAVE];
+    __shared__ PivDesc s_d;
+    if ((int)blockIdx.x >= nact) return;
+    const int b = active[blockIdx.x];
+    for (int sdx = 0; sdx < nsel; sdx++) {
+        if (sdx) __syncthreads();
+        if (!tie_obj_once(L, Bv, Tv, b, sv, si, &s_d)) break;
+    }
+}
+
 // ---- which LPs need a pass over their tableau: pending pivots to apply, or beta to recompute ----
 __global__ void k_list_pending(BatchView Bv, const int *active, int nact, int it)
 {
@@ -2350,6 +2528,13 @@ struct bslv_lpq {
     std::vector<double> canon_dir;
     double *tdir_d = nullptr, *tg_d = nullptr; int *tstate_d = nullptr, *titers_d = nullptr, *tstat_d = nullptr; int tie_Bcap = 0;
     long last_canon[4] = {0, 0, 0, 0};
+    // tie phase of objective batches (bslv_lpq_set_canonical_obj): the switch, the cost range it was set for (indices of the model as given)
+    // and ddir, per-LP state of a batch, the counters of the last objective batch
+    bool canon_obj = false;
+    int cobj_first = 0, cobj_cnt = 0;
+    std::vector<double> cobj_dir;
+    double *odir_d = nullptr, *og_d = nullptr; int *ostate_d = nullptr, *oiters_d = nullptr, *ostat_d = nullptr; int tie_obj_Bcap = 0; size_t odir_cap = 0;
+    long last_canon_obj[4] = {0, 0, 0, 0};
     // refactorisation of the revised form (bslv_lpq_refactor, bslv_lpq_set_refactor): the switch, the marks of the last batch (device / host),
     // the replay's per-LP lists, the counters of the last solve call or explicit refactor
     bool refactor_on = false;
@@ -2673,7 +2858,7 @@ void bslv_lpq_destroy(bslv_lpq *h)
     fr(h->Tstd); fr(h->lb_d); fr(h->ub_d); fr(h->art_d);
     fr(h->dbg_d); fr(h->list_d); fr(h->cptr_d); fr(h->cidx_d); fr(h->rptr_d); fr(h->ridx_d); fr(h->cval_d); fr(h->rval_d); fr(h->cost_d); fr(h->dsl_d); fr(h->trow_d); fr(h->uvec_d); fr(h->xfull_d); fr(h->hmail_d);
     fr(h->src_d); fr(h->dst_d); fr(h->status_d); fr(h->iters_d); fr(h->mode_d); fr(h->ver_d); fr(h->qslot_d); fr(h->init_d);
-    fr(h->tdir_d); fr(h->tg_d); fr(h->tstate_d); fr(h->titers_d); fr(h->tstat_d); fr(h->rmark_d); fr(h->rfx_i_d); fr(h->rfx_c_d);
+    fr(h->tdir_d); fr(h->tg_d); fr(h->tstate_d); fr(h->titers_d); fr(h->tstat_d); fr(h->odir_d); fr(h->og_d); fr(h->ostate_d); fr(h->oiters_d); fr(h->ostat_d); fr(h->rmark_d); fr(h->rfx_i_d); fr(h->rfx_c_d);
     fr(h->vlo_d); fr(h->vup_d); fr(h->prow_d); fr(h->desc_d); fr(h->out_d); fr(h->active_d); fr(h->work_d); fr(h->nwork_d); fr(h->npend_d); fr(h->pcol_d); fr(h->dcur_d); fr(h->dper_d); fr(h->pflags_d); fr(h->stall_d); fr(h->xstat_d); fr(h->cvals_d);
     if (h->status_h) (void)hipHostFree(h->status_h);
     if (h->active_h) (void)hipHostFree(h->active_h);
@@ -3222,6 +3407,20 @@ static int ensure_tie(bslv_lpq *h)
     h->tie_Bcap = h->Bcap;
     return 0;
 }
+// ... and of the tie phase of an objective batch (g: ld doubles per LP)
+static int ensure_tie_obj(bslv_lpq *h)
+{
+    if (h->tie_obj_Bcap >= h->Bcap && h->og_d) return 0;
+    auto fr = [](auto *&p) { if (p) (void)hipFree(p); p = nullptr; };
+    fr(h->og_d); fr(h->ostate_d); fr(h->oiters_d);
+    h->tie_obj_Bcap = 0;
+    HIP_TRY(malloc0s(&h->og_d, (size_t)h->Bcap * h->L.ld * sizeof(double), h->stream));
+    HIP_TRY(malloc0s(&h->ostate_d, (size_t)h->Bcap * sizeof(int), h->stream));
+    HIP_TRY(malloc0s(&h->oiters_d, (size_t)h->Bcap * sizeof(int), h->stream));
+    if (!h->ostat_d) HIP_TRY(malloc0s(&h->ostat_d, 4 * sizeof(int), h->stream));
+    h->tie_obj_Bcap = h->Bcap;
+    return 0;
+}
 // host wall clock of the calls an apply() makes for its tableaux (bslv_lpq_materialise, bslv_lpq_park): lazy_stats[2]
 struct LazyClock { bslv_lpq *h; std::chrono::steady_clock::time_point t; ~LazyClock() { h->lazy_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); } };
 int bslv_lpq_set_lazy(bslv_lpq *h, int on)
@@ -3344,6 +3543,7 @@ int bslv_lpq_solve_batch_obj(bslv_lpq *h, int B, const int *src, const int *dst,
                              int cost_first, int cost_cnt, const double *costs, int *status, int *iters)
 {
     if (!h || cost_cnt < 1 || cost_first < 0 || cost_first + cost_cnt > h->ps.M0 + h->ps.N0 || !costs) { set_error("bslv_lpq_solve_batch_obj: bad argument"); return BSLV_E_ARG; }
+    if (h->canon_obj && (cost_first != h->cobj_first || cost_cnt != h->cobj_cnt)) { set_error("bslv_lpq_solve_batch_obj: the cost range (%d, %d) is not the one bslv_lpq_set_canonical_obj was set for (%d, %d)", cost_first, cost_cnt, h->cobj_first, h->cobj_cnt); return BSLV_E_ARG; }
     if (h->ps.nfold) {      // indices of the model as given -> the engine's (a cost on a folded row would be a cost on its column: not asked for by any caller)
         for (int t = 0; t < cost_cnt; t++) if (h->ps.map_var(cost_first + t) != h->ps.map_var(cost_first) + t) { set_error("bslv_lpq_solve_batch_obj: the cost range covers rows the presolve folded into column bounds"); return BSLV_E_ARG; }
         cost_first = h->ps.map_var(cost_first);
@@ -3367,6 +3567,7 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
         h->last_iters = 0; h->last_pivots = 0; h->last_passes = 0; h->last_launches = 0;
         for (int k = 0; k < 3; k++) h->last_p1[k] = 0;
         for (int k = 0; k < 4; k++) h->last_canon[k] = 0;
+        if (cvals) for (int k = 0; k < 4; k++) h->last_canon_obj[k] = 0;
         return 0;
     }
     if (!h || B < 0 || (B > 0 && (!src || !dst)) || (B > 0 && h->L.vcnt > 0 && (!vlo || !vup))) {
@@ -3410,7 +3611,7 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
     }
     if (const char *e = getenv("BSLV_UPD_GRID")) h->upd_grid = std::max(64, atoi(e));
     {   // one work-list length per lock-step iteration, zeroed here: no reset between iterations
-        const int need = L.maxit + 64 + (h->canonical ? tie_rounds_max(L) : 0);      // (the rounds of a tie phase count on behind the others')
+        const int need = L.maxit + 64 + ((h->canonical || h->canon_obj) ? tie_rounds_max(L) : 0);      // (the rounds of a tie phase count on behind the others')
         if (need > h->nworkcap) { if (h->nwork_d) (void)hipFree(h->nwork_d); h->nwork_d = nullptr; HIP_TRY(malloc0s(&h->nwork_d, need * sizeof(int), s)); h->nworkcap = need; }
         HIP_TRY(hipMemsetAsync(h->nwork_d, 0, need * sizeof(int), s));
     }
@@ -3534,18 +3735,16 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
         // max(KP, K) pivots more at the next, so no selection is made on a matrix older than 2 K + KP
         if (period > 0) chunk = std::min(chunk, std::max(1, period / KP));
     }
-    // TIE PHASE (bslv_lpq_set_canonical): the LPs that ended OPTIMAL go on to their canonical basis, in rounds of the same shape --
-    // KP tie pivots on vectors (k_select_tie), one pass.  Their work lists count on from L.maxit + 64.
+    // TIE PHASE (bslv_lpq_set_canonical; objective batches: bslv_lpq_set_canonical_obj): the LPs that ended OPTIMAL go on to their
+    // canonical basis, in rounds of the same shape -- KP tie pivots on vectors (k_select_tie / k_select_tie_obj), one pass.  Their work
+    // lists count on from L.maxit + 64.
     int tie_rounds = 0;
     const int tie_base = L.maxit + 64;
-    for (int k = 0; k < 4; k++) h->last_canon[k] = 0;
-    if (h->canonical && !L.objmode && !L.rev && L.vcnt > 0 && !max_rounds) {
-        if ((rc = ensure_tie(h))) return rc;
-        TieView tv;
-        tv.dir = h->tdir_d; tv.g = h->tg_d; tv.state = h->tstate_d; tv.iters = h->titers_d; tv.stat = h->tstat_d; tv.cap = tie_cap(L);
-        HIP_TRY(hipMemsetAsync(h->tstate_d, 0, (size_t)B * sizeof(int), s));
-        HIP_TRY(hipMemsetAsync(h->titers_d, 0, (size_t)B * sizeof(int), s));
-        HIP_TRY(hipMemsetAsync(h->tstat_d, 0, 4 * sizeof(int), s));
+    // the rounds of a tie phase: launch(nt) selects for the nt LPs of the active list; state_d, iters_d, stat_d: the phase's per-LP state and counters
+    auto tie_phase = [&](int *state_d, int *iters_d, int *stat_d, auto launch, long out[4]) -> int {
+        HIP_TRY(hipMemsetAsync(state_d, 0, (size_t)B * sizeof(int), s));
+        HIP_TRY(hipMemsetAsync(iters_d, 0, (size_t)B * sizeof(int), s));
+        HIP_TRY(hipMemsetAsync(stat_d, 0, 4 * sizeof(int), s));
         int nt = 0;
         for (int b = 0; b < B; b++) if (h->status_h[b] == BSLV_LP_OPTIMAL) h->active_h[nt++] = b;
         if (nt) HIP_TRY(hipMemcpyAsync(h->active_d, h->active_h, nt * sizeof(int), hipMemcpyHostToDevice, s));
@@ -3554,11 +3753,11 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
         int tchunk = 1;
         while (nt > 0 && tie_rounds < rounds_max) {
             for (int c = 0; c < tchunk && tie_rounds < rounds_max; c++, tie_rounds++) {
-                hipLaunchKernelGGL(k_select_tie, dim3(nt), dim3(plan.nt), 0, s, L, bv, tv, h->active_d, nt, KP);
+                launch(nt);
                 if ((rc = pass_round(nt, tie_base + tie_rounds))) return rc;
             }
             HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpyAsync(tstate.data(), h->tstate_d, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipMemcpyAsync(tstate.data(), state_d, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, s));
             HIP_TRY(hipStreamSynchronize(s));
             int left = 0;
             for (int k = 0; k < nt; k++) { const int b = h->active_h[k]; if (tstate[b] != TIE_DONE) h->active_h[left++] = b; }
@@ -3568,11 +3767,28 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
         }
         HIP_TRY(hipMemcpyAsync(h->status_h, h->status_d, B * sizeof(int), hipMemcpyDeviceToHost, s));
         int ts[4];
-        HIP_TRY(hipMemcpyAsync(ts, h->tstat_d, sizeof ts, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(ts, stat_d, sizeof ts, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
-        for (int k = 0; k < 4; k++) h->last_canon[k] = ts[k];
+        for (int k = 0; k < 4; k++) out[k] = ts[k];
         // (the cap on the pivots of an LP ends every phase long before the rounds run out; an LP still in it would keep the basis reached)
-        for (int k = 0; k < nt; k++) { const int b = h->active_h[k]; if (h->status_h[b] == ST_RUNNING) { h->status_h[b] = BSLV_LP_OPTIMAL; h->last_canon[3]++; HIP_TRY(hipMemcpy(h->status_d + b, h->status_h + b, sizeof(int), hipMemcpyHostToDevice)); } }
+        for (int k = 0; k < nt; k++) { const int b = h->active_h[k]; if (h->status_h[b] == ST_RUNNING) { h->status_h[b] = BSLV_LP_OPTIMAL; out[3]++; HIP_TRY(hipMemcpy(h->status_d + b, h->status_h + b, sizeof(int), hipMemcpyHostToDevice)); } }
+        return 0;
+    };
+    for (int k = 0; k < 4; k++) h->last_canon[k] = 0;
+    if (L.objmode) for (int k = 0; k < 4; k++) h->last_canon_obj[k] = 0;
+    if (h->canonical && !L.objmode && !L.rev && L.vcnt > 0 && !max_rounds) {
+        if ((rc = ensure_tie(h))) return rc;
+        TieView tv;
+        tv.dir = h->tdir_d; tv.g = h->tg_d; tv.state = h->tstate_d; tv.iters = h->titers_d; tv.stat = h->tstat_d; tv.cap = tie_cap(L);
+        auto launch = [&](int nt) { hipLaunchKernelGGL(k_select_tie, dim3(nt), dim3(plan.nt), 0, s, L, bv, tv, h->active_d, nt, KP); };
+        if ((rc = tie_phase(tv.state, tv.iters, tv.stat, launch, h->last_canon))) return rc;
+    }
+    if (h->canon_obj && L.objmode && !L.rev && !max_rounds) {
+        if ((rc = ensure_tie_obj(h))) return rc;
+        TieObjView tv;
+        tv.dir = h->odir_d; tv.g = h->og_d; tv.state = h->ostate_d; tv.iters = h->oiters_d; tv.stat = h->ostat_d; tv.cap = tie_cap(L);
+        auto launch = [&](int nt) { hipLaunchKernelGGL(k_select_tie_obj, dim3(nt), dim3(plan.nt), 0, s, L, bv, tv, h->active_d, nt, KP); };
+        if ((rc = tie_phase(tv.state, tv.iters, tv.stat, launch, h->last_canon_obj))) return rc;
     }
     {   // tableau passes of this batch: sum of the work-list lengths of the rounds
         std::vector<int> nw(std::max(it, 1), 0);
@@ -4072,6 +4288,34 @@ int bslv_lpq_last_canonical_stats(const bslv_lpq *h, long out[4])
 {
     if (!h || !out) return BSLV_E_ARG;
     for (int k = 0; k < 4; k++) out[k] = h->last_canon[k];
+    return 0;
+}
+// The canonical optimal point (tie phase of objective batches) for every later solve_batch_obj: see bslv_hip.h; the dual variant's cut is built from this point (bslv_algs.c:1479-1486)
+int bslv_lpq_set_canonical_obj(bslv_lpq *h, int on, int cost_first, int cost_cnt, const double *ddir)
+{
+    if (!h || (on && !ddir)) { set_error("bslv_lpq_set_canonical_obj: bad argument"); return BSLV_E_ARG; }
+    if (!on) { h->canon_obj = false; return 0; }
+    if (h->L.rev) { set_error("bslv_lpq_set_canonical_obj: the revised form has no tie phase for objective batches (the canonical point is the tableau form's)"); return BSLV_E_ARG; }
+    if (cost_cnt < 1 || cost_first < 0 || cost_first + cost_cnt > h->ps.M0 + h->ps.N0) { set_error("bslv_lpq_set_canonical_obj: bad cost range (%d, %d)", cost_first, cost_cnt); return BSLV_E_ARG; }
+    for (int j = 0; j < cost_cnt; j++) if (!std::isfinite(ddir[j])) { set_error("bslv_lpq_set_canonical_obj: ddir[%d] is not finite", j); return BSLV_E_ARG; }
+    if ((size_t)cost_cnt > h->odir_cap) {
+        if (h->odir_d) (void)hipFree(h->odir_d);
+        h->odir_d = nullptr; h->odir_cap = 0;
+        HIP_TRY(malloc0(&h->odir_d, (size_t)cost_cnt * sizeof(double)));
+        h->odir_cap = (size_t)cost_cnt;
+    }
+    h->cobj_dir.assign(ddir, ddir + cost_cnt);
+    HIP_TRY(hipMemcpyAsync(h->odir_d, h->cobj_dir.data(), (size_t)cost_cnt * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    h->cobj_first = cost_first; h->cobj_cnt = cost_cnt;
+    h->canon_obj = true;
+    return 0;
+}
+int bslv_lpq_get_canonical_obj(const bslv_lpq *h) { return h && h->canon_obj; }
+int bslv_lpq_last_canonical_obj_stats(const bslv_lpq *h, long out[4])
+{
+    if (!h || !out) return BSLV_E_ARG;
+    for (int k = 0; k < 4; k++) out[k] = h->last_canon_obj[k];
     return 0;
 }
 int bslv_lpq_last_ext_stats(const bslv_lpq *h, long out[4])

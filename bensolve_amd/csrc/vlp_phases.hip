@@ -309,8 +309,10 @@ struct DualPreimg {
 static std::mutex g_dpre_mu;
 static std::unordered_map<const bslv_poly *, DualPreimg *> g_dpre;
 
+// canonical: the P1(w) LPs end in their canonical optimal point (bslv_lpq_set_canonical_obj; hom == 0 only); cstats: its four counters, summed
+static thread_local long g_canon_obj[4] = {0, 0, 0, 0};      // of phase 2 of this thread's last bslv_vlp_solve_dual2
 static int dual_benson(const Problem &pb, const Sol &S, int hom, double eps, int batch, bslv_poly **poly_out, int *status, long *lps, long *steps,
-                       DualPreimg *store = nullptr)
+                       DualPreimg *store = nullptr, bool canonical = false, long *cstats = nullptr)
 {
     *status = 0; *poly_out = nullptr;
     const int m = pb.m, n = pb.n, q = pb.q, M = m + q + (hom ? 1 : 0), N = n + q;
@@ -346,10 +348,19 @@ static int dual_benson(const Problem &pb, const Sol &S, int hom, double eps, int
     if ((rc = bslv_lpq_solve_batch(lp, 1, &zero, &zero, nullptr, nullptr, &st, &it))) return done(rc);
     if (st == BSLV_LP_INFEASIBLE) { *status = 1; bslv_poly_destroy(poly); poly = nullptr; return done(0); }
     if (st != BSLV_LP_OPTIMAL) { set_error("phase 2 (dual): the feasibility LP has status %d", st); return done(BSLV_E_STATE); }
+    auto count_canonical = [&]() { long cs[4]; if (cstats && bslv_lpq_last_canonical_obj_stats(lp, cs) == 0) for (int k = 0; k < 4; k++) cstats[k] += cs[k]; };
+    if (canonical && !hom) {
+        // canonical optimal points: ddir = sum_j (1 + hash01(j)) R_j, a generic interior point of the cone the weights live in -- ddir . y is
+        // bounded below on every optimal face (the default cone: ddir_k = 1 + hash01(k), the primal driver's direction)
+        std::vector<double> ddir(q, 0.0);
+        for (int i = 0; i < q; i++) for (int j = 0; j < S.r; j++) ddir[i] += (1.0 + hash01(j)) * S.R[(size_t)i * S.r + j];
+        if ((rc = bslv_lpq_set_canonical_obj(lp, 1, M + n, q, ddir.data()))) return done(rc);      // (the revised form: the LP engine's message, no fallback)
+    }
     // ... then PART 1 (:1397-1443): w = mean of the columns of R
     std::vector<double> w(q, 0.0), y(q), val(q);
     for (int i = 0; i < q; i++) { for (int j = 0; j < nw0; j++) w[i] += W0[(size_t)i * nw0 + j]; w[i] /= nw0; }
     if ((rc = bslv_lpq_solve_batch_obj(lp, 1, &zero, &zero, nullptr, nullptr, M + n, q, w.data(), &st, &it))) return done(rc);
+    count_canonical();
     if (st != BSLV_LP_OPTIMAL) { *status = st == BSLV_LP_INFEASIBLE ? 1 : 2; bslv_poly_destroy(poly); poly = nullptr; return done(0); }
     ++*lps;
     if ((rc = bslv_lpq_get_primal(lp, 1, &zero, M + n, q, y.data()))) return done(rc);
@@ -426,6 +437,7 @@ static int dual_benson(const Problem &pb, const Sol &S, int hom, double eps, int
         }
         if (np > 0) {
             if ((rc = bslv_lpq_solve_batch_obj(lp, np, src.data(), dst.data(), nullptr, nullptr, M + n, q, W.data(), stv.data(), itv.data()))) return done(rc);
+            count_canonical();
             {   // an LP given up (UNDEFINED: in the revised form the pivot cross-check found B^-1 drifted; nothing refactorises it) is solved
                 // once more from slot 0, the first optimal basis -- primal feasible, as every optimal slot -- as the reference retries lp_solve
                 // from the standard basis (bslv_lp.c:222-227)
@@ -437,6 +449,7 @@ static int dual_benson(const Problem &pb, const Sol &S, int hom, double eps, int
                 if (nr > 0) {
                     rst.resize(nr); rit.resize(nr);
                     if ((rc = bslv_lpq_solve_batch_obj(lp, nr, rsrc.data(), rdst.data(), nullptr, nullptr, M + n, q, rW.data(), rst.data(), rit.data()))) return done(rc);
+                    count_canonical();
                     for (int k = 0; k < nr; k++) { stv[rt[k]] = rst[k]; itv[rt[k]] += rit[k]; }
                 }
             }
@@ -498,9 +511,9 @@ static int dual_benson(const Problem &pb, const Sol &S, int hom, double eps, int
     return done(0);
 }
 
-static int phase2_dual(const Problem &pb, const Sol &S, double eps, int batch, bslv_poly **poly_out, int *status, long *lps, long *steps, DualPreimg *store = nullptr)
+static int phase2_dual(const Problem &pb, const Sol &S, double eps, int batch, bslv_poly **poly_out, int *status, long *lps, long *steps, DualPreimg *store = nullptr, bool canonical = false)
 {
-    return dual_benson(pb, S, 0, eps, batch, poly_out, status, lps, steps, store);
+    return dual_benson(pb, S, 0, eps, batch, poly_out, status, lps, steps, store, canonical, g_canon_obj);
 }
 
 // ---- phase 1, dual algorithm (bslv_algs.c:1248-1371): the dual variant on the homogeneous problem; R from the vertices of
@@ -698,6 +711,8 @@ int bslv_vlp_solve_dual2(int m, int n, int q, const double *A, const double *P,
         return BSLV_E_ARG;
     }
     *lower_image_out = nullptr;
+    for (int k = 0; k < 4; k++) g_canon_obj[k] = 0;
+    if (const char *e = getenv("BSLV_CANONICAL_OBJ")) if (atoi(e) != 0) flags |= BSLV_VLP_CANONICAL;
     Sol S;
     std::vector<double> Pn;
     long lps = 0, steps = 0;
@@ -710,7 +725,7 @@ int bslv_vlp_solve_dual2(int m, int n, int q, const double *A, const double *P,
     bslv_poly *poly = nullptr;
     DualPreimg *store = (flags & BSLV_VLP_PREIMAGES) ? new DualPreimg() : nullptr;
     if (store) { store->m = m; store->n = n; store->q = q; }
-    if ((rc = phase2_dual(pb, S, eps_benson_phase2, batch, &poly, &vst, &lps, &steps, store))) { delete store; return rc; }
+    if ((rc = phase2_dual(pb, S, eps_benson_phase2, batch, &poly, &vst, &lps, &steps, store, (flags & BSLV_VLP_CANONICAL) != 0))) { delete store; return rc; }
     if (vst) { delete store; *vlp_status = vst; phase2_failure(info, vst, bounded, lps); return 0; }
     if (store) {
         // pre-images of the extreme DIRECTIONS of the upper image (dual slots that are directions; bslv_algs.c:1508-1535): x of
@@ -748,6 +763,13 @@ int bslv_vlp_solve_dual2(int m, int n, int q, const double *A, const double *P,
     *lower_image_out = poly;
     *vlp_status = 4;
     fill_info(info, S, optdir, lps, steps);
+    return 0;
+}
+
+int bslv_vlp_last_canonical_obj_stats(long out[4])
+{
+    if (!out) return BSLV_E_ARG;
+    for (int k = 0; k < 4; k++) out[k] = g_canon_obj[k];
     return 0;
 }
 

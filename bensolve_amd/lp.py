@@ -238,6 +238,27 @@ class LpEngine:
         check(self.lib.bslv_lpq_last_canonical_stats(self.h, o))
         return dict(entered=int(o[0]), tie_pivots=int(o[1]), no_candidate=int(o[2]), capped=int(o[3]))
 
+    def set_canonical_obj(self, on, cost_first=None, ddir=None):
+        """canonical optimal points for every later solve_batch_obj over the cost range cost_first .. cost_first + len(ddir) - 1:
+        the solution that stays optimal for the costs c + t * ddir for small t > 0, found by a tie phase after optimality
+        (bslv_lpq_set_canonical_obj, include/bslv_hip.h).  Returns the library's code (0, or BSLV_E_ARG for the revised form, a
+        bad range, a missing or non-finite direction)."""
+        self.lib.bslv_lpq_set_canonical_obj.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
+        d = None if ddir is None else np.ascontiguousarray(ddir, np.float64).reshape(-1)
+        return int(self.lib.bslv_lpq_set_canonical_obj(self.h, int(bool(on)), 0 if cost_first is None else int(cost_first),
+                                                       0 if d is None else len(d), None if d is None else d.ctypes.data))
+
+    def get_canonical_obj(self):
+        self.lib.bslv_lpq_get_canonical_obj.argtypes = [ctypes.c_void_p]
+        return int(self.lib.bslv_lpq_get_canonical_obj(self.h))
+
+    def last_canonical_obj_stats(self):
+        """tie phase of the last solve_batch_obj (bslv_lpq_last_canonical_obj_stats)"""
+        o = (ctypes.c_long * 4)()
+        self.lib.bslv_lpq_last_canonical_obj_stats.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        check(self.lib.bslv_lpq_last_canonical_obj_stats(self.h, o))
+        return dict(entered=int(o[0]), tie_iters=int(o[1]), unbounded=int(o[2]), capped=int(o[3]))
+
     def refactor(self, slots):
         """revised form: rebuild the basis inverse of the slots in place from their heads (bslv_lpq_refactor); returns the
         per-slot statuses (0, or 3 = UNDEFINED for a singular basis: the slot is then reset to the standard basis)"""

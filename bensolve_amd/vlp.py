@@ -37,10 +37,12 @@ def cone_vertenum(gen):
 
 
 def solve_primal(prob, cone_kind=0, gen=None, c=None, bounded=False, eps_phase0=1e-8, eps_phase1=1e-8, eps_benson_phase1=1e-7,
-                 eps_benson_phase2=1e-7, batch=256, alg_phase2="primal", alg_phase1="primal", preimages=False):
+                 eps_benson_phase2=1e-7, batch=256, alg_phase2="primal", alg_phase1="primal", preimages=False, canonical=False):
     """prob: dict as bensolve_amd.synth builds them (P as in the file: not negated).  Returns dict(status, message, info...,
     dump = slot-indexed dump of the result polyhedron with the sign changes of poly_trans_primal applied).  alg_phase2 = "dual":
-    phase2_dual; the dump is then given with the sides swapped back, so that X / pi are the upper image in both cases."""
+    phase2_dual; the dump is then given with the sides swapped back, so that X / pi are the upper image in both cases.
+    canonical (with alg_phase2 = "dual"): every P1(w) ends in its canonical optimal point (BSLV_VLP_CANONICAL, include/bslv_hip.h);
+    out["canonical_obj"] then holds the tie phase's counters summed over phase 2 (all zero with the flag off)."""
     dual2 = alg_phase2 == "dual"
     lib = load_library()
     vp = ctypes.c_void_p
@@ -59,10 +61,16 @@ def solve_primal(prob, cone_kind=0, gen=None, c=None, bounded=False, eps_phase0=
     check((lib.bslv_vlp_solve_dual2 if dual2 else lib.bslv_vlp_solve_primal)(prob["m"], prob["n"], prob["q"], A.ctypes.data, P.ctypes.data, rt.ctypes.data, arrs[0].ctypes.data, arrs[1].ctypes.data,
                                     ct.ctypes.data, arrs[2].ctypes.data, arrs[3].ctypes.data, int(prob.get("optdir", 1)), cone_kind,
                                     None if g is None else g.ctypes.data, 0 if g is None else g.shape[1], None if cc is None else cc.ctypes.data,
-                                    int(bounded), (1 if alg_phase1 == "dual" else 0) | (2 if preimages else 0), eps_phase0, eps_phase1, eps_benson_phase1, eps_benson_phase2, batch,
+                                    int(bounded), (1 if alg_phase1 == "dual" else 0) | (2 if preimages else 0) | (4 if (canonical and dual2) else 0), eps_phase0, eps_phase1, eps_benson_phase1, eps_benson_phase2, batch,
                                     ctypes.byref(h), ctypes.byref(st), ctypes.byref(info)))
     q = prob["q"]
     out = dict(status=STATUS.get(st.value, st.value), message=info.message.decode(), lps=info.lps, steps=info.steps, c_dir=info.c_dir)
+
+    if dual2:
+        cs = (ctypes.c_long * 4)()
+        lib.bslv_vlp_last_canonical_obj_stats.argtypes = [vp]
+        check(lib.bslv_vlp_last_canonical_obj_stats(cs))
+        out["canonical_obj"] = dict(entered=int(cs[0]), tie_iters=int(cs[1]), unbounded=int(cs[2]), capped=int(cs[3]))
 
     def mat(ptr, k):
         return np.ctypeslib.as_array(ptr, shape=(q * k,)).reshape(q, k).copy() if ptr and k > 0 else None

@@ -258,13 +258,36 @@ int  bslv_lpq_last_phase1_stats(const bslv_lpq *h, long out[3]);
  * OPTIMAL goes on into a TIE PHASE -- dual simplex pivots of length zero among the rows that sit on a bound, chosen by the derivative
  * of the basic values with respect to t (lp_engine.hip, k_select_tie) -- when the rounds of its batch are over.  The phase keeps the
  * status OPTIMAL however it ends; its pivots are counted in iters[].  Works with every method and with the extended selection on or
- * off (it does not need it); objective batches (solve_batch_obj) ignore the switch; the revised form answers BSLV_E_ARG.  With on = 0
+ * off (it does not need it); objective batches (solve_batch_obj) ignore this switch -- theirs is bslv_lpq_set_canonical_obj, below, and
+ * the two are independent; the revised form answers BSLV_E_ARG.  With on = 0
  * (dir may be NULL) the engine computes what it always did.
  * bslv_lpq_last_canonical_stats, of the last solve_batch: [0] LPs that entered the tie phase (all that ended OPTIMAL), [1] tie pivots,
  * [2] LPs whose phase ended without an entering candidate (the shifted LP is infeasible for t > 0), [3] LPs that gave up at the cap. */
 int  bslv_lpq_set_canonical(bslv_lpq *h, int on, const double *dir /* var_cnt, NULL with on = 0 */);
 int  bslv_lpq_get_canonical(const bslv_lpq *h);
 int  bslv_lpq_last_canonical_stats(const bslv_lpq *h, long out[4]);
+/* CANONICAL OPTIMAL POINTS of objective batches.  The dual variant builds the cut of the lower image from the optimal point y = P x of
+ * P1(w) (phase2_dual takes it from lp_primal_solution_cols, bslv_algs.c:1479-1486).  Where w is the normal of a face of the upper
+ * image of dimension >= 1 the LP is dual degenerate: every y of that face is optimal and the pivoting ends in P x of whichever vertex x
+ * of the feasible set it reached, which need not be a vertex of the image.  With on != 0 every later solve_batch_obj over the cost
+ * range (cost_first, cost_cnt) ends in the CANONICAL optimal solution instead: the one that stays optimal for the costs c + t ddir
+ * (ddir: cost_cnt values, one per variable of the cost range) for all small enough t > 0, i.e. the lexicographic minimum of
+ * (c . x, ddir . x).  No t is ever formed: an LP that ends OPTIMAL goes on into a tie phase when the rounds of its batch are over --
+ * primal simplex steps among the nonbasic columns whose reduced cost is zero (|d_j| <= 1e-9), chosen by g, the reduced-cost row of
+ * ddir, which the engine keeps per LP and updates with every pivot (lp_engine.hip, k_select_tie_obj).  Unlike the steps of
+ * bslv_lpq_set_canonical these have a length: x moves along the optimal face, the objective by at most 1e-9 x step.  The phase keeps
+ * the status OPTIMAL however it ends -- no wrong tied column (canonical), an entering column without a blocking row (ddir . x is
+ * unbounded on the optimal face: the basis reached stays), or the cap of 1000 + 2 (M + N) iterations; its iterations are counted in
+ * iters[].  A solve_batch_obj with another cost range answers BSLV_E_ARG while the switch is on; solve_batch ignores the switch; it
+ * is independent of bslv_lpq_set_canonical.  A non-finite ddir, a bad range or on with ddir == NULL is BSLV_E_ARG, and so is on for an
+ * engine in the revised form (its tie phase needs g from B^-1: not built).  With on = 0 the engine computes what it always did, bit
+ * for bit.
+ * bslv_lpq_last_canonical_obj_stats, of the last solve_batch_obj: [0] LPs that entered the phase (all that ended OPTIMAL), [1] tie
+ * iterations (pivots + bound switches), [2] LPs that ended on a column without a blocking row, [3] LPs that gave up at the cap; all
+ * zero after a batch with the switch off. */
+int  bslv_lpq_set_canonical_obj(bslv_lpq *h, int on, int cost_first, int cost_cnt, const double *ddir /* cost_cnt; NULL with on = 0 */);
+int  bslv_lpq_get_canonical_obj(const bslv_lpq *h);
+int  bslv_lpq_last_canonical_obj_stats(const bslv_lpq *h, long out[4]);
 
 /* ------------------------------------------------------------------------------------------
  * 2. Polyhedron engine  (replaces bslv_poly.h:90-118)
@@ -417,7 +440,7 @@ int  bslv_benson_unprocessed_left(const bslv_benson *h);
  * its LP engine (the bound of row j is R_j . v, :1041-1046); the LPs of the retry ladder are solved with it too, the weighted-sum LPs
  * of PART 1 are not.  Off by default; BSLV_CANONICAL_DUAL=1 switches it on when an engine is created.  A homogeneous engine (hom != 0)
  * answers BSLV_E_ARG: its cut (w + alpha eta, alpha) has another normal cone (the environment switch leaves such engines alone).  The
- * dual-variant entry points do not know the switch.  bslv_benson_canonical_stats: the four counts of bslv_lpq_last_canonical_stats
+ * dual-variant entry points do not know this switch; theirs is BSLV_VLP_CANONICAL (bslv_vlp_solve_dual2).  bslv_benson_canonical_stats: the four counts of bslv_lpq_last_canonical_stats
  * summed over the LPs of the last solve_local, retries included (last), and over all of them (total); either may be NULL. */
 int  bslv_benson_set_canonical(bslv_benson *h, int on);
 int  bslv_benson_get_canonical(const bslv_benson *h);
@@ -506,8 +529,14 @@ typedef struct bslv_vlp_info {
 } bslv_vlp_info;
 /* flags: PHASE1_DUAL = "-A dual" (opt->alg_phase1, bslv_main.c:283-296: phase1_dual, bslv_algs.c:1248-1371, instead of
  * phase1_primal); PREIMAGES = "-s" (opt->solution == PRE_IMG_ON; bslv_vlp_solve_primal only): the phase-2 engine keeps the
- * pre-images (BSLV_BENSON_PREIMAGES) and the directions of the upper image get theirs (bslv_algs.c:1083-1112) */
-enum { BSLV_VLP_PHASE1_DUAL = 1, BSLV_VLP_PREIMAGES = 2 };
+ * pre-images (BSLV_BENSON_PREIMAGES) and the directions of the upper image get theirs (bslv_algs.c:1083-1112);
+ * CANONICAL (bslv_vlp_solve_dual2 only; BSLV_CANONICAL_OBJ=1 in the environment sets it there): phase 2 switches
+ * bslv_lpq_set_canonical_obj on for its P1(w) LPs -- PART 1, the batches and their retries -- with ddir = sum_j (1 + hash01(j)) R_j
+ * over the generators R_j of the cone the weights live in (a generic interior point of it, so ddir . y is bounded below on every
+ * optimal face; the default cone: ddir_k = 1 + hash01(k), the direction of bslv_benson_set_canonical): every cut of the lower image is
+ * then built from a VERTEX of the upper image (bslv_algs.c:1479-1486) and is a facet.  The homogeneous engine of phase1_dual is left
+ * alone.  An LP engine that comes up in the revised form makes the call fail with that engine's message. */
+enum { BSLV_VLP_PHASE1_DUAL = 1, BSLV_VLP_PREIMAGES = 2, BSLV_VLP_CANONICAL = 4 };
 /* cone_kind 0 default (R^q_+), 1 `gen` generates C, 2 `gen` generates C* (vlp->cone_gen); c_in: q or NULL (vlp->c).
  * vlp_status (sol->status, bslv_main.h:103): 1 infeasible, 2 unbounded, 3 no vertex, 4 optimal, 5 input error.
  * With status 4 *engine_out is the finished phase-2 engine (bslv_benson_poly(engine) is the result; destroy it). */
@@ -526,6 +555,9 @@ int  bslv_vlp_solve_dual2(int m, int n, int q, const double *A, const double *P,
                           int optdir, int cone_kind, const double *gen, int n_gen, const double *c_in,
                           int bounded, int flags, double eps_phase0, double eps_phase1, double eps_benson_phase1, double eps_benson_phase2,
                           int batch, bslv_poly **lower_image_out, int *vlp_status, bslv_vlp_info *info /* may be NULL */);
+/* the four counters of bslv_lpq_last_canonical_obj_stats summed over the objective solves of phase 2 of the calling thread's last
+ * bslv_vlp_solve_dual2 (all zero without BSLV_VLP_CANONICAL) */
+int  bslv_vlp_last_canonical_obj_stats(long out[4]);
 /* option -s with the dual algorithm (flags & BSLV_VLP_PREIMAGES in bslv_vlp_solve_dual2; phase2_dual with PRE_IMG_ON,
  * bslv_algs.c:1388-1389, 1431-1432, 1484-1497, 1508-1546): x (n values) of an element of the UPPER image = dual slot `facet` of the
  * returned polyhedron, (u, w) (m + q values) of a vertex of the LOWER image = its primal element.  0 + data, 1: nothing stored.
