@@ -2305,26 +2305,10 @@ __global__ __launch_bounds__(NT) void k_rfx_finish(LpView L, BatchView Bv, RfxVi
     for (int i = threadIdx.x; i < M; i += NT) { const int k = rowvar[i]; bh[i] = k; pos[k] = i; }
     if (threadIdx.x == 0) Bv.mode[b] = MODE_REFRESH;
 }
-// y = sum over the rows i of c[bh_i] X[i, :] for the engine's own cost vector (cost[0] is the constant, auxiliary variables cost nothing)
-// into the LP's scratch vector uvec (free until k_rev_u): what rev_price_y does for the cost range of an objective batch
-__global__ void k_rfx_y(LpView L, BatchView Bv, RfxView R, int n)
-{
-    const int b = blockIdx.y, c = blockIdx.x * blockDim.x + threadIdx.x, M = L.M;
-    if (b >= n || c >= L.ldt) return;
-    double v = 0.0;
-    if (c < M && Bv.mode[b] == MODE_REFRESH) {
-        const int slot = Bv.dst[b];
-        const int *bh = L.bh + (size_t)slot * M;
-        const double *X = L.T + (size_t)slot * L.slotT;
-        for (int i = 0; i < M; i++) {
-            const int k = bh[i];
-            const double ck = k >= M ? R.cost[k - M + 1] : 0.0;
-            if (ck != 0.0) v = fma(ck, X[(size_t)i * L.ldt + c], v);
-        }
-    }
-    Bv.uvec[(size_t)b * L.ldt + c] = v;
-}
-// d_j = c[nh_j] - y . K[nh_j] into dcur, by column slices as k_rev_price has them
+// The explicit rebuild's price: d_j = c[nh_j] - y . K[nh_j] into dcur for the engine's own cost vector, by column slices as k_rev_price
+// has them.  NOT k_per_price with the identity list: that one adds per_cost to every column, 0.0 for an auxiliary variable, and
+// (-0.0) + 0.0 = +0.0 -- here an auxiliary column keeps what rev_row_slice wrote (-y_k, -0.0 where y_k is an exact zero), and the
+// getters hand dsl out as it is.  It also prices an LP whose replay failed (y = 0 then), which k_per_price leaves alone.
 __global__ __launch_bounds__(NT) void k_rfx_price(LpView L, BatchView Bv, RfxView R, int n)
 {
     const int b = blockIdx.y, M = L.M;
@@ -2417,8 +2401,12 @@ __device__ __forceinline__ double per_cost(const LpView &L, const BatchView &Bv,
     if (L.objmode) { const int t = k - L.cfirst; if (t >= 0 && t < L.ccnt) return Bv.cvals[(size_t)b * L.ccnt + t]; }
     return k >= L.M ? cost[k - L.M + 1] : 0.0;
 }
-// y = sum over the rows i of c[bh_i] X[i, :] for the LP's OWN cost (k_rfx_y knows the engine's only), rows in ascending order, into
-// Rv's scratch vector uvec (free until k_rev_u).  Grid (column blocks, n).
+// y of a rebuilt inverse, for both callers of the replay.  The periodic refactorisation runs it on its own view Rv with the list of the
+// due LPs; the explicit rebuild (refactor_impl) with Rv = Bv and the identity list, in a batch without objective values (objmode 0),
+// where per_cost is the engine's cost vector (cost[0] is the constant, auxiliary variables cost nothing): the same sums in the same order
+// as the kernel the explicit rebuild had of its own.
+// y = sum over the rows i of c[bh_i] X[i, :] for the LP's OWN cost, rows in ascending order, zero costs skipped, into Rv's scratch vector
+// uvec (free until k_rev_u): what rev_price_y does for the cost range of an objective batch.  Grid (column blocks, n).
 __global__ void k_per_y(LpView L, BatchView Bv, BatchView Rv, const int *due, const double *cost, int n)
 {
     const int k = blockIdx.y, c = blockIdx.x * blockDim.x + threadIdx.x, M = L.M;
@@ -2659,6 +2647,14 @@ static int ensure_batch(bslv_lpq *h, int B)
     return 0;
 }
 
+// the work-list lengths (nwork_d, one counter per pass of a call): room for `need` of them, the first `zero` zeroed on the stream
+static int ensure_nwork(bslv_lpq *h, int need, int zero)
+{
+    hipStream_t s = h->stream;
+    if (need > h->nworkcap) { if (h->nwork_d) (void)hipFree(h->nwork_d); h->nwork_d = nullptr; HIP_TRY(malloc0s(&h->nwork_d, need * sizeof(int), s)); h->nworkcap = need; }
+    HIP_TRY(hipMemsetAsync(h->nwork_d, 0, (size_t)zero * sizeof(int), s));
+    return 0;
+}
 static BatchView bview(bslv_lpq *h)
 {
     BatchView v;
@@ -3001,19 +2997,36 @@ int bslv_lpq_reset_slot(bslv_lpq *h, int slot)
 // caller names the slots it will use as parents: bslv_lpq_materialise(h, n, slots) gives those their tableau -- the same pass, the
 // same arithmetic -- and bslv_lpq_discard_pending(h) drops the rest.  A batch that is started while slots are still open gives all
 // of them their tableau first (the retry batches of the driver).  Slots that were neither materialised nor parked (below) must not be used as `src`.
-// one pass over the work list of counter slot cnt_slot of a view (at most `upper` LPs); ev: events around k_flush (set_profile), or nullptr
-static int flush_launch(bslv_lpq *h, const BatchView &bv, int cnt_slot, int upper, std::pair<hipEvent_t, hipEvent_t> *ev)
+typedef std::pair<hipEvent_t, hipEvent_t> EventPair;
+static int event_pair(EventPair *ev)
+{
+    HIP_TRY(hipEventCreate(&ev->first)); HIP_TRY(hipEventCreate(&ev->second));
+    return 0;
+}
+// One pass over the work list of counter slot cnt_slot of a view (at most `upper` LPs): every pass of the engine is launched here.
+// ev: the caller's events, recorded around the pass (set_profile), or nullptr.  refresh: the work list again where the pass belongs to
+// a round of a solve of the revised form -- k_rev_u for the LPs of the list that asked for a refresh of beta, inside the events (its
+// batch-size argument is read only without a list: `upper` stands in).  The geometry below is worked out per pass, a few host
+// instructions and one getenv beside four launches, so that BSLV_FLUSH_NT and the LDS limit act wherever a pass is made.
+static int flush_launch(bslv_lpq *h, const BatchView &bv, int cnt_slot, int upper, const EventPair *ev, const int *refresh = nullptr)
 {
     LpView &L = h->L;
     hipStream_t s = h->stream;
-    const int wide = (size_t)KP * L.ldt * sizeof(double) > h->flush_lds_max;
+    const int wide = (size_t)KP * L.ldt * sizeof(double) > h->flush_lds_max;      // pivot rows from global memory in k_flush
     const size_t lds = wide ? 0 : (size_t)KP * L.ldt * sizeof(double);
-    const bool big_flush = getenv("BSLV_FLUSH_NT") ? atoi(getenv("BSLV_FLUSH_NT")) > NT : lds > 53 * 1024;
+    // (160 KB of LDS per CU: three workgroups of NT threads need lds <= ~53 KB)
+    const char *e = getenv("BSLV_FLUSH_NT");
+    const bool big_flush = e ? atoi(e) > NT : lds > 53 * 1024;
     const int tiles = (L.mrows + TR - 1) / TR;
-    int tr = upper * tiles >= 2048 ? 32 : (upper * tiles * 2 >= 2048 ? 16 : (upper * tiles * 4 >= 2048 ? 8 : 4));
-    if (big_flush) { const long rows = (long)upper * L.mrows; tr = rows >= 2048L * 128 ? 128 : rows >= 2048L * 64 ? 64 : rows >= 2048L * 32 ? 32 : 16; }
+    // few LPs left: smaller row tiles keep >= ~2k workgroups in flight
+    int tr = upper * tiles >= 2048 ? 32 : (upper * tiles * 2 >= 2048 ? 16 : (upper * tiles * 4 >= 2048 ? 8 : 4));      // (4: one row per wave -- a single LP of a few thousand rows)
+    if (big_flush) {                                            // 16 waves per workgroup: at least one row per wave, more where the batch still fills the chip
+        const long rows = (long)upper * L.mrows;
+        tr = rows >= 2048L * 128 ? 128 : rows >= 2048L * 64 ? 64 : rows >= 2048L * 32 ? 32 : 16;
+    }
     const int ntile = (L.mrows + tr - 1) / tr, fnt = big_flush ? NT_BIG : NT;
-    if (ev) { HIP_TRY(hipEventCreate(&ev->first)); HIP_TRY(hipEventCreate(&ev->second)); HIP_TRY(hipEventRecord(ev->first, s)); }
+    if (ev) HIP_TRY(hipEventRecord(ev->first, s));
+    if (refresh) hipLaunchKernelGGL(k_rev_u, dim3(upper), dim3(NT), 0, s, L, bv, upper, refresh, cnt_slot);
     if (wide) hipLaunchKernelGGL(k_flush<true>, dim3(std::min(upper * ntile, h->upd_grid)), dim3(fnt), 0, s, L, bv, cnt_slot, ntile, tr);
     else hipLaunchKernelGGL(k_flush<false>, dim3(std::min(upper * ntile, h->upd_grid)), dim3(fnt), lds, s, L, bv, cnt_slot, ntile, tr);
     if (ev) HIP_TRY(hipEventRecord(ev->second, s));
@@ -3024,9 +3037,10 @@ static int flush_launch(bslv_lpq *h, const BatchView &bv, int cnt_slot, int uppe
 static int flush_list(bslv_lpq *h, int cnt_slot, int upper, bool account = true)      // (account: the pass counts in the statistics of the lazy tableaux and of the last batch)
 {
     hipStream_t s = h->stream;
-    std::pair<hipEvent_t, hipEvent_t> ev{nullptr, nullptr};
-    const int rc = flush_launch(h, bview(h), cnt_slot, upper, h->profile ? &ev : nullptr);
-    if (rc) return rc;
+    EventPair ev{nullptr, nullptr};
+    int rc;
+    if (h->profile && (rc = event_pair(&ev))) return rc;
+    if ((rc = flush_launch(h, bview(h), cnt_slot, upper, h->profile ? &ev : nullptr))) return rc;
     int n = 0;
     HIP_TRY(hipMemcpyAsync(&n, h->nwork_d + cnt_slot, sizeof(int), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
@@ -3134,9 +3148,10 @@ static int park_pass(bslv_lpq *h, const int *recs, int n)
     HIP_TRY(hipMemcpyAsync(P.list_d, P.list_h, (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemsetAsync(P.nwork, 0, sizeof(int), s));
     hipLaunchKernelGGL(k_list_given, dim3((n + 255) / 256), dim3(256), 0, s, pv, (const int *)P.list_d, n, 0);
-    std::pair<hipEvent_t, hipEvent_t> ev{nullptr, nullptr};
-    const int rc = flush_launch(h, pv, 0, n, h->profile ? &ev : nullptr);
-    if (rc) return rc;
+    EventPair ev{nullptr, nullptr};
+    int rc;
+    if (h->profile && (rc = event_pair(&ev))) return rc;
+    if ((rc = flush_launch(h, pv, 0, n, h->profile ? &ev : nullptr))) return rc;
     if (h->profile) P.pre_ev.push_back(ev);
     hipLaunchKernelGGL(k_store_d_list, dim3((h->L.ld + 255) / 256, n), dim3(256), 0, s, h->L, pv, (const int *)P.list_d, n);
     HIP_TRY(hipGetLastError());
@@ -3291,7 +3306,8 @@ static void period_free(bslv_lpq *h)
     P.ev.clear();
     P.cap = 0; P.nwcap = 0;
 }
-static int period_rounds_max(const LpView &L) { return (L.M + KP - 1) / KP + 2; }
+// the rounds of a replay at most (a round = KP replay steps on vectors, one pass); its refresh pass counts in work list replay_rounds_max + 1
+static int replay_rounds_max(const LpView &L) { return (L.M + KP - 1) / KP + 2; }
 static int ensure_period(bslv_lpq *h)
 {
     bslv_lpq::Period &P = h->per;
@@ -3302,7 +3318,7 @@ static int ensure_period(bslv_lpq *h)
     period_free(h);
     const size_t cap = (size_t)h->Bcap;
     for (int **p : {&P.src, &P.dst, &P.status, &P.iters, &P.mode, &P.ver, &P.npend, &P.flushed, &P.pflags, &P.stall, &P.work, &P.iota, &P.due, &P.res}) HIP_TRY(malloc0(p, cap * sizeof(int)));
-    P.nwcap = period_rounds_max(L) + 2;
+    P.nwcap = replay_rounds_max(L) + 2;
     HIP_TRY(malloc0(&P.nwork, (size_t)P.nwcap * sizeof(int)));
     HIP_TRY(malloc0(&P.stat, 2 * sizeof(long long)));
     HIP_TRY(malloc0(&P.desc, cap * KP * sizeof(PivDesc)));
@@ -3327,23 +3343,33 @@ static BatchView period_view(bslv_lpq *h, const BatchView &bv)
     v.lazy = 0;
     return v;
 }
-// The n LPs of the batch that k_per_due listed (per.due, batch indices in the order of the active list) are refactorised in their dst
-// slots and go on -- bounds, nonbasic statuses and values, iteration count, pflags, stall and Bland state and their place in the batch are
-// not touched; the matrix, the heads of the basic variables, beta and the true reduced costs are rebuilt before the next selection.  An
-// LP whose basis the replay finds singular ends UNDEFINED (status_h follows).  at_start: counts in out[0], else in out[1].
-static int period_refactor(bslv_lpq *h, const BatchView &bv, int n, bool at_start)
+static RfxView rfx_view(const bslv_lpq *h)
 {
-    bslv_lpq::Period &P = h->per;
+    const size_t BM = (size_t)h->Bcap * h->L.M;
+    RfxView R;
+    R.enter = h->rfx_i_d; R.rowvar = h->rfx_i_d + BM; R.elig = h->rfx_i_d + 2 * BM; R.cnt = h->rfx_c_d; R.cost = h->cost_d;
+    return R;
+}
+}  // extern "C"
+// THE REPLAY (the kernels: k_rfx_*), for the explicit rebuild and the periodic refactorisation alike, in two pieces with the pricing,
+// which differs, between them.  replay_rebuild: B^-1 of the n LPs of the view rv is rebuilt in their dst slots from the heads there
+// (through k_rfx_finish); returns the rounds made in *rounds.  replay_refresh: k_rev_u and the refresh pass for beta.  iota: 0..n-1 on
+// the device, the active list of the replay's passes.  pass(cnt_slot): one tableau pass over the work list that k_list_pending has
+// just written there -- the callers differ in how they launch and account it.
+template <class Pass>
+static int replay_pass(bslv_lpq *h, const BatchView &rv, const int *iota, int n, int cnt_slot, Pass &pass)
+{
+    hipLaunchKernelGGL(k_list_pending, dim3((n + 255) / 256), dim3(256), 0, h->stream, rv, iota, n, cnt_slot);
+    return pass(cnt_slot);
+}
+template <class Pass>
+static int replay_rebuild(bslv_lpq *h, const BatchView &rv, const int *iota, int n, Pass &pass, int *rounds_out = nullptr)
+{
     LpView &L = h->L;
     hipStream_t s = h->stream;
-    const auto t0 = std::chrono::steady_clock::now();
-    const int M = L.M, rounds_max = period_rounds_max(L);
+    const int M = L.M;
     int rc;
-    BatchView rv = period_view(h, bv);
-    RfxView R;
-    R.enter = h->rfx_i_d; R.rowvar = h->rfx_i_d + (size_t)h->Bcap * M; R.elig = h->rfx_i_d + (size_t)h->Bcap * 2 * M; R.cnt = h->rfx_c_d; R.cost = h->cost_d;
-    HIP_TRY(hipMemsetAsync(P.nwork, 0, (size_t)P.nwcap * sizeof(int), s));
-    hipLaunchKernelGGL(k_per_setup, dim3((n + 255) / 256), dim3(256), 0, s, bv, rv, (const int *)P.due, n);
+    const RfxView R = rfx_view(h);
     hipLaunchKernelGGL(k_rfx_setup, dim3(n), dim3(NT), 0, s, L, rv, R, n);
     {
         const size_t total = (size_t)M * L.ldt;
@@ -3355,25 +3381,54 @@ static int period_refactor(bslv_lpq *h, const BatchView &bv, int n, bool at_star
     HIP_TRY(hipStreamSynchronize(s));
     int kmax = 0;
     for (int k = 0; k < n; k++) if (cnt[(size_t)k * 4 + 2] == RFX_RUN) kmax = std::max(kmax, cnt[(size_t)k * 4]);
-    const int rounds = std::min((kmax + KP - 1) / KP, rounds_max);
+    // one round = KP replay steps on vectors, one pass; an LP with fewer structural basics is done earlier and is passed over
+    const int rounds = std::min((kmax + KP - 1) / KP, replay_rounds_max(L));
     const int snt = M >= 1536 ? NT_BIG : NT;
-    auto pass = [&](int cnt_slot) -> int {
-        hipLaunchKernelGGL(k_list_pending, dim3((n + 255) / 256), dim3(256), 0, s, rv, (const int *)P.iota, n, cnt_slot);
-        if (h->profile) P.ev.emplace_back(nullptr, nullptr);
-        return flush_launch(h, rv, cnt_slot, n, h->profile ? &P.ev.back() : nullptr);
-    };
     for (int it = 0; it < rounds; it++) {
         hipLaunchKernelGGL(k_rfx_select, dim3(n), dim3(snt), 0, s, L, rv, R, n, KP);
-        if ((rc = pass(it))) return rc;
+        if ((rc = replay_pass(h, rv, iota, n, it, pass))) return rc;
     }
     hipLaunchKernelGGL(k_rfx_finish, dim3(n), dim3(NT), 0, s, L, rv, R, n);
-    // the LP's own costs on the rebuilt inverse -> its reduced costs (and the perturbed row's offsets), then uvec = -K_N x_N and beta[M],
-    // then the refresh pass for beta: all of it before the next selection
-    hipLaunchKernelGGL(k_per_y, dim3((L.ldt + 255) / 256, n), dim3(256), 0, s, L, bv, rv, (const int *)P.due, (const double *)h->cost_d, n);
-    hipLaunchKernelGGL(k_per_price, dim3((L.ld + REV_PRICE_SLICE - 1) / REV_PRICE_SLICE, n), dim3(NT), 0, s, L, bv, rv, (const int *)P.due, (const double *)h->cost_d, n);
-    hipLaunchKernelGGL(k_rev_u, dim3(n), dim3(NT), 0, s, L, rv, n, (const int *)nullptr, 0);
-    if ((rc = pass(rounds_max + 1))) return rc;
-    hipLaunchKernelGGL(k_per_resume, dim3((n + 255) / 256), dim3(256), 0, s, bv, rv, R, (const int *)P.due, n, h->age0_d, P.res);
+    if (rounds_out) *rounds_out = rounds;
+    return 0;
+}
+// after the caller's pricing (y, the reduced costs): uvec = -K_N x_N and beta[M], then the refresh pass for beta
+template <class Pass>
+static int replay_refresh(bslv_lpq *h, const BatchView &rv, const int *iota, int n, Pass &pass)
+{
+    hipLaunchKernelGGL(k_rev_u, dim3(n), dim3(NT), 0, h->stream, h->L, rv, n, (const int *)nullptr, 0);
+    return replay_pass(h, rv, iota, n, replay_rounds_max(h->L) + 1, pass);
+}
+// y for the replay's LP k = LP due[k] of the batch view bv (the explicit rebuild: rv = bv, due = iota), into rv's uvec
+static void replay_y(bslv_lpq *h, const BatchView &bv, const BatchView &rv, const int *due, int n)
+{
+    hipLaunchKernelGGL(k_per_y, dim3((h->L.ldt + 255) / 256, n), dim3(256), 0, h->stream, h->L, bv, rv, due, (const double *)h->cost_d, n);
+}
+extern "C" {
+// The n LPs of the batch that k_per_due listed (per.due, batch indices in the order of the active list) are refactorised in their dst
+// slots and go on -- bounds, nonbasic statuses and values, iteration count, pflags, stall and Bland state and their place in the batch are
+// not touched; the matrix, the heads of the basic variables, beta and the true reduced costs are rebuilt before the next selection.  An
+// LP whose basis the replay finds singular ends UNDEFINED (status_h follows).  at_start: counts in out[0], else in out[1].
+static int period_refactor(bslv_lpq *h, const BatchView &bv, int n, bool at_start)
+{
+    bslv_lpq::Period &P = h->per;
+    hipStream_t s = h->stream;
+    const auto t0 = std::chrono::steady_clock::now();
+    int rc, rounds = 0;
+    const BatchView rv = period_view(h, bv);
+    HIP_TRY(hipMemsetAsync(P.nwork, 0, (size_t)P.nwcap * sizeof(int), s));
+    hipLaunchKernelGGL(k_per_setup, dim3((n + 255) / 256), dim3(256), 0, s, bv, rv, (const int *)P.due, n);
+    // no host wait after a pass; its events are read when the call is over.  All of the replay is on the stream before the next selection.
+    auto pass = [&](int cnt_slot) -> int {
+        if (h->profile) { P.ev.emplace_back(nullptr, nullptr); if ((rc = event_pair(&P.ev.back()))) return rc; }
+        return flush_launch(h, rv, cnt_slot, n, h->profile ? &P.ev.back() : nullptr);
+    };
+    if ((rc = replay_rebuild(h, rv, P.iota, n, pass, &rounds))) return rc;
+    // the LP's own costs on the rebuilt inverse -> its reduced costs (and the perturbed row's offsets), then beta
+    replay_y(h, bv, rv, P.due, n);
+    hipLaunchKernelGGL(k_per_price, dim3((h->L.ld + REV_PRICE_SLICE - 1) / REV_PRICE_SLICE, n), dim3(NT), 0, s, h->L, bv, rv, (const int *)P.due, (const double *)h->cost_d, n);
+    if ((rc = replay_refresh(h, rv, P.iota, n, pass))) return rc;
+    hipLaunchKernelGGL(k_per_resume, dim3((n + 255) / 256), dim3(256), 0, s, bv, rv, rfx_view(h), (const int *)P.due, n, h->age0_d, P.res);
     HIP_TRY(hipGetLastError());
     std::vector<int> due(n), res(n), nw(P.nwcap);
     HIP_TRY(hipMemcpyAsync(due.data(), P.due, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
@@ -3594,7 +3649,6 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
     // (before k_prep: the pass reads and writes slots the batch touches)
     if ((rc = park_before(h, B, src, B, dst))) return rc;
     LpView &L = h->L;
-    const int wide = (size_t)KP * L.ldt * sizeof(double) > h->flush_lds_max;      // pivot rows from global memory in k_flush
     auto t0 = std::chrono::steady_clock::now();
     hipStream_t s = h->stream;
     HIP_TRY(hipMemcpyAsync(h->src_d, src, B * sizeof(int), hipMemcpyHostToDevice, s));
@@ -3612,8 +3666,7 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
     if (const char *e = getenv("BSLV_UPD_GRID")) h->upd_grid = std::max(64, atoi(e));
     {   // one work-list length per lock-step iteration, zeroed here: no reset between iterations
         const int need = L.maxit + 64 + ((h->canonical || h->canon_obj) ? tie_rounds_max(L) : 0);      // (the rounds of a tie phase count on behind the others')
-        if (need > h->nworkcap) { if (h->nwork_d) (void)hipFree(h->nwork_d); h->nwork_d = nullptr; HIP_TRY(malloc0s(&h->nwork_d, need * sizeof(int), s)); h->nworkcap = need; }
-        HIP_TRY(hipMemsetAsync(h->nwork_d, 0, need * sizeof(int), s));
+        if ((rc = ensure_nwork(h, need, need))) return rc;
     }
     HIP_TRY(hipMemsetAsync(h->xstat_d, 0, 8 * sizeof(int), s));
     if (L.rfx) HIP_TRY(hipMemsetAsync(h->rmark_d, 0, (size_t)B * sizeof(int), s));
@@ -3658,9 +3711,6 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
         else hipLaunchKernelGGL((k_init_grouped<16, 2>), grid, dim3(NT), 0, s, L, bv, order, chunks);
     } else hipLaunchKernelGGL(k_init, dim3(tiles, B), dim3(NT), 0, s, L, bv, B);
     HIP_TRY(hipGetLastError());
-    const size_t lds = wide ? 0 : (size_t)KP * L.ldt * sizeof(double);
-    // (160 KB of LDS per CU: three workgroups of NT threads need lds <= ~53 KB)
-    const bool big_flush = getenv("BSLV_FLUSH_NT") ? atoi(getenv("BSLV_FLUSH_NT")) > NT : lds > 53 * 1024;
     SelectPlan plan;
     if ((rc = plan_select(h, B, vlo, vup, &plan))) return rc;
     L.trace = getenv("BSLV_LP_TRACE") ? atoi(getenv("BSLV_LP_TRACE")) : -1;
@@ -3693,27 +3743,14 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
     // the pass of round `it` over the tableaux of the `running` LPs of the active list that have something pending
     auto pass_round = [&](const int running, const int it) -> int {
         hipLaunchKernelGGL(k_list_pending, dim3((running + 255) / 256), dim3(256), 0, s, bv, h->active_d, running, it);
-        if (h->profile) {
-            if (nev == h->evpool.size()) {
-                hipEvent_t a, b2;
-                HIP_TRY(hipEventCreate(&a)); HIP_TRY(hipEventCreate(&b2));
-                h->evpool.emplace_back(a, b2);
-            }
-            HIP_TRY(hipEventRecord(h->evpool[nev].first, s));
+        if (h->profile && nev == h->evpool.size()) {      // (pooled: no event is created per round once the pool has grown)
+            EventPair ev;
+            if ((rc = event_pair(&ev))) return rc;
+            h->evpool.push_back(ev);
         }
-        // few LPs left: smaller row tiles keep >= ~2k workgroups in flight
-        int tr = running * tiles >= 2048 ? 32 : (running * tiles * 2 >= 2048 ? 16 : (running * tiles * 4 >= 2048 ? 8 : 4));      // (4: one row per wave -- a single LP of a few thousand rows)
-        if (big_flush) {                                            // 16 waves per workgroup: at least one row per wave, more where the batch still fills the chip
-            const long rows = (long)running * L.mrows;
-            tr = rows >= 2048L * 128 ? 128 : rows >= 2048L * 64 ? 64 : rows >= 2048L * 32 ? 32 : 16;
-        }
-        const int ntile = (L.mrows + tr - 1) / tr;
-        const int fnt = big_flush ? NT_BIG : NT;
-        if (L.rev) hipLaunchKernelGGL(k_rev_u, dim3(running), dim3(NT), 0, s, L, bv, B, (const int *)h->work_d, it);      // (only the LPs that asked for a refresh of beta)
-        if (wide) hipLaunchKernelGGL(k_flush<true>, dim3(std::min(running * ntile, h->upd_grid)), dim3(fnt), 0, s, L, bv, it, ntile, tr);
-        else hipLaunchKernelGGL(k_flush<false>, dim3(std::min(running * ntile, h->upd_grid)), dim3(fnt), lds, s, L, bv, it, ntile, tr);
-        if (h->profile) { HIP_TRY(hipEventRecord(h->evpool[nev].second, s)); nev++; }
-        hipLaunchKernelGGL(k_after_flush, dim3((running + 255) / 256), dim3(256), 0, s, bv, it);
+        // (revised form: only the LPs that asked for a refresh of beta are done by k_rev_u)
+        if ((rc = flush_launch(h, bv, it, running, h->profile ? &h->evpool[nev] : nullptr, L.rev ? h->work_d : nullptr))) return rc;
+        if (h->profile) nev++;
         return 0;
     };
     while (running > 0 && it < L.maxit + 8 && !(max_rounds && it >= max_rounds)) {
@@ -3879,7 +3916,7 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
     return 0;
 }
 
-// ---- refactorisation of the revised form: host side (the kernels: k_rfx_*) ----
+// ---- refactorisation of the revised form: host side (the kernels: k_rfx_*, k_per_y; the sequence: replay_rebuild, replay_refresh) ----
 static int ensure_rfx(bslv_lpq *h)
 {
     if (h->rfx_Bcap >= h->Bcap && h->rfx_i_d) return 0;
@@ -3900,50 +3937,24 @@ static int refactor_impl(bslv_lpq *h, int n, const int *slots, int *status_out, 
     int rc;
     if ((rc = ensure_batch(h, n))) return rc;
     if ((rc = ensure_rfx(h))) return rc;
-    const int M = L.M;
-    const int rounds_max = (M + KP - 1) / KP + 2;
-    {   // the work lists of the rounds and of the refresh pass behind them
-        const int need = std::max(L.maxit + 64, rounds_max + 2);
-        if (need > h->nworkcap) { if (h->nwork_d) (void)hipFree(h->nwork_d); h->nwork_d = nullptr; HIP_TRY(malloc0s(&h->nwork_d, need * sizeof(int), s)); h->nworkcap = need; }
-        HIP_TRY(hipMemsetAsync(h->nwork_d, 0, (size_t)(rounds_max + 2) * sizeof(int), s));
-    }
-    L.objmode = 0;
+    const int rounds_max = replay_rounds_max(L);
+    if ((rc = ensure_nwork(h, std::max(L.maxit + 64, rounds_max + 2), rounds_max + 2))) return rc;      // the work lists of the rounds and of the refresh pass behind them
+    L.objmode = 0;                                  // (the engine's own cost vector: per_cost)
     for (int b = 0; b < n; b++) h->active_h[b] = b;
     HIP_TRY(hipMemcpyAsync(h->active_d, h->active_h, n * sizeof(int), hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(h->src_d, slots, n * sizeof(int), hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(h->dst_d, slots, n * sizeof(int), hipMemcpyHostToDevice, s));
-    BatchView bv = bview(h);
-    RfxView R;
-    R.enter = h->rfx_i_d; R.rowvar = h->rfx_i_d + (size_t)h->Bcap * M; R.elig = h->rfx_i_d + (size_t)h->Bcap * 2 * M; R.cnt = h->rfx_c_d; R.cost = h->cost_d;
-    hipLaunchKernelGGL(k_rfx_setup, dim3(n), dim3(NT), 0, s, L, bv, R, n);
-    {
-        const size_t total = (size_t)M * L.ldt;
-        hipLaunchKernelGGL(k_rfx_identity, dim3((unsigned)std::min<size_t>((total + 255) / 256, 4096), n), dim3(256), 0, s, L, bv, R, n);
-    }
-    HIP_TRY(hipGetLastError());
-    std::vector<int> cnt((size_t)n * 4);
-    HIP_TRY(hipMemcpyAsync(cnt.data(), h->rfx_c_d, cnt.size() * sizeof(int), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    int kmax = 0;
-    for (int b = 0; b < n; b++) if (cnt[(size_t)b * 4 + 2] == RFX_RUN) kmax = std::max(kmax, cnt[(size_t)b * 4]);
-    // one round = KP replay steps on vectors, one pass; an LP with fewer structural basics is done earlier and is passed over
-    const int rounds = std::min((kmax + KP - 1) / KP, rounds_max);
-    const int snt = M >= 1536 ? NT_BIG : NT;
-    for (int it = 0; it < rounds; it++) {
-        hipLaunchKernelGGL(k_rfx_select, dim3(n), dim3(snt), 0, s, L, bv, R, n, KP);
-        hipLaunchKernelGGL(k_list_pending, dim3((n + 255) / 256), dim3(256), 0, s, bv, h->active_d, n, it);
-        if ((rc = flush_list(h, it, n, false))) return rc;
-    }
-    hipLaunchKernelGGL(k_rfx_finish, dim3(n), dim3(NT), 0, s, L, bv, R, n);
-    // the reduced costs of the engine's own cost vector -> dsl, then uvec = -K_N x_N and beta[M], then one refresh pass for beta
-    hipLaunchKernelGGL(k_rfx_y, dim3((L.ldt + 255) / 256, n), dim3(256), 0, s, L, bv, R, n);
-    hipLaunchKernelGGL(k_rfx_price, dim3((L.ld + REV_PRICE_SLICE - 1) / REV_PRICE_SLICE, n), dim3(NT), 0, s, L, bv, R, n);
+    const BatchView bv = bview(h);
+    // in place on the batch view, LP b = slot b of the list; every pass waits on the host and counts in no statistics
+    auto pass = [&](int cnt_slot) { return flush_list(h, cnt_slot, n, false); };
+    if ((rc = replay_rebuild(h, bv, h->active_d, n, pass))) return rc;
+    // the reduced costs of the engine's own cost vector -> dsl, then beta
+    replay_y(h, bv, bv, h->active_d, n);
+    hipLaunchKernelGGL(k_rfx_price, dim3((L.ld + REV_PRICE_SLICE - 1) / REV_PRICE_SLICE, n), dim3(NT), 0, s, L, bv, rfx_view(h), n);
     hipLaunchKernelGGL(k_rev_store_d, dim3((L.ld + 255) / 256, n), dim3(256), 0, s, L, bv, n);
-    hipLaunchKernelGGL(k_rev_u, dim3(n), dim3(NT), 0, s, L, bv, n, (const int *)nullptr, 0);
-    hipLaunchKernelGGL(k_list_pending, dim3((n + 255) / 256), dim3(256), 0, s, bv, h->active_d, n, rounds_max + 1);
-    HIP_TRY(hipGetLastError());
-    if ((rc = flush_list(h, rounds_max + 1, n, false))) return rc;
+    if ((rc = replay_refresh(h, bv, h->active_d, n, pass))) return rc;
     hipLaunchKernelGGL(k_age_zero, dim3((n + 255) / 256), dim3(256), 0, s, (const int *)h->dst_d, n, h->age_d);      // built from the identity (a failed slot is reset below)
+    std::vector<int> cnt((size_t)n * 4);
     HIP_TRY(hipMemcpy(cnt.data(), h->rfx_c_d, cnt.size() * sizeof(int), hipMemcpyDeviceToHost));
     for (int b = 0; b < n; b++) {
         const bool ok = cnt[(size_t)b * 4 + 2] == RFX_RUN;

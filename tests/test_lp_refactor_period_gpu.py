@@ -394,6 +394,37 @@ def test_runs_with_a_period_are_deterministic():
             assert _same_bits(a["res"][k][f], b["res"][k][f]), (k, f)
 
 
+@pytest.mark.parametrize("case", ["main", "wide"])
+def test_explicit_and_periodic_rebuild_are_the_same_replay(case):
+    """the same basis -- a child of the cold solve with the cold solve's own bounds, which makes no pivot -- rebuilt by bslv_lpq_refactor
+    and by the periodic refactorisation at the start of the call that makes the child: the same heads, and the same bits in the inverse
+    and in what the getters read from the slot"""
+    p = _problem(case)
+    model = p["model"]
+    free = np.full((1, model.r), -np.inf)
+    got = {}
+    for how in ("explicit", "periodic"):
+        eng = _engine(case)
+        _cold(eng, case)
+        if how == "periodic":
+            assert eng.set_refactor_period(1) == 0
+        st, it = eng.solve_batch([0], [2], free, p["ub"][:1])
+        assert st[0] == OPTIMAL and it[0] == 0, (how, st, it)
+        if how == "explicit":
+            assert list(eng.refactor([2])) == [0]
+        else:
+            assert eng.last_period_stats()["at_start"] == 1, eng.last_period_stats()
+        assert eng.slot_age(2) == 0, how
+        got[how] = (eng.get_inverse(2), _read(eng, model, [2]))
+        eng.close()
+    (ha, Xa), ra = got["explicit"]
+    (hb, Xb), rb = got["periodic"]
+    assert np.array_equal(ha, hb)
+    assert _same_bits(Xa, Xb)
+    for k in ("obj", "w", "y"):
+        assert _same_bits(ra[k], rb[k]), k
+
+
 # ---- 10. with the rescue on as well ----
 def test_period_and_rescue_together():
     """the parent is aged (cold solve without a period), so with K = 6 every child is refactorised at the start; the cross-check of one
