@@ -1017,14 +1017,15 @@ __global__ __launch_bounds__(PB) void k_pair_flags_bits(int d, const unsigned lo
 // S-degenerate at q = 10): the pair blocks that hold an adjacent pair are known (nzlist, a few per element) and so is where each
 // block's pairs go (bpre: the scanned block sums of the flags pass); the listed blocks are simply tested AGAIN and write their pairs.
 __global__ __launch_bounds__(PB) void k_pair_retest_emit(int d, const unsigned long long *bits, int nm, int W, const int *fm_cnt, const int *fm_off, const int *fm_list,
-                                                          const int *members, const int *nzlist, const int *nzcount, const Tri *bpre, int2 *E, int ebase, int *EP)
+                                                          const int *members, const int *nzlist, const int *nzcount, const Tri *bpre, int2 *E, int ebase, int *EP,
+                                                          long long vb0 /* first virtual block of the window that nzlist / bpre are relative to */)
 {
     __shared__ Tri lds[16];
     extern __shared__ unsigned long long s_m[];
     const int n = *nzcount;
     for (int k = blockIdx.x; k < n; k += gridDim.x) {
         const int blk = nzlist[k];
-        const PairBlk pb = pair_block(nm, blk);
+        const PairBlk pb = pair_block(nm, vb0 + blk);
         const bool adj = pair_block_test(d, bits, nm, W, pb, fm_cnt, fm_off, fm_list, s_m);
         Tri t{adj ? 1 : 0, 0, 0};
         Tri tot;
@@ -1045,7 +1046,8 @@ __global__ __launch_bounds__(PB) void k_pair_retest_emit(int d, const unsigned l
 constexpr int PTI = 8;
 __global__ __launch_bounds__(PB) void k_pair_flags_tiled(int d, const unsigned long long *bits, int nm, int W, unsigned char *pflag, Tri *bsum,
                                                           const int *fm_cnt, const int *fm_off, const int *fm_list /* NULL: scan all elements */,
-                                                          int *nzlist, int *nzcount, int gy0 /* first row group of this launch (a rank's share of the pair space) */)
+                                                          int *nzlist, int *nzcount, int gy0 /* first row group of this launch (a rank's share of the pair space, or a window's) */,
+                                                          long long vb0 /* first virtual block of the window: pflag, bsum and nzlist are relative to it */)
 {
     extern __shared__ unsigned long long s_t[];       // PTI x W row words | W x (PB + PTI) column words | 4 x W (one M per wave)
     const int i0 = ((int)blockIdx.y + gy0) * PTI, c = blockIdx.x;
@@ -1111,7 +1113,7 @@ __global__ __launch_bounds__(PB) void k_pair_flags_tiled(int d, const unsigned l
             __builtin_amdgcn_wave_barrier();
             if (lane == src) adj = !found;
         }
-        const long long vb = GL - pair_G(L1 - i) + c;           // virtual block (row i, chunk c), as pair_block enumerates them
+        const long long vb = GL - pair_G(L1 - i) + c - vb0;     // virtual block (row i, chunk c), as pair_block enumerates them, within the window
         if (pflag) pflag[(size_t)vb * PB + threadIdx.x] = adj ? 1 : 0;       // (nullptr: the listed blocks are tested again at emission, k_pair_retest_emit)
         const int cnt = __syncthreads_count(adj);
         if (threadIdx.x == 0) {
@@ -1124,13 +1126,13 @@ __global__ __launch_bounds__(PB) void k_pair_flags_tiled(int d, const unsigned l
 // emission for large facets: only the pair blocks that hold an adjacent pair (k_pair_flags_bits listed them, in any order:
 // every block writes to its own offset), a fixed grid walking the list
 __global__ __launch_bounds__(PB) void k_pair_emit_list(const int *members, int nm, const int *nzlist, const int *nzcount, const unsigned char *pflag,
-                                                        const Tri *bpre, int2 *E, int ebase, int *EP)
+                                                        const Tri *bpre, int2 *E, int ebase, int *EP, long long vb0 /* as k_pair_retest_emit */)
 {
     __shared__ Tri lds[16];
     const int n = *nzcount;
     for (int k = blockIdx.x; k < n; k += gridDim.x) {
         const int blk = nzlist[k];
-        const PairBlk pb = pair_block(nm, blk);
+        const PairBlk pb = pair_block(nm, vb0 + blk);
         unsigned char f = pflag[(size_t)blk * PB + threadIdx.x];
         Tri t{f, 0, 0};
         Tri tot;
@@ -2421,6 +2423,8 @@ struct bslv_poly {
     // multi-GPU: pair space of large facets dealt to the ranks (k2_multi).  Below ~3e4 elements the two all-gathers cost more than the pair tests
     int largest_facet = 0;            // members of the largest new facet pruned so far (any path)
     bool k2_noflags = getenv("BSLV_K2_NOFLAGS") != nullptr; long n_noflag_prunes = 0;     // large-facet prunes emit by testing the listed pair blocks again instead of keeping a flag per pair
+    // large-facet prunes walk the pair space in windows of at most this many pair blocks (k2_multi; bslv_poly_set_prune_window, BSLV_K2_WINDOW)
+    long long window_blocks = 0x7FFFFFF0ll, win_max_blocks = 0; long n_win_prunes = 0, n_windows = 0;
     int shard_min = 32768; long n_sharded = 0; int2 *shard_e = nullptr; size_t shardcap = 0;
     int *nzlist = nullptr; size_t nzcap = 0;         // pair blocks with an adjacent pair (+ their count behind the list)      // facet-major member lists of a large new facet (k_fm_*)       // chunk totals of the two-level scan (k_scan_chunks)
     Tri *totals = nullptr;            // device, 4 entries
@@ -2586,7 +2590,7 @@ static int ensure_ecap(bslv_poly *h, int need)
 static int ensure_bsum(bslv_poly *h, int nb)
 {
     if (nb <= h->bsumcap) return 0;
-    int ncap = std::max(nb, std::max(1024, h->bsumcap * 2));
+    int ncap = (int)std::max<long long>(nb, std::min<long long>(std::max<long long>(1024, 2ll * h->bsumcap), 0x7FFFFFF8ll));
     int rc;
     if ((rc = grow(&h->bsum, 0, ncap, h->stream))) return rc;
     h->bsumcap = ncap;
@@ -2712,43 +2716,141 @@ static int wait_mail(bslv_poly *h, int slot, int seq)
 // the multi-kernel adjacency prune (facets too large for k2_fused, or whose bit matrix does not fit in LDS);
 // members[0..nm) complete.  Appends the adjacent pairs at E[ecur][h->ne..) and advances h->ne.
 // stamp: fstamp value of this prune, above every state k2_fused may have left for the same cut.
+// The tiled path (k_pair_flags_tiled) walks the pair space in WINDOWS of at most h->window_blocks pair blocks (pair_windows; bslv_poly_set_prune_window),
+// with 64-bit virtual block ids on the host and per row in the kernels and 32-bit ids relative to the window in bsum / nzlist / pflag, which are sized
+// by the largest window: a facet of any number of pair blocks is pruned, in one window by default as long as it has at most 0x7FFFFFF0 of them.
+// These paths keep 32-bit block ids of the whole facet, their caps and their messages: the one-dimensional launches (k_pair_flags_bits, k_pair_flags:
+// at most 2^32 work-items), the sorted-list path, and a prune whose pair space is dealt to the ranks (shard).  The limits on the numbers of edges,
+// elements and pool offsets are unchanged.
+struct PairWin { int g0, g1; long long vb0, nb; };       // row groups [g0, g1) = virtual blocks [vb0, vb0 + nb)
+constexpr long long PAIR_WINDOW_DEFAULT = 0x7FFFFFF0ll;
+static inline long long pair_S(int nm, long long i) { const long long L = nm - 1; return pair_G(L) - pair_G(L - std::min(i, L)); }      // pair blocks in front of row i
+// the greedy rule: a window takes consecutive row groups (PTI rows each) while it holds at most wblocks pair blocks, and at least one
+static void pair_windows(int nm, long long wblocks, std::vector<PairWin> &out)
+{
+    const int ngroups = (nm - 1 + PTI - 1) / PTI;
+    out.clear();
+    for (int ga = 0; ga < ngroups;) {
+        const long long s0 = pair_S(nm, (long long)ga * PTI);
+        int lo = ga + 1, hi = ngroups;                    // the last group boundary within wblocks of s0 (S is monotone)
+        while (lo < hi) {
+            const int mid = lo + (hi - lo + 1) / 2;
+            if (pair_S(nm, (long long)mid * PTI) - s0 <= wblocks) lo = mid; else hi = mid - 1;
+        }
+        out.push_back(PairWin{ga, lo, s0, pair_S(nm, (long long)lo * PTI) - s0});
+        ga = lo;
+    }
+}
+// bslv_selftest_pair_blocks: hashed pairs i < j < nm through the index arithmetic of a windowed prune -- the virtual block as
+// k_pair_flags_tiled forms it, its window and id relative to that window, and back through pair_block as the emission kernels do
+__global__ __launch_bounds__(PB) void k_selftest_pair_blocks(int nm, const long long *vb0s, int nwin, int samples, unsigned long long *bad)
+{
+    const int k = blockIdx.x * PB + threadIdx.x;
+    if (k >= samples) return;
+    auto mix = [](unsigned long long x) { x += 0x9E3779B97F4A7C15ull; x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull; x = (x ^ (x >> 27)) * 0x94D049BB133111EBull; return x ^ (x >> 31); };
+    int i = (int)(mix(2ull * k) % (unsigned long long)(nm - 1));
+    int j = i + 1 + (int)(mix(2ull * k + 1) % (unsigned long long)(nm - 1 - i));
+    if (k == 0) { i = 0; j = nm - 1; }                       // the corners of the pair space
+    if (k == 1) { i = nm - 2; j = nm - 1; }
+    if (k == 2) { i = 0; j = 1; }
+    const int c = (j - i - 1) / PB;
+    const long long L1 = nm - 1, GL = pair_G(L1);
+    const long long vb = GL - pair_G(L1 - i) + c;
+    int lo = 0, hi = nwin - 1;                               // the window that holds vb
+    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (vb0s[mid] <= vb) lo = mid; else hi = mid - 1; }
+    const long long rel = vb - vb0s[lo];
+    const int blk = (int)rel;                                // what nzlist carries
+    const PairBlk pb = pair_block(nm, vb0s[lo] + blk);
+    if (rel < 0 || rel > 0x7FFFFFFFll || pb.i != i || pb.j0 != i + 1 + PB * c) atomicAdd(bad, 1ull);
+}
 static int k2_multi(bslv_poly *h, int nm, long long len_ub, int stamp)
 {
     hipStream_t s = h->stream;
     int rc;
     const long long nbp = pair_G(nm - 1);
     h->largest_facet = std::max(h->largest_facet, nm);
-    if (nbp > 0x7FFFFFF0ll) { set_error("new facet has too many elements (%d): more than 2^31 blocks of 256 pairs (block indices are 32-bit)", nm); return BSLV_E_CAPACITY; }
-    // one flag byte per pair between the test and the ordered emission -- unless that array is out of reach (k_pair_retest_emit below)
-    auto ensure_pflag = [&]() -> int {
-        if ((size_t)nbp * PB > h->pflagcap) { size_t nc = std::max((size_t)nbp * PB, h->pflagcap * 2); if ((rc = grow(&h->pflag, 0, nc, s))) return rc; h->pflagcap = nc; }
-        return 0;
-    };
-    bool noflags = false;
-    if ((rc = ensure_bsum(h, (int)nbp + 1))) return rc;
     // local incidence bit matrix: at most one local id per list entry of the members
     const int nranks = (int)h->facet_of_rank.size();
     const int W = (int)((std::min<long long>(len_ub, nranks) + 63) / 64);
-    if ((size_t)W * nm > h->bitscap) { size_t nc = std::max((size_t)W * nm, h->bitscap * 2); if ((rc = grow(&h->bits, 0, nc, s))) return rc; h->bitscap = nc; }
     const size_t lds_bits = (size_t)W * 5 * sizeof(unsigned long long);
-    bool used_list = false, shard = false;
+    // large facets: the row-tiled pair kernel (2-D grid), the list of pair blocks that hold an edge, and member lists by
+    // facet, so that confirming an edge scans one facet's elements instead of all nm
+    const size_t lds_tiled = ((size_t)PTI * W + (size_t)W * (PB + PTI) + 4 * (size_t)W) * sizeof(unsigned long long);
+    const int ngroups = (nm - 1 + PTI - 1) / PTI;
+    const bool tiled = lds_bits <= 48 * 1024 && nm >= h->fm_min && h->d > 1 && lds_tiled <= 48 * 1024;      // (more than 65535 row groups: several launches, below)
+    const bool fm = tiled && h->member_lists && len_ub <= (1ll << 30);
+    const bool shard = tiled && bslv_dist_world() > 1 && nm >= h->shard_min;
+    // the windows of the tiled path (one, [0, ngroups), for every facet whose pair space holds at most window_blocks blocks);
+    // every other path numbers the blocks of the whole facet with 32-bit indices
+    const bool windowed = tiled && !shard;
+    if (!windowed && nbp > 0x7FFFFFF0ll) { set_error("new facet has too many elements (%d): more than 2^31 blocks of 256 pairs (block indices are 32-bit)", nm); return BSLV_E_CAPACITY; }
+    std::vector<PairWin> wins;
+    long long wmax = nbp;              // blocks of the largest window: what bsum, bsum2, nzlist and pflag are sized by
+    if (windowed && nbp > h->window_blocks) {
+        pair_windows(nm, h->window_blocks, wins);
+        wmax = 0;
+        for (const PairWin &w : wins) wmax = std::max(wmax, w.nb);
+    } else
+        wins.push_back(PairWin{0, ngroups, 0, nbp});
+    // one flag byte per pair between the test and the ordered emission -- unless that array is out of reach (k_pair_retest_emit below)
+    auto ensure_pflag = [&]() -> int {
+        if ((size_t)wmax * PB > h->pflagcap) { size_t nc = std::max((size_t)wmax * PB, h->pflagcap * 2); if ((rc = grow(&h->pflag, 0, nc, s))) return rc; h->pflagcap = nc; }
+        return 0;
+    };
+    bool noflags = false;
+    if ((rc = ensure_bsum(h, (int)wmax + 1))) return rc;
+    if ((size_t)W * nm > h->bitscap) { size_t nc = std::max((size_t)W * nm, h->bitscap * 2); if ((rc = grow(&h->bits, 0, nc, s))) return rc; h->bitscap = nc; }
+    // the scan of nb block sums; the total arrives through mailbox 2
+    auto scan_blocks = [&](int nb, Tri *tot) -> int {
+        const int seq = ++h->mailseq;
+        if (nb <= (1 << 16))
+            hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(1024), 0, s, h->bsum, nb, h->totals + 2, h->mail_d + 2, (const int *)nullptr, seq);
+        else {
+            const int nch = (int)(((long long)nb + 1023) / 1024);
+            if ((size_t)nch > h->bsum2cap) { size_t nc = std::max((size_t)nch, h->bsum2cap * 2); if ((rc = grow(&h->bsum2, 0, nc, s))) return rc; h->bsum2cap = nc; }
+            hipLaunchKernelGGL(k_scan_chunks, dim3(nch), dim3(1024), 0, s, h->bsum, nb, h->bsum2);
+            hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(1024), 0, s, h->bsum2, nch, h->totals + 2, h->mail_d + 2, (const int *)nullptr, seq);
+            hipLaunchKernelGGL(k_scan_add, dim3(nch), dim3(1024), 0, s, h->bsum, nb, (const Tri *)h->bsum2);
+        }
+        HIP_TRY(hipGetLastError());
+        if ((rc = wait_mail(h, 2, seq))) return rc;
+        *tot = h->mail_v[2].t;
+        return 0;
+    };
+    bool used_list = false, counted_noflag = false;
+    // appends the tp.a adjacent pairs of the blocks just scanned (those from virtual block vb0 on) at E[ecur][h->ne..)
+    auto emit_pairs = [&](const Tri tp, long long vb0) -> int {
+        if (tp.a <= 0) return 0;
+        if ((long long)h->ne + tp.a > 0x3FFFFF00ll) { set_error("polyhedron too large: more than 2^30 edges"); return BSLV_E_CAPACITY; }
+        if ((rc = ensure_ecap(h, h->ne + tp.a))) return rc;
+        if (noflags) {
+            hipLaunchKernelGGL(k_pair_retest_emit, dim3(4096), dim3(PB), lds_bits, s, h->d, (const unsigned long long *)h->bits, nm, W,
+                               fm ? (const int *)h->fm_cnt : (const int *)nullptr, fm ? (const int *)(h->fm_cnt + W * 64) : (const int *)nullptr, fm ? (const int *)h->fm_list : (const int *)nullptr,
+                               (const int *)h->members, (const int *)h->nzlist, (const int *)(h->nzlist + h->nzcap), (const Tri *)h->bsum, h->E[h->ecur], h->ne, h->EP[h->ecur], vb0);
+            if (!counted_noflag) h->n_noflag_prunes++;
+            counted_noflag = true;
+        } else if (used_list)
+            hipLaunchKernelGGL(k_pair_emit_list, dim3(4096), dim3(PB), 0, s, h->members, nm, (const int *)h->nzlist, (const int *)(h->nzlist + h->nzcap), (const unsigned char *)h->pflag,
+                               (const Tri *)h->bsum, h->E[h->ecur], h->ne, h->EP[h->ecur], vb0);
+        else
+            hipLaunchKernelGGL(k_pair_emit, dim3((unsigned)nbp), dim3(PB), 0, s, h->members, nm, (const PairBlk *)nullptr, h->pflag, h->bsum,
+                               h->E[h->ecur], h->ne, h->EP[h->ecur]);
+        HIP_TRY(hipGetLastError());
+        h->ne += tp.a;
+        return 0;
+    };
     if (lds_bits <= 48 * 1024) {
         HIP_TRY(hipMemsetAsync(h->nlocal, 0, sizeof(int), s));
         const int nbm = (nm * LPM + PB - 1) / PB;
         hipLaunchKernelGGL(k_local_ids, dim3(nbm), dim3(PB), 0, s, h->P, h->members, nm, W, stamp, h->fstamp, h->flocal, h->nlocal, h->bits);
         hipLaunchKernelGGL(k_build_bits, dim3(nbm), dim3(PB), 0, s, h->P, h->members, nm, W, h->flocal, h->bits);
-        // large facets: the row-tiled pair kernel (2-D grid), the list of pair blocks that hold an edge, and member lists by
-        // facet, so that confirming an edge scans one facet's elements instead of all nm
-        const size_t lds_tiled = ((size_t)PTI * W + (size_t)W * (PB + PTI) + 4 * (size_t)W) * sizeof(unsigned long long);
-        const int ngroups = (nm - 1 + PTI - 1) / PTI;
-        const bool tiled = nm >= h->fm_min && h->d > 1 && lds_tiled <= 48 * 1024;      // (more than 65535 row groups: several launches, below)
-        const bool fm = tiled && h->member_lists && len_ub <= (1ll << 30);
         // large facets: no flag array at all from 4 GiB of flags on (bslv_poly_debug_set key 16 / BSLV_K2_NOFLAGS=1: always, for the tests);
-        // not when the pair space is dealt to the ranks (each rank's share of the flags is a fraction)
+        // not when the pair space is dealt to the ranks (each rank's share of the flags is a fraction).  The rule looks at the whole
+        // facet, also when the prune runs in windows
         noflags = tiled && !(bslv_dist_world() > 1 && nm >= h->shard_min) && (h->k2_noflags || (size_t)nbp * PB >= ((size_t)4 << 30));
         if (!noflags && (rc = ensure_pflag())) return rc;
         if (tiled) {
-            if ((size_t)nbp > h->nzcap) { size_t nc = std::max((size_t)nbp, h->nzcap * 2); if (h->nzlist) (void)hipFree(h->nzlist); h->nzlist = nullptr; HIP_TRY(malloc0s(&h->nzlist, (nc + 1) * sizeof(int), s)); h->nzcap = nc; }
+            if ((size_t)wmax > h->nzcap) { size_t nc = std::max((size_t)wmax, h->nzcap * 2); if (h->nzlist) (void)hipFree(h->nzlist); h->nzlist = nullptr; HIP_TRY(malloc0s(&h->nzlist, (nc + 1) * sizeof(int), s)); h->nzcap = nc; }
             HIP_TRY(hipMemsetAsync(h->nzlist + h->nzcap, 0, sizeof(int), s));
         }
         if (fm) {
@@ -2764,26 +2866,42 @@ static int k2_multi(bslv_poly *h, int nm, long long len_ub, int stamp)
             hipLaunchKernelGGL(k_fm_fill, dim3(nbw), dim3(PB), 0, s, (const unsigned long long *)h->bits, nm, W, h->fm_cnt + 2 * nf, h->fm_list);
         }
         if (tiled) {
+            auto launch_flags = [&](int g0, int g1, long long vb0) {
+                for (int ga = g0; ga < g1; ga += 65535)          // (gridDim.y holds 65535 row groups: facets of more than 65535 * PTI elements take several launches)
+                    hipLaunchKernelGGL(k_pair_flags_tiled, dim3((unsigned)((nm - 1 + PB - 1) / PB), (unsigned)std::min(65535, g1 - ga)), dim3(PB), lds_tiled, s, h->d, h->bits, nm, W, noflags ? (unsigned char *)nullptr : h->pflag, h->bsum,
+                                       fm ? (const int *)h->fm_cnt : (const int *)nullptr, fm ? (const int *)(h->fm_cnt + W * 64) : (const int *)nullptr, fm ? (const int *)h->fm_list : (const int *)nullptr,
+                                       h->nzlist, h->nzlist + h->nzcap, ga, vb0);
+            };
+            if (!shard) {
+                // A WINDOW is a contiguous range of row groups, tested, scanned and emitted before the next one starts: what a rank's
+                // share of a sharded prune is, in time instead of across ranks.  Rows are enumerated lexicographically, so a window's
+                // blocks are contiguous in virtual-block order and the edges the windows append one after the other are the edge
+                // list a single pass writes.  The member lists and the bit matrix above serve every window.
+                used_list = true;
+                for (size_t k = 0; k < wins.size(); k++) {
+                    const PairWin &w = wins[k];
+                    if (k > 0) HIP_TRY(hipMemsetAsync(h->nzlist + h->nzcap, 0, sizeof(int), s));
+                    launch_flags(w.g0, w.g1, w.vb0);
+                    Tri tw;
+                    if ((rc = scan_blocks((int)w.nb, &tw))) return rc;
+                    if ((rc = emit_pairs(tw, w.vb0))) return rc;
+                }
+                if (wins.size() > 1) { h->n_win_prunes++; h->n_windows += (long)wins.size(); }
+                h->win_max_blocks = std::max(h->win_max_blocks, wmax);
+                return 0;
+            }
             // Multi-GPU: the PAIR SPACE of a large facet is dealt to the ranks -- contiguous row groups of equal pair
             // count -- every rank tests its share, and the adjacent pairs found (a few per element, not the nm^2 / 2 flags) are
             // all-gathered and appended in rank order = in the order of the virtual pair blocks, i.e. the edge list is the one a
             // single GPU writes.  Everything else of the cut stays replicated.
-            int g0 = 0, g1 = ngroups;
             const int world = bslv_dist_world(), rank = bslv_dist_rank();
-            shard = world > 1 && nm >= h->shard_min;
-            if (shard) {
-                const double total = 0.5 * (double)(nm - 1) * (double)nm;
-                auto before = [&](int g) { const double r = std::min((double)g * PTI, (double)(nm - 1)); return r * (double)(nm - 1) - 0.5 * r * (r - 1.0); };   // pairs in the rows of groups < g
-                auto bound = [&](int k) { if (k <= 0) return 0; if (k >= world) return ngroups; int lo = 0, hi = ngroups; const double want = total * k / world;
-                                          while (lo < hi) { const int mid = (lo + hi) / 2; if (before(mid) < want) lo = mid + 1; else hi = mid; } return lo; };
-                g0 = bound(rank); g1 = bound(rank + 1);
-                HIP_TRY(hipMemsetAsync(h->bsum, 0, (size_t)nbp * sizeof(Tri), s));          // the blocks of the other ranks: no pair
-                h->n_sharded++;
-            }
-            for (int ga = g0; ga < g1; ga += 65535)          // (gridDim.y holds 65535 row groups: facets of more than 65535 * PTI elements take several launches)
-                hipLaunchKernelGGL(k_pair_flags_tiled, dim3((unsigned)((nm - 1 + PB - 1) / PB), (unsigned)std::min(65535, g1 - ga)), dim3(PB), lds_tiled, s, h->d, h->bits, nm, W, noflags ? (unsigned char *)nullptr : h->pflag, h->bsum,
-                                   fm ? (const int *)h->fm_cnt : (const int *)nullptr, fm ? (const int *)(h->fm_cnt + W * 64) : (const int *)nullptr, fm ? (const int *)h->fm_list : (const int *)nullptr,
-                                   h->nzlist, h->nzlist + h->nzcap, ga);
+            const double total = 0.5 * (double)(nm - 1) * (double)nm;
+            auto before = [&](int g) { const double r = std::min((double)g * PTI, (double)(nm - 1)); return r * (double)(nm - 1) - 0.5 * r * (r - 1.0); };   // pairs in the rows of groups < g
+            auto bound = [&](int k) { if (k <= 0) return 0; if (k >= world) return ngroups; int lo = 0, hi = ngroups; const double want = total * k / world;
+                                      while (lo < hi) { const int mid = (lo + hi) / 2; if (before(mid) < want) lo = mid + 1; else hi = mid; } return lo; };
+            HIP_TRY(hipMemsetAsync(h->bsum, 0, (size_t)nbp * sizeof(Tri), s));          // the blocks of the other ranks: no pair
+            h->n_sharded++;
+            launch_flags(bound(rank), bound(rank + 1), 0);
         }
         else {
             // one-dimensional grid of pair blocks: at most 2^32 work-items (the runtime wraps a larger grid silently)
@@ -2797,19 +2915,8 @@ static int k2_multi(bslv_poly *h, int nm, long long len_ub, int stamp)
         if ((long long)nbp * PB >= (1ll << 32)) { set_error("new facet has too many elements (%d) for the one-dimensional pair launch", nm); return BSLV_E_CAPACITY; }
         hipLaunchKernelGGL(k_pair_flags, dim3((unsigned)nbp), dim3(PB), 0, s, h->P, h->members, nm, (const PairBlk *)nullptr, h->pflag, h->bsum);
     }
-    const int seq = ++h->mailseq;
-    if (nbp <= (1 << 16))
-        hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(1024), 0, s, h->bsum, (int)nbp, h->totals + 2, h->mail_d + 2, (const int *)nullptr, seq);
-    else {
-        const int nch = (int)((nbp + 1023) / 1024);
-        if ((size_t)nch > h->bsum2cap) { size_t nc = std::max((size_t)nch, h->bsum2cap * 2); if ((rc = grow(&h->bsum2, 0, nc, s))) return rc; h->bsum2cap = nc; }
-        hipLaunchKernelGGL(k_scan_chunks, dim3(nch), dim3(1024), 0, s, h->bsum, (int)nbp, h->bsum2);
-        hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(1024), 0, s, h->bsum2, nch, h->totals + 2, h->mail_d + 2, (const int *)nullptr, seq);
-        hipLaunchKernelGGL(k_scan_add, dim3(nch), dim3(1024), 0, s, h->bsum, (int)nbp, (const Tri *)h->bsum2);
-    }
-    HIP_TRY(hipGetLastError());
-    if ((rc = wait_mail(h, 2, seq))) return rc;
-    const Tri tp = h->mail_v[2].t;
+    Tri tp;
+    if ((rc = scan_blocks((int)nbp, &tp))) return rc;
     if (shard) {
         // this rank's pairs into a staging list, counts and pairs all-gathered (8 bytes per pair, carried as the bit pattern of a double)
         const int world = bslv_dist_world();
@@ -2820,7 +2927,7 @@ static int k2_multi(bslv_poly *h, int nm, long long len_ub, int stamp)
             if ((size_t)tp.a > h->shardcap) { const size_t nc = std::max<size_t>((size_t)tp.a, std::max<size_t>(4096, h->shardcap * 2)); if ((rc = grow(&h->shard_e, 0, nc, s))) return rc; h->shardcap = nc; }
             if (tp.a > 0)
                 hipLaunchKernelGGL(k_pair_emit_list, dim3(4096), dim3(PB), 0, s, h->members, nm, (const int *)h->nzlist, (const int *)(h->nzlist + h->nzcap), (const unsigned char *)h->pflag,
-                                   (const Tri *)h->bsum, h->shard_e, 0, (int *)nullptr);
+                                   (const Tri *)h->bsum, h->shard_e, 0, (int *)nullptr, 0ll);
             HIP_TRY(hipGetLastError());
             if (tp.a > 0) HIP_TRY(hipMemcpyAsync(mine.data(), h->shard_e, (size_t)tp.a * sizeof(int2), hipMemcpyDeviceToHost, s));
             HIP_TRY(hipStreamSynchronize(s));
@@ -2851,26 +2958,7 @@ static int k2_multi(bslv_poly *h, int nm, long long len_ub, int stamp)
         }
         return 0;
     }
-    if (tp.a > 0) {
-        if ((long long)h->ne + tp.a > 0x3FFFFF00ll) { set_error("polyhedron too large: more than 2^30 edges"); return BSLV_E_CAPACITY; }
-        if ((rc = ensure_ecap(h, h->ne + tp.a))) return rc;
-        if (noflags) {
-            const int Wn = (int)((std::min<long long>(len_ub, (long long)h->facet_of_rank.size()) + 63) / 64);
-            const bool fmn = h->member_lists && len_ub <= (1ll << 30);
-            hipLaunchKernelGGL(k_pair_retest_emit, dim3(4096), dim3(PB), (size_t)Wn * 5 * sizeof(unsigned long long), s, h->d, (const unsigned long long *)h->bits, nm, Wn,
-                               fmn ? (const int *)h->fm_cnt : (const int *)nullptr, fmn ? (const int *)(h->fm_cnt + Wn * 64) : (const int *)nullptr, fmn ? (const int *)h->fm_list : (const int *)nullptr,
-                               (const int *)h->members, (const int *)h->nzlist, (const int *)(h->nzlist + h->nzcap), (const Tri *)h->bsum, h->E[h->ecur], h->ne, h->EP[h->ecur]);
-            h->n_noflag_prunes++;
-        } else if (used_list)
-            hipLaunchKernelGGL(k_pair_emit_list, dim3(4096), dim3(PB), 0, s, h->members, nm, (const int *)h->nzlist, (const int *)(h->nzlist + h->nzcap), (const unsigned char *)h->pflag,
-                               (const Tri *)h->bsum, h->E[h->ecur], h->ne, h->EP[h->ecur]);
-        else
-        hipLaunchKernelGGL(k_pair_emit, dim3((unsigned)nbp), dim3(PB), 0, s, h->members, nm, (const PairBlk *)nullptr, h->pflag, h->bsum,
-                           h->E[h->ecur], h->ne, h->EP[h->ecur]);
-        HIP_TRY(hipGetLastError());
-        h->ne += tp.a;
-    }
-    return 0;
+    return emit_pairs(tp, 0);
 }
 
 // waits for the adjacency prune still in flight (k2_fused of the previous cut) and books its edges; when the
@@ -3321,6 +3409,7 @@ int bslv_poly_create(bslv_poly **out, int dim, int v2h, const double *c)
     if (const char *e = getenv("BSLV_POLY_SNAP")) h->snap = atoi(e) != 0;
     if (const char *e = getenv("BSLV_CROSS_UB")) h->cross_ub = std::max(0, atoi(e));
     if (const char *e = getenv("BSLV_K2_LDS")) h->k2_lds = (size_t)std::max(64, atoi(e));      // test hook: a small value forces the multi-kernel prune
+    if (const char *e = getenv("BSLV_K2_WINDOW")) { const long long v = atoll(e); if (v > 0) h->window_blocks = std::min(v, PAIR_WINDOW_DEFAULT); }
     if (getenv("BSLV_K2_DEBUG") && malloc0(&h->k2dbg, 16 * sizeof(unsigned long long)) == hipSuccess) (void)hipMemset(h->k2dbg, 0, 16 * sizeof(unsigned long long));
     h->rounds = new RoundsBuf();
     // dual slot 0: "facet at infinity", ideal point (0,..,0,-1)  (bslv_poly.c:83-92)
@@ -3847,6 +3936,60 @@ int bslv_poly_snapped(bslv_poly *h, long *moved)
 }
 int bslv_poly_largest_facet(const bslv_poly *h) { return h ? h->largest_facet : 0; }      // members of the largest new facet that went through the multi-kernel prune
 long bslv_poly_noflag_prunes(const bslv_poly *h) { return h ? h->n_noflag_prunes : 0; }      // large-facet prunes that emitted by testing the listed pair blocks again (no flag byte per pair)
+// windows of the large-facet prune (k2_multi): the most pair blocks one window may hold; 0 = the default, 0x7FFFFFF0
+int bslv_poly_set_prune_window(bslv_poly *h, long blocks)
+{
+    if (!h || blocks < 0) return BSLV_E_ARG;
+    h->window_blocks = blocks == 0 ? PAIR_WINDOW_DEFAULT : std::min<long long>(blocks, PAIR_WINDOW_DEFAULT);
+    return 0;
+}
+long bslv_poly_get_prune_window(const bslv_poly *h) { return h ? (long)h->window_blocks : 0; }
+int bslv_poly_prune_window_stats(const bslv_poly *h, long out[3])
+{
+    if (!h || !out) return BSLV_E_ARG;
+    out[0] = h->n_win_prunes; out[1] = h->n_windows; out[2] = (long)h->win_max_blocks;
+    return 0;
+}
+// The index arithmetic of a windowed prune without a polyhedron: the host builds the window table of a facet of nm members and
+// checks it, a kernel maps `samples` hashed pairs to (window, relative block id) and back (k_selftest_pair_blocks).
+// out[0] windows, [1] pair blocks in total, [2] pairs that did not come back as (i, i + 1 + 256 c), [3] the largest relative id.
+int bslv_selftest_pair_blocks(int nm, long window_blocks, int samples, long out[4])
+{
+    if (nm < 2 || window_blocks < 0 || samples < 1 || !out) return BSLV_E_ARG;
+    const long long wb = window_blocks == 0 ? PAIR_WINDOW_DEFAULT : std::min<long long>(window_blocks, PAIR_WINDOW_DEFAULT);
+    const long long total = pair_G(nm - 1);
+    std::vector<PairWin> wins;
+    pair_windows(nm, wb, wins);
+    long long at = 0, wmax = 0; int g = 0;
+    for (const PairWin &w : wins) {
+        const long long one = pair_S(nm, (long long)(w.g0 + 1) * PTI) - w.vb0;          // its first row group alone
+        if (w.g0 != g || w.g1 <= w.g0 || w.vb0 != at || w.nb < 1 || w.nb > std::max(wb, one) || w.nb - 1 >= (1ll << 31)) {
+            set_error("pair windows of %d members: window [%d, %d) at block %lld with %lld blocks breaks the table (expected group %d at block %lld, at most %lld blocks)",
+                      nm, w.g0, w.g1, w.vb0, w.nb, g, at, std::max(wb, one));
+            return BSLV_E_STATE;
+        }
+        g = w.g1; at += w.nb; wmax = std::max(wmax, w.nb);
+    }
+    if (g != (nm - 1 + PTI - 1) / PTI || at != total) { set_error("pair windows of %d members cover %lld of %lld blocks", nm, at, total); return BSLV_E_STATE; }
+    std::vector<long long> vb0s(wins.size());
+    for (size_t k = 0; k < wins.size(); k++) vb0s[k] = wins[k].vb0;
+    long long *vb0_d = nullptr; unsigned long long *bad_d = nullptr, bad = 0;
+    auto cleanup = [&]() { if (vb0_d) (void)hipFree(vb0_d); if (bad_d) (void)hipFree(bad_d); };
+    if (hipMalloc((void **)&vb0_d, vb0s.size() * sizeof(long long)) != hipSuccess || hipMalloc((void **)&bad_d, sizeof(unsigned long long)) != hipSuccess) {
+        cleanup(); set_error("bslv_selftest_pair_blocks: allocation failed"); return BSLV_E_NOMEM;
+    }
+    hipError_t e = hipMemcpy(vb0_d, vb0s.data(), vb0s.size() * sizeof(long long), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(bad_d, 0, sizeof(unsigned long long));
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_selftest_pair_blocks, dim3((unsigned)((samples + PB - 1) / PB)), dim3(PB), 0, 0, nm, (const long long *)vb0_d, (int)wins.size(), samples, bad_d);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(&bad, bad_d, sizeof bad, hipMemcpyDeviceToHost);
+    cleanup();
+    if (e != hipSuccess) { set_error("bslv_selftest_pair_blocks: %s", hipGetErrorString(e)); return BSLV_E_NODEVICE; }
+    out[0] = (long)wins.size(); out[1] = (long)total; out[2] = (long)bad; out[3] = (long)(wmax - 1);
+    return 0;
+}
 long bslv_poly_rounds2_late_left(const bslv_poly *h) { return h ? h->r2_late_left : 0; }
 long bslv_poly_rounds2_torn_reads(const bslv_poly *h) { return h ? h->r2_torn_reads + h->mail_torn_reads : 0; }      // (both kinds of mailbox)
 

@@ -117,6 +117,33 @@ class PolyEngine:
         self.lib.bslv_poly_sharded_prunes.argtypes = [ctypes.c_void_p]
         return self.lib.bslv_poly_sharded_prunes(self.h)
 
+    def set_prune_window(self, blocks):
+        """the most pair blocks (one row, 256 columns) a window of a large facet's adjacency prune may hold; 0 = default"""
+        self.lib.bslv_poly_set_prune_window.argtypes = [ctypes.c_void_p, ctypes.c_long]
+        check(self.lib.bslv_poly_set_prune_window(self.h, int(blocks)))
+
+    def get_prune_window(self):
+        self.lib.bslv_poly_get_prune_window.restype = ctypes.c_long
+        self.lib.bslv_poly_get_prune_window.argtypes = [ctypes.c_void_p]
+        return self.lib.bslv_poly_get_prune_window(self.h)
+
+    def prune_window_stats(self):
+        """(prunes that ran in more than one window, their windows in total, most pair blocks any window held)"""
+        out = (ctypes.c_long * 3)()
+        self.lib.bslv_poly_prune_window_stats.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        check(self.lib.bslv_poly_prune_window_stats(self.h, out))
+        return list(out)
+
+    @staticmethod
+    def selftest_pair_blocks(nm, window_blocks=0, samples=100000):
+        """index arithmetic of a windowed prune of a facet of nm members, no polyhedron needed:
+        [windows, pair blocks in total, sampled pairs mapped wrongly, largest relative block id]"""
+        lib = load_library()
+        out = (ctypes.c_long * 4)()
+        lib.bslv_selftest_pair_blocks.argtypes = [ctypes.c_int, ctypes.c_long, ctypes.c_int, ctypes.c_void_p]
+        check(lib.bslv_selftest_pair_blocks(int(nm), int(window_blocks), int(samples), out))
+        return list(out)
+
     def set_snap(self, on=1):
         """the projection sub-band of poly__cut (bslv_poly.c:666-674); cuts are then applied one at a time"""
         self.lib.bslv_poly_set_snap.argtypes = [ctypes.c_void_p, ctypes.c_int]

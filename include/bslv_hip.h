@@ -329,6 +329,21 @@ int  bslv_poly_set_snap(bslv_poly *h, int on);
 int  bslv_poly_snapped(bslv_poly *h, long *moved);        /* elements moved so far */
 int  bslv_poly_largest_facet(const bslv_poly *h);     /* members of the largest new facet that went through the multi-kernel prune */
 long bslv_poly_noflag_prunes(const bslv_poly *h);      /* large-facet prunes that kept no flag byte per pair (k_pair_retest_emit) */
+/* The multi-kernel prune of a large new facet (row-tiled pair kernel) walks the pair space in WINDOWS: contiguous ranges of row groups
+ * (8 rows each), each tested, scanned and emitted before the next one starts.  A pair block is one row i with 256 columns j > i; block
+ * ids are 64-bit on the host and 32-bit relative to the window on the device, and the scratch arrays (16 B per block) are sized by the
+ * largest window, so a facet of any number of pair blocks is pruned.  The edge list is the one a single pass writes, bit for bit.
+ * bslv_poly_set_prune_window: blocks > 0 = the most pair blocks a window may hold (values above the default are taken as the default;
+ * a single row group larger than `blocks` still forms a window), 0 = the default, 0x7FFFFFF0: every facet below 2^31 blocks (about
+ * 1.05 M members) runs in one window, exactly as without windows.  blocks < 0 is BSLV_E_ARG and changes nothing.  Also
+ * BSLV_K2_WINDOW=blocks, read when a polyhedron engine is created (also those bslv_benson_create* and bslv_vlp_solve_* create): the
+ * knob for a card with less free memory than 16 B x 2^31.  The one-dimensional pair launches, the sorted-list path and a prune whose
+ * pair space is dealt to the ranks ignore the window and keep their 32-bit caps (BSLV_E_CAPACITY).
+ * bslv_poly_prune_window_stats: out[0] prunes that ran in more than one window, [1] the windows of those prunes in total, [2] the
+ * largest number of pair blocks any window held (one-window prunes of the tiled path included). */
+int  bslv_poly_set_prune_window(bslv_poly *h, long blocks);
+long bslv_poly_get_prune_window(const bslv_poly *h);
+int  bslv_poly_prune_window_stats(const bslv_poly *h, long out[3]);
 /* cuts that were still untouched when a chunk's rounds ended on "no cut alive" and were handed to the one-cut pipeline instead
  * (0 in every run but one of round 2's test runs; kept as a counter so that it cannot hide) */
 long bslv_poly_rounds2_late_left(const bslv_poly *h);
@@ -390,6 +405,13 @@ int  bslv_poly_get_dual_edges(bslv_poly *h, int *ab);
  * messages with the sequence number FIRST and the content afterwards; 0 = every message was taken with its own content
  * (*torn_out: reads that had to be repeated), negative = a reader accepted foreign content.  which: 0 Mail, 1 round state */
 int  bslv_selftest_mailbox(int which, int rounds, long *torn_out);
+/* self-test of the index arithmetic of a windowed prune (needs a GPU, no polyhedron): the host builds the window table of a facet of
+ * nm >= 2 members for window_blocks (0 = default, as bslv_poly_set_prune_window) and checks that the windows are contiguous, cover all
+ * G(nm-1) pair blocks, hold at most max(window_blocks, their single row group) blocks each and keep every relative id below 2^31
+ * (BSLV_E_STATE otherwise); a kernel takes `samples` hashed pairs i < j < nm, forms the virtual block as the pair kernel does, maps it
+ * to (window, relative id) and back as the emission kernels do.  out[0] windows, [1] pair blocks in total, [2] pairs that did not come
+ * back as (i, i + 1 + 256 c), [3] the largest relative id.  The only place where block ids beyond 2^32 run in milliseconds. */
+int  bslv_selftest_pair_blocks(int nm, long window_blocks, int samples, long out[4]);
 
 /* ------------------------------------------------------------------------------------------
  * 4. Batched Benson phase-2 driver  (replaces phase2_primal's loop, bslv_algs.c:958-1082,
