@@ -3,10 +3,13 @@ oracle's primal simplex, oracle/lp_dense.c) and a certificate of optimality that
 
 random_lp                      one LP: feasible around a point, infeasible or unbounded by construction, or "wild"
 general_set                    one model and 16 LPs that differ only in the bounds of a per-LP range (tests/test_lp_general_gpu.py)
+objective_set                  the model of a shape with a zero cost and 3 x 16 cost vectors over a range of variables, rows included
+                               (tests/test_lp_obj_general_gpu.py); unbounded_objective_set: some of them unbounded
 certify / assert_certified     residuals of a returned solution in np.longdouble, and the project's bounds on them
 
 Run as a program (`python tests/lp_cases.py [M N ...]`) it solves every LP of every set with both yardsticks, asserts that they agree
-and prints the oracle's residuals per shape: the check made when the seeds were chosen."""
+and prints the oracle's residuals per shape: the check made when the seeds were chosen.  `python tests/lp_cases.py obj [M N ...]` does
+the same for the objective sets, per shape and cost range."""
 import os
 import sys
 
@@ -203,10 +206,15 @@ FAR = (10, 12, 14)
 COL_FIRST = 1               # arrangement "b": the range starts at this (odd) column
 
 
+def model_seed(M, N):
+    """of general_model: GENERAL_SEEDS', or OBJECTIVE_SEEDS' (below) for the shapes that only the objective sets have"""
+    return GENERAL_SEEDS[(M, N)] if (M, N) in GENERAL_SEEDS else OBJECTIVE_SEEDS[(M, N)]
+
+
 def general_model(M, N):
     """the model of a shape: random_lp's feasible and bounded LP, with rows 0 and 1 made a pair with equal coefficients (row 0 bounded
     below, row 1 above) on three boxed columns and one column that starts on an artificial bound.  Returns a dict with A, cost, lo, up, x0 and the bound types of rows and columns."""
-    rng = np.random.default_rng(GENERAL_SEEDS[(M, N)])
+    rng = np.random.default_rng(model_seed(M, N))
     A, lo, up, cost, x0, tr, tc = random_lp(M, N, rng, "feasible", bounded=True, parts=True)
     cols = list(PAIR_COLS)
     A[0] = 0.0
@@ -337,7 +345,182 @@ def assert_references_agree(M, N, arr):
     return rows, w
 
 
+# ---- the objective sets ----------------------------------------------------------------------------------------------------
+# Shapes that only the objective sets have, (M, N) -> seed of general_model.  Chosen on the CPU (python tests/lp_cases.py obj): both
+# yardsticks call all 48 LPs of every set OPTIMAL and agree, and the conditions of assert_objective_references_agree hold.
+OBJECTIVE_SEEDS = {(24, 512): 13, (24, 513): 14, (24, 1024): 15, (24, 1025): 16, (24, 8192): 17, (24, 8193): 18}
+OBJ_SHAPES = [(15, 16), (16, 17), (31, 64), (32, 65), (33, 257), (24, 512), (24, 513), (24, 1024), (24, 1025), (24, 1120), (24, 1121),
+              (24, 1535), (24, 1536), (24, 2048), (24, 2049), (24, 4100), (24, 8192), (24, 8193)]
+OBJ_RANGES = ("cols", "straddle", "head")
+GENS = ("gen1", "gen2", "gen3")
+UNB_LPS = {2: 1.0, 9: 1.0, 5: -1.0}         # unbounded_objective_set: LP -> the cost of the free column without a row
+
+
+def obj_ranges(M, N):
+    """the cost ranges a shape runs: a slot of the two largest shapes is 2 MB, they run "cols" only"""
+    return ("cols",) if N >= 8192 else OBJ_RANGES
+
+
+def cost_range(M, N, rng_name):
+    """(cost_first, cost_cnt) in the engine's numbering: rows 0 .. M-1, columns M .. M+N-1"""
+    return {"cols": (M, N), "straddle": (M - 3, 8), "head": (M + 1, 5)}[rng_name]
+
+
+def _signed(c, lo, up):
+    """costs that pull no variable where it has no bound: f -> 0, l -> |c|, u -> -|c|, d and s as drawn"""
+    flo, fup = np.isfinite(lo), np.isfinite(up)
+    return np.where(flo & fup, c, np.where(flo, np.abs(c), np.where(fup, -np.abs(c), 0.0)))
+
+
+def fold(A, first, c):
+    """the cost vector (N + 1, no shift) of the columns alone that is the same function on r = A x as the costs c on the variables
+    first .. first + len(c) - 1: c'_cols = c_cols + A' c_rows"""
+    M, N = A.shape
+    full = np.zeros(M + N)
+    full[first:first + len(c)] = c
+    return np.concatenate([[0.0], full[M:] + A.T @ full[:M]])
+
+
+_OSETS = {}
+
+
+def objective_set(M, N, rng_name):
+    """The model of general_model(M, N) with a zero engine cost and NLP cost vectors over one range of variables in each of three
+    generations: gen1 rounded normal values times 3, signed by the bound type of the variable that carries them (row or column), every
+    fourth vector with 70 % of its entries zeroed (ties, and variables of the range without a cost); gen2 is gen1 permuted by `perm`
+    (LP b of gen2 has the costs of LP perm[b] of gen1) times uniform(0.9, 1.1) entrywise; gen3 is gen2 times uniform(0.95, 1.05).
+    Returns a dict: the model, cost_first, cost_cnt, costs (gen -> NLP x cost_cnt), folded (gen -> the NLP folded cost vectors the
+    yardsticks and the certificate take) and perm."""
+    key = (M, N, rng_name)
+    if key in _OSETS:
+        return _OSETS[key]
+    m = general_model(M, N)
+    A, lo, up = m["A"], m["lo"], m["up"]
+    first, cnt = cost_range(M, N, rng_name)
+    assert 0 <= first and first + cnt <= M + N
+    rng = np.random.default_rng(model_seed(M, N) * 1000 + 10 + OBJ_RANGES.index(rng_name))
+    vl, vu = lo[first:first + cnt], up[first:first + cnt]
+    c1 = _signed(np.round(rng.normal(size=(NLP, cnt)) * 3), vl, vu)
+    for t in range(3, NLP, 4):
+        c1[t, rng.random(cnt) < 0.7] = 0.0
+    perm = (np.arange(NLP) * 7 + 3) % NLP         # (general_set's)
+    c2 = c1[perm] * rng.uniform(0.9, 1.1, size=(NLP, cnt))
+    c3 = c2 * rng.uniform(0.95, 1.05, size=(NLP, cnt))
+    costs = dict(gen1=c1, gen2=c2, gen3=c3)
+    for c in costs.values():
+        assert np.array_equal(c, _signed(c, vl, vu))
+    folded = {g: [fold(A, first, c) for c in costs[g]] for g in GENS}
+    out = dict(m, cost=np.zeros(N + 1), rng_name=rng_name, cost_first=first, cost_cnt=cnt, costs=costs, folded=folded, perm=perm)
+    _OSETS[key] = out
+    return out
+
+
+def unbounded_objective_set(M, N):
+    """unbounded_model(M, N) -- column 0 in no row and free -- with a zero engine cost and NLP cost vectors over the columns 0, 1, 2:
+    (+1, 0, 0) or (-1, 0, 0) for the LPs of UNB_LPS, which are UNBOUNDED, and (0, c1, c2), signed by type, for the others"""
+    A, lo, up, _ = unbounded_model(M, N)
+    first, cnt = M, 3
+    rng = np.random.default_rng(model_seed(M, N) * 1000 + 20)
+    c = _signed(np.round(rng.normal(size=(NLP, cnt)) * 3), lo[first:first + cnt], up[first:first + cnt])
+    c[:, 0] = 0.0
+    for t, v in UNB_LPS.items():
+        c[t] = (v, 0.0, 0.0)
+    return dict(M=M, N=N, A=A, lo=lo, up=up, cost=np.zeros(N + 1), cost_first=first, cost_cnt=cnt, costs=c, folded=[fold(A, first, v) for v in c])
+
+
+def _reference_rows(A, lo, up, folded):
+    rows = []
+    for c in folded:
+        so, zo, po, do = oracle_solution(A, lo, up, c)
+        sh, zh = highs(A, lo, up, c)
+        rows.append(dict(st=so, obj=zo, st_highs=sh, obj_highs=zh, prim=po, dual=do, cert=certify(A, lo, up, c, so, zo, po, do)))
+    return rows
+
+
+_OREF = {}
+
+
+def objective_references(M, N, rng_name):
+    """the 3 x NLP LPs of an objective set with the answers of both yardsticks (for the folded costs), the oracle's solution and its own
+    certificate, computed once and shared: gen -> rows of dict(st, obj, st_highs, obj_highs, prim, dual, cert), and the oracle's worst
+    residuals over the set"""
+    key = (M, N, rng_name)
+    if key not in _OREF:
+        s = objective_set(M, N, rng_name)
+        ref = {g: _reference_rows(s["A"], s["lo"], s["up"], s["folded"][g]) for g in GENS}
+        _OREF[key] = (ref, worst([r["cert"] for g in GENS for r in ref[g]]))
+    return _OREF[key]
+
+
+def _assert_rows_agree(rows, tag):
+    for t, r in enumerate(rows):
+        assert r["st"] == r["st_highs"], (tag, t, r["st"], r["st_highs"])
+        if r["st"] == OPTIMAL:
+            np.testing.assert_allclose(r["obj"], r["obj_highs"], rtol=RTOL, atol=1e-9, err_msg=str((tag, t)))
+            assert_certified(r["cert"], r["obj"], r["cert"]["gap"], ("oracle", tag, t))
+
+
+def assert_objective_references_agree(M, N, rng_name):
+    """what the tests assert of the yardsticks, and of the inputs, before they look at the engine: all 48 LPs OPTIMAL for both, equal
+    values, the oracle's solutions certified; in the union of the optimal points some boxed column on its upper and some on its lower
+    bound, each with a non-zero reduced cost (places for bound flips); "cols": at least a quarter of the columns that carry a cost are
+    nonbasic (a non-zero reduced cost, or more cost-carrying columns than the M a basis holds).  Returns (references, worst residuals, a dict of these counts)."""
+    ref, w = objective_references(M, N, rng_name)
+    s = objective_set(M, N, rng_name)
+    lo, up = s["lo"][M:], s["up"][M:]
+    boxed = np.isfinite(lo) & np.isfinite(up) & (lo < up)
+    at_up = at_lo = 0
+    carrying = nonbasic = 0
+    for g in GENS:
+        _assert_rows_agree(ref[g], (M, N, rng_name, g))
+        for t, r in enumerate(ref[g]):
+            assert r["st"] == OPTIMAL, (M, N, rng_name, g, t, r["st"])
+            x, d = r["prim"][M:], r["dual"][M:]
+            at_up += int(np.sum(boxed & (d < -DUAL_ZERO) & (np.abs(x - up) <= TOL_SIDE)))
+            at_lo += int(np.sum(boxed & (d > DUAL_ZERO) & (np.abs(x - lo) <= TOL_SIDE)))
+            if rng_name == "cols":
+                c = s["costs"][g][t] != 0.0
+                carrying += int(c.sum())
+                nonbasic += max(int(np.sum(c & (np.abs(d) > DUAL_ZERO))), int(c.sum()) - M)
+    assert at_up > 0 and at_lo > 0, (M, N, rng_name, at_up, at_lo)
+    if rng_name == "cols":
+        assert 4 * nonbasic >= carrying, (M, N, rng_name, nonbasic, carrying)
+    return ref, w, dict(boxed_at_up=at_up, boxed_at_lo=at_lo, carrying=carrying, nonbasic=nonbasic)
+
+
+_UREF = {}
+
+
+def unbounded_objective_references(M, N):
+    """rows as objective_references' for unbounded_objective_set, asserted: the LPs of UNB_LPS UNBOUNDED, the others OPTIMAL, for both
+    yardsticks; and the oracle's worst residuals over the OPTIMAL ones"""
+    if (M, N) not in _UREF:
+        s = unbounded_objective_set(M, N)
+        rows = _reference_rows(s["A"], s["lo"], s["up"], s["folded"])
+        _assert_rows_agree(rows, (M, N, "unbounded"))
+        for t, r in enumerate(rows):
+            assert r["st"] == (UNBOUNDED if t in UNB_LPS else OPTIMAL), (M, N, t, r["st"])
+        _UREF[(M, N)] = (rows, worst([r["cert"] for r in rows]))
+    return _UREF[(M, N)]
+
+
+def _main_obj(shapes):
+    for M, N in shapes:
+        for rng_name in obj_ranges(M, N):
+            ref, w, n = assert_objective_references_agree(M, N, rng_name)
+            print("lp_obj_general_residuals oracle M %d N %d range %s statuses %s boxed at up %d at lo %d%s rows %.3e feas %.3e dj %.3e side %.3e gap %.3e" % (
+                M, N, rng_name, " ".join("".join(str(r["st"]) for r in ref[g]) for g in GENS), n["boxed_at_up"], n["boxed_at_lo"],
+                " nonbasic %d of %d" % (n["nonbasic"], n["carrying"]) if rng_name == "cols" else "", w["rows"], w["feas"], w["dj"], w["side"], w["gap"]), flush=True)
+        if N < 8192:
+            rows, w = unbounded_objective_references(M, N)
+            print("lp_obj_general_residuals oracle M %d N %d unbounded objectives statuses %s gap %.3e" % (M, N, "".join(str(r["st"]) for r in rows), w["gap"]), flush=True)
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "obj":
+        v = [int(a) for a in sys.argv[2:]]
+        _main_obj(list(zip(v[0::2], v[1::2])) if v else OBJ_SHAPES)
+        sys.exit(0)
     shapes = list(GENERAL_SEEDS)
     if len(sys.argv) > 1:
         v = [int(a) for a in sys.argv[1:]]
