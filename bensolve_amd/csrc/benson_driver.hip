@@ -101,6 +101,11 @@ struct bslv_benson {
     long last_canon[4] = {0, 0, 0, 0}, tot_canon[4] = {0, 0, 0, 0};     // of the last solve_local / of all: bslv_lpq_last_canonical_stats
     // totals
     long tot_lps = 0, tot_cuts = 0, tot_pivots = 0;
+    // BSLV_POLY_CHECK=1: bslv_poly_check on the polyhedron after every apply(); the first result that is not clean is printed with the
+    // number of the outer iteration, the tally when the engine is destroyed (stderr).  Off by default: one flag test per apply().
+    bool poly_check = getenv("BSLV_POLY_CHECK") && atoi(getenv("BSLV_POLY_CHECK")) != 0;
+    long applies = 0, audits = 0, audits_dirty = 0, audit_sum[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};      // (audit_sum: the twelve counts added up over the audits)
+    double audit_ms = 0;
 };
 
 static int rec_len(const bslv_benson *h) { return h->q + 5; }
@@ -114,6 +119,12 @@ bslv_lpq *bslv_benson_lp(bslv_benson *h) { return h ? h->lp : nullptr; }
 void bslv_benson_destroy(bslv_benson *h)
 {
     if (!h) return;
+    if (h->poly_check) {
+        const long *a = h->audit_sum;
+        fprintf(stderr, "BSLV_POLY_CHECK: %ld audits after %ld outer iterations%s, %ld not clean, %.1f ms in all; summed over the audits: %ld bad and %ld unlisted incidences, %ld infeasible, "
+                "%ld bad and %ld duplicate edges, %ld missing and %ld extra among %ld adjacent pairs\n", h->audits, h->applies, h->hom ? " [homogeneous problem]" : "", h->audits_dirty, h->audit_ms,
+                a[3], a[4], a[5], a[7], a[8], a[10], a[11], a[9]);
+    }
     if (h->lp) bslv_lpq_destroy(h->lp);
     if (h->poly) bslv_poly_destroy(h->poly);
     delete h;
@@ -962,6 +973,23 @@ int bslv_benson_apply_ctx(bslv_benson *h, int ctx, int nrec, const double *recor
     h->tot_lps += nrec;
     h->tot_cuts += applied;
     if (stats) { stats[0] = nrec; stats[1] = applied; stats[2] = ncut - applied - handed_back + nduplicate; stats[3] = (long)confirmed.size(); stats[4] = nfail; }
+    h->applies++;
+    if (h->poly_check) {
+        const auto t0 = std::chrono::steady_clock::now();
+        long ck[12];
+        int offs[30], n_off = 0;
+        if ((rc = bslv_poly_check(h->poly, 0.0, 0, -1, ck, nullptr, offs, 10, &n_off))) return rc;
+        h->audit_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        h->audits++;
+        for (int k = 0; k < 12; k++) h->audit_sum[k] += ck[k];
+        if (ck[3] || ck[4] || ck[5] || ck[7] || ck[8] || ck[10] || ck[11]) {
+            if (h->audits_dirty++ == 0) {
+                fprintf(stderr, "BSLV_POLY_CHECK: outer iteration %ld (%d cuts handed in, %ld applied)%s: %ld elements, %ld facets, %ld incidences (%ld bad, %ld unlisted), %ld infeasible, %ld edges (%ld bad, %ld duplicate), "
+                        "%ld adjacent pairs (%ld missing, %ld extra)\n", h->applies, ncut, applied, h->hom ? " [homogeneous problem]" : "", ck[0], ck[1], ck[2], ck[3], ck[4], ck[5], ck[6], ck[7], ck[8], ck[9], ck[10], ck[11]);
+                for (int k = 0; k < n_off && k < 10; k++) fprintf(stderr, "BSLV_POLY_CHECK:   offender: kind %d (%d, %d)\n", offs[3 * k], offs[3 * k + 1], offs[3 * k + 2]);
+            }
+        }
+    }
     return 0;
 }
 

@@ -25,7 +25,9 @@ static void usage(void)
            "  -o, --output_filename F  base name of the result files (default: input name up to the first '.')\n"
            "  -m, --message_level N    0-3 (default 1)\n"
            "  -B, --batch N            LPs per outer iteration (default 1024)\n"
-           "  -k/-L/-l METHOD, -M N, -f FORMAT, -p, -t   accepted as in the reference's command line; the LP method is recorded in the\n"
+           "  -t, --test               audit the result polyhedron on the device after phase 2 (incidences, feasibility, the edge list\n"
+           "                           against the edge test over all pairs) and print one line: polyhedron check: ... ok, or the counts\n"
+           "  -k/-L/-l METHOD, -M N, -f FORMAT, -p   accepted as in the reference's command line; the LP method is recorded in the\n"
            "                           .log (every LP is solved by the engine's dual simplex), no graphics file is written\n"
            );
 }
@@ -91,7 +93,7 @@ int main(int argc, char **argv)
 {
     if (argc < 2 || argv[1][0] == '-') { usage(); return 1; }
     const char *file = argv[1];
-    int bounded = 0, msg = 1, batch = 1024, dual2 = 0, dual1 = 0, presol = 0, plot_asked = 0;
+    int bounded = 0, msg = 1, batch = 1024, dual2 = 0, dual1 = 0, presol = 0, plot_asked = 0, test_asked = 0;
     int lp_method[3] = {0, 0, 0};                  /* per phase: 0 as the reference's default, 1 primal_simplex, 2 dual_simplex, 3 dual_primal_simplex */
     double eps = 1e-7, eps1 = 1e-7;
     char base[1024] = "";
@@ -129,7 +131,7 @@ int main(int argc, char **argv)
         else if (!strcmp(o, "-M") || !strcmp(o, "--lp_message_level")) { const int v = atoi(ARG()); if (v < 0 || v > 3) { printf("option --lp_message_level (-M): invalid argument\n"); return 1; } }
         else if (!strcmp(o, "-f") || !strcmp(o, "--format")) { const char *v = ARG(); if (strcmp(v, "auto") && strcmp(v, "long") && strcmp(v, "short")) { printf("option --format (-f): invalid argument\n"); return 1; } }
         else if (!strcmp(o, "-p") || !strcmp(o, "--plot")) plot_asked = 1;
-        else if (!strcmp(o, "-t") || !strcmp(o, "--test")) { /* the reference's integrity tests of its own polytope lists: nothing to test here */ }
+        else if (!strcmp(o, "-t") || !strcmp(o, "--test")) test_asked = 1;          /* poly__polyck on the result (bslv_poly.c:940-990): below, after phase 2 */
         else if (!strcmp(o, "-h") || !strcmp(o, "--help")) { usage(); return 1; }
         else { printf("invalid option %s\n", o); return 1; }
     }
@@ -187,6 +189,18 @@ int main(int argc, char **argv)
     if (presol && h && (rc = bslv_sol_write_preimages(h, base, ".sol", v->m, v->n, v->optdir, info.c_dir))) { printf("writing the pre-images failed (%d): %s\n", rc, bslv_last_error()); return 3; }
     if (presol && lower && (rc = bslv_sol_write_preimages_dual(lower, base, ".sol", v->m, v->n, v->optdir, info.c_dir))) { printf("writing the pre-images failed (%d): %s\n", rc, bslv_last_error()); return 3; }
     if (h) bslv_benson_totals(h, &lps, &cuts, &piv);
+    if (test_asked && rank == 0) {                                        /* like the reference's check it reports and never aborts: exit status and .log stay */
+        long ck[12];
+        int offs[30], n_off = 0;
+        if (bslv_poly_check(dual2 ? lower : bslv_benson_poly(h), 0.0, 0, -1, ck, NULL, offs, 10, &n_off)) printf("polyhedron check: not run: %s\n", bslv_last_error());
+        else if (!(ck[3] || ck[4] || ck[5] || ck[7] || ck[8] || ck[10] || ck[11]))
+            printf("polyhedron check: %ld elements, %ld facets, %ld incidences, %ld edges, %ld adjacent pairs: ok\n", ck[0], ck[1], ck[2], ck[6], ck[9]);
+        else {
+            printf("polyhedron check: %ld elements, %ld facets, %ld incidences (%ld bad, %ld unlisted), %ld infeasible, %ld edges (%ld bad, %ld duplicate), %ld adjacent pairs (%ld missing, %ld extra): FAILED\n",
+                   ck[0], ck[1], ck[2], ck[3], ck[4], ck[5], ck[6], ck[7], ck[8], ck[9], ck[10], ck[11]);
+            for (int k = 0; k < n_off && k < 10; k++) printf("  offender: kind %d (%d, %d)\n", offs[3 * k], offs[3 * k + 1], offs[3 * k + 2]);
+        }
+    }
     {   /* <name>.log, fields and layout of bslv_main.c:346-397 */
         char lfile[1100];
         snprintf(lfile, sizeof lfile, "%s.log", base);

@@ -345,6 +345,34 @@ void poly__inc2file(polytope *poly, permutation *prm, permutation *prm_dual, con
 
 void poly__swap(poly_args *a, poly_args *b) { (void)a; (void)b; fprintf(stderr, "bslv_poly_compat: poly__swap serves the plot option only, which is not supported\n"); exit(3); }
 void poly__plot(polytope *poly, const char *fname) { (void)poly; (void)fname; fprintf(stderr, "bslv_poly_compat: poly__plot (option -p) is not supported\n"); exit(3); }
-void poly__polyck(poly_args *args) { (void)args; }
+// bslv_poly.c:940-990 on the engine behind args (bslv_poly_check): the reference's own messages for what it checks (an incidence that
+// is not geometric :956, a missing adjacency :983), one line each for what it does not.  Prints to stderr, never aborts.
+void poly__polyck(poly_args *args)
+{
+    Shadow *S = shadow_of(args);
+    push_caller_writes(S);
+    if (!args->init_data.intlsd) return;                        // (nothing but queued halfspaces yet: the reference's loops are empty too)
+    constexpr int MAXOFF = 256;
+    long ck[12];
+    std::vector<int> off(3 * MAXOFF);
+    int n_off = 0;
+    if (bslv_poly_check(S->eng, 0.0, 0, -1, ck, nullptr, off.data(), MAXOFF, &n_off)) { fprintf(stderr, "Error:\tpoly__polyck did not run: %s\n", bslv_last_error()); return; }
+    for (int k = 0; k < std::min(n_off, MAXOFF); k++) {
+        const int kind = off[3 * k], a = off[3 * k + 1], b = off[3 * k + 2];
+        switch (kind) {
+        case 3: if (b >= 0) fprintf(stderr, "Error:\tHyperplane %zu does not contain vertex %zu.\n", (size_t)b, (size_t)a);
+                else fprintf(stderr, "Error:\tVertex %zu: its incidence list holds an entry that is no hyperplane.\n", (size_t)a);
+                break;
+        case 4: fprintf(stderr, "Error:\tHyperplane %zu contains vertex %zu, which does not list it.\n", (size_t)b, (size_t)a); break;
+        case 5: fprintf(stderr, "Error:\tVertex %zu lies outside the halfspace of hyperplane %zu.\n", (size_t)a, (size_t)b); break;
+        case 7: fprintf(stderr, "Error:\tThe adjacence-lists hold the pair (%d, %d), which is no pair of vertices.\n", a, b); break;
+        case 8: fprintf(stderr, "Error:\tVertices %zu and %zu appear in each other's adjacence-list more than once.\n", (size_t)a, (size_t)b); break;
+        case 10: fprintf(stderr, "Error:\tVertices %zu and %zu are adjacent (due to their incidence relation), but vertex %zu does not apper in vertex' %zu adjacence-list.\n", (size_t)b, (size_t)a, (size_t)a, (size_t)b); break;
+        case 11: fprintf(stderr, "Error:\tVertices %zu and %zu are not adjacent (due to their incidence relation), but appear in each other's adjacence-list.\n", (size_t)a, (size_t)b); break;
+        default: break;
+        }
+    }
+    if (n_off > MAXOFF) fprintf(stderr, "Error:\t%d more findings of poly__polyck are not listed.\n", n_off - MAXOFF);
+}
 
 }  // extern "C"

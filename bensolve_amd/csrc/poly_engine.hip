@@ -12,6 +12,7 @@
 //       (|inc_i & inc_j| >= d-1) per lane, then a wave-cooperative superset scan for the surviving pairs.
 // A batch of cuts (bslv_poly_add_cuts) is classified at once (k_classify_batch_t) and applied in rounds of independent
 // cuts: poly_rounds_kernels.inc (k_edge_flags / k_edge_emit_m, k_vert_flags / k_vert_emit_m), poly_rounds2_kernels.inc.
+// bslv_poly_check, the read-only audit of the resident state (poly__polyck, bslv_poly.c:940-990): poly_check.inc.
 // What runs once per chunk or per step and not per cut -- the hot lists, the vertex selections -- compacts through
 // k_compact_count / k_compact_emit.
 // HBM layout: coordinates SoA X[k*cap + i] (coalesced K1 loads), flags 1 B/element, incidence as
@@ -4298,3 +4299,5 @@ int bslv_poly_get_dual_edges(bslv_poly *h, int *ab)
 }
 
 }  // extern "C"
+
+#include "poly_check.inc"

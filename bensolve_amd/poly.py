@@ -213,6 +213,38 @@ class PolyEngine:
     def bench_fill(self, nv, seed=1):
         check(self.lib.bslv_poly_bench_fill(self.h, int(nv), int(seed)))
 
+    CHECK_FIELDS = ("elements", "facets", "incidences", "bad_incidences", "unlisted_incidences", "infeasible",
+                    "edges", "bad_edges", "duplicate_edges", "passing_pairs", "missing_edges", "extra_edges")
+
+    def check(self, tol=0, rows=None, max_offenders=64):
+        """bslv_poly_check: the consistency check of the resident polyhedron (poly__polyck and its converse).
+        rows = (first, count) of the live elements whose pairs are scanned, None = all.  Returns the twelve counts by name and as
+        the list `out`, `worst` = (largest residual of a listed incidence, most negative slack), `offenders` = sorted (kind, a, b)
+        tuples (at most max_offenders) and their total `n_offenders`; `clean` = every defect count is zero."""
+        first, count = (0, -1) if rows is None else (int(rows[0]), int(rows[1]))
+        out = (ctypes.c_long * 12)()
+        worst = (ctypes.c_double * 2)()
+        off = np.zeros((max(int(max_offenders), 0), 3), np.int32)
+        n_off = ctypes.c_int()
+        f = self.lib.bslv_poly_check
+        f.argtypes = [ctypes.c_void_p, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                      ctypes.c_int, ctypes.c_void_p]
+        check(f(self.h, float(tol), first, count, out, worst, off.ctypes.data if len(off) else None, int(max_offenders), ctypes.byref(n_off)))
+        res = dict(zip(self.CHECK_FIELDS, out))
+        res["out"] = list(out)
+        res["worst"] = (worst[0], worst[1])
+        res["n_offenders"] = n_off.value
+        res["offenders"] = [tuple(int(v) for v in r) for r in off[:min(n_off.value, len(off))]]
+        res["clean"] = not any(out[k] for k in (3, 4, 5, 7, 8, 10, 11))
+        return res
+
+    def debug_corrupt(self, what, a, b=0, x=0.0):
+        """TESTS ONLY (bslv_poly_debug_corrupt): 0 delete edge number a, 1 append edge (a, b), 2 drop the last entry of element a's
+        incidence list, 3 add x to coordinate b of element a"""
+        f = self.lib.bslv_poly_debug_corrupt
+        f.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double]
+        check(f(self.h, int(what), int(a), int(b), float(x)))
+
     def counts(self):
         L, h = self.lib, self.h
         return dict(nprimal=L.bslv_poly_nprimal(h), ndual=L.bslv_poly_ndual(h), nedges=L.bslv_poly_nedges(h),

@@ -401,6 +401,38 @@ int  bslv_poly_get_primal_range(bslv_poly *h, int first, int count, double *coor
 int  bslv_poly_get_edges(bslv_poly *h, int *ab);
 int  bslv_poly_get_inc(bslv_poly *h, int *pairs);
 int  bslv_poly_get_dual_edges(bslv_poly *h, int *ab);
+/* CONSISTENCY CHECK of the resident polyhedron (poly__polyck, bslv_poly.c:940-990, and its converse). Read-only: no element, list,
+ * edge, counter or statistic of the engine changes, and the next cut behaves bit for bit as without the call.
+ *   out[0]  live elements                       out[1]  live facets (as bslv_poly_get_dual defines live)
+ *   out[2]  incidences examined
+ *   out[3]  BAD INCIDENCES: listed (element, facet) with |hp.x - alpha| > tol, alpha = 0 for an ideal element and hp the engine's own
+ *           hyperplane of the dual slot; also a list entry that is no valid rank or an unapplied facet, an entry that does not ascend
+ *           strictly, and (once) a list that does not lie inside the pool
+ *   out[4]  UNLISTED INCIDENCES: a live element within POLY_EPS (1e-9) of a live facet's hyperplane that its list does not hold
+ *   out[5]  INFEASIBLE: live element with hp.x - alpha < -tol for a live facet
+ *   out[6]  edges in the list                   out[7]  BAD EDGES: an endpoint out of range, dead, or a == b
+ *   out[8]  DUPLICATE EDGES: the same unordered pair again
+ *   out[9]  pairs of the examined rows that pass the edge test (edge_test, bslv_poly.c:467-512)
+ *   out[10] MISSING: passes the test, not listed (the reference's third check)
+ *   out[11] EXTRA: listed, fails the test (the converse, which the reference omits)
+ * Dual slot 0 while it is ideal is the facet at infinity (bslv_poly.c:83-92): its incidences are combinatorial, so it is counted in
+ * [1] and [2], its entries are checked for rank and order, and it takes no part in the residuals of [3] nor in [4] and [5].
+ * worst[0] = the largest |residual| of a listed incidence, worst[1] = the most negative slack met in [5]'s scan (0: none).
+ * Rows: the live elements in ascending slot order are rows 0 .. L-1; the pair scan covers the pairs (i, j), i < j, with i in
+ * [row_first, row_first + row_count), and [9]-[11] count those pairs only -- [11] counts a listed edge under the row of its smaller
+ * endpoint, so the counts of a partition of the rows add up to those of the whole.  [2]-[8] are always over the whole polyhedron.
+ * Offenders: (kind, a, b) with kind = the index into out (3, 4, 5, 7, 8, 10, 11) and (a, b) = (element, dual slot; -1 where the entry
+ * names none) or (element, element), sorted by (kind, a, b); if there are more than max_off, *n_off is the total and which are kept
+ * is unspecified.  BSLV_E_ARG: bad range, max_off < 0; BSLV_E_STATE: before bslv_poly_init.  The call waits for its stream.
+ * What the check finds out of range it counts ([3], [7]) and never dereferences.  BSLV_POLY_CHECK_TIMING=1: one line per call on
+ * stderr with the time of each kernel (HIP events). */
+int  bslv_poly_check(bslv_poly *h, double tol /* <= 0: 1e-6, the reference's */, int row_first, int row_count /* < 0: all */,
+                     long out[12], double worst[2] /* may be NULL */,
+                     int *offenders /* 3 * max_off ints (kind, a, b), may be NULL */, int max_off, int *n_off);
+/* for tests only: damage the resident state by plain copies (no kernel).  what 0: delete edge number a from the list (the last edge
+ * takes its place), 1: append edge (a, b), 2: drop the last entry of element a's incidence list, 3: add x to coordinate b of element
+ * a.  Anything else, or an index out of range, is BSLV_E_ARG. */
+int  bslv_poly_debug_corrupt(bslv_poly *h, int what, int a, int b, double x);
 /* host-only self-test of the two mailbox readers of the polyhedron engine (no GPU needed): a writer thread publishes `rounds`
  * messages with the sequence number FIRST and the content afterwards; 0 = every message was taken with its own content
  * (*torn_out: reads that had to be repeated), negative = a reader accepted foreign content.  which: 0 Mail, 1 round state */
