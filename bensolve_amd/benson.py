@@ -166,6 +166,23 @@ class BensonEngine:
         keys = ("entered", "tie_pivots", "no_candidate", "capped")
         return dict(last=dict(zip(keys, list(last))), total=dict(zip(keys, list(tot))))
 
+    def set_certify(self, on):
+        """bslv_lpq_certify on the OPTIMAL LPs of every solve_local (bslv_benson_set_certify, include/bslv_hip.h); off by default"""
+        self.lib.bslv_benson_set_certify.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        check(self.lib.bslv_benson_set_certify(self.h, int(bool(on))))
+
+    def get_certify(self):
+        self.lib.bslv_benson_get_certify.argtypes = [ctypes.c_void_p]
+        return int(self.lib.bslv_benson_get_certify(self.h))
+
+    def certify_stats(self):
+        """LPs certified, LPs not certified, calls, and the largest residual of each kind so far (bslv_benson_certify_stats)"""
+        counts, worst = (ctypes.c_long * 3)(), (ctypes.c_double * 5)()
+        self.lib.bslv_benson_certify_stats.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        check(self.lib.bslv_benson_certify_stats(self.h, counts, worst))
+        return dict(lps=int(counts[0]), not_certified=int(counts[1]), calls=int(counts[2]),
+                    worst=dict(zip(("rows", "feas", "dj", "side", "gap"), [float(v) for v in worst])))
+
     def set_pipelined(self, on):
         check(self.lib.bslv_benson_set_pipelined(self.h, int(on)))
 

@@ -106,6 +106,13 @@ struct bslv_benson {
     bool poly_check = getenv("BSLV_POLY_CHECK") && atoi(getenv("BSLV_POLY_CHECK")) != 0;
     long applies = 0, audits = 0, audits_dirty = 0, audit_sum[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};      // (audit_sum: the twelve counts added up over the audits)
     double audit_ms = 0;
+    // BSLV_LP_CERTIFY=1 / bslv_benson_set_certify: bslv_lpq_certify on the LPs of every solve_local that ended OPTIMAL, after the retries
+    // and before the getters; the first LP that is not certified is printed with the number of the batch, the tally when the engine is
+    // destroyed (stderr).  The run goes on and no record, cut or status changes.  Off by default: one flag test per solve_local.
+    bool certify = getenv("BSLV_LP_CERTIFY") && atoi(getenv("BSLV_LP_CERTIFY")) != 0;
+    bool certify_used = false, certify_printed = false;
+    long cert_counts[3] = {0, 0, 0};                  // LPs certified, LPs with a verdict other than 0, calls
+    double cert_worst[5] = {0, 0, 0, 0, 0};           // the largest residual of each kind so far
 };
 
 static int rec_len(const bslv_benson *h) { return h->q + 5; }
@@ -124,6 +131,11 @@ void bslv_benson_destroy(bslv_benson *h)
         fprintf(stderr, "BSLV_POLY_CHECK: %ld audits after %ld outer iterations%s, %ld not clean, %.1f ms in all; summed over the audits: %ld bad and %ld unlisted incidences, %ld infeasible, "
                 "%ld bad and %ld duplicate edges, %ld missing and %ld extra among %ld adjacent pairs\n", h->audits, h->applies, h->hom ? " [homogeneous problem]" : "", h->audits_dirty, h->audit_ms,
                 a[3], a[4], a[5], a[7], a[8], a[10], a[11], a[9]);
+    }
+    if (h->certify_used) {
+        const double *w = h->cert_worst;
+        fprintf(stderr, "BSLV_LP_CERTIFY: %ld LPs in %ld batches%s, %ld not certified; worst residuals: rows %.3e feas %.3e dj %.3e side %.3e gap %.3e\n", h->cert_counts[0], h->cert_counts[2],
+                h->hom ? " [homogeneous problem]" : "", h->cert_counts[1], w[0], w[1], w[2], w[3], w[4]);
     }
     if (h->lp) bslv_lpq_destroy(h->lp);
     if (h->poly) bslv_poly_destroy(h->poly);
@@ -269,6 +281,51 @@ int bslv_benson_set_canonical(bslv_benson *h, int on)
     return 0;
 }
 int bslv_benson_get_canonical(const bslv_benson *h) { return h && h->canonical; }
+// The LP certificate of every solve_local (bslv_lpq_certify): see bslv_hip.h.  The P1(w) batches of the dual variant (vlp_phases.hip) do
+// not go through solve_local: the LP-level call serves them.
+int bslv_benson_set_certify(bslv_benson *h, int on)
+{
+    if (!h) { set_error("bslv_benson_set_certify: bad argument"); return BSLV_E_ARG; }
+    h->certify = on != 0;
+    return 0;
+}
+int bslv_benson_get_certify(const bslv_benson *h) { return h && h->certify; }
+int bslv_benson_certify_stats(const bslv_benson *h, long counts[3], double worst[5])
+{
+    if (!h) return BSLV_E_ARG;
+    for (int k = 0; k < 3; k++) if (counts) counts[k] = h->cert_counts[k];
+    for (int k = 0; k < 5; k++) if (worst) worst[k] = h->cert_worst[k];
+    return 0;
+}
+// the LPs of a batch that ended OPTIMAL, with the bounds they were solved with
+static int certify_batch(bslv_benson *h, int nl, const int *st, const int *dst, const double *vlo, const double *vup, int r)
+{
+    std::vector<int> sl, which;
+    for (int k = 0; k < nl; k++) if (st[k] == BSLV_LP_OPTIMAL) { sl.push_back(dst[k]); which.push_back(k); }
+    const int n = (int)sl.size();
+    h->certify_used = true;
+    h->cert_counts[2]++;
+    if (!n) return 0;
+    std::vector<double> lo((size_t)n * r), up((size_t)n * r), res((size_t)n * 5);
+    std::vector<int> at((size_t)n * 5), vd(n);
+    for (int t = 0; t < n; t++) { memcpy(&lo[(size_t)t * r], vlo + (size_t)which[t] * r, r * sizeof(double)); memcpy(&up[(size_t)t * r], vup + (size_t)which[t] * r, r * sizeof(double)); }
+    const int rc = bslv_lpq_certify(h->lp, n, sl.data(), lo.data(), up.data(), 0, 0, nullptr, nullptr, res.data(), at.data(), vd.data());
+    if (rc) return rc;
+    h->cert_counts[0] += n;
+    for (int t = 0; t < n; t++) {
+        for (int k = 0; k < 5; k++) if (res[(size_t)t * 5 + k] > h->cert_worst[k]) h->cert_worst[k] = res[(size_t)t * 5 + k];
+        if (!vd[t]) continue;
+        h->cert_counts[1]++;
+        if (!h->certify_printed) {
+            h->certify_printed = true;
+            const double *w = &res[(size_t)t * 5];
+            const int *a = &at[(size_t)t * 5];
+            fprintf(stderr, "BSLV_LP_CERTIFY: batch %ld, LP %d (slot %d) is not certified (verdict %d)%s: rows %.3e at %d, feas %.3e at %d, dj %.3e at %d, side %.3e at %d, gap %.3e\n", h->cert_counts[2], which[t], sl[t], vd[t],
+                    h->hom ? " [homogeneous problem]" : "", w[0], a[0], w[1], a[1], w[2], a[2], w[3], a[3], w[4]);
+        }
+    }
+    return 0;
+}
 // tie phase of the LPs of the last solve_local (retries included) / of all so far: bslv_lpq_last_canonical_stats
 int bslv_benson_canonical_stats(const bslv_benson *h, long last[4], long total[4])
 {
@@ -792,6 +849,7 @@ int bslv_benson_solve_local_ctx(bslv_benson *h, int ctx, double *records, int *p
     }
     h->last_src = src; h->last_piv = it; h->last_gen.resize(nl);
     for (int k = 0; k < nl; k++) h->last_gen[k] = h->slot_gen[dst[k]];
+    if (h->certify && (rc = certify_batch(h, nl, st.data(), dst.data(), vlo.data(), vup.data(), r))) return rc;
     std::vector<double> ww((size_t)nl * q), yy((size_t)nl * q), zz(nl);
     if ((rc = bslv_lpq_get_dual(h->lp, nl, dst.data(), h->m, q, ww.data()))) return rc;                 // bslv_algs.c:1050
     if ((rc = bslv_lpq_get_primal(h->lp, nl, dst.data(), h->M + h->n, q, yy.data()))) return rc;        // :1055

@@ -15,6 +15,7 @@
 // would be after the pivots still pending -- rebuilt from the stored tableau and the pending (pivot row, multipliers) pairs)
 // + k_flush (persistent grid over (LP, row tile): pure HBM streaming, every tableau element read once, all pending pivots
 // applied to it in order, written once -> 16 B per element per ROUND instead of per pivot).
+// bslv_lpq_certify, the read-only optimality certificate of solved slots (tests/lp_cases.py: certify, on the device): lp_certify.inc.
 #include "common.h"
 #include <vector>
 #include <algorithm>
@@ -2562,6 +2563,9 @@ struct bslv_lpq {
     int last_init_parents = 0, last_init_family = 0, last_init_chunks = 0;      // distinct src slots of the last batch, its largest family; chunks k_init_grouped ran on (0: k_init ran)
     double *vlo_d = nullptr, *vup_d = nullptr, *prow_d = nullptr, *out_d = nullptr;
     size_t out_cap = 0;
+    // bslv_lpq_certify (lp_certify.inc): its scratch, grown to the largest call and released with the engine; the counters of the last call
+    void *cert_d = nullptr; size_t cert_cap = 0;
+    long last_cert[3] = {0, 0, 0};
     PivDesc *desc_d = nullptr;
     int *status_h = nullptr;          // pinned
     // stats
@@ -2849,7 +2853,7 @@ void bslv_lpq_destroy(bslv_lpq *h)
     park_free(h);
     period_free(h);
     auto fr = [](void *p) { if (p) (void)hipFree(p); };
-    fr(h->age_d); fr(h->age0_d);
+    fr(h->age_d); fr(h->age0_d); fr(h->cert_d);
     fr(h->L.T); fr(h->L.beta); fr(h->L.xN); fr(h->L.bh); fr(h->L.nh); fr(h->L.nstat); fr(h->L.pos);
     fr(h->Tstd); fr(h->lb_d); fr(h->ub_d); fr(h->art_d);
     fr(h->dbg_d); fr(h->list_d); fr(h->cptr_d); fr(h->cidx_d); fr(h->rptr_d); fr(h->ridx_d); fr(h->cval_d); fr(h->rval_d); fr(h->cost_d); fr(h->dsl_d); fr(h->trow_d); fr(h->uvec_d); fr(h->xfull_d); fr(h->hmail_d);
@@ -4346,3 +4350,5 @@ int bslv_lpq_last_stats(const bslv_lpq *h, int *lockstep_iters, long *pivots, do
 }
 
 }  // extern "C"
+
+#include "lp_certify.inc"

@@ -201,6 +201,43 @@ class LpEngine:
         check(self.lib.bslv_lpq_get_obj(self.h, len(slots), slots.ctypes.data, out.ctypes.data))
         return out
 
+    def certify(self, slots, vlo=None, vup=None, cost_first=0, costs=None, tol=None):
+        """the optimality certificate of solved slots, computed on the device (bslv_lpq_certify, include/bslv_hip.h): a dict with res
+        (B, 5: rows, feas, dj, side, gap), at (B, 5: the variable of the worst residual, -1 where there is none) and verdict (B, a bit
+        per kind over its tolerance, 0 = certified).  vlo / vup: the per-LP bounds the LPs were solved with; costs (B, cost_cnt) from
+        cost_first: an objective batch's; tol: six values, entries <= 0 or None = the defaults."""
+        slots = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        B = len(slots)
+        keep = []
+
+        def arr(a):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, np.float64)
+            keep.append(a)
+            return a.ctypes.data
+
+        c = None if costs is None else np.ascontiguousarray(costs, np.float64).reshape(B, -1)
+        t = None if tol is None else np.ascontiguousarray(tol, np.float64).reshape(6)
+        res, at, verdict = np.zeros((B, 5), np.float64), np.full((B, 5), -1, np.int32), np.zeros(B, np.int32)
+        self.lib.bslv_lpq_certify.argtypes = [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 5
+        check(self.lib.bslv_lpq_certify(self.h, B, slots.ctypes.data, arr(vlo), arr(vup), int(cost_first), 0 if c is None else c.shape[1], arr(c), arr(t),
+                                        res.ctypes.data, at.ctypes.data, verdict.ctypes.data))
+        return dict(res=res, at=at, verdict=verdict)
+
+    def last_certify_stats(self):
+        """of the last certify call (bslv_lpq_last_certify_stats)"""
+        o = (ctypes.c_long * 3)()
+        self.lib.bslv_lpq_last_certify_stats.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        check(self.lib.bslv_lpq_last_certify_stats(self.h, o))
+        return dict(lps=int(o[0]), not_certified=int(o[1]), launches=int(o[2]))
+
+    def debug_poke(self, slot, what, var, delta):
+        """tests only: add delta to the stored value (what 0) or the stored reduced cost (what 1, nonbasic only) of a variable of a
+        slot (bslv_lpq_debug_poke).  Returns the library's code (0, or BSLV_E_ARG)."""
+        self.lib.bslv_lpq_debug_poke.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double]
+        return int(self.lib.bslv_lpq_debug_poke(self.h, int(slot), int(what), int(var), float(delta)))
+
     def set_extended(self, on):
         """the extended selection (perturbation, primal clean-up) for every later solve of this engine (include/bslv_hip.h)"""
         self.lib.bslv_lpq_set_extended.argtypes = [ctypes.c_void_p, ctypes.c_int]

@@ -199,6 +199,46 @@ int  bslv_lpq_solve_batch_obj(bslv_lpq *h, int B, const int *src, const int *dst
 int  bslv_lpq_get_primal(bslv_lpq *h, int B, const int *slot, int first, int cnt, double *out);
 int  bslv_lpq_get_dual(bslv_lpq *h, int B, const int *slot, int first, int cnt, double *out);
 int  bslv_lpq_get_obj(bslv_lpq *h, int B, const int *slot, double *out);
+/* CERTIFICATE of solved slots.  Read-only: no slot, vector, age, parked record, counter or statistic changes, and the next
+ * solve behaves bit for bit as without the call.  It computes on the device, from the model and the vectors the getters above would
+ * return -- nothing else of a slot is read -- the worst residual of each of five kinds, for LPs that came back BSLV_LP_OPTIMAL:
+ * with p / y the primal / dual vector over all M + N variables of the model AS GIVEN (folded rows, parked and lazily open slots
+ * included), r = p[:M], x = p[M:], lambda = y[:M], d = y[M:], lo / up the bounds given to create / set_bounds with the per-LP range
+ * replaced by vlo[b] / vup[b] (the engine's artificial bounds play no part), and c the engine's own cost or, with cost_cnt > 0, zero
+ * everywhere except costs[b] on cost_first .. (rows may carry a cost there, as in bslv_lpq_solve_batch_obj: a cost c_i on row i is the
+ * column cost a_ij c_i, so c_j stands for c_j + sum_i a_ij c_i below; a range over folded rows is BSLV_E_ARG as it is there):
+ *   res[b*5 + 0]  rows   max_i |r_i - sum_j a_ij x_j|
+ *   res[b*5 + 1]  feas   max_k of (lo_k - p_k) / (1 + |lo_k|) and (p_k - up_k) / (1 + |up_k|) over the finite bounds, not below 0
+ *   res[b*5 + 2]  dj     max_j |d_j - (c_j - sum_i a_ij lambda_i)|
+ *   res[b*5 + 3]  side   over the k with |y_k| > tol[5]: |p_k - the bound of y_k's sign| (y > 0: lower, y < 0: upper); +inf if that
+ *                        bound is infinite
+ *   res[b*5 + 4]  gap    max(|D - P|, |P - z|), P = c0 + c . x, D = c0 + sum_k y_k (the bound of y_k's sign) over the k whose bound is
+ *                        finite, z = what bslv_lpq_get_obj returns for the slot and c0 = the engine's constant shift cost[0] -- for a
+ *                        slot of an objective batch too: there get_obj is the batch's objective plus the same shift
+ * Every sum is accumulated compensated (as accurate as in twice the working precision, rounded once) in a fixed order: the same call on
+ * the same state returns the same bits.  at[b*5 + k] is the variable, in the model as given, where the worst residual of kind k was met
+ * (ties: the smaller index; feas: the variable nearest to or furthest beyond a finite bound); -1 for gap and where nothing was examined.
+ * verdict[b] is a bit mask: bit k is set when residual k of LP b is over its tolerance (or is not a number); 0 = certified.
+ * tol: rows, feas, dj, side = 1e-9, 1e-8, 1e-8, 1e-7; tol[4] = 1e-9 is applied as tol[4] (1 + |z|); tol[5] = 1e-9 is the dual-zero
+ * threshold of side.  tol == NULL or an entry <= 0: that default.
+ * BSLV_E_ARG: h == NULL, B < 0, a slot out of range, vlo / vup missing with var_cnt > 0, res == NULL with B > 0, a cost range outside
+ * the model.  B == 0 returns 0.  A slot may be named more than once, with different bounds.  Works in both forms and under every
+ * method and switch.  The call waits for its stream.  Its scratch grows with the largest call and is released by bslv_lpq_destroy
+ * (bslv_lpq_slot_bytes and the pool do not change); a call whose scratch would exceed 256 MiB runs its LPs in chunks.
+ * BSLV_LP_CERTIFY_TIMING=1: one line per call on stderr with the time of each kernel (HIP events).
+ * bslv_lpq_last_certify_stats, of the last call: [0] LPs examined, [1] LPs with a verdict other than 0, [2] kernel launches. */
+int bslv_lpq_certify(bslv_lpq *h, int B, const int *slot,
+                     const double *vlo, const double *vup,      /* B * var_cnt, as given to the solve; may be NULL when var_cnt == 0 */
+                     int cost_first, int cost_cnt, const double *costs, /* an objective batch's (B * cost_cnt); cost_cnt == 0: the engine's own cost */
+                     const double *tol,                         /* 6 doubles or NULL = the defaults above */
+                     double *res,                               /* B * 5: rows, feas, dj, side, gap */
+                     int *at,                                   /* B * 5, may be NULL */
+                     int *verdict);                             /* B, may be NULL */
+int bslv_lpq_last_certify_stats(const bslv_lpq *h, long out[3]);
+/* for tests only: damage a slot by plain copies (no kernel).  what 0 adds delta to the stored value of variable var (basic or nonbasic,
+ * wherever it lives), what 1 to the stored reduced cost of a NONBASIC variable (a basic one is BSLV_E_ARG).  var is an index of the
+ * engine's own model: an engine with folded rows answers BSLV_E_ARG. */
+int bslv_lpq_debug_poke(bslv_lpq *h, int slot, int what, int var, double delta);
 /* statistics of the last solve_batch: lock-step iterations, tableau-update kernel launches,
  * and the HIP-event time (ms) spent in the tableau-update kernel */
 /* when on, every tableau-update launch is bracketed by HIP events on the engine's stream */
@@ -499,6 +539,16 @@ int  bslv_benson_unprocessed_left(const bslv_benson *h);
 int  bslv_benson_set_canonical(bslv_benson *h, int on);
 int  bslv_benson_get_canonical(const bslv_benson *h);
 int  bslv_benson_canonical_stats(const bslv_benson *h, long last[4], long total[4]);
+/* LP CERTIFICATE: with on != 0 bslv_benson_solve_local and its _ctx twin certify the LPs of the batch that ended BSLV_LP_OPTIMAL with
+ * bslv_lpq_certify, after the retries and before the getters, with the slots and bounds of the solve.  The first LP that is not certified
+ * is printed on stderr (batch number, slot, the five residuals and where they were met), a summary line when the engine is destroyed;
+ * the run goes on, no record, cut or status changes.  Off by default (nothing is allocated, no launch is added); BSLV_LP_CERTIFY=1
+ * switches it on when an engine is created.  bslv_benson_certify_stats: counts = LPs certified, LPs with a verdict other than 0, calls;
+ * worst = the largest residual of each kind so far (rows, feas, dj, side, gap); either may be NULL.  The P1(w) batches of the dual
+ * variant do not pass through solve_local: bslv_lpq_certify serves them directly. */
+int  bslv_benson_set_certify(bslv_benson *h, int on);
+int  bslv_benson_get_certify(const bslv_benson *h);
+int  bslv_benson_certify_stats(const bslv_benson *h, long counts[3], double worst[5]);
 /* batch selection: 1 = newest vertices first (default), 2 = spread evenly over the unprocessed queue, 3 = newest first but at
  * most `cap` children of one cut per batch, chosen from a window of `window` batches (set_sibling_rule; default 1, 8): the
  * children of one cut mostly see the same facet of the upper image, so their LPs return the same cut -- the reference's
