@@ -129,6 +129,13 @@ struct BatchView {
     int lazy;               // bslv_lpq_set_lazy: an LP that is finished when its pass would be due keeps its pending pivots; its slot gets the tableau only when asked for (bslv_lpq_materialise)
     unsigned long long *dbg; // BSLV_REV_PROBE & 8: 100 MHz clock ticks per phase of the dual selection of LP 0 (timing experiments)
 };
+// Dual Devex pricing (bslv_lpq_set_pricing): what a batch keeps for it.  A view of its own, an argument of the DVX kernels alone: two
+// more pointers in BatchView move the argument segment of EVERY kernel that takes one (measured: other scratch sizes and scalar spills
+// in k_select, k_select_p1 and k_select_cached), and the kernels of the default rule are to stay what they were.
+struct DvxView {
+    double *snorm;          // [B][Mp1p] reference norm s_i >= 1 of every basis row (the square root of the Devex weight), 1 in the reference framework
+    int *stat;              // [3] of the batch: dual selections under the weighted rule, those whose row is not the row of the largest violation, resets of a framework after the start
+};
 
 __device__ __forceinline__ double LO(const LpView &L, const BatchView &Bv, int b, int k)
 {
@@ -458,6 +465,14 @@ __device__ __forceinline__ ValIdx leave_candidate(ValIdx best, double lo, double
     if (!isinf(up)) { double v = bt - up; if (v > btol(up)) best = better_max(best, ValIdx{bland ? (double)(nvar - k) : v, 2 * i}); }
     return best;
 }
+// ... under dual Devex pricing (bslv_lpq_set_pricing): largest violation over the row's reference norm s >= 1 -- with s == 1 the key is
+// the violation itself, bit for bit (x / 1.0 is exact); Bland's rule does not look at s
+__device__ __forceinline__ ValIdx leave_candidate_dvx(ValIdx best, double lo, double up, double bt, double s, int k, int i, bool bland, int nvar)
+{
+    if (!isinf(lo)) { double v = lo - bt; if (v > btol(lo)) best = better_max(best, ValIdx{bland ? (double)(nvar - k) : v / s, 2 * i + 1}); }
+    if (!isinf(up)) { double v = bt - up; if (v > btol(up)) best = better_max(best, ValIdx{bland ? (double)(nvar - k) : v / s, 2 * i}); }
+    return best;
+}
 // may a column of status st with the (signed) row entry a enter?
 __device__ __forceinline__ bool is_candidate(int st, double a, double ptol) { return st != NS_S && !(fabs(a) < ptol) && ((a > 0 && (st == NS_L || st == NS_F)) || (a < 0 && (st == NS_U || st == NS_F))); }
 __device__ __forceinline__ double harris_key(double d, double a, bool bland) { return (fabs(d) + (bland ? 0.0 : TOL_DJ)) / fabs(a); }
@@ -553,7 +568,10 @@ __global__ void k_rev_identity(LpView L, int slot, const double *cost)
 // EIGHT at a time with independent loads (index, value, then the gathers from rho) and two columns are in flight per thread: entry after
 // entry, each a chain of three dependent loads, cost 0.7 ms per selection on ex09 (37 000 columns, one workgroup).
 // Slice t of ns takes the columns t, t + ns, t + 2 ns, ...: the few dense columns sit next to each other in the list and would all fall to one slice of a contiguous split.
-__device__ __forceinline__ void rev_row_slice(const LpView &L, const double *brow, const int *nh, double *row, int t_sl, int ns_sl)
+constexpr int REV_HQ = 512;                        // places in rev_row_slice's queue of heavy columns
+// (XS: the DVX instances of the selection hand in the LDS of the queue, xq[REV_HQ + 1] -- see SelSharedDvx -- and leave the others' alone)
+template <bool XS = false>
+__device__ __forceinline__ void rev_row_slice(const LpView &L, const double *brow, const int *nh, double *row, int t_sl, int ns_sl, int *xq = nullptr)
 {
     const int tid = threadIdx.x, NT = (int)blockDim.x, M = L.M, N = L.N;
     constexpr int RU = 8;
@@ -573,9 +591,11 @@ __device__ __forceinline__ void rev_row_slice(const LpView &L, const double *bro
     // A column with many non-zeros (ex09: 75 of its 36 939 columns hold 512 or 1024, the others 2 or 4) is not one thread's to sum -- 128
     // rounds of dependent loads, 150 us, while the other 1023 threads of the workgroup wait: it goes to a queue in LDS and a whole wave
     // takes it, 64 non-zeros per round.
-    constexpr int HEAVY = 32, HQ = 512;
-    __shared__ int hq[HQ];
-    __shared__ int hq_n;
+    constexpr int HEAVY = 32, HQ = REV_HQ;
+    int *p_hq, *p_hq_n;
+    if constexpr (XS) { p_hq = xq; p_hq_n = xq + HQ; }
+    else { __shared__ int hq[HQ]; __shared__ int hq_n; p_hq = hq; p_hq_n = &hq_n; }
+    int *const hq = p_hq; int &hq_n = *p_hq_n;
     if (tid == 0) hq_n = 0;
     __syncthreads();
     const int j1 = L.ld;
@@ -675,9 +695,14 @@ constexpr int REV_PRICE_SLICE = 2 * NT;             // columns per slice of k_re
 // workgroups of one LP sit on different XCDs, each with its own L2.
 constexpr int REV_SLICE = 2048;                    // columns per slice (two per thread of a 1024-thread workgroup)
 __device__ __forceinline__ int rev_nslices(const LpView &L) { return (L.ld + REV_SLICE - 1) / REV_SLICE; }
-__device__ void rev_take_slices(const LpView &L, int *mb, const int n, const double *brow, const int *nh, double *row, unsigned long long *cnt = nullptr)
+// (XS: the DVX instances of the selection hand in the LDS word for the ticket, with the late flag and rev_row_slice's queue behind it -- see SelSharedDvx -- and leave the others' alone)
+template <bool XS>
+__device__ __forceinline__ void rev_take_slices_in(const LpView &L, int *mb, const int n, const double *brow, const int *nh, double *row, unsigned long long *cnt, int *xt)
 {
-    __shared__ int s_t;
+    int *p_t;
+    if constexpr (XS) p_t = xt;
+    else { __shared__ int l_t; p_t = &l_t; }
+    int &s_t = *p_t;
     const int ns = rev_nslices(L);
     for (;;) {
         __syncthreads();
@@ -693,21 +718,29 @@ __device__ void rev_take_slices(const LpView &L, int *mb, const int n, const dou
         const int t = s_t;
         if (t < 0) break;
         if (cnt && threadIdx.x == 0) *cnt += 1;
-        rev_row_slice(L, brow, nh, row, t, ns);
+        rev_row_slice<XS>(L, brow, nh, row, t, ns, XS ? xt + 2 : nullptr);
         if (!(L.probe & 16)) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");      // (the slice is out before it is counted)
         __syncthreads();
         if (threadIdx.x == 0) __hip_atomic_fetch_add(&mb[1], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
-__device__ __forceinline__ void rev_helper(const LpView &L, const BatchView &Bv, const int b)
+__device__ void rev_take_slices(const LpView &L, int *mb, const int n, const double *brow, const int *nh, double *row, unsigned long long *cnt = nullptr)
 {
-    extern __shared__ unsigned char dyn_sel[];
-    __shared__ int s_req;
+    rev_take_slices_in<false>(L, mb, n, brow, nh, row, cnt, nullptr);
+}
+// (XS: as rev_take_slices_in; xr: the request word and the ticket, xdyn: the kernel's dynamic LDS)
+template <bool XS = false>
+__device__ __forceinline__ void rev_helper(const LpView &L, const BatchView &Bv, const int b, int *xr = nullptr, unsigned char *xdyn = nullptr)
+{
+    int *p_req; unsigned char *dyn;
+    if constexpr (XS) { p_req = xr; dyn = xdyn; }
+    else { extern __shared__ unsigned char dyn_sel[]; __shared__ int l_req; p_req = &l_req; dyn = dyn_sel; }
+    int &s_req = *p_req;
     int *mb = Bv.hmail + (size_t)b * 8;
     const int tid = threadIdx.x, NT = (int)blockDim.x;
     const int slot = Bv.dst[b];
     const int *nh = L.nh + (size_t)slot * L.N;
-    double *srho = L.rho_off >= 0 ? reinterpret_cast<double *>(dyn_sel + L.rho_off) : nullptr;
+    double *srho = L.rho_off >= 0 ? reinterpret_cast<double *>(dyn + L.rho_off) : nullptr;
     int last = L.launch_id << 8;
     for (long spins = 0; spins < 20000000L; spins++) {          // (bounded: ~10 s; a helper that leaves is not missed, see above)
         if (tid == 0) s_req = __hip_atomic_load(&mb[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // (relaxed: an acquire here invalidates the L2 of the XCD on every poll, for everyone on it)
@@ -721,7 +754,8 @@ __device__ __forceinline__ void rev_helper(const LpView &L, const BatchView &Bv,
         const int np = __hip_atomic_load(&mb[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         const double *brow_g = Bv.prow + (size_t)b * KP * L.ldt + (size_t)np * L.ldt;
         if (srho) { for (int c = tid; c < L.ldt; c += NT) srho[c] = brow_g[c]; __syncthreads(); }
-        rev_take_slices(L, mb, req & 0xFF, srho ? srho : brow_g, nh, Bv.trow + (size_t)b * L.ld);
+        if constexpr (XS) rev_take_slices_in<true>(L, mb, req & 0xFF, srho ? srho : brow_g, nh, Bv.trow + (size_t)b * L.ld, nullptr, xr + 1);
+        else rev_take_slices(L, mb, req & 0xFF, srho ? srho : brow_g, nh, Bv.trow + (size_t)b * L.ld);
     }
 }
 // BSLV_REV_PROBE & 8: 100 MHz clock ticks per phase of the selections of LP 0, summed in Bv.dbg[k] (solve_batch_impl prints them)
@@ -802,14 +836,18 @@ __device__ __forceinline__ void fetch_row_tableau(const LpView &L, const SelCtx 
     for (int j = threadIdx.x; j < L.ld; j += (int)blockDim.x) c.row[j] = j < L.N ? virt_entry(c.T0[(size_t)r * L.ld + j], r, j, c.np, c.pd, c.prow0, c.pcol0, L.ld, L.Mp1p) : 0.0;
 }
 // revised form: rho = row r of B^-1, then one sparse product per column -- by this workgroup, or dealt in slices to it and its helpers
-__device__ __forceinline__ void fetch_row_revised(const LpView &L, const BatchView &Bv, const SelCtx &c, const int r)
+// (XS: as rev_take_slices_in; xr: the request number, the late flag and the ticket, xdyn: the kernel's dynamic LDS)
+template <bool XS = false>
+__device__ __forceinline__ void fetch_row_revised(const LpView &L, const BatchView &Bv, const SelCtx &c, const int r, int *xr = nullptr, unsigned char *xdyn = nullptr)
 {
-    extern __shared__ unsigned char dyn_sel[];
-    __shared__ int s_n, s_late;
+    int *p_n, *p_late; unsigned char *dyn;
+    if constexpr (XS) { p_n = xr; p_late = xr + 2; dyn = xdyn; }
+    else { extern __shared__ unsigned char dyn_sel[]; __shared__ int l_n, l_late; p_n = &l_n; p_late = &l_late; dyn = dyn_sel; }
+    int &s_n = *p_n, &s_late = *p_late;
     const int tid = threadIdx.x, NT = (int)blockDim.x, b = c.b, np = c.np, ldt = L.ldt;
     double *brow_g = c.prow0 + (size_t)np * ldt;
     // rho also goes to LDS when it fits (ex09: 37 KB): the sparse products below gather from it ~200 000 times per selection
-    double *srho = L.rho_off >= 0 ? reinterpret_cast<double *>(dyn_sel + L.rho_off) : nullptr;
+    double *srho = L.rho_off >= 0 ? reinterpret_cast<double *>(dyn + L.rho_off) : nullptr;
     for (int i = tid; i < ldt; i += NT) {
         const double v = i < L.M ? virt_entry_b(c.T0[(size_t)r * ldt + i], r, i, np, c.pd, c.prow0, c.pcol0, ldt, L.Mp1p) : 0.0;
         brow_g[i] = v;
@@ -817,7 +855,7 @@ __device__ __forceinline__ void fetch_row_revised(const LpView &L, const BatchVi
     }
     __syncthreads();
     const double *brow = srho ? srho : brow_g;
-    if (L.helpers <= 1) { rev_row_slice(L, brow, c.nh, c.row, 0, 1); return; }
+    if (L.helpers <= 1) { rev_row_slice<XS>(L, brow, c.nh, c.row, 0, 1, XS ? xr + 3 : nullptr); return; }
     // hand the row out in slices (rev_take_slices): rho is in global memory (brow_g), the request goes out, this workgroup takes
     // slices like everyone else and then waits for the ones others took
     unsigned long long tf = ((L.probe & 8) && b == 0) ? wall_clock64() : 0ull;
@@ -836,7 +874,8 @@ __device__ __forceinline__ void fetch_row_revised(const LpView &L, const BatchVi
     }
     __syncthreads();
     phase_mark(L, Bv, b, 9, tf);
-    rev_take_slices(L, mb, s_n, brow, c.nh, c.row, ((L.probe & 8) && b == 0) ? &Bv.dbg[13] : nullptr);
+    if constexpr (XS) rev_take_slices_in<true>(L, mb, s_n, brow, c.nh, c.row, ((L.probe & 8) && b == 0) ? &Bv.dbg[13] : nullptr, xr + 1);
+    else rev_take_slices(L, mb, s_n, brow, c.nh, c.row, ((L.probe & 8) && b == 0) ? &Bv.dbg[13] : nullptr);
     phase_mark(L, Bv, b, 10, tf);
     if (tid == 0) {
         const int ns = rev_nslices(L);
@@ -848,13 +887,13 @@ __device__ __forceinline__ void fetch_row_revised(const LpView &L, const BatchVi
     phase_mark(L, Bv, b, 11, tf);
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");      // (the slices the others wrote)
     phase_mark(L, Bv, b, 12, tf);
-    if (s_late) { rev_row_slice(L, brow, c.nh, c.row, 0, 1); __syncthreads(); }      // (never seen; the row is this workgroup's to deliver either way)
+    if (s_late) { rev_row_slice<XS>(L, brow, c.nh, c.row, 0, 1, XS ? xr + 3 : nullptr); __syncthreads(); }      // (never seen; the row is this workgroup's to deliver either way)
 }
 // (TABLEAU: an instance that never sees the revised form -- k_select_p1 -- leaves its code, and the LDS it declares, out)
-template <bool TABLEAU = false>
-__device__ __forceinline__ void fetch_row(const LpView &L, const BatchView &Bv, const SelCtx &c, const int r)
+template <bool TABLEAU = false, bool XS = false>
+__device__ __forceinline__ void fetch_row(const LpView &L, const BatchView &Bv, const SelCtx &c, const int r, int *xr = nullptr, unsigned char *xdyn = nullptr)
 {
-    if (TABLEAU || !L.rev) fetch_row_tableau(L, c, r); else fetch_row_revised(L, Bv, c, r); __syncthreads();
+    if (TABLEAU || !L.rev) fetch_row_tableau(L, c, r); else fetch_row_revised<XS>(L, Bv, c, r, xr, xdyn); __syncthreads();
 }
 __device__ __forceinline__ void fetch_col_tableau(const LpView &L, const SelCtx &c, const int q)
 {
@@ -1009,9 +1048,10 @@ __device__ __forceinline__ bool phase1_prepare(const LpView &L, const BatchView 
 // is outside its bounds the step is one of PHASE 1, priced by d1 (phase1_prepare), with the SAME ratio test except that an infeasible
 // basic variable blocks where it reaches the bound it violates and nowhere else (oracle/lp_dense.c primal_simplex).  rsig: infeas_sign
 // the leaving variable had.
-template <bool P1>
+// (DVX: the instances of dual Devex pricing, which hand in the LDS of a row fetch -- see fetch_row_revised)
+template <bool P1, bool DVX = false>
 __device__ __forceinline__ bool primal_step(const LpView &L, const BatchView &Bv, const SelCtx &c, int &pf, const bool bland, double *sv, int *si,
-                                            int &r, int &q, bool &below, double &pstep, int &rsig)
+                                            int &r, int &q, bool &below, double &pstep, int &rsig, int *xr = nullptr, unsigned char *xdyn = nullptr)
 {
     const int tid = threadIdx.x, NT = (int)blockDim.x, b = c.b, M = L.M, N = L.N;
     const double *pc = c.pc;
@@ -1136,7 +1176,7 @@ __device__ __forceinline__ bool primal_step(const LpView &L, const BatchView &Bv
     below = !(lv.i & 1);                   // the leaving variable goes to its lower bound
     pstep = fabs(dq) * tstep / (1.0 + fabs(beta[M]));      // (what the step moves the objective by, relative: the ratio test's tolerance gives a degenerate step a length of 1e-9, not 0)
     if constexpr (P1) if (ph1) { pstep = fabs(dq) * tstep; if (tid == 0) atomicAdd(&Bv.xstat[6], 1); }      // (phase 1: by how much the sum of infeasibilities falls)
-    fetch_row<P1>(L, Bv, c, r);
+    fetch_row<P1, DVX>(L, Bv, c, r, xr, xdyn);
     return true;
 }
 // Bound flipping ratio test: sorted breakpoints of row r; a boxed candidate switches bound (sflag) while the row stays infeasible.  Returns the number of switches (the first of sidx)
@@ -1243,12 +1283,25 @@ __device__ __forceinline__ bool switch_bounds(const LpView &L, const BatchView &
 // function that is not inlined and declares LDS is laid out per MODULE, though: one more kernel calling one (select_once_p1) would
 // move the others' variables into a table looked up by kernel.  So k_select_p1 declares everything itself and hands it down.
 struct SelShared { double sv[NT_BIG / WAVE]; int si[NT_BIG / WAVE]; PivDesc d; int cnt3[3]; unsigned char *dyn; };
-template <bool EXT, bool P1 = false>
-__device__ __forceinline__ bool select_once(const LpView &L, const BatchView &Bv, const int b, const int cap2, SelShared *xs = nullptr)
+// DVX: DUAL DEVEX PRICING (bslv_lpq_set_pricing; Forrest and Goldfarb's reference framework, dual form).  Every basis row i of the LP
+// has a reference norm s_i >= 1 (DvxView::snorm; the square root of the usual weight), 1 in the reference framework: the basis the solve starts
+// from.  Phase A takes the violated row with the largest violation / s_i (leave_candidate_dvx), and a dual pivot on row r with the
+// multipliers f_i of Phase D (|f_i| = |alpha_iq / alpha_rq|) and p = 1 / alpha_rq leaves
+//   s_i = max(s_i, |f_i| s_r)  (i != r),      s_r = max(s_r |p|, 1)
+// in the loop that updates beta: no entry of the tableau is read for it.  A basis change that is no such dual step -- a primal clean-up
+// or phase-1 pivot here, a refactorisation replay on the host side -- starts a new framework (all s_i = 1); bound switches change
+// nothing.  Instances of their own (k_select_dvx, k_select_p1_dvx), so that the kernels of the default rule stay what they were; like P1
+// they get their LDS handed down (SelSharedDvx: also the words of the revised form's row fetch).
+struct SelSharedDvx : SelShared { int rv[3 + REV_HQ + 1]; };      // rv: request word of a helper / request number of the LP's own workgroup, slice ticket, late flag; rev_row_slice's queue and its length
+template <bool EXT, bool P1 = false, bool DVX = false>
+__device__ __forceinline__ bool select_once(const LpView &L, const BatchView &Bv, const int b, const int cap2, SelShared *xs = nullptr, const DvxView *dv = nullptr)
 {
     static_assert(EXT || !P1, "phase 1 lives in the extended selection");
+    constexpr bool XS = P1 || DVX;            // the LDS comes from the kernel
     double *sv; int *si; PivDesc *p_d; unsigned char *dyn;
-    if constexpr (P1) { sv = xs->sv; si = xs->si; p_d = &xs->d; dyn = xs->dyn; }
+    int *xr = nullptr;
+    if constexpr (DVX && !P1) xr = static_cast<SelSharedDvx *>(xs)->rv;      // (P1: tableau form only, no row fetch of the revised form)
+    if constexpr (XS) { sv = xs->sv; si = xs->si; p_d = &xs->d; dyn = xs->dyn; }
     else {
         __shared__ double l_sv[NT_BIG / WAVE];
         __shared__ int l_si[NT_BIG / WAVE];
@@ -1292,22 +1345,38 @@ __device__ __forceinline__ bool select_once(const LpView &L, const BatchView &Bv
     const bool primal = EXT && (pf & PF_PRIMAL);
     double pstep = 1.0;                      // length of a primal step (clean-up)
     int rsig = 0;                            // phase 1: which bound the leaving variable violated
+    double *const snorm = DVX ? dv->snorm + (size_t)b * L.Mp1p : nullptr;      // dual Devex pricing: the reference norms of the rows
+    bool other_row = false;                  // ... the weighted rule chose another row than the largest violation's
 
     if (primal) {
-        if (!primal_step<P1>(L, Bv, c, pf, bland, sv, si, r, q, below, pstep, rsig)) return true;
+        if (!primal_step<P1, DVX>(L, Bv, c, pf, bland, sv, si, r, q, below, pstep, rsig, xr, dyn)) return true;
     } else {
     // ---- dual simplex step ----
     unsigned long long tk = (L.probe & 8) ? wall_clock64() : 0ull;
     // Phase A: the leaving row
     ValIdx best{0.0, -1};
+    if constexpr (DVX) {
+        // (the row of the largest violation is found beside it, for the statistics only: bslv_lpq_last_pricing_stats)
+        ValIdx plain{0.0, -1};
+        for (int i = tid; i < M; i += NT) {
+            int k = c.bh[i];
+            const double lo = LO(L, Bv, b, k), up = UP(L, Bv, b, k), bt = beta[i];
+            best = leave_candidate_dvx(best, lo, up, bt, snorm[i], k, i, bland, L.M + L.N);
+            plain = leave_candidate(plain, lo, up, bt, k, i, bland, L.M + L.N);
+        }
+        best = block_argmax(best, sv, si);
+        plain = block_argmax(plain, sv, si);
+        other_row = !bland && best.i >= 0 && (best.i >> 1) != (plain.i >> 1);
+    } else {
     for (int i = tid; i < M; i += NT) {
         int k = c.bh[i];
         best = leave_candidate(best, LO(L, Bv, b, k), UP(L, Bv, b, k), beta[i], k, i, bland, L.M + L.N);
     }
     best = block_argmax(best, sv, si);
+    }
     if (best.i < 0) {
         if (EXT && (pf & PF_PERT)) {
-            if (perturbation_off<P1>(L, Bv, c, pf, sv)) return true;
+            if (perturbation_off<XS>(L, Bv, c, pf, sv)) return true;
             dwork = drow;
         }
         conclude_optimal(L, Bv, c, Bv.iters[b], Bv.verified[b], NT, sv);
@@ -1317,7 +1386,7 @@ __device__ __forceinline__ bool select_once(const LpView &L, const BatchView &Bv
     r = best.i >> 1; below = best.i & 1;
     const double sgn = below ? 1.0 : -1.0;
     phase_mark(L, Bv, b, 0, tk);
-    fetch_row<P1>(L, Bv, c, r);
+    fetch_row<P1, DVX>(L, Bv, c, r, xr, dyn);
     phase_mark(L, Bv, b, 1, tk);
 
     // pass 0: row scale for the relative pivot tolerance
@@ -1325,7 +1394,7 @@ __device__ __forceinline__ bool select_once(const LpView &L, const BatchView &Bv
     for (int j = tid; j < N; j += NT) rmax = fmax(rmax, fabs(row[j]));
     rmax = block_max(rmax, sv);
     const double ptol = TOL_PIV * (1.0 + rmax);
-    if constexpr (EXT) nflip = flip_breakpoints<P1>(L, Bv, c, r, below, sgn, ptol, dwork, cap2, skey, sidx, sflag, P1 ? xs->cnt3 : nullptr);
+    if constexpr (EXT) nflip = flip_breakpoints<XS>(L, Bv, c, r, below, sgn, ptol, dwork, cap2, skey, sidx, sflag, XS ? xs->cnt3 : nullptr);
     // pass 1: Harris bound on the dual step
     phase_mark(L, Bv, b, 2, tk);
     // (both passes fetch FOUR columns per thread and iteration with all loads issued first: on wide problems -- ex09: 37 000 columns,
@@ -1376,6 +1445,8 @@ __device__ __forceinline__ bool select_once(const LpView &L, const BatchView &Bv
     unsigned long long tk2 = (L.probe & 8) ? wall_clock64() : 0ull;
     if (!P1 && L.rev && !col_ready) { fetch_col(L, c, q); col_ready = true; }    // (the tableau form gathers its column in Phase D)
     phase_mark(L, Bv, b, 5, tk2);
+    double sr = 1.0;                                                 // dual Devex pricing: the leaving row's norm as it was (read by all before Phase D writes it)
+    if constexpr (DVX) sr = snorm[r];
     // Phase C: the descriptor, the basis heads
     if (tid == 0) {
         const double trq = row[q];
@@ -1391,6 +1462,10 @@ __device__ __forceinline__ bool select_once(const LpView &L, const BatchView &Bv
             s_d.r = -1;
         } else {
             s_d = commit_pivot(L, Bv, c, r, q, below, bland, Bv.iters[b], Bv.verified[b], (nflip > 0 && !incr) ? MODE_REFRESH : MODE_PIVOT, dwork, primal, nflip, pf & PF_PERT);
+            if constexpr (DVX) {
+                if (primal) atomicAdd(&dv->stat[2], 1);           // (a primal or phase-1 pivot: a new reference framework, see Phase D)
+                else if (!bland) { atomicAdd(&dv->stat[0], 1); if (other_row) atomicAdd(&dv->stat[1], 1); }
+            }
             if constexpr (EXT) {
                 if (nflip > 0) atomicAdd(&Bv.xstat[0], 1);
                 if (incr) atomicAdd(&Bv.xstat[4], 1);
@@ -1408,9 +1483,14 @@ __device__ __forceinline__ bool select_once(const LpView &L, const BatchView &Bv
     if (d.r < 0) return true;                      // (given up: see above)
     // Phase D: the entering column as it is after the pending pivots -> multipliers of all rows, beta; the reduced-cost row
     for (int i = tid; i <= M; i += NT) {
-        if (i == r) { pc[i] = 0.0; beta[i] = d.enter_val; continue; }
+        if (i == r) {
+            pc[i] = 0.0; beta[i] = d.enter_val;
+            if constexpr (DVX) snorm[i] = primal ? 1.0 : fmax(sr * fabs(d.p), 1.0);
+            continue;
+        }
         const double f = (i == M ? drow[q] : (col_ready ? pc[i] : virt_entry(c.T0[(size_t)i * ld + q], i, q, np, c.pd, c.prow0, c.pcol0, ld, L.Mp1p))) * d.p;
         pc[i] = f;
+        if constexpr (DVX) { if (i < M) snorm[i] = primal ? 1.0 : fmax(snorm[i], fabs(f) * sr); }
         if constexpr (P1) {      // phase 1: did the step move a row other than the leaving one across a bound?  (d1 is then rebuilt)
             if ((pf & PF_PHASE1) && i < M) {
                 const int k = c.bh[i];
@@ -1627,6 +1707,9 @@ __device__ __forceinline__ bool select_once_cached(const LpView &L, const BatchV
 // (the extended instance is a function of its own, as the compiler always had it: inlined into the 1024-thread kernel it spills 300 registers, called none)
 __device__ __noinline__ bool select_once_ext(const LpView &L, const BatchView &Bv, const int b, const int cap2) { return select_once<true>(L, Bv, b, cap2); }
 __device__ __noinline__ bool select_once_p1(const LpView &L, const BatchView &Bv, const int b, const int cap2, SelShared *xs) { return select_once<true, true>(L, Bv, b, cap2, xs); }
+// (dual Devex pricing: the same three shapes)
+__device__ __noinline__ bool select_once_dvx_ext(const LpView &L, const BatchView &Bv, const int b, const int cap2, SelShared *xs, const DvxView *dv) { return select_once<true, false, true>(L, Bv, b, cap2, xs, dv); }
+__device__ __noinline__ bool select_once_dvx_p1(const LpView &L, const BatchView &Bv, const int b, const int cap2, SelShared *xs, const DvxView *dv) { return select_once<true, true, true>(L, Bv, b, cap2, xs, dv); }
 // One launch selects up to nsel pivots per LP, one after the other, by the same workgroup: the KP selections between two passes
 // over the tableau depend only on the LP's own vectors (beta, the reduced-cost row, the pending pivot rows and multipliers) -- no
 // grid-wide dependency asks for a launch each (rounds 1-3 launched this kernel KP times per pass, 17 % of all GPU time in
@@ -1675,6 +1758,53 @@ __global__ __launch_bounds__(NT) void k_select_cached(LpView L, BatchView Bv, co
         if (sdx) __syncthreads();
         if (!select_once_cached<CPT>(L, Bv, b)) break;
     }
+}
+
+// k_select<EXT> and k_select_p1 under dual Devex pricing (bslv_lpq_set_pricing; select_once<.., DVX>): what a batch launches while the
+// switch is on, in both forms and at both block sizes, the helpers of the revised form included.  Kernels of their own, with their LDS
+// declared here and handed down (see SelShared), so that the ones above compile to what they always did.  k_select_cached has no such
+// instance: with the switch on, the plan does not take it.
+template <bool EXT>
+__global__ __launch_bounds__(NT_BIG) void k_select_dvx(LpView L, BatchView Bv, DvxView Dv, const int *active, int nact, int cap2, int nsel)
+{
+    __shared__ SelSharedDvx xs;
+    extern __shared__ unsigned char dyn_dvx[];
+    if ((int)blockIdx.x >= nact) return;
+    const int b = active[blockIdx.x];
+    if (blockIdx.y > 0) { rev_helper<true>(L, Bv, b, xs.rv, dyn_dvx); return; }
+    if (threadIdx.x == 0) xs.dyn = dyn_dvx;
+    __syncthreads();
+    for (int sdx = 0; sdx < nsel; sdx++) {
+        if (sdx) __syncthreads();
+        if (!(EXT ? select_once_dvx_ext(L, Bv, b, cap2, &xs, &Dv) : select_once<false, false, true>(L, Bv, b, cap2, &xs, &Dv))) break;
+    }
+    if (L.helpers > 1) {
+        __syncthreads();
+        if (threadIdx.x == 0) __hip_atomic_store(&Bv.hmail[(size_t)b * 8], (L.launch_id << 8) | 0xFF, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+__global__ __launch_bounds__(NT_BIG) void k_select_p1_dvx(LpView L, BatchView Bv, DvxView Dv, const int *active, int nact, int cap2, int nsel)
+{
+    __shared__ SelShared xs;
+    extern __shared__ unsigned char dyn_p1_dvx[];
+    if ((int)blockIdx.x >= nact) return;
+    const int b = active[blockIdx.x];
+    if (threadIdx.x == 0) xs.dyn = dyn_p1_dvx;
+    __syncthreads();
+    for (int sdx = 0; sdx < nsel; sdx++) {
+        if (sdx) __syncthreads();
+        if (!select_once_dvx_p1(L, Bv, b, cap2, &xs, &Dv)) break;
+    }
+}
+
+// the reference norms of LP list[k] (nullptr: LP k) of the batch, k < n, back to 1: the start of a solve, and a refactorisation replay
+__global__ void k_dvx_ones(DvxView Dv, int Mp1p, const int *list, int n, int count)
+{
+    if ((int)blockIdx.y >= n) return;
+    const int b = list ? list[blockIdx.y] : (int)blockIdx.y;
+    double *s = Dv.snorm + (size_t)b * Mp1p;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < Mp1p; i += gridDim.x * blockDim.x) s[i] = 1.0;
+    if (count && blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&Dv.stat[2], 1);
 }
 
 // ---- TIE PHASE (bslv_lpq_set_canonical): the canonical optimal basis of a primal degenerate LP ----
@@ -2512,6 +2642,13 @@ struct bslv_lpq {
     long last_ext[5] = {0, 0, 0, 0, 0};
     int method = BSLV_LP_METHOD_DUAL;  // bslv_lpq_set_method (BSLV_LP_METHOD at create)
     long last_p1[3] = {0, 0, 0};       // phase 1 of the last batch: LPs that entered it, its iterations, rebuilds of its pricing vector
+    // dual Devex pricing (bslv_lpq_set_pricing, BSLV_LP_PRICING at create): the rule, the reference norms and counters of a batch (allocated by
+    // the first batch that runs under the rule), the counters of the last solve call, the size of the last batch that ran under the rule (0: none did)
+    int pricing = BSLV_LP_PRICING_DANTZIG;
+    double *snorm_d = nullptr; int *dvxstat_d = nullptr; int snorm_Bcap = 0;
+    long last_dvx[3] = {0, 0, 0};
+    int snorm_B = 0;
+    size_t select_dvx_lds_max[3] = {64 * 1024, 64 * 1024, 64 * 1024};      // dynamic LDS of k_select_dvx<false>, k_select_dvx<true>, k_select_p1_dvx
     // tie phase (bslv_lpq_set_canonical): the switch, the direction (host / device), per-LP state of a batch, the counters of the last batch
     bool canonical = false;
     std::vector<double> canon_dir;
@@ -2836,6 +2973,8 @@ static int raw_create(bslv_lpq **out, int M, int N, const double *A, const doubl
     if (const char *e = getenv("BSLV_LP_METHOD")) {
         if (!rev) h->method = !strcmp(e, "primal") ? BSLV_LP_METHOD_PRIMAL : !strcmp(e, "repair") ? BSLV_LP_METHOD_REPAIR : BSLV_LP_METHOD_DUAL;
     }
+    // BSLV_LP_PRICING=dantzig|devex: the rule for the leaving row of a dual step (bslv_lpq_set_pricing), in both forms
+    if (const char *e = getenv("BSLV_LP_PRICING")) h->pricing = !strcmp(e, "devex") ? BSLV_LP_PRICING_DEVEX : BSLV_LP_PRICING_DANTZIG;
     // BSLV_LP_REFACTOR=1: the in-call rescue of bslv_lpq_set_refactor, for an engine in the revised form (the tableau form has no inverse to rebuild)
     L.rfx = 0; L.drift_b = -1; L.drift_p = -1;
     if (const char *e = getenv("BSLV_LP_REFACTOR")) { if (rev) h->refactor_on = atoi(e) != 0; }
@@ -2853,7 +2992,7 @@ void bslv_lpq_destroy(bslv_lpq *h)
     park_free(h);
     period_free(h);
     auto fr = [](void *p) { if (p) (void)hipFree(p); };
-    fr(h->age_d); fr(h->age0_d); fr(h->cert_d);
+    fr(h->age_d); fr(h->age0_d); fr(h->cert_d); fr(h->snorm_d); fr(h->dvxstat_d);
     fr(h->L.T); fr(h->L.beta); fr(h->L.xN); fr(h->L.bh); fr(h->L.nh); fr(h->L.nstat); fr(h->L.pos);
     fr(h->Tstd); fr(h->lb_d); fr(h->ub_d); fr(h->art_d);
     fr(h->dbg_d); fr(h->list_d); fr(h->cptr_d); fr(h->cidx_d); fr(h->rptr_d); fr(h->ridx_d); fr(h->cval_d); fr(h->rval_d); fr(h->cost_d); fr(h->dsl_d); fr(h->trow_d); fr(h->uvec_d); fr(h->xfull_d); fr(h->hmail_d);
@@ -3227,6 +3366,7 @@ struct SelectPlan {
     bool p1;                // ... with phase 1 in its primal steps (k_select_p1): the PRIMAL and REPAIR methods
     int nt, per_launch; size_t lds;     // threads per workgroup; selections per launch; dynamic LDS of a k_select launch
     int cpt;                // columns per thread of k_select_cached (plain dual selection, tableau form, NT threads), 0: k_select
+    bool dvx;               // dual Devex pricing (bslv_lpq_set_pricing): the DVX instance of whichever of k_select<false>, k_select<true>, k_select_p1 the rest asks for; never k_select_cached
 };
 static int plan_select(bslv_lpq *h, int B, const double *vlo, const double *vup, SelectPlan *plan)
 {
@@ -3237,12 +3377,22 @@ static int plan_select(bslv_lpq *h, int B, const double *vlo, const double *vup,
     if (!bfrt && L.vcnt > 0)
         for (size_t k = 0; k < (size_t)B * L.vcnt && !bfrt; k++) bfrt = std::isfinite(vlo[k]) && std::isfinite(vup[k]) && vlo[k] < vup[k];
     if (getenv("BSLV_LP_EXT")) bfrt = p1 || atoi(getenv("BSLV_LP_EXT")) != 0;      // test hook: force the extended selection on / off
+    const bool dvx = h->pricing == BSLV_LP_PRICING_DEVEX && !L.objmode;      // (objective batches make primal steps only: they keep the kernels they had)
+    // the kernel of an extended (ext) or plain selection and the dynamic LDS it may use so far
+    auto sel_kernel = [&](bool ext) -> const void * {
+        if (dvx) return p1 ? (const void *)k_select_p1_dvx : ext ? (const void *)k_select_dvx<true> : (const void *)k_select_dvx<false>;
+        return p1 ? (const void *)k_select_p1 : ext ? (const void *)k_select<true> : (const void *)k_select<false>;
+    };
+    auto sel_lds_max = [&](bool ext) -> size_t & {
+        if (dvx) return h->select_dvx_lds_max[p1 ? 2 : ext ? 1 : 0];
+        return p1 ? h->select1_lds_max : ext ? h->select_lds_max : h->select0_lds_max;
+    };
     int cap2 = 2;
     while (cap2 < L.N) cap2 <<= 1;
     size_t sel_lds = (size_t)cap2 * (sizeof(double) + sizeof(int)) + (size_t)L.N;
     if (bfrt && sel_lds > 144 * 1024) { cap2 = 0; sel_lds = (size_t)L.N; }     // rows too long for the in-LDS sort: extended selection without the long-step part
-    if (bfrt && sel_lds > (p1 ? h->select1_lds_max : h->select_lds_max)) {
-        if (sel_lds <= 144 * 1024 && hipFuncSetAttribute(p1 ? (const void *)k_select_p1 : (const void *)k_select<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sel_lds) == hipSuccess) (p1 ? h->select1_lds_max : h->select_lds_max) = sel_lds;
+    if (bfrt && sel_lds > sel_lds_max(true)) {
+        if (sel_lds <= 144 * 1024 && hipFuncSetAttribute(sel_kernel(true), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sel_lds) == hipSuccess) sel_lds_max(true) = sel_lds;
         else bfrt = false;
     }
     if (p1 && !bfrt) { set_error("bslv_lpq_solve_batch: rows too long for the extended selection the primal method needs (N=%d)", L.N); return BSLV_E_CAPACITY; }
@@ -3252,21 +3402,21 @@ static int plan_select(bslv_lpq *h, int B, const double *vlo, const double *vup,
     L.rho_off = -1;
     if (L.rev) {
         const size_t off = bfrt ? (sel_lds + 15) / 16 * 16 : 0, want = off + (size_t)L.ldt * sizeof(double);
-        size_t &lim = bfrt ? h->select_lds_max : h->select0_lds_max;
+        size_t &lim = sel_lds_max(bfrt);
         bool ok = want <= lim;
         if (!ok && want <= 144 * 1024) {
-            ok = hipFuncSetAttribute(bfrt ? (const void *)k_select<true> : (const void *)k_select<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)want) == hipSuccess;
+            ok = hipFuncSetAttribute(sel_kernel(bfrt), hipFuncAttributeMaxDynamicSharedMemorySize, (int)want) == hipSuccess;
             if (ok) lim = want; else (void)hipGetLastError();
         }
         if (ok) { L.rho_off = (int)off; plan->lds = want; }
     }
-    plan->ext = bfrt; plan->cap2 = bfrt ? cap2 : 0; plan->p1 = p1;
+    plan->ext = bfrt; plan->cap2 = bfrt ? cap2 : 0; plan->p1 = p1; plan->dvx = dvx;
     // (measured, BSLV_SELECT_NT: S-degenerate, 2011 columns, 64 LPs per step: LP phase 67.6 / 52.0 / 46.6 ms with 256 / 512 / 1024 threads;
     //  S-degenerate-q4 to termination with 256 LPs per step 12.1 -> 10.4 s; same pivots)
     plan->nt = getenv("BSLV_SELECT_NT") ? atoi(getenv("BSLV_SELECT_NT")) : (L.N >= 1536 ? NT_BIG : NT);
     plan->per_launch = (getenv("BSLV_SELECT_FUSE") && atoi(getenv("BSLV_SELECT_FUSE")) == 0) ? 1 : KP;
     const bool cache = !(getenv("BSLV_SELECT_CACHE") && atoi(getenv("BSLV_SELECT_CACHE")) == 0);      // 0: k_select<false> where k_select_cached would run (same results bit for bit, tests/test_lp_select_cache_gpu.py)
-    plan->cpt = (cache && !bfrt && !L.rev && plan->nt == NT && L.N <= 6 * NT) ? (L.N <= 2 * NT ? 2 : (L.N <= 4 * NT ? 4 : 6)) : 0;
+    plan->cpt = (cache && !dvx && !bfrt && !L.rev && plan->nt == NT && L.N <= 6 * NT) ? (L.N <= 2 * NT ? 2 : (L.N <= 4 * NT ? 4 : 6)) : 0;
     return 0;
 }
 // the KP selections of one round for the `running` LPs of the active list
@@ -3282,7 +3432,13 @@ static void launch_select(bslv_lpq *h, const SelectPlan &p, const BatchView &bv,
             helpers = std::max(1, std::min(std::min(hmax, (L.ld + 2047) / 2048), 256 / std::max(1, running)));
         }
         L.helpers = helpers; L.launch_id = (++h->launch_seq) & 0x3FFFFF;
-        if (p.cpt == 2) hipLaunchKernelGGL(k_select_cached<2>, dim3(running), dim3(NT), 0, s, L, bv, h->active_d, running, p.per_launch);
+        if (p.dvx) {
+            const DvxView dv{h->snorm_d, h->dvxstat_d};
+            if (p.p1) hipLaunchKernelGGL(k_select_p1_dvx, dim3(running), dim3(p.nt), p.lds, s, L, bv, dv, h->active_d, running, p.cap2, p.per_launch);
+            else if (p.ext) hipLaunchKernelGGL(k_select_dvx<true>, dim3(running, helpers), dim3(p.nt), p.lds, s, L, bv, dv, h->active_d, running, p.cap2, p.per_launch);
+            else hipLaunchKernelGGL(k_select_dvx<false>, dim3(running, helpers), dim3(p.nt), p.lds, s, L, bv, dv, h->active_d, running, 0, p.per_launch);
+        }
+        else if (p.cpt == 2) hipLaunchKernelGGL(k_select_cached<2>, dim3(running), dim3(NT), 0, s, L, bv, h->active_d, running, p.per_launch);
         else if (p.cpt == 4) hipLaunchKernelGGL(k_select_cached<4>, dim3(running), dim3(NT), 0, s, L, bv, h->active_d, running, p.per_launch);
         else if (p.cpt == 6) hipLaunchKernelGGL(k_select_cached<6>, dim3(running), dim3(NT), 0, s, L, bv, h->active_d, running, p.per_launch);
         else if (p.p1) hipLaunchKernelGGL(k_select_p1, dim3(running), dim3(p.nt), p.lds, s, L, bv, h->active_d, running, p.cap2, p.per_launch);
@@ -3433,6 +3589,8 @@ static int period_refactor(bslv_lpq *h, const BatchView &bv, int n, bool at_star
     hipLaunchKernelGGL(k_per_price, dim3((h->L.ld + REV_PRICE_SLICE - 1) / REV_PRICE_SLICE, n), dim3(NT), 0, s, h->L, bv, rv, (const int *)P.due, (const double *)h->cost_d, n);
     if ((rc = replay_refresh(h, rv, P.iota, n, pass))) return rc;
     hipLaunchKernelGGL(k_per_resume, dim3((n + 255) / 256), dim3(256), 0, s, bv, rv, rfx_view(h), (const int *)P.due, n, h->age0_d, P.res);
+    // dual Devex pricing: the replay may have moved heads between rows, so the LPs go on in a new reference framework (at the start they are in one)
+    if (h->snorm_B > 0 && !at_start) hipLaunchKernelGGL(k_dvx_ones, dim3((h->L.Mp1p + 255) / 256, n), dim3(256), 0, s, DvxView{h->snorm_d, h->dvxstat_d}, h->L.Mp1p, (const int *)P.due, n, 1);
     HIP_TRY(hipGetLastError());
     std::vector<int> due(n), res(n), nw(P.nwcap);
     HIP_TRY(hipMemcpyAsync(due.data(), P.due, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
@@ -3674,8 +3832,22 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
     }
     HIP_TRY(hipMemsetAsync(h->xstat_d, 0, 8 * sizeof(int), s));
     if (L.rfx) HIP_TRY(hipMemsetAsync(h->rmark_d, 0, (size_t)B * sizeof(int), s));
+    // dual Devex pricing: the reference norms of the batch (allocated by the first batch that runs under the rule) start at 1
+    const bool dvx = h->pricing == BSLV_LP_PRICING_DEVEX && !L.objmode;
+    if (dvx) {
+        if (h->snorm_Bcap < h->Bcap) {
+            if (h->snorm_d) (void)hipFree(h->snorm_d);
+            h->snorm_d = nullptr; h->snorm_Bcap = 0;
+            HIP_TRY(malloc0s(&h->snorm_d, (size_t)h->Bcap * L.Mp1p * sizeof(double), s));
+            h->snorm_Bcap = h->Bcap;
+        }
+        if (!h->dvxstat_d) HIP_TRY(malloc0s(&h->dvxstat_d, 4 * sizeof(int), s));
+        HIP_TRY(hipMemsetAsync(h->dvxstat_d, 0, 4 * sizeof(int), s));
+    }
+    h->snorm_B = dvx ? B : 0;
     BatchView bv = bview(h);
     bv.cvals = h->cvals_d;
+    if (dvx) hipLaunchKernelGGL(k_dvx_ones, dim3((L.Mp1p + 255) / 256, B), dim3(256), 0, s, DvxView{h->snorm_d, h->dvxstat_d}, L.Mp1p, (const int *)nullptr, B, 0);
     const int tiles = (L.mrows + TR - 1) / TR;
     if (L.rev) hipLaunchKernelGGL(k_age_begin, dim3((B + 255) / 256), dim3(256), 0, s, bv, (const long long *)h->age_d, h->age0_d, B);      // the age of every LP's matrix: its parent's
     {   // (objective batches keep their own start; the revised form knows the dual method only: bslv_lpq_set_method)
@@ -3890,6 +4062,7 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
         P.list_inflight = false; P.pairs_inflight = false;      // (the readbacks above have waited for the stream)
     }
     { int xs[8]; HIP_TRY(hipMemcpy(xs, h->xstat_d, sizeof xs, hipMemcpyDeviceToHost)); for (int k = 0; k < 5; k++) h->last_ext[k] = xs[k]; for (int k = 0; k < 3; k++) h->last_p1[k] = xs[5 + k]; }
+    if (dvx) { int ds[3]; HIP_TRY(hipMemcpy(ds, h->dvxstat_d, sizeof ds, hipMemcpyDeviceToHost)); for (int k = 0; k < 3; k++) h->last_dvx[k] += ds[k]; }      // (added: the rescue's solves count with the call)
     if (h->profile) {
         double ms = 0;
         for (size_t e = 0; e < nev; e++) { float t = 0; (void)hipEventElapsedTime(&t, h->evpool[e].first, h->evpool[e].second); ms += t; }
@@ -3979,6 +4152,8 @@ static int solve_batch_rescue(bslv_lpq *h, int B, const int *src, const int *dst
         LpView &L = h->L;
         for (int k = 0; k < 4; k++) h->last_rfx[k] = 0;
         for (int k = 0; k < 4; k++) h->last_per[k] = 0;      // (solve_batch_impl adds to them: the rescue's solves count with the call)
+        for (int k = 0; k < 3; k++) h->last_dvx[k] = 0;
+        h->snorm_B = 0;
         h->rmark_valid = false;
         L.rfx = (h->refactor_on && L.rev) ? 1 : 0;
         L.drift_b = -1; L.drift_p = -1;
@@ -4001,6 +4176,10 @@ static int solve_batch_rescue(bslv_lpq *h, int B, const int *src, const int *dst
     for (int k = 0; k < 5; k++) ext[k] = h->last_ext[k];
     for (int k = 0; k < 3; k++) p1[k] = h->last_p1[k];
     const int vc = L.vcnt;
+    // dual Devex pricing: the norms of the batch (bslv_lpq_last_pricing_norms) -- a re-solve is a batch of its own whose LP k is LP lps[k] of this one
+    std::vector<double> sn;
+    const int snB = h->snorm_B;
+    if (snB > 0) { sn.resize((size_t)snB * L.Mp1p); HIP_TRY(hipMemcpy(sn.data(), h->snorm_d, sn.size() * sizeof(double), hipMemcpyDeviceToHost)); }
     for (int attempt = 0; attempt < RESCUE_MAX && !todo.empty(); attempt++) {
         const auto t0 = std::chrono::steady_clock::now();
         const int n = (int)todo.size();
@@ -4025,6 +4204,7 @@ static int solve_batch_rescue(bslv_lpq *h, int B, const int *src, const int *dst
         tot_upd += h->last_update_ms; tot_ms += h->last_total_ms;
         for (int k = 0; k < 5; k++) ext[k] += h->last_ext[k];
         for (int k = 0; k < 3; k++) p1[k] += h->last_p1[k];
+        if (snB > 0 && h->snorm_B == m) for (int k = 0; k < m; k++) HIP_TRY(hipMemcpy(&sn[(size_t)lps[k] * L.Mp1p], h->snorm_d + (size_t)k * L.Mp1p, (size_t)L.Mp1p * sizeof(double), hipMemcpyDeviceToHost));
         for (int k = 0; k < m; k++) {
             const int b = lps[k];
             if (iters) iters[b] += it2[k];
@@ -4037,6 +4217,7 @@ static int solve_batch_rescue(bslv_lpq *h, int B, const int *src, const int *dst
     h->last_update_ms = tot_upd; h->last_total_ms = tot_ms;
     for (int k = 0; k < 5; k++) h->last_ext[k] = ext[k];
     for (int k = 0; k < 3; k++) h->last_p1[k] = p1[k];
+    if (snB > 0) { HIP_TRY(hipMemcpy(h->snorm_d, sn.data(), sn.size() * sizeof(double), hipMemcpyHostToDevice)); h->snorm_B = snB; }
     return 0;
 }
 int bslv_lpq_refactor(bslv_lpq *h, int n, const int *slots, int *status_out)
@@ -4279,6 +4460,29 @@ int bslv_lpq_last_phase1_stats(const bslv_lpq *h, long out[3])
 {
     if (!h || !out) return BSLV_E_ARG;
     for (int k = 0; k < 3; k++) out[k] = h->last_p1[k];
+    return 0;
+}
+// The pricing rule of the dual steps (select_once<.., DVX>): see bslv_hip.h
+int bslv_lpq_set_pricing(bslv_lpq *h, int rule)
+{
+    if (!h || (rule != BSLV_LP_PRICING_DANTZIG && rule != BSLV_LP_PRICING_DEVEX)) { set_error("bslv_lpq_set_pricing: bad argument (rule %d)", rule); return BSLV_E_ARG; }
+    h->pricing = rule;
+    return 0;
+}
+int bslv_lpq_get_pricing(const bslv_lpq *h) { return h ? h->pricing : BSLV_LP_PRICING_DANTZIG; }
+int bslv_lpq_last_pricing_stats(const bslv_lpq *h, long out[3])
+{
+    if (!h || !out) return BSLV_E_ARG;
+    for (int k = 0; k < 3; k++) out[k] = h->last_dvx[k];
+    return 0;
+}
+int bslv_lpq_last_pricing_norms(bslv_lpq *h, int b, double *s)
+{
+    if (!h || !s) { set_error("bslv_lpq_last_pricing_norms: bad argument"); return BSLV_E_ARG; }
+    if (h->snorm_B <= 0 || !h->snorm_d) { set_error("bslv_lpq_last_pricing_norms: the last solve call did not run under Devex pricing"); return BSLV_E_STATE; }
+    if (b < 0 || b >= h->snorm_B) { set_error("bslv_lpq_last_pricing_norms: LP %d of a batch of %d", b, h->snorm_B); return BSLV_E_ARG; }
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpy(s, h->snorm_d + (size_t)b * h->L.Mp1p, (size_t)h->L.M * sizeof(double), hipMemcpyDeviceToHost));
     return 0;
 }
 // The canonical optimal basis (tie phase) for every later solve_batch: see bslv_hip.h; the cut of a vertex is built from these duals (bslv_algs.c:1050)

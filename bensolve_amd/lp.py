@@ -254,6 +254,32 @@ class LpEngine:
         self.lib.bslv_lpq_get_method.argtypes = [ctypes.c_void_p]
         return int(self.lib.bslv_lpq_get_method(self.h))
 
+    def set_pricing(self, rule):
+        """the pricing rule of the dual steps of every later solve_batch: 0 largest violation (default), 1 dual Devex
+        (bslv_lpq_set_pricing, include/bslv_hip.h).  Returns the library's code (0, or BSLV_E_ARG for an unknown rule)."""
+        self.lib.bslv_lpq_set_pricing.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        return int(self.lib.bslv_lpq_set_pricing(self.h, int(rule)))
+
+    def get_pricing(self):
+        self.lib.bslv_lpq_get_pricing.argtypes = [ctypes.c_void_p]
+        return int(self.lib.bslv_lpq_get_pricing(self.h))
+
+    def last_pricing_stats(self):
+        """Devex pricing of the last solve call (bslv_lpq_last_pricing_stats)"""
+        o = (ctypes.c_long * 3)()
+        self.lib.bslv_lpq_last_pricing_stats.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        check(self.lib.bslv_lpq_last_pricing_stats(self.h, o))
+        return dict(weighted=int(o[0]), other_row=int(o[1]), resets=int(o[2]))
+
+    def last_pricing_norms(self, b):
+        """tests: the Devex reference norms of the rows of LP b of the last batch, in the engine's own row numbering
+        (bslv_lpq_last_pricing_norms; raises on BSLV_E_STATE when the last solve call did not run under Devex)"""
+        M = self.M - self.rows_folded()
+        s = np.empty(M, np.float64)
+        self.lib.bslv_lpq_last_pricing_norms.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+        check(self.lib.bslv_lpq_last_pricing_norms(self.h, int(b), s.ctypes.data))
+        return s
+
     def set_canonical(self, on, dir=None):
         """canonical optimal duals for every later solve_batch: the basis that stays optimal when the per-LP bounds move by
         t * dir (var_cnt values) for small t > 0, found by a tie phase after optimality (bslv_lpq_set_canonical, include/bslv_hip.h).

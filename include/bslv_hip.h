@@ -289,6 +289,33 @@ enum { BSLV_LP_METHOD_DUAL = 0, BSLV_LP_METHOD_PRIMAL = 1, BSLV_LP_METHOD_REPAIR
 int  bslv_lpq_set_method(bslv_lpq *h, int method);
 int  bslv_lpq_get_method(const bslv_lpq *h);
 int  bslv_lpq_last_phase1_stats(const bslv_lpq *h, long out[3]);
+/* THE PRICING RULE of the dual simplex steps of every later solve_batch of this engine: which violated basis row leaves.  (The
+ * reference leaves it to GLPK's defaults, glp_init_smcp with only meth set, bslv_lp.c:153-217: projected steepest edge.)
+ *   DANTZIG  the default, and the engine as it was: the row with the largest bound violation (oracle/lp_dense.c dual_simplex).
+ *   DEVEX    dual Devex pricing (Forrest and Goldfarb): every basis row i of an LP has a reference norm s_i >= 1, all 1 in the
+ *            reference framework -- the basis the solve starts from (solve_batch, the in-call rescue's re-solve, the re-start after a
+ *            periodic refactorisation); the row with the largest violation / s_i leaves, ties as under DANTZIG.  A dual pivot on row r
+ *            with the entering column's multipliers f_i = alpha_iq / alpha_rq leaves s_i = max(s_i, |f_i| s_r) (i != r) and
+ *            s_r = max(s_r / |alpha_rq|, 1); the multipliers are the ones the delayed update forms anyway, no tableau entry is read for
+ *            the norms.  Bound switches of the long-step ratio test change nothing; any other basis change (a primal clean-up step, a
+ *            phase-1 step, a refactorisation replay) starts a new framework.  Bland's rule, once it holds, ignores the norms.
+ * With all s_i = 1 the rule IS the default one, bit for bit: the first pivot of every solve, and every LP the default rule solves in at
+ * most one pivot, are the same.  Otherwise: same statuses and optimal values, other pivots, possibly another optimal basis.
+ * Both forms, every method, extended selection on or off, canonical duals on or off.  Objective batches (solve_batch_obj: primal steps
+ * only), the tie phases of the canonical switches and the replay's own selection never read the norms.  With the switch on a batch
+ * runs kernel instances of its own (k_select_dvx, k_select_p1_dvx) and the plan does NOT take k_select_cached, the register-resident
+ * selection of narrow tableau-form batches; with it off nothing is allocated, nothing launched and no bit differs.  Any other rule is
+ * BSLV_E_ARG.  BSLV_LP_PRICING=dantzig|devex sets the rule an engine is created with.
+ * bslv_lpq_last_pricing_stats, of the last solve call: [0] dual selections made under the weighted rule, [1] of those, selections whose
+ * row is not the row of the largest violation, [2] new reference frameworks after the start (one per primal or phase-1 pivot, one per
+ * LP and refactorisation replay during the rounds).  All 0 with the switch off.
+ * bslv_lpq_last_pricing_norms (for tests): s_0 .. s_(M-1) of LP b of the last batch, M rows of the engine's OWN model (the given rows
+ * less bslv_lpq_rows_folded); BSLV_E_STATE if the last solve call did not run under DEVEX, BSLV_E_ARG for b outside the batch. */
+enum { BSLV_LP_PRICING_DANTZIG = 0, BSLV_LP_PRICING_DEVEX = 1 };
+int  bslv_lpq_set_pricing(bslv_lpq *h, int rule);
+int  bslv_lpq_get_pricing(const bslv_lpq *h);
+int  bslv_lpq_last_pricing_stats(const bslv_lpq *h, long out[3]);
+int  bslv_lpq_last_pricing_norms(bslv_lpq *h, int b, double *s);
 /* CANONICAL OPTIMAL DUALS.  Benson's cut is built from the dual solution of P2(v) (w = lp_dual_solution_rows, bslv_algs.c:1050).  Where
  * the optimum is primal degenerate -- y = v + z c on an edge or a vertex of the image -- every w of the normal cone at y is optimal and
  * the basis the pivoting ended in names one of them, which need not be a facet normal.  With on != 0 every later solve_batch ends in the
