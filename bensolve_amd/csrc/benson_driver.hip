@@ -353,7 +353,7 @@ int bslv_benson_start(bslv_benson *h, int *vlp_status)
         if (j > 0 && (rc = bslv_lpq_reset_slot(h->lp, 0))) return rc;
         if ((rc = bslv_lpq_solve_batch(h->lp, 1, &zero, &zero, vlo.data(), vup.data(), &st, &it))) return rc;
         h->tot_pivots += it;
-        if (st != BSLV_LP_OPTIMAL) { *vlp_status = (st == BSLV_LP_INFEASIBLE) ? 1 : 2; return 0; }
+        if (st != BSLV_LP_OPTIMAL) { report_ray(h->lp, "phase 2 (primal), weighted-sum LP", st, 0, vlo.data(), vup.data(), 0, 0, nullptr); *vlp_status = (st == BSLV_LP_INFEASIBLE) ? 1 : 2; return 0; }
         h->tot_lps++;
         double obj;
         if ((rc = bslv_lpq_get_obj(h->lp, 1, &zero, &obj))) return rc;

@@ -10,6 +10,8 @@
 namespace bslv {
 
 void set_error(const char *fmt, ...);
+// the drivers' one line on stderr about the LP whose status ends a run, while the LP engine keeps rays (bslv_lpq_set_rays; lp_certify.inc)
+void report_ray(bslv_lpq *lp, const char *phase, int status, int slot, const double *vlo, const double *vup, int cost_first, int cost_cnt, const double *costs);
 
 #define HIP_TRY(expr)                                                                         \
     do {                                                                                      \

@@ -309,6 +309,108 @@ __global__ __launch_bounds__(NT) void k_cert_final(LpView L, CertView C)
     C.verdict[b] = verdict;
 }
 
+// ---- bslv_lpq_certify_rays: the residuals of the stored rays (see bslv_hip.h), from the vectors bslv_lpq_get_ray returns (the model as
+// given).  The products are k_cert_dense / k_cert_sparse's, over the FARKAS LPs of the call (A' z) and over its DIRECTION LPs (A delta x),
+// each kind compacted: pidx[b] is the place of LP b among the LPs of its kind.  k_cert_ray_final: one workgroup per LP, as k_cert_final.
+struct RayCertView {
+    CertFold F;
+    int vfirst0, vcnt;
+    const double *vlo, *vup;
+    const double *cost;                 // N0 + 1, the engine's own
+    int cfirst0, ccnt;
+    const double *costs;                // [B][ccnt]
+    const double *zg;                   // [B][M0 + N0] as given
+    const int *kind, *pidx;
+    const double *f_hi, *f_lo;          // [nF][N0]  sum over the engine's rows of a_ij z_i
+    const double *d_hi, *d_lo;          // [nD][Mi]  sum_j a_ij delta x_j
+    double tol[4];
+    double *res; int *at, *verdict;
+};
+__global__ __launch_bounds__(NT) void k_cert_ray_final(RayCertView C)
+{
+    __shared__ ValIdx vi_s[NT];
+    __shared__ double sh_s[NT], sl_s[NT];
+    const CertFold &F = C.F;
+    const int b = blockIdx.x, t = threadIdx.x;
+    const int M0 = F.M0, N0 = F.N0, Mi = F.Mi, NG = M0 + N0;
+    const int kind = C.kind[b];
+    if (kind == BSLV_LP_RAY_NONE) {
+        if (t == 0) { for (int k = 0; k < 4; k++) { C.res[(size_t)b * 4 + k] = NAN; C.at[(size_t)b * 4 + k] = -1; } C.verdict[b] = 15; }
+        return;
+    }
+    const bool farkas = kind == BSLV_LP_RAY_FARKAS;
+    const double *z = C.zg + (size_t)b * NG;
+    const size_t p = (size_t)C.pidx[b];
+    ValIdx r0{-1.0, -1}, r1{0.0, -1}, nan{0.0, -1};
+    double Ss = 0.0, Sc = 0.0, As = 0.0, Ac = 0.0;
+    // (one loop per kind, chosen outside: the two share no load but z, lo and up)
+    if (farkas) {
+        for (int k = t; k < NG; k += NT) {
+            const int jv = k - C.vfirst0;
+            const bool per_lp = jv >= 0 && jv < C.vcnt;
+            const double lo = per_lp ? C.vlo[(size_t)b * C.vcnt + jv] : F.lb0[k], up = per_lp ? C.vup[(size_t)b * C.vcnt + jv] : F.ub0[k];
+            const double zk = z[k];
+            if (zk != zk) nan = ValIdx{1.0, k};
+            if (k >= M0) {                  // ident: z_{M+j} + sum_i a_ij z_i, the folded rows' terms elementwise
+                const int j = k - M0;
+                double s = 0.0, c = 0.0;
+                dd_add(s, c, zk);
+                dd_add(s, c, C.f_hi[p * N0 + j]);
+                c += C.f_lo[p * N0 + j];
+                if (F.fptr) for (int u = F.fptr[j]; u < F.fptr[j + 1]; u++) dd_mad(s, c, F.fold_a[F.frow[u]], z[F.frow[u]]);
+                r0 = better_max(r0, ValIdx{fabs(s + c), k});
+            }
+            if (fabs(zk) > C.tol[2]) {
+                const double bnd = zk > 0.0 ? lo : up;
+                if (isfinite(bnd)) { dd_mad(Ss, Sc, zk, bnd); dd_mad(As, Ac, fabs(zk), fabs(bnd)); }
+                else r1 = better_max(r1, ValIdx{fabs(zk), k});
+            }
+        }
+    } else {
+        for (int k = t; k < NG; k += NT) {
+            const int jv = k - C.vfirst0;
+            const bool per_lp = jv >= 0 && jv < C.vcnt;
+            const double lo = per_lp ? C.vlo[(size_t)b * C.vcnt + jv] : F.lb0[k], up = per_lp ? C.vup[(size_t)b * C.vcnt + jv] : F.ub0[k];
+            const double zk = z[k];
+            if (zk != zk) nan = ValIdx{1.0, k};
+            if (k < M0) {                   // rows: delta r - A delta x
+                const int i = F.row_in ? F.row_in[k] : k;
+                double val;
+                if (i >= 0) {
+                    double s, e;
+                    two_sum(zk, -C.d_hi[p * Mi + i], s, e);
+                    val = fabs(s + (e - C.d_lo[p * Mi + i]));
+                } else {                    // folded: delta r - a delta x_j, the product exact
+                    const double a = F.fold_a[k], x = z[M0 + F.fold_col[k]], h = a * x, e = fma(a, x, -h);
+                    val = fabs((zk - h) - e);
+                }
+                r0 = better_max(r0, ValIdx{val, k});
+            }
+            if (isfinite(lo)) r1 = better_max(r1, ValIdx{-zk, k});
+            if (isfinite(up)) r1 = better_max(r1, ValIdx{zk, k});
+            const int tc = k - C.cfirst0;
+            const double ck = C.ccnt > 0 ? ((tc >= 0 && tc < C.ccnt) ? C.costs[(size_t)b * C.ccnt + tc] : 0.0) : (k >= M0 ? C.cost[k - M0 + 1] : 0.0);
+            dd_mad(Ss, Sc, -ck, zk);
+            dd_mad(As, Ac, fabs(ck), fabs(zk));
+        }
+    }
+    r0 = cert_block_argmax(r0, vi_s);
+    r1 = cert_block_argmax(r1, vi_s);
+    nan = cert_block_argmax(nan, vi_s);
+    cert_block_sum(Ss, Sc, sh_s, sl_s);
+    cert_block_sum(As, Ac, sh_s, sl_s);
+    if (t) return;
+    double r[4] = {r0.i < 0 ? 0.0 : r0.v, r1.v > 0.0 ? r1.v : 0.0, Ss + Sc, As + Ac};      // (not below 0, and no -0)
+    if (nan.v > 0.0) { r[0] = NAN; r[1] = NAN; }
+    const int a[4] = {r0.i, r1.v > 0.0 ? r1.i : -1, -1, -1};
+    int verdict = 0;
+    if (!(r[0] <= (farkas ? C.tol[0] : C.tol[1]))) verdict |= 1;
+    if (!(r[1] <= C.tol[2])) verdict |= 2;
+    if (!(r[2] > C.tol[3] * (1.0 + r[3]))) verdict |= 4;
+    for (int k = 0; k < 4; k++) { C.res[(size_t)b * 4 + k] = r[k]; C.at[(size_t)b * 4 + k] = a[k]; }
+    C.verdict[b] = verdict;
+}
+
 }  // namespace bslv
 
 struct CertTimer {          // BSLV_LP_CERTIFY_TIMING=1: HIP events around each kernel
@@ -483,6 +585,176 @@ int bslv_lpq_last_certify_stats(const bslv_lpq *h, long out[3])
     for (int k = 0; k < 3; k++) out[k] = h->last_cert[k];
     return 0;
 }
+
+int bslv_lpq_certify_rays(bslv_lpq *h, int B, const int *slot, const double *vlo, const double *vup, int cost_first, int cost_cnt, const double *costs,
+                          const double *tol, double *res, int *at, int *verdict)
+{
+    if (!h || B < 0) { set_error("bslv_lpq_certify_rays: bad argument"); return BSLV_E_ARG; }
+    if (!h->rays_on) { set_error("bslv_lpq_certify_rays: the ray store is off (bslv_lpq_set_rays)"); return BSLV_E_STATE; }
+    const LpView &L = h->L;
+    const bslv_lpq::Presolve &P = h->ps;
+    const int M0 = P.M0, N0 = P.N0, Mi = L.M, NG = M0 + N0, vcnt = L.vcnt;
+    if (cost_cnt < 0 || cost_first < 0 || cost_first + cost_cnt > NG || (cost_cnt > 0 && !costs)) { set_error("bslv_lpq_certify_rays: bad cost range (%d, %d)", cost_first, cost_cnt); return BSLV_E_ARG; }
+    if (B == 0) return 0;
+    if (!slot || !res || (vcnt > 0 && (!vlo || !vup))) { set_error("bslv_lpq_certify_rays: bad argument"); return BSLV_E_ARG; }
+    for (int b = 0; b < B; b++) if (slot[b] < 0 || slot[b] >= h->slots) { set_error("bslv_lpq_certify_rays: bad slot"); return BSLV_E_ARG; }
+    int vfirst0 = 0;
+    if (vcnt > 0) {
+        if (L.vfirst >= Mi) vfirst0 = M0 + (L.vfirst - Mi);
+        else for (int i = 0; i < M0; i++) if (P.row_in[i] == L.vfirst) vfirst0 = i;
+    }
+    auto al = [](size_t n) { return (n + 255) / 256 * 256; };
+    std::vector<int> fptr, frow;
+    if (P.nfold) {
+        fptr.assign(N0 + 1, 0);
+        for (int i = 0; i < M0; i++) if (P.row_in[i] < 0) fptr[P.fold_col[i] + 1]++;
+        for (int j = 0; j < N0; j++) fptr[j + 1] += fptr[j];
+        frow.resize(P.nfold);
+        std::vector<int> fill(fptr.begin(), fptr.end() - 1);
+        for (int i = 0; i < M0; i++) if (P.row_in[i] < 0) frow[fill[P.fold_col[i]]++] = i;
+    }
+    const int NP = std::max(Mi, N0);      // (an LP has one kind: its product's input and output fit in 3 NP)
+    const size_t per_lp = 8 * ((size_t)NG + 3 * NP + 2 * vcnt + cost_cnt + 4) + 4 * 7;
+    size_t budget = (size_t)256 << 20;
+    if (const char *e = getenv("BSLV_LP_CERTIFY_SCRATCH_MB")) budget = (size_t)std::max(1, atoi(e)) << 20;
+    size_t Bc = std::max<size_t>(1, budget / per_lp);
+    if (Bc >= (size_t)CERT_G) Bc = Bc / CERT_G * CERT_G;
+    if (const char *e = getenv("BSLV_LP_CERTIFY_CHUNK")) Bc = (size_t)std::max(1, atoi(e));
+    Bc = std::min(Bc, (size_t)B);
+    size_t cur = 0;
+    auto take = [&](size_t bytes) { const size_t at = cur; cur += al(std::max<size_t>(bytes, 1)); return at; };
+    const size_t o_lb0 = take((size_t)NG * 8), o_ub0 = take((size_t)NG * 8), o_cost = take((size_t)(N0 + 1) * 8);
+    const size_t nf = P.nfold ? 1 : 0;
+    const size_t o_row_in = take(nf * M0 * 4), o_fold_col = take(nf * M0 * 4), o_fold_a = take(nf * M0 * 8), o_fptr = take(nf * (N0 + 1) * 4), o_frow = take(nf * P.nfold * 4);
+    const size_t o_kind = take(Bc * 4), o_pidx = take(Bc * 4), o_verdict = take(Bc * 4), o_at = take(Bc * 4 * 4), o_res = take(Bc * 4 * 8);
+    const size_t o_vlo = take(Bc * 8 * vcnt), o_vup = take(Bc * 8 * vcnt), o_costs = take(Bc * 8 * cost_cnt);
+    const size_t o_zg = take(Bc * 8 * NG), o_v = take(Bc * 8 * NP), o_hi = take(Bc * 8 * NP), o_lo = take(Bc * 8 * NP);
+    hipStream_t s = h->stream;
+    int rc;
+    if ((rc = cert_ensure(h, cur))) return rc;
+    char *base = (char *)h->cert_d;
+    RayCertView C{};
+    CertFold &F = C.F;
+    F.M0 = M0; F.N0 = N0; F.Mi = Mi;
+    HIP_TRY(hipMemcpyAsync(base + o_lb0, P.lb0.data(), (size_t)NG * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(base + o_ub0, P.ub0.data(), (size_t)NG * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(base + o_cost, h->cost.data(), (size_t)(N0 + 1) * 8, hipMemcpyHostToDevice, s));
+    F.lb0 = (const double *)(base + o_lb0); F.ub0 = (const double *)(base + o_ub0); C.cost = (const double *)(base + o_cost);
+    if (P.nfold) {
+        HIP_TRY(hipMemcpyAsync(base + o_row_in, P.row_in.data(), (size_t)M0 * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(base + o_fold_col, P.fold_col.data(), (size_t)M0 * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(base + o_fold_a, P.fold_a.data(), (size_t)M0 * 8, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(base + o_fptr, fptr.data(), (size_t)(N0 + 1) * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(base + o_frow, frow.data(), (size_t)P.nfold * 4, hipMemcpyHostToDevice, s));
+        F.row_in = (const int *)(base + o_row_in); F.fold_col = (const int *)(base + o_fold_col); F.fold_a = (const double *)(base + o_fold_a);
+        F.fptr = (const int *)(base + o_fptr); F.frow = (const int *)(base + o_frow);
+    }
+    int *kind_d = (int *)(base + o_kind), *pidx_d = (int *)(base + o_pidx), *verdict_d = (int *)(base + o_verdict), *at_d = (int *)(base + o_at);
+    double *res_d = (double *)(base + o_res), *vlo_d = (double *)(base + o_vlo), *vup_d = (double *)(base + o_vup), *costs_d = (double *)(base + o_costs);
+    double *zg_d = (double *)(base + o_zg), *v_d = (double *)(base + o_v), *hi_d = (double *)(base + o_hi), *lo_d = (double *)(base + o_lo);
+    const double deflt[4] = {1e-8, 1e-9, 1e-9, 1e-9};      // (bslv_lpq_certify's dj, rows, dual-zero and gap numbers)
+    for (int k = 0; k < 4; k++) C.tol[k] = (tol && tol[k] > 0.0) ? tol[k] : deflt[k];
+    C.vfirst0 = vfirst0; C.vcnt = vcnt; C.vlo = vlo_d; C.vup = vup_d;
+    C.cfirst0 = cost_first; C.ccnt = cost_cnt; C.costs = costs_d;
+    C.zg = zg_d; C.kind = kind_d; C.pidx = pidx_d;
+    C.res = res_d; C.at = at_d; C.verdict = verdict_d;
+    const bool timing = getenv("BSLV_LP_CERTIFY_TIMING") != nullptr;
+    CertTimer T(timing, s);
+    long launches = 0, bad = 0;
+    std::vector<int> vd(Bc), kd(Bc), px(Bc);
+    std::vector<double> zg(Bc * NG), v(Bc * NP);
+    for (size_t b0 = 0; b0 < (size_t)B; b0 += Bc) {
+        const int nb = (int)std::min(Bc, (size_t)B - b0);
+        if ((rc = bslv_lpq_get_ray(h, nb, slot + b0, kd.data(), zg.data()))) return rc;
+        // the LPs of each kind, compacted: the FARKAS ones from the front of v, the DIRECTION ones behind them
+        int nF = 0, nD = 0;
+        for (int b = 0; b < nb; b++) nF += kd[b] == BSLV_LP_RAY_FARKAS;
+        double *vF = v.data(), *vD = v.data() + (size_t)nF * Mi;
+        for (int b = 0, f = 0; b < nb; b++) {
+            const double *z = &zg[(size_t)b * NG];
+            px[b] = -1;
+            if (kd[b] == BSLV_LP_RAY_FARKAS) { for (int i = 0; i < M0; i++) if (P.row_in[i] >= 0) vF[(size_t)f * Mi + P.row_in[i]] = z[i]; px[b] = f++; }
+            else if (kd[b] == BSLV_LP_RAY_DIRECTION) { memcpy(vD + (size_t)nD * N0, z + M0, (size_t)N0 * 8); px[b] = nD++; }
+        }
+        HIP_TRY(hipMemcpyAsync(kind_d, kd.data(), (size_t)nb * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(pidx_d, px.data(), (size_t)nb * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(zg_d, zg.data(), (size_t)nb * NG * 8, hipMemcpyHostToDevice, s));
+        if (nF + nD) HIP_TRY(hipMemcpyAsync(v_d, v.data(), ((size_t)nF * Mi + (size_t)nD * N0) * 8, hipMemcpyHostToDevice, s));
+        if (vcnt > 0) {
+            HIP_TRY(hipMemcpyAsync(vlo_d, vlo + b0 * vcnt, (size_t)nb * vcnt * 8, hipMemcpyHostToDevice, s));
+            HIP_TRY(hipMemcpyAsync(vup_d, vup + b0 * vcnt, (size_t)nb * vcnt * 8, hipMemcpyHostToDevice, s));
+        }
+        if (cost_cnt > 0) HIP_TRY(hipMemcpyAsync(costs_d, costs + b0 * cost_cnt, (size_t)nb * cost_cnt * 8, hipMemcpyHostToDevice, s));
+        // A' z of the FARKAS LPs, A delta x of the DIRECTION LPs (outputs side by side as the inputs are)
+        double *fh = hi_d, *fl = lo_d, *dh = hi_d + (size_t)nF * N0, *dl = lo_d + (size_t)nF * N0;
+        C.f_hi = fh; C.f_lo = fl; C.d_hi = dh; C.d_lo = dl;
+        for (int which = 0; which < 2; which++) {
+            const bool trans = which == 0;
+            const int n = trans ? nF : nD;
+            if (n == 0) continue;
+            const int groups = (n + CERT_G - 1) / CERT_G, nout = trans ? N0 : Mi, nred = trans ? Mi : N0;
+            const double *vin = trans ? v_d : v_d + (size_t)nF * Mi;
+            double *hi = trans ? fh : dh, *lo = trans ? fl : dl;
+            T.start();
+            if (!L.rev) {
+                const dim3 grid((nout + CERT_TO - 1) / CERT_TO, groups);
+                if (trans) hipLaunchKernelGGL(k_cert_dense<true>, grid, dim3(NT), 0, s, h->Tstd, L.ld, nout, nred, vin, (size_t)nred, n, hi, lo, (size_t)nout);
+                else hipLaunchKernelGGL(k_cert_dense<false>, grid, dim3(NT), 0, s, h->Tstd, L.ld, nout, nred, vin, (size_t)nred, n, hi, lo, (size_t)nout);
+            } else {
+                const dim3 grid((nout + CERT_SR - 1) / CERT_SR, groups);
+                if (trans) hipLaunchKernelGGL(k_cert_sparse, grid, dim3(NT), 0, s, L.cptr, L.cidx, L.cval, nout, vin, (size_t)nred, n, hi, lo, (size_t)nout);
+                else hipLaunchKernelGGL(k_cert_sparse, grid, dim3(NT), 0, s, L.rptr, L.ridx, L.rval, nout, vin, (size_t)nred, n, hi, lo, (size_t)nout);
+            }
+            launches++;
+            T.stop(which);
+        }
+        T.start();
+        hipLaunchKernelGGL(k_cert_ray_final, dim3(nb), dim3(NT), 0, s, C);
+        launches++;
+        T.stop(2);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(res + b0 * 4, res_d, (size_t)nb * 4 * 8, hipMemcpyDeviceToHost, s));
+        if (at) HIP_TRY(hipMemcpyAsync(at + b0 * 4, at_d, (size_t)nb * 4 * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(vd.data(), verdict_d, (size_t)nb * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        for (int b = 0; b < nb; b++) { bad += vd[b] != 0; if (verdict) verdict[b0 + b] = vd[b]; }
+    }
+    h->last_raycert[0] = B; h->last_raycert[1] = bad; h->last_raycert[2] = launches;
+    if (timing) fprintf(stderr, "bslv_lpq_certify_rays: %d LPs (%s form, %d x %d, chunks of %zu) A' z %.3f ms, A delta x %.3f ms, final %.3f ms; %ld launches, %ld not certified\n",
+                        B, L.rev ? "revised" : "tableau", Mi, N0, Bc, T.ms[0], T.ms[1], T.ms[2], launches, bad);
+    return 0;
+}
+
+int bslv_lpq_last_ray_certify_stats(const bslv_lpq *h, long out[3])
+{
+    if (!h || !out) return BSLV_E_ARG;
+    for (int k = 0; k < 3; k++) out[k] = h->last_raycert[k];
+    return 0;
+}
+
+}  // extern "C"
+
+// The drivers' helper (benson_driver.hip, vlp_phases.hip): an LP came back INFEASIBLE or UNBOUNDED and that ends the run.  While the
+// engine keeps rays (BSLV_LP_RAYS=1 arranges that), one line on stderr says what the stored ray proves for the model as given; with the
+// switch off nothing is done and nothing is printed.
+namespace bslv {
+void report_ray(bslv_lpq *lp, const char *phase, int status, int slot, const double *vlo, const double *vup, int cost_first, int cost_cnt, const double *costs)
+{
+    if (!lp || !bslv_lpq_get_rays(lp) || (status != BSLV_LP_INFEASIBLE && status != BSLV_LP_UNBOUNDED)) return;
+    int kind = BSLV_LP_RAY_NONE, at[4] = {-1, -1, -1, -1}, verdict = -1;
+    double res[4] = {NAN, NAN, NAN, NAN};
+    if (bslv_lpq_get_ray(lp, 1, &slot, &kind, nullptr) || bslv_lpq_certify_rays(lp, 1, &slot, vlo, vup, cost_first, cost_cnt, costs, nullptr, res, at, &verdict)) {
+        fprintf(stderr, "BSLV_LP_RAYS: %s: LP status %s, the ray could not be examined (%s)\n", phase, status == BSLV_LP_INFEASIBLE ? "INFEASIBLE" : "UNBOUNDED", bslv_last_error());
+        return;
+    }
+    const bool dir = kind == BSLV_LP_RAY_DIRECTION;
+    fprintf(stderr, "BSLV_LP_RAYS: %s: LP status %s, ray kind %s, %s %.3e at %d, %s %.3e at %d, margin %.3e, scale %.3e, verdict %d: %s\n", phase,
+            status == BSLV_LP_INFEASIBLE ? "INFEASIBLE" : "UNBOUNDED", kind == BSLV_LP_RAY_FARKAS ? "FARKAS" : dir ? "DIRECTION" : "NONE",
+            dir ? "rows" : "ident", res[0], at[0], dir ? "cross" : "open", res[1], at[1], res[2], res[3], verdict, verdict == 0 ? "certified" : "not certified");
+}
+}  // namespace bslv
+
+extern "C" {
 
 // for tests only: plain copies, no kernel
 int bslv_lpq_debug_poke(bslv_lpq *h, int slot, int what, int var, double delta)

@@ -57,6 +57,14 @@ constexpr int PF_PERT = 1, PF_PRIMAL = 2, PF_PERT_PENDING = 4, PF_USES_SHIFT = 8
 // primal phase 1 (bits 4..7 of pflags; the perturbations of the solve are counted from bit PF_USES_SHIFT up): the LP is in phase 1 and dper
 // holds its pricing vector d1; it has been there in this solve; d1 has to be rebuilt from the rows; d1 is current although nothing is pending
 constexpr int PF_PHASE1 = 16, PF_P1_SEEN = 32, PF_P1_STALE = 64, PF_P1_KEEP = 128;
+// RAY RECORD (bslv_lpq_set_rays): the thread that concludes INFEASIBLE or UNBOUNDED while it holds the proof leaves one word in
+// BatchView::stall -- a finished LP has no use for its stall count, and no member is added to BatchView (see DvxView) -- from which k_ray
+// builds the vector after the rounds: RAY_REC | index << 7 | pending pivots << 3 | side << 2 | what.  what: RAY_ROW = the dual selection's
+// row `index` without an entering candidate (side: below its lower bound), RAY_P1 = phase 1 without an improving column, RAY_DIR = the
+// primal step's column `index` without a blocking row (side: dir = +1).  The pending count says where the selection's row[] / pc[] lie.
+// A stall count never reaches RAY_REC (it is at most the iteration limit).
+constexpr int RAY_REC = 1 << 30, RAY_ROW = 1, RAY_P1 = 2, RAY_DIR = 3, RAY_IDX_MAX = 1 << 23;
+__device__ __forceinline__ int ray_record(int what, int idx, int np, bool side) { return RAY_REC | (idx << 7) | (np << 3) | (side ? 4 : 0) | what; }
 constexpr int STALL_LIMIT = 3;         // consecutive degenerate pivots (dual step <= 1e-11) after which the costs are perturbed
 constexpr int PERT_MAX_USES = 3;       // perturbations per solve
 #ifndef BSLV_KP
@@ -801,9 +809,10 @@ __device__ __forceinline__ void conclude_optimal(const LpView &L, const BatchVie
     if (tid == 0) { Bv.status[b] = flag > 0.0 ? BSLV_LP_UNBOUNDED : BSLV_LP_OPTIMAL; Bv.mode[b] = MODE_NONE; }
 }
 // No entering candidate: primal infeasible -- unless the violation is rounding debris in beta: recompute it first
-__device__ __forceinline__ void conclude_infeasible(const BatchView &Bv, const int b, const int verified)
+// (r, below, np: the row at hand, for the ray record)
+__device__ __forceinline__ void conclude_infeasible(const BatchView &Bv, const int b, const int verified, const int r, const bool below, const int np)
 {
-    if (threadIdx.x == 0) { if (!(verified & 1)) Bv.mode[b] = MODE_REFRESH; else { Bv.status[b] = BSLV_LP_INFEASIBLE; Bv.mode[b] = MODE_NONE; } }
+    if (threadIdx.x == 0) { if (!(verified & 1)) Bv.mode[b] = MODE_REFRESH; else { Bv.status[b] = BSLV_LP_INFEASIBLE; Bv.mode[b] = MODE_NONE; Bv.stall[b] = ray_record(RAY_ROW, r, np, below); } }
 }
 __device__ __noinline__ void trace_pivot(int b, int iters, bool primal, int r, int kb, bool below, double viol, int q, int kn, double trq, double dq, int nflip, double obj, bool bland, bool perturbed)
 {
@@ -1080,7 +1089,7 @@ __device__ __forceinline__ bool primal_step(const LpView &L, const BatchView &Bv
             // nothing lowers the sum of infeasibilities: primal infeasible -- on a recomputed beta (the pass leaves nothing pending: d1 is rebuilt too)
             if (tid == 0) {
                 if (!(Bv.verified[b] & 1)) { Bv.mode[b] = MODE_REFRESH; Bv.pflags[b] = pf | PF_P1_STALE; }
-                else { Bv.status[b] = BSLV_LP_INFEASIBLE; Bv.mode[b] = MODE_NONE; }
+                else { Bv.status[b] = BSLV_LP_INFEASIBLE; Bv.mode[b] = MODE_NONE; Bv.stall[b] = ray_record(RAY_P1, 0, c.np, false); }      // (sg is in c.pc, d1 in dper)
             }
             return false;
         }
@@ -1117,7 +1126,7 @@ __device__ __forceinline__ bool primal_step(const LpView &L, const BatchView &Bv
     }
     tmax = block_min(tmax, sv);
     if (isinf(tmax)) {
-        if (tid == 0) { Bv.status[b] = (P1 && ph1) ? BSLV_LP_UNEXPECTED : BSLV_LP_UNBOUNDED; Bv.mode[b] = MODE_NONE; }      // (phase 1 has a bounded objective: the oracle says UNEXPECTED too)
+        if (tid == 0) { Bv.status[b] = (P1 && ph1) ? BSLV_LP_UNEXPECTED : BSLV_LP_UNBOUNDED; Bv.mode[b] = MODE_NONE; Bv.stall[b] = ray_record(RAY_DIR, q, c.np, dir > 0.0); }      // (phase 1 has a bounded objective: the oracle says UNEXPECTED too)
         return false;
     }
     ValIdx lv{0.0, -1};
@@ -1417,7 +1426,7 @@ __device__ __forceinline__ bool select_once(const LpView &L, const BatchView &Bv
     }
     th = block_min(th, sv);
     phase_mark(L, Bv, b, 3, tk);
-    if (isinf(th)) { conclude_infeasible(Bv, b, Bv.verified[b]); return true; }
+    if (isinf(th)) { conclude_infeasible(Bv, b, Bv.verified[b], r, below, np); return true; }
     // pass 2: largest |pivot| within the bound
     ValIdx piv{0.0, -1};
     for (int j0 = tid; j0 < N; j0 += PU * NT) {
@@ -1622,7 +1631,7 @@ __device__ __forceinline__ bool select_once_cached(const LpView &L, const BatchV
     }
     th = block_min(th, sv);
     phase_mark(L, Bv, b, 3, tk);
-    if (isinf(th)) { conclude_infeasible(Bv, b, verified); return true; }
+    if (isinf(th)) { conclude_infeasible(Bv, b, verified, r, below, np); return true; }
     // pass 2: largest |pivot| within the bound
     ValIdx piv{0.0, -1};
     if (bland) {
@@ -2309,6 +2318,75 @@ __global__ void k_get_obj(LpView L, const int *slots, int B, double c0, double *
     if (b >= B) return;
     out[b] = L.beta[(size_t)slots[b] * L.Mp1p + L.M] + c0;
 }
+// ---- k_ray (bslv_lpq_set_rays): the Farkas vector or recession direction of every LP of the batch that concluded with one in hand
+// (the ray record in Bv.stall, see RAY_REC) -> the ray store of its slot, in the engine's own indices; kind NONE for every other LP.
+// One workgroup per LP, once after the rounds of the call.  With x_B = T x_N (T = -B^-1 N: what row[] and pc[] hold a row / column of)
+//   RAY_ROW  basic variable k = bh[r] below its lower bound:  z_k = 1, z_{nh[j]} = -row[j];  above its upper bound: the negative
+//   RAY_P1   z_{bh[i]} = -sg_i (sg = infeas_sign: -1 below), z_{nh[j]} = d1[j] = sum_i sg_i T[i][j]
+//   RAY_DIR  delta_{nh[q]} = dir, delta_{bh[i]} = pc[i] dir
+// then every entry is divided by the largest absolute entry (a value: which entry holds it does not matter; ties need no rule).
+// THE VECTORS ARE STILL THERE: an LP whose status has left ST_RUNNING is skipped by every selection at its first line (select_once,
+// select_once_cached), so row[] (prow at the record's pending count, or trow in the revised form -- select_once_cached stores it too), pc[]
+// and dper stand as the concluding selection left them; k_flush and k_park_copy only READ prow / pcol / desc, k_rev_u writes uvec / xfull,
+// the refactorisation during a solve lists running LPs only, and the tie phases (which run after this kernel) take OPTIMAL LPs only.
+// The heads bh / nh of the slot follow committed pivots alone.
+struct RayView { int *kind; double *ray; int *stat; };      // [slots], [slots][M + N]; [3] of the call: FARKAS stored, DIRECTION stored, conclusions without a ray
+__global__ __launch_bounds__(NT) void k_ray(LpView L, BatchView Bv, RayView R, int B)
+{
+    __shared__ double sv[NT / WAVE];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    if (b >= B) return;
+    const int slot = Bv.dst[b], st = Bv.status[b], rec = Bv.stall[b], M = L.M, N = L.N;
+    const bool has = (st == BSLV_LP_INFEASIBLE || st == BSLV_LP_UNBOUNDED) && (rec & RAY_REC);
+    if (!has) {
+        if (tid == 0) { R.kind[slot] = BSLV_LP_RAY_NONE; if (st == BSLV_LP_INFEASIBLE || st == BSLV_LP_UNBOUNDED) atomicAdd(&R.stat[2], 1); }
+        return;
+    }
+    const int what = rec & 3, np = min((rec >> 3) & 15, KP - 1), idx = (rec >> 7) & (RAY_IDX_MAX - 1);
+    const double sgn = (rec & 4) ? 1.0 : -1.0;
+    const double *row = L.rev ? Bv.trow + (size_t)b * L.ld : Bv.prow + ((size_t)b * KP + np) * L.ld;
+    const double *pc = Bv.pcol + ((size_t)b * KP + np) * L.Mp1p, *d1 = Bv.dper + (size_t)b * L.ld;
+    const int *bh = L.bh + (size_t)slot * M, *nh = L.nh + (size_t)slot * N;
+    double *z = R.ray + (size_t)slot * (M + N);
+    // (every vector is loaded whatever the record says -- all three are the batch's own, allocated in both forms -- and the entry is a
+    // SELECT among the three rules: a branch on `what` inside these loops left the index of the store undefined on the RAY_DIR path in the
+    // code the compiler made of it, and the first objective batch with an unbounded LP wrote to a wild address)
+    const bool is_row = what == RAY_ROW, is_p1 = what == RAY_P1;
+    double amax = 0.0;
+    for (int i = tid; i < M; i += NT) {
+        const double c = pc[i];
+        const int k = bh[i];
+        const double v_row = i == idx ? sgn : 0.0, v_p1 = c == 0.0 ? 0.0 : -c, v_dir = c * sgn;
+        const double v = is_row ? v_row : (is_p1 ? v_p1 : v_dir);
+        z[k] = v;
+        amax = fmax(amax, fabs(v));
+    }
+    for (int j = tid; j < N; j += NT) {
+        const double a = row[j], d = d1[j];
+        const int k = nh[j];
+        const double v_dir = j == idx ? sgn : 0.0;
+        const double v = is_row ? -sgn * a : (is_p1 ? d : v_dir);
+        z[k] = v;
+        amax = fmax(amax, fabs(v));
+    }
+    amax = block_max(amax, sv);      // (its barriers also put z in front of the whole workgroup)
+    if (amax > 0.0 && amax < INFINITY) for (int k = tid; k < M + N; k += NT) z[k] = z[k] / amax;
+    if (tid == 0) {
+        const int kind = what == RAY_DIR ? BSLV_LP_RAY_DIRECTION : BSLV_LP_RAY_FARKAS;
+        R.kind[slot] = kind;
+        atomicAdd(&R.stat[kind == BSLV_LP_RAY_FARKAS ? 0 : 1], 1);
+    }
+}
+// the kinds and vectors of the listed slots, gathered for one copy to the host (bslv_lpq_get_ray)
+__global__ void k_ray_get(RayView R, const int *slots, int B, int nv, int *kind, double *out)
+{
+    const size_t n = (size_t)B * nv, idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= n) return;
+    const int b = (int)(idx / nv), k = (int)(idx % nv), slot = slots[b];
+    if (k == 0) kind[b] = R.kind[slot];
+    if (out) out[idx] = R.kind[slot] == BSLV_LP_RAY_NONE ? 0.0 : R.ray[(size_t)slot * nv + k];
+}
+
 __global__ void k_std_heads(LpView L, int slot)
 {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -2703,6 +2781,12 @@ struct bslv_lpq {
     // bslv_lpq_certify (lp_certify.inc): its scratch, grown to the largest call and released with the engine; the counters of the last call
     void *cert_d = nullptr; size_t cert_cap = 0;
     long last_cert[3] = {0, 0, 0};
+    // the ray store (bslv_lpq_set_rays, BSLV_LP_RAYS at create): per slot a kind and a vector of M + N doubles beside the pool (like the
+    // ages: no part of bslv_lpq_slot_bytes), the call's counters on the device; the counters of the last solve call and of the last
+    // bslv_lpq_certify_rays
+    bool rays_on = false;
+    int *raykind_d = nullptr, *raystat_d = nullptr; double *ray_d = nullptr;
+    long last_ray[3] = {0, 0, 0}, last_raycert[3] = {0, 0, 0};
     PivDesc *desc_d = nullptr;
     int *status_h = nullptr;          // pinned
     // stats
@@ -2982,6 +3066,8 @@ static int raw_create(bslv_lpq **out, int M, int N, const double *A, const doubl
     if (const char *e = getenv("BSLV_LP_REFACTOR_EVERY")) { if (rev) h->period = std::max(0, atoi(e)); }
     // BSLV_LP_PARK=0: bslv_lpq_park makes the passes at once, as bslv_lpq_materialise does (bslv_lpq_set_park)
     if (const char *e = getenv("BSLV_LP_PARK")) h->park.on = atoi(e) != 0;
+    // BSLV_LP_RAYS=1: the ray store of bslv_lpq_set_rays, in both forms
+    if (const char *e = getenv("BSLV_LP_RAYS")) if (atoi(e) != 0 && (rc = bslv_lpq_set_rays(h, 1))) return fail(rc);
     *out = h;
     return 0;
 }
@@ -2992,6 +3078,7 @@ void bslv_lpq_destroy(bslv_lpq *h)
     park_free(h);
     period_free(h);
     auto fr = [](void *p) { if (p) (void)hipFree(p); };
+    fr(h->raykind_d); fr(h->raystat_d); fr(h->ray_d);
     fr(h->age_d); fr(h->age0_d); fr(h->cert_d); fr(h->snorm_d); fr(h->dvxstat_d);
     fr(h->L.T); fr(h->L.beta); fr(h->L.xN); fr(h->L.bh); fr(h->L.nh); fr(h->L.nstat); fr(h->L.pos);
     fr(h->Tstd); fr(h->lb_d); fr(h->ub_d); fr(h->art_d);
@@ -3127,6 +3214,7 @@ int bslv_lpq_reset_slot(bslv_lpq *h, int slot)
     hipLaunchKernelGGL(k_std_heads, dim3((n + 255) / 256), dim3(256), 0, h->stream, L, slot);
     HIP_TRY(hipGetLastError());
     if (L.rev) HIP_TRY(hipMemsetAsync(h->age_d + slot, 0, sizeof(long long), h->stream));      // (the identity: no step applied)
+    if (h->rays_on) HIP_TRY(hipMemsetAsync(h->raykind_d + slot, 0, sizeof(int), h->stream));     // (BSLV_LP_RAY_NONE)
     HIP_TRY(hipStreamSynchronize(h->stream));
     return 0;
 }
@@ -3785,6 +3873,7 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
         for (int k = 0; k < 3; k++) h->last_p1[k] = 0;
         for (int k = 0; k < 4; k++) h->last_canon[k] = 0;
         if (cvals) for (int k = 0; k < 4; k++) h->last_canon_obj[k] = 0;
+        if (h->rays_on) h->last_ray[2] += B;      // (no slot is touched: nothing to hang a ray on)
         return 0;
     }
     if (!h || B < 0 || (B > 0 && (!src || !dst)) || (B > 0 && h->L.vcnt > 0 && (!vlo || !vup))) {
@@ -3947,6 +4036,27 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
         // with a period the status vector is read at least every max(1, K / KP) rounds: an LP below K at one readback has made at most
         // max(KP, K) pivots more at the next, so no selection is made on a matrix older than 2 K + KP
         if (period > 0) chunk = std::min(chunk, std::max(1, period / KP));
+    }
+    // the ray store: kind and vector of every dst slot (k_ray; before the tie phases, which reuse the scratch of their OPTIMAL LPs)
+    if (h->rays_on) {
+        static const bool tm = getenv("BSLV_LP_RAY_TIMING") != nullptr;      // one line per solve call on stderr: the HIP-event time of k_ray
+        EventPair ev{nullptr, nullptr};
+        if (tm && (rc = event_pair(&ev))) return rc;
+        HIP_TRY(hipMemsetAsync(h->raystat_d, 0, 3 * sizeof(int), s));
+        if (tm) HIP_TRY(hipEventRecord(ev.first, s));
+        hipLaunchKernelGGL(k_ray, dim3(B), dim3(NT), 0, s, L, bv, RayView{h->raykind_d, h->ray_d, h->raystat_d}, B);
+        if (tm) HIP_TRY(hipEventRecord(ev.second, s));
+        HIP_TRY(hipGetLastError());
+        int rs[3];
+        HIP_TRY(hipMemcpyAsync(rs, h->raystat_d, sizeof rs, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        for (int k = 0; k < 3; k++) h->last_ray[k] += rs[k];      // (added: the rescue's solves count with the call)
+        if (tm) {
+            float ms = 0;
+            (void)hipEventElapsedTime(&ms, ev.first, ev.second);
+            (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second);
+            fprintf(stderr, "bslv_lpq k_ray: %d LPs (%s form, %d x %d), %d FARKAS, %d DIRECTION, %d without a ray: %.3f ms\n", B, L.rev ? "revised" : "tableau", L.M, L.N, rs[0], rs[1], rs[2], ms);
+        }
     }
     // TIE PHASE (bslv_lpq_set_canonical; objective batches: bslv_lpq_set_canonical_obj): the LPs that ended OPTIMAL go on to their
     // canonical basis, in rounds of the same shape -- KP tie pivots on vectors (k_select_tie / k_select_tie_obj), one pass.  Their work
@@ -4136,7 +4246,7 @@ static int refactor_impl(bslv_lpq *h, int n, const int *slots, int *status_out, 
     for (int b = 0; b < n; b++) {
         const bool ok = cnt[(size_t)b * 4 + 2] == RFX_RUN;
         if (status_out) status_out[b] = ok ? 0 : BSLV_LP_UNDEFINED;
-        if (ok) { *ok_out += 1; *pivots_out += cnt[(size_t)b * 4 + 1]; }
+        if (ok) { *ok_out += 1; *pivots_out += cnt[(size_t)b * 4 + 1]; if (h->rays_on) HIP_TRY(hipMemsetAsync(h->raykind_d + slots[b], 0, sizeof(int), s)); }
         else { *failed_out += 1; if ((rc = bslv_lpq_reset_slot(h, slots[b]))) return rc; }      // (nothing can read a half-built inverse)
     }
     return 0;
@@ -4153,6 +4263,7 @@ static int solve_batch_rescue(bslv_lpq *h, int B, const int *src, const int *dst
         for (int k = 0; k < 4; k++) h->last_rfx[k] = 0;
         for (int k = 0; k < 4; k++) h->last_per[k] = 0;      // (solve_batch_impl adds to them: the rescue's solves count with the call)
         for (int k = 0; k < 3; k++) h->last_dvx[k] = 0;
+        for (int k = 0; k < 3; k++) h->last_ray[k] = 0;
         h->snorm_B = 0;
         h->rmark_valid = false;
         L.rfx = (h->refactor_on && L.rev) ? 1 : 0;
@@ -4535,6 +4646,83 @@ int bslv_lpq_last_canonical_obj_stats(const bslv_lpq *h, long out[4])
 {
     if (!h || !out) return BSLV_E_ARG;
     for (int k = 0; k < 4; k++) out[k] = h->last_canon_obj[k];
+    return 0;
+}
+// The ray store: see bslv_hip.h
+int bslv_lpq_set_rays(bslv_lpq *h, int on)
+{
+    if (!h) { set_error("bslv_lpq_set_rays: no engine"); return BSLV_E_ARG; }
+    if (!on) {
+        if (h->rays_on) HIP_TRY(hipStreamSynchronize(h->stream));
+        auto fr = [](void *p) { if (p) (void)hipFree(p); };
+        fr(h->raykind_d); fr(h->raystat_d); fr(h->ray_d);
+        h->raykind_d = nullptr; h->raystat_d = nullptr; h->ray_d = nullptr;
+        h->rays_on = false;
+        return 0;
+    }
+    if (h->rays_on) return 0;
+    const LpView &L = h->L;
+    if (std::max(L.M, L.N) >= RAY_IDX_MAX || KP > 15) { set_error("bslv_lpq_set_rays: %d x %d is beyond the ray record's index range", L.M, L.N); return BSLV_E_ARG; }
+    HIP_TRY(malloc0(&h->raykind_d, (size_t)h->slots * sizeof(int)));
+    HIP_TRY(malloc0(&h->raystat_d, 4 * sizeof(int)));
+    HIP_TRY(malloc0(&h->ray_d, (size_t)h->slots * (L.M + L.N) * sizeof(double)));
+    h->rays_on = true;
+    return 0;
+}
+int bslv_lpq_get_rays(const bslv_lpq *h) { return h && h->rays_on; }
+int bslv_lpq_last_ray_stats(const bslv_lpq *h, long out[3])
+{
+    if (!h || !out) return BSLV_E_ARG;
+    for (int k = 0; k < 3; k++) out[k] = h->last_ray[k];
+    return 0;
+}
+// kinds and vectors of the listed slots IN THE INDICES OF THE MODEL AS GIVEN.  Folded rows: a column entry whose needed bound (the lower
+// one for z_j > 0, the upper one for z_j < 0) came from folded row i moves there, z_i = z_j / a_ij, z_j = 0 -- the rule get_mapped and
+// k_cert_expand apply to duals, with the sign of the entry in the place of the side the column sits on; a DIRECTION has
+// delta r_i = a_ij delta x_j on folded rows.
+int bslv_lpq_get_ray(bslv_lpq *h, int B, const int *slot, int *kind, double *ray)
+{
+    if (!h || B < 0) { set_error("bslv_lpq_get_ray: bad argument"); return BSLV_E_ARG; }
+    if (!h->rays_on) { set_error("bslv_lpq_get_ray: the ray store is off (bslv_lpq_set_rays)"); return BSLV_E_STATE; }
+    if (B == 0) return 0;
+    if (!slot || !kind) { set_error("bslv_lpq_get_ray: bad argument"); return BSLV_E_ARG; }
+    for (int b = 0; b < B; b++) if (slot[b] < 0 || slot[b] >= h->slots) { set_error("bslv_lpq_get_ray: bad slot %d at %d (pool %d)", slot[b], b, h->slots); return BSLV_E_ARG; }
+    const bslv_lpq::Presolve &P = h->ps;
+    const int NE = h->L.M + h->L.N, NG = P.M0 + P.N0, Mi = h->L.M, M0 = P.M0;
+    int rc;
+    if ((rc = ensure_batch(h, B))) return rc;
+    const size_t nd = (size_t)B * NE;
+    if ((rc = ensure_out(h, nd + (size_t)(B + 1) / 2))) return rc;      // (the kinds behind the vectors)
+    int *kind_d = reinterpret_cast<int *>(h->out_d + nd);
+    hipStream_t s = h->stream;
+    HIP_TRY(hipMemcpyAsync(h->qslot_d, slot, B * sizeof(int), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_ray_get, dim3((unsigned)((nd + 255) / 256)), dim3(256), 0, s, RayView{h->raykind_d, h->ray_d, h->raystat_d}, (const int *)h->qslot_d, B, NE, kind_d, ray ? h->out_d : (double *)nullptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(kind, kind_d, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, s));
+    std::vector<double> ze;
+    double *dstp = ray;
+    if (ray && P.nfold) { ze.resize(nd); dstp = ze.data(); }
+    if (ray) HIP_TRY(hipMemcpyAsync(dstp, h->out_d, nd * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (!ray || !P.nfold) return 0;
+    for (int b = 0; b < B; b++) {
+        const double *e = &ze[(size_t)b * NE];
+        double *g = ray + (size_t)b * NG;
+        for (int i = 0; i < M0; i++) g[i] = P.row_in[i] >= 0 ? e[P.row_in[i]] : 0.0;
+        for (int j = 0; j < P.N0; j++) g[M0 + j] = e[Mi + j];
+        if (kind[b] == BSLV_LP_RAY_DIRECTION) { for (int i = 0; i < M0; i++) if (P.row_in[i] < 0) g[i] = P.fold_a[i] * e[Mi + P.fold_col[i]]; continue; }
+        if (kind[b] != BSLV_LP_RAY_FARKAS) continue;
+        for (int j = 0; j < P.N0; j++) {
+            const double zj = e[Mi + j];
+            if (!(zj != 0.0)) continue;
+            const bool at_lo = zj > 0.0;
+            const int src = at_lo ? P.lo_src[j] : P.up_src[j];
+            if (src < 0) continue;
+            const double own = at_lo ? P.lb0[M0 + j] : P.ub0[M0 + j], folded = at_lo ? P.clo[j] : P.cup[j];
+            if (own == folded) continue;      // (the column's own bound says the same: the entry stays, as a dual does)
+            g[src] = zj / P.fold_a[src]; g[M0 + j] = 0.0;
+        }
+    }
     return 0;
 }
 int bslv_lpq_last_ext_stats(const bslv_lpq *h, long out[4])

@@ -199,7 +199,7 @@ static int phase0(const Problem &pb, Sol &S, double eps_phase0, int *status, lon
     std::vector<double> ub(p, 0.0), z(d), wred(d), V((size_t)d * d, 0.0), C((size_t)d * d, 0.0);
     int st;
     if ((rc = solve0(lp, p, ub.data(), &st))) return done(rc);                                          // :689-698
-    if (st == BSLV_LP_UNBOUNDED) { *status = 2; return done(0); }
+    if (st == BSLV_LP_UNBOUNDED) { const std::vector<double> vlo(p, -INFINITY); report_ray(lp, "phase 0, first LP", st, 0, vlo.data(), ub.data(), 0, 0, nullptr); *status = 2; return done(0); }
     if (st != BSLV_LP_OPTIMAL) { set_error("phase 0: first LP has status %d (the reference asserts optimality, bslv_algs.c:697)", st); return done(BSLV_E_STATE); }
     ++*lps;
     if ((rc = bslv_lpq_get_dual(lp, 1, &zero, yrow0, d, z.data()))) return done(rc);                     // :699
@@ -346,7 +346,7 @@ static int dual_benson(const Problem &pb, const Sol &S, int hom, double eps, int
     // a primal feasible basis first (zero objective: every basis is dual feasible, the dual simplex repairs the bounds) ...
     if ((rc = bslv_lpq_reset_slot(lp, 0))) return done(rc);
     if ((rc = bslv_lpq_solve_batch(lp, 1, &zero, &zero, nullptr, nullptr, &st, &it))) return done(rc);
-    if (st == BSLV_LP_INFEASIBLE) { *status = 1; bslv_poly_destroy(poly); poly = nullptr; return done(0); }
+    if (st == BSLV_LP_INFEASIBLE) { report_ray(lp, "phase 2 (dual), feasibility LP", st, 0, nullptr, nullptr, 0, 0, nullptr); *status = 1; bslv_poly_destroy(poly); poly = nullptr; return done(0); }
     if (st != BSLV_LP_OPTIMAL) { set_error("phase 2 (dual): the feasibility LP has status %d", st); return done(BSLV_E_STATE); }
     auto count_canonical = [&]() { long cs[4]; if (cstats && bslv_lpq_last_canonical_obj_stats(lp, cs) == 0) for (int k = 0; k < 4; k++) cstats[k] += cs[k]; };
     if (canonical && !hom) {
@@ -361,7 +361,7 @@ static int dual_benson(const Problem &pb, const Sol &S, int hom, double eps, int
     for (int i = 0; i < q; i++) { for (int j = 0; j < nw0; j++) w[i] += W0[(size_t)i * nw0 + j]; w[i] /= nw0; }
     if ((rc = bslv_lpq_solve_batch_obj(lp, 1, &zero, &zero, nullptr, nullptr, M + n, q, w.data(), &st, &it))) return done(rc);
     count_canonical();
-    if (st != BSLV_LP_OPTIMAL) { *status = st == BSLV_LP_INFEASIBLE ? 1 : 2; bslv_poly_destroy(poly); poly = nullptr; return done(0); }
+    if (st != BSLV_LP_OPTIMAL) { report_ray(lp, "phase 2 (dual), first LP", st, 0, nullptr, nullptr, M + n, q, w.data()); *status = st == BSLV_LP_INFEASIBLE ? 1 : 2; bslv_poly_destroy(poly); poly = nullptr; return done(0); }
     ++*lps;
     if ((rc = bslv_lpq_get_primal(lp, 1, &zero, M + n, q, y.data()))) return done(rc);
     if (store) {                                                                     // x of the first vertex (:1431-1432)
@@ -454,7 +454,7 @@ static int dual_benson(const Problem &pb, const Sol &S, int hom, double eps, int
                 }
             }
             for (int t = 0; t < np; t++) if (stv[t] != BSLV_LP_OPTIMAL) {
-                if (stv[t] == BSLV_LP_UNBOUNDED) { *status = 2; bslv_poly_destroy(poly); poly = nullptr; return done(0); }      // :1472-1477
+                if (stv[t] == BSLV_LP_UNBOUNDED) { report_ray(lp, "phase 2 (dual), LP of a vertex", stv[t], dst[t], nullptr, nullptr, M + n, q, &W[(size_t)t * q]); *status = 2; bslv_poly_destroy(poly); poly = nullptr; return done(0); }      // :1472-1477
                 set_error("phase 2 (dual): LP status %d (the reference asserts unboundedness here, bslv_algs.c:1474)", stv[t]);
                 return done(BSLV_E_STATE);
             }

@@ -232,6 +232,64 @@ class LpEngine:
         check(self.lib.bslv_lpq_last_certify_stats(self.h, o))
         return dict(lps=int(o[0]), not_certified=int(o[1]), launches=int(o[2]))
 
+    def set_rays(self, on):
+        """the ray store: a kind and a vector per slot for LPs that come back INFEASIBLE or UNBOUNDED (bslv_lpq_set_rays,
+        include/bslv_hip.h).  Returns the library's code."""
+        self.lib.bslv_lpq_set_rays.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        return int(self.lib.bslv_lpq_set_rays(self.h, int(bool(on))))
+
+    def get_rays(self):
+        self.lib.bslv_lpq_get_rays.argtypes = [ctypes.c_void_p]
+        return int(self.lib.bslv_lpq_get_rays(self.h))
+
+    def get_ray(self, slots, vectors=True):
+        """(kind (B), ray (B, M + N) or None) of the slots, in the indices of the model as given (bslv_lpq_get_ray): kind 0 none,
+        1 a Farkas vector, 2 a recession direction"""
+        slots = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        B = len(slots)
+        kind = np.zeros(B, np.int32)
+        ray = np.zeros((B, self.M + self.N), np.float64) if vectors else None
+        self.lib.bslv_lpq_get_ray.argtypes = [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 3
+        check(self.lib.bslv_lpq_get_ray(self.h, B, slots.ctypes.data, kind.ctypes.data, ray.ctypes.data if vectors else None))
+        return kind, ray
+
+    def last_ray_stats(self):
+        """of the last solve call (bslv_lpq_last_ray_stats)"""
+        o = (ctypes.c_long * 3)()
+        self.lib.bslv_lpq_last_ray_stats.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        check(self.lib.bslv_lpq_last_ray_stats(self.h, o))
+        return dict(farkas=int(o[0]), direction=int(o[1]), none=int(o[2]))
+
+    def certify_rays(self, slots, vlo=None, vup=None, cost_first=0, costs=None, tol=None):
+        """the certificate of the stored rays, computed on the device (bslv_lpq_certify_rays, include/bslv_hip.h): a dict with res
+        (B, 4: ident / rows, open / cross, margin, its scale), at (B, 4) and verdict (B; 0 = the LP is infeasible / unbounded in the
+        model as given).  vlo / vup, cost_first / costs as for certify; tol: four values, entries <= 0 or None = the defaults."""
+        slots = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        B = len(slots)
+        keep = []
+
+        def arr(a):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, np.float64)
+            keep.append(a)
+            return a.ctypes.data
+
+        c = None if costs is None else np.ascontiguousarray(costs, np.float64).reshape(B, -1)
+        t = None if tol is None else np.ascontiguousarray(tol, np.float64).reshape(4)
+        res, at, verdict = np.zeros((B, 4), np.float64), np.full((B, 4), -1, np.int32), np.zeros(B, np.int32)
+        self.lib.bslv_lpq_certify_rays.argtypes = [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 5
+        check(self.lib.bslv_lpq_certify_rays(self.h, B, slots.ctypes.data, arr(vlo), arr(vup), int(cost_first), 0 if c is None else c.shape[1], arr(c), arr(t),
+                                             res.ctypes.data, at.ctypes.data, verdict.ctypes.data))
+        return dict(res=res, at=at, verdict=verdict)
+
+    def last_ray_certify_stats(self):
+        """of the last certify_rays call (bslv_lpq_last_ray_certify_stats)"""
+        o = (ctypes.c_long * 3)()
+        self.lib.bslv_lpq_last_ray_certify_stats.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        check(self.lib.bslv_lpq_last_ray_certify_stats(self.h, o))
+        return dict(lps=int(o[0]), not_certified=int(o[1]), launches=int(o[2]))
+
     def debug_poke(self, slot, what, var, delta):
         """tests only: add delta to the stored value (what 0) or the stored reduced cost (what 1, nonbasic only) of a variable of a
         slot (bslv_lpq_debug_poke).  Returns the library's code (0, or BSLV_E_ARG)."""

@@ -239,6 +239,64 @@ int bslv_lpq_last_certify_stats(const bslv_lpq *h, long out[3]);
  * wherever it lives), what 1 to the stored reduced cost of a NONBASIC variable (a basic one is BSLV_E_ARG).  var is an index of the
  * engine's own model: an engine with folded rows answers BSLV_E_ARG. */
 int bslv_lpq_debug_poke(bslv_lpq *h, int slot, int what, int var, double delta);
+/* RAYS: why an LP came back BSLV_LP_INFEASIBLE or BSLV_LP_UNBOUNDED.  Off unless asked for (bslv_lpq_set_rays(h, 1), or BSLV_LP_RAYS=1
+ * in the environment when an engine is created; both forms); off, nothing is allocated, no kernel is launched and no result bit differs.
+ * On, every slot has a kind and a vector of M + N doubles beside the pool (like the ages: bslv_lpq_slot_bytes is what it was),
+ * allocated by set_rays(1), released by set_rays(0) and bslv_lpq_destroy.  A solve call (solve_batch, solve_batch_obj, the in-call
+ * rescue's re-solve) sets the kind of every dst slot it was accepted for; bslv_lpq_reset_slot and a successful bslv_lpq_refactor set
+ * NONE.  The kind is NONE unless the LP's final conclusion is one of three, in which the kernel holds the proof when it concludes
+ * (x_B = T x_N, alpha = T; the concluding thread records row / column, side and where the vectors lie, the kernel k_ray builds the
+ * vector once after the rounds of the call -- no selection kernel is kept out of the plan, each holds its vector at the conclusion):
+ *   FARKAS, dual row    INFEASIBLE from the dual selection: row r, basic variable k = bh[r], has no entering candidate.  Below its
+ *                       lower bound: z_k = 1, z_nh[j] = -alpha_rj for every nonbasic position j, 0 on the other basic variables; above
+ *                       its upper bound: the negative of that.
+ *   FARKAS, phase 1     INFEASIBLE from the primal phase 1 (methods PRIMAL / REPAIR): no column lowers the sum of infeasibilities.
+ *                       z = sum_i sigma_i (e_bh[i] - sum_j alpha_ij e_nh[j]), sigma_i = +1 below the lower bound, -1 above the upper one.
+ *   DIRECTION           UNBOUNDED from a primal step (objective batches, methods PRIMAL / REPAIR): entering position q moves by dir
+ *                       = +-1 and no row blocks.  delta_nh[q] = dir, delta_bh[i] = alpha_iq dir, 0 elsewhere.
+ * The stored vector is divided by its largest absolute entry (one division per entry; the divisor is a value, so ties need no rule).
+ * A FARKAS vector z has z . (A x, x) = 0 for every x; with every entry's NEEDED bound (the lower one for z_k > 0, the upper one for
+ * z_k < 0) finite and S = sum_k z_k (needed bound) > 0 no point of the box exists.  A conclusion that leaned on one of the engine's
+ * ARTIFICIAL bounds shows as an entry whose needed bound, in the model as given, is infinite: no proof for that model.
+ * TWO CONCLUSIONS STORE NOTHING (kind NONE, counted in last_ray_stats[2]):
+ *   - UNBOUNDED on an active artificial bound (the dual method found no violated row while a nonbasic variable with a non-zero reduced
+ *     cost sits on an artificial bound).  The engine never looked for a ray there, and a single column is in general not a ray.  A
+ *     caller who needs the ray re-solves the LP under BSLV_LP_METHOD_PRIMAL.
+ *   - the empty box a folded row left (solve_batch answers INFEASIBLE without touching a slot).
+ * bslv_lpq_get_ray answers in the indices of the model AS GIVEN: kind[b] and, unless ray == NULL, ray[b * (M + N) ..] of slot[b] (zeros
+ * for NONE).  With folded rows a column entry z_j whose needed bound came from folded row i (coefficient a_ij) moves to that row:
+ * z_i = z_j / a_ij, z_j = 0 -- the rule of the duals; a DIRECTION has delta r_i = a_ij delta x_j there.
+ * BSLV_E_STATE with the switch off, BSLV_E_ARG for a slot out of range or h == NULL; B == 0 returns 0; a slot may be named twice.
+ * bslv_lpq_last_ray_stats, of the last solve call: [0] FARKAS rays stored, [1] DIRECTION rays stored, [2] INFEASIBLE / UNBOUNDED
+ * conclusions without a ray.  BSLV_LP_RAY_TIMING=1: one line per solve call on stderr with the HIP-event time of k_ray. */
+enum { BSLV_LP_RAY_NONE = 0, BSLV_LP_RAY_FARKAS = 1, BSLV_LP_RAY_DIRECTION = 2 };
+int bslv_lpq_set_rays(bslv_lpq *h, int on);
+int bslv_lpq_get_rays(const bslv_lpq *h);
+int bslv_lpq_get_ray(bslv_lpq *h, int B, const int *slot, int *kind /* B */, double *ray /* B * (M + N), may be NULL */);
+int bslv_lpq_last_ray_stats(const bslv_lpq *h, long out[3]);
+/* CERTIFICATE of the stored rays.  Read-only like bslv_lpq_certify, same meaning of vlo / vup / costs: the bounds of the model as given
+ * with the per-LP range replaced, the engine's artificial bounds play no part.  Per LP four residuals, with z / delta = what
+ * bslv_lpq_get_ray returns for the slot:
+ *   FARKAS     res[0] ident   max_j |z_{M+j} + sum_i a_ij z_i|
+ *              res[1] open    the largest |z_k| whose needed bound is infinite (at[1] = k); entries with |z_k| <= tol[2] count as zero:
+ *                             they are left out here and in the two sums
+ *              res[2] margin  S = sum_k z_k (needed bound) over the other entries
+ *              res[3]         sum_k |z_k (needed bound)|
+ *   DIRECTION  res[0] rows    max_i |delta r_i - sum_j a_ij delta x_j|
+ *              res[1] cross   max over k of -delta_k where lo_k is finite and of delta_k where up_k is finite, not below 0
+ *              res[2] margin  -c . delta, c as in bslv_lpq_certify (a cost on a row counts as c_i delta r_i)
+ *              res[3]         sum_k |c_k delta_k|
+ * verdict: bit 0 = res[0] > tol[0] (FARKAS) or > tol[1] (DIRECTION); bit 1 = res[1] > tol[2]; bit 2 = not (res[2] > tol[3] (1 + res[3]));
+ * bit 3 = the slot's kind is NONE (its res are NaN, its at -1); a residual that is not a number sets its bit (so NONE reads 15).
+ * 0 = the LP is infeasible / unbounded in the model as given.  at[b*4 + 0] / [1]: where res[0] / res[1] was met (ties: the smaller
+ * index; -1 where res[1] is 0), [2] = [3] = -1.  tol (4 doubles, or NULL; an entry <= 0: the default) = 1e-8, 1e-9, 1e-9, 1e-9: the dj,
+ * rows, dual-zero and gap numbers of bslv_lpq_certify.  Every sum is compensated, in a fixed order: same state, same bits.
+ * BSLV_E_STATE with the ray store off; BSLV_E_ARG as bslv_lpq_certify.  bslv_lpq_last_ray_certify_stats: [0] LPs examined, [1] LPs with a
+ * verdict other than 0, [2] kernel launches. */
+int bslv_lpq_certify_rays(bslv_lpq *h, int B, const int *slot, const double *vlo, const double *vup,
+                          int cost_first, int cost_cnt, const double *costs, const double *tol /* 4 or NULL */,
+                          double *res /* B * 4 */, int *at /* B * 4, may be NULL */, int *verdict /* B, may be NULL */);
+int bslv_lpq_last_ray_certify_stats(const bslv_lpq *h, long out[3]);
 /* statistics of the last solve_batch: lock-step iterations, tableau-update kernel launches,
  * and the HIP-event time (ms) spent in the tableau-update kernel */
 /* when on, every tableau-update launch is bracketed by HIP events on the engine's stream */
