@@ -2379,6 +2379,9 @@ struct bslv_poly {
     bool r2_spec = true;              // rounds are queued one ahead of the host (BSLV_R2_SPEC=0 / debug_set key 12: the host reads every round's mailbox before it queues the next)
     long r2_spec_void = 0;            // rounds that were queued ahead and found the device halted (bslv_poly_rounds2_stats)
     bool r2_mis = true;               // rounds take a MAXIMAL independent set from a conflict matrix of the chunk (round 3); BSLV_R2_MIS=0 / debug_set key 11: the local minima of one random order (round 2)
+    bool r2_ride = true;              // a round's new vertices are classified by workgroups of the launch of its prunes (k_r2_prune_classify); BSLV_R2_RIDE=0 / debug_set key 18: two launches
+    int r2_ride_gmax = 240;           // ... by at most this many workgroups (the CUs but 16 for the prunes; BSLV_R2_RIDE_G / debug_set key 19, a test hook: 1 exercises the stride)
+    int r2_ride_threads = 256;        // ... in each of which this many threads work (a power of two, 64 .. K2T; BSLV_R2_RIDE_T / debug_set key 20)
     int chunk_cuts = 1024;             // cuts classified and applied together (bslv_poly_debug_set(h, 7, n); at most 4096)
     int r2_defer = 0;                 // rounds of a chunk stop when one holds fewer cuts than this; what is left is handed BACK to the caller (rc 2) -- see bslv_poly_set_defer
     bool r2_deferred = false;         // (the last run_rounds2 stopped for that reason)
@@ -3405,6 +3408,14 @@ int bslv_poly_create(bslv_poly **out, int dim, int v2h, const double *c)
     if (getenv("BSLV_NO_ROUNDS2")) h->rounds2_enabled = false;
     if (const char *e = getenv("BSLV_R2_MIS")) h->r2_mis = atoi(e) != 0;
     if (const char *e = getenv("BSLV_R2_SPEC")) h->r2_spec = atoi(e) != 0;
+    {   // the workgroups that classify beside a round's prunes: each holds a CU's LDS, so at most the CUs less 16 that a round's prunes take
+        int dev = 0, cus = 0;
+        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0) h->r2_ride_gmax = std::max(cus / 2, cus - 16);
+        else (void)hipGetLastError();
+    }
+    if (const char *e = getenv("BSLV_R2_RIDE")) h->r2_ride = atoi(e) != 0;
+    if (const char *e = getenv("BSLV_R2_RIDE_G")) h->r2_ride_gmax = std::max(1, atoi(e));
+    if (const char *e = getenv("BSLV_R2_RIDE_T")) bslv_poly_debug_set(h, 20, atol(e));
     if (const char *e = getenv("BSLV_CHUNK_CUTS")) h->chunk_cuts = std::min(4096, std::max(32, atoi(e)));
     if (const char *e = getenv("BSLV_R2_MIN_CUTS")) h->r2_min_cuts = std::max(-1, atoi(e));
     if (const char *e = getenv("BSLV_POLY_SNAP")) h->snap = atoi(e) != 0;
@@ -3905,7 +3916,10 @@ int bslv_poly_debug_set(bslv_poly *h, int key, long value)
     case 7: h->chunk_cuts = (int)std::min(4096L, std::max(32L, value)); return 0;    /* cuts classified and applied together */
     case 10: h->shard_min = (int)std::max(2L, value); return 0;           /* multi-GPU: facets from this size on have their pair space dealt to the ranks */
     case 12: h->r2_spec = value != 0; return 0;                           /* rounds queued one ahead of the host (1) / mailbox read before every round (0) */
-    case 16: h->k2_noflags = value != 0; return 0;                        /* multi-kernel prune of large facets without a flag byte per pair (forced; by itself from 4 GiB of flags on) */
+    case 18: h->r2_ride = value != 0; return 0;                           /* rounds: the new vertices classified inside the launch of the prunes (1) / a launch of their own (0) */
+    case 19: h->r2_ride_gmax = (int)std::max(1L, std::min(4096L, value)); return 0;     /* ... by at most this many workgroups (test hook) */
+    case 20: { int t = 64; while (t < K2T && t < value) t <<= 1; h->r2_ride_threads = t; return 0; }      /* ... threads of each that work: a power of two, 64 .. 1024 */
+    case 16: h->k2_noflags = value != 0; return 0;                       /* multi-kernel prune of large facets without a flag byte per pair (forced; by itself from 4 GiB of flags on) */
     case 11: h->r2_mis = value != 0; return 0;                            /* rounds: maximal independent set from the conflict matrix (1) / local minima of one order (0) */
     case 14: h->r2_defer = (int)std::max(0L, value); return 0;           /* see bslv_poly_set_defer */
     case 8: h->r2_min_cuts = (int)std::max(-1L, value); return 0;        /* rounds go on while they average at least this many cuts (0: until every round holds one cut, -1: always) */

@@ -19,6 +19,7 @@ struct Rounds2Buf {
     // round as a bit mask, per element the class words that hold a touch
     unsigned *M = nullptr, *selw = nullptr, *wm = nullptr; int *mcnt = nullptr; int wmcap = 0;
     int *fc2 = nullptr, *fl2 = nullptr, *fc_ticket = nullptr; int fc_slices = 0, fc_stride = 0;      // K2V2: counters of prunes with long member lists
+    size_t ride_lds = 128 * 1024;     // dynamic LDS granted to k_r2_prune_classify
 };
 constexpr int R2_ADJW = (K2_MAXNM * (K2_MAXNM - 1) / 2 + 31) / 32;
 constexpr int R2_MAILS = 4;
@@ -32,6 +33,7 @@ static void rounds2_free(Rounds2Buf &V)
     if (V.gout_h) (void)hipHostFree(V.gout_h);
     V = Rounds2Buf();
 }
+static hipError_t r2_prune_classify_grant(int d, int lds);
 static int rounds2_ensure(bslv_poly *h, Rounds2Buf &V, int Bc)
 {
     hipStream_t s = h->stream;
@@ -51,6 +53,8 @@ static int rounds2_ensure(bslv_poly *h, Rounds2Buf &V, int Bc)
             (void)hipGetLastError();
             h->r2_mis = false;               // (no room for the matrix in LDS: the local-minima rule of round 2)
         }
+        // the prunes' LDS for the kernel that also classifies, as bslv_poly_create asks for k2_fused_t (refused: two launches when the prunes want more than 48 KB)
+        if (r2_prune_classify_grant(h->d, 128 * 1024) != hipSuccess) { (void)hipGetLastError(); V.ride_lds = 48 * 1024; }
     }
     if (h->P.cap > V.wmcap) { if ((rc = grow(&V.wm, (size_t)V.wmcap, (size_t)h->P.cap, s, true))) return rc; V.wmcap = h->P.cap; }
     if (Bc > V.bcap) {
@@ -90,6 +94,26 @@ static void launch_r2_classify3(int d, dim3 grid, hipStream_t s, A... a)
         CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8) CASE(9) CASE(10)
 #undef CASE
     default: hipLaunchKernelGGL(k_r2_classify3<0>, grid, dim3(PB), 0, s, a...); break;
+    }
+}
+// the kernel of a round's prunes with the classification riding along: launch / grant of its dynamic LDS, by dimension
+template <class... A>
+static void launch_r2_prune_classify(int d, dim3 grid, size_t lds, hipStream_t s, A... a)
+{
+    switch (d) {
+#define CASE(D) case D: hipLaunchKernelGGL(k_r2_prune_classify<D>, grid, dim3(K2T), lds, s, a...); break;
+        CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8) CASE(9) CASE(10)
+#undef CASE
+    default: hipLaunchKernelGGL(k_r2_prune_classify<0>, grid, dim3(K2T), lds, s, a...); break;
+    }
+}
+static hipError_t r2_prune_classify_grant(int d, int lds)
+{
+    switch (d) {
+#define CASE(D) case D: return hipFuncSetAttribute((const void *)k_r2_prune_classify<D>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8) CASE(9) CASE(10)
+#undef CASE
+    default: return hipFuncSetAttribute((const void *)k_r2_prune_classify<0>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     }
 }
 // host: one attempt to take the round state for `seq` (as mail_try_read does for a Mail)
@@ -344,15 +368,26 @@ static int run_rounds2(bslv_poly *h, RoundsBuf &R, const std::vector<int> &todo,
         const int S_ub = std::max(1, std::min(Bc - napplied - nredundant, V.scap));
         const K2V2 KV{V.st_d, R.cutof, V.mem_g, V.adj_g, V.cnt_g, V.nm_g, R2_ADJW, &V.st_d->pair_tests, V.fc2, V.fl2, V.fc_ticket, V.fc2 ? V.fc_slices : 0, V.fc_stride};
         const int seq = ++V.seq;
-        // the new vertices of the round against the cuts that are still alive: one launch whose grid strides over whatever the round made
+        // the new vertices of the round against the cuts that are still alive: workgroups that stride over whatever the round made.  Nothing
+        // reads these class words before the next round's k_r2_minit, and the prunes read none: the classification rides along in
+        // the launch of the prunes (k_r2_prune_classify) unless BSLV_R2_RIDE=0 asks for the two launches
         const int want = std::max(2048, 2 * last_ncross);
-        launch_r2_classify3(d, dim3(std::max(1, std::min(4096, (want + PB / nwp - 1) / (PB / nwp)))), s, h->P, (const double *)h->hps_d, Bc, nw, nwp, (const RState *)V.st_d,
-                            (const unsigned *)V.alive, V.hw, V.wm, (int *)nullptr, mis ? 1 : 0);
-        hipLaunchKernelGGL(k2_fused_t<true>, dim3(S_ub), dim3(K2T), h->k2_lds, s, h->P, h->members, 0, 0, 0, h->fcount, h->flocal, (int)(h->k2_lds / 8), Enew, 0,
-                           (int *)nullptr, h->totals + 2, h->k2mail_d, 0, h->k2dbg, (const CutDev *)nullptr, h->abort_d, (int *)nullptr, Hp{}, (int *)nullptr,
-                           (int *)nullptr, KV);
+        if (h->r2_ride && h->k2_lds <= V.ride_lds) {
+            // G workgroups, in each of which r2_ride_threads threads work (PB, the shape of k_r2_classify3: see the kernel), enough for `want`
+            // vertices in one pass, at most r2_ride_gmax: each holds the LDS of a CU like a prune does; the prunes are dispatched first
+            const int nthr = std::max(h->r2_ride_threads, std::min(nwp, K2T));
+            const int vpb = std::max(1, nthr / nwp), G = std::max(1, std::min(h->r2_ride_gmax, (want + vpb - 1) / vpb));
+            launch_r2_prune_classify(d, dim3(S_ub + G), h->k2_lds, s, h->P, h->members, h->fcount, h->flocal, (int)(h->k2_lds / 8), Enew, h->totals + 2, h->k2mail_d, h->k2dbg, h->abort_d,
+                                     Hp{}, KV, (const double *)h->hps_d, Bc, nw, nwp, (const unsigned *)V.alive, V.hw, V.wm, G, nthr, mis ? 1 : 0);
+        } else {
+            launch_r2_classify3(d, dim3(std::max(1, std::min(4096, (want + PB / nwp - 1) / (PB / nwp)))), s, h->P, (const double *)h->hps_d, Bc, nw, nwp, (const RState *)V.st_d,
+                                (const unsigned *)V.alive, V.hw, V.wm, (int *)nullptr, mis ? 1 : 0);
+            hipLaunchKernelGGL(k2_fused_t<true>, dim3(S_ub), dim3(K2T), h->k2_lds, s, h->P, h->members, 0, 0, 0, h->fcount, h->flocal, (int)(h->k2_lds / 8), Enew, 0,
+                               (int *)nullptr, h->totals + 2, h->k2mail_d, 0, h->k2dbg, (const CutDev *)nullptr, h->abort_d, (int *)nullptr, Hp{}, (int *)nullptr,
+                               (int *)nullptr, KV);
+        }
         hipLaunchKernelGGL(k_r2_k2emit, dim3(S_ub), dim3(K2T), 0, s, V.st_d, (const int *)V.cnt_g, (const int *)V.nm_g, (const unsigned *)V.adj_g, (const int *)V.mem_g,
-                           R2_ADJW, Enew, h->EP[1 - cur], h->ecap, V.mail_d + (seq % R2_MAILS), seq, (const unsigned long long *)V.hw, (const unsigned *)V.wm, nw, (const unsigned *)V.alive);
+                           R2_ADJW, Enew, h->EP[1 - cur], h->ecap, V.mail_d + (seq % R2_MAILS), seq);
         HIP_TRY(hipGetLastError());
         cur = 1 - cur;
         *seq_out = seq; *sub_out = S_ub;
@@ -497,8 +532,7 @@ static int run_rounds2(bslv_poly *h, RoundsBuf &R, const std::vector<int> &todo,
             if ((rc = ensure_ecap(h, m.ne_next + m.epairs + 1))) return rc;
             seq = ++V.seq;
             hipLaunchKernelGGL(k_r2_k2emit, dim3(S_ub), dim3(K2T), 0, s, V.st_d, (const int *)V.cnt_g, (const int *)V.nm_g, (const unsigned *)V.adj_g,
-                               (const int *)V.mem_g, R2_ADJW, h->E[h->ecur], h->EP[h->ecur], h->ecap, V.mail_d + (seq % R2_MAILS), seq, (const unsigned long long *)V.hw, (const unsigned *)V.wm, nw,
-                               (const unsigned *)V.alive);
+                               (const int *)V.mem_g, R2_ADJW, h->E[h->ecur], h->EP[h->ecur], h->ecap, V.mail_d + (seq % R2_MAILS), seq);
             HIP_TRY(hipGetLastError());
             if ((rc = r2_wait(h, V, seq, &m))) return rc;
             if (m.eover) { set_error("internal: the edge list is still too short after growing"); return BSLV_E_STATE; }

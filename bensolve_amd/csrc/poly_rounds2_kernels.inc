@@ -17,9 +17,11 @@
 //   k_flags2      (the single-cut kernel, unchanged) flags, list lengths, keep marks
 //   k_r2_emit     the single-cut emit pass with the halfspace and the facet rank of the OWNER of each crossing edge / on-plane
 //                 element; verdict on the capacities
-//   k_r2_classify3 the new vertices against the alive cuts of the chunk, which of their words hold a touch, their MINUS marks
-//   k2_fused_t<true> one workgroup per selected cut: the adjacency prune of its new facet, result as a bitmap
-//   k_r2_k2emit   ordered emission of the adjacent pairs of all selected cuts, commit of the sizes, mailbox to the host
+//   k_r2_prune_classify  one launch of two kinds of workgroups, which do not depend on each other:
+//                 one workgroup per selected cut: the adjacency prune of its new facet, result as a bitmap (k2_fused_body<true>);
+//                 behind them: the new vertices against the alive cuts of the chunk, which of their words hold a touch (r2_classify3_body)
+//                 (BSLV_R2_RIDE=0: as two launches, k_r2_classify3 and k2_fused_t<true>)
+//   k_r2_k2emit  ordered emission of the adjacent pairs of all selected cuts, commit of the sizes, mailbox to the host
 //
 // The classes of an element against the cuts of the chunk never change (coordinates are immutable), so the class words of
 // the chunk's batched classification serve every round; only the vertices a round creates are classified (once).
@@ -989,9 +991,10 @@ __global__ __launch_bounds__(PB) void k_r2_assign3(PolyView P, const unsigned lo
 }
 // classes of the vertices a round created against the alive cuts of the chunk + which of their words hold a touch (wm) + their
 // MINUS marks (mcnt).  A workgroup takes PB / nwp vertices at a time (nwp = nw rounded up to a power of two: the lanes of one
-// vertex are neighbours in a wave), the grid strides over all new vertices: whatever a round creates is covered by ONE launch,
-// which the adjacent pairs of the round's prunes rely on (k_r2_k2emit reads these words).
-// block / nblocks: this workgroup's number among those that classify; nthr: its threads
+// vertex are neighbours in a wave), the workgroups stride over all new vertices: whatever a round creates is covered by ONE launch.
+// The next round's k_r2_minit is the first to read these words (k_r2_k2emit reads none).
+// block / nblocks: this workgroup's number among those that classify; nthr: its threads (PB in k_r2_classify3, K2T when it rides along
+// with the prunes in k_r2_prune_classify).  No barrier in here: workgroups of another kernel call it from a role branch.
 template <int D>
 __device__ __forceinline__ void r2_classify3_body(const PolyView &P, const double *__restrict__ hps, int B, int nw, int nwp, const RState *st, const unsigned *__restrict__ alive,
                                                   unsigned long long *__restrict__ hw, unsigned *__restrict__ wm, int *mcnt, int block, int nblocks, int nthr, int packed = 1)
@@ -1041,6 +1044,32 @@ __global__ __launch_bounds__(PB) void k_r2_classify3(PolyView P, const double *_
 {
     r2_classify3_body<D>(P, hps, B, nw, nwp, st, alive, hw, wm, mcnt, (int)blockIdx.x, (int)gridDim.x, PB, packed);
 }
+// A round's prunes and the classification of its new vertices in ONE launch (BSLV_R2_RIDE, the default): the two do not depend on
+// each other -- a prune reads incidence lists, owners and the on-plane list and writes mem_g / adj_g / cnt_g / nm_g, the
+// classification writes only the class words (hw, wm) of the new vertices, which nothing reads before the next round's k_r2_minit.
+// The roles come from the DEVICE's S (the grid is sized for the S_ub the host knows, up to the whole chunk), so that the
+// classification is dispatched directly behind the real prunes:
+//   blockIdx.x < S            the prune of selected cut blockIdx.x (k2_fused_body<true>, as k2_fused_t<true> runs it)
+//   S <= blockIdx.x < S + G   workgroup blockIdx.x - S of G that classify; the body strides over the new vertices, any G >= 1 covers them
+//   the rest                  returns
+// Workgroup 0 enters the prune body whatever S is: it clears the other round's ticket there, and the body returns at once when
+// the round does not go ahead or S is 0.  r2_classify3_body has no barrier, so the (workgroup-uniform) role branch is safe.
+template <int D>
+__global__ __launch_bounds__(K2T) void k_r2_prune_classify(PolyView P, int *members, int *fcount, int *flocal, int lds_words, int2 *E, Tri *totals, Mail *mail, unsigned long long *dbg,
+                                                           int *abort_flag, Hp hn, K2V2 V, const double *__restrict__ hps, int B, int nw, int nwp, const unsigned *__restrict__ alive,
+                                                           unsigned long long *__restrict__ hw, unsigned *__restrict__ wm, int G, int nthr, int packed)
+{
+    const int S = max(V.st->S, 0), b = (int)blockIdx.x;
+    if (b >= S) {
+        // only the first nthr threads (whole waves) of a classifying workgroup work: the classification is bound by the loads of the
+        // halfspaces per CU (every lane of a wave reads another halfspace), so it wants few waves on MANY CUs, and a workgroup of this launch
+        // has a CU to itself -- with all K2T threads at work a round's new vertices sat on 57 CUs, 16 waves each, and took twice the prunes' time
+        if (b < S + G && (int)threadIdx.x < nthr) r2_classify3_body<D>(P, hps, B, nw, nwp, V.st, alive, hw, wm, (int *)nullptr, b - S, G, nthr, packed);
+        if (b > 0) return;
+    }
+    k2_fused_body<true>(P, members, 0, 0, 0, fcount, flocal, lds_words, E, 0, (int *)nullptr, totals, mail, 0, dbg, (const CutDev *)nullptr, abort_flag, (int *)nullptr, hn, (int *)nullptr,
+                        (int *)nullptr, V);
+}
 
 // The cuts still alive when a chunk hands them back (bslv_poly_set_defer) WILL be applied, with a later batch: every element that is
 // MINUS for one of them will be removed then.  It is marked as processed now, so that no batch in between spends an LP on it
@@ -1077,12 +1106,11 @@ __global__ __launch_bounds__(PB) void k_r2_words(PolyView P, const unsigned long
 // ordered emission of the adjacent pairs of every selected cut (cut by cut in selection order, pairs in lexicographic order
 // of the member positions: what a sequence of k2_fused launches appends), commit of the round, mailbox
 __global__ __launch_bounds__(K2T) void k_r2_k2emit(RState *st, const int *__restrict__ cnt_g, const int *__restrict__ nm_g, const unsigned *__restrict__ adj_g,
-                                                   const int *__restrict__ mem_g, int adjw_cap, int2 *E, int *EP, int ecap, RState *mail, int seq,
-                                                   const unsigned long long *__restrict__ hw, const unsigned *__restrict__ wm, int nw, const unsigned *__restrict__ alive_g)
+                                                   const int *__restrict__ mem_g, int adjw_cap, int2 *E, int *EP, int ecap, RState *mail, int seq)
 {
     __shared__ Tri lds[16];
     __shared__ int s_carry;
-    (void)hw; (void)wm; (void)nw; (void)alive_g;      // (the conflict matrix is rebuilt every round: nothing to add for the new edges here)
+    // (it reads no class words: the conflict matrix is rebuilt every round, there is nothing to add for the new edges here)
     const int S = st->S, s = blockIdx.x, tid = threadIdx.x;
     const int h2 = st->halt2;
     if (S <= 0 || !st->go || st->halt || (h2 != 0 && h2 != seq)) {

@@ -478,7 +478,7 @@ long bslv_poly_rounds2_torn_reads(const bslv_poly *h);
 /* test hook, same switches as the BSLV_* environment variables but at run time: key 0 dynamic LDS bytes of the one-workgroup
  * prune (64 forces the multi-kernel prune), 1 speculative launch on/off, 2 hot mode on/off, 3 CROSS_UB, 4 size of a new facet
  * from which the multi-kernel prune builds facet-major member lists (default 4096), 5 member lists on/off, 6 device-selected
- * rounds of independent cuts inside a hot chunk on/off, 7 cuts per chunk (32..4096, default 512); keys 8, 10-12, 14 and 16:
+ * rounds of independent cuts inside a hot chunk on/off, 7 cuts per chunk (32..4096, default 512); keys 8, 10-12, 14, 16 and 18-20:
  * bslv_poly_debug_set in poly_engine.hip; any other key is BSLV_E_ARG */
 /* bslv_poly_add_cuts may hand cuts BACK (rc 2: not applied, dual slot left unused) when the rounds of a chunk get thinner than
  * min_cuts cuts -- the tail of a chunk is its cliques, one cut each per pass over the polyhedron; the caller hands the same
