@@ -6,6 +6,7 @@ expected outputs, no reference text.
   poly_ref.npz   canonicalised results of the REFERENCE polyhedron engine (bslv_poly.c, unmodified,
                  via oracle/_ref/libref_poly.so) for fixed cut sequences
   poly_ref_live.npz  the same for the random-tangent sequences the oracle is also checked on live
+  poly_ref_dims.npz / .json  the same at dimensions 7 and 9 to 16 (`make_golden.py dims`), larger index sets as SHA-256 and size
   lp_highs.json  optimal objective values of P2(v) instances from scipy/HiGHS (independent solver;
                  the reference's own LP solver, GLPK, is not installed: parity unpinned by the reference)
   hybrid_*.npz   outputs of oracle/_ref/bensolve_hybrid (reference driver + reference polyhedron
@@ -258,6 +259,58 @@ def make_poly_large():
     json.dump(meta, open(os.path.join(HERE, "poly_ref_large.json"), "w"), indent=1)
 
 
+def poly_cases_dims():
+    """dimensions 7 and 9 to 16, which poly_ref.npz does not reach (generators: tests/poly_harness.py): simple vertices with lists of
+    exactly q facets, lists of 64 and of 128 (cross-polytopes), of q + 2 (truncated cube), cones given by ideal generators, and
+    polytopes whose ordinary vertices lie on more facets than the dimension"""
+    cases = {}
+    for q in (7, 9, 10, 11, 12, 16):
+        vals, k0 = ph.truncated_simplex(q, 2 * (q + 1), 5)
+        cases["truncated_simplex_q%d" % q] = (q, 0, None, False, vals, None, k0)
+    for q in (7, 8):
+        cases["cross_q%d" % q] = (q, 0, None, False, ph.sign_vectors(q), None, None)
+    cases["cube_trunc_q7"] = (7, 0, None, False, ph.truncated_cube(7), None, None)
+    for q in (7, 11, 16):
+        gens = ph.ideal_cone(q, 3)
+        cases["ideal_cone_q%d" % q] = (q, 0, None, True, gens, [1] * len(gens), None)
+    for q in (11, 16):
+        vals, k0 = ph.degenerate_simplex(q, 0)
+        cases["degenerate_simplex_q%d" % q] = (q, 0, None, False, vals, None, k0)
+    return cases
+
+
+def make_poly_dims():
+    """layout of poly_ref.npz (in_meta, in_vals, in_ideals, rc, canonical outputs); a case whose index sets would take more than
+    DIMS_SET_LIMIT pairs stores them as SHA-256 and size in poly_ref_dims.json, as poly_ref_large.json does.  The file stays below
+    the size of poly_ref.npz."""
+    out, meta = {}, {}
+    for name, case in poly_cases_dims().items():
+        rcs, can = run_case("ref", case)
+        q, v2h, c, apex, vals, ideals, init_after = case
+        out[name + "/in_vals"] = np.asarray(vals, float)
+        out[name + "/in_ideals"] = np.asarray([0] * len(vals) if ideals is None else ideals)
+        out[name + "/in_meta"] = np.array([q, v2h, int(apex), -1 if init_after is None else init_after])
+        out[name + "/rc"] = np.asarray(rcs)
+        for k in ("pi", "Y", "di"):
+            out[name + "/" + k] = can[k]
+        # (random doubles do not compress: the coordinates of the largest polytopes are left out, poly_harness.assert_matches_dims_golden
+        # recomputes them from the facets and the incidence set, which is then pinned by its digest)
+        drop_x = can["X"].size > DIMS_X_LIMIT and not can["pi"].any() and not can["di"].any()
+        if not drop_x:
+            out[name + "/X"] = can["X"]
+        if drop_x or sum(len(can[k]) for k in ("E", "I", "DE")) > DIMS_SET_LIMIT:
+            meta[name] = {k: digest_pairs(can[k]) for k in ("E", "I", "DE")}
+        else:
+            for k in ("E", "I", "DE"):
+                out[name + "/" + k] = pack(can)[k].astype(np.int32)
+        print("poly dims", name, "primal", len(can["X"]), "dual", len(can["Y"]), "rc", int(sum(rcs)), meta.get(name, "sets in full"))
+    np.savez_compressed(os.path.join(HERE, "poly_ref_dims.npz"), **out)
+    json.dump(meta, open(os.path.join(HERE, "poly_ref_dims.json"), "w"), indent=1)
+
+
+DIMS_SET_LIMIT = 20000          # pairs of the three index sets together
+DIMS_X_LIMIT = 6000            # coordinates
+
 LIVE_CASES = [(3, 500, 21), (4, 150, 22), (5, 150, 23)]
 
 
@@ -347,6 +400,9 @@ if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "snap":
         make_poly_snap()
         sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "dims":
+        make_poly_dims()
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "live":
         make_poly_live()
         sys.exit(0)
@@ -354,5 +410,6 @@ if __name__ == "__main__":
     make_poly_snap()
     make_poly_live()
     make_poly_large()
+    make_poly_dims()
     make_lp()
     make_hybrid()

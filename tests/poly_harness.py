@@ -182,6 +182,103 @@ def tangent_halfspaces(q, N, seed):
     return D / np.linalg.norm(D, axis=1, keepdims=True)
 
 
+def truncated_simplex(q, ncut, seed):
+    """a regular simplex in dimension q, then `ncut` cuts that chop its corners in rings of growing depth: few hundred to two thousand
+    vertices in a dimension where random halfspaces would make millions"""
+    A = np.eye(q + 1) - 1.0 / (q + 1)
+    U = np.linalg.svd(A)[0][:, :q]
+    N = A @ U
+    N /= np.linalg.norm(N, axis=1, keepdims=True)
+    rng = np.random.default_rng(seed)
+    cuts = []
+    for k in range(ncut):
+        c = -N[k % (q + 1)] + 0.05 * rng.normal(size=q)
+        cuts.append(c / np.linalg.norm(c) / (q * (0.5 - 0.1 * (k // (q + 1)))))
+    return np.vstack([N, np.array(cuts)]), q + 1
+
+
+def cube(q):
+    """the cube [-1, 1]^q: 2^q simple vertices"""
+    return np.vstack([np.eye(q), -np.eye(q)])
+
+
+def sign_vectors(q):
+    """all 2^q sign vectors: through cone_polar the cross-polytope, whose 2 q vertices lie on 2^(q-1) facets each"""
+    import itertools
+    return np.array(list(itertools.product([-1, 1], repeat=q)), float)
+
+
+def truncated_cube(q):
+    """the cube, then every corner cut off through the midpoints of its edges (signs / (q - 2)): q 2^(q-1) vertices on
+    q + 2 facets each, lists longer than the dimension and shorter than the engine's register lists"""
+    return np.vstack([cube(q), sign_vectors(q) / (q - 2)])
+
+
+def ideal_cone(q, seed):
+    """generators (ideal dual points, after dual0_apex: cone_vertenum's sequence) of a cone: the unit vectors and q + 4 non-negative
+    rows (a fifth of their entries zero) of which three entries in ten are perturbed by 0.2 N(0, 1), so that some generators leave
+    the orthant.  The dual cone has the apex and extreme directions on up to 9 / 18 / 27 facets at q = 7 / 11 / 16 (seed 3)."""
+    rng = np.random.default_rng(seed)
+    R = rng.random((q + 4, q)) * (rng.random((q + 4, q)) < 0.8)
+    R = R + 0.2 * rng.normal(size=R.shape) * (rng.random((q + 4, q)) < 0.3)
+    return np.vstack([np.eye(q), R])
+
+
+def degenerate_simplex(q, seed):
+    """A polytope whose ORDINARY vertices lie on more than q facets.  The centred regular simplex {y : u_i.y >= -1} has the vertices
+    x_i = q u_i, which sum to zero, so for every t with sum(t) = 0 there is exactly one v with v.x_i = t_i: v = sum_i t_i u_i / (q + 1)
+    (u_i.u_j = -1/q off the diagonal).  A cut v.y >= -1 with t_i = -1 on a set T of simplex vertices contains the whole face conv(T):
+    the vertices of T that are still there lie ON it (one facet more each), and so does every vertex that earlier cuts made inside
+    conv(T).  Each of the first q // 2 cuts has t = -2 on one vertex that is still there (the cut removes it: no cut is redundant),
+    -1 on five to seven others -- among them corners that earlier cuts removed, which puts the vertices made on their edges onto the
+    new plane -- and the rest share what makes the sum zero, unevenly (random weights), so that no other vertex comes near a plane.
+    Returns (vals, q + 1)."""
+    A = np.eye(q + 1) - 1.0 / (q + 1)
+    U = np.linalg.svd(A)[0][:, :q]
+    N = A @ U
+    N /= np.linalg.norm(N, axis=1, keepdims=True)
+    rng = np.random.default_rng(seed)
+    cuts, gone = [], []
+    for k in range(q // 2):
+        t = np.zeros(q + 1)
+        on = [int(i) for i in rng.permutation([i for i in range(q + 1) if i != k])[:5 + k % 3] if i not in gone[-2:]] + gone[-2:]
+        t[k] = -2.0
+        t[on] = -1.0
+        rest = np.array([i for i in range(q + 1) if i != k and i not in on])
+        w = 1.0 + rng.random(len(rest))
+        t[rest] = -t.sum() * w / w.sum()
+        cuts.append(t @ N / (q + 1))
+        gone.append(k)
+    # ... and a ring of ordinary corner cuts (truncated_simplex's first ring) through the degenerate region, so that a batch of the
+    # cuts after the simplex is long enough for the rounds of independent cuts
+    for k in range(q + 1):
+        c = -N[k] + 0.05 * rng.normal(size=q)
+        cuts.append(c / np.linalg.norm(c) / (q * 0.5))
+    return np.vstack([N, np.array(cuts)]), q + 1
+
+
+def upper_image_sequence(vals, c, v2h):
+    """Dual points for v2h = LOWER2UPPER / UPPER2LOWER whose halfspaces are a projective image of the cone_polar halfspaces
+    n.y >= -1 of `vals`.  y = z / (1 - a.z) turns n.y >= -1 into (n - a).z >= -1.  LOWER2UPPER maps a dual point v to
+    (v', 1 - c'.v').z >= v_d: every normal m has c.m = 1 (c_d = 1), so a = -t c with t > max(-c.n) makes all c.(n - a) positive,
+    and v = (m', -1) / c.m.  UPPER2LOWER maps v to (v' - v_d c', -1).z >= -v_d: every normal points down, a = t e_d with
+    t > max n_d, and v = (m' + c', 1) / -m_d.  The image is an unbounded polyhedron (c, or -e_d, is a direction of recession),
+    which is what these two modes are for.  Only c_1 .. c_(d-1) enter either map."""
+    n = np.asarray(vals, float)
+    q = n.shape[1]
+    cc = np.array(c, float)
+    if v2h == LOWER2UPPER:
+        cc[q - 1] = 1.0
+        m = n + (1.25 * max(0.0, (-n @ cc).max()) + 0.25) * cc / (cc @ cc)
+        lam = 1.0 / (m @ cc)
+        return np.hstack([m[:, :q - 1] * lam[:, None], -lam[:, None]])
+    assert v2h == UPPER2LOWER
+    m = n.copy()
+    m[:, q - 1] -= 1.25 * max(0.0, n[:, q - 1].max()) + 0.25
+    lam = -1.0 / m[:, q - 1]
+    return np.hstack([(m[:, :q - 1] + cc[None, :q - 1]) * lam[:, None], lam[:, None]])
+
+
 def run_sequence(P, vals, ideals=None, init_after=None):
     """feed dual vertices; poly__intl_apprx after the first `init_after` (default: all queued first
     like cone_vertenum does, bslv_algs.c:341-350)"""
@@ -271,6 +368,37 @@ def digest_pairs(pairs):
     import hashlib
     a = np.array(sorted(pairs), np.int64).reshape(-1, 2)
     return [hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest(), len(a)]
+
+
+def assert_matches_dims_golden(can, gold_npz, gold_meta, name, rtol=1e-9, atol=1e-9):
+    """canonicalised result against a case of tests/golden/poly_ref_dims.npz (the reference's results at dimensions 7 and 9 to 16).
+    Facets and flags always in full; the index sets in full, or bit-exact through SHA-256 and size where poly_ref_dims.json lists the
+    case.  The largest polytopes are stored without their vertex coordinates (the file stays below poly_ref.npz): there every vertex
+    is recomputed from the REFERENCE's data as the point on its facets, Y_f . x = -1 for the facets f the incidence set gives it (the
+    set is the reference's, by its digest; the facets are the fixture's), and compared at the same tolerance."""
+    g = lambda k: gold_npz[name + "/" + k]
+    assert can["Y"].shape == g("Y").shape and len(can["X"]) == len(g("pi")), (can["X"].shape, len(g("pi")), can["Y"].shape, g("Y").shape)
+    assert np.array_equal(can["pi"], g("pi")) and np.array_equal(can["di"], g("di"))
+    np.testing.assert_allclose(can["Y"], g("Y"), rtol=rtol, atol=atol)
+    for k in ("E", "I", "DE"):
+        if name in gold_meta:
+            assert digest_pairs(can[k]) == list(gold_meta[name][k]), "%s: index set %s differs from the reference's" % (name, k)
+        else:
+            assert can[k] == {tuple(int(x) for x in e) for e in g(k)}, "%s: index set %s differs from the reference's" % (name, k)
+    if name + "/X" in gold_npz.files:
+        np.testing.assert_allclose(can["X"], g("X"), rtol=rtol, atol=atol)
+        return
+    assert name in gold_meta and not g("pi").any() and not g("di").any()
+    Y, q = g("Y"), can["X"].shape[1]
+    lists = [[] for _ in range(len(can["X"]))]
+    for a, f in sorted(can["I"]):
+        lists[a].append(f)
+    X = np.empty_like(can["X"])
+    for a, F in enumerate(lists):
+        assert len(F) >= q
+        X[a], _, rank, _ = np.linalg.lstsq(Y[F], -np.ones(len(F)), rcond=None)
+        assert rank == q
+    np.testing.assert_allclose(can["X"], X, rtol=rtol, atol=atol)
 
 
 def assert_matches_large_golden(can, gold_npz, gold_meta, name, rtol=1e-9, atol=1e-9):

@@ -64,6 +64,90 @@ def test_oracle_matches_reference_golden_at_survey_sizes(name):
     ph.assert_matches_large_golden(can, GOLD_L, META_L, name)
 
 
+GOLD_D = np.load(os.path.join(HERE, "golden", "poly_ref_dims.npz"))
+META_D = json.load(open(os.path.join(HERE, "golden", "poly_ref_dims.json")))
+NAMES_D = sorted({k.split("/")[0] for k in GOLD_D.files})
+
+
+def test_dims_fixture_holds_the_cases_of_the_generators():
+    """the inputs stored with the fixture are what poly_harness's generators give today, so the GPU tests (which call the generators)
+    and this file (which reads the fixture) speak of the same polyhedra; and the file stays below poly_ref.npz"""
+    exp = {}
+    for q in (7, 9, 10, 11, 12, 16):
+        exp["truncated_simplex_q%d" % q] = ph.truncated_simplex(q, 2 * (q + 1), 5)
+    for q in (7, 8):
+        exp["cross_q%d" % q] = (ph.sign_vectors(q), -1)
+    exp["cube_trunc_q7"] = (ph.truncated_cube(7), -1)
+    for q in (7, 11, 16):
+        exp["ideal_cone_q%d" % q] = (ph.ideal_cone(q, 3), -1)
+    for q in (11, 16):
+        exp["degenerate_simplex_q%d" % q] = ph.degenerate_simplex(q, 0)
+    assert sorted(exp) == NAMES_D
+    for name, (vals, k0) in exp.items():
+        assert np.array_equal(GOLD_D[name + "/in_vals"], vals), name
+        assert int(GOLD_D[name + "/in_meta"][3]) == k0 and int(GOLD_D[name + "/in_meta"][0]) == vals.shape[1], name
+    size = lambda f: os.path.getsize(os.path.join(HERE, "golden", f))
+    assert size("poly_ref_dims.npz") < size("poly_ref.npz")
+
+
+@pytest.mark.parametrize("name", NAMES_D)
+def test_oracle_matches_reference_golden_at_dimensions_7_to_16(name):
+    """dimensions the other fixtures do not reach (7, 9, 10, 11, 12, 16; tests/golden/make_golden.py dims, from the unmodified
+    bslv_poly.c): the same cuts found redundant, the same canonical sets, coordinates at 1e-9.  Where oracle/_ref exists the compiled
+    reference runs live through the same comparison."""
+    q, v2h, apex, init_after = [int(x) for x in GOLD_D[name + "/in_meta"]]
+    for kind in ("oracle", "ref") if ph.ref_available() else ("oracle",):
+        P = ph.FlatPoly(kind, q, v2h)
+        if apex:
+            P.dual0_apex()
+        rcs = ph.run_sequence(P, GOLD_D[name + "/in_vals"], list(GOLD_D[name + "/in_ideals"]), None if init_after < 0 else init_after)
+        P.dual_adjacency()
+        can = ph.canonical(P.dump())
+        P.close()
+        assert list(rcs) == list(GOLD_D[name + "/rc"]), kind
+        ph.assert_matches_dims_golden(can, GOLD_D, META_D, name)
+
+
+@pytest.mark.parametrize("v2h", [ph.LOWER2UPPER, ph.UPPER2LOWER])
+@pytest.mark.parametrize("q", [7, 11, 16])
+def test_oracle_matches_compiled_reference_in_the_image_modes(q, v2h):
+    """lowerV2upperH / upperV2lowerH with a non-trivial c at d = 7, 11, 16 (the sequences of tests/test_poly_dims_gpu.py): no fixture
+    carries c, so this comparison runs where the compiled reference exists; without it the oracle's result is checked for what the
+    map promises -- every live vertex satisfies every applied halfspace of the mode and lies on those it lists"""
+    vals, k0 = ph.truncated_simplex(q, 2 * (q + 1), 5)
+    c = np.concatenate([0.5 + np.arange(q - 1) % 3 * 0.25, [1.0]])
+    V = ph.upper_image_sequence(vals, c, v2h)
+    res = {}
+    for kind in ("oracle", "ref") if ph.ref_available() else ("oracle",):
+        P = ph.FlatPoly(kind, q, v2h, c)
+        rcs = ph.run_sequence(P, V, None, k0)
+        P.dual_adjacency()
+        res[kind] = (list(rcs), P.dump())
+        P.close()
+    if "ref" in res:
+        assert res["oracle"][0] == res["ref"][0]
+        ph.assert_same(ph.canonical(res["oracle"][1]), ph.canonical(res["ref"][1]))
+    d = res["oracle"][1]
+    if v2h == ph.LOWER2UPPER:
+        H = np.hstack([V[:, :q - 1], 1.0 - V[:, :q - 1] @ c[:q - 1, None], V[:, q - 1:]])
+    else:
+        H = np.hstack([V[:, :q - 1] - V[:, q - 1:] * c[None, :q - 1], -np.ones((len(V), 1)), -V[:, q - 1:]])
+    pts = d["pu"].astype(bool) & (d["pi"] == 0)
+    dirs = d["pu"].astype(bool) & (d["pi"] == 1)
+    assert pts.sum() > 10 * q and dirs.sum() >= q
+    assert (d["X"][pts] @ H[:, :q].T - H[:, q][None, :]).min() > -1e-9 * (1 + np.abs(d["X"][pts]).max())
+    assert (d["X"][dirs] @ H[:, :q].T).min() > -1e-9
+    # a listed incidence is geometric: dual slot f >= 1 holds input f - 1 until the start re-adds the cuts it did not choose
+    Yall = d["Y"]
+    if v2h == ph.LOWER2UPPER:
+        Hall = np.hstack([Yall[:, :q - 1], 1.0 - Yall[:, :q - 1] @ c[:q - 1, None], Yall[:, q - 1:]])
+    else:
+        Hall = np.hstack([Yall[:, :q - 1] - Yall[:, q - 1:] * c[None, :q - 1], -np.ones((len(Yall), 1)), -Yall[:, q - 1:]])
+    I = d["I"][pts[d["I"][:, 0]] & (d["di"][d["I"][:, 1]] == 0)]
+    res_inc = np.einsum("ij,ij->i", d["X"][I[:, 0]], Hall[I[:, 1], :q]) - Hall[I[:, 1], q]
+    assert np.abs(res_inc).max() < 1e-9 * (1 + np.abs(d["X"][pts]).max())
+
+
 GOLD_LIVE = np.load(os.path.join(HERE, "golden", "poly_ref_live.npz"))
 
 

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import poly_harness as ph
+from poly_harness import truncated_simplex
 from bensolve_amd.poly import PolyEngine
 from test_poly_modes_gpu import hooks, R2_MODES, _r2_cases
 
@@ -86,21 +87,6 @@ def oracle_canonical(idx):
     exp = ph.canonical(O.dump())
     O.close()
     return exp
-
-
-def truncated_simplex(q, ncut, seed):
-    """a regular simplex in dimension q, then `ncut` cuts that chop its corners in rings of growing depth: few hundred to two thousand
-    vertices in a dimension where random halfspaces would make millions"""
-    A = np.eye(q + 1) - 1.0 / (q + 1)
-    U = np.linalg.svd(A)[0][:, :q]
-    N = A @ U
-    N /= np.linalg.norm(N, axis=1, keepdims=True)
-    rng = np.random.default_rng(seed)
-    cuts = []
-    for k in range(ncut):
-        c = -N[k % (q + 1)] + 0.05 * rng.normal(size=q)
-        cuts.append(c / np.linalg.norm(c) / (q * (0.5 - 0.1 * (k // (q + 1)))))
-    return np.vstack([N, np.array(cuts)]), q + 1
 
 
 CASES = _r2_cases()
