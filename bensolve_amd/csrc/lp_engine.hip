@@ -144,6 +144,11 @@ struct DvxView {
     double *snorm;          // [B][Mp1p] reference norm s_i >= 1 of every basis row (the square root of the Devex weight), 1 in the reference framework
     int *stat;              // [3] of the batch: dual selections under the weighted rule, those whose row is not the row of the largest violation, resets of a framework after the start
 };
+// Primal Devex pricing (bslv_lpq_set_primal_pricing): the same for the primal steps, an argument of the PDV kernels alone
+struct PdvView {
+    double *tnorm;          // [B][ld] reference norm t_j >= 1 of every nonbasic column POSITION j (the square root of the Devex weight), 1 in the reference framework
+    int *stat;              // [3] of the batch: primal selections under the weighted rule, those whose column is not the column of the largest score, new frameworks after the start
+};
 
 __device__ __forceinline__ double LO(const LpView &L, const BatchView &Bv, int b, int k)
 {
@@ -1058,9 +1063,11 @@ __device__ __forceinline__ bool phase1_prepare(const LpView &L, const BatchView 
 // basic variable blocks where it reaches the bound it violates and nowhere else (oracle/lp_dense.c primal_simplex).  rsig: infeas_sign
 // the leaving variable had.
 // (DVX: the instances of dual Devex pricing, which hand in the LDS of a row fetch -- see fetch_row_revised)
-template <bool P1, bool DVX = false>
+// (PDV: the instances of primal Devex pricing, bslv_lpq_set_primal_pricing -- see select_once.  They hand in their LDS as DVX does, and
+//  the entering column is the eligible one with the largest score / t_j instead of the largest score; Bland's rule takes no notice)
+template <bool P1, bool DVX = false, bool PDV = false>
 __device__ __forceinline__ bool primal_step(const LpView &L, const BatchView &Bv, const SelCtx &c, int &pf, const bool bland, double *sv, int *si,
-                                            int &r, int &q, bool &below, double &pstep, int &rsig, int *xr = nullptr, unsigned char *xdyn = nullptr)
+                                            int &r, int &q, bool &below, double &pstep, int &rsig, int *xr = nullptr, unsigned char *xdyn = nullptr, const PdvView *pv = nullptr)
 {
     const int tid = threadIdx.x, NT = (int)blockDim.x, b = c.b, M = L.M, N = L.N;
     const double *pc = c.pc;
@@ -1073,6 +1080,40 @@ __device__ __forceinline__ bool primal_step(const LpView &L, const BatchView &Bv
         if (ph1) dj = d1;
     }
     ValIdx ent{0.0, -1};
+    bool other_col = false;                  // primal Devex pricing: the weighted rule chose another column than the largest score's
+    if constexpr (PDV) {
+        // (four columns per thread with all loads issued first, as the passes of the dual selection; the column of the largest
+        //  unweighted score is found beside it, for the statistics only: bslv_lpq_last_primal_pricing_stats)
+        const double *tn = pv->tnorm + (size_t)b * L.ld;
+        ValIdx plain{0.0, -1};
+        constexpr int PU = 4;
+        for (int j0 = tid; j0 < N; j0 += PU * NT) {
+            int stv[PU]; double vv[PU], tv[PU];
+#pragma unroll
+            for (int u = 0; u < PU; u++) {
+                const int j = j0 + u * NT;
+                const bool in = j < N;
+                stv[u] = in ? c.nstat[j] : NS_S; vv[u] = in ? dj[j] : 0.0; tv[u] = in ? tn[j] : 1.0;
+            }
+#pragma unroll
+            for (int u = 0; u < PU; u++) {
+                const int j = j0 + u * NT, st = stv[u];
+                if (st == NS_S) continue;
+                const double v = vv[u];
+                double sc = 0.0;
+                if (st == NS_L) { if (v < -TOL_DJ) sc = -v; }
+                else if (st == NS_U) { if (v > TOL_DJ) sc = v; }
+                else if (fabs(v) > TOL_DJ) sc = fabs(v);
+                if (sc > 0.0) {
+                    ent = better_max(ent, ValIdx{bland ? (double)(L.M + L.N - c.nh[j]) : sc / tv[u], j});      // (t == 1: sc / t is sc bit for bit)
+                    plain = better_max(plain, ValIdx{sc, j});
+                }
+            }
+        }
+        ent = block_argmax(ent, sv, si);
+        plain = block_argmax(plain, sv, si);
+        other_col = !bland && ent.i != plain.i;
+    } else {
     for (int j = tid; j < N; j += NT) {
         const int st = c.nstat[j];
         if (st == NS_S) continue;
@@ -1084,6 +1125,7 @@ __device__ __forceinline__ bool primal_step(const LpView &L, const BatchView &Bv
         if (sc > 0.0) ent = better_max(ent, ValIdx{bland ? (double)(L.M + L.N - c.nh[j]) : sc, j});
     }
     ent = block_argmax(ent, sv, si);
+    }
     if (ent.i < 0) {
         if (P1 && ph1) {
             // nothing lowers the sum of infeasibilities: primal infeasible -- on a recomputed beta (the pass leaves nothing pending: d1 is rebuilt too)
@@ -1099,6 +1141,7 @@ __device__ __forceinline__ bool primal_step(const LpView &L, const BatchView &Bv
     }
     if (Bv.iters[b] >= L.maxit) { if (tid == 0) { Bv.status[b] = BSLV_LP_UNDEFINED; Bv.mode[b] = MODE_NONE; } return false; }
     q = ent.i;
+    if constexpr (PDV) if (tid == 0 && !bland) { atomicAdd(&pv->stat[0], 1); if (other_col) atomicAdd(&pv->stat[1], 1); }      // (a selection priced by the norms: it ends in a pivot, a bound switch or a ray)
     const int stq = c.nstat[q], kq = c.nh[q];
     const double dq = dj[q];
     const double dir = (stq == NS_U || (stq == NS_F && dq > 0.0)) ? -1.0 : 1.0;
@@ -1185,7 +1228,7 @@ __device__ __forceinline__ bool primal_step(const LpView &L, const BatchView &Bv
     below = !(lv.i & 1);                   // the leaving variable goes to its lower bound
     pstep = fabs(dq) * tstep / (1.0 + fabs(beta[M]));      // (what the step moves the objective by, relative: the ratio test's tolerance gives a degenerate step a length of 1e-9, not 0)
     if constexpr (P1) if (ph1) { pstep = fabs(dq) * tstep; if (tid == 0) atomicAdd(&Bv.xstat[6], 1); }      // (phase 1: by how much the sum of infeasibilities falls)
-    fetch_row<P1, DVX>(L, Bv, c, r, xr, xdyn);
+    fetch_row<P1, DVX || PDV>(L, Bv, c, r, xr, xdyn);
     return true;
 }
 // Bound flipping ratio test: sorted breakpoints of row r; a boxed candidate switches bound (sflag) while the row stays infeasible.  Returns the number of switches (the first of sidx)
@@ -1302,14 +1345,24 @@ struct SelShared { double sv[NT_BIG / WAVE]; int si[NT_BIG / WAVE]; PivDesc d; i
 // nothing.  Instances of their own (k_select_dvx, k_select_p1_dvx), so that the kernels of the default rule stay what they were; like P1
 // they get their LDS handed down (SelSharedDvx: also the words of the revised form's row fetch).
 struct SelSharedDvx : SelShared { int rv[3 + REV_HQ + 1]; };      // rv: request word of a helper / request number of the LP's own workgroup, slice ticket, late flag; rev_row_slice's queue and its length
-template <bool EXT, bool P1 = false, bool DVX = false>
-__device__ __forceinline__ bool select_once(const LpView &L, const BatchView &Bv, const int b, const int cap2, SelShared *xs = nullptr, const DvxView *dv = nullptr)
+// PDV: PRIMAL DEVEX PRICING (bslv_lpq_set_primal_pricing; the same framework, primal form).  Every nonbasic column position j of the LP
+// has a reference norm t_j >= 1 (PdvView::tnorm), 1 in the reference framework: the basis the solve starts from.  A primal step, of phase
+// 1 or 2, takes the eligible column with the largest score / t_j (primal_step), and a primal pivot (r, q) with the pivot row alpha_r that
+// fetch_row has just produced leaves
+//   t_j = max(t_j, |alpha_rj / alpha_rq| t_q)  (j != q),      t_q = max(t_q / |alpha_rq|, 1)   (position q now holds the leaving variable)
+// in one more pass over the row: no further entry of the tableau is read for it.  The norms do not depend on the cost, so phase 1 and
+// phase 2 share them.  A dual pivot of the LP here, a refactorisation replay on the host side, start a new framework (all t_j = 1); bound
+// switches change nothing.  Instances of their own again (k_select_pdv, k_select_p1_pdv), which take the LDS of the DVX ones; no
+// instance carries both rules.
+template <bool EXT, bool P1 = false, bool DVX = false, bool PDV = false>
+__device__ __forceinline__ bool select_once(const LpView &L, const BatchView &Bv, const int b, const int cap2, SelShared *xs = nullptr, const DvxView *dv = nullptr, const PdvView *pv = nullptr)
 {
     static_assert(EXT || !P1, "phase 1 lives in the extended selection");
-    constexpr bool XS = P1 || DVX;            // the LDS comes from the kernel
+    static_assert(!(DVX && PDV) && (EXT || !PDV), "one rule per instance; primal steps live in the extended selection");
+    constexpr bool XS = P1 || DVX || PDV;     // the LDS comes from the kernel
     double *sv; int *si; PivDesc *p_d; unsigned char *dyn;
     int *xr = nullptr;
-    if constexpr (DVX && !P1) xr = static_cast<SelSharedDvx *>(xs)->rv;      // (P1: tableau form only, no row fetch of the revised form)
+    if constexpr ((DVX || PDV) && !P1) xr = static_cast<SelSharedDvx *>(xs)->rv;      // (P1: tableau form only, no row fetch of the revised form)
     if constexpr (XS) { sv = xs->sv; si = xs->si; p_d = &xs->d; dyn = xs->dyn; }
     else {
         __shared__ double l_sv[NT_BIG / WAVE];
@@ -1356,9 +1409,12 @@ __device__ __forceinline__ bool select_once(const LpView &L, const BatchView &Bv
     int rsig = 0;                            // phase 1: which bound the leaving variable violated
     double *const snorm = DVX ? dv->snorm + (size_t)b * L.Mp1p : nullptr;      // dual Devex pricing: the reference norms of the rows
     bool other_row = false;                  // ... the weighted rule chose another row than the largest violation's
+    double *const tnorm = PDV ? pv->tnorm + (size_t)b * ld : nullptr;          // primal Devex pricing: the reference norms of the column positions
+    double tq = 1.0;                         // ... the entering position's norm as it was (read by all, barriers before the update writes it)
 
     if (primal) {
-        if (!primal_step<P1, DVX>(L, Bv, c, pf, bland, sv, si, r, q, below, pstep, rsig, xr, dyn)) return true;
+        if (!primal_step<P1, DVX, PDV>(L, Bv, c, pf, bland, sv, si, r, q, below, pstep, rsig, xr, dyn, pv)) return true;
+        if constexpr (PDV) tq = tnorm[q];
     } else {
     // ---- dual simplex step ----
     unsigned long long tk = (L.probe & 8) ? wall_clock64() : 0ull;
@@ -1395,7 +1451,7 @@ __device__ __forceinline__ bool select_once(const LpView &L, const BatchView &Bv
     r = best.i >> 1; below = best.i & 1;
     const double sgn = below ? 1.0 : -1.0;
     phase_mark(L, Bv, b, 0, tk);
-    fetch_row<P1, DVX>(L, Bv, c, r, xr, dyn);
+    fetch_row<P1, DVX || PDV>(L, Bv, c, r, xr, dyn);
     phase_mark(L, Bv, b, 1, tk);
 
     // pass 0: row scale for the relative pivot tolerance
@@ -1490,6 +1546,31 @@ __device__ __forceinline__ bool select_once(const LpView &L, const BatchView &Bv
     __syncthreads();
     const PivDesc d = s_d;
     if (d.r < 0) return true;                      // (given up: see above)
+    if constexpr (PDV) {
+        // primal Devex pricing: the norms follow a primal pivot along the pivot row (four columns per thread, loads first; a max, so
+        // the order does not matter); a dual pivot starts a new framework
+        if (primal) {
+            constexpr int PU = 4;
+            const double tnew = fmax(tq * fabs(d.p), 1.0);
+            for (int j0 = tid; j0 < N; j0 += PU * NT) {
+                double av[PU], tv[PU];
+#pragma unroll
+                for (int u = 0; u < PU; u++) {
+                    const int j = j0 + u * NT;
+                    const bool in = j < N;
+                    av[u] = in ? row[j] : 0.0; tv[u] = in ? tnorm[j] : 1.0;
+                }
+#pragma unroll
+                for (int u = 0; u < PU; u++) {
+                    const int j = j0 + u * NT;
+                    if (j < N) tnorm[j] = j == q ? tnew : fmax(tv[u], fabs(av[u] * d.p) * tq);
+                }
+            }
+        } else {
+            for (int j = tid; j < N; j += NT) tnorm[j] = 1.0;
+            if (tid == 0) atomicAdd(&pv->stat[2], 1);
+        }
+    }
     // Phase D: the entering column as it is after the pending pivots -> multipliers of all rows, beta; the reduced-cost row
     for (int i = tid; i <= M; i += NT) {
         if (i == r) {
@@ -1719,6 +1800,9 @@ __device__ __noinline__ bool select_once_p1(const LpView &L, const BatchView &Bv
 // (dual Devex pricing: the same three shapes)
 __device__ __noinline__ bool select_once_dvx_ext(const LpView &L, const BatchView &Bv, const int b, const int cap2, SelShared *xs, const DvxView *dv) { return select_once<true, false, true>(L, Bv, b, cap2, xs, dv); }
 __device__ __noinline__ bool select_once_dvx_p1(const LpView &L, const BatchView &Bv, const int b, const int cap2, SelShared *xs, const DvxView *dv) { return select_once<true, true, true>(L, Bv, b, cap2, xs, dv); }
+// (primal Devex pricing: the two extended shapes)
+__device__ __noinline__ bool select_once_pdv_ext(const LpView &L, const BatchView &Bv, const int b, const int cap2, SelShared *xs, const PdvView *pv) { return select_once<true, false, false, true>(L, Bv, b, cap2, xs, nullptr, pv); }
+__device__ __noinline__ bool select_once_pdv_p1(const LpView &L, const BatchView &Bv, const int b, const int cap2, SelShared *xs, const PdvView *pv) { return select_once<true, true, false, true>(L, Bv, b, cap2, xs, nullptr, pv); }
 // One launch selects up to nsel pivots per LP, one after the other, by the same workgroup: the KP selections between two passes
 // over the tableau depend only on the LP's own vectors (beta, the reduced-cost row, the pending pivot rows and multipliers) -- no
 // grid-wide dependency asks for a launch each (rounds 1-3 launched this kernel KP times per pass, 17 % of all GPU time in
@@ -1814,6 +1898,50 @@ __global__ void k_dvx_ones(DvxView Dv, int Mp1p, const int *list, int n, int cou
     double *s = Dv.snorm + (size_t)b * Mp1p;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < Mp1p; i += gridDim.x * blockDim.x) s[i] = 1.0;
     if (count && blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&Dv.stat[2], 1);
+}
+
+// k_select<true> and k_select_p1 under primal Devex pricing (bslv_lpq_set_primal_pricing; select_once<.., PDV>): what an objective batch
+// launches while the switch is on, in both forms and at both block sizes, the helpers of the revised form included, and what a PRIMAL /
+// REPAIR batch launches while the dual rule is the default one.  Kernels of their own, as the DVX ones and for the same reason.
+__global__ __launch_bounds__(NT_BIG) void k_select_pdv(LpView L, BatchView Bv, PdvView Pv, const int *active, int nact, int cap2, int nsel)
+{
+    __shared__ SelSharedDvx xs;
+    extern __shared__ unsigned char dyn_pdv[];
+    if ((int)blockIdx.x >= nact) return;
+    const int b = active[blockIdx.x];
+    if (blockIdx.y > 0) { rev_helper<true>(L, Bv, b, xs.rv, dyn_pdv); return; }
+    if (threadIdx.x == 0) xs.dyn = dyn_pdv;
+    __syncthreads();
+    for (int sdx = 0; sdx < nsel; sdx++) {
+        if (sdx) __syncthreads();
+        if (!select_once_pdv_ext(L, Bv, b, cap2, &xs, &Pv)) break;
+    }
+    if (L.helpers > 1) {
+        __syncthreads();
+        if (threadIdx.x == 0) __hip_atomic_store(&Bv.hmail[(size_t)b * 8], (L.launch_id << 8) | 0xFF, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+__global__ __launch_bounds__(NT_BIG) void k_select_p1_pdv(LpView L, BatchView Bv, PdvView Pv, const int *active, int nact, int cap2, int nsel)
+{
+    __shared__ SelShared xs;
+    extern __shared__ unsigned char dyn_p1_pdv[];
+    if ((int)blockIdx.x >= nact) return;
+    const int b = active[blockIdx.x];
+    if (threadIdx.x == 0) xs.dyn = dyn_p1_pdv;
+    __syncthreads();
+    for (int sdx = 0; sdx < nsel; sdx++) {
+        if (sdx) __syncthreads();
+        if (!select_once_pdv_p1(L, Bv, b, cap2, &xs, &Pv)) break;
+    }
+}
+// the reference norms of LP list[k] (nullptr: LP k) of the batch, k < n, back to 1: the start of a solve, and a refactorisation replay
+__global__ void k_pdv_ones(PdvView Pv, int ld, const int *list, int n, int count)
+{
+    if ((int)blockIdx.y >= n) return;
+    const int b = list ? list[blockIdx.y] : (int)blockIdx.y;
+    double *t = Pv.tnorm + (size_t)b * ld;
+    for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < ld; j += gridDim.x * blockDim.x) t[j] = 1.0;
+    if (count && blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&Pv.stat[2], 1);
 }
 
 // ---- TIE PHASE (bslv_lpq_set_canonical): the canonical optimal basis of a primal degenerate LP ----
@@ -2727,6 +2855,14 @@ struct bslv_lpq {
     long last_dvx[3] = {0, 0, 0};
     int snorm_B = 0;
     size_t select_dvx_lds_max[3] = {64 * 1024, 64 * 1024, 64 * 1024};      // dynamic LDS of k_select_dvx<false>, k_select_dvx<true>, k_select_p1_dvx
+    // primal Devex pricing (bslv_lpq_set_primal_pricing, BSLV_LP_PRIMAL_PRICING at create): the same for the primal steps; pdv_dst: the
+    // slots of the LPs of the last batch that ran under the rule (bslv_lpq_last_primal_pricing_norms answers by variable)
+    int ppricing = BSLV_LP_PRICING_DANTZIG;
+    double *tnorm_d = nullptr; int *pdvstat_d = nullptr; int tnorm_Bcap = 0;
+    long last_pdv[3] = {0, 0, 0};
+    int tnorm_B = 0;
+    std::vector<int> pdv_dst;
+    size_t select_pdv_lds_max[2] = {64 * 1024, 64 * 1024};      // dynamic LDS of k_select_pdv, k_select_p1_pdv
     // tie phase (bslv_lpq_set_canonical): the switch, the direction (host / device), per-LP state of a batch, the counters of the last batch
     bool canonical = false;
     std::vector<double> canon_dir;
@@ -3059,6 +3195,8 @@ static int raw_create(bslv_lpq **out, int M, int N, const double *A, const doubl
     }
     // BSLV_LP_PRICING=dantzig|devex: the rule for the leaving row of a dual step (bslv_lpq_set_pricing), in both forms
     if (const char *e = getenv("BSLV_LP_PRICING")) h->pricing = !strcmp(e, "devex") ? BSLV_LP_PRICING_DEVEX : BSLV_LP_PRICING_DANTZIG;
+    // BSLV_LP_PRIMAL_PRICING=dantzig|devex: the rule for the entering column of a primal step (bslv_lpq_set_primal_pricing), in both forms
+    if (const char *e = getenv("BSLV_LP_PRIMAL_PRICING")) h->ppricing = !strcmp(e, "devex") ? BSLV_LP_PRICING_DEVEX : BSLV_LP_PRICING_DANTZIG;
     // BSLV_LP_REFACTOR=1: the in-call rescue of bslv_lpq_set_refactor, for an engine in the revised form (the tableau form has no inverse to rebuild)
     L.rfx = 0; L.drift_b = -1; L.drift_p = -1;
     if (const char *e = getenv("BSLV_LP_REFACTOR")) { if (rev) h->refactor_on = atoi(e) != 0; }
@@ -3079,7 +3217,7 @@ void bslv_lpq_destroy(bslv_lpq *h)
     period_free(h);
     auto fr = [](void *p) { if (p) (void)hipFree(p); };
     fr(h->raykind_d); fr(h->raystat_d); fr(h->ray_d);
-    fr(h->age_d); fr(h->age0_d); fr(h->cert_d); fr(h->snorm_d); fr(h->dvxstat_d);
+    fr(h->age_d); fr(h->age0_d); fr(h->cert_d); fr(h->snorm_d); fr(h->dvxstat_d); fr(h->tnorm_d); fr(h->pdvstat_d);
     fr(h->L.T); fr(h->L.beta); fr(h->L.xN); fr(h->L.bh); fr(h->L.nh); fr(h->L.nstat); fr(h->L.pos);
     fr(h->Tstd); fr(h->lb_d); fr(h->ub_d); fr(h->art_d);
     fr(h->dbg_d); fr(h->list_d); fr(h->cptr_d); fr(h->cidx_d); fr(h->rptr_d); fr(h->ridx_d); fr(h->cval_d); fr(h->rval_d); fr(h->cost_d); fr(h->dsl_d); fr(h->trow_d); fr(h->uvec_d); fr(h->xfull_d); fr(h->hmail_d);
@@ -3455,7 +3593,18 @@ struct SelectPlan {
     int nt, per_launch; size_t lds;     // threads per workgroup; selections per launch; dynamic LDS of a k_select launch
     int cpt;                // columns per thread of k_select_cached (plain dual selection, tableau form, NT threads), 0: k_select
     bool dvx;               // dual Devex pricing (bslv_lpq_set_pricing): the DVX instance of whichever of k_select<false>, k_select<true>, k_select_p1 the rest asks for; never k_select_cached
+    bool pdv;               // primal Devex pricing (bslv_lpq_set_primal_pricing): the PDV instance of k_select<true> or k_select_p1 (see pdv_batch)
 };
+// Which batches run under primal Devex pricing: objective batches whenever the primal rule is DEVEX (their steps are primal ones and the
+// dual rule does not reach them); PRIMAL / REPAIR batches (k_select_p1: tableau form) when the dual rule is DANTZIG -- with both rules on
+// they keep the dual-Devex instance, no instance carries both; DUAL-method batches never (their clean-up steps stay as they are)
+static bool pdv_batch(const bslv_lpq *h)
+{
+    const LpView &L = h->L;
+    if (h->ppricing != BSLV_LP_PRICING_DEVEX) return false;
+    if (L.objmode) return true;
+    return h->method != BSLV_LP_METHOD_DUAL && !L.rev && h->pricing != BSLV_LP_PRICING_DEVEX;
+}
 static int plan_select(bslv_lpq *h, int B, const double *vlo, const double *vup, SelectPlan *plan)
 {
     LpView &L = h->L;
@@ -3467,11 +3616,14 @@ static int plan_select(bslv_lpq *h, int B, const double *vlo, const double *vup,
     if (getenv("BSLV_LP_EXT")) bfrt = p1 || atoi(getenv("BSLV_LP_EXT")) != 0;      // test hook: force the extended selection on / off
     const bool dvx = h->pricing == BSLV_LP_PRICING_DEVEX && !L.objmode;      // (objective batches make primal steps only: they keep the kernels they had)
     // the kernel of an extended (ext) or plain selection and the dynamic LDS it may use so far
+    const bool pdv = pdv_batch(h);
     auto sel_kernel = [&](bool ext) -> const void * {
+        if (pdv) return p1 ? (const void *)k_select_p1_pdv : (const void *)k_select_pdv;      // (both are extended selections: without one the batch is refused below)
         if (dvx) return p1 ? (const void *)k_select_p1_dvx : ext ? (const void *)k_select_dvx<true> : (const void *)k_select_dvx<false>;
         return p1 ? (const void *)k_select_p1 : ext ? (const void *)k_select<true> : (const void *)k_select<false>;
     };
     auto sel_lds_max = [&](bool ext) -> size_t & {
+        if (pdv) return h->select_pdv_lds_max[p1 ? 1 : 0];
         if (dvx) return h->select_dvx_lds_max[p1 ? 2 : ext ? 1 : 0];
         return p1 ? h->select1_lds_max : ext ? h->select_lds_max : h->select0_lds_max;
     };
@@ -3498,7 +3650,7 @@ static int plan_select(bslv_lpq *h, int B, const double *vlo, const double *vup,
         }
         if (ok) { L.rho_off = (int)off; plan->lds = want; }
     }
-    plan->ext = bfrt; plan->cap2 = bfrt ? cap2 : 0; plan->p1 = p1; plan->dvx = dvx;
+    plan->ext = bfrt; plan->cap2 = bfrt ? cap2 : 0; plan->p1 = p1; plan->dvx = dvx; plan->pdv = pdv;
     // (measured, BSLV_SELECT_NT: S-degenerate, 2011 columns, 64 LPs per step: LP phase 67.6 / 52.0 / 46.6 ms with 256 / 512 / 1024 threads;
     //  S-degenerate-q4 to termination with 256 LPs per step 12.1 -> 10.4 s; same pivots)
     plan->nt = getenv("BSLV_SELECT_NT") ? atoi(getenv("BSLV_SELECT_NT")) : (L.N >= 1536 ? NT_BIG : NT);
@@ -3520,7 +3672,12 @@ static void launch_select(bslv_lpq *h, const SelectPlan &p, const BatchView &bv,
             helpers = std::max(1, std::min(std::min(hmax, (L.ld + 2047) / 2048), 256 / std::max(1, running)));
         }
         L.helpers = helpers; L.launch_id = (++h->launch_seq) & 0x3FFFFF;
-        if (p.dvx) {
+        if (p.pdv) {
+            const PdvView pv{h->tnorm_d, h->pdvstat_d};
+            if (p.p1) hipLaunchKernelGGL(k_select_p1_pdv, dim3(running), dim3(p.nt), p.lds, s, L, bv, pv, h->active_d, running, p.cap2, p.per_launch);
+            else hipLaunchKernelGGL(k_select_pdv, dim3(running, helpers), dim3(p.nt), p.lds, s, L, bv, pv, h->active_d, running, p.cap2, p.per_launch);
+        }
+        else if (p.dvx) {
             const DvxView dv{h->snorm_d, h->dvxstat_d};
             if (p.p1) hipLaunchKernelGGL(k_select_p1_dvx, dim3(running), dim3(p.nt), p.lds, s, L, bv, dv, h->active_d, running, p.cap2, p.per_launch);
             else if (p.ext) hipLaunchKernelGGL(k_select_dvx<true>, dim3(running, helpers), dim3(p.nt), p.lds, s, L, bv, dv, h->active_d, running, p.cap2, p.per_launch);
@@ -3678,6 +3835,7 @@ static int period_refactor(bslv_lpq *h, const BatchView &bv, int n, bool at_star
     if ((rc = replay_refresh(h, rv, P.iota, n, pass))) return rc;
     hipLaunchKernelGGL(k_per_resume, dim3((n + 255) / 256), dim3(256), 0, s, bv, rv, rfx_view(h), (const int *)P.due, n, h->age0_d, P.res);
     // dual Devex pricing: the replay may have moved heads between rows, so the LPs go on in a new reference framework (at the start they are in one)
+    if (h->tnorm_B > 0 && !at_start) hipLaunchKernelGGL(k_pdv_ones, dim3((h->L.ld + 255) / 256, n), dim3(256), 0, s, PdvView{h->tnorm_d, h->pdvstat_d}, h->L.ld, (const int *)P.due, n, 1);
     if (h->snorm_B > 0 && !at_start) hipLaunchKernelGGL(k_dvx_ones, dim3((h->L.Mp1p + 255) / 256, n), dim3(256), 0, s, DvxView{h->snorm_d, h->dvxstat_d}, h->L.Mp1p, (const int *)P.due, n, 1);
     HIP_TRY(hipGetLastError());
     std::vector<int> due(n), res(n), nw(P.nwcap);
@@ -3934,8 +4092,22 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
         HIP_TRY(hipMemsetAsync(h->dvxstat_d, 0, 4 * sizeof(int), s));
     }
     h->snorm_B = dvx ? B : 0;
+    // primal Devex pricing: likewise
+    const bool pdv = pdv_batch(h);
+    if (pdv) {
+        if (h->tnorm_Bcap < h->Bcap) {
+            if (h->tnorm_d) (void)hipFree(h->tnorm_d);
+            h->tnorm_d = nullptr; h->tnorm_Bcap = 0;
+            HIP_TRY(malloc0s(&h->tnorm_d, (size_t)h->Bcap * L.ld * sizeof(double), s));
+            h->tnorm_Bcap = h->Bcap;
+        }
+        if (!h->pdvstat_d) HIP_TRY(malloc0s(&h->pdvstat_d, 4 * sizeof(int), s));
+        HIP_TRY(hipMemsetAsync(h->pdvstat_d, 0, 4 * sizeof(int), s));
+    }
+    h->tnorm_B = pdv ? B : 0;
     BatchView bv = bview(h);
     bv.cvals = h->cvals_d;
+    if (pdv) hipLaunchKernelGGL(k_pdv_ones, dim3((L.ld + 255) / 256, B), dim3(256), 0, s, PdvView{h->tnorm_d, h->pdvstat_d}, L.ld, (const int *)nullptr, B, 0);
     if (dvx) hipLaunchKernelGGL(k_dvx_ones, dim3((L.Mp1p + 255) / 256, B), dim3(256), 0, s, DvxView{h->snorm_d, h->dvxstat_d}, L.Mp1p, (const int *)nullptr, B, 0);
     const int tiles = (L.mrows + TR - 1) / TR;
     if (L.rev) hipLaunchKernelGGL(k_age_begin, dim3((B + 255) / 256), dim3(256), 0, s, bv, (const long long *)h->age_d, h->age0_d, B);      // the age of every LP's matrix: its parent's
@@ -4173,6 +4345,7 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
     }
     { int xs[8]; HIP_TRY(hipMemcpy(xs, h->xstat_d, sizeof xs, hipMemcpyDeviceToHost)); for (int k = 0; k < 5; k++) h->last_ext[k] = xs[k]; for (int k = 0; k < 3; k++) h->last_p1[k] = xs[5 + k]; }
     if (dvx) { int ds[3]; HIP_TRY(hipMemcpy(ds, h->dvxstat_d, sizeof ds, hipMemcpyDeviceToHost)); for (int k = 0; k < 3; k++) h->last_dvx[k] += ds[k]; }      // (added: the rescue's solves count with the call)
+    if (pdv) { int ds[3]; HIP_TRY(hipMemcpy(ds, h->pdvstat_d, sizeof ds, hipMemcpyDeviceToHost)); for (int k = 0; k < 3; k++) h->last_pdv[k] += ds[k]; h->pdv_dst.assign(dst, dst + B); }
     if (h->profile) {
         double ms = 0;
         for (size_t e = 0; e < nev; e++) { float t = 0; (void)hipEventElapsedTime(&t, h->evpool[e].first, h->evpool[e].second); ms += t; }
@@ -4263,8 +4436,9 @@ static int solve_batch_rescue(bslv_lpq *h, int B, const int *src, const int *dst
         for (int k = 0; k < 4; k++) h->last_rfx[k] = 0;
         for (int k = 0; k < 4; k++) h->last_per[k] = 0;      // (solve_batch_impl adds to them: the rescue's solves count with the call)
         for (int k = 0; k < 3; k++) h->last_dvx[k] = 0;
+        for (int k = 0; k < 3; k++) h->last_pdv[k] = 0;
         for (int k = 0; k < 3; k++) h->last_ray[k] = 0;
-        h->snorm_B = 0;
+        h->snorm_B = 0; h->tnorm_B = 0;
         h->rmark_valid = false;
         L.rfx = (h->refactor_on && L.rev) ? 1 : 0;
         L.drift_b = -1; L.drift_p = -1;
@@ -4291,6 +4465,11 @@ static int solve_batch_rescue(bslv_lpq *h, int B, const int *src, const int *dst
     std::vector<double> sn;
     const int snB = h->snorm_B;
     if (snB > 0) { sn.resize((size_t)snB * L.Mp1p); HIP_TRY(hipMemcpy(sn.data(), h->snorm_d, sn.size() * sizeof(double), hipMemcpyDeviceToHost)); }
+    // primal Devex pricing: likewise (the re-solve runs in the LP's own slot, so the slots of the batch stand)
+    std::vector<double> tn;
+    const int tnB = h->tnorm_B;
+    const std::vector<int> tn_dst = h->pdv_dst;
+    if (tnB > 0) { tn.resize((size_t)tnB * L.ld); HIP_TRY(hipMemcpy(tn.data(), h->tnorm_d, tn.size() * sizeof(double), hipMemcpyDeviceToHost)); }
     for (int attempt = 0; attempt < RESCUE_MAX && !todo.empty(); attempt++) {
         const auto t0 = std::chrono::steady_clock::now();
         const int n = (int)todo.size();
@@ -4316,6 +4495,7 @@ static int solve_batch_rescue(bslv_lpq *h, int B, const int *src, const int *dst
         for (int k = 0; k < 5; k++) ext[k] += h->last_ext[k];
         for (int k = 0; k < 3; k++) p1[k] += h->last_p1[k];
         if (snB > 0 && h->snorm_B == m) for (int k = 0; k < m; k++) HIP_TRY(hipMemcpy(&sn[(size_t)lps[k] * L.Mp1p], h->snorm_d + (size_t)k * L.Mp1p, (size_t)L.Mp1p * sizeof(double), hipMemcpyDeviceToHost));
+        if (tnB > 0 && h->tnorm_B == m) for (int k = 0; k < m; k++) HIP_TRY(hipMemcpy(&tn[(size_t)lps[k] * L.ld], h->tnorm_d + (size_t)k * L.ld, (size_t)L.ld * sizeof(double), hipMemcpyDeviceToHost));
         for (int k = 0; k < m; k++) {
             const int b = lps[k];
             if (iters) iters[b] += it2[k];
@@ -4329,6 +4509,7 @@ static int solve_batch_rescue(bslv_lpq *h, int B, const int *src, const int *dst
     for (int k = 0; k < 5; k++) h->last_ext[k] = ext[k];
     for (int k = 0; k < 3; k++) h->last_p1[k] = p1[k];
     if (snB > 0) { HIP_TRY(hipMemcpy(h->snorm_d, sn.data(), sn.size() * sizeof(double), hipMemcpyHostToDevice)); h->snorm_B = snB; }
+    if (tnB > 0) { HIP_TRY(hipMemcpy(h->tnorm_d, tn.data(), tn.size() * sizeof(double), hipMemcpyHostToDevice)); h->tnorm_B = tnB; h->pdv_dst = tn_dst; }
     return 0;
 }
 int bslv_lpq_refactor(bslv_lpq *h, int n, const int *slots, int *status_out)
@@ -4594,6 +4775,35 @@ int bslv_lpq_last_pricing_norms(bslv_lpq *h, int b, double *s)
     if (b < 0 || b >= h->snorm_B) { set_error("bslv_lpq_last_pricing_norms: LP %d of a batch of %d", b, h->snorm_B); return BSLV_E_ARG; }
     HIP_TRY(hipStreamSynchronize(h->stream));
     HIP_TRY(hipMemcpy(s, h->snorm_d + (size_t)b * h->L.Mp1p, (size_t)h->L.M * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+// The pricing rule of the primal steps (select_once<.., PDV>): see bslv_hip.h
+int bslv_lpq_set_primal_pricing(bslv_lpq *h, int rule)
+{
+    if (!h || (rule != BSLV_LP_PRICING_DANTZIG && rule != BSLV_LP_PRICING_DEVEX)) { set_error("bslv_lpq_set_primal_pricing: bad argument (rule %d)", rule); return BSLV_E_ARG; }
+    h->ppricing = rule;
+    return 0;
+}
+int bslv_lpq_get_primal_pricing(const bslv_lpq *h) { return h ? h->ppricing : BSLV_LP_PRICING_DANTZIG; }
+int bslv_lpq_last_primal_pricing_stats(const bslv_lpq *h, long out[3])
+{
+    if (!h || !out) return BSLV_E_ARG;
+    for (int k = 0; k < 3; k++) out[k] = h->last_pdv[k];
+    return 0;
+}
+int bslv_lpq_last_primal_pricing_norms(bslv_lpq *h, int b, double *t)
+{
+    if (!h || !t) { set_error("bslv_lpq_last_primal_pricing_norms: bad argument"); return BSLV_E_ARG; }
+    if (h->tnorm_B <= 0 || !h->tnorm_d || (int)h->pdv_dst.size() != h->tnorm_B) { set_error("bslv_lpq_last_primal_pricing_norms: the last solve call did not run under primal Devex pricing"); return BSLV_E_STATE; }
+    if (b < 0 || b >= h->tnorm_B) { set_error("bslv_lpq_last_primal_pricing_norms: LP %d of a batch of %d", b, h->tnorm_B); return BSLV_E_ARG; }
+    const LpView &L = h->L;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    // by position -> by variable: the heads of the LP's slot name the variable at every nonbasic position
+    std::vector<double> tp(L.N); std::vector<int> nh(L.N);
+    HIP_TRY(hipMemcpy(tp.data(), h->tnorm_d + (size_t)b * L.ld, (size_t)L.N * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(nh.data(), L.nh + (size_t)h->pdv_dst[b] * L.N, (size_t)L.N * sizeof(int), hipMemcpyDeviceToHost));
+    for (int k = 0; k < L.M + L.N; k++) t[k] = 0.0;
+    for (int j = 0; j < L.N; j++) if (nh[j] >= 0 && nh[j] < L.M + L.N) t[nh[j]] = tp[j];
     return 0;
 }
 // The canonical optimal basis (tie phase) for every later solve_batch: see bslv_hip.h; the cut of a vertex is built from these duals (bslv_algs.c:1050)

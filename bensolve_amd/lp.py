@@ -338,6 +338,33 @@ class LpEngine:
         check(self.lib.bslv_lpq_last_pricing_norms(self.h, int(b), s.ctypes.data))
         return s
 
+    def set_primal_pricing(self, rule):
+        """the pricing rule of the primal steps (objective batches; PRIMAL / REPAIR batches while the dual rule is the default):
+        0 largest reduced-cost violation (default), 1 primal Devex (bslv_lpq_set_primal_pricing, include/bslv_hip.h).  Returns the
+        library's code (0, or BSLV_E_ARG for an unknown rule)."""
+        self.lib.bslv_lpq_set_primal_pricing.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        return int(self.lib.bslv_lpq_set_primal_pricing(self.h, int(rule)))
+
+    def get_primal_pricing(self):
+        self.lib.bslv_lpq_get_primal_pricing.argtypes = [ctypes.c_void_p]
+        return int(self.lib.bslv_lpq_get_primal_pricing(self.h))
+
+    def last_primal_pricing_stats(self):
+        """primal Devex pricing of the last solve call (bslv_lpq_last_primal_pricing_stats)"""
+        o = (ctypes.c_long * 3)()
+        self.lib.bslv_lpq_last_primal_pricing_stats.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        check(self.lib.bslv_lpq_last_primal_pricing_stats(self.h, o))
+        return dict(weighted=int(o[0]), other_col=int(o[1]), resets=int(o[2]))
+
+    def last_primal_pricing_norms(self, b):
+        """tests: the primal Devex reference norms of LP b of the last batch by variable of the engine's own model, rows (less the
+        folded ones) then columns; 0 for a basic variable (bslv_lpq_last_primal_pricing_norms; raises on BSLV_E_STATE when the
+        last solve call ran no weighted instance)"""
+        t = np.empty(self.M - self.rows_folded() + self.N, np.float64)
+        self.lib.bslv_lpq_last_primal_pricing_norms.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+        check(self.lib.bslv_lpq_last_primal_pricing_norms(self.h, int(b), t.ctypes.data))
+        return t
+
     def set_canonical(self, on, dir=None):
         """canonical optimal duals for every later solve_batch: the basis that stays optimal when the per-LP bounds move by
         t * dir (var_cnt values) for small t > 0, found by a tie phase after optimality (bslv_lpq_set_canonical, include/bslv_hip.h).

@@ -374,6 +374,46 @@ int  bslv_lpq_set_pricing(bslv_lpq *h, int rule);
 int  bslv_lpq_get_pricing(const bslv_lpq *h);
 int  bslv_lpq_last_pricing_stats(const bslv_lpq *h, long out[3]);
 int  bslv_lpq_last_pricing_norms(bslv_lpq *h, int b, double *s);
+/* THE PRICING RULE of the PRIMAL simplex steps, the counterpart of the above: which eligible nonbasic column enters.  Primal steps are
+ * the whole solve of an objective batch (solve_batch_obj: the P1(w) LPs of the dual Benson variant) and phase 1 with the primal phase 2
+ * behind it of a batch under BSLV_LP_METHOD_PRIMAL / _REPAIR.  (The reference: GLPK's projected steepest edge, as above.)
+ *   DANTZIG  the default, and the engine as it was: the column with the largest reduced-cost violation |d_j| beyond TOL_DJ.
+ *   DEVEX    primal Devex pricing: every nonbasic column POSITION j of an LP has a reference norm t_j >= 1, all 1 in the reference
+ *            framework -- the basis the solve starts from (solve_batch_obj, solve_batch under PRIMAL / REPAIR, the in-call rescue's
+ *            re-solve, the re-start after a periodic refactorisation); among the columns eligible under DANTZIG the one with the largest
+ *            |d_j| / t_j enters, ties as under DANTZIG.  Phase 1 weights its own pricing vector by the same norms, and nothing is reset
+ *            when it ends: the norms do not depend on the cost.  A primal pivot (r, q) with the pivot row alpha_r leaves
+ *            t_j = max(t_j, |alpha_rj / alpha_rq| t_q) (j != q) and, for position q, which now holds the leaving variable,
+ *            t_q = max(t_q / |alpha_rq|, 1): one more pass over the pivot row the selection has fetched anyway, no further tableau entry
+ *            is read.  A bound switch of the entering variable changes nothing; a dual simplex pivot of the LP and a refactorisation
+ *            replay start a new framework (all t_j = 1).  Bland's rule, whenever it holds, ignores the norms.  The norms belong to the
+ *            LP of the batch, not to its slot: children do not inherit them.
+ * With all t_j = 1 the rule IS the default one, bit for bit: the first primal selection of every solve, and every LP of at most one
+ * primal selection, are the same.  Otherwise: same statuses and optimal values, other pivots, possibly another optimal basis.
+ * WHICH BATCHES run under the rule (kernel instances of their own: k_select_pdv in both forms, k_select_p1_pdv):
+ *   - objective batches whenever the primal rule is DEVEX, whatever the dual rule is;
+ *   - PRIMAL / REPAIR batches when the primal rule is DEVEX and the dual rule (bslv_lpq_set_pricing) is DANTZIG.  With BOTH rules on
+ *     such a batch keeps the dual-Devex instance: its primal steps are priced as before and the counters below read 0 -- no instance
+ *     carries both rules;
+ *   - DUAL-method batches never: their primal clean-up steps stay as they are.
+ * The tie phases of the canonical switches and the replay's own selection never read or write the norms.  With the switch off nothing
+ * is allocated, nothing launched and no bit differs.  Any other rule is BSLV_E_ARG; both forms accept the call.
+ * BSLV_LP_PRIMAL_PRICING=dantzig|devex sets the rule an engine is created with (so the Benson and VLP drivers and bensolve_hip get it
+ * without an option of their own).
+ * In the REVISED form use it with bslv_lpq_set_refactor_period (or bslv_lpq_set_refactor): on long solves (ex09's P1(w): thousands of
+ * pivots) the basis inverse drifts further along Devex's columns than along the default rule's, and without a refactorisation LPs came
+ * back UNDEFINED, one UNBOUNDED, that are OPTIMAL under both rules with a period of 200 (profiles/lp_primal_pricing_pivots.txt).
+ * bslv_lpq_last_primal_pricing_stats, of the last solve call: [0] primal selections priced under the weighted rule (phase 1 and 2,
+ * pivots and bound switches; not those under Bland's rule), [1] of those, selections whose column is not the column of the largest
+ * unweighted score, [2] new reference frameworks after the start (one per dual pivot of an LP, one per LP and refactorisation replay
+ * during the rounds).  All 0 with the switch off.
+ * bslv_lpq_last_primal_pricing_norms (for tests): the norms of LP b of the last batch BY VARIABLE of the engine's own model, M + N values,
+ * rows first (the given rows less bslv_lpq_rows_folded), then columns: t for a nonbasic variable, 0 for a basic one.  BSLV_E_STATE if
+ * the last solve call ran no weighted instance, BSLV_E_ARG for b outside the batch. */
+int  bslv_lpq_set_primal_pricing(bslv_lpq *h, int rule);
+int  bslv_lpq_get_primal_pricing(const bslv_lpq *h);
+int  bslv_lpq_last_primal_pricing_stats(const bslv_lpq *h, long out[3]);
+int  bslv_lpq_last_primal_pricing_norms(bslv_lpq *h, int b, double *t /* M + N */);
 /* CANONICAL OPTIMAL DUALS.  Benson's cut is built from the dual solution of P2(v) (w = lp_dual_solution_rows, bslv_algs.c:1050).  Where
  * the optimum is primal degenerate -- y = v + z c on an edge or a vertex of the image -- every w of the normal cone at y is optimal and
  * the basis the pivoting ended in names one of them, which need not be a facet normal.  With on != 0 every later solve_batch ends in the
