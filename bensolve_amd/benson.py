@@ -183,6 +183,21 @@ class BensonEngine:
         return dict(lps=int(counts[0]), not_certified=int(counts[1]), calls=int(counts[2]),
                     worst=dict(zip(("rows", "feas", "dj", "side", "gap"), [float(v) for v in worst])))
 
+    def set_compact(self, dead_fraction, min_slots=-1):
+        """apply() ends with a compaction of the polyhedron when it holds at least min_slots slots (-1: 65536) and the share
+        dead_fraction of them is dead (bslv_benson_set_compact, include/bslv_hip.h); 0 = off, the default"""
+        self.lib.bslv_benson_set_compact.argtypes = [ctypes.c_void_p, ctypes.c_double, ctypes.c_long]
+        check(self.lib.bslv_benson_set_compact(self.h, float(dead_fraction), int(min_slots)))
+
+    def compact_stats(self):
+        """compactions, slots removed, pool words removed, microseconds -- all summed (bslv_benson_compact_stats)"""
+        out = (ctypes.c_long * 4)()
+        self.lib.bslv_benson_compact_stats.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        check(self.lib.bslv_benson_compact_stats(self.h, out))
+        res = dict(zip(("compactions", "slots_removed", "pool_removed", "us"), [int(v) for v in out]))
+        res["out"] = [int(v) for v in out]
+        return res
+
     def set_pipelined(self, on):
         check(self.lib.bslv_benson_set_pipelined(self.h, int(on)))
 

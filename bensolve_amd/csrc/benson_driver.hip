@@ -84,6 +84,7 @@ struct bslv_benson {
         std::vector<int> b_idx, b_parent, b_owner, b_front;    // whole batch (all ranks)
         std::vector<double> b_val;
         std::vector<int> l_pos, l_slot;               // local shard: position in batch, dst slot
+        bool pending = false;                         // collected and not yet applied: its b_idx are in flight (solve_local, the records)
     } ctx[2];
     std::mutex slot_mu;                               // tableau-slot bookkeeping is shared by solve_local and apply
     int mark_at_collect = 0;                          // pipelined mode: batch members get the sltn mark when collected
@@ -113,6 +114,11 @@ struct bslv_benson {
     bool certify_used = false, certify_printed = false;
     long cert_counts[3] = {0, 0, 0};                  // LPs certified, LPs with a verdict other than 0, calls
     double cert_worst[5] = {0, 0, 0, 0, 0};           // the largest residual of each kind so far
+    // bslv_benson_set_compact / BSLV_POLY_COMPACT=f[:min]: apply() ends with bslv_poly_compact when the polyhedron holds at least
+    // compact_min slots and the share compact_f of them is dead.  Off by default (0): one flag test per apply().
+    double compact_f = 0.0;
+    long compact_min = 65536;
+    long compact_tot[4] = {0, 0, 0, 0};               // compactions, slots removed, pool words removed, microseconds
 };
 
 static int rec_len(const bslv_benson *h) { return h->q + 5; }
@@ -252,6 +258,10 @@ int bslv_benson_create_ex(bslv_benson **out, int m, int n, int q, const double *
         }
     }
     if (const char *e = getenv("BSLV_LP_PARK")) h->park = atoi(e) != 0;      // (the LP engine reads it too)
+    if (const char *e = getenv("BSLV_POLY_COMPACT")) {      // "f[:min]" (bslv_benson_set_compact); homogeneous engines too: nothing about it depends on the cut formula
+        double f = 0.0; long mn = -1;
+        if (sscanf(e, "%lf:%ld", &f, &mn) >= 1) (void)bslv_benson_set_compact(h, f, mn);      // (a value it refuses leaves the switch off, like the other variables)
+    }
     for (int s = pool_slots - 1; s >= 1; s--) h->free_slots.push_back(s);
     h->slot_src.assign((size_t)pool_slots * q, 0.0);
     h->slot_valid.assign(pool_slots, 0);
@@ -290,6 +300,21 @@ int bslv_benson_set_certify(bslv_benson *h, int on)
     return 0;
 }
 int bslv_benson_get_certify(const bslv_benson *h) { return h && h->certify; }
+// The compaction trigger of apply(): see bslv_hip.h and maybe_compact.
+int bslv_benson_set_compact(bslv_benson *h, double dead_fraction, long min_slots)
+{
+    if (!h) { set_error("bslv_benson_set_compact: bad argument"); return BSLV_E_ARG; }
+    if (!(dead_fraction >= 0.0 && dead_fraction <= 1.0)) { set_error("bslv_benson_set_compact: the dead fraction must lie in [0, 1] (0 = off)"); return BSLV_E_ARG; }
+    h->compact_f = dead_fraction;
+    h->compact_min = min_slots < 0 ? 65536 : min_slots;
+    return 0;
+}
+int bslv_benson_compact_stats(const bslv_benson *h, long out[4])
+{
+    if (!h || !out) return BSLV_E_ARG;
+    for (int k = 0; k < 4; k++) out[k] = h->compact_tot[k];
+    return 0;
+}
 int bslv_benson_certify_stats(const bslv_benson *h, long counts[3], double worst[5])
 {
     if (!h) return BSLV_E_ARG;
@@ -653,6 +678,7 @@ static int deal_batch(bslv_benson *h, bslv_benson::BatchCtx &B, int rank, int wo
     }
     B.l_pos.clear();
     for (int k = 0; k < nb; k++) if (B.b_owner[k] == rank) B.l_pos.push_back(k);
+    B.pending = nb > 0;
     *n_local = (int)B.l_pos.size();
     *n_total = nb;
     return 0;
@@ -886,6 +912,36 @@ int bslv_benson_solve_local_ctx(bslv_benson *h, int ctx, double *records, int *p
     return 0;
 }
 
+// The opt-in compaction at the end of apply() (bslv_benson_set_compact).  The decision reads replicated state only -- the slots and the
+// live count of the polyhedron, which every rank holds alike -- so every rank compacts after the same apply and the element ids in
+// the records that travel between ranks stay comparable.  Skipped while the OTHER batch context holds a collected batch that is not
+// applied yet (pipelined mode): its b_idx are in use by solve_local on another thread and come back in its records.
+// What the driver holds by primal element is primg_p (option -s); everything else is keyed by facet or tableau slot, which do not move.
+static int maybe_compact(bslv_benson *h, int ctx)
+{
+    if (h->ctx[1 - ctx].pending) return 0;
+    const long slots = bslv_poly_nprimal(h->poly);
+    if (slots < h->compact_min || slots <= 0) return 0;
+    long g[6];
+    int rc;
+    if ((rc = bslv_poly_garbage(h->poly, g))) return rc;          // (the one counting launch of an apply with the switch on)
+    if ((double)(g[0] - g[1]) < h->compact_f * (double)g[0] || g[0] == g[1]) return 0;
+    std::vector<int> map((size_t)g[0]);
+    if ((rc = bslv_poly_compact(h->poly, map.data(), g))) return rc;
+    long st[8];
+    if ((rc = bslv_poly_last_compact_stats(h->poly, st))) return rc;
+    h->compact_tot[0]++; h->compact_tot[1] += st[1]; h->compact_tot[2] += st[2]; h->compact_tot[3] += st[6];
+    if (!h->primg_p.empty()) {
+        std::unordered_map<int, std::vector<double>> moved;
+        for (auto &kv : h->primg_p)
+            if (kv.first >= 0 && kv.first < (int)map.size() && map[kv.first] >= 0) moved[map[kv.first]] = std::move(kv.second);      // (the pre-image of a cut-off vertex goes with it)
+        h->primg_p.swap(moved);
+    }
+    for (int c = 0; c < 2; c++)               // (both contexts are applied: their ids are history, kept consistent all the same)
+        for (int &v : h->ctx[c].b_idx) v = (v >= 0 && v < (int)map.size()) ? map[v] : -1;
+    return 0;
+}
+
 // Apply ALL ranks' records (any order in; applied in ascending source slot).  stats (may be NULL):
 // [0] LPs, [1] cuts applied, [2] redundant cuts, [3] confirmed vertices, [4] LP failures
 int bslv_benson_apply_ctx(bslv_benson *h, int ctx, int nrec, const double *records, long *stats);
@@ -1032,6 +1088,8 @@ int bslv_benson_apply_ctx(bslv_benson *h, int ctx, int nrec, const double *recor
     h->tot_cuts += applied;
     if (stats) { stats[0] = nrec; stats[1] = applied; stats[2] = ncut - applied - handed_back + nduplicate; stats[3] = (long)confirmed.size(); stats[4] = nfail; }
     h->applies++;
+    B.pending = false;
+    if (h->compact_f > 0.0 && (rc = maybe_compact(h, ctx))) return rc;
     if (h->poly_check) {
         const auto t0 = std::chrono::steady_clock::now();
         long ck[12];

@@ -2479,6 +2479,9 @@ struct bslv_poly {
     int *r2f_d = nullptr; int r2fcap = 0, r2f_n = 0;   // dual slot of every facet rank (device copy of facet_of_rank, extended on demand)
     int *fhist_d = nullptr; int fhistcap = 0;           // unprocessed elements per parent facet + 4 ints of threshold
     unsigned char *chosen_d = nullptr; size_t chosencap = 0;   // bslv_poly_children_of: one byte per dual slot from the oldest chosen one on
+    unsigned long long *cmp_d = nullptr;                 // counters of bslv_poly_garbage / bslv_poly_compact (poly_compact.inc), allocated by their first call
+    long cmp_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};        // bslv_poly_last_compact_stats
+    bool cmp_keep_cap = false;                           // debug_set key 21 (test hook): a compaction keeps the capacities it finds
 };
 
 static void v2h_map(const bslv_poly *h, const double *v, int is_dir, double *hp)
@@ -3463,7 +3466,7 @@ void bslv_poly_destroy(bslv_poly *h)
     for (int k = 0; k < 2; k++) { fr(h->hotbuf.E[k]); fr(h->hotbuf.EP[k]); }
     fr(h->snapped_d);
     fr(h->hotbuf.eflag); fr(h->alive); fr(h->hv_d); fr(h->ecount); fr(h->lslot_d); fr(h->lbits_d); fr(h->lnslots_d);
-    fr(h->shard_e); fr(h->blks); fr(h->pflag); fr(h->fstamp); fr(h->flocal); fr(h->nlocal); fr(h->bits); fr(h->hps_d); fr(h->clsw); fr(h->live_d); fr(h->anyminus); fr(h->idx_d); fr(h->val_d); fr(h->fl_d); fr(h->par_d); fr(h->r2f_d); fr(h->fhist_d); fr(h->chosen_d);
+    fr(h->shard_e); fr(h->blks); fr(h->pflag); fr(h->fstamp); fr(h->flocal); fr(h->nlocal); fr(h->bits); fr(h->hps_d); fr(h->clsw); fr(h->live_d); fr(h->anyminus); fr(h->idx_d); fr(h->val_d); fr(h->fl_d); fr(h->par_d); fr(h->r2f_d); fr(h->fhist_d); fr(h->chosen_d); fr(h->cmp_d);
     if (h->rounds) { rounds_free(*h->rounds); delete h->rounds; }
     if (h->rounds2) { rounds2_free(*h->rounds2); delete h->rounds2; }
     if (h->totals_h) (void)hipHostFree(h->totals_h);
@@ -3923,7 +3926,8 @@ int bslv_poly_debug_set(bslv_poly *h, int key, long value)
     case 11: h->r2_mis = value != 0; return 0;                            /* rounds: maximal independent set from the conflict matrix (1) / local minima of one order (0) */
     case 14: h->r2_defer = (int)std::max(0L, value); return 0;           /* see bslv_poly_set_defer */
     case 8: h->r2_min_cuts = (int)std::max(-1L, value); return 0;        /* rounds go on while they average at least this many cuts (0: until every round holds one cut, -1: always) */
-    case 5: h->member_lists = value != 0; return 0;                     /* edges of large facets confirmed through member lists (1) or against all elements (0) */           /* facets from this size on confirm edges through the facet-major member lists (4096) */
+    case 21: h->cmp_keep_cap = value != 0; return 0;                     /* bslv_poly_compact keeps the old capacities (test hook: the renumbering without the re-allocations that follow smaller arrays) */
+    case 5: h->member_lists = value != 0; return 0;                    /* edges of large facets confirmed through member lists (1) or against all elements (0) */           /* facets from this size on confirm edges through the facet-major member lists (4096) */
     default: return BSLV_E_ARG;
     }
 }
@@ -4315,3 +4319,4 @@ int bslv_poly_get_dual_edges(bslv_poly *h, int *ab)
 }  // extern "C"
 
 #include "poly_check.inc"
+#include "poly_compact.inc"

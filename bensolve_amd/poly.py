@@ -238,6 +238,40 @@ class PolyEngine:
         res["clean"] = not any(out[k] for k in (3, 4, 5, 7, 8, 10, 11))
         return res
 
+    GARBAGE_FIELDS = ("slots", "live", "pool_used", "pool_live", "edges", "bytes")
+    COMPACT_STAT_FIELDS = ("calls", "slots_removed", "pool_removed", "bytes_returned", "slots_removed_total", "pool_removed_total",
+                           "us", "us_total")
+
+    def garbage(self):
+        """bslv_poly_garbage: live / garbage figures of the resident polyhedron by name (and as the list `out`); read-only"""
+        out = (ctypes.c_long * 6)()
+        self.lib.bslv_poly_garbage.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        check(self.lib.bslv_poly_garbage(self.h, out))
+        res = dict(zip(self.GARBAGE_FIELDS, [int(v) for v in out]))
+        res["out"] = [int(v) for v in out]
+        return res
+
+    def compact(self):
+        """bslv_poly_compact: the live elements become 0 .. live-1 in ascending order of their old slots, their lists are packed.
+        Returns (new_of_old, figures after the call); new_of_old[i] = -1 for a dead slot.  Element ids taken before are stale."""
+        n = self.lib.bslv_poly_nprimal(self.h)
+        new_of_old = np.full(n, -1, np.int32)
+        out = (ctypes.c_long * 6)()
+        self.lib.bslv_poly_compact.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        check(self.lib.bslv_poly_compact(self.h, new_of_old.ctypes.data if n else None, out))
+        res = dict(zip(self.GARBAGE_FIELDS, [int(v) for v in out]))
+        res["out"] = [int(v) for v in out]
+        return new_of_old, res
+
+    def last_compact_stats(self):
+        """bslv_poly_last_compact_stats by name (and as the list `out`)"""
+        out = (ctypes.c_long * 8)()
+        self.lib.bslv_poly_last_compact_stats.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        check(self.lib.bslv_poly_last_compact_stats(self.h, out))
+        res = dict(zip(self.COMPACT_STAT_FIELDS, [int(v) for v in out]))
+        res["out"] = [int(v) for v in out]
+        return res
+
     def debug_corrupt(self, what, a, b=0, x=0.0):
         """TESTS ONLY (bslv_poly_debug_corrupt): 0 delete edge number a, 1 append edge (a, b), 2 drop the last entry of element a's
         incidence list, 3 add x to coordinate b of element a"""

@@ -598,6 +598,40 @@ int  bslv_poly_check(bslv_poly *h, double tol /* <= 0: 1e-6, the reference's */,
  * takes its place), 1: append edge (a, b), 2: drop the last entry of element a's incidence list, 3: add x to coordinate b of element
  * a.  Anything else, or an index out of range, is BSLV_E_ARG. */
 int  bslv_poly_debug_corrupt(bslv_poly *h, int what, int a, int b, double x);
+/* COMPACTION of the resident polyhedron.  The slot of a cut-off element is never reused and a rebuilt incidence list is copied to the
+ * end of the pool, so slots and pool words grow with the run, not with the live polyhedron; the 32-bit limits (2^30 elements, 2^30
+ * edges, 0xF0000000 pool words) and everything proportional to nprimal count the dead as well.
+ * bslv_poly_garbage (read-only, one small launch): out[0] primal slots in use (nprimal), [1] live elements, [2] pool words used, [3]
+ * pool words the lists of live elements hold (sum of their lengths, slack not counted), [4] edges, [5] device bytes of the element,
+ * pool and edge arrays at their current capacities.
+ * bslv_poly_compact renumbers the live elements 0 .. live-1 in ascending order of their old slots (MONOTONE: live element i becomes its
+ * rank among the live ones, dead slots vanish) and packs their lists; nprimal afterwards equals the live count.  new_of_old (nprimal-
+ * before ints, may be NULL) receives the map, -1 for a dead slot; out (may be NULL) the six figures AFTER the call.  A second call
+ * straight after is a no-op: the identity map, 0 removed, no allocation.
+ *   Kept bit for bit: the coordinates, the used / ideal / sltn marks, every incidence list in its order (the lists hold facet RANKS,
+ *   which do not change), the edge list in its order with both ends mapped, and the whole dual side (dual points, hyperplanes, the
+ *   order of application, dual edges).  So bslv_poly_unprocessed2 / children_of / children_hist answer the same elements under their new
+ *   names with the same parent facets, and the .sol writers produce the same bytes (they number live elements in slot order anyway).
+ *   The pool is rebuilt densely (offsets = a 64-bit scan of the list lengths over the live elements), lists are packed WITHOUT slack --
+ *   a long list gets its slack back at its next rebuild -- and no keep mark is set over the new pool.
+ *   Legal only between bslv_poly_add / bslv_poly_add_cuts calls (never from inside a chunk of cuts: BSLV_E_STATE); a prune still in
+ *   flight is waited for first.  A halfspace that was classified ahead of its turn is DROPPED: it is classified once more by its cut.
+ *   An edge with an end that is no live element, or a list that does not lie inside the pool, is BSLV_E_STATE with a message and
+ *   nothing is moved -- bslv_poly_check calls both defects, so none is expected, and none is silently dropped.
+ *   OUT OF PLACE: every new array is allocated before anything moves, so a failed allocation is BSLV_E_NODEVICE and leaves the
+ *   polyhedron untouched; the peak is old + new.  New capacities are max(the engine's minimum for that array, twice what is needed) and
+ *   never above the old capacity: this is how memory is handed back.
+ *   STALE IDS: element ids handed out before the call (bslv_poly_unprocessed*, bslv_poly_next, bslv_poly_children_of) are stale
+ *   afterwards; the caller maps them through new_of_old.  bslv_poly_mark and every later call take NEW ids.
+ *   h == NULL: BSLV_E_ARG.  Before bslv_poly_init, or with no element: 0, nothing done, the figures zero.
+ * The reference's struct interface (bslv_poly_compat.h) does not offer compaction, and the drivers of the dual variant never ask.
+ * bslv_poly_last_compact_stats: out[0] calls so far, [1] slots removed by the last call, [2] pool words removed, [3] bytes handed back
+ * (capacities before - after), [4] slots removed by all calls, [5] pool words removed by all calls, [6] microseconds of the last call
+ * (host clock around it), [7] of all calls.
+ * The Benson driver can make the call by itself between applies: bslv_benson_set_compact / BSLV_POLY_COMPACT (section 4). */
+int  bslv_poly_garbage(bslv_poly *h, long out[6]);
+int  bslv_poly_compact(bslv_poly *h, int *new_of_old /* nprimal-before ints, may be NULL */, long out[6] /* may be NULL */);
+int  bslv_poly_last_compact_stats(const bslv_poly *h, long out[8]);
 /* host-only self-test of the two mailbox readers of the polyhedron engine (no GPU needed): a writer thread publishes `rounds`
  * messages with the sequence number FIRST and the content afterwards; 0 = every message was taken with its own content
  * (*torn_out: reads that had to be repeated), negative = a reader accepted foreign content.  which: 0 Mail, 1 round state */
@@ -674,6 +708,23 @@ int  bslv_benson_canonical_stats(const bslv_benson *h, long last[4], long total[
 int  bslv_benson_set_certify(bslv_benson *h, int on);
 int  bslv_benson_get_certify(const bslv_benson *h);
 int  bslv_benson_certify_stats(const bslv_benson *h, long counts[3], double worst[5]);
+/* COMPACTION TRIGGER: with dead_fraction f in (0, 1] bslv_benson_apply and its _ctx twin END -- after the cuts and the parking -- with
+ * bslv_poly_compact on their polyhedron when it holds at least min_slots primal slots (< 0: the default, 65536) and
+ * (slots - live) / slots >= f; the driver then re-keys what it holds by primal element (the pre-images of option -s) through
+ * new_of_old.  0 = off, the default: no launch, no synchronisation, no allocation and no bit of any result changes; switched on, an
+ * apply that reaches min_slots pays one small counting launch.  f negative, above 1 or NaN: BSLV_E_ARG, the switch stays as it was.
+ * BSLV_POLY_COMPACT=f[:min] sets it when an engine is created, homogeneous engines included (nothing about compaction depends on the
+ * cut formula).
+ * PIPELINED MODE: while the OTHER batch context holds a collected batch that is not applied yet, the trigger is skipped -- that batch's
+ * element ids are in flight in solve_local_ctx, possibly on another thread, and come back in its records; it fires at the next apply
+ * that finds the other context empty.
+ * SEVERAL RANKS: the decision reads replicated state only (slots, live count), so every rank compacts after the same apply and the
+ * element ids in the records that travel between ranks keep one meaning.
+ * STALE IDS: an element id a caller took from the engine's polyhedron before an apply (bslv_poly_unprocessed*, bslv_benson_preimage_p
+ * keys) may be stale after it once the switch is on; bslv_benson_collect_given must be given ids read after the last apply.
+ * bslv_benson_compact_stats: out[0] compactions, [1] slots removed, [2] pool words removed, [3] microseconds, all of them summed. */
+int  bslv_benson_set_compact(bslv_benson *h, double dead_fraction /* 0 = off (default); (0, 1] */, long min_slots /* < 0: the default, 65536 */);
+int  bslv_benson_compact_stats(const bslv_benson *h, long out[4]);
 /* batch selection: 1 = newest vertices first (default), 2 = spread evenly over the unprocessed queue, 3 = newest first but at
  * most `cap` children of one cut per batch, chosen from a window of `window` batches (set_sibling_rule; default 1, 8): the
  * children of one cut mostly see the same facet of the upper image, so their LPs return the same cut -- the reference's
