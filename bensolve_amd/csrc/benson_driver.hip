@@ -1207,6 +1207,21 @@ int bslv_benson_pool_stats(bslv_benson *h, long out[4])
     out[0] = (long)h->free_slots.size(); out[1] = resident; out[2] = held; out[3] = h->pool_slots;
     return 0;
 }
+// the resident warm-start sources themselves (what pool_stats counts in out[1]) and the generation of each; read-only, for probes
+int bslv_benson_resident_slots(bslv_benson *h, int max_out, int *slots, int *gen)
+{
+    if (!h) return 0;
+    std::lock_guard<std::mutex> lk(h->slot_mu);
+    int n = 0;
+    for (auto &pr : h->parents) {
+        if (pr.first != -2) { auto it = h->facet_slot.find(pr.first); if (it == h->facet_slot.end() || it->second != pr.second) continue; }
+        if (n >= max_out) break;
+        if (slots) slots[n] = pr.second;
+        if (gen) gen[n] = h->slot_gen[pr.second];
+        n++;
+    }
+    return n;
+}
 // pre-images (option -s): x[n] of a vertex of the upper image / (u[m], w[q]) of a vertex of the lower image.  Returns 0 and
 // fills out, or 1 when nothing was stored for that element (directions; elements that were never confirmed).
 int bslv_benson_preimage_p(const bslv_benson *h, int element, double *x)

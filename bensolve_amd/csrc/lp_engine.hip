@@ -2896,7 +2896,11 @@ struct bslv_lpq {
         std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;      // events around the replay's passes (set_profile)
     } per;
     long last_per[4] = {0, 0, 0, 0};
-    long last_passes = 0;              // (LP, pass) pairs of the last batch: how many tableaux k_flush read and wrote
+    // a basis loaded into a slot (bslv_lpq_load_basis, bslv_lpq_rebuild; lp_basis.inc): per LP of a call the nonbasic status (-1: basic)
+    // and value of every variable, and the counters of the last call
+    int *lb_nst_d = nullptr; double *lb_xv_d = nullptr; size_t lb_cap = 0;
+    long last_rebuild[4] = {0, 0, 0, 0};
+    long last_passes = 0;             // (LP, pass) pairs of the last batch: how many tableaux k_flush read and wrote
     long last_launches = 0;            // k_flush launches of the last batch: one per lock-step round + one per pass made on request (bslv_lpq_materialise)
     size_t select_lds_max = 64 * 1024; // dynamic LDS of k_select<true> (candidate sort of the bound flipping ratio test)
     size_t select0_lds_max = 64 * 1024; // ... of k_select<false> (revised form: rho)
@@ -3216,7 +3220,7 @@ void bslv_lpq_destroy(bslv_lpq *h)
     park_free(h);
     period_free(h);
     auto fr = [](void *p) { if (p) (void)hipFree(p); };
-    fr(h->raykind_d); fr(h->raystat_d); fr(h->ray_d);
+    fr(h->raykind_d); fr(h->raystat_d); fr(h->ray_d); fr(h->lb_nst_d); fr(h->lb_xv_d);
     fr(h->age_d); fr(h->age0_d); fr(h->cert_d); fr(h->snorm_d); fr(h->dvxstat_d); fr(h->tnorm_d); fr(h->pdvstat_d);
     fr(h->L.T); fr(h->L.beta); fr(h->L.xN); fr(h->L.bh); fr(h->L.nh); fr(h->L.nstat); fr(h->L.pos);
     fr(h->Tstd); fr(h->lb_d); fr(h->ub_d); fr(h->art_d);
@@ -4954,3 +4958,4 @@ int bslv_lpq_last_stats(const bslv_lpq *h, int *lockstep_iters, long *pivots, do
 }  // extern "C"
 
 #include "lp_certify.inc"
+#include "lp_basis.inc"

@@ -468,6 +468,63 @@ class LpEngine:
         check(self.lib.bslv_lpq_get_inverse(self.h, int(slot), heads.ctypes.data, X.ctypes.data if matrix else None))
         return heads, X
 
+    # status codes of get_basis / load_basis (GLPK's GLP_BS .. GLP_NS)
+    VS_BASIC, VS_LOWER, VS_UPPER, VS_FREE, VS_FIXED = 1, 2, 3, 4, 5
+
+    def _own_rows(self):
+        self.lib.bslv_lpq_rows_folded.argtypes = [ctypes.c_void_p]
+        return self.M - int(self.lib.bslv_lpq_rows_folded(self.h))
+
+    def var_map(self):
+        """own_of_given: for every variable of the model as given (rows, then columns) its index in the engine's own model, -1 for a
+        row the presolve folded into a column's bounds (bslv_lpq_var_map)"""
+        out = np.empty(self.M + self.N, np.int32)
+        self.lib.bslv_lpq_var_map.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        check(self.lib.bslv_lpq_var_map(self.h, out.ctypes.data))
+        return out
+
+    def get_basis(self, slot):
+        """(vstat, row_of) of a slot over the engine's own variables: the status codes VS_*, and the row of every basic variable, -1
+        for a nonbasic one (bslv_lpq_get_basis)"""
+        n = self._own_rows() + self.N
+        vstat, row_of = np.empty(n, np.int32), np.empty(n, np.int32)
+        self.lib.bslv_lpq_get_basis.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+        check(self.lib.bslv_lpq_get_basis(self.h, int(slot), vstat.ctypes.data, row_of.ctypes.data))
+        return vstat, row_of
+
+    def load_basis(self, slots, vstat, vlo=None, vup=None):
+        """install the bases vstat (len(slots) x (M + N) codes VS_*, the engine's own model) in the slots; vlo / vup: the per-LP bounds
+        the nonbasic values come from, or None for the model's (bslv_lpq_load_basis).  Returns the per-slot statuses: 0, or 3 =
+        UNDEFINED for a singular basis (that slot is then reset to the standard basis).  A refused argument raises."""
+        slots = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        n = len(slots)
+        vstat = np.ascontiguousarray(vstat, np.int32).reshape(n, self._own_rows() + self.N)
+        assert (vlo is None) == (vup is None)
+        if vlo is not None:
+            vlo = np.ascontiguousarray(vlo, np.float64).reshape(n, self.vcnt)
+            vup = np.ascontiguousarray(vup, np.float64).reshape(n, self.vcnt)
+        st = np.zeros(n, np.int32)
+        self.lib.bslv_lpq_load_basis.argtypes = [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 5
+        check(self.lib.bslv_lpq_load_basis(self.h, n, slots.ctypes.data, vstat.ctypes.data, None if vlo is None else vlo.ctypes.data,
+                                           None if vup is None else vup.ctypes.data, st.ctypes.data))
+        return st
+
+    def rebuild(self, slots):
+        """rebuild the slots in place from their own basis and the model: every variable keeps its nonbasic status and value
+        (bslv_lpq_rebuild; the revised form: bslv_lpq_refactor).  Returns the per-slot statuses as load_basis does."""
+        slots = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        st = np.zeros(len(slots), np.int32)
+        self.lib.bslv_lpq_rebuild.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+        check(self.lib.bslv_lpq_rebuild(self.h, len(slots), slots.ctypes.data, st.ctypes.data))
+        return st
+
+    def last_rebuild_stats(self):
+        """of the last load_basis / rebuild (bslv_lpq_last_rebuild_stats)"""
+        o = (ctypes.c_long * 4)()
+        self.lib.bslv_lpq_last_rebuild_stats.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        check(self.lib.bslv_lpq_last_rebuild_stats(self.h, o))
+        return dict(rebuilt=int(o[0]), replay_pivots=int(o[1]), passes=int(o[2]), failed=int(o[3]))
+
     def debug_perturb_inverse(self, slot, rel):
         """tests only: a deterministic stand-in for drift in the stored inverse of a slot (bslv_lpq_debug_perturb_inverse)"""
         self.lib.bslv_lpq_debug_perturb_inverse.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_double]

@@ -145,6 +145,56 @@ int  bslv_lpq_last_period_stats(const bslv_lpq *h, long out[4]);
 int  bslv_lpq_get_inverse(bslv_lpq *h, int slot, int *heads /* M */, double *X /* M x M row-major, may be NULL */);
 int  bslv_lpq_debug_perturb_inverse(bslv_lpq *h, int slot, double rel);
 int  bslv_lpq_debug_swap_heads(bslv_lpq *h, int slot, int r, int q);
+/* A BASIS TAKEN OUT OF A SLOT AND PUT INTO ONE, in both forms (GLPK has glp_get_row_stat / glp_set_row_stat beside glp_std_basis; the
+ * reference itself only ever calls glp_std_basis, bslv_lp.c:101,225).  Every index is one of the engine's OWN model, as in
+ * bslv_lpq_get_inverse: M = rows given minus bslv_lpq_rows_folded, variables 0..M-1 auxiliary, M..M+N-1 structural.
+ * bslv_lpq_var_map is the one translation a caller needs: own_of_given[v] for every variable v of the model as given (M_given + N), -1
+ * for a folded row.  The status codes are GLPK's GLP_BS .. GLP_NS.
+ * bslv_lpq_get_basis: vstat[k] of every variable of a slot that may be passed as `src` and, unless row_of is NULL, the row of a basic
+ * variable (-1 otherwise).  Heads and statuses follow every committed pivot, so a parked or lazily open slot answers what it answers after
+ * bslv_lpq_materialise.  A nonbasic variable is reported by the side the engine holds it on -- LOWER / UPPER also where that bound is one
+ * of the engine's artificial ones (+-1e7 in place of an infinite bound on the side a cost needs), which load_basis accepts back -- FIXED
+ * where its bounds were equal in the solve that left it, FREE where it rests at 0 without a bound.  A slot that bslv_lpq_reset_slot left
+ * reports every structural LOWER: the standard basis' placeholder, which the next solve replaces by the side the bounds allow.
+ * bslv_lpq_load_basis installs the basis vstat[b * (M + N) ..] in slot slots[b] (distinct, as for bslv_lpq_refactor).  Nothing numeric
+ * in the slot is read.  Nonbasic values come from the bound the status names: vlo / vup[b * var_cnt ..] inside the per-LP range (both
+ * NULL: the model's bounds there too), the model's bounds (with the artificial ones) elsewhere, FREE is 0; a LOWER / UPPER variable whose
+ * two bounds are equal is held as FIXED.  The tableau form rebuilds the slot's tableau on the device: the slot starts as the standard
+ * image [A ; cost], the structural basic variables enter in ascending variable id, each on the row partial pivoting chooses among the
+ * rows whose auxiliary variable is nonbasic in the target and not yet pivoted (ties: the smallest row), as ordinary pending pivots, KP
+ * per pass of the tableau-update kernel, the cost row carried by the same pivots, and a refresh pass recomputes the basic values and the
+ * objective; nonbasic position j ends holding structural j or the auxiliary variable that left when structural j entered.  The revised
+ * form writes heads, statuses and values and runs the replay of bslv_lpq_refactor; the slot's age is 0.  Either way the reduced costs
+ * are those of the ENGINE'S OWN cost vector, no atomics enter the arithmetic and every reduction has a fixed order: the result is a
+ * function of (vstat, model, bounds).  The slot is then a valid `src`.
+ * FEASIBILITY IS NOT CHECKED: that is the caller's business.  A later solve_batch from such a slot first re-seats every nonbasic variable
+ * against the bounds of ITS call, as from any parent.  Then under BSLV_LP_METHOD_DUAL a basis that is not dual feasible comes back
+ * BSLV_LP_UNDEFINED (primal infeasibility is what the dual simplex removes); under PRIMAL a phase 1 removes primal infeasibility and
+ * primal steps the dual one; under REPAIR the dual simplex runs where it can start and the primal start takes the rest.  A basis that is
+ * optimal for the call's bounds comes back OPTIMAL with 0 iterations.
+ * BSLV_E_ARG, with nothing changed: a status code outside 1..5; a count of BASIC other than M; LOWER / UPPER naming an infinite bound (a
+ * free variable has none to name); FREE on a variable with a finite bound of the model's own; FIXED on a variable whose bounds differ; a
+ * slot out of range or named twice; n < 0; only one of vlo / vup.  A SINGULAR basis is not an error of the call: by the test of
+ * bslv_lpq_refactor -- a pivot with |v_r| <= 1e-9 (1 + max |v|) -- status_out[b] (may be NULL) = BSLV_LP_UNDEFINED, that slot is reset as by
+ * bslv_lpq_reset_slot and the other slots of the call are unaffected; 0 otherwise.  A call while slots of the last batch still wait for
+ * their tableau (bslv_lpq_set_lazy) gives all of them their tableau first, as a solve does; a parked record of a named slot is dropped,
+ * one that reads a named slot as its parent makes its pass first.
+ * bslv_lpq_rebuild is load_basis with the slot's own basis: every variable keeps its nonbasic status and value, the tableau, the reduced
+ * costs (the engine's own cost vector: see bslv_lpq_refactor for slots of an objective batch) and the basic values are rebuilt from the
+ * model.  A slot whose pass is parked or pending is materialised first, by bslv_lpq_materialise.  In the revised form it IS
+ * bslv_lpq_refactor: same code path, same result bit for bit.  bslv_lpq_refactor, _set_refactor and _set_refactor_period keep refusing
+ * the tableau form: no rebuild happens inside a solve there.
+ * bslv_lpq_last_rebuild_stats, of the last load_basis / rebuild: [0] slots rebuilt, [1] replay pivots, [2] passes over a slot ((LP, pass)
+ * pairs of the tableau-update kernel, the refresh pass included), [3] slots that failed (singular).
+ * BSLV_LP_BASIS_TIMING=1 (tableau form): one line per call on stderr with the HIP-event time of the replay, of its passes and of the
+ * refresh pass alone -- a plain pass of the tableau-update kernel over the same slots, for comparison. */
+enum { BSLV_LP_VS_BASIC = 1, BSLV_LP_VS_LOWER = 2, BSLV_LP_VS_UPPER = 3, BSLV_LP_VS_FREE = 4, BSLV_LP_VS_FIXED = 5 };
+int  bslv_lpq_var_map(const bslv_lpq *h, int *own_of_given /* M_given + N */);
+int  bslv_lpq_get_basis(bslv_lpq *h, int slot, int *vstat /* M + N, engine's own model */, int *row_of /* M + N or NULL */);
+int  bslv_lpq_load_basis(bslv_lpq *h, int n, const int *slots, const int *vstat /* n * (M + N) */,
+                         const double *vlo, const double *vup /* n * var_cnt, or both NULL: the model's bounds */, int *status_out /* n or NULL */);
+int  bslv_lpq_rebuild(bslv_lpq *h, int n, const int *slots, int *status_out);
+int  bslv_lpq_last_rebuild_stats(const bslv_lpq *h, long out[4]);
 int  bslv_lpq_pool_slots(const bslv_lpq *h);
 size_t bslv_lpq_slot_bytes(const bslv_lpq *h);
 /* LAZY TABLEAUX.  The first pass of a solve writes the LP's tableau into its own slot -- the largest memory item of a batch, and
@@ -752,6 +802,10 @@ int  bslv_benson_collect_given(bslv_benson *h, int n, const int *idx, const doub
 int  bslv_benson_last_local(bslv_benson *h, int max_out, int *src, int *pivots, int *gen);
 /* tableau pool: out[0] free slots, [1] resident warm-start sources, [2] held by a batch in flight, [3] pool size */
 int  bslv_benson_pool_stats(bslv_benson *h, long out[4]);
+/* the resident warm-start sources themselves (read-only, for probes: scripts/probe/tableau_drift.py): their slots and, per slot, its
+ * generation -- the warm starts between the root tableau and the slot; either may be NULL.  Returns the number of entries written, at
+ * most max_out */
+int  bslv_benson_resident_slots(bslv_benson *h, int max_out, int *slots, int *gen);
 /* apply() parks the tableau passes of the slots it keeps (bslv_lpq_park) and tells the LP engine which parked slots the pool has
  * evicted (bslv_lpq_drop_parked); set_park(h, 0), or BSLV_LP_PARK=0 at create, makes the passes at the end of apply() instead
  * (bslv_lpq_materialise).  Same LPs, same cuts, same slots either way.  park_stats: as bslv_lpq_park_stats. */
