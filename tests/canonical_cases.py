@@ -178,6 +178,15 @@ PROBLEMS = {
     # P2 has 84 columns here: a tableau row crosses 64 columns and one step of the row length (ld = 96)
     "covering-30x80x3": lambda: _covering(30, 80, 3, 4, 27, 10),
 }
+# Wide sets: P2 of covering_vlp(24, n, q, seed) has N = n + q + 1 columns, one on each side of a threshold of the launch code
+# (tests/test_lp_canonical_gpu.py names them).  q = 3: M + 1 = 32 rows, the last row tile of a pass is full; q = 4: 34, it holds one row.
+# N -> (n, q, seed, nweights, npairs), chosen on the CPU (python tests/canonical_cases.py prints what each set keeps).  The sets
+# with q = 4 take 18 weights and 3 pairs: with 27 and 10 (34 and 37 candidates, 28 and 34 kept) they need 11 s and 15 s to build.
+WIDE = {256: (252, 3, 1, 27, 10), 257: (253, 3, 1, 27, 10), 1120: (1116, 3, 2, 27, 10), 1121: (1117, 3, 2, 27, 10),
+        1535: (1531, 3, 3, 27, 10), 1536: (1532, 3, 3, 27, 10), 2048: (2043, 4, 4, 18, 3), 2049: (2044, 4, 4, 18, 3)}
+WIDE_NAMES = {N: "wide-24x%dx%d" % v[:2] for N, v in WIDE.items()}
+for _N, _v in WIDE.items():
+    PROBLEMS[WIDE_NAMES[_N]] = lambda v=_v: _covering(24, v[0], v[1], v[2], v[3], v[4])
 _cache = {}
 
 
@@ -199,3 +208,16 @@ def check_case_set(c):
     assert kept >= 12, "only %d cases kept" % kept
     assert 2 * int(c["degenerate"].sum()) >= kept, "%d of %d kept cases are degenerate" % (int(c["degenerate"].sum()), kept)
     assert 4 * c["dropped"] <= c["candidates"], "%d of %d candidates dropped by the keep rule" % (c["dropped"], c["candidates"])
+
+
+if __name__ == "__main__":
+    import os
+    import sys
+    import time
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    for name in sys.argv[1:] or sorted(PROBLEMS):
+        t0 = time.time()
+        prob, c = cases(name)
+        check_case_set(c)
+        print("canonical_cases %s: m %d n %d q %d candidates %d kept %d degenerate %d dropped %d (%.1f s)" % (
+            name, prob["m"], prob["n"], prob["q"], c["candidates"], len(c["V"]), int(c["degenerate"].sum()), c["dropped"], time.time() - t0), flush=True)

@@ -4,7 +4,18 @@ P2(v) is primal degenerate where the ray v + z c meets an edge or a vertex of th
 optimal and the engine returns the one its pivots reached.  With the switch on it has to return the dual of P2(v + t d) for small
 t > 0 -- which HiGHS computes by solving the shifted LPs (tests/canonical_cases.py: the keep rule, the conditions on the case sets)
 -- whatever basis the LP started from, and leave status and objective as they are bit for bit.  With the switch off nothing may
-differ from an engine that never saw the new calls."""
+differ from an engine that never saw the new calls.
+
+Wide sets (canonical_cases.WIDE: covering problems of 24 rows whose P2 has N columns), the threshold of the launch code each pair of
+names straddles and the line of bensolve_amd/csrc/lp_engine.hip it comes from:
+  wide-24x252x3  wide-24x253x3     N = 256, 257: one workgroup width of NT = 256 columns against a second stride of every
+                                   "for (int j = tid; j < N; j += NT)" of tie_once (k_select_tie runs "dim3(plan.nt)" threads)
+  wide-24x1116x3 wide-24x1117x3    N = 1120, 1121: the 1024-thread k_flush that makes the tie pivots' tableau pass: flush_launch,
+                                   "big_flush = e ? atoi(e) > NT : lds > 53 * 1024" with lds = KP * ldt * 8, ldt = 1120 against 1136
+  wide-24x1531x3 wide-24x1532x3    N = 1535, 1536: plan_select, "L.N >= 1536 ? NT_BIG : NT" -- k_select_tie's block size with it
+  wide-24x2043x4 wide-24x2044x4    N = 2048, 2049: plan_init, "ld2 > 16 * WAVE": k_init_grouped against k_init
+q = 3 gives P2 M + 1 = 32 rows, the last row tile of k_flush is full; q = 4 gives 34, that tile holds a single row.  Every wide set
+has to show tie pivots, and the N = 1121 set gives the same bits under the other launch shapes (BSLV_FLUSH_NT, BSLV_SELECT_NT)."""
 import os
 
 import numpy as np
@@ -16,6 +27,7 @@ from bensolve_amd.lp import P2Model, LpEngine
 pytestmark = pytest.mark.gpu
 RTOL = 1e-9               # tests/test_lp_gpu.py's bound against HiGHS
 NAMES = sorted(cc.PROBLEMS)
+WIDE_NAMES = [cc.WIDE_NAMES[N] for N in sorted(cc.WIDE)]
 
 
 def _solve_cold_then_batch(eng, model, V, canonical=False):
@@ -145,6 +157,45 @@ def test_switch_off_is_the_engine_as_it_was(name):
         eng.close()
     assert rows[0] == rows[1]
     assert rows[0]["st"] == out[0]["st"].tobytes() and rows[0]["it"] == out[0]["it"].tobytes()
+
+
+@pytest.mark.parametrize("name", WIDE_NAMES)
+def test_tie_phase_pivots_on_the_wide_sets(name):
+    """non-vacuity: at every width the tie phase really pivoted (the engine's answer is used to avoid an empty test, never as a bound)"""
+    c, out = _res(name)
+    on = out[1]
+    print("lp_canonical_shapes %s: N %d, %d cases, %d degenerate, %d dropped; largest |w - expected| with the switch on %.3e; tie phase %s" % (
+        name, P2Model(cc.cases(name)[0]).N, len(c["V"]), int(c["degenerate"].sum()), c["dropped"], np.abs(on["w"] - c["w"]).max(), on["canon"]))
+    assert on["canon"]["tie_pivots"] > 0
+    assert on["canon"]["entered"] == len(c["V"])          # (bslv_hip.h: all that ended OPTIMAL)
+
+
+def test_launch_shapes_do_not_change_the_canonical_duals(monkeypatch):
+    """the N = 1121 set under 256 and 1024 threads per k_flush workgroup and 1024 per selection (and tie) workgroup: status, pivots,
+    objective, the full primal and dual vectors and the tie counters are the same bits as with nothing set; an engine of its own per arm"""
+    name = cc.WIDE_NAMES[1121]
+    prob, c = cc.cases(name)
+    cc.check_case_set(c)
+    model = P2Model(prob)
+    assert model.N == 1121
+    V, n = c["V"], model.M + model.N
+    rows = []
+    for env in ({}, {"BSLV_FLUSH_NT": "256"}, {"BSLV_FLUSH_NT": "1024"}, {"BSLV_SELECT_NT": "1024"}):
+        for k in ("BSLV_SELECT_NT", "BSLV_FLUSH_NT"):
+            monkeypatch.delenv(k, raising=False)
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        eng = LpEngine.from_model(model, pool_slots=len(V) + 2)
+        dst, st, it = _solve_cold_then_batch(eng, model, V, canonical=True)
+        rows.append(dict(st=st.tobytes(), it=it.tobytes(), obj=eng.obj(dst).tobytes(), x=eng.primal(dst, 0, n).tobytes(), y=eng.dual(dst, 0, n).tobytes(),
+                         canon=eng.last_canonical_stats()))
+        w = eng.dual(dst, model.w_first, model.q)
+        eng.close()
+        print("lp_canonical_shapes %s %s: largest |w - expected| %.3e; tie phase %s" % (name, env or "unset", np.abs(w - c["w"]).max(), rows[-1]["canon"]))
+        np.testing.assert_allclose(w, c["w"], rtol=RTOL, atol=1e-9)
+    assert rows[0]["canon"]["tie_pivots"] > 0
+    for r in rows[1:]:
+        assert r == rows[0]
 
 
 def test_revised_form_refuses_the_switch():
