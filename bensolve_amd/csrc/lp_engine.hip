@@ -20,6 +20,7 @@
 #include <vector>
 #include <algorithm>
 #include <chrono>
+#include <type_traits>
 
 namespace bslv {
 
@@ -58,7 +59,7 @@ constexpr int PF_PERT = 1, PF_PRIMAL = 2, PF_PERT_PENDING = 4, PF_USES_SHIFT = 8
 // holds its pricing vector d1; it has been there in this solve; d1 has to be rebuilt from the rows; d1 is current although nothing is pending
 constexpr int PF_PHASE1 = 16, PF_P1_SEEN = 32, PF_P1_STALE = 64, PF_P1_KEEP = 128;
 // RAY RECORD (bslv_lpq_set_rays): the thread that concludes INFEASIBLE or UNBOUNDED while it holds the proof leaves one word in
-// BatchView::stall -- a finished LP has no use for its stall count, and no member is added to BatchView (see DvxView) -- from which k_ray
+// BatchView::stall -- a finished LP has no use for its stall count, and no member is added to BatchView (see NormView) -- from which k_ray
 // builds the vector after the rounds: RAY_REC | index << 7 | pending pivots << 3 | side << 2 | what.  what: RAY_ROW = the dual selection's
 // row `index` without an entering candidate (side: below its lower bound), RAY_P1 = phase 1 without an improving column, RAY_DIR = the
 // primal step's column `index` without a blocking row (side: dir = +1).  The pending count says where the selection's row[] / pc[] lie.
@@ -137,17 +138,18 @@ struct BatchView {
     int lazy;               // bslv_lpq_set_lazy: an LP that is finished when its pass would be due keeps its pending pivots; its slot gets the tableau only when asked for (bslv_lpq_materialise)
     unsigned long long *dbg; // BSLV_REV_PROBE & 8: 100 MHz clock ticks per phase of the dual selection of LP 0 (timing experiments)
 };
-// Dual Devex pricing (bslv_lpq_set_pricing): what a batch keeps for it.  A view of its own, an argument of the DVX kernels alone: two
-// more pointers in BatchView move the argument segment of EVERY kernel that takes one (measured: other scratch sizes and scalar spills
-// in k_select, k_select_p1 and k_select_cached), and the kernels of the default rule are to stay what they were.
-struct DvxView {
-    double *snorm;          // [B][Mp1p] reference norm s_i >= 1 of every basis row (the square root of the Devex weight), 1 in the reference framework
-    int *stat;              // [3] of the batch: dual selections under the weighted rule, those whose row is not the row of the largest violation, resets of a framework after the start
-};
-// Primal Devex pricing (bslv_lpq_set_primal_pricing): the same for the primal steps, an argument of the PDV kernels alone
-struct PdvView {
-    double *tnorm;          // [B][ld] reference norm t_j >= 1 of every nonbasic column POSITION j (the square root of the Devex weight), 1 in the reference framework
-    int *stat;              // [3] of the batch: primal selections under the weighted rule, those whose column is not the column of the largest score, new frameworks after the start
+// Devex pricing, dual (bslv_lpq_set_pricing) or primal (bslv_lpq_set_primal_pricing): what a batch keeps for its rule.  A view of its
+// own, an argument of the priced kernels alone: two more pointers in BatchView move the argument segment of EVERY kernel that takes one
+// (measured: other scratch sizes and scalar spills in k_select, k_select_p1 and k_select_cached), and the kernels of the default rule
+// are to stay what they were.
+enum { RULE_DVX = 1, RULE_PDV = 2 };      // the rule of a priced instance (k_select_priced); no instance carries both
+struct NormView {
+    // reference norms >= 1 (the square roots of the Devex weights), 1 in the reference framework.  DVX: [B][Mp1p], s_i of every basis row;
+    // PDV: [B][ld], t_j of every nonbasic column POSITION j
+    double *norm;
+    // [3] of the batch: selections under the weighted rule; those whose row (DVX) / column (PDV) is not the one of the largest violation /
+    // score; frameworks started anew after the start
+    int *stat;
 };
 
 __device__ __forceinline__ double LO(const LpView &L, const BatchView &Bv, int b, int k)
@@ -1067,8 +1069,9 @@ __device__ __forceinline__ bool phase1_prepare(const LpView &L, const BatchView 
 //  the entering column is the eligible one with the largest score / t_j instead of the largest score; Bland's rule takes no notice)
 template <bool P1, bool DVX = false, bool PDV = false>
 __device__ __forceinline__ bool primal_step(const LpView &L, const BatchView &Bv, const SelCtx &c, int &pf, const bool bland, double *sv, int *si,
-                                            int &r, int &q, bool &below, double &pstep, int &rsig, int *xr = nullptr, unsigned char *xdyn = nullptr, const PdvView *pv = nullptr)
+                                            int &r, int &q, bool &below, double &pstep, int &rsig, int *xr = nullptr, unsigned char *xdyn = nullptr, const NormView *nv = nullptr)
 {
+    static_assert(!(DVX && PDV), "one rule per instance: nv holds the norms of one");
     const int tid = threadIdx.x, NT = (int)blockDim.x, b = c.b, M = L.M, N = L.N;
     const double *pc = c.pc;
     double *beta = c.beta;
@@ -1084,7 +1087,7 @@ __device__ __forceinline__ bool primal_step(const LpView &L, const BatchView &Bv
     if constexpr (PDV) {
         // (four columns per thread with all loads issued first, as the passes of the dual selection; the column of the largest
         //  unweighted score is found beside it, for the statistics only: bslv_lpq_last_primal_pricing_stats)
-        const double *tn = pv->tnorm + (size_t)b * L.ld;
+        const double *tn = nv->norm + (size_t)b * L.ld;
         ValIdx plain{0.0, -1};
         constexpr int PU = 4;
         for (int j0 = tid; j0 < N; j0 += PU * NT) {
@@ -1141,7 +1144,7 @@ __device__ __forceinline__ bool primal_step(const LpView &L, const BatchView &Bv
     }
     if (Bv.iters[b] >= L.maxit) { if (tid == 0) { Bv.status[b] = BSLV_LP_UNDEFINED; Bv.mode[b] = MODE_NONE; } return false; }
     q = ent.i;
-    if constexpr (PDV) if (tid == 0 && !bland) { atomicAdd(&pv->stat[0], 1); if (other_col) atomicAdd(&pv->stat[1], 1); }      // (a selection priced by the norms: it ends in a pivot, a bound switch or a ray)
+    if constexpr (PDV) if (tid == 0 && !bland) { atomicAdd(&nv->stat[0], 1); if (other_col) atomicAdd(&nv->stat[1], 1); }      // (a selection priced by the norms: it ends in a pivot, a bound switch or a ray)
     const int stq = c.nstat[q], kq = c.nh[q];
     const double dq = dj[q];
     const double dir = (stq == NS_U || (stq == NS_F && dq > 0.0)) ? -1.0 : 1.0;
@@ -1336,26 +1339,26 @@ __device__ __forceinline__ bool switch_bounds(const LpView &L, const BatchView &
 // move the others' variables into a table looked up by kernel.  So k_select_p1 declares everything itself and hands it down.
 struct SelShared { double sv[NT_BIG / WAVE]; int si[NT_BIG / WAVE]; PivDesc d; int cnt3[3]; unsigned char *dyn; };
 // DVX: DUAL DEVEX PRICING (bslv_lpq_set_pricing; Forrest and Goldfarb's reference framework, dual form).  Every basis row i of the LP
-// has a reference norm s_i >= 1 (DvxView::snorm; the square root of the usual weight), 1 in the reference framework: the basis the solve starts
+// has a reference norm s_i >= 1 (NormView::norm; the square root of the usual weight), 1 in the reference framework: the basis the solve starts
 // from.  Phase A takes the violated row with the largest violation / s_i (leave_candidate_dvx), and a dual pivot on row r with the
 // multipliers f_i of Phase D (|f_i| = |alpha_iq / alpha_rq|) and p = 1 / alpha_rq leaves
 //   s_i = max(s_i, |f_i| s_r)  (i != r),      s_r = max(s_r |p|, 1)
 // in the loop that updates beta: no entry of the tableau is read for it.  A basis change that is no such dual step -- a primal clean-up
 // or phase-1 pivot here, a refactorisation replay on the host side -- starts a new framework (all s_i = 1); bound switches change
-// nothing.  Instances of their own (k_select_dvx, k_select_p1_dvx), so that the kernels of the default rule stay what they were; like P1
+// nothing.  Instances of their own (k_select_priced<RULE_DVX, ..>), so that the kernels of the default rule stay what they were; like P1
 // they get their LDS handed down (SelSharedDvx: also the words of the revised form's row fetch).
 struct SelSharedDvx : SelShared { int rv[3 + REV_HQ + 1]; };      // rv: request word of a helper / request number of the LP's own workgroup, slice ticket, late flag; rev_row_slice's queue and its length
 // PDV: PRIMAL DEVEX PRICING (bslv_lpq_set_primal_pricing; the same framework, primal form).  Every nonbasic column position j of the LP
-// has a reference norm t_j >= 1 (PdvView::tnorm), 1 in the reference framework: the basis the solve starts from.  A primal step, of phase
+// has a reference norm t_j >= 1 (NormView::norm), 1 in the reference framework: the basis the solve starts from.  A primal step, of phase
 // 1 or 2, takes the eligible column with the largest score / t_j (primal_step), and a primal pivot (r, q) with the pivot row alpha_r that
 // fetch_row has just produced leaves
 //   t_j = max(t_j, |alpha_rj / alpha_rq| t_q)  (j != q),      t_q = max(t_q / |alpha_rq|, 1)   (position q now holds the leaving variable)
 // in one more pass over the row: no further entry of the tableau is read for it.  The norms do not depend on the cost, so phase 1 and
 // phase 2 share them.  A dual pivot of the LP here, a refactorisation replay on the host side, start a new framework (all t_j = 1); bound
-// switches change nothing.  Instances of their own again (k_select_pdv, k_select_p1_pdv), which take the LDS of the DVX ones; no
+// switches change nothing.  Instances of their own again (k_select_priced<RULE_PDV, ..>), which take the LDS of the DVX ones; no
 // instance carries both rules.
 template <bool EXT, bool P1 = false, bool DVX = false, bool PDV = false>
-__device__ __forceinline__ bool select_once(const LpView &L, const BatchView &Bv, const int b, const int cap2, SelShared *xs = nullptr, const DvxView *dv = nullptr, const PdvView *pv = nullptr)
+__device__ __forceinline__ bool select_once(const LpView &L, const BatchView &Bv, const int b, const int cap2, SelShared *xs = nullptr, const NormView *nv = nullptr)
 {
     static_assert(EXT || !P1, "phase 1 lives in the extended selection");
     static_assert(!(DVX && PDV) && (EXT || !PDV), "one rule per instance; primal steps live in the extended selection");
@@ -1407,13 +1410,13 @@ __device__ __forceinline__ bool select_once(const LpView &L, const BatchView &Bv
     const bool primal = EXT && (pf & PF_PRIMAL);
     double pstep = 1.0;                      // length of a primal step (clean-up)
     int rsig = 0;                            // phase 1: which bound the leaving variable violated
-    double *const snorm = DVX ? dv->snorm + (size_t)b * L.Mp1p : nullptr;      // dual Devex pricing: the reference norms of the rows
+    double *const snorm = DVX ? nv->norm + (size_t)b * L.Mp1p : nullptr;      // dual Devex pricing: the reference norms of the rows
     bool other_row = false;                  // ... the weighted rule chose another row than the largest violation's
-    double *const tnorm = PDV ? pv->tnorm + (size_t)b * ld : nullptr;          // primal Devex pricing: the reference norms of the column positions
+    double *const tnorm = PDV ? nv->norm + (size_t)b * ld : nullptr;          // primal Devex pricing: the reference norms of the column positions
     double tq = 1.0;                         // ... the entering position's norm as it was (read by all, barriers before the update writes it)
 
     if (primal) {
-        if (!primal_step<P1, DVX, PDV>(L, Bv, c, pf, bland, sv, si, r, q, below, pstep, rsig, xr, dyn, pv)) return true;
+        if (!primal_step<P1, DVX, PDV>(L, Bv, c, pf, bland, sv, si, r, q, below, pstep, rsig, xr, dyn, nv)) return true;
         if constexpr (PDV) tq = tnorm[q];
     } else {
     // ---- dual simplex step ----
@@ -1528,8 +1531,8 @@ __device__ __forceinline__ bool select_once(const LpView &L, const BatchView &Bv
         } else {
             s_d = commit_pivot(L, Bv, c, r, q, below, bland, Bv.iters[b], Bv.verified[b], (nflip > 0 && !incr) ? MODE_REFRESH : MODE_PIVOT, dwork, primal, nflip, pf & PF_PERT);
             if constexpr (DVX) {
-                if (primal) atomicAdd(&dv->stat[2], 1);           // (a primal or phase-1 pivot: a new reference framework, see Phase D)
-                else if (!bland) { atomicAdd(&dv->stat[0], 1); if (other_row) atomicAdd(&dv->stat[1], 1); }
+                if (primal) atomicAdd(&nv->stat[2], 1);           // (a primal or phase-1 pivot: a new reference framework, see Phase D)
+                else if (!bland) { atomicAdd(&nv->stat[0], 1); if (other_row) atomicAdd(&nv->stat[1], 1); }
             }
             if constexpr (EXT) {
                 if (nflip > 0) atomicAdd(&Bv.xstat[0], 1);
@@ -1568,7 +1571,7 @@ __device__ __forceinline__ bool select_once(const LpView &L, const BatchView &Bv
             }
         } else {
             for (int j = tid; j < N; j += NT) tnorm[j] = 1.0;
-            if (tid == 0) atomicAdd(&pv->stat[2], 1);
+            if (tid == 0) atomicAdd(&nv->stat[2], 1);
         }
     }
     // Phase D: the entering column as it is after the pending pivots -> multipliers of all rows, beta; the reduced-cost row
@@ -1797,12 +1800,9 @@ __device__ __forceinline__ bool select_once_cached(const LpView &L, const BatchV
 // (the extended instance is a function of its own, as the compiler always had it: inlined into the 1024-thread kernel it spills 300 registers, called none)
 __device__ __noinline__ bool select_once_ext(const LpView &L, const BatchView &Bv, const int b, const int cap2) { return select_once<true>(L, Bv, b, cap2); }
 __device__ __noinline__ bool select_once_p1(const LpView &L, const BatchView &Bv, const int b, const int cap2, SelShared *xs) { return select_once<true, true>(L, Bv, b, cap2, xs); }
-// (dual Devex pricing: the same three shapes)
-__device__ __noinline__ bool select_once_dvx_ext(const LpView &L, const BatchView &Bv, const int b, const int cap2, SelShared *xs, const DvxView *dv) { return select_once<true, false, true>(L, Bv, b, cap2, xs, dv); }
-__device__ __noinline__ bool select_once_dvx_p1(const LpView &L, const BatchView &Bv, const int b, const int cap2, SelShared *xs, const DvxView *dv) { return select_once<true, true, true>(L, Bv, b, cap2, xs, dv); }
-// (primal Devex pricing: the two extended shapes)
-__device__ __noinline__ bool select_once_pdv_ext(const LpView &L, const BatchView &Bv, const int b, const int cap2, SelShared *xs, const PdvView *pv) { return select_once<true, false, false, true>(L, Bv, b, cap2, xs, nullptr, pv); }
-__device__ __noinline__ bool select_once_pdv_p1(const LpView &L, const BatchView &Bv, const int b, const int cap2, SelShared *xs, const PdvView *pv) { return select_once<true, true, false, true>(L, Bv, b, cap2, xs, nullptr, pv); }
+// (Devex pricing: the extended and the phase-1 shape of either rule)
+template <int RULE, bool P1>
+__device__ __noinline__ bool select_once_priced(const LpView &L, const BatchView &Bv, const int b, const int cap2, SelShared *xs, const NormView *nv) { return select_once<true, P1, RULE == RULE_DVX, RULE == RULE_PDV>(L, Bv, b, cap2, xs, nv); }
 // One launch selects up to nsel pivots per LP, one after the other, by the same workgroup: the KP selections between two passes
 // over the tableau depend only on the LP's own vectors (beta, the reduced-cost row, the pending pivot rows and multipliers) -- no
 // grid-wide dependency asks for a launch each (rounds 1-3 launched this kernel KP times per pass, 17 % of all GPU time in
@@ -1853,95 +1853,48 @@ __global__ __launch_bounds__(NT) void k_select_cached(LpView L, BatchView Bv, co
     }
 }
 
-// k_select<EXT> and k_select_p1 under dual Devex pricing (bslv_lpq_set_pricing; select_once<.., DVX>): what a batch launches while the
-// switch is on, in both forms and at both block sizes, the helpers of the revised form included.  Kernels of their own, with their LDS
-// declared here and handed down (see SelShared), so that the ones above compile to what they always did.  k_select_cached has no such
-// instance: with the switch on, the plan does not take it.
-template <bool EXT>
-__global__ __launch_bounds__(NT_BIG) void k_select_dvx(LpView L, BatchView Bv, DvxView Dv, const int *active, int nact, int cap2, int nsel)
+// k_select<EXT> and k_select_p1 under Devex pricing (select_once<.., DVX> or <.., PDV>), in both forms and at both block sizes, the
+// helpers of the revised form included.  RULE_DVX (bslv_lpq_set_pricing): what a batch launches while the switch is on, in the three
+// shapes plain, EXT and P1.  RULE_PDV (bslv_lpq_set_primal_pricing): what an objective batch launches while the switch is on, and a
+// PRIMAL / REPAIR batch while the dual rule is the default one; EXT and P1 only, primal steps live in the extended selection.  Kernels
+// of their own, with their LDS declared here and handed down (see SelShared), so that the ones above compile to what they always did.
+// k_select_cached has no such instance: with a switch on, the plan does not take it.  P1 is the tableau form alone: no helpers, and
+// no words of a row fetch in its LDS.
+// (the dynamic LDS of an instance under a name of its own, as the kernels above have it: with one name for all five the compiler no
+//  longer knows its address where a pointer to it is made, and the helper branch and the extended instances get other code)
+template <int RULE, bool P1, bool EXT> extern __shared__ unsigned char dyn_priced[];
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wundefined-var-template"      // (dynamic LDS has no definition)
+template <int RULE, bool P1, bool EXT>
+__global__ __launch_bounds__(NT_BIG) void k_select_priced(LpView L, BatchView Bv, NormView Nv, const int *active, int nact, int cap2, int nsel)
 {
-    __shared__ SelSharedDvx xs;
-    extern __shared__ unsigned char dyn_dvx[];
+    static_assert(RULE == RULE_DVX ? EXT || !P1 : RULE == RULE_PDV && EXT, "the five instances: DVX plain, EXT, P1; PDV EXT, P1");
+    __shared__ std::conditional_t<P1, SelShared, SelSharedDvx> xs;
+    unsigned char *const dyn = dyn_priced<RULE, P1, EXT>;
     if ((int)blockIdx.x >= nact) return;
     const int b = active[blockIdx.x];
-    if (blockIdx.y > 0) { rev_helper<true>(L, Bv, b, xs.rv, dyn_dvx); return; }
-    if (threadIdx.x == 0) xs.dyn = dyn_dvx;
+    if constexpr (!P1) if (blockIdx.y > 0) { rev_helper<true>(L, Bv, b, xs.rv, dyn); return; }
+    if (threadIdx.x == 0) xs.dyn = dyn;
     __syncthreads();
     for (int sdx = 0; sdx < nsel; sdx++) {
         if (sdx) __syncthreads();
-        if (!(EXT ? select_once_dvx_ext(L, Bv, b, cap2, &xs, &Dv) : select_once<false, false, true>(L, Bv, b, cap2, &xs, &Dv))) break;
+        if (!(EXT ? select_once_priced<RULE, P1>(L, Bv, b, cap2, &xs, &Nv) : select_once<false, false, true>(L, Bv, b, cap2, &xs, &Nv))) break;
     }
-    if (L.helpers > 1) {
+    if constexpr (!P1) if (L.helpers > 1) {
         __syncthreads();
         if (threadIdx.x == 0) __hip_atomic_store(&Bv.hmail[(size_t)b * 8], (L.launch_id << 8) | 0xFF, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
-__global__ __launch_bounds__(NT_BIG) void k_select_p1_dvx(LpView L, BatchView Bv, DvxView Dv, const int *active, int nact, int cap2, int nsel)
-{
-    __shared__ SelShared xs;
-    extern __shared__ unsigned char dyn_p1_dvx[];
-    if ((int)blockIdx.x >= nact) return;
-    const int b = active[blockIdx.x];
-    if (threadIdx.x == 0) xs.dyn = dyn_p1_dvx;
-    __syncthreads();
-    for (int sdx = 0; sdx < nsel; sdx++) {
-        if (sdx) __syncthreads();
-        if (!select_once_dvx_p1(L, Bv, b, cap2, &xs, &Dv)) break;
-    }
-}
+#pragma clang diagnostic pop
 
-// the reference norms of LP list[k] (nullptr: LP k) of the batch, k < n, back to 1: the start of a solve, and a refactorisation replay
-__global__ void k_dvx_ones(DvxView Dv, int Mp1p, const int *list, int n, int count)
+// the reference norms (rows of ld values) of LP list[k] (nullptr: LP k) of the batch, k < n, back to 1: the start of a solve, and a refactorisation replay
+__global__ void k_norm_ones(NormView Nv, int ld, const int *list, int n, int count)
 {
     if ((int)blockIdx.y >= n) return;
     const int b = list ? list[blockIdx.y] : (int)blockIdx.y;
-    double *s = Dv.snorm + (size_t)b * Mp1p;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < Mp1p; i += gridDim.x * blockDim.x) s[i] = 1.0;
-    if (count && blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&Dv.stat[2], 1);
-}
-
-// k_select<true> and k_select_p1 under primal Devex pricing (bslv_lpq_set_primal_pricing; select_once<.., PDV>): what an objective batch
-// launches while the switch is on, in both forms and at both block sizes, the helpers of the revised form included, and what a PRIMAL /
-// REPAIR batch launches while the dual rule is the default one.  Kernels of their own, as the DVX ones and for the same reason.
-__global__ __launch_bounds__(NT_BIG) void k_select_pdv(LpView L, BatchView Bv, PdvView Pv, const int *active, int nact, int cap2, int nsel)
-{
-    __shared__ SelSharedDvx xs;
-    extern __shared__ unsigned char dyn_pdv[];
-    if ((int)blockIdx.x >= nact) return;
-    const int b = active[blockIdx.x];
-    if (blockIdx.y > 0) { rev_helper<true>(L, Bv, b, xs.rv, dyn_pdv); return; }
-    if (threadIdx.x == 0) xs.dyn = dyn_pdv;
-    __syncthreads();
-    for (int sdx = 0; sdx < nsel; sdx++) {
-        if (sdx) __syncthreads();
-        if (!select_once_pdv_ext(L, Bv, b, cap2, &xs, &Pv)) break;
-    }
-    if (L.helpers > 1) {
-        __syncthreads();
-        if (threadIdx.x == 0) __hip_atomic_store(&Bv.hmail[(size_t)b * 8], (L.launch_id << 8) | 0xFF, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-    }
-}
-__global__ __launch_bounds__(NT_BIG) void k_select_p1_pdv(LpView L, BatchView Bv, PdvView Pv, const int *active, int nact, int cap2, int nsel)
-{
-    __shared__ SelShared xs;
-    extern __shared__ unsigned char dyn_p1_pdv[];
-    if ((int)blockIdx.x >= nact) return;
-    const int b = active[blockIdx.x];
-    if (threadIdx.x == 0) xs.dyn = dyn_p1_pdv;
-    __syncthreads();
-    for (int sdx = 0; sdx < nsel; sdx++) {
-        if (sdx) __syncthreads();
-        if (!select_once_pdv_p1(L, Bv, b, cap2, &xs, &Pv)) break;
-    }
-}
-// the reference norms of LP list[k] (nullptr: LP k) of the batch, k < n, back to 1: the start of a solve, and a refactorisation replay
-__global__ void k_pdv_ones(PdvView Pv, int ld, const int *list, int n, int count)
-{
-    if ((int)blockIdx.y >= n) return;
-    const int b = list ? list[blockIdx.y] : (int)blockIdx.y;
-    double *t = Pv.tnorm + (size_t)b * ld;
+    double *t = Nv.norm + (size_t)b * ld;
     for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < ld; j += gridDim.x * blockDim.x) t[j] = 1.0;
-    if (count && blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&Pv.stat[2], 1);
+    if (count && blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&Nv.stat[2], 1);
 }
 
 // ---- TIE PHASE (bslv_lpq_set_canonical): the canonical optimal basis of a primal degenerate LP ----
@@ -2797,6 +2750,15 @@ __global__ void k_per_resume(BatchView Bv, BatchView Rv, RfxView R, const int *d
 
 using namespace bslv;
 
+// What the engine keeps for a Devex rule: the reference norms and counters of a batch (NormView; allocated by the first batch that runs
+// under the rule, for Bcap LPs), the size of the last batch that ran under the rule (0: none did), the counters of the last solve call
+struct DevexNorms {
+    double *norm_d = nullptr; int *stat_d = nullptr; int Bcap = 0;
+    int B = 0;
+    long last[3] = {0, 0, 0};
+    NormView view() const { return NormView{norm_d, stat_d}; }
+};
+
 struct bslv_lpq {
     LpView L{};
     int slots = 0;
@@ -2848,21 +2810,12 @@ struct bslv_lpq {
     long last_ext[5] = {0, 0, 0, 0, 0};
     int method = BSLV_LP_METHOD_DUAL;  // bslv_lpq_set_method (BSLV_LP_METHOD at create)
     long last_p1[3] = {0, 0, 0};       // phase 1 of the last batch: LPs that entered it, its iterations, rebuilds of its pricing vector
-    // dual Devex pricing (bslv_lpq_set_pricing, BSLV_LP_PRICING at create): the rule, the reference norms and counters of a batch (allocated by
-    // the first batch that runs under the rule), the counters of the last solve call, the size of the last batch that ran under the rule (0: none did)
-    int pricing = BSLV_LP_PRICING_DANTZIG;
-    double *snorm_d = nullptr; int *dvxstat_d = nullptr; int snorm_Bcap = 0;
-    long last_dvx[3] = {0, 0, 0};
-    int snorm_B = 0;
-    size_t select_dvx_lds_max[3] = {64 * 1024, 64 * 1024, 64 * 1024};      // dynamic LDS of k_select_dvx<false>, k_select_dvx<true>, k_select_p1_dvx
-    // primal Devex pricing (bslv_lpq_set_primal_pricing, BSLV_LP_PRIMAL_PRICING at create): the same for the primal steps; pdv_dst: the
-    // slots of the LPs of the last batch that ran under the rule (bslv_lpq_last_primal_pricing_norms answers by variable)
-    int ppricing = BSLV_LP_PRICING_DANTZIG;
-    double *tnorm_d = nullptr; int *pdvstat_d = nullptr; int tnorm_Bcap = 0;
-    long last_pdv[3] = {0, 0, 0};
-    int tnorm_B = 0;
+    // dual Devex pricing (bslv_lpq_set_pricing, BSLV_LP_PRICING at create) and primal Devex pricing (bslv_lpq_set_primal_pricing,
+    // BSLV_LP_PRIMAL_PRICING at create): the rule and what the engine keeps for it (DevexNorms); pdv_dst: the slots of the LPs of the
+    // last batch that ran under the primal rule (bslv_lpq_last_primal_pricing_norms answers by variable)
+    int pricing = BSLV_LP_PRICING_DANTZIG, ppricing = BSLV_LP_PRICING_DANTZIG;
+    DevexNorms dvx, pdv;
     std::vector<int> pdv_dst;
-    size_t select_pdv_lds_max[2] = {64 * 1024, 64 * 1024};      // dynamic LDS of k_select_pdv, k_select_p1_pdv
     // tie phase (bslv_lpq_set_canonical): the switch, the direction (host / device), per-LP state of a batch, the counters of the last batch
     bool canonical = false;
     std::vector<double> canon_dir;
@@ -2902,9 +2855,8 @@ struct bslv_lpq {
     long last_rebuild[4] = {0, 0, 0, 0};
     long last_passes = 0;             // (LP, pass) pairs of the last batch: how many tableaux k_flush read and wrote
     long last_launches = 0;            // k_flush launches of the last batch: one per lock-step round + one per pass made on request (bslv_lpq_materialise)
-    size_t select_lds_max = 64 * 1024; // dynamic LDS of k_select<true> (candidate sort of the bound flipping ratio test)
-    size_t select0_lds_max = 64 * 1024; // ... of k_select<false> (revised form: rho)
-    size_t select1_lds_max = 64 * 1024; // ... of k_select_p1
+    // dynamic LDS (candidate sort of the bound flipping ratio test; revised form: rho) that each selection kernel may use so far, indexed as select_kernel is
+    size_t select_lds_max[3][3] = {{64 * 1024, 64 * 1024, 64 * 1024}, {64 * 1024, 64 * 1024, 64 * 1024}, {64 * 1024, 64 * 1024, 64 * 1024}};
     size_t price_lds_max = 64 * 1024;  // ... of k_rev_price (revised form, new objective: y)
     int obj_batches = 0;               // solve_batch_obj calls so far (BSLV_LP_OBJ_UNDEFINED counts them)
     bool has_boxed = false;            // some variable outside the per-LP range has two finite, non-artificial bounds
@@ -3221,7 +3173,8 @@ void bslv_lpq_destroy(bslv_lpq *h)
     period_free(h);
     auto fr = [](void *p) { if (p) (void)hipFree(p); };
     fr(h->raykind_d); fr(h->raystat_d); fr(h->ray_d); fr(h->lb_nst_d); fr(h->lb_xv_d);
-    fr(h->age_d); fr(h->age0_d); fr(h->cert_d); fr(h->snorm_d); fr(h->dvxstat_d); fr(h->tnorm_d); fr(h->pdvstat_d);
+    fr(h->age_d); fr(h->age0_d); fr(h->cert_d);
+    for (const DevexNorms *r : {&h->dvx, &h->pdv}) { fr(r->norm_d); fr(r->stat_d); }
     fr(h->L.T); fr(h->L.beta); fr(h->L.xN); fr(h->L.bh); fr(h->L.nh); fr(h->L.nstat); fr(h->L.pos);
     fr(h->Tstd); fr(h->lb_d); fr(h->ub_d); fr(h->art_d);
     fr(h->dbg_d); fr(h->list_d); fr(h->cptr_d); fr(h->cidx_d); fr(h->rptr_d); fr(h->ridx_d); fr(h->cval_d); fr(h->rval_d); fr(h->cost_d); fr(h->dsl_d); fr(h->trow_d); fr(h->uvec_d); fr(h->xfull_d); fr(h->hmail_d);
@@ -3592,13 +3545,32 @@ static void plan_init(bslv_lpq *h, int B, const int *src, InitPlan *plan)
 // How the selections of a batch are launched: plan_select decides once per solve_batch (every environment switch is read at every
 // solve: the tests change them between solves of one process), launch_select launches once per round
 struct SelectPlan {
-    bool ext; int cap2;     // the extended selection k_select<true>; its candidate arrays in LDS (0: rows too long for the in-LDS sort, no long-step part)
-    bool p1;                // ... with phase 1 in its primal steps (k_select_p1): the PRIMAL and REPAIR methods
+    const void *fn;         // the kernel of the batch (select_kernel), unless cpt names k_select_cached
+    bool helper_dim;        // its grid has the dimension of the revised form's helper workgroups (every shape but P1)
+    const DevexNorms *norms; // it takes the NormView of this record after the BatchView; nullptr: a kernel of the default rule
+    int cap2;               // the candidate arrays of an extended selection in LDS (0: a plain selection, or rows too long for the in-LDS sort: no long-step part)
     int nt, per_launch; size_t lds;     // threads per workgroup; selections per launch; dynamic LDS of a k_select launch
-    int cpt;                // columns per thread of k_select_cached (plain dual selection, tableau form, NT threads), 0: k_select
-    bool dvx;               // dual Devex pricing (bslv_lpq_set_pricing): the DVX instance of whichever of k_select<false>, k_select<true>, k_select_p1 the rest asks for; never k_select_cached
-    bool pdv;               // primal Devex pricing (bslv_lpq_set_primal_pricing): the PDV instance of k_select<true> or k_select_p1 (see pdv_batch)
+    int cpt;                // columns per thread of k_select_cached (plain dual selection of the default rule, tableau form, NT threads), 0: fn
 };
+// The selection kernels by rule (0: the default one, RULE_DVX, RULE_PDV) and shape; bslv_lpq::select_lds_max has the same indices
+enum { SHAPE_PLAIN, SHAPE_EXT, SHAPE_P1 };     // k_select<false>; the extended selection k_select<true>; ... with phase 1 in its primal steps (k_select_p1): the PRIMAL and REPAIR methods
+static const void *select_kernel(int rule, int shape)
+{
+    static const void *const k[3][3] = {
+        {(const void *)k_select<false>, (const void *)k_select<true>, (const void *)k_select_p1},
+        {(const void *)k_select_priced<RULE_DVX, false, false>, (const void *)k_select_priced<RULE_DVX, false, true>, (const void *)k_select_priced<RULE_DVX, true, true>},
+        {nullptr, (const void *)k_select_priced<RULE_PDV, false, true>, (const void *)k_select_priced<RULE_PDV, true, true>}};      // (primal steps live in the extended selection: without one the batch is refused, plan_select)
+    return k[rule][shape];
+}
+// the kernel of (rule, shape) may be launched with `want` bytes of dynamic LDS, its limit raised if need be
+static bool select_lds_fits(bslv_lpq *h, int rule, int shape, size_t want)
+{
+    size_t &lim = h->select_lds_max[rule][shape];
+    if (want <= lim) return true;
+    if (want <= 144 * 1024 && hipFuncSetAttribute(select_kernel(rule, shape), hipFuncAttributeMaxDynamicSharedMemorySize, (int)want) == hipSuccess) { lim = want; return true; }
+    (void)hipGetLastError();
+    return false;
+}
 // Which batches run under primal Devex pricing: objective batches whenever the primal rule is DEVEX (their steps are primal ones and the
 // dual rule does not reach them); PRIMAL / REPAIR batches (k_select_p1: tableau form) when the dual rule is DANTZIG -- with both rules on
 // they keep the dual-Devex instance, no instance carries both; DUAL-method batches never (their clean-up steps stay as they are)
@@ -3619,42 +3591,25 @@ static int plan_select(bslv_lpq *h, int B, const double *vlo, const double *vup,
         for (size_t k = 0; k < (size_t)B * L.vcnt && !bfrt; k++) bfrt = std::isfinite(vlo[k]) && std::isfinite(vup[k]) && vlo[k] < vup[k];
     if (getenv("BSLV_LP_EXT")) bfrt = p1 || atoi(getenv("BSLV_LP_EXT")) != 0;      // test hook: force the extended selection on / off
     const bool dvx = h->pricing == BSLV_LP_PRICING_DEVEX && !L.objmode;      // (objective batches make primal steps only: they keep the kernels they had)
-    // the kernel of an extended (ext) or plain selection and the dynamic LDS it may use so far
     const bool pdv = pdv_batch(h);
-    auto sel_kernel = [&](bool ext) -> const void * {
-        if (pdv) return p1 ? (const void *)k_select_p1_pdv : (const void *)k_select_pdv;      // (both are extended selections: without one the batch is refused below)
-        if (dvx) return p1 ? (const void *)k_select_p1_dvx : ext ? (const void *)k_select_dvx<true> : (const void *)k_select_dvx<false>;
-        return p1 ? (const void *)k_select_p1 : ext ? (const void *)k_select<true> : (const void *)k_select<false>;
-    };
-    auto sel_lds_max = [&](bool ext) -> size_t & {
-        if (pdv) return h->select_pdv_lds_max[p1 ? 1 : 0];
-        if (dvx) return h->select_dvx_lds_max[p1 ? 2 : ext ? 1 : 0];
-        return p1 ? h->select1_lds_max : ext ? h->select_lds_max : h->select0_lds_max;
-    };
+    const int rule = pdv ? RULE_PDV : dvx ? RULE_DVX : 0;
     int cap2 = 2;
     while (cap2 < L.N) cap2 <<= 1;
     size_t sel_lds = (size_t)cap2 * (sizeof(double) + sizeof(int)) + (size_t)L.N;
     if (bfrt && sel_lds > 144 * 1024) { cap2 = 0; sel_lds = (size_t)L.N; }     // rows too long for the in-LDS sort: extended selection without the long-step part
-    if (bfrt && sel_lds > sel_lds_max(true)) {
-        if (sel_lds <= 144 * 1024 && hipFuncSetAttribute(sel_kernel(true), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sel_lds) == hipSuccess) sel_lds_max(true) = sel_lds;
-        else bfrt = false;
-    }
+    if (bfrt && !select_lds_fits(h, rule, p1 ? SHAPE_P1 : SHAPE_EXT, sel_lds)) bfrt = false;
     if (p1 && !bfrt) { set_error("bslv_lpq_solve_batch: rows too long for the extended selection the primal method needs (N=%d)", L.N); return BSLV_E_CAPACITY; }
     if (L.objmode && !bfrt) { set_error("bslv_lpq_solve_batch_obj: rows too long for the extended selection (N=%d)", L.N); return BSLV_E_CAPACITY; }
+    const int shape = p1 ? SHAPE_P1 : bfrt ? SHAPE_EXT : SHAPE_PLAIN;      // (settled: the kernel whose limit is raised below is the kernel launched)
     // revised form: rho (a row of B^-1) in LDS behind the selection's own arrays, when there is room
     plan->lds = bfrt ? sel_lds : 0;
     L.rho_off = -1;
     if (L.rev) {
         const size_t off = bfrt ? (sel_lds + 15) / 16 * 16 : 0, want = off + (size_t)L.ldt * sizeof(double);
-        size_t &lim = sel_lds_max(bfrt);
-        bool ok = want <= lim;
-        if (!ok && want <= 144 * 1024) {
-            ok = hipFuncSetAttribute(sel_kernel(bfrt), hipFuncAttributeMaxDynamicSharedMemorySize, (int)want) == hipSuccess;
-            if (ok) lim = want; else (void)hipGetLastError();
-        }
-        if (ok) { L.rho_off = (int)off; plan->lds = want; }
+        if (select_lds_fits(h, rule, shape, want)) { L.rho_off = (int)off; plan->lds = want; }
     }
-    plan->ext = bfrt; plan->cap2 = bfrt ? cap2 : 0; plan->p1 = p1; plan->dvx = dvx; plan->pdv = pdv;
+    plan->fn = select_kernel(rule, shape); plan->helper_dim = !p1; plan->norms = pdv ? &h->pdv : dvx ? &h->dvx : nullptr;
+    plan->cap2 = bfrt ? cap2 : 0;
     // (measured, BSLV_SELECT_NT: S-degenerate, 2011 columns, 64 LPs per step: LP phase 67.6 / 52.0 / 46.6 ms with 256 / 512 / 1024 threads;
     //  S-degenerate-q4 to termination with 256 LPs per step 12.1 -> 10.4 s; same pivots)
     plan->nt = getenv("BSLV_SELECT_NT") ? atoi(getenv("BSLV_SELECT_NT")) : (L.N >= 1536 ? NT_BIG : NT);
@@ -3676,25 +3631,62 @@ static void launch_select(bslv_lpq *h, const SelectPlan &p, const BatchView &bv,
             helpers = std::max(1, std::min(std::min(hmax, (L.ld + 2047) / 2048), 256 / std::max(1, running)));
         }
         L.helpers = helpers; L.launch_id = (++h->launch_seq) & 0x3FFFFF;
-        if (p.pdv) {
-            const PdvView pv{h->tnorm_d, h->pdvstat_d};
-            if (p.p1) hipLaunchKernelGGL(k_select_p1_pdv, dim3(running), dim3(p.nt), p.lds, s, L, bv, pv, h->active_d, running, p.cap2, p.per_launch);
-            else hipLaunchKernelGGL(k_select_pdv, dim3(running, helpers), dim3(p.nt), p.lds, s, L, bv, pv, h->active_d, running, p.cap2, p.per_launch);
-        }
-        else if (p.dvx) {
-            const DvxView dv{h->snorm_d, h->dvxstat_d};
-            if (p.p1) hipLaunchKernelGGL(k_select_p1_dvx, dim3(running), dim3(p.nt), p.lds, s, L, bv, dv, h->active_d, running, p.cap2, p.per_launch);
-            else if (p.ext) hipLaunchKernelGGL(k_select_dvx<true>, dim3(running, helpers), dim3(p.nt), p.lds, s, L, bv, dv, h->active_d, running, p.cap2, p.per_launch);
-            else hipLaunchKernelGGL(k_select_dvx<false>, dim3(running, helpers), dim3(p.nt), p.lds, s, L, bv, dv, h->active_d, running, 0, p.per_launch);
-        }
-        else if (p.cpt == 2) hipLaunchKernelGGL(k_select_cached<2>, dim3(running), dim3(NT), 0, s, L, bv, h->active_d, running, p.per_launch);
+        if (p.cpt == 2) hipLaunchKernelGGL(k_select_cached<2>, dim3(running), dim3(NT), 0, s, L, bv, h->active_d, running, p.per_launch);
         else if (p.cpt == 4) hipLaunchKernelGGL(k_select_cached<4>, dim3(running), dim3(NT), 0, s, L, bv, h->active_d, running, p.per_launch);
         else if (p.cpt == 6) hipLaunchKernelGGL(k_select_cached<6>, dim3(running), dim3(NT), 0, s, L, bv, h->active_d, running, p.per_launch);
-        else if (p.p1) hipLaunchKernelGGL(k_select_p1, dim3(running), dim3(p.nt), p.lds, s, L, bv, h->active_d, running, p.cap2, p.per_launch);
-        else if (p.ext) hipLaunchKernelGGL(k_select<true>, dim3(running, helpers), dim3(p.nt), p.lds, s, L, bv, h->active_d, running, p.cap2, p.per_launch);
-        else hipLaunchKernelGGL(k_select<false>, dim3(running, helpers), dim3(p.nt), p.lds, s, L, bv, h->active_d, running, 0, p.per_launch);
+        else {
+            // (LpView, BatchView, [NormView,] active, nact, cap2, nsel)
+            NormView nv = p.norms ? p.norms->view() : NormView{};
+            void *priced[] = {&L, (void *)&bv, &nv, &h->active_d, &running, (void *)&p.cap2, (void *)&p.per_launch};
+            void *plain[] = {&L, (void *)&bv, &h->active_d, &running, (void *)&p.cap2, (void *)&p.per_launch};
+            (void)hipLaunchKernel(p.fn, dim3(running, p.helper_dim ? helpers : 1), dim3(p.nt), p.norms ? priced : plain, p.lds, s);
+        }
     }
 }
+// Devex pricing, the steps of a batch that keeps reference norms (rec: bslv_lpq::dvx with rows of ld = Mp1p values, ::pdv with ld = ld).
+// The start of a solve: room for the engine's largest batch, counters at zero, every norm at 1; rec.B = 0 for a batch not under the rule
+static int devex_begin(bslv_lpq *h, DevexNorms &rec, bool on, int B, int ld, hipStream_t s)
+{
+    rec.B = on ? B : 0;
+    if (!on) return 0;
+    if (rec.Bcap < h->Bcap) {
+        if (rec.norm_d) (void)hipFree(rec.norm_d);
+        rec.norm_d = nullptr; rec.Bcap = 0;
+        HIP_TRY(malloc0s(&rec.norm_d, (size_t)h->Bcap * ld * sizeof(double), s));
+        rec.Bcap = h->Bcap;
+    }
+    if (!rec.stat_d) HIP_TRY(malloc0s(&rec.stat_d, 4 * sizeof(int), s));
+    HIP_TRY(hipMemsetAsync(rec.stat_d, 0, 4 * sizeof(int), s));
+    hipLaunchKernelGGL(k_norm_ones, dim3((ld + 255) / 256, B), dim3(256), 0, s, rec.view(), ld, (const int *)nullptr, B, 0);
+    return 0;
+}
+// a new reference framework, counted, for the n LPs of the device list `due` (a refactorisation replay in the rounds)
+static void devex_reframe(bslv_lpq *h, const DevexNorms &rec, int ld, const int *due, int n)
+{
+    if (rec.B > 0) hipLaunchKernelGGL(k_norm_ones, dim3((ld + 255) / 256, n), dim3(256), 0, h->stream, rec.view(), ld, due, n, 1);
+}
+// the end of a solve: the batch's counters are added to those of the call (added: the rescue's solves count with the call)
+static int devex_collect(bslv_lpq *h, DevexNorms &rec)
+{
+    if (rec.B <= 0) return 0;
+    int ds[3];
+    HIP_TRY(hipMemcpy(ds, rec.stat_d, sizeof ds, hipMemcpyDeviceToHost));
+    for (int k = 0; k < 3; k++) rec.last[k] += ds[k];
+    return 0;
+}
+// the norms of a batch (what bslv_lpq_last_pricing_norms and .._primal_pricing_norms answer from) across the re-solves of a rescue, each
+// a batch of its own whose LP k is LP lps[k] of this one: kept on the host, the re-solved LPs' rows taken over, put back when all is done
+struct SavedNorms {
+    DevexNorms &rec; const int ld, B; std::vector<double> v;
+    SavedNorms(DevexNorms &r, int ld_) : rec(r), ld(ld_), B(r.B) {}
+    int save() { if (B > 0) { v.resize((size_t)B * ld); HIP_TRY(hipMemcpy(v.data(), rec.norm_d, v.size() * sizeof(double), hipMemcpyDeviceToHost)); } return 0; }
+    int take(const std::vector<int> &lps, int m)      // (after a re-solve of m LPs that ran under the rule)
+    {
+        if (B > 0 && rec.B == m) for (int k = 0; k < m; k++) HIP_TRY(hipMemcpy(&v[(size_t)lps[k] * ld], rec.norm_d + (size_t)k * ld, (size_t)ld * sizeof(double), hipMemcpyDeviceToHost));
+        return 0;
+    }
+    int restore() { if (B > 0) { HIP_TRY(hipMemcpy(rec.norm_d, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice)); rec.B = B; } return 0; }
+};
 static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, const double *vlo, const double *vup,
                             int cfirst, int ccnt, const double *cvals, int *status, int *iters);
 static int solve_batch_rescue(bslv_lpq *h, int B, const int *src, const int *dst, const double *vlo, const double *vup,
@@ -3838,9 +3830,8 @@ static int period_refactor(bslv_lpq *h, const BatchView &bv, int n, bool at_star
     hipLaunchKernelGGL(k_per_price, dim3((h->L.ld + REV_PRICE_SLICE - 1) / REV_PRICE_SLICE, n), dim3(NT), 0, s, h->L, bv, rv, (const int *)P.due, (const double *)h->cost_d, n);
     if ((rc = replay_refresh(h, rv, P.iota, n, pass))) return rc;
     hipLaunchKernelGGL(k_per_resume, dim3((n + 255) / 256), dim3(256), 0, s, bv, rv, rfx_view(h), (const int *)P.due, n, h->age0_d, P.res);
-    // dual Devex pricing: the replay may have moved heads between rows, so the LPs go on in a new reference framework (at the start they are in one)
-    if (h->tnorm_B > 0 && !at_start) hipLaunchKernelGGL(k_pdv_ones, dim3((h->L.ld + 255) / 256, n), dim3(256), 0, s, PdvView{h->tnorm_d, h->pdvstat_d}, h->L.ld, (const int *)P.due, n, 1);
-    if (h->snorm_B > 0 && !at_start) hipLaunchKernelGGL(k_dvx_ones, dim3((h->L.Mp1p + 255) / 256, n), dim3(256), 0, s, DvxView{h->snorm_d, h->dvxstat_d}, h->L.Mp1p, (const int *)P.due, n, 1);
+    // Devex pricing: the replay may have moved heads between rows, so the LPs go on in a new reference framework (at the start they are in one)
+    if (!at_start) { devex_reframe(h, h->pdv, h->L.ld, P.due, n); devex_reframe(h, h->dvx, h->L.Mp1p, P.due, n); }
     HIP_TRY(hipGetLastError());
     std::vector<int> due(n), res(n), nw(P.nwcap);
     HIP_TRY(hipMemcpyAsync(due.data(), P.due, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
@@ -4083,36 +4074,12 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
     }
     HIP_TRY(hipMemsetAsync(h->xstat_d, 0, 8 * sizeof(int), s));
     if (L.rfx) HIP_TRY(hipMemsetAsync(h->rmark_d, 0, (size_t)B * sizeof(int), s));
-    // dual Devex pricing: the reference norms of the batch (allocated by the first batch that runs under the rule) start at 1
+    // Devex pricing: the reference norms of the batch start at 1
     const bool dvx = h->pricing == BSLV_LP_PRICING_DEVEX && !L.objmode;
-    if (dvx) {
-        if (h->snorm_Bcap < h->Bcap) {
-            if (h->snorm_d) (void)hipFree(h->snorm_d);
-            h->snorm_d = nullptr; h->snorm_Bcap = 0;
-            HIP_TRY(malloc0s(&h->snorm_d, (size_t)h->Bcap * L.Mp1p * sizeof(double), s));
-            h->snorm_Bcap = h->Bcap;
-        }
-        if (!h->dvxstat_d) HIP_TRY(malloc0s(&h->dvxstat_d, 4 * sizeof(int), s));
-        HIP_TRY(hipMemsetAsync(h->dvxstat_d, 0, 4 * sizeof(int), s));
-    }
-    h->snorm_B = dvx ? B : 0;
-    // primal Devex pricing: likewise
     const bool pdv = pdv_batch(h);
-    if (pdv) {
-        if (h->tnorm_Bcap < h->Bcap) {
-            if (h->tnorm_d) (void)hipFree(h->tnorm_d);
-            h->tnorm_d = nullptr; h->tnorm_Bcap = 0;
-            HIP_TRY(malloc0s(&h->tnorm_d, (size_t)h->Bcap * L.ld * sizeof(double), s));
-            h->tnorm_Bcap = h->Bcap;
-        }
-        if (!h->pdvstat_d) HIP_TRY(malloc0s(&h->pdvstat_d, 4 * sizeof(int), s));
-        HIP_TRY(hipMemsetAsync(h->pdvstat_d, 0, 4 * sizeof(int), s));
-    }
-    h->tnorm_B = pdv ? B : 0;
+    if ((rc = devex_begin(h, h->dvx, dvx, B, L.Mp1p, s)) || (rc = devex_begin(h, h->pdv, pdv, B, L.ld, s))) return rc;
     BatchView bv = bview(h);
     bv.cvals = h->cvals_d;
-    if (pdv) hipLaunchKernelGGL(k_pdv_ones, dim3((L.ld + 255) / 256, B), dim3(256), 0, s, PdvView{h->tnorm_d, h->pdvstat_d}, L.ld, (const int *)nullptr, B, 0);
-    if (dvx) hipLaunchKernelGGL(k_dvx_ones, dim3((L.Mp1p + 255) / 256, B), dim3(256), 0, s, DvxView{h->snorm_d, h->dvxstat_d}, L.Mp1p, (const int *)nullptr, B, 0);
     const int tiles = (L.mrows + TR - 1) / TR;
     if (L.rev) hipLaunchKernelGGL(k_age_begin, dim3((B + 255) / 256), dim3(256), 0, s, bv, (const long long *)h->age_d, h->age0_d, B);      // the age of every LP's matrix: its parent's
     {   // (objective batches keep their own start; the revised form knows the dual method only: bslv_lpq_set_method)
@@ -4348,8 +4315,8 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
         P.list_inflight = false; P.pairs_inflight = false;      // (the readbacks above have waited for the stream)
     }
     { int xs[8]; HIP_TRY(hipMemcpy(xs, h->xstat_d, sizeof xs, hipMemcpyDeviceToHost)); for (int k = 0; k < 5; k++) h->last_ext[k] = xs[k]; for (int k = 0; k < 3; k++) h->last_p1[k] = xs[5 + k]; }
-    if (dvx) { int ds[3]; HIP_TRY(hipMemcpy(ds, h->dvxstat_d, sizeof ds, hipMemcpyDeviceToHost)); for (int k = 0; k < 3; k++) h->last_dvx[k] += ds[k]; }      // (added: the rescue's solves count with the call)
-    if (pdv) { int ds[3]; HIP_TRY(hipMemcpy(ds, h->pdvstat_d, sizeof ds, hipMemcpyDeviceToHost)); for (int k = 0; k < 3; k++) h->last_pdv[k] += ds[k]; h->pdv_dst.assign(dst, dst + B); }
+    if ((rc = devex_collect(h, h->dvx)) || (rc = devex_collect(h, h->pdv))) return rc;
+    if (pdv) h->pdv_dst.assign(dst, dst + B);
     if (h->profile) {
         double ms = 0;
         for (size_t e = 0; e < nev; e++) { float t = 0; (void)hipEventElapsedTime(&t, h->evpool[e].first, h->evpool[e].second); ms += t; }
@@ -4439,10 +4406,8 @@ static int solve_batch_rescue(bslv_lpq *h, int B, const int *src, const int *dst
         LpView &L = h->L;
         for (int k = 0; k < 4; k++) h->last_rfx[k] = 0;
         for (int k = 0; k < 4; k++) h->last_per[k] = 0;      // (solve_batch_impl adds to them: the rescue's solves count with the call)
-        for (int k = 0; k < 3; k++) h->last_dvx[k] = 0;
-        for (int k = 0; k < 3; k++) h->last_pdv[k] = 0;
+        for (DevexNorms *r : {&h->dvx, &h->pdv}) { r->B = 0; for (int k = 0; k < 3; k++) r->last[k] = 0; }
         for (int k = 0; k < 3; k++) h->last_ray[k] = 0;
-        h->snorm_B = 0; h->tnorm_B = 0;
         h->rmark_valid = false;
         L.rfx = (h->refactor_on && L.rev) ? 1 : 0;
         L.drift_b = -1; L.drift_p = -1;
@@ -4465,15 +4430,10 @@ static int solve_batch_rescue(bslv_lpq *h, int B, const int *src, const int *dst
     for (int k = 0; k < 5; k++) ext[k] = h->last_ext[k];
     for (int k = 0; k < 3; k++) p1[k] = h->last_p1[k];
     const int vc = L.vcnt;
-    // dual Devex pricing: the norms of the batch (bslv_lpq_last_pricing_norms) -- a re-solve is a batch of its own whose LP k is LP lps[k] of this one
-    std::vector<double> sn;
-    const int snB = h->snorm_B;
-    if (snB > 0) { sn.resize((size_t)snB * L.Mp1p); HIP_TRY(hipMemcpy(sn.data(), h->snorm_d, sn.size() * sizeof(double), hipMemcpyDeviceToHost)); }
-    // primal Devex pricing: likewise (the re-solve runs in the LP's own slot, so the slots of the batch stand)
-    std::vector<double> tn;
-    const int tnB = h->tnorm_B;
+    // Devex pricing: the norms of the batch (the re-solve runs in the LP's own slot, so the slots of the batch stand)
+    SavedNorms sn(h->dvx, L.Mp1p), tn(h->pdv, L.ld);
     const std::vector<int> tn_dst = h->pdv_dst;
-    if (tnB > 0) { tn.resize((size_t)tnB * L.ld); HIP_TRY(hipMemcpy(tn.data(), h->tnorm_d, tn.size() * sizeof(double), hipMemcpyDeviceToHost)); }
+    if ((rc = sn.save()) || (rc = tn.save())) return rc;
     for (int attempt = 0; attempt < RESCUE_MAX && !todo.empty(); attempt++) {
         const auto t0 = std::chrono::steady_clock::now();
         const int n = (int)todo.size();
@@ -4498,8 +4458,7 @@ static int solve_batch_rescue(bslv_lpq *h, int B, const int *src, const int *dst
         tot_upd += h->last_update_ms; tot_ms += h->last_total_ms;
         for (int k = 0; k < 5; k++) ext[k] += h->last_ext[k];
         for (int k = 0; k < 3; k++) p1[k] += h->last_p1[k];
-        if (snB > 0 && h->snorm_B == m) for (int k = 0; k < m; k++) HIP_TRY(hipMemcpy(&sn[(size_t)lps[k] * L.Mp1p], h->snorm_d + (size_t)k * L.Mp1p, (size_t)L.Mp1p * sizeof(double), hipMemcpyDeviceToHost));
-        if (tnB > 0 && h->tnorm_B == m) for (int k = 0; k < m; k++) HIP_TRY(hipMemcpy(&tn[(size_t)lps[k] * L.ld], h->tnorm_d + (size_t)k * L.ld, (size_t)L.ld * sizeof(double), hipMemcpyDeviceToHost));
+        if ((rc = sn.take(lps, m)) || (rc = tn.take(lps, m))) return rc;
         for (int k = 0; k < m; k++) {
             const int b = lps[k];
             if (iters) iters[b] += it2[k];
@@ -4512,8 +4471,8 @@ static int solve_batch_rescue(bslv_lpq *h, int B, const int *src, const int *dst
     h->last_update_ms = tot_upd; h->last_total_ms = tot_ms;
     for (int k = 0; k < 5; k++) h->last_ext[k] = ext[k];
     for (int k = 0; k < 3; k++) h->last_p1[k] = p1[k];
-    if (snB > 0) { HIP_TRY(hipMemcpy(h->snorm_d, sn.data(), sn.size() * sizeof(double), hipMemcpyHostToDevice)); h->snorm_B = snB; }
-    if (tnB > 0) { HIP_TRY(hipMemcpy(h->tnorm_d, tn.data(), tn.size() * sizeof(double), hipMemcpyHostToDevice)); h->tnorm_B = tnB; h->pdv_dst = tn_dst; }
+    if ((rc = sn.restore()) || (rc = tn.restore())) return rc;
+    if (tn.B > 0) h->pdv_dst = tn_dst;
     return 0;
 }
 int bslv_lpq_refactor(bslv_lpq *h, int n, const int *slots, int *status_out)
@@ -4769,16 +4728,16 @@ int bslv_lpq_get_pricing(const bslv_lpq *h) { return h ? h->pricing : BSLV_LP_PR
 int bslv_lpq_last_pricing_stats(const bslv_lpq *h, long out[3])
 {
     if (!h || !out) return BSLV_E_ARG;
-    for (int k = 0; k < 3; k++) out[k] = h->last_dvx[k];
+    for (int k = 0; k < 3; k++) out[k] = h->dvx.last[k];
     return 0;
 }
 int bslv_lpq_last_pricing_norms(bslv_lpq *h, int b, double *s)
 {
     if (!h || !s) { set_error("bslv_lpq_last_pricing_norms: bad argument"); return BSLV_E_ARG; }
-    if (h->snorm_B <= 0 || !h->snorm_d) { set_error("bslv_lpq_last_pricing_norms: the last solve call did not run under Devex pricing"); return BSLV_E_STATE; }
-    if (b < 0 || b >= h->snorm_B) { set_error("bslv_lpq_last_pricing_norms: LP %d of a batch of %d", b, h->snorm_B); return BSLV_E_ARG; }
+    if (h->dvx.B <= 0 || !h->dvx.norm_d) { set_error("bslv_lpq_last_pricing_norms: the last solve call did not run under Devex pricing"); return BSLV_E_STATE; }
+    if (b < 0 || b >= h->dvx.B) { set_error("bslv_lpq_last_pricing_norms: LP %d of a batch of %d", b, h->dvx.B); return BSLV_E_ARG; }
     HIP_TRY(hipStreamSynchronize(h->stream));
-    HIP_TRY(hipMemcpy(s, h->snorm_d + (size_t)b * h->L.Mp1p, (size_t)h->L.M * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(s, h->dvx.norm_d + (size_t)b * h->L.Mp1p, (size_t)h->L.M * sizeof(double), hipMemcpyDeviceToHost));
     return 0;
 }
 // The pricing rule of the primal steps (select_once<.., PDV>): see bslv_hip.h
@@ -4792,19 +4751,19 @@ int bslv_lpq_get_primal_pricing(const bslv_lpq *h) { return h ? h->ppricing : BS
 int bslv_lpq_last_primal_pricing_stats(const bslv_lpq *h, long out[3])
 {
     if (!h || !out) return BSLV_E_ARG;
-    for (int k = 0; k < 3; k++) out[k] = h->last_pdv[k];
+    for (int k = 0; k < 3; k++) out[k] = h->pdv.last[k];
     return 0;
 }
 int bslv_lpq_last_primal_pricing_norms(bslv_lpq *h, int b, double *t)
 {
     if (!h || !t) { set_error("bslv_lpq_last_primal_pricing_norms: bad argument"); return BSLV_E_ARG; }
-    if (h->tnorm_B <= 0 || !h->tnorm_d || (int)h->pdv_dst.size() != h->tnorm_B) { set_error("bslv_lpq_last_primal_pricing_norms: the last solve call did not run under primal Devex pricing"); return BSLV_E_STATE; }
-    if (b < 0 || b >= h->tnorm_B) { set_error("bslv_lpq_last_primal_pricing_norms: LP %d of a batch of %d", b, h->tnorm_B); return BSLV_E_ARG; }
+    if (h->pdv.B <= 0 || !h->pdv.norm_d || (int)h->pdv_dst.size() != h->pdv.B) { set_error("bslv_lpq_last_primal_pricing_norms: the last solve call did not run under primal Devex pricing"); return BSLV_E_STATE; }
+    if (b < 0 || b >= h->pdv.B) { set_error("bslv_lpq_last_primal_pricing_norms: LP %d of a batch of %d", b, h->pdv.B); return BSLV_E_ARG; }
     const LpView &L = h->L;
     HIP_TRY(hipStreamSynchronize(h->stream));
     // by position -> by variable: the heads of the LP's slot name the variable at every nonbasic position
     std::vector<double> tp(L.N); std::vector<int> nh(L.N);
-    HIP_TRY(hipMemcpy(tp.data(), h->tnorm_d + (size_t)b * L.ld, (size_t)L.N * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(tp.data(), h->pdv.norm_d + (size_t)b * L.ld, (size_t)L.N * sizeof(double), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(nh.data(), L.nh + (size_t)h->pdv_dst[b] * L.N, (size_t)L.N * sizeof(int), hipMemcpyDeviceToHost));
     for (int k = 0; k < L.M + L.N; k++) t[k] = 0.0;
     for (int j = 0; j < L.N; j++) if (nh[j] >= 0 && nh[j] < L.M + L.N) t[nh[j]] = tp[j];

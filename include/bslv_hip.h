@@ -411,7 +411,7 @@ int  bslv_lpq_last_phase1_stats(const bslv_lpq *h, long out[3]);
  * most one pivot, are the same.  Otherwise: same statuses and optimal values, other pivots, possibly another optimal basis.
  * Both forms, every method, extended selection on or off, canonical duals on or off.  Objective batches (solve_batch_obj: primal steps
  * only), the tie phases of the canonical switches and the replay's own selection never read the norms.  With the switch on a batch
- * runs kernel instances of its own (k_select_dvx, k_select_p1_dvx) and the plan does NOT take k_select_cached, the register-resident
+ * runs kernel instances of its own (k_select_priced<RULE_DVX, ..>) and the plan does NOT take k_select_cached, the register-resident
  * selection of narrow tableau-form batches; with it off nothing is allocated, nothing launched and no bit differs.  Any other rule is
  * BSLV_E_ARG.  BSLV_LP_PRICING=dantzig|devex sets the rule an engine is created with.
  * bslv_lpq_last_pricing_stats, of the last solve call: [0] dual selections made under the weighted rule, [1] of those, selections whose
@@ -440,7 +440,7 @@ int  bslv_lpq_last_pricing_norms(bslv_lpq *h, int b, double *s);
  *            LP of the batch, not to its slot: children do not inherit them.
  * With all t_j = 1 the rule IS the default one, bit for bit: the first primal selection of every solve, and every LP of at most one
  * primal selection, are the same.  Otherwise: same statuses and optimal values, other pivots, possibly another optimal basis.
- * WHICH BATCHES run under the rule (kernel instances of their own: k_select_pdv in both forms, k_select_p1_pdv):
+ * WHICH BATCHES run under the rule (kernel instances of their own: k_select_priced<RULE_PDV, ..>, in both forms):
  *   - objective batches whenever the primal rule is DEVEX, whatever the dual rule is;
  *   - PRIMAL / REPAIR batches when the primal rule is DEVEX and the dual rule (bslv_lpq_set_pricing) is DANTZIG.  With BOTH rules on
  *     such a batch keeps the dual-Devex instance: its primal steps are priced as before and the counters below read 0 -- no instance

@@ -18,6 +18,7 @@ from bensolve_amd.lp import P2Model, LpEngine, bounds_from_types
 pytestmark = pytest.mark.gpu
 RTOL = 1e-9
 OPTIMAL, UNDEFINED = 4, 3
+E_ARG = 2
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 #        m,   n,    q, seed, dense_cols, B
 CASES = {"main": (40, 300, 3, 5, 0, 24), "wide": (120, 6000, 3, 11, 6, 8)}
@@ -87,7 +88,7 @@ def _read(eng, model, slots):
     return dict(obj=eng.obj(slots).copy(), w=eng.dual(slots, model.w_first, model.q).copy(), y=eng.primal(slots, model.y_first, model.q).copy())
 
 
-def _first_generation(case, rev="1", hook=None, switch=None):
+def _first_generation(case, rev="1", hook=None, switch=None, pricing=None):
     """engine with the cold solve in slot 0 and the warm batch in slots 1..B; the hook (BSLV_LP_REV_DRIFT) covers the warm batch only"""
     p = _problem(case)
     model, B = p["model"], p["B"]
@@ -97,6 +98,8 @@ def _first_generation(case, rev="1", hook=None, switch=None):
         assert eng.lib.bslv_lpq_is_revised(eng.h) == int(rev)
         if switch is not None:
             assert eng.set_refactor(switch) == 0
+        if pricing is not None:
+            assert eng.set_pricing(pricing) == 0
         eng.reset_slot(0)
         st0, _ = eng.solve_batch([0], [0], np.full((1, model.r), -np.inf), p["ub"][:1])
         assert st0[0] == OPTIMAL, st0
@@ -340,6 +343,36 @@ def test_rescue_of_an_lp_the_cross_check_gives_up(case):
     eng.close()
 
 
+@pytest.mark.parametrize("case", ["main", "wide"])
+def test_rescue_under_dual_devex_keeps_the_batch_norms(case):
+    """dual Devex pricing (set_pricing(1)) with the rescue on: the re-solve of the one LP is a batch of 1 that overwrites the head of the
+    norm buffer, so the call saves the batch's norms before it and puts them back after, with the rescued LP's own in its place"""
+    import ctypes
+    p = _problem(case)
+    B, M = p["B"], p["model"].M
+    eng, st, it = _first_generation(case, switch=1, pricing=1)
+    assert np.all(st == OPTIMAL), st
+    assert eng.last_refactor_stats() == dict(refactorised=0, replay_pivots=0, rescued=0, failed=0)
+    ref = [eng.last_pricing_norms(k) for k in range(B)]
+    eng.close()
+    cand = np.nonzero(it >= 4)[0]
+    assert len(cand) > 0, it
+    b = int(cand[0])
+    eng, st, _ = _first_generation(case, hook="%d:%d" % (b, int(it[b]) // 2), switch=1, pricing=1)
+    assert np.all(st == OPTIMAL), st
+    got = [eng.last_pricing_norms(k) for k in range(B)]
+    for k in range(B):
+        if k != b:
+            assert _same_bits(got[k], ref[k]), k
+    assert got[b].shape == (M,) and np.all(np.isfinite(got[b])) and np.all(got[b] >= 1.0), got[b]
+    buf = np.empty(M)
+    eng.lib.bslv_lpq_last_pricing_norms.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+    assert eng.lib.bslv_lpq_last_pricing_norms(eng.h, B, buf.ctypes.data) == E_ARG      # (the batch's length, not the re-solve's 1)
+    stats = eng.last_refactor_stats()
+    assert stats["refactorised"] == 1 and stats["rescued"] == 1 and stats["failed"] == 0, stats
+    eng.close()
+
+
 # ---- other heads than a solve leaves: bslv_lpq_debug_swap_heads ----
 def _heads(eng, slot):
     return eng.get_inverse(slot, matrix=False)[0]
@@ -511,13 +544,15 @@ class _P1Model:
         self.y_first = M + n
 
 
-def _obj_chain(model, W, hook=None, switch=None):
+def _obj_chain(model, W, hook=None, switch=None, primal_pricing=None):
     B = len(W)
     with _env(BSLV_LP_REV="1", BSLV_LP_REFACTOR=None, BSLV_LP_REV_DRIFT=None):
         eng = LpEngine(model.M, model.N, model.L, model.lo, model.up, np.zeros(model.N + 1), 0, 0, B + 2)
         assert eng.lib.bslv_lpq_is_revised(eng.h) == 1
         if switch is not None:
             assert eng.set_refactor(switch) == 0
+        if primal_pricing is not None:
+            assert eng.set_primal_pricing(primal_pricing) == 0
         eng.reset_slot(0)
         st, _ = eng.solve_batch([0], [0], np.zeros((1, 0)), np.zeros((1, 0)))
         assert st[0] == OPTIMAL
@@ -528,12 +563,17 @@ def _obj_chain(model, W, hook=None, switch=None):
             st, it = eng.solve_batch_obj(np.zeros(B, np.int32), dst, model.y_first, W)
     out = dict(st=st.copy(), it=it.copy(), obj=eng.obj(dst).copy(), y=eng.primal(dst, model.y_first, model.q).copy(),
                u=eng.dual(dst, 0, model.m).copy(), stats=eng.last_refactor_stats())
+    if primal_pricing:
+        import ctypes
+        out["norms"] = [eng.last_primal_pricing_norms(k) for k in range(B)]
+        buf = np.empty(model.M + model.N)
+        eng.lib.bslv_lpq_last_primal_pricing_norms.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+        out["rc_past_the_batch"] = eng.lib.bslv_lpq_last_primal_pricing_norms(eng.h, B, buf.ctypes.data)
     eng.close()
     return out
 
 
-def test_rescue_in_an_objective_batch():
-    """the same through solve_batch_obj: one batch of P1(w) LPs as the dual variant of Benson's algorithm builds them"""
+def _obj_batch():
     m, n, q, seed = 40, 300, 3, 5
     rng = np.random.default_rng(seed)
     base = synth.covering_vlp(m, n, q, seed)
@@ -544,6 +584,13 @@ def test_rescue_in_an_objective_batch():
     B = 16
     W = rng.uniform(0.1, 1.0, size=(B, q))
     W /= W.sum(axis=1, keepdims=True)
+    return model, W
+
+
+def test_rescue_in_an_objective_batch():
+    """the same through solve_batch_obj: one batch of P1(w) LPs as the dual variant of Benson's algorithm builds them"""
+    model, W = _obj_batch()
+    B = len(W)
     ref = _obj_chain(model, W)
     assert np.all(ref["st"] == OPTIMAL), ref["st"]
     cand = np.nonzero(ref["it"] >= 4)[0]
@@ -562,6 +609,29 @@ def test_rescue_in_an_objective_batch():
     for res in (off, on):
         for k in ("obj", "y", "u"):
             assert _same_bits(res[k][others], ref[k][others]), k
+
+
+def test_rescue_under_primal_devex_in_an_objective_batch():
+    """primal Devex pricing (set_primal_pricing(1)) in the objective batch above, with the rescue on: the batch's norms -- per variable,
+    through the heads of each LP's own dst slot; 0 for a basic variable -- and its length survive the re-solve of the one LP"""
+    model, W = _obj_batch()
+    B = len(W)
+    ref = _obj_chain(model, W, switch=1, primal_pricing=1)
+    assert np.all(ref["st"] == OPTIMAL), ref["st"]
+    assert ref["stats"] == dict(refactorised=0, replay_pivots=0, rescued=0, failed=0)
+    cand = np.nonzero(ref["it"] >= 4)[0]
+    assert len(cand) > 0, ref["it"]
+    b = int(cand[0])
+    on = _obj_chain(model, W, hook="%d:%d" % (b, int(ref["it"][b]) // 2), switch=1, primal_pricing=1)
+    assert np.all(on["st"] == OPTIMAL), on["st"]
+    for k in range(B):
+        if k != b:
+            assert _same_bits(on["norms"][k], ref["norms"][k]), k
+    t = on["norms"][b]
+    assert t.shape == (model.M + model.N,) and np.all(np.isfinite(t)), t
+    assert int((t == 0).sum()) == model.M and int((t >= 1.0).sum()) == model.N, t      # (basic: 0; every nonbasic one at least 1)
+    assert on["rc_past_the_batch"] == E_ARG
+    assert on["stats"]["refactorised"] == 1 and on["stats"]["rescued"] == 1 and on["stats"]["failed"] == 0, on["stats"]
 
 
 # ---- end to end: the Benson driver and the command line with a rescue in every batch ----
