@@ -851,16 +851,19 @@ __device__ __forceinline__ void fetch_row_tableau(const LpView &L, const SelCtx 
 {
     for (int j = threadIdx.x; j < L.ld; j += (int)blockDim.x) c.row[j] = j < L.N ? virt_entry(c.T0[(size_t)r * L.ld + j], r, j, c.np, c.pd, c.prow0, c.pcol0, L.ld, L.Mp1p) : 0.0;
 }
-// revised form: rho = row r of B^-1, then one sparse product per column -- by this workgroup, or dealt in slices to it and its helpers
+// revised form: rho = row r of B^-1, then one sparse product per column -- by this workgroup, or dealt in slices to it and its helpers.
+// Two halves: rev_form_rho leaves rho of row r where the helpers look for it -- the place of the next pending row, prow0 + np * ldt, free
+// until k_flush reads it as row np -- and in the LDS copy at L.rho_off when there is one, and returns the copy to gather from (brow);
+// rev_row_of_rho makes the tableau row c.row[j] = -(rho . K[nh_j]) of whatever lies there.  The second half is shared with phase 1 of the revised form, whose pricing
+// vector is the row of a synthesised rho (phase1_prepare), and it is the one place where the mailbox protocol of the helpers is stated.
 // (XS: as rev_take_slices_in; xr: the request number, the late flag and the ticket, xdyn: the kernel's dynamic LDS)
 template <bool XS = false>
-__device__ __forceinline__ void fetch_row_revised(const LpView &L, const BatchView &Bv, const SelCtx &c, const int r, int *xr = nullptr, unsigned char *xdyn = nullptr)
+__device__ __forceinline__ const double *rev_form_rho(const LpView &L, const SelCtx &c, const int r, unsigned char *xdyn = nullptr)
 {
-    int *p_n, *p_late; unsigned char *dyn;
-    if constexpr (XS) { p_n = xr; p_late = xr + 2; dyn = xdyn; }
-    else { extern __shared__ unsigned char dyn_sel[]; __shared__ int l_n, l_late; p_n = &l_n; p_late = &l_late; dyn = dyn_sel; }
-    int &s_n = *p_n, &s_late = *p_late;
-    const int tid = threadIdx.x, NT = (int)blockDim.x, b = c.b, np = c.np, ldt = L.ldt;
+    unsigned char *dyn;
+    if constexpr (XS) dyn = xdyn;
+    else { extern __shared__ unsigned char dyn_sel[]; dyn = dyn_sel; }
+    const int tid = threadIdx.x, NT = (int)blockDim.x, np = c.np, ldt = L.ldt;
     double *brow_g = c.prow0 + (size_t)np * ldt;
     // rho also goes to LDS when it fits (ex09: 37 KB): the sparse products below gather from it ~200 000 times per selection
     double *srho = L.rho_off >= 0 ? reinterpret_cast<double *>(dyn + L.rho_off) : nullptr;
@@ -870,7 +873,16 @@ __device__ __forceinline__ void fetch_row_revised(const LpView &L, const BatchVi
         if (srho) srho[i] = v;
     }
     __syncthreads();
-    const double *brow = srho ? srho : brow_g;
+    return srho ? srho : brow_g;
+}
+template <bool XS = false>
+__device__ __forceinline__ void rev_row_of_rho(const LpView &L, const BatchView &Bv, const SelCtx &c, const double *brow, int *xr = nullptr)
+{
+    int *p_n, *p_late;
+    if constexpr (XS) { p_n = xr; p_late = xr + 2; }
+    else { __shared__ int l_n, l_late; p_n = &l_n; p_late = &l_late; }
+    int &s_n = *p_n, &s_late = *p_late;
+    const int tid = threadIdx.x, b = c.b, np = c.np;
     if (L.helpers <= 1) { rev_row_slice<XS>(L, brow, c.nh, c.row, 0, 1, XS ? xr + 3 : nullptr); return; }
     // hand the row out in slices (rev_take_slices): rho is in global memory (brow_g), the request goes out, this workgroup takes
     // slices like everyone else and then waits for the ones others took
@@ -904,6 +916,12 @@ __device__ __forceinline__ void fetch_row_revised(const LpView &L, const BatchVi
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");      // (the slices the others wrote)
     phase_mark(L, Bv, b, 12, tf);
     if (s_late) { rev_row_slice<XS>(L, brow, c.nh, c.row, 0, 1, XS ? xr + 3 : nullptr); __syncthreads(); }      // (never seen; the row is this workgroup's to deliver either way)
+}
+template <bool XS = false>
+__device__ __forceinline__ void fetch_row_revised(const LpView &L, const BatchView &Bv, const SelCtx &c, const int r, int *xr = nullptr, unsigned char *xdyn = nullptr)
+{
+    const double *brow = rev_form_rho<XS>(L, c, r, xdyn);
+    rev_row_of_rho<XS>(L, Bv, c, brow, xr);
 }
 // (TABLEAU: an instance that never sees the revised form -- k_select_p1 -- leaves its code, and the LDS it declares, out)
 template <bool TABLEAU = false, bool XS = false>
@@ -1016,7 +1034,14 @@ __device__ __forceinline__ int infeas_sign(double lo, double up, double bt)
 // is fetched).  With an infeasible row the LP is in phase 1 (true) and d1[j] = sum_i sg_i T[i][j] prices it -- T as it is after the pending
 // pivots.  d1 is rebuilt from the rows on entry, after a pass over the tableau (nothing pending) and when the last step moved a row
 // other than the leaving one across a bound (PF_P1_STALE); between those it follows every pivot like the reduced costs do (select_once).
-__device__ __forceinline__ bool phase1_prepare(const LpView &L, const BatchView &Bv, const SelCtx &c, int &pf, double *sg, double *d1, double *sv)
+// REV (k_select_p1_rev: a slot holds B^-1 and no tableau row to walk): with T[i][j] = -rho_i . K[nh_j] the same vector is ONE tableau row,
+// the one of the synthesised y1 = sum over the infeasible rows of sg_i rho_i (what rev_price_y does with the costs of an objective
+// batch): d1[j] = -(y1 . K[nh_j]).  A thread owns columns of B^-1 and adds the rows in ascending order, so the reads of a row are
+// coalesced and the sum has a fixed order; y1 lies where a pivot row's rho would (rev_form_rho) and its products take the pivot rows'
+// path, helpers included (rev_row_of_rho).  They write the LP's scratch row (c.row, free until the step fetches its pivot row), from
+// which d1 is copied.  The rebuild rule is the tableau form's.  (xr, xdyn: the LDS of the row fetch, see fetch_row_revised)
+template <bool REV = false>
+__device__ __forceinline__ bool phase1_prepare(const LpView &L, const BatchView &Bv, const SelCtx &c, int &pf, double *sg, double *d1, double *sv, int *xr = nullptr, unsigned char *xdyn = nullptr)
 {
     const int tid = threadIdx.x, NT = (int)blockDim.x, b = c.b, M = L.M;
     int ninf = 0;
@@ -1037,6 +1062,28 @@ __device__ __forceinline__ bool phase1_prepare(const LpView &L, const BatchView 
     }
     const bool enter = !(pf & PF_PHASE1);
     if (enter || (pf & PF_P1_STALE) || (c.np == 0 && !(pf & PF_P1_KEEP))) {
+        if constexpr (REV) {
+            unsigned long long tp = ((L.probe & 8) && b == 0) ? wall_clock64() : 0ull;      // (BSLV_REV_PROBE & 8: clock ticks and number of LP 0's rebuilds in dbg[14], dbg[15])
+            const int ldt = L.ldt;
+            double *y_g = c.prow0 + (size_t)c.np * ldt;
+            double *sy = L.rho_off >= 0 ? reinterpret_cast<double *>(xdyn + L.rho_off) : nullptr;
+            for (int col = tid; col < ldt; col += NT) {
+                double acc = 0.0;
+                if (col < M)
+                    for (int i = 0; i < M; i++) {
+                        const double s = sg[i];
+                        if (s != 0.0) acc += s * virt_entry_b(c.T0[(size_t)i * ldt + col], i, col, c.np, c.pd, c.prow0, c.pcol0, ldt, L.Mp1p);
+                    }
+                y_g[col] = acc;
+                if (sy) sy[col] = acc;
+            }
+            __syncthreads();
+            rev_row_of_rho<true>(L, Bv, c, sy ? sy : y_g, xr);
+            __syncthreads();
+            for (int j = tid; j < L.ld; j += NT) d1[j] = j < L.N ? c.row[j] : 0.0;
+            phase_mark(L, Bv, b, 14, tp);
+            if ((L.probe & 8) && b == 0 && tid == 0) Bv.dbg[15] += 1;
+        } else
         for (int j = tid; j < L.ld; j += NT) {
             double acc = 0.0;
             if (j < L.N)
@@ -1067,7 +1114,9 @@ __device__ __forceinline__ bool phase1_prepare(const LpView &L, const BatchView 
 // (DVX: the instances of dual Devex pricing, which hand in the LDS of a row fetch -- see fetch_row_revised)
 // (PDV: the instances of primal Devex pricing, bslv_lpq_set_primal_pricing -- see select_once.  They hand in their LDS as DVX does, and
 //  the entering column is the eligible one with the largest score / t_j instead of the largest score; Bland's rule takes no notice)
-template <bool P1, bool DVX = false, bool PDV = false>
+// (P1R, with P1: the instance of k_select_p1_rev, phase 1 in the revised form -- rows and columns come from fetch_row / fetch_col's revised
+//  variants, and it hands in the LDS of a row fetch as DVX does)
+template <bool P1, bool DVX = false, bool PDV = false, bool P1R = false>
 __device__ __forceinline__ bool primal_step(const LpView &L, const BatchView &Bv, const SelCtx &c, int &pf, const bool bland, double *sv, int *si,
                                             int &r, int &q, bool &below, double &pstep, int &rsig, int *xr = nullptr, unsigned char *xdyn = nullptr, const NormView *nv = nullptr)
 {
@@ -1079,7 +1128,7 @@ __device__ __forceinline__ bool primal_step(const LpView &L, const BatchView &Bv
     bool ph1 = false;
     if constexpr (P1) {
         double *d1 = Bv.dper + (size_t)b * L.ld;
-        ph1 = phase1_prepare(L, Bv, c, pf, c.pc, d1, sv);
+        ph1 = phase1_prepare<P1R>(L, Bv, c, pf, c.pc, d1, sv, xr, xdyn);
         if (ph1) dj = d1;
     }
     ValIdx ent{0.0, -1};
@@ -1148,7 +1197,7 @@ __device__ __forceinline__ bool primal_step(const LpView &L, const BatchView &Bv
     const int stq = c.nstat[q], kq = c.nh[q];
     const double dq = dj[q];
     const double dir = (stq == NS_U || (stq == NS_F && dq > 0.0)) ? -1.0 : 1.0;
-    fetch_col<P1>(L, c, q);
+    fetch_col<P1 && !P1R>(L, c, q);
     double cmax = 0.0;
     for (int i = tid; i < M; i += NT) cmax = fmax(cmax, fabs(pc[i]));
     cmax = block_max(cmax, sv);
@@ -1231,7 +1280,7 @@ __device__ __forceinline__ bool primal_step(const LpView &L, const BatchView &Bv
     below = !(lv.i & 1);                   // the leaving variable goes to its lower bound
     pstep = fabs(dq) * tstep / (1.0 + fabs(beta[M]));      // (what the step moves the objective by, relative: the ratio test's tolerance gives a degenerate step a length of 1e-9, not 0)
     if constexpr (P1) if (ph1) { pstep = fabs(dq) * tstep; if (tid == 0) atomicAdd(&Bv.xstat[6], 1); }      // (phase 1: by how much the sum of infeasibilities falls)
-    fetch_row<P1, DVX || PDV>(L, Bv, c, r, xr, xdyn);
+    fetch_row<P1 && !P1R, DVX || PDV || P1R>(L, Bv, c, r, xr, xdyn);
     return true;
 }
 // Bound flipping ratio test: sorted breakpoints of row r; a boxed candidate switches bound (sflag) while the row stays infeasible.  Returns the number of switches (the first of sidx)
@@ -1357,15 +1406,19 @@ struct SelSharedDvx : SelShared { int rv[3 + REV_HQ + 1]; };      // rv: request
 // phase 2 share them.  A dual pivot of the LP here, a refactorisation replay on the host side, start a new framework (all t_j = 1); bound
 // switches change nothing.  Instances of their own again (k_select_priced<RULE_PDV, ..>), which take the LDS of the DVX ones; no
 // instance carries both rules.
-template <bool EXT, bool P1 = false, bool DVX = false, bool PDV = false>
+// P1R (with P1 and the default rule): phase 1 in the revised form (bslv_lpq_solve_batch_method; k_select_p1_rev).  P1 alone stays the tableau
+// form's instance, with the revised form's code left out (TAB below).
+template <bool EXT, bool P1 = false, bool DVX = false, bool PDV = false, bool P1R = false>
 __device__ __forceinline__ bool select_once(const LpView &L, const BatchView &Bv, const int b, const int cap2, SelShared *xs = nullptr, const NormView *nv = nullptr)
 {
     static_assert(EXT || !P1, "phase 1 lives in the extended selection");
     static_assert(!(DVX && PDV) && (EXT || !PDV), "one rule per instance; primal steps live in the extended selection");
+    static_assert(!P1R || (P1 && !DVX && !PDV), "the revised form's phase 1 is an instance of the default rule");
     constexpr bool XS = P1 || DVX || PDV;     // the LDS comes from the kernel
+    constexpr bool TAB = P1 && !P1R;          // an instance that never sees the revised form
     double *sv; int *si; PivDesc *p_d; unsigned char *dyn;
     int *xr = nullptr;
-    if constexpr ((DVX || PDV) && !P1) xr = static_cast<SelSharedDvx *>(xs)->rv;      // (P1: tableau form only, no row fetch of the revised form)
+    if constexpr (((DVX || PDV) && !P1) || P1R) xr = static_cast<SelSharedDvx *>(xs)->rv;      // (P1 without P1R: tableau form only, no row fetch of the revised form)
     if constexpr (XS) { sv = xs->sv; si = xs->si; p_d = &xs->d; dyn = xs->dyn; }
     else {
         __shared__ double l_sv[NT_BIG / WAVE];
@@ -1416,7 +1469,7 @@ __device__ __forceinline__ bool select_once(const LpView &L, const BatchView &Bv
     double tq = 1.0;                         // ... the entering position's norm as it was (read by all, barriers before the update writes it)
 
     if (primal) {
-        if (!primal_step<P1, DVX, PDV>(L, Bv, c, pf, bland, sv, si, r, q, below, pstep, rsig, xr, dyn, nv)) return true;
+        if (!primal_step<P1, DVX, PDV, P1R>(L, Bv, c, pf, bland, sv, si, r, q, below, pstep, rsig, xr, dyn, nv)) return true;
         if constexpr (PDV) tq = tnorm[q];
     } else {
     // ---- dual simplex step ----
@@ -1454,7 +1507,7 @@ __device__ __forceinline__ bool select_once(const LpView &L, const BatchView &Bv
     r = best.i >> 1; below = best.i & 1;
     const double sgn = below ? 1.0 : -1.0;
     phase_mark(L, Bv, b, 0, tk);
-    fetch_row<P1, DVX || PDV>(L, Bv, c, r, xr, dyn);
+    fetch_row<TAB, DVX || PDV || P1R>(L, Bv, c, r, xr, dyn);
     phase_mark(L, Bv, b, 1, tk);
 
     // pass 0: row scale for the relative pivot tolerance
@@ -1511,7 +1564,7 @@ __device__ __forceinline__ bool select_once(const LpView &L, const BatchView &Bv
     }
     bool col_ready = primal;                                         // pc[] holds the entering column (primal steps fetch it first)
     unsigned long long tk2 = (L.probe & 8) ? wall_clock64() : 0ull;
-    if (!P1 && L.rev && !col_ready) { fetch_col(L, c, q); col_ready = true; }    // (the tableau form gathers its column in Phase D)
+    if (!TAB && L.rev && !col_ready) { fetch_col(L, c, q); col_ready = true; }    // (the tableau form gathers its column in Phase D)
     phase_mark(L, Bv, b, 5, tk2);
     double sr = 1.0;                                                 // dual Devex pricing: the leaving row's norm as it was (read by all before Phase D writes it)
     if constexpr (DVX) sr = snorm[r];
@@ -1523,7 +1576,7 @@ __device__ __forceinline__ bool select_once(const LpView &L, const BatchView &Bv
         // retry (bslv_lp.c:222-227: from the standard basis, an exact identity) takes over instead of a solve on a corrupted inverse -- or,
         // with bslv_lpq_set_refactor, the LP is marked and the call itself rebuilds the inverse from the heads and solves it again
         // (BSLV_LP_REV_DRIFT: the test hook that takes the check as failed at a given pivot of a given LP)
-        if (!P1 && L.rev && (!(fabs(trq - pc[r]) <= 1e-8 * (1.0 + fabs(trq))) || (b == L.drift_b && Bv.iters[b] + 1 == L.drift_p))) {
+        if (!TAB && L.rev && (!(fabs(trq - pc[r]) <= 1e-8 * (1.0 + fabs(trq))) || (b == L.drift_b && Bv.iters[b] + 1 == L.drift_p))) {
             Bv.status[b] = BSLV_LP_UNDEFINED; Bv.mode[b] = MODE_NONE;
             if (L.rfx) Bv.rmark[b] = 1;
             if (L.trace == b) printf("lp %d it %d: pivot element from the row %.17g, from the column %.17g: B^-1 has drifted\n", b, Bv.iters[b], trq, pc[r]);
@@ -1800,6 +1853,7 @@ __device__ __forceinline__ bool select_once_cached(const LpView &L, const BatchV
 // (the extended instance is a function of its own, as the compiler always had it: inlined into the 1024-thread kernel it spills 300 registers, called none)
 __device__ __noinline__ bool select_once_ext(const LpView &L, const BatchView &Bv, const int b, const int cap2) { return select_once<true>(L, Bv, b, cap2); }
 __device__ __noinline__ bool select_once_p1(const LpView &L, const BatchView &Bv, const int b, const int cap2, SelShared *xs) { return select_once<true, true>(L, Bv, b, cap2, xs); }
+__device__ __noinline__ bool select_once_p1_rev(const LpView &L, const BatchView &Bv, const int b, const int cap2, SelShared *xs) { return select_once<true, true, false, false, true>(L, Bv, b, cap2, xs); }
 // (Devex pricing: the extended and the phase-1 shape of either rule)
 template <int RULE, bool P1>
 __device__ __noinline__ bool select_once_priced(const LpView &L, const BatchView &Bv, const int b, const int cap2, SelShared *xs, const NormView *nv) { return select_once<true, P1, RULE == RULE_DVX, RULE == RULE_PDV>(L, Bv, b, cap2, xs, nv); }
@@ -1836,6 +1890,30 @@ __global__ __launch_bounds__(NT_BIG) void k_select_p1(LpView L, BatchView Bv, co
     for (int sdx = 0; sdx < nsel; sdx++) {
         if (sdx) __syncthreads();
         if (!select_once_p1(L, Bv, b, cap2, &xs)) break;
+    }
+}
+
+// k_select_p1 for the revised form: what a PRIMAL or REPAIR call of bslv_lpq_solve_batch_method launches there.  The extended selection
+// with phase 1, rows and columns by fetch_row / fetch_col's revised variants, the phase-1 pricing vector as the tableau row of a
+// synthesised rho (phase1_prepare<true>), helper workgroups for the sparse products as in k_select.  The default pricing rule only.  Like
+// the priced instances it declares its LDS itself -- the words of the revised form's row fetch with it -- and hands it down, under a
+// dynamic-LDS name of its own: the kernels above compile to what they always did.
+extern __shared__ unsigned char dyn_p1_rev[];
+__global__ __launch_bounds__(NT_BIG) void k_select_p1_rev(LpView L, BatchView Bv, const int *active, int nact, int cap2, int nsel)
+{
+    __shared__ SelSharedDvx xs;
+    if ((int)blockIdx.x >= nact) return;
+    const int b = active[blockIdx.x];
+    if (blockIdx.y > 0) { rev_helper<true>(L, Bv, b, xs.rv, dyn_p1_rev); return; }
+    if (threadIdx.x == 0) xs.dyn = dyn_p1_rev;
+    __syncthreads();
+    for (int sdx = 0; sdx < nsel; sdx++) {
+        if (sdx) __syncthreads();
+        if (!select_once_p1_rev(L, Bv, b, cap2, &xs)) break;
+    }
+    if (L.helpers > 1) {                       // every path of the LP's own workgroup ends here: the helpers may go
+        __syncthreads();
+        if (threadIdx.x == 0) __hip_atomic_store(&Bv.hmail[(size_t)b * 8], (L.launch_id << 8) | 0xFF, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
 
@@ -2716,6 +2794,9 @@ __global__ void k_per_y(LpView L, BatchView Bv, BatchView Rv, const int *due, co
 // The LP goes on: its TRUE reduced costs d_j = c[nh_j] - y . K[nh_j] from the rebuilt inverse, by column slices as k_rfx_price has
 // them, into the batch's dcur; a perturbed row keeps its offsets to the true one, dper_new = d_new + (dper_old - d_old).  Rv's dcur
 // gets the row too: k_rev_u, which runs on Rv next, takes beta[M] = d . x_N from there.  A replay that failed leaves the LP's vectors alone.
+// (An LP in phase 1 keeps its pricing vector d1 in dper, which is no perturbed cost row and must not be shifted like one: PF_PERT and
+// PF_PHASE1 exclude each other -- phase1_prepare clears the perturbation bits where it sets PF_PHASE1, and no perturbation starts from a
+// primal step -- so `pert` is false for it; k_per_resume has d1 rebuilt instead.)
 __global__ __launch_bounds__(NT) void k_per_price(LpView L, BatchView Bv, BatchView Rv, const int *due, const double *cost, int n)
 {
     const int k = blockIdx.y;
@@ -2741,6 +2822,9 @@ __global__ void k_per_resume(BatchView Bv, BatchView Rv, RfxView R, const int *d
     const int b = due[k];
     if (R.cnt[(size_t)k * 4 + 2] == RFX_RUN && Rv.status[k] == ST_RUNNING) {
         Bv.flushed[b] = 1; Bv.verified[b] = (Bv.verified[b] & 2) | 1;
+        // (phase 1, revised form: the replay has moved the basic variables to other rows; the signs and d1 are rebuilt from the new
+        // inverse before the next selection)
+        { const int pf = Bv.pflags[b]; if (pf & PF_PHASE1) Bv.pflags[b] = pf | PF_P1_STALE; }
         age0[b] = -(long long)Bv.iters[b];
         res[k] = R.cnt[(size_t)k * 4 + 1];
     } else { Bv.status[b] = BSLV_LP_UNDEFINED; Bv.mode[b] = MODE_NONE; res[k] = -1; }
@@ -2809,6 +2893,7 @@ struct bslv_lpq {
     double *cvals_d = nullptr; size_t cvals_cap = 0;     // objective coefficients of solve_batch_obj
     long last_ext[5] = {0, 0, 0, 0, 0};
     int method = BSLV_LP_METHOD_DUAL;  // bslv_lpq_set_method (BSLV_LP_METHOD at create)
+    int call_method = BSLV_LP_METHOD_DUAL;  // the method of the solve call in flight: `method`, or what bslv_lpq_solve_batch_method was given (the rescue's re-solves included)
     long last_p1[3] = {0, 0, 0};       // phase 1 of the last batch: LPs that entered it, its iterations, rebuilds of its pricing vector
     // dual Devex pricing (bslv_lpq_set_pricing, BSLV_LP_PRICING at create) and primal Devex pricing (bslv_lpq_set_primal_pricing,
     // BSLV_LP_PRIMAL_PRICING at create): the rule and what the engine keeps for it (DevexNorms); pdv_dst: the slots of the LPs of the
@@ -2856,7 +2941,7 @@ struct bslv_lpq {
     long last_passes = 0;             // (LP, pass) pairs of the last batch: how many tableaux k_flush read and wrote
     long last_launches = 0;            // k_flush launches of the last batch: one per lock-step round + one per pass made on request (bslv_lpq_materialise)
     // dynamic LDS (candidate sort of the bound flipping ratio test; revised form: rho) that each selection kernel may use so far, indexed as select_kernel is
-    size_t select_lds_max[3][3] = {{64 * 1024, 64 * 1024, 64 * 1024}, {64 * 1024, 64 * 1024, 64 * 1024}, {64 * 1024, 64 * 1024, 64 * 1024}};
+    size_t select_lds_max[3][4] = {{64 * 1024, 64 * 1024, 64 * 1024, 64 * 1024}, {64 * 1024, 64 * 1024, 64 * 1024, 64 * 1024}, {64 * 1024, 64 * 1024, 64 * 1024, 64 * 1024}};
     size_t price_lds_max = 64 * 1024;  // ... of k_rev_price (revised form, new objective: y)
     int obj_batches = 0;               // solve_batch_obj calls so far (BSLV_LP_OBJ_UNDEFINED counts them)
     bool has_boxed = false;            // some variable outside the per-LP range has two finite, non-artificial bounds
@@ -3546,20 +3631,22 @@ static void plan_init(bslv_lpq *h, int B, const int *src, InitPlan *plan)
 // solve: the tests change them between solves of one process), launch_select launches once per round
 struct SelectPlan {
     const void *fn;         // the kernel of the batch (select_kernel), unless cpt names k_select_cached
-    bool helper_dim;        // its grid has the dimension of the revised form's helper workgroups (every shape but P1)
+    bool helper_dim;        // its grid has the dimension of the revised form's helper workgroups (every shape but P1, the tableau form's alone)
     const DevexNorms *norms; // it takes the NormView of this record after the BatchView; nullptr: a kernel of the default rule
     int cap2;               // the candidate arrays of an extended selection in LDS (0: a plain selection, or rows too long for the in-LDS sort: no long-step part)
     int nt, per_launch; size_t lds;     // threads per workgroup; selections per launch; dynamic LDS of a k_select launch
     int cpt;                // columns per thread of k_select_cached (plain dual selection of the default rule, tableau form, NT threads), 0: fn
 };
 // The selection kernels by rule (0: the default one, RULE_DVX, RULE_PDV) and shape; bslv_lpq::select_lds_max has the same indices
-enum { SHAPE_PLAIN, SHAPE_EXT, SHAPE_P1 };     // k_select<false>; the extended selection k_select<true>; ... with phase 1 in its primal steps (k_select_p1): the PRIMAL and REPAIR methods
+// k_select<false>; the extended selection k_select<true>; ... with phase 1 in its primal steps, the PRIMAL and REPAIR methods: k_select_p1
+// in the tableau form, k_select_p1_rev in the revised form (the default rule only: plan_select gives such a batch no other)
+enum { SHAPE_PLAIN, SHAPE_EXT, SHAPE_P1, SHAPE_P1_REV };
 static const void *select_kernel(int rule, int shape)
 {
-    static const void *const k[3][3] = {
-        {(const void *)k_select<false>, (const void *)k_select<true>, (const void *)k_select_p1},
-        {(const void *)k_select_priced<RULE_DVX, false, false>, (const void *)k_select_priced<RULE_DVX, false, true>, (const void *)k_select_priced<RULE_DVX, true, true>},
-        {nullptr, (const void *)k_select_priced<RULE_PDV, false, true>, (const void *)k_select_priced<RULE_PDV, true, true>}};      // (primal steps live in the extended selection: without one the batch is refused, plan_select)
+    static const void *const k[3][4] = {
+        {(const void *)k_select<false>, (const void *)k_select<true>, (const void *)k_select_p1, (const void *)k_select_p1_rev},
+        {(const void *)k_select_priced<RULE_DVX, false, false>, (const void *)k_select_priced<RULE_DVX, false, true>, (const void *)k_select_priced<RULE_DVX, true, true>, nullptr},
+        {nullptr, (const void *)k_select_priced<RULE_PDV, false, true>, (const void *)k_select_priced<RULE_PDV, true, true>, nullptr}};      // (primal steps live in the extended selection: without one the batch is refused, plan_select)
     return k[rule][shape];
 }
 // the kernel of (rule, shape) may be launched with `want` bytes of dynamic LDS, its limit raised if need be
@@ -3579,28 +3666,34 @@ static bool pdv_batch(const bslv_lpq *h)
     const LpView &L = h->L;
     if (h->ppricing != BSLV_LP_PRICING_DEVEX) return false;
     if (L.objmode) return true;
-    return h->method != BSLV_LP_METHOD_DUAL && !L.rev && h->pricing != BSLV_LP_PRICING_DEVEX;
+    return h->call_method != BSLV_LP_METHOD_DUAL && !L.rev && h->pricing != BSLV_LP_PRICING_DEVEX;
 }
+// A PRIMAL / REPAIR batch of the revised form (bslv_lpq_solve_batch_method): k_select_p1_rev, the instance of the default rule, whatever
+// the two pricing switches say -- neither Devex rule has an instance for the revised form's phase 1, and both counter triples read 0
+static bool rev_p1_batch(const bslv_lpq *h) { return h->L.rev && !h->L.objmode && h->call_method != BSLV_LP_METHOD_DUAL; }
+// ... and the batches under dual Devex pricing (objective batches make primal steps only: they keep the kernels they had)
+static bool dvx_batch(const bslv_lpq *h) { return h->pricing == BSLV_LP_PRICING_DEVEX && !h->L.objmode && !rev_p1_batch(h); }
 static int plan_select(bslv_lpq *h, int B, const double *vlo, const double *vup, SelectPlan *plan)
 {
     LpView &L = h->L;
     // bound flipping ratio test only where a variable has two finite, non-artificial bounds
-    const bool p1 = h->method != BSLV_LP_METHOD_DUAL && !L.objmode && !L.rev;      // (objective batches keep their own start)
+    const bool p1 = h->call_method != BSLV_LP_METHOD_DUAL && !L.objmode;      // (objective batches keep their own start)
     bool bfrt = h->has_boxed || L.objmode || h->force_ext || p1;        // (the primal steps live in the extended selection)
     if (!bfrt && L.vcnt > 0)
         for (size_t k = 0; k < (size_t)B * L.vcnt && !bfrt; k++) bfrt = std::isfinite(vlo[k]) && std::isfinite(vup[k]) && vlo[k] < vup[k];
     if (getenv("BSLV_LP_EXT")) bfrt = p1 || atoi(getenv("BSLV_LP_EXT")) != 0;      // test hook: force the extended selection on / off
-    const bool dvx = h->pricing == BSLV_LP_PRICING_DEVEX && !L.objmode;      // (objective batches make primal steps only: they keep the kernels they had)
+    const bool dvx = dvx_batch(h);
     const bool pdv = pdv_batch(h);
     const int rule = pdv ? RULE_PDV : dvx ? RULE_DVX : 0;
     int cap2 = 2;
     while (cap2 < L.N) cap2 <<= 1;
     size_t sel_lds = (size_t)cap2 * (sizeof(double) + sizeof(int)) + (size_t)L.N;
     if (bfrt && sel_lds > 144 * 1024) { cap2 = 0; sel_lds = (size_t)L.N; }     // rows too long for the in-LDS sort: extended selection without the long-step part
-    if (bfrt && !select_lds_fits(h, rule, p1 ? SHAPE_P1 : SHAPE_EXT, sel_lds)) bfrt = false;
+    const int shape_p1 = L.rev ? SHAPE_P1_REV : SHAPE_P1;
+    if (bfrt && !select_lds_fits(h, rule, p1 ? shape_p1 : SHAPE_EXT, sel_lds)) bfrt = false;
     if (p1 && !bfrt) { set_error("bslv_lpq_solve_batch: rows too long for the extended selection the primal method needs (N=%d)", L.N); return BSLV_E_CAPACITY; }
     if (L.objmode && !bfrt) { set_error("bslv_lpq_solve_batch_obj: rows too long for the extended selection (N=%d)", L.N); return BSLV_E_CAPACITY; }
-    const int shape = p1 ? SHAPE_P1 : bfrt ? SHAPE_EXT : SHAPE_PLAIN;      // (settled: the kernel whose limit is raised below is the kernel launched)
+    const int shape = p1 ? shape_p1 : bfrt ? SHAPE_EXT : SHAPE_PLAIN;      // (settled: the kernel whose limit is raised below is the kernel launched)
     // revised form: rho (a row of B^-1) in LDS behind the selection's own arrays, when there is room
     plan->lds = bfrt ? sel_lds : 0;
     L.rho_off = -1;
@@ -3608,7 +3701,7 @@ static int plan_select(bslv_lpq *h, int B, const double *vlo, const double *vup,
         const size_t off = bfrt ? (sel_lds + 15) / 16 * 16 : 0, want = off + (size_t)L.ldt * sizeof(double);
         if (select_lds_fits(h, rule, shape, want)) { L.rho_off = (int)off; plan->lds = want; }
     }
-    plan->fn = select_kernel(rule, shape); plan->helper_dim = !p1; plan->norms = pdv ? &h->pdv : dvx ? &h->dvx : nullptr;
+    plan->fn = select_kernel(rule, shape); plan->helper_dim = shape != SHAPE_P1; plan->norms = pdv ? &h->pdv : dvx ? &h->dvx : nullptr;
     plan->cap2 = bfrt ? cap2 : 0;
     // (measured, BSLV_SELECT_NT: S-degenerate, 2011 columns, 64 LPs per step: LP phase 67.6 / 52.0 / 46.6 ms with 256 / 512 / 1024 threads;
     //  S-degenerate-q4 to termination with 256 LPs per step 12.1 -> 10.4 s; same pivots)
@@ -3990,6 +4083,16 @@ int bslv_lpq_lazy_stats(const bslv_lpq *h, long out[3])
 int bslv_lpq_solve_batch(bslv_lpq *h, int B, const int *src, const int *dst, const double *vlo,
                          const double *vup, int *status, int *iters)
 {
+    if (h) h->call_method = h->method;
+    return solve_batch_rescue(h, B, src, dst, vlo, vup, 0, 0, nullptr, status, iters);
+}
+// ... under `method` for this call only: see bslv_hip.h.  The engine's own method is neither read nor changed; in the revised form this
+// is the way to PRIMAL and REPAIR (k_select_p1_rev), which bslv_lpq_set_method refuses there.
+int bslv_lpq_solve_batch_method(bslv_lpq *h, int method, int B, const int *src, const int *dst, const double *vlo,
+                                const double *vup, int *status, int *iters)
+{
+    if (!h || method < BSLV_LP_METHOD_DUAL || method > BSLV_LP_METHOD_REPAIR) { set_error("bslv_lpq_solve_batch_method: bad argument (method %d)", method); return BSLV_E_ARG; }
+    h->call_method = method;
     return solve_batch_rescue(h, B, src, dst, vlo, vup, 0, 0, nullptr, status, iters);
 }
 // The LPs of the batch differ in their OBJECTIVE (lp_set_obj_coeffs + lp_solve, bslv_lp.c:141-151,219: what phase2_dual
@@ -4007,6 +4110,7 @@ int bslv_lpq_solve_batch_obj(bslv_lpq *h, int B, const int *src, const int *dst,
         cost_first = h->ps.map_var(cost_first);
     }
     for (size_t j = 0; j < h->cost.size(); j++) if (h->cost[j] != 0.0) { set_error("bslv_lpq_solve_batch_obj: the engine was created with a non-zero cost vector"); return BSLV_E_STATE; }
+    h->call_method = h->method;
     const int rc = solve_batch_rescue(h, B, src, dst, vlo, vup, cost_first, cost_cnt, costs, status, iters);
     ++h->obj_batches;
     // test hook BSLV_LP_OBJ_UNDEFINED=K:b -- LP b of the K-th objective batch of this engine is REPORTED as UNDEFINED (as when the pivot
@@ -4075,15 +4179,15 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
     HIP_TRY(hipMemsetAsync(h->xstat_d, 0, 8 * sizeof(int), s));
     if (L.rfx) HIP_TRY(hipMemsetAsync(h->rmark_d, 0, (size_t)B * sizeof(int), s));
     // Devex pricing: the reference norms of the batch start at 1
-    const bool dvx = h->pricing == BSLV_LP_PRICING_DEVEX && !L.objmode;
+    const bool dvx = dvx_batch(h);
     const bool pdv = pdv_batch(h);
     if ((rc = devex_begin(h, h->dvx, dvx, B, L.Mp1p, s)) || (rc = devex_begin(h, h->pdv, pdv, B, L.ld, s))) return rc;
     BatchView bv = bview(h);
     bv.cvals = h->cvals_d;
     const int tiles = (L.mrows + TR - 1) / TR;
     if (L.rev) hipLaunchKernelGGL(k_age_begin, dim3((B + 255) / 256), dim3(256), 0, s, bv, (const long long *)h->age_d, h->age0_d, B);      // the age of every LP's matrix: its parent's
-    {   // (objective batches keep their own start; the revised form knows the dual method only: bslv_lpq_set_method)
-        const int method = (L.objmode || L.rev) ? BSLV_LP_METHOD_DUAL : h->method;
+    {   // (objective batches keep their own start; both forms take the call's method: the engine's own, or bslv_lpq_solve_batch_method's)
+        const int method = L.objmode ? BSLV_LP_METHOD_DUAL : h->call_method;
         if (method == BSLV_LP_METHOD_PRIMAL) hipLaunchKernelGGL(k_prep<BSLV_LP_METHOD_PRIMAL>, dim3(B), dim3(NT), 0, s, L, bv, B);
         else if (method == BSLV_LP_METHOD_REPAIR) hipLaunchKernelGGL(k_prep<BSLV_LP_METHOD_REPAIR>, dim3(B), dim3(NT), 0, s, L, bv, B);
         else hipLaunchKernelGGL(k_prep<BSLV_LP_METHOD_DUAL>, dim3(B), dim3(NT), 0, s, L, bv, B);
@@ -4336,6 +4440,7 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
         const double n = (double)std::max<unsigned long long>(dg[7], 1) * 100.0;       // ticks of 10 ns -> us per selection
         fprintf(stderr, "lp select phases (LP 0, %llu selections, us each): leaving row %.1f | tableau row %.1f | row scale + candidates %.1f | Harris pass %.1f | pivot choice %.1f | column %.1f | descriptor + vector updates %.1f\n",
                 dg[7], dg[0] / n, dg[1] / n, dg[2] / n, dg[3] / n, dg[4] / n, dg[5] / n, dg[6] / n);
+        if (L.rev && dg[15]) fprintf(stderr, "   phase-1 pricing vector of LP 0 (revised form): %llu rebuilds, %.1f us each, %.3f ms in all\n", dg[15], dg[14] / (dg[15] * 100.0), dg[14] / 1e5);
         if (L.rev) fprintf(stderr, "   tableau row with helpers: rho + release fence %.1f | request %.1f | own slices %.1f | wait for the others %.1f | acquire fence %.1f; slices taken by the LP's own workgroup %.2f of %d\n", dg[8] / n, dg[9] / n, dg[10] / n, dg[11] / n, dg[12] / n, dg[13] * 100.0 / n, (L.ld + 2047) / 2048);
     }
     {

@@ -168,6 +168,22 @@ class LpEngine:
                                             vup.ctypes.data, status.ctypes.data, iters.ctypes.data))
         return status, iters
 
+    def solve_batch_method(self, method, src, dst, vlo, vup):
+        """solve_batch under `method` (0 dual, 1 primal, 2 repair) for this call only; the engine's own method stays what it is.  In the
+        revised form the only way to PRIMAL and REPAIR (bslv_lpq_solve_batch_method)."""
+        src = np.ascontiguousarray(src, np.int32)
+        dst = np.ascontiguousarray(dst, np.int32)
+        B = len(src)
+        vlo = np.ascontiguousarray(vlo, np.float64).reshape(B, self.vcnt)
+        vup = np.ascontiguousarray(vup, np.float64).reshape(B, self.vcnt)
+        status = np.empty(B, np.int32)
+        iters = np.empty(B, np.int32)
+        self.lib.bslv_lpq_solve_batch_method.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 6
+        self.lib.bslv_lpq_solve_batch_method.restype = ctypes.c_int
+        check(self.lib.bslv_lpq_solve_batch_method(self.h, int(method), B, src.ctypes.data, dst.ctypes.data, vlo.ctypes.data,
+                                                   vup.ctypes.data, status.ctypes.data, iters.ctypes.data))
+        return status, iters
+
     def solve_batch_obj(self, src, dst, cost_first, costs, vlo=None, vup=None):
         """LPs that differ in the objective: costs[b, t] on variable cost_first + t (bslv_lpq_solve_batch_obj)."""
         src = np.ascontiguousarray(src, np.int32)

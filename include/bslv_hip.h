@@ -235,6 +235,23 @@ int  bslv_lpq_reset_slot(bslv_lpq *h, int slot);
  * iters[b] the number of dual-simplex pivots.  Any of status/iters may be NULL. */
 int  bslv_lpq_solve_batch(bslv_lpq *h, int B, const int *src, const int *dst,
                           const double *vlo, const double *vup, int *status, int *iters);
+/* solve_batch under `method` (BSLV_LP_METHOD_DUAL / _PRIMAL / _REPAIR, see bslv_lpq_set_method) for THIS call only; the engine's own
+ * method (bslv_lpq_set_method) is neither read nor changed.  Both forms.  What a retry or a re-solve for a ray wants: another method
+ * for one call, not for the engine.
+ *   Tableau form  the call IS set_method(method); solve_batch(..); set_method(old), bit for bit: statuses, iters, slots, getters and
+ *                 every last_* statistic.
+ *   Revised form  DUAL is solve_batch bit for bit.  PRIMAL and REPAIR mean what bslv_lpq_set_method says of them: the start of
+ *                 primal_start_status, phase 1 by the sum of infeasibilities with the Harris test of oracle/lp_dense.c primal_simplex,
+ *                 then primal steps on the true reduced costs; they imply the extended selection.  This call is the only way to them
+ *                 there: set_method and BSLV_LP_METHOD stay what they were.  The phase-1 pricing vector of a slot that holds B^-1 is the
+ *                 tableau row of a synthesised rho, y1 = sum of +-(row i of B^-1) over the infeasible rows, rebuilt when the tableau
+ *                 form rebuilds its own (last_phase1_stats[2]) and after a periodic refactorisation of an LP in phase 1.  Such a batch
+ *                 runs the kernel instance of the DEFAULT pricing rule (k_select_p1_rev) whatever the two pricing switches say.
+ * method outside 0..2, or h == NULL: BSLV_E_ARG, nothing changed.  bslv_lpq_last_phase1_stats, last_stats, last_ext_stats, last_passes,
+ * last_period_stats and the ages cover the call as they cover a solve_batch; the in-call rescue (bslv_lpq_set_refactor) re-solves under
+ * the call's method. */
+int  bslv_lpq_solve_batch_method(bslv_lpq *h, int method, int B, const int *src, const int *dst,
+                                 const double *vlo, const double *vup, int *status, int *iters);
 /* The LPs of the batch differ in their OBJECTIVE (lp_set_obj_coeffs + lp_solve, bslv_lp.c:141-151, 219-259, as phase2_dual
  * drives them, bslv_algs.c:1469-1477): cost costs[b*cost_cnt + t] on variable cost_first + t, zero elsewhere (the engine must
  * have been created with a zero cost vector).  LP b starts from the basis of slot src[b], which has to be primal feasible
@@ -311,7 +328,8 @@ int bslv_lpq_debug_poke(bslv_lpq *h, int slot, int what, int var, double delta);
  * TWO CONCLUSIONS STORE NOTHING (kind NONE, counted in last_ray_stats[2]):
  *   - UNBOUNDED on an active artificial bound (the dual method found no violated row while a nonbasic variable with a non-zero reduced
  *     cost sits on an artificial bound).  The engine never looked for a ray there, and a single column is in general not a ray.  A
- *     caller who needs the ray re-solves the LP under BSLV_LP_METHOD_PRIMAL.
+ *     caller who needs the ray re-solves the LP under BSLV_LP_METHOD_PRIMAL (bslv_lpq_set_method; in the revised form, and for one
+ *     call in either form, bslv_lpq_solve_batch_method).
  *   - the empty box a folded row left (solve_batch answers INFEASIBLE without touching a slot).
  * bslv_lpq_get_ray answers in the indices of the model AS GIVEN: kind[b] and, unless ray == NULL, ray[b * (M + N) ..] of slot[b] (zeros
  * for NONE).  With folded rows a column entry z_j whose needed bound came from folded row i (coefficient a_ij) moves to that row:
@@ -389,8 +407,10 @@ int  bslv_lpq_get_extended(const bslv_lpq *h);
  *   REPAIR  the dual simplex, except that an LP whose start is dual infeasible is started as under PRIMAL instead of coming back
  *           UNDEFINED (GLP_DUALP: "dual, and primal if it fails").
  * Both imply the extended selection (the primal steps live there).  Objective batches (solve_batch_obj) keep their own start.
- * Not for the revised form: there a method other than DUAL is BSLV_E_ARG.  BSLV_LP_METHOD=dual|primal|repair sets the method an
- * engine is created with (ignored by an engine that comes up in the revised form).
+ * Not for the revised form: there a method other than DUAL is BSLV_E_ARG here, and the engine-wide method stays DUAL.  The revised
+ * form does have PRIMAL and REPAIR, per call: bslv_lpq_solve_batch_method, in both forms, solves one batch under a method of its own
+ * and leaves this one alone.  (Still open: an engine-wide PRIMAL / REPAIR default for the revised form, here and through BSLV_LP_METHOD.)
+ * BSLV_LP_METHOD=dual|primal|repair sets the method an engine is created with (ignored by an engine that comes up in the revised form).
  * bslv_lpq_last_phase1_stats, of the last solve_batch: [0] LPs that entered phase 1, [1] phase-1 iterations (pivots + bound
  * switches), [2] rebuilds of the phase-1 pricing vector from the tableau rows (it is otherwise updated with every pivot). */
 enum { BSLV_LP_METHOD_DUAL = 0, BSLV_LP_METHOD_PRIMAL = 1, BSLV_LP_METHOD_REPAIR = 2 };
@@ -417,6 +437,8 @@ int  bslv_lpq_last_phase1_stats(const bslv_lpq *h, long out[3]);
  * bslv_lpq_last_pricing_stats, of the last solve call: [0] dual selections made under the weighted rule, [1] of those, selections whose
  * row is not the row of the largest violation, [2] new reference frameworks after the start (one per primal or phase-1 pivot, one per
  * LP and refactorisation replay during the rounds).  All 0 with the switch off.
+ * REVISED FORM, PRIMAL / REPAIR (bslv_lpq_solve_batch_method): no Devex instance carries the revised form's phase 1.  Such a batch runs
+ * the instance of the default rule whatever this switch says -- the bits of the switch off -- and the counters read 0.
  * bslv_lpq_last_pricing_norms (for tests): s_0 .. s_(M-1) of LP b of the last batch, M rows of the engine's OWN model (the given rows
  * less bslv_lpq_rows_folded); BSLV_E_STATE if the last solve call did not run under DEVEX, BSLV_E_ARG for b outside the batch. */
 enum { BSLV_LP_PRICING_DANTZIG = 0, BSLV_LP_PRICING_DEVEX = 1 };
@@ -445,7 +467,9 @@ int  bslv_lpq_last_pricing_norms(bslv_lpq *h, int b, double *s);
  *   - PRIMAL / REPAIR batches when the primal rule is DEVEX and the dual rule (bslv_lpq_set_pricing) is DANTZIG.  With BOTH rules on
  *     such a batch keeps the dual-Devex instance: its primal steps are priced as before and the counters below read 0 -- no instance
  *     carries both rules;
- *   - DUAL-method batches never: their primal clean-up steps stay as they are.
+ *   - DUAL-method batches never: their primal clean-up steps stay as they are;
+ *   - PRIMAL / REPAIR batches of the REVISED form (bslv_lpq_solve_batch_method) never, under either switch: no Devex instance carries
+ *     the revised form's phase 1, the batch runs the instance of the default rule and both counter triples read 0.
  * The tie phases of the canonical switches and the replay's own selection never read or write the norms.  With the switch off nothing
  * is allocated, nothing launched and no bit differs.  Any other rule is BSLV_E_ARG; both forms accept the call.
  * BSLV_LP_PRIMAL_PRICING=dantzig|devex sets the rule an engine is created with (so the Benson and VLP drivers and bensolve_hip get it
