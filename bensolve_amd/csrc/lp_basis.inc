@@ -357,7 +357,7 @@ int bslv_lpq_rebuild(bslv_lpq *h, int n, const int *slots, int *status_out)
         HIP_TRY(hipMemcpy(nw.data(), h->nwork_d, nw.size() * sizeof(int), hipMemcpyDeviceToHost));
         long passes = 0;
         for (int v : nw) passes += v;
-        h->last_rebuild[0] = h->last_rfx[0]; h->last_rebuild[1] = h->last_rfx[1]; h->last_rebuild[2] = passes; h->last_rebuild[3] = h->last_rfx[3];
+        h->last_rebuild[0] = h->last.rfx[0]; h->last_rebuild[1] = h->last.rfx[1]; h->last_rebuild[2] = passes; h->last_rebuild[3] = h->last.rfx[3];
         return 0;
     }
     // a slot whose pass is parked or pending gets its tableau first; then its own basis is read back: every variable keeps its

@@ -1991,12 +1991,14 @@ __global__ void k_norm_ones(NormView Nv, int ld, const int *list, int n, int cou
 // the LPs that ended OPTIMAL (an LP is ST_RUNNING again while it is in the phase, so that the pass kernels treat it as they treat any LP
 // that still pivots) -- the kernels of a solve without the switch are not touched.
 constexpr int TIE_NEW = 0, TIE_RUN = 1, TIE_DONE = 2;      // TieView::state
+// one view for this phase and for the tie phase of an objective batch below (after the semicolon: what the member is there)
 struct TieView {
-    const double *dir;      // [vcnt] direction of the shift, per variable of the per-LP range
-    double *g;              // [B][Mp1p] d beta / d t
-    int *state, *iters;     // [B] TIE_*; tie pivots of the LP
-    int *stat;              // [4] LPs that entered the phase, tie pivots, LPs that ended without an entering candidate, LPs that gave up at the cap
-    int cap;                // tie pivots per LP
+    const double *dir;      // [vcnt] direction of the shift, per variable of the per-LP range; [ccnt] ddir, per variable of the cost range
+    double *g;              // [B][Mp1p] d beta / d t; [B][ld] reduced-cost row of ddir
+    int *state, *iters;     // [B] TIE_*; tie pivots of the LP; tie iterations (pivots + bound switches)
+    int *stat;              // [4] LPs that entered the phase, tie pivots (iterations), LPs that ended without an entering candidate (on a column
+                            // without a blocking row), LPs that gave up at the cap
+    int cap;                // tie pivots (iterations) per LP
 };
 __device__ __forceinline__ double tie_shift(const LpView &L, const TieView &Tv, int k)
 {
@@ -2136,17 +2138,10 @@ __global__ __launch_bounds__(NT_BIG) void k_select_tie(LpView L, BatchView Bv, T
 // along the optimal face, beta, x_N and the objective (by at most TOL_DJ x step) follow as in any primal step, and the step is an
 // ordinary PivDesc for k_flush, lazy tableaux, parked passes and warm starts.  The phase ends OPTIMAL in every case: no wrong tied
 // column (canonical), an entering column without a blocking row (ddir . x is unbounded on the optimal face: the basis reached stays), or
-// the cap on its iterations -- after conclude_optimal's recomputation of beta where the solve has made that many pivots.
-struct TieObjView {
-    const double *dir;      // [ccnt] ddir, per variable of the cost range
-    double *g;              // [B][ld] reduced-cost row of ddir
-    int *state, *iters;     // [B] TIE_*; tie iterations (pivots + bound switches) of the LP
-    int *stat;              // [4] LPs that entered the phase, tie iterations, LPs that ended on a column without a blocking row, LPs that gave up at the cap
-    int cap;                // tie iterations per LP
-};
+// the cap on its iterations -- after conclude_optimal's recomputation of beta where the solve has made that many pivots.  (TieView: above)
 // the phase of LP b ends (why: the counter of Tv.stat that says so, or -1) -- on a recomputed beta by conclude_optimal's rule: false when
 // the LP waits for that pass first (the selection after it comes to the same end)
-__device__ __forceinline__ bool tie_obj_finish(const BatchView &Bv, const TieObjView &Tv, const int b, const int why)
+__device__ __forceinline__ bool tie_obj_finish(const BatchView &Bv, const TieView &Tv, const int b, const int why)
 {
     const int verified = Bv.verified[b], iters = Bv.iters[b];
     __syncthreads();
@@ -2159,7 +2154,7 @@ __device__ __forceinline__ bool tie_obj_finish(const BatchView &Bv, const TieObj
 }
 // One tie iteration of LP b by the calling workgroup; false when the LP cannot select again before the next pass (finished, waiting for
 // a refresh, KP pivots pending).  sv, si, p_d: LDS of the kernel (see SelShared for why it is handed down).
-__device__ __forceinline__ bool tie_obj_once(const LpView &L, const BatchView &Bv, const TieObjView &Tv, const int b, double *sv, int *si, PivDesc *p_d)
+__device__ __forceinline__ bool tie_obj_once(const LpView &L, const BatchView &Bv, const TieView &Tv, const int b, double *sv, int *si, PivDesc *p_d)
 {
     const int tid = threadIdx.x, NT = (int)blockDim.x;
     const int state = Tv.state[b], np = Bv.npend[b], titer = Tv.iters[b], mode = Bv.mode[b];
@@ -2286,7 +2281,7 @@ __device__ __forceinline__ bool tie_obj_once(const LpView &L, const BatchView &B
     return true;
 }
 // Launched only while the switch is on (tableau form, objective batches), with the workgroup size of the batch's selections
-__global__ __launch_bounds__(NT_BIG) void k_select_tie_obj(LpView L, BatchView Bv, TieObjView Tv, const int *active, int nact, int nsel)
+__global__ __launch_bounds__(NT_BIG) void k_select_tie_obj(LpView L, BatchView Bv, TieView Tv, const int *active, int nact, int nsel)
 {
     __shared__ double sv[NT_BIG / WAVE];
     __shared__ int si[NT_BIG / WAVE];
@@ -2842,6 +2837,39 @@ struct DevexNorms {
     long last[3] = {0, 0, 0};
     NormView view() const { return NormView{norm_d, stat_d}; }
 };
+// What the engine keeps for a tie phase (bslv_lpq_set_canonical; objective batches: bslv_lpq_set_canonical_obj): the switch, the
+// direction (host / device, room for dir_cap values), the per-LP state of a batch (TieView; for Bcap LPs), the counters of the last batch
+// the phase could have run in (every solve_batch; every solve_batch_obj)
+struct TiePhase {
+    bool on = false;
+    std::vector<double> dir;
+    double *dir_d = nullptr; size_t dir_cap = 0;
+    double *g_d = nullptr; int *state_d = nullptr, *iters_d = nullptr, *stat_d = nullptr; int Bcap = 0;
+    long last[4] = {0, 0, 0, 0};
+    TieView view(int cap) const { return TieView{dir_d, g_d, state_d, iters_d, stat_d, cap}; }
+};
+// The counters of a batch, as solve_batch_impl gathers them: lock-step rounds, pivots, (LP, pass) pairs (how many tableaux k_flush read
+// and wrote), k_flush launches (one per round; a pass made on request, bslv_lpq_materialise, adds itself to the last call's), HIP-event
+// time of the passes (set_profile) and host wall clock, the extended selection's five counters, phase 1: LPs that entered it, its
+// iterations, rebuilds of its pricing vector
+struct BatchStats {
+    int iters = 0;
+    long pivots = 0, passes = 0, launches = 0;
+    double update_ms = 0, total_ms = 0;
+    long ext[5] = {0, 0, 0, 0, 0}, p1[3] = {0, 0, 0};
+    void add(const BatchStats &o)
+    {
+        iters += o.iters; pivots += o.pivots; passes += o.passes; launches += o.launches; update_ms += o.update_ms; total_ms += o.total_ms;
+        for (int k = 0; k < 5; k++) ext[k] += o.ext[k];
+        for (int k = 0; k < 3; k++) p1[k] += o.p1[k];
+    }
+};
+// ... and of a solve call: its first batch stored, the re-solves of the rescue added (solve_batch_impl); beside them what the call adds
+// to where it is produced, zeroed by solve_batch_rescue: the refactorisations (rfx; bslv_lpq_refactor: of that call), the periodic
+// refactorisation (per; [3] is a maximum) and the ray store (ray)
+struct CallStats : BatchStats {
+    long rfx[4] = {0, 0, 0, 0}, per[4] = {0, 0, 0, 0}, ray[3] = {0, 0, 0};
+};
 
 struct bslv_lpq {
     LpView L{};
@@ -2891,36 +2919,26 @@ struct bslv_lpq {
     int *npend_d = nullptr, *flushed_d = nullptr; double *pcol_d = nullptr, *dcur_d = nullptr;     // delayed update (see BatchView)
     double *dper_d = nullptr; int *pflags_d = nullptr, *stall_d = nullptr, *xstat_d = nullptr;
     double *cvals_d = nullptr; size_t cvals_cap = 0;     // objective coefficients of solve_batch_obj
-    long last_ext[5] = {0, 0, 0, 0, 0};
+    CallStats last;                    // the counters of the last solve call (bslv_lpq_last_stats and the getters beside it)
     int method = BSLV_LP_METHOD_DUAL;  // bslv_lpq_set_method (BSLV_LP_METHOD at create)
     int call_method = BSLV_LP_METHOD_DUAL;  // the method of the solve call in flight: `method`, or what bslv_lpq_solve_batch_method was given (the rescue's re-solves included)
-    long last_p1[3] = {0, 0, 0};       // phase 1 of the last batch: LPs that entered it, its iterations, rebuilds of its pricing vector
     // dual Devex pricing (bslv_lpq_set_pricing, BSLV_LP_PRICING at create) and primal Devex pricing (bslv_lpq_set_primal_pricing,
     // BSLV_LP_PRIMAL_PRICING at create): the rule and what the engine keeps for it (DevexNorms); pdv_dst: the slots of the LPs of the
     // last batch that ran under the primal rule (bslv_lpq_last_primal_pricing_norms answers by variable)
     int pricing = BSLV_LP_PRICING_DANTZIG, ppricing = BSLV_LP_PRICING_DANTZIG;
     DevexNorms dvx, pdv;
     std::vector<int> pdv_dst;
-    // tie phase (bslv_lpq_set_canonical): the switch, the direction (host / device), per-LP state of a batch, the counters of the last batch
-    bool canonical = false;
-    std::vector<double> canon_dir;
-    double *tdir_d = nullptr, *tg_d = nullptr; int *tstate_d = nullptr, *titers_d = nullptr, *tstat_d = nullptr; int tie_Bcap = 0;
-    long last_canon[4] = {0, 0, 0, 0};
-    // tie phase of objective batches (bslv_lpq_set_canonical_obj): the switch, the cost range it was set for (indices of the model as given)
-    // and ddir, per-LP state of a batch, the counters of the last objective batch
-    bool canon_obj = false;
+    // the tie phases (TiePhase): of solve_batch (bslv_lpq_set_canonical) and of objective batches (bslv_lpq_set_canonical_obj), with the
+    // cost range that one was set for (indices of the model as given)
+    TiePhase tie, tie_obj;
     int cobj_first = 0, cobj_cnt = 0;
-    std::vector<double> cobj_dir;
-    double *odir_d = nullptr, *og_d = nullptr; int *ostate_d = nullptr, *oiters_d = nullptr, *ostat_d = nullptr; int tie_obj_Bcap = 0; size_t odir_cap = 0;
-    long last_canon_obj[4] = {0, 0, 0, 0};
     // refactorisation of the revised form (bslv_lpq_refactor, bslv_lpq_set_refactor): the switch, the marks of the last batch (device / host),
-    // the replay's per-LP lists, the counters of the last solve call or explicit refactor
+    // the replay's per-LP lists (the counters of the last solve call or explicit refactor: last.rfx)
     bool refactor_on = false;
     int *rmark_d = nullptr; std::vector<int> rmark_h; bool rmark_valid = false;
     int *rfx_i_d = nullptr, *rfx_c_d = nullptr; int rfx_Bcap = 0;
-    long last_rfx[4] = {0, 0, 0, 0};
     // age of the slots' matrices (revised form: [slots], and per LP of a batch, see k_age_begin) and the periodic refactorisation
-    // (bslv_lpq_set_refactor_period): the period, the replay's own batch view (see period_view), the counters of the last solve call
+    // (bslv_lpq_set_refactor_period): the period, the replay's own batch view (see period_view) (the counters of the last solve call: last.per)
     long long *age_d = nullptr, *age0_d = nullptr;
     int period = 0;
     struct Period {
@@ -2933,13 +2951,10 @@ struct bslv_lpq {
         std::vector<int> failed;                     // batch indices whose replay found the basis singular (their slots are reset when the call is over)
         std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;      // events around the replay's passes (set_profile)
     } per;
-    long last_per[4] = {0, 0, 0, 0};
     // a basis loaded into a slot (bslv_lpq_load_basis, bslv_lpq_rebuild; lp_basis.inc): per LP of a call the nonbasic status (-1: basic)
     // and value of every variable, and the counters of the last call
     int *lb_nst_d = nullptr; double *lb_xv_d = nullptr; size_t lb_cap = 0;
     long last_rebuild[4] = {0, 0, 0, 0};
-    long last_passes = 0;             // (LP, pass) pairs of the last batch: how many tableaux k_flush read and wrote
-    long last_launches = 0;            // k_flush launches of the last batch: one per lock-step round + one per pass made on request (bslv_lpq_materialise)
     // dynamic LDS (candidate sort of the bound flipping ratio test; revised form: rho) that each selection kernel may use so far, indexed as select_kernel is
     size_t select_lds_max[3][4] = {{64 * 1024, 64 * 1024, 64 * 1024, 64 * 1024}, {64 * 1024, 64 * 1024, 64 * 1024, 64 * 1024}, {64 * 1024, 64 * 1024, 64 * 1024, 64 * 1024}};
     size_t price_lds_max = 64 * 1024;  // ... of k_rev_price (revised form, new objective: y)
@@ -2959,17 +2974,13 @@ struct bslv_lpq {
     void *cert_d = nullptr; size_t cert_cap = 0;
     long last_cert[3] = {0, 0, 0};
     // the ray store (bslv_lpq_set_rays, BSLV_LP_RAYS at create): per slot a kind and a vector of M + N doubles beside the pool (like the
-    // ages: no part of bslv_lpq_slot_bytes), the call's counters on the device; the counters of the last solve call and of the last
-    // bslv_lpq_certify_rays
+    // ages: no part of bslv_lpq_slot_bytes), the call's counters on the device; the counters of the last bslv_lpq_certify_rays (of the
+    // last solve call: last.ray)
     bool rays_on = false;
     int *raykind_d = nullptr, *raystat_d = nullptr; double *ray_d = nullptr;
-    long last_ray[3] = {0, 0, 0}, last_raycert[3] = {0, 0, 0};
+    long last_raycert[3] = {0, 0, 0};
     PivDesc *desc_d = nullptr;
     int *status_h = nullptr;          // pinned
-    // stats
-    int last_iters = 0;
-    long last_pivots = 0;
-    double last_update_ms = 0, last_total_ms = 0;
     bool profile = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> evpool;
     // PRESOLVE at the boundary (round 3): a row of A with a single non-zero outside the per-LP range is a bound on that column
@@ -3260,11 +3271,12 @@ void bslv_lpq_destroy(bslv_lpq *h)
     fr(h->raykind_d); fr(h->raystat_d); fr(h->ray_d); fr(h->lb_nst_d); fr(h->lb_xv_d);
     fr(h->age_d); fr(h->age0_d); fr(h->cert_d);
     for (const DevexNorms *r : {&h->dvx, &h->pdv}) { fr(r->norm_d); fr(r->stat_d); }
+    for (const TiePhase *r : {&h->tie, &h->tie_obj}) { fr(r->dir_d); fr(r->g_d); fr(r->state_d); fr(r->iters_d); fr(r->stat_d); }
     fr(h->L.T); fr(h->L.beta); fr(h->L.xN); fr(h->L.bh); fr(h->L.nh); fr(h->L.nstat); fr(h->L.pos);
     fr(h->Tstd); fr(h->lb_d); fr(h->ub_d); fr(h->art_d);
     fr(h->dbg_d); fr(h->list_d); fr(h->cptr_d); fr(h->cidx_d); fr(h->rptr_d); fr(h->ridx_d); fr(h->cval_d); fr(h->rval_d); fr(h->cost_d); fr(h->dsl_d); fr(h->trow_d); fr(h->uvec_d); fr(h->xfull_d); fr(h->hmail_d);
     fr(h->src_d); fr(h->dst_d); fr(h->status_d); fr(h->iters_d); fr(h->mode_d); fr(h->ver_d); fr(h->qslot_d); fr(h->init_d);
-    fr(h->tdir_d); fr(h->tg_d); fr(h->tstate_d); fr(h->titers_d); fr(h->tstat_d); fr(h->odir_d); fr(h->og_d); fr(h->ostate_d); fr(h->oiters_d); fr(h->ostat_d); fr(h->rmark_d); fr(h->rfx_i_d); fr(h->rfx_c_d);
+    fr(h->rmark_d); fr(h->rfx_i_d); fr(h->rfx_c_d);
     fr(h->vlo_d); fr(h->vup_d); fr(h->prow_d); fr(h->desc_d); fr(h->out_d); fr(h->active_d); fr(h->work_d); fr(h->nwork_d); fr(h->npend_d); fr(h->pcol_d); fr(h->dcur_d); fr(h->dper_d); fr(h->pflags_d); fr(h->stall_d); fr(h->xstat_d); fr(h->cvals_d);
     if (h->status_h) (void)hipHostFree(h->status_h);
     if (h->active_h) (void)hipHostFree(h->active_h);
@@ -3455,8 +3467,8 @@ static int flush_list(bslv_lpq *h, int cnt_slot, int upper, bool account = true)
     int n = 0;
     HIP_TRY(hipMemcpyAsync(&n, h->nwork_d + cnt_slot, sizeof(int), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    if (account) { h->last_passes += n; h->last_launches += 1; h->lazy_materialised += n; }
-    if (h->profile) { float t = 0; (void)hipEventElapsedTime(&t, ev.first, ev.second); h->last_update_ms += t; (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
+    if (account) { h->last.passes += n; h->last.launches += 1; h->lazy_materialised += n; }
+    if (h->profile) { float t = 0; (void)hipEventElapsedTime(&t, ev.first, ev.second); h->last.update_ms += t; (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
     return 0;
 }
 // batch indices list[0..n) of the last batch (nullptr: all of it): their slots get their tableau
@@ -3780,8 +3792,6 @@ struct SavedNorms {
     }
     int restore() { if (B > 0) { HIP_TRY(hipMemcpy(rec.norm_d, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice)); rec.B = B; } return 0; }
 };
-static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, const double *vlo, const double *vup,
-                            int cfirst, int ccnt, const double *cvals, int *status, int *iters);
 static int solve_batch_rescue(bslv_lpq *h, int B, const int *src, const int *dst, const double *vlo, const double *vup,
                               int cfirst, int ccnt, const double *cvals, int *status, int *iters);
 // ---- periodic refactorisation inside a solve (bslv_lpq_set_refactor_period): host side (the kernels: k_per_*, k_rfx_*) ----
@@ -3932,7 +3942,7 @@ static int period_refactor(bslv_lpq *h, const BatchView &bv, int n, bool at_star
     HIP_TRY(hipMemcpyAsync(nw.data(), P.nwork, (size_t)P.nwcap * sizeof(int), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     for (int k = 0; k < n; k++) {
-        if (res[k] >= 0) { h->last_per[at_start ? 0 : 1] += 1; h->last_per[2] += res[k]; }
+        if (res[k] >= 0) { h->last.per[at_start ? 0 : 1] += 1; h->last.per[2] += res[k]; }
         else { P.failed.push_back(due[k]); h->status_h[due[k]] = BSLV_LP_UNDEFINED; }
     }
     for (int k = 0; k < P.nwcap; k++) P.passes += nw[k];
@@ -3944,32 +3954,18 @@ static int period_refactor(bslv_lpq *h, const BatchView &bv, int n, bool at_star
 // every round an LP of the phase is in makes a pivot or ends it, except the one it waits in for a pass with KP pivots pending
 static int tie_cap(const LpView &L) { return 2 * PRIMAL_STALL + 2 * (L.M + L.N); }
 static int tie_rounds_max(const LpView &L) { return tie_cap(L) + 8; }
-// the per-LP vectors of the tie phase, for batches as large as the batch buffers
-static int ensure_tie(bslv_lpq *h)
+// the per-LP vectors of a tie phase, for batches as large as the batch buffers (gstride doubles of g per LP: Mp1p, objective batches ld)
+static int ensure_tie(bslv_lpq *h, TiePhase &r, int gstride)
 {
-    if (h->tie_Bcap >= h->Bcap && h->tg_d) return 0;
+    if (r.Bcap >= h->Bcap && r.g_d) return 0;
     auto fr = [](auto *&p) { if (p) (void)hipFree(p); p = nullptr; };
-    fr(h->tg_d); fr(h->tstate_d); fr(h->titers_d);
-    h->tie_Bcap = 0;
-    HIP_TRY(malloc0s(&h->tg_d, (size_t)h->Bcap * h->L.Mp1p * sizeof(double), h->stream));
-    HIP_TRY(malloc0s(&h->tstate_d, (size_t)h->Bcap * sizeof(int), h->stream));
-    HIP_TRY(malloc0s(&h->titers_d, (size_t)h->Bcap * sizeof(int), h->stream));
-    if (!h->tstat_d) HIP_TRY(malloc0s(&h->tstat_d, 4 * sizeof(int), h->stream));
-    h->tie_Bcap = h->Bcap;
-    return 0;
-}
-// ... and of the tie phase of an objective batch (g: ld doubles per LP)
-static int ensure_tie_obj(bslv_lpq *h)
-{
-    if (h->tie_obj_Bcap >= h->Bcap && h->og_d) return 0;
-    auto fr = [](auto *&p) { if (p) (void)hipFree(p); p = nullptr; };
-    fr(h->og_d); fr(h->ostate_d); fr(h->oiters_d);
-    h->tie_obj_Bcap = 0;
-    HIP_TRY(malloc0s(&h->og_d, (size_t)h->Bcap * h->L.ld * sizeof(double), h->stream));
-    HIP_TRY(malloc0s(&h->ostate_d, (size_t)h->Bcap * sizeof(int), h->stream));
-    HIP_TRY(malloc0s(&h->oiters_d, (size_t)h->Bcap * sizeof(int), h->stream));
-    if (!h->ostat_d) HIP_TRY(malloc0s(&h->ostat_d, 4 * sizeof(int), h->stream));
-    h->tie_obj_Bcap = h->Bcap;
+    fr(r.g_d); fr(r.state_d); fr(r.iters_d);
+    r.Bcap = 0;
+    HIP_TRY(malloc0s(&r.g_d, (size_t)h->Bcap * gstride * sizeof(double), h->stream));
+    HIP_TRY(malloc0s(&r.state_d, (size_t)h->Bcap * sizeof(int), h->stream));
+    HIP_TRY(malloc0s(&r.iters_d, (size_t)h->Bcap * sizeof(int), h->stream));
+    if (!r.stat_d) HIP_TRY(malloc0s(&r.stat_d, 4 * sizeof(int), h->stream));
+    r.Bcap = h->Bcap;
     return 0;
 }
 // host wall clock of the calls an apply() makes for its tableaux (bslv_lpq_materialise, bslv_lpq_park): lazy_stats[2]
@@ -4104,7 +4100,7 @@ int bslv_lpq_solve_batch_obj(bslv_lpq *h, int B, const int *src, const int *dst,
                              int cost_first, int cost_cnt, const double *costs, int *status, int *iters)
 {
     if (!h || cost_cnt < 1 || cost_first < 0 || cost_first + cost_cnt > h->ps.M0 + h->ps.N0 || !costs) { set_error("bslv_lpq_solve_batch_obj: bad argument"); return BSLV_E_ARG; }
-    if (h->canon_obj && (cost_first != h->cobj_first || cost_cnt != h->cobj_cnt)) { set_error("bslv_lpq_solve_batch_obj: the cost range (%d, %d) is not the one bslv_lpq_set_canonical_obj was set for (%d, %d)", cost_first, cost_cnt, h->cobj_first, h->cobj_cnt); return BSLV_E_ARG; }
+    if (h->tie_obj.on && (cost_first != h->cobj_first || cost_cnt != h->cobj_cnt)) { set_error("bslv_lpq_solve_batch_obj: the cost range (%d, %d) is not the one bslv_lpq_set_canonical_obj was set for (%d, %d)", cost_first, cost_cnt, h->cobj_first, h->cobj_cnt); return BSLV_E_ARG; }
     if (h->ps.nfold) {      // indices of the model as given -> the engine's (a cost on a folded row would be a cost on its column: not asked for by any caller)
         for (int t = 0; t < cost_cnt; t++) if (h->ps.map_var(cost_first + t) != h->ps.map_var(cost_first) + t) { set_error("bslv_lpq_solve_batch_obj: the cost range covers rows the presolve folded into column bounds"); return BSLV_E_ARG; }
         cost_first = h->ps.map_var(cost_first);
@@ -4121,16 +4117,18 @@ int bslv_lpq_solve_batch_obj(bslv_lpq *h, int B, const int *src, const int *dst,
     }
     return rc;
 }
+// One batch.  Its counters (BatchStats) are gathered in a record of its own and become the call's (h->last) when the batch is over:
+// stored, or added for a re-solve of the rescue (resolve)
 static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, const double *vlo, const double *vup,
-                            int cfirst, int ccnt, const double *cvals, int *status, int *iters)
+                            int cfirst, int ccnt, const double *cvals, int *status, int *iters, bool resolve)
 {
     if (h && h->ps.empty_box && B > 0 && status) {        // (bslv_lpq_set_bounds left a folded row no room: fold_bounds)
         for (int b = 0; b < B; b++) { status[b] = BSLV_LP_INFEASIBLE; if (iters) iters[b] = 0; }
-        h->last_iters = 0; h->last_pivots = 0; h->last_passes = 0; h->last_launches = 0;
-        for (int k = 0; k < 3; k++) h->last_p1[k] = 0;
-        for (int k = 0; k < 4; k++) h->last_canon[k] = 0;
-        if (cvals) for (int k = 0; k < 4; k++) h->last_canon_obj[k] = 0;
-        if (h->rays_on) h->last_ray[2] += B;      // (no slot is touched: nothing to hang a ray on)
+        h->last.iters = 0; h->last.pivots = 0; h->last.passes = 0; h->last.launches = 0;
+        for (int k = 0; k < 3; k++) h->last.p1[k] = 0;
+        for (int k = 0; k < 4; k++) h->tie.last[k] = 0;
+        if (cvals) for (int k = 0; k < 4; k++) h->tie_obj.last[k] = 0;
+        if (h->rays_on) h->last.ray[2] += B;      // (no slot is touched: nothing to hang a ray on)
         return 0;
     }
     if (!h || B < 0 || (B > 0 && (!src || !dst)) || (B > 0 && h->L.vcnt > 0 && (!vlo || !vup))) {
@@ -4173,7 +4171,7 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
     }
     if (const char *e = getenv("BSLV_UPD_GRID")) h->upd_grid = std::max(64, atoi(e));
     {   // one work-list length per lock-step iteration, zeroed here: no reset between iterations
-        const int need = L.maxit + 64 + ((h->canonical || h->canon_obj) ? tie_rounds_max(L) : 0);      // (the rounds of a tie phase count on behind the others')
+        const int need = L.maxit + 64 + ((h->tie.on || h->tie_obj.on) ? tie_rounds_max(L) : 0);      // (the rounds of a tie phase count on behind the others')
         if ((rc = ensure_nwork(h, need, need))) return rc;
     }
     HIP_TRY(hipMemsetAsync(h->xstat_d, 0, 8 * sizeof(int), s));
@@ -4234,7 +4232,7 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
     for (int b = 0; b < B; b++) h->active_h[b] = b;
     HIP_TRY(hipMemcpyAsync(h->active_d, h->active_h, B * sizeof(int), hipMemcpyHostToDevice, s));
     size_t nev = 0;
-    h->last_update_ms = 0;
+    BatchStats st;
     static const int max_rounds = getenv("BSLV_LP_MAXROUNDS") ? atoi(getenv("BSLV_LP_MAXROUNDS")) : 0;      // (timing experiments)
     L.probe = getenv("BSLV_REV_PROBE") ? atoi(getenv("BSLV_REV_PROBE")) : 0;
     // PERIODIC REFACTORISATION (bslv_lpq_set_refactor_period): the LPs of the active list that are due are listed on the stream
@@ -4297,7 +4295,7 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
         int rs[3];
         HIP_TRY(hipMemcpyAsync(rs, h->raystat_d, sizeof rs, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
-        for (int k = 0; k < 3; k++) h->last_ray[k] += rs[k];      // (added: the rescue's solves count with the call)
+        for (int k = 0; k < 3; k++) h->last.ray[k] += rs[k];      // (added: the rescue's solves count with the call)
         if (tm) {
             float ms = 0;
             (void)hipEventElapsedTime(&ms, ev.first, ev.second);
@@ -4310,11 +4308,11 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
     // lists count on from L.maxit + 64.
     int tie_rounds = 0;
     const int tie_base = L.maxit + 64;
-    // the rounds of a tie phase: launch(nt) selects for the nt LPs of the active list; state_d, iters_d, stat_d: the phase's per-LP state and counters
-    auto tie_phase = [&](int *state_d, int *iters_d, int *stat_d, auto launch, long out[4]) -> int {
-        HIP_TRY(hipMemsetAsync(state_d, 0, (size_t)B * sizeof(int), s));
-        HIP_TRY(hipMemsetAsync(iters_d, 0, (size_t)B * sizeof(int), s));
-        HIP_TRY(hipMemsetAsync(stat_d, 0, 4 * sizeof(int), s));
+    // the rounds of the tie phase r: launch(nt) selects for the nt LPs of the active list
+    auto tie_phase = [&](TiePhase &r, auto launch) -> int {
+        HIP_TRY(hipMemsetAsync(r.state_d, 0, (size_t)B * sizeof(int), s));
+        HIP_TRY(hipMemsetAsync(r.iters_d, 0, (size_t)B * sizeof(int), s));
+        HIP_TRY(hipMemsetAsync(r.stat_d, 0, 4 * sizeof(int), s));
         int nt = 0;
         for (int b = 0; b < B; b++) if (h->status_h[b] == BSLV_LP_OPTIMAL) h->active_h[nt++] = b;
         if (nt) HIP_TRY(hipMemcpyAsync(h->active_d, h->active_h, nt * sizeof(int), hipMemcpyHostToDevice, s));
@@ -4327,7 +4325,7 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
                 if ((rc = pass_round(nt, tie_base + tie_rounds))) return rc;
             }
             HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpyAsync(tstate.data(), state_d, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipMemcpyAsync(tstate.data(), r.state_d, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, s));
             HIP_TRY(hipStreamSynchronize(s));
             int left = 0;
             for (int k = 0; k < nt; k++) { const int b = h->active_h[k]; if (tstate[b] != TIE_DONE) h->active_h[left++] = b; }
@@ -4337,28 +4335,24 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
         }
         HIP_TRY(hipMemcpyAsync(h->status_h, h->status_d, B * sizeof(int), hipMemcpyDeviceToHost, s));
         int ts[4];
-        HIP_TRY(hipMemcpyAsync(ts, stat_d, sizeof ts, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(ts, r.stat_d, sizeof ts, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
-        for (int k = 0; k < 4; k++) out[k] = ts[k];
+        for (int k = 0; k < 4; k++) r.last[k] = ts[k];
         // (the cap on the pivots of an LP ends every phase long before the rounds run out; an LP still in it would keep the basis reached)
-        for (int k = 0; k < nt; k++) { const int b = h->active_h[k]; if (h->status_h[b] == ST_RUNNING) { h->status_h[b] = BSLV_LP_OPTIMAL; out[3]++; HIP_TRY(hipMemcpy(h->status_d + b, h->status_h + b, sizeof(int), hipMemcpyHostToDevice)); } }
+        for (int k = 0; k < nt; k++) { const int b = h->active_h[k]; if (h->status_h[b] == ST_RUNNING) { h->status_h[b] = BSLV_LP_OPTIMAL; r.last[3]++; HIP_TRY(hipMemcpy(h->status_d + b, h->status_h + b, sizeof(int), hipMemcpyHostToDevice)); } }
         return 0;
     };
-    for (int k = 0; k < 4; k++) h->last_canon[k] = 0;
-    if (L.objmode) for (int k = 0; k < 4; k++) h->last_canon_obj[k] = 0;
-    if (h->canonical && !L.objmode && !L.rev && L.vcnt > 0 && !max_rounds) {
-        if ((rc = ensure_tie(h))) return rc;
-        TieView tv;
-        tv.dir = h->tdir_d; tv.g = h->tg_d; tv.state = h->tstate_d; tv.iters = h->titers_d; tv.stat = h->tstat_d; tv.cap = tie_cap(L);
-        auto launch = [&](int nt) { hipLaunchKernelGGL(k_select_tie, dim3(nt), dim3(plan.nt), 0, s, L, bv, tv, h->active_d, nt, KP); };
-        if ((rc = tie_phase(tv.state, tv.iters, tv.stat, launch, h->last_canon))) return rc;
+    for (int k = 0; k < 4; k++) h->tie.last[k] = 0;
+    if (L.objmode) for (int k = 0; k < 4; k++) h->tie_obj.last[k] = 0;
+    if (h->tie.on && !L.objmode && !L.rev && L.vcnt > 0 && !max_rounds) {
+        if ((rc = ensure_tie(h, h->tie, L.Mp1p))) return rc;
+        const TieView tv = h->tie.view(tie_cap(L));
+        if ((rc = tie_phase(h->tie, [&](int nt) { hipLaunchKernelGGL(k_select_tie, dim3(nt), dim3(plan.nt), 0, s, L, bv, tv, h->active_d, nt, KP); }))) return rc;
     }
-    if (h->canon_obj && L.objmode && !L.rev && !max_rounds) {
-        if ((rc = ensure_tie_obj(h))) return rc;
-        TieObjView tv;
-        tv.dir = h->odir_d; tv.g = h->og_d; tv.state = h->ostate_d; tv.iters = h->oiters_d; tv.stat = h->ostat_d; tv.cap = tie_cap(L);
-        auto launch = [&](int nt) { hipLaunchKernelGGL(k_select_tie_obj, dim3(nt), dim3(plan.nt), 0, s, L, bv, tv, h->active_d, nt, KP); };
-        if ((rc = tie_phase(tv.state, tv.iters, tv.stat, launch, h->last_canon_obj))) return rc;
+    if (h->tie_obj.on && L.objmode && !L.rev && !max_rounds) {
+        if ((rc = ensure_tie(h, h->tie_obj, L.ld))) return rc;
+        const TieView tv = h->tie_obj.view(tie_cap(L));
+        if ((rc = tie_phase(h->tie_obj, [&](int nt) { hipLaunchKernelGGL(k_select_tie_obj, dim3(nt), dim3(plan.nt), 0, s, L, bv, tv, h->active_d, nt, KP); }))) return rc;
     }
     {   // tableau passes of this batch: sum of the work-list lengths of the rounds
         std::vector<int> nw(std::max(it, 1), 0);
@@ -4370,7 +4364,7 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
             HIP_TRY(hipMemcpy(nw.data(), h->nwork_d + tie_base, (size_t)tie_rounds * sizeof(int), hipMemcpyDeviceToHost));
             for (int k = 0; k < tie_rounds; k++) passes += nw[k];
         }
-        h->last_passes = passes + h->per.passes;      // (the replay's passes count in work lists of their own)
+        st.passes = passes + h->per.passes;      // (the replay's passes count in work lists of their own)
     }
     if (L.rev) hipLaunchKernelGGL(k_rev_store_d, dim3((L.ld + 255) / 256, B), dim3(256), 0, s, L, bv, B);       // the reduced costs of every LP go to its slot
     if (bv.lazy) {
@@ -4386,7 +4380,7 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
             h->last_npend.resize(h->last_flushed_at + B);
             HIP_TRY(hipMemcpy(h->last_npend.data(), h->npend_d, h->last_npend.size() * sizeof(int), hipMemcpyDeviceToHost));
         }
-        h->lazy_skipped += B - std::min<long>(B, h->last_passes);
+        h->lazy_skipped += B - std::min<long>(B, st.passes);
     } else {   // tableaux of the solves that made no pivot
         const int cnt_slot = L.maxit + 40;
         hipLaunchKernelGGL(k_list_unpivoted, dim3((B + 255) / 256), dim3(256), 0, s, bv, B, cnt_slot);
@@ -4396,7 +4390,7 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
     if (L.rev) hipLaunchKernelGGL(k_age_end, dim3((B + 255) / 256), dim3(256), 0, s, bv, h->age_d, (const long long *)h->age0_d, B);
     if (period > 0) {
         HIP_TRY(hipMemcpy(per_stat, h->per.stat, sizeof per_stat, hipMemcpyDeviceToHost));
-        h->last_per[3] = std::max(h->last_per[3], (long)per_stat[1]);
+        h->last.per[3] = std::max(h->last.per[3], (long)per_stat[1]);
         // a slot whose replay failed holds a half-built matrix: it is reset, as bslv_lpq_refactor does (now: the solve has left its vectors in it)
         for (int b : h->per.failed) if ((rc = bslv_lpq_reset_slot(h, dst[b]))) return rc;
     }
@@ -4407,18 +4401,18 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
         HIP_TRY(hipMemcpy(itv.data(), h->iters_d, B * sizeof(int), hipMemcpyDeviceToHost));
         long piv = 0;
         for (int b = 0; b < B; b++) piv += itv[b];
-        h->last_pivots = piv;
+        st.pivots = piv;
         if (iters) memcpy(iters, itv.data(), B * sizeof(int));
     }
-    h->last_iters = it + tie_rounds;
-    h->last_launches = it + tie_rounds + h->per.launches;
+    st.iters = it + tie_rounds;
+    st.launches = it + tie_rounds + h->per.launches;
     {   // the unpark passes made since the last batch count with this one (they ran on the stream before its first kernel)
         bslv_lpq::Park &P = h->park;
-        h->last_passes += P.pre_passes; h->last_launches += P.pre_launches;
+        st.passes += P.pre_passes; st.launches += P.pre_launches;
         P.pre_passes = 0; P.pre_launches = 0;
         P.list_inflight = false; P.pairs_inflight = false;      // (the readbacks above have waited for the stream)
     }
-    { int xs[8]; HIP_TRY(hipMemcpy(xs, h->xstat_d, sizeof xs, hipMemcpyDeviceToHost)); for (int k = 0; k < 5; k++) h->last_ext[k] = xs[k]; for (int k = 0; k < 3; k++) h->last_p1[k] = xs[5 + k]; }
+    { int xs[8]; HIP_TRY(hipMemcpy(xs, h->xstat_d, sizeof xs, hipMemcpyDeviceToHost)); for (int k = 0; k < 5; k++) st.ext[k] = xs[k]; for (int k = 0; k < 3; k++) st.p1[k] = xs[5 + k]; }
     if ((rc = devex_collect(h, h->dvx)) || (rc = devex_collect(h, h->pdv))) return rc;
     if (pdv) h->pdv_dst.assign(dst, dst + B);
     if (h->profile) {
@@ -4426,13 +4420,14 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
         for (size_t e = 0; e < nev; e++) { float t = 0; (void)hipEventElapsedTime(&t, h->evpool[e].first, h->evpool[e].second); ms += t; }
         for (auto &e : h->park.pre_ev) { float t = 0; (void)hipEventElapsedTime(&t, e.first, e.second); ms += t; }
         for (auto &e : h->per.ev) { float t = 0; (void)hipEventElapsedTime(&t, e.first, e.second); ms += t; }
-        h->last_update_ms = ms;
+        st.update_ms = ms;
     }
     for (auto &e : h->per.ev) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
     h->per.ev.clear();
     for (auto &e : h->park.pre_ev) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
     h->park.pre_ev.clear();
-    h->last_total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    st.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (resolve) h->last.add(st); else static_cast<BatchStats &>(h->last) = st;
     if (L.probe & 8) {
         unsigned long long dg[16];
         HIP_TRY(hipMemcpy(dg, h->dbg_d, sizeof dg, hipMemcpyDeviceToHost));
@@ -4445,8 +4440,8 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
     }
     {
         static const bool tm = getenv("BSLV_LP_TIMING") != nullptr;
-        if (tm) fprintf(stderr, "lp solve_batch: %s form %d x %d, B %d, %d lock-step rounds, %ld pivots, %ld passes, %.1f ms; %d parents, largest family %d, %s\n", L.rev ? "revised" : "tableau", L.M, L.N, B, it, h->last_pivots, h->last_passes, h->last_total_ms, h->last_init_parents, h->last_init_family, h->last_init_chunks ? "k_init_grouped" : "k_init");
-        if (tm && period > 0) fprintf(stderr, "lp period %d: %ld refactorisations at the start, %ld during the rounds, %ld replay pivots, largest age at a selection %ld, %ld replay passes, %.1f ms in refactorisations\n", period, h->last_per[0], h->last_per[1], h->last_per[2], h->last_per[3], h->per.passes, h->per.ms);
+        if (tm) fprintf(stderr, "lp solve_batch: %s form %d x %d, B %d, %d lock-step rounds, %ld pivots, %ld passes, %.1f ms; %d parents, largest family %d, %s\n", L.rev ? "revised" : "tableau", L.M, L.N, B, it, st.pivots, st.passes, st.total_ms, h->last_init_parents, h->last_init_family, h->last_init_chunks ? "k_init_grouped" : "k_init");
+        if (tm && period > 0) fprintf(stderr, "lp period %d: %ld refactorisations at the start, %ld during the rounds, %ld replay pivots, largest age at a selection %ld, %ld replay passes, %.1f ms in refactorisations\n", period, h->last.per[0], h->last.per[1], h->last.per[2], h->last.per[3], h->per.passes, h->per.ms);
         if (tm && h->park.cap) fprintf(stderr, "lp park (totals): %ld parked, %ld unparked for a child, %ld because their source was about to be overwritten, %ld dropped unused, %zu live\n", h->park.stats[0], h->park.stats[1], h->park.stats[2], h->park.stats[3], h->park.live.size());
     }
     return 0;
@@ -4509,16 +4504,16 @@ static int solve_batch_rescue(bslv_lpq *h, int B, const int *src, const int *dst
 {
     if (h) {
         LpView &L = h->L;
-        for (int k = 0; k < 4; k++) h->last_rfx[k] = 0;
-        for (int k = 0; k < 4; k++) h->last_per[k] = 0;      // (solve_batch_impl adds to them: the rescue's solves count with the call)
+        for (int k = 0; k < 4; k++) h->last.rfx[k] = 0;
+        for (int k = 0; k < 4; k++) h->last.per[k] = 0;      // (solve_batch_impl adds to them: the rescue's solves count with the call)
         for (DevexNorms *r : {&h->dvx, &h->pdv}) { r->B = 0; for (int k = 0; k < 3; k++) r->last[k] = 0; }
-        for (int k = 0; k < 3; k++) h->last_ray[k] = 0;
+        for (int k = 0; k < 3; k++) h->last.ray[k] = 0;
         h->rmark_valid = false;
         L.rfx = (h->refactor_on && L.rev) ? 1 : 0;
         L.drift_b = -1; L.drift_p = -1;
         if (L.rev) if (const char *e = getenv("BSLV_LP_REV_DRIFT")) { int lp = -1, p = -1; if (sscanf(e, "%d:%d", &lp, &p) == 2 && lp >= 0 && p >= 1) { L.drift_b = lp; L.drift_p = p; } }
     }
-    int rc = solve_batch_impl(h, B, src, dst, vlo, vup, cfirst, ccnt, cvals, status, iters);
+    int rc = solve_batch_impl(h, B, src, dst, vlo, vup, cfirst, ccnt, cvals, status, iters, false);
     if (!h) return rc;
     LpView &L = h->L;
     L.drift_b = -1; L.drift_p = -1;             // (once per call: not again in the rescue)
@@ -4526,14 +4521,9 @@ static int solve_batch_rescue(bslv_lpq *h, int B, const int *src, const int *dst
     std::vector<int> todo;
     {
         std::vector<char> taken(h->slots, 0);
-        for (int b = 0; b < B; b++) if (h->rmark_h[b]) { if (taken[dst[b]]) h->last_rfx[3]++; else { taken[dst[b]] = 1; todo.push_back(b); } }
+        for (int b = 0; b < B; b++) if (h->rmark_h[b]) { if (taken[dst[b]]) h->last.rfx[3]++; else { taken[dst[b]] = 1; todo.push_back(b); } }
     }
     if (todo.empty()) return 0;
-    int tot_iters = h->last_iters; long tot_pivots = h->last_pivots, tot_passes = h->last_passes, tot_launches = h->last_launches;
-    double tot_upd = h->last_update_ms, tot_ms = h->last_total_ms;
-    long ext[5], p1[3];
-    for (int k = 0; k < 5; k++) ext[k] = h->last_ext[k];
-    for (int k = 0; k < 3; k++) p1[k] = h->last_p1[k];
     const int vc = L.vcnt;
     // Devex pricing: the norms of the batch (the re-solve runs in the LP's own slot, so the slots of the batch stand)
     SavedNorms sn(h->dvx, L.Mp1p), tn(h->pdv, L.ld);
@@ -4544,8 +4534,10 @@ static int solve_batch_rescue(bslv_lpq *h, int B, const int *src, const int *dst
         const int n = (int)todo.size();
         std::vector<int> slots(n), rst(n);
         for (int k = 0; k < n; k++) slots[k] = dst[todo[k]];
-        if ((rc = refactor_impl(h, n, slots.data(), rst.data(), &h->last_rfx[0], &h->last_rfx[1], &h->last_rfx[3]))) return rc;
-        tot_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        const double upd = h->last.update_ms;      // (set_profile: the replay's passes are in the call's wall clock only)
+        if ((rc = refactor_impl(h, n, slots.data(), rst.data(), &h->last.rfx[0], &h->last.rfx[1], &h->last.rfx[3]))) return rc;
+        h->last.update_ms = upd;
+        h->last.total_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         std::vector<int> lps, sl;
         for (int k = 0; k < n; k++) if (rst[k] == 0) { lps.push_back(todo[k]); sl.push_back(slots[k]); }
         todo.clear();
@@ -4558,24 +4550,16 @@ static int solve_batch_rescue(bslv_lpq *h, int B, const int *src, const int *dst
         }
         std::vector<int> st2(m), it2(m);
         h->rmark_valid = false;
-        if ((rc = solve_batch_impl(h, m, sl.data(), sl.data(), vc > 0 ? lo2.data() : nullptr, vc > 0 ? up2.data() : nullptr, cfirst, ccnt, cvals ? cv2.data() : nullptr, st2.data(), it2.data()))) return rc;
-        tot_iters += h->last_iters; tot_pivots += h->last_pivots; tot_passes += h->last_passes; tot_launches += h->last_launches;
-        tot_upd += h->last_update_ms; tot_ms += h->last_total_ms;
-        for (int k = 0; k < 5; k++) ext[k] += h->last_ext[k];
-        for (int k = 0; k < 3; k++) p1[k] += h->last_p1[k];
+        if ((rc = solve_batch_impl(h, m, sl.data(), sl.data(), vc > 0 ? lo2.data() : nullptr, vc > 0 ? up2.data() : nullptr, cfirst, ccnt, cvals ? cv2.data() : nullptr, st2.data(), it2.data(), true))) return rc;
         if ((rc = sn.take(lps, m)) || (rc = tn.take(lps, m))) return rc;
         for (int k = 0; k < m; k++) {
             const int b = lps[k];
             if (iters) iters[b] += it2[k];
-            if (st2[k] != BSLV_LP_UNDEFINED) { if (status) status[b] = st2[k]; h->last_rfx[2]++; }
+            if (st2[k] != BSLV_LP_UNDEFINED) { if (status) status[b] = st2[k]; h->last.rfx[2]++; }
             else if (h->rmark_valid && h->rmark_h[k] && attempt + 1 < RESCUE_MAX) todo.push_back(b);      // (drifted again: once more)
-            else h->last_rfx[3]++;                 // (k_prep refused the restart, or the cap: the LP stays UNDEFINED, as without the switch)
+            else h->last.rfx[3]++;                 // (k_prep refused the restart, or the cap: the LP stays UNDEFINED, as without the switch)
         }
     }
-    h->last_iters = tot_iters; h->last_pivots = tot_pivots; h->last_passes = tot_passes; h->last_launches = tot_launches;
-    h->last_update_ms = tot_upd; h->last_total_ms = tot_ms;
-    for (int k = 0; k < 5; k++) h->last_ext[k] = ext[k];
-    for (int k = 0; k < 3; k++) h->last_p1[k] = p1[k];
     if ((rc = sn.restore()) || (rc = tn.restore())) return rc;
     if (tn.B > 0) h->pdv_dst = tn_dst;
     return 0;
@@ -4591,9 +4575,9 @@ int bslv_lpq_refactor(bslv_lpq *h, int n, const int *slots, int *status_out)
         if (taken[slots[b]]) { set_error("bslv_lpq_refactor: bad slot %d at %d: named twice", slots[b], b); return BSLV_E_ARG; }
         taken[slots[b]] = 1;
     }
-    for (int k = 0; k < 4; k++) h->last_rfx[k] = 0;
+    for (int k = 0; k < 4; k++) h->last.rfx[k] = 0;
     if (n == 0) return 0;
-    return refactor_impl(h, n, slots, status_out, &h->last_rfx[0], &h->last_rfx[1], &h->last_rfx[3]);
+    return refactor_impl(h, n, slots, status_out, &h->last.rfx[0], &h->last.rfx[1], &h->last.rfx[3]);
 }
 int bslv_lpq_set_refactor(bslv_lpq *h, int on)
 {
@@ -4606,7 +4590,7 @@ int bslv_lpq_get_refactor(const bslv_lpq *h) { return h && h->refactor_on; }
 int bslv_lpq_last_refactor_stats(const bslv_lpq *h, long out[4])
 {
     if (!h || !out) return BSLV_E_ARG;
-    for (int k = 0; k < 4; k++) out[k] = h->last_rfx[k];
+    for (int k = 0; k < 4; k++) out[k] = h->last.rfx[k];
     return 0;
 }
 int bslv_lpq_set_refactor_period(bslv_lpq *h, int pivots)
@@ -4633,7 +4617,7 @@ int bslv_lpq_slot_age(const bslv_lpq *h, int slot, long *age)
 int bslv_lpq_last_period_stats(const bslv_lpq *h, long out[4])
 {
     if (!h || !out) return BSLV_E_ARG;
-    for (int k = 0; k < 4; k++) out[k] = h->last_per[k];
+    for (int k = 0; k < 4; k++) out[k] = h->last.per[k];
     return 0;
 }
 int bslv_lpq_get_inverse(bslv_lpq *h, int slot, int *heads, double *X)
@@ -4793,9 +4777,9 @@ int bslv_lpq_get_obj(bslv_lpq *h, int B, const int *slot, double *out)
     return 0;
 }
 
-long bslv_lpq_last_passes(const bslv_lpq *h) { return h ? h->last_passes : 0; }
-long bslv_lpq_last_launches(const bslv_lpq *h) { return h ? h->last_launches : 0; }
-long bslv_lpq_last_flip_updates(const bslv_lpq *h) { return h ? h->last_ext[4] : 0; }
+long bslv_lpq_last_passes(const bslv_lpq *h) { return h ? h->last.passes : 0; }
+long bslv_lpq_last_launches(const bslv_lpq *h) { return h ? h->last.launches : 0; }
+long bslv_lpq_last_flip_updates(const bslv_lpq *h) { return h ? h->last.ext[4] : 0; }
 long bslv_lpq_last_init_chunks(const bslv_lpq *h) { return h ? h->last_init_chunks : 0; }
 // The extended selection for every LP of this engine from now on (on != 0) or only where a variable is boxed (0, the default
 // below 1 GiB per tableau).  It changes the pivots taken, not the optimal value: used by the callers' retry when the plain
@@ -4819,7 +4803,7 @@ int bslv_lpq_get_method(const bslv_lpq *h) { return h ? h->method : BSLV_LP_METH
 int bslv_lpq_last_phase1_stats(const bslv_lpq *h, long out[3])
 {
     if (!h || !out) return BSLV_E_ARG;
-    for (int k = 0; k < 3; k++) out[k] = h->last_p1[k];
+    for (int k = 0; k < 3; k++) out[k] = h->last.p1[k];
     return 0;
 }
 // The pricing rule of the dual steps (select_once<.., DVX>): see bslv_hip.h
@@ -4874,56 +4858,59 @@ int bslv_lpq_last_primal_pricing_norms(bslv_lpq *h, int b, double *t)
     for (int j = 0; j < L.N; j++) if (nh[j] >= 0 && nh[j] < L.M + L.N) t[nh[j]] = tp[j];
     return 0;
 }
+// the direction of a tie phase, n values: the host copy, and the device's (at least one double; grown when n outgrows it)
+static int tie_upload_dir(bslv_lpq *h, TiePhase &r, const double *dir, int n)
+{
+    if (!r.dir_d || (size_t)n > r.dir_cap) {
+        if (r.dir_d) (void)hipFree(r.dir_d);
+        r.dir_d = nullptr; r.dir_cap = 0;
+        HIP_TRY(malloc0(&r.dir_d, (size_t)std::max(1, n) * sizeof(double)));
+        r.dir_cap = (size_t)std::max(1, n);
+    }
+    r.dir.assign(dir, dir + n);
+    if (n > 0) {
+        HIP_TRY(hipMemcpyAsync(r.dir_d, r.dir.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+    }
+    return 0;
+}
 // The canonical optimal basis (tie phase) for every later solve_batch: see bslv_hip.h; the cut of a vertex is built from these duals (bslv_algs.c:1050)
 int bslv_lpq_set_canonical(bslv_lpq *h, int on, const double *dir)
 {
     if (!h || (on && !dir)) { set_error("bslv_lpq_set_canonical: bad argument"); return BSLV_E_ARG; }
     if (h->L.rev && on) { set_error("bslv_lpq_set_canonical: the revised form has no tie phase (the canonical dual is the tableau form's)"); return BSLV_E_ARG; }
-    if (!on) { h->canonical = false; return 0; }
+    if (!on) { h->tie.on = false; return 0; }
     const int vc = h->L.vcnt;
     for (int j = 0; j < vc; j++) if (!std::isfinite(dir[j])) { set_error("bslv_lpq_set_canonical: dir[%d] is not finite", j); return BSLV_E_ARG; }
-    if (!h->tdir_d) HIP_TRY(malloc0(&h->tdir_d, (size_t)std::max(1, vc) * sizeof(double)));
-    h->canon_dir.assign(dir, dir + vc);
-    if (vc > 0) {
-        HIP_TRY(hipMemcpyAsync(h->tdir_d, h->canon_dir.data(), (size_t)vc * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream));
-    }
-    h->canonical = true;
+    if (const int rc = tie_upload_dir(h, h->tie, dir, vc)) return rc;
+    h->tie.on = true;
     return 0;
 }
-int bslv_lpq_get_canonical(const bslv_lpq *h) { return h && h->canonical; }
+int bslv_lpq_get_canonical(const bslv_lpq *h) { return h && h->tie.on; }
 int bslv_lpq_last_canonical_stats(const bslv_lpq *h, long out[4])
 {
     if (!h || !out) return BSLV_E_ARG;
-    for (int k = 0; k < 4; k++) out[k] = h->last_canon[k];
+    for (int k = 0; k < 4; k++) out[k] = h->tie.last[k];
     return 0;
 }
 // The canonical optimal point (tie phase of objective batches) for every later solve_batch_obj: see bslv_hip.h; the dual variant's cut is built from this point (bslv_algs.c:1479-1486)
 int bslv_lpq_set_canonical_obj(bslv_lpq *h, int on, int cost_first, int cost_cnt, const double *ddir)
 {
     if (!h || (on && !ddir)) { set_error("bslv_lpq_set_canonical_obj: bad argument"); return BSLV_E_ARG; }
-    if (!on) { h->canon_obj = false; return 0; }
+    if (!on) { h->tie_obj.on = false; return 0; }
     if (h->L.rev) { set_error("bslv_lpq_set_canonical_obj: the revised form has no tie phase for objective batches (the canonical point is the tableau form's)"); return BSLV_E_ARG; }
     if (cost_cnt < 1 || cost_first < 0 || cost_first + cost_cnt > h->ps.M0 + h->ps.N0) { set_error("bslv_lpq_set_canonical_obj: bad cost range (%d, %d)", cost_first, cost_cnt); return BSLV_E_ARG; }
     for (int j = 0; j < cost_cnt; j++) if (!std::isfinite(ddir[j])) { set_error("bslv_lpq_set_canonical_obj: ddir[%d] is not finite", j); return BSLV_E_ARG; }
-    if ((size_t)cost_cnt > h->odir_cap) {
-        if (h->odir_d) (void)hipFree(h->odir_d);
-        h->odir_d = nullptr; h->odir_cap = 0;
-        HIP_TRY(malloc0(&h->odir_d, (size_t)cost_cnt * sizeof(double)));
-        h->odir_cap = (size_t)cost_cnt;
-    }
-    h->cobj_dir.assign(ddir, ddir + cost_cnt);
-    HIP_TRY(hipMemcpyAsync(h->odir_d, h->cobj_dir.data(), (size_t)cost_cnt * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (const int rc = tie_upload_dir(h, h->tie_obj, ddir, cost_cnt)) return rc;
     h->cobj_first = cost_first; h->cobj_cnt = cost_cnt;
-    h->canon_obj = true;
+    h->tie_obj.on = true;
     return 0;
 }
-int bslv_lpq_get_canonical_obj(const bslv_lpq *h) { return h && h->canon_obj; }
+int bslv_lpq_get_canonical_obj(const bslv_lpq *h) { return h && h->tie_obj.on; }
 int bslv_lpq_last_canonical_obj_stats(const bslv_lpq *h, long out[4])
 {
     if (!h || !out) return BSLV_E_ARG;
-    for (int k = 0; k < 4; k++) out[k] = h->last_canon_obj[k];
+    for (int k = 0; k < 4; k++) out[k] = h->tie_obj.last[k];
     return 0;
 }
 // The ray store: see bslv_hip.h
@@ -4951,7 +4938,7 @@ int bslv_lpq_get_rays(const bslv_lpq *h) { return h && h->rays_on; }
 int bslv_lpq_last_ray_stats(const bslv_lpq *h, long out[3])
 {
     if (!h || !out) return BSLV_E_ARG;
-    for (int k = 0; k < 3; k++) out[k] = h->last_ray[k];
+    for (int k = 0; k < 3; k++) out[k] = h->last.ray[k];
     return 0;
 }
 // kinds and vectors of the listed slots IN THE INDICES OF THE MODEL AS GIVEN.  Folded rows: a column entry whose needed bound (the lower
@@ -5006,16 +4993,16 @@ int bslv_lpq_get_ray(bslv_lpq *h, int B, const int *slot, int *kind, double *ray
 int bslv_lpq_last_ext_stats(const bslv_lpq *h, long out[4])
 {
     if (!h || !out) return BSLV_E_ARG;
-    for (int k = 0; k < 4; k++) out[k] = h->last_ext[k];
+    for (int k = 0; k < 4; k++) out[k] = h->last.ext[k];
     return 0;
 }
 int bslv_lpq_last_stats(const bslv_lpq *h, int *lockstep_iters, long *pivots, double *update_ms, double *total_ms)
 {
     if (!h) return BSLV_E_ARG;
-    if (lockstep_iters) *lockstep_iters = h->last_iters;
-    if (pivots) *pivots = h->last_pivots;
-    if (update_ms) *update_ms = h->last_update_ms;
-    if (total_ms) *total_ms = h->last_total_ms;
+    if (lockstep_iters) *lockstep_iters = h->last.iters;
+    if (pivots) *pivots = h->last.pivots;
+    if (update_ms) *update_ms = h->last.update_ms;
+    if (total_ms) *total_ms = h->last.total_ms;
     return 0;
 }
 

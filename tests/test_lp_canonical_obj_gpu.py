@@ -151,6 +151,41 @@ def test_switch_off_is_the_engine_as_it_was(name):
     assert rows[0]["st"] == off["st"].tobytes() and rows[0]["it"] == off["it"].tobytes() and rows[0]["x"] == off["val"].tobytes()
 
 
+def test_the_two_tie_phases_keep_their_own_counters():
+    """both switches on in one engine, on the smallest model (decoy-3: 4 rows, 10 columns): an objective batch leaves the counters of
+    the canonical basis at zero, a solve_batch leaves those of the objective phase standing (only an objective batch resets them), and
+    the same objective batch again gives the same counters and the same solutions, bit for bit"""
+    prob, c, model, _ = _run("decoy-3")
+    W = c["W"]
+    B = len(W)
+    eng = _start(model, 2 * B + 1)
+    try:
+        assert eng.set_canonical_obj(1, model.y_first, cc.direction(model.q)) == 0
+        assert eng.set_canonical(1, np.ones(eng.vcnt)) == 0
+        assert eng.get_canonical_obj() == 1 and eng.get_canonical() == 1
+        zero = dict(entered=0, tie_pivots=0, no_candidate=0, capped=0)
+
+        def batch(dst):
+            _, st, _ = _batch(eng, model, W, dst=dst)
+            assert np.all(st == OPTIMAL), st
+            n = model.M + model.N
+            return eng.last_canonical_obj_stats(), [eng.obj(dst).tobytes(), eng.primal(dst, 0, n).tobytes(), eng.dual(dst, 0, n).tobytes()]
+
+        dst = np.arange(1, B + 1, dtype=np.int32)
+        stats, first = batch(dst)
+        assert stats["entered"] > 0, stats
+        assert eng.last_canonical_stats() == zero
+        st, _ = eng.solve_batch(dst[:1], dst[:1], np.zeros((1, 0)), np.zeros((1, 0)))
+        assert st[0] == OPTIMAL, st
+        assert eng.last_canonical_obj_stats() == stats
+        assert eng.last_canonical_stats() == zero
+        stats2, second = batch(np.arange(B + 1, 2 * B + 1, dtype=np.int32))
+        assert stats2 == stats
+        assert second == first
+    finally:
+        eng.close()
+
+
 def _check_certificates(model, prob, val, dual, W, obj):
     """_check_certificates of tests/test_lp_rev_obj_gpu.py: y = P x, x feasible; the duals of the rows and the reduced costs of the
     columns have the signs their bounds allow, sit only on variables at a bound, and give the objective back.

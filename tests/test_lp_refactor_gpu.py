@@ -343,6 +343,43 @@ def test_rescue_of_an_lp_the_cross_check_gives_up(case):
     eng.close()
 
 
+SUMMED = ("lockstep_iters", "pivots", "passes", "launches", "flip_iterations", "perturbations", "primal_steps", "wrong_sign_removals",
+          "flip_vector_updates", "phase1_lps", "phase1_iterations", "phase1_rebuilds")
+
+
+def test_counters_of_a_rescued_call_cover_the_whole_call():
+    """last_stats() of a call with a rescue in it is the sum over the batch and the re-solve of the rescued LP: the same batch with the
+    switch off, then by hand what the rescue does (refactor of the LP's slot, the LP solved again in place with its own bounds), gives
+    the two summands"""
+    case = "main"
+    p = _problem(case)
+    model = p["model"]
+    ref = _reference(case)
+    b = int(np.nonzero(ref["it"] >= 4)[0][0])
+    hook = "%d:%d" % (b, int(ref["it"][b]) // 2)
+    slot = p["dst"][b:b + 1]
+    # run A: hook on, switch off, then the rescue by hand
+    eng, st, _ = _first_generation(case, hook=hook)
+    assert st[b] == UNDEFINED, st
+    a1 = eng.last_stats()
+    with _env(BSLV_LP_REV_DRIFT=None):
+        assert eng.refactor(slot)[0] == 0
+        st2, _ = eng.solve_batch(slot, slot, np.full((1, model.r), -np.inf), p["ub"][b:b + 1])
+    assert st2[0] == OPTIMAL, st2
+    a2 = eng.last_stats()
+    eng.close()
+    # run B: hook on, switch on
+    eng, st, _ = _first_generation(case, hook=hook, switch=1)
+    assert np.all(st == OPTIMAL), st
+    got = eng.last_stats()
+    stats = eng.last_refactor_stats()
+    eng.close()
+    for k in SUMMED:
+        print("%-22s batch %6d + re-solve %6d, the rescued call %6d" % (k, a1[k], a2[k], got[k]))
+    assert {k: got[k] for k in SUMMED} == {k: a1[k] + a2[k] for k in SUMMED}
+    assert stats["refactorised"] == 1 and stats["rescued"] == 1 and stats["failed"] == 0, stats
+
+
 @pytest.mark.parametrize("case", ["main", "wide"])
 def test_rescue_under_dual_devex_keeps_the_batch_norms(case):
     """dual Devex pricing (set_pricing(1)) with the rescue on: the re-solve of the one LP is a batch of 1 that overwrites the head of the
