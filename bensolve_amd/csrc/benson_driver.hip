@@ -283,11 +283,10 @@ int bslv_benson_set_canonical(bslv_benson *h, int on)
     if (!h) { set_error("bslv_benson_set_canonical: bad argument"); return BSLV_E_ARG; }
     if (on && h->hom) { set_error("bslv_benson_set_canonical: a homogeneous engine cuts with (w + alpha eta, alpha), which has another normal cone"); return BSLV_E_ARG; }
     if (!on) { h->canonical = false; return bslv_lpq_set_canonical(h->lp, 0, nullptr); }
-    if (bslv_lpq_is_revised(h->lp)) return bslv_lpq_set_canonical(h->lp, 1, h->c.data());      // (answers BSLV_E_ARG with its message)
     const int q = h->q, r = h->r;
     h->canon_dir.assign(r, 0.0);
     for (int j = 0; j < r; j++) for (int k = 0; k < q; k++) h->canon_dir[j] += h->R[(size_t)k * r + j] * (1.0 + hash01(k));
-    h->canonical = true;      // (the LP engine gets the switch with the first batch of P2 LPs: the weighted-sum LPs of PART 1 are not P2(v))
+    h->canonical = true;      // (the LP engine gets the switch with the first batch of P2 LPs: the weighted-sum LPs of PART 1 are not P2(v); a revised engine has no switch and gets the direction with every call, see solve_local)
     return 0;
 }
 int bslv_benson_get_canonical(const bslv_benson *h) { return h && h->canonical; }
@@ -836,8 +835,13 @@ int bslv_benson_solve_local_ctx(bslv_benson *h, int ctx, double *records, int *p
     }
     for (int k = 0; k < 4; k++) h->last_canon[k] = 0;
     auto count_canonical = [h]() { long cs[4]; if (bslv_lpq_last_canonical_stats(h->lp, cs) == 0) for (int k = 0; k < 4; k++) { h->last_canon[k] += cs[k]; h->tot_canon[k] += cs[k]; } };
-    if (h->canonical && !bslv_lpq_get_canonical(h->lp) && (rc = bslv_lpq_set_canonical(h->lp, 1, h->canon_dir.data()))) return rc;      // (stays on: the retries below solve with it too)
-    if ((rc = bslv_lpq_solve_batch(h->lp, nl, src.data(), dst.data(), vlo.data(), vup.data(), st.data(), it.data()))) return rc;
+    // (a revised LP engine has no switch: there the batch and its retries get the direction per call, bslv_lpq_solve_batch_canonical)
+    const bool canon_call = h->canonical && bslv_lpq_is_revised(h->lp);
+    auto solve = [h, canon_call](int n, const int *s, const int *d, const double *lo, const double *up, int *stat, int *iter) {
+        return canon_call ? bslv_lpq_solve_batch_canonical(h->lp, h->canon_dir.data(), n, s, d, lo, up, stat, iter) : bslv_lpq_solve_batch(h->lp, n, s, d, lo, up, stat, iter);
+    };
+    if (h->canonical && !canon_call && !bslv_lpq_get_canonical(h->lp) && (rc = bslv_lpq_set_canonical(h->lp, 1, h->canon_dir.data()))) return rc;      // (stays on: the retries below solve with it too)
+    if ((rc = solve(nl, src.data(), dst.data(), vlo.data(), vup.data(), st.data(), it.data()))) return rc;
     count_canonical();
     {
         // The reference's retry (bslv_lp.c:222-227: undefined -> standard basis -> solve again), in two stages.  A tableau is
@@ -862,7 +866,7 @@ int bslv_benson_solve_local_ctx(bslv_benson *h, int ctx, double *records, int *p
                 memcpy(&up2[(size_t)t * r], &vup[(size_t)redo[t] * r], r * sizeof(double));
                 if (stage >= 1 && (rc = bslv_lpq_reset_slot(h->lp, d2[t]))) return rc;
             }
-            if ((rc = bslv_lpq_solve_batch(h->lp, nr, s2.data(), d2.data(), lo2.data(), up2.data(), st2.data(), it2.data()))) return rc;
+            if ((rc = solve(nr, s2.data(), d2.data(), lo2.data(), up2.data(), st2.data(), it2.data()))) return rc;
             count_canonical();
             std::vector<int> still;
             for (int t = 0; t < nr; t++) {

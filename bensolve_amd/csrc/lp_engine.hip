@@ -2013,9 +2013,53 @@ __device__ __forceinline__ void tie_finish(const BatchView &Bv, const TieView &T
         if (why >= 0) atomicAdd(&Tv.stat[why], 1);
     }
 }
+// revised form, entry of the tie phase: g = sum over the shifted nonbasic per-LP variables of T[:, j] dir, T[:, j] = -B^-1 K_k through the
+// pending steps.  The columns are combined first, u = sum dir_t K_kt in ascending t (K_k = e_k for k < M, a CSC column of -A otherwise:
+// the unit vectors come first and touch a row each, the CSC columns follow one after the other, so every u_i is summed in that order),
+// then ONE product with B^-1 as stored and the pending steps in order -- fetch_col_revised with u in place of K_kq -- instead of a
+// column fetch per variable: the per-LP range can be as long as M.  u lies where the next pivot row's rho will (free until then).
+__device__ __forceinline__ void tie_entry_revised(const LpView &L, const TieView &Tv, const SelCtx &c, double *g)
+{
+    const int tid = threadIdx.x, NT = (int)blockDim.x, M = L.M, ldt = L.ldt;
+    double *u = c.prow0 + (size_t)c.np * ldt;
+    for (int i = tid; i < M; i += NT) u[i] = 0.0;
+    __syncthreads();
+    for (int t = tid; t < L.vcnt; t += NT) {
+        const int k = L.vfirst + t, p = c.pos[k];
+        if (k < M && p < 0 && c.nstat[-1 - p] != NS_F) u[k] = Tv.dir[t];
+    }
+    for (int t = max(0, M - L.vfirst); t < L.vcnt; t++) {
+        const int k = L.vfirst + t, p = c.pos[k];
+        if (p >= 0 || c.nstat[-1 - p] == NS_F) continue;      // (basic, or free at zero: no bound to move with -- the same for every thread)
+        __syncthreads();
+        const double dt = Tv.dir[t];
+        for (int e = L.cptr[k - M] + tid; e < L.cptr[k - M + 1]; e += NT) u[L.cidx[e]] = fma(-L.cval[e], dt, u[L.cidx[e]]);
+    }
+    __syncthreads();
+    for (int i = tid; i < M; i += NT) {           // (B^-1 as stored) u, in ascending k
+        const double *Bi = c.T0 + (size_t)i * ldt;
+        double v = 0.0;
+        for (int k = 0; k < M; k++) { const double uk = u[k]; if (uk != 0.0) v = fma(uk, Bi[k], v); }
+        g[i] = v;
+    }
+    for (int sp = 0; sp < c.np; sp++) {           // ... through the pending pivots, in order
+        __syncthreads();
+        const PivDesc d = c.pd[sp];
+        const double vr = g[d.r];
+        __syncthreads();
+        for (int i = tid; i < M; i += NT) g[i] = i == d.r ? -d.p * vr : fma(-c.pcol0[(size_t)sp * L.Mp1p + i], vr, g[i]);
+    }
+    __syncthreads();
+    for (int i = tid; i < M; i += NT) g[i] = -g[i];
+}
 // One tie pivot of LP b by the calling workgroup; false when the LP cannot select again before the next pass (finished, KP pivots pending).
 // sv, si, p_d, s_g: LDS of the kernel (see SelShared for why it is handed down).
-__device__ __forceinline__ bool tie_once(const LpView &L, const BatchView &Bv, const TieView &Tv, const int b, double *sv, int *si, PivDesc *p_d, double *s_g)
+// REV (k_select_tie_rev: a slot holds B^-1): g on entry from one product with B^-1 (tie_entry_revised), the pivot row and the entering
+// column by fetch_row / fetch_col's revised variants (xr, xdyn: the LDS of the row fetch, see fetch_row_revised), and select_once's
+// cross-check of the pivot element between the two -- an LP that fails it commits nothing and leaves the phase OPTIMAL on the basis
+// it had reached (Tv.stat[3]).  Everything else is the one text of both forms.
+template <bool REV = false>
+__device__ __forceinline__ bool tie_once(const LpView &L, const BatchView &Bv, const TieView &Tv, const int b, double *sv, int *si, PivDesc *p_d, double *s_g, int *xr = nullptr, unsigned char *xdyn = nullptr)
 {
     const int tid = threadIdx.x, NT = (int)blockDim.x;
     const int state = Tv.state[b], np = Bv.npend[b], titer = Tv.iters[b];
@@ -2028,6 +2072,8 @@ __device__ __forceinline__ bool tie_once(const LpView &L, const BatchView &Bv, c
     __syncthreads();                           // (everyone has read the LP's state before thread 0 changes it)
     if (state == TIE_NEW) {
         // entry: g through the pending pivots, one column gather per nonbasic per-LP variable
+        if constexpr (REV) tie_entry_revised(L, Tv, c, g);
+        else
         for (int i = tid; i < M; i += NT) {
             double acc = 0.0;
             for (int t = 0; t < L.vcnt; t++) {
@@ -2057,7 +2103,7 @@ __device__ __forceinline__ bool tie_once(const LpView &L, const BatchView &Bv, c
     if (titer >= Tv.cap) { tie_finish(Bv, Tv, b, 3); return false; }
     const int r = best.i >> 1; const bool below = best.i & 1;
     const double sgn = below ? 1.0 : -1.0;
-    fetch_row<true>(L, Bv, c, r);
+    if constexpr (REV) fetch_row<false, true>(L, Bv, c, r, xr, xdyn); else fetch_row<true>(L, Bv, c, r);
     // the dual ratio test of select_once, on the true reduced costs
     double rmax = 0.0;
     for (int j = tid; j < N; j += NT) rmax = fmax(rmax, fabs(row[j]));
@@ -2077,8 +2123,14 @@ __device__ __forceinline__ bool tie_once(const LpView &L, const BatchView &Bv, c
     }
     piv = block_argmax(piv, sv, si);
     const int q = piv.i;
+    if constexpr (REV) fetch_col(L, c, q);      // (the tableau form gathers its column in Phase D)
     // Phase C: the descriptor, the basis heads -- and the step of length zero
     if (tid == 0) {
+        // (revised form: select_once's cross-check of the pivot element, the row's against the column's, with its test hook)
+        if (REV && (!(fabs(row[q] - pc[r]) <= 1e-8 * (1.0 + fabs(row[q]))) || (b == L.drift_b && Bv.iters[b] + 1 == L.drift_p))) {
+            if (L.trace == b) printf("lp %d it %d (tie phase): pivot element from the row %.17g, from the column %.17g: B^-1 has drifted\n", b, Bv.iters[b], row[q], pc[r]);
+            p_d->r = -1;
+        } else {
         const double sk = tie_shift(L, Tv, c.bh[r]), sq = c.nstat[q] == NS_F ? 0.0 : tie_shift(L, Tv, c.nh[q]);
         const double br = beta[r], xq = c.xN[q], gr = g[r];
         PivDesc d = commit_pivot(L, Bv, c, r, q, below, bland, Bv.iters[b], Bv.verified[b], MODE_PIVOT, drow, false, 0, false);
@@ -2089,14 +2141,16 @@ __device__ __forceinline__ bool tie_once(const LpView &L, const BatchView &Bv, c
         s_g[0] = gr - sk; s_g[1] = sq;
         Tv.iters[b] = titer + 1;
         atomicAdd(&Tv.stat[1], 1);
+        }
     }
     __syncthreads();
     const PivDesc d = *p_d;
+    if constexpr (REV) if (d.r < 0) { tie_finish(Bv, Tv, b, 3); return false; }      // (given up: the optimum is known, the basis reached stays)
     const double gp = s_g[0], sq = s_g[1];     // rate at which the leaving row crosses its bound; shift of the entering variable's own bound
     // Phase D: the multipliers of all rows; g follows the pivot as beta does in select_once (beta itself: a step of length zero)
     for (int i = tid; i <= M; i += NT) {
         if (i == r) { pc[i] = 0.0; beta[i] = d.enter_val; g[i] = fma(-gp, d.p, sq); continue; }
-        const double f = (i == M ? drow[q] : virt_entry(c.T0[(size_t)i * ld + q], i, q, np, c.pd, c.prow0, c.pcol0, ld, L.Mp1p)) * d.p;
+        const double f = (i == M ? drow[q] : (REV ? pc[i] : virt_entry(c.T0[(size_t)i * ld + q], i, q, np, c.pd, c.prow0, c.pcol0, ld, L.Mp1p))) * d.p;
         pc[i] = f;
         if (i < M) g[i] = fma(-f, gp, g[i]);
     }
@@ -2120,6 +2174,27 @@ __global__ __launch_bounds__(NT_BIG) void k_select_tie(LpView L, BatchView Bv, T
     for (int sdx = 0; sdx < nsel; sdx++) {
         if (sdx) __syncthreads();
         if (!tie_once(L, Bv, Tv, b, sv, si, &s_d, s_g)) break;
+    }
+}
+// k_select_tie for the revised form: what bslv_lpq_solve_batch_canonical launches there (tie_once<true>), with helper workgroups for the
+// sparse products of the pivot rows as in k_select.  Like k_select_p1_rev it declares its LDS itself -- the words of the revised form's
+// row fetch with it -- and hands it down, under a dynamic-LDS name of its own (rho alone): the kernels above compile to what they always
+// did.  A tie pivot is a rank-1 step on B^-1 like any other and counts in the slot's age; no periodic refactorisation runs inside the phase.
+extern __shared__ unsigned char dyn_tie_rev[];
+__global__ __launch_bounds__(NT_BIG) void k_select_tie_rev(LpView L, BatchView Bv, TieView Tv, const int *active, int nact, int nsel)
+{
+    __shared__ SelSharedDvx xs;
+    __shared__ double s_g[2];
+    if ((int)blockIdx.x >= nact) return;
+    const int b = active[blockIdx.x];
+    if (blockIdx.y > 0) { rev_helper<true>(L, Bv, b, xs.rv, dyn_tie_rev); return; }
+    for (int sdx = 0; sdx < nsel; sdx++) {
+        if (sdx) __syncthreads();
+        if (!tie_once<true>(L, Bv, Tv, b, xs.sv, xs.si, &xs.d, s_g, xs.rv, dyn_tie_rev)) break;
+    }
+    if (L.helpers > 1) {                       // every path of the LP's own workgroup ends here: the helpers may go
+        __syncthreads();
+        if (threadIdx.x == 0) __hip_atomic_store(&Bv.hmail[(size_t)b * 8], (L.launch_id << 8) | 0xFF, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
 
@@ -2932,6 +3007,9 @@ struct bslv_lpq {
     // cost range that one was set for (indices of the model as given)
     TiePhase tie, tie_obj;
     int cobj_first = 0, cobj_cnt = 0;
+    // bslv_lpq_solve_batch_canonical: the direction of the call (device; on while the call runs).  The per-LP state and the counters of
+    // its phase are `tie`'s, whose switch and direction the call leaves alone
+    TiePhase tie_call;
     // refactorisation of the revised form (bslv_lpq_refactor, bslv_lpq_set_refactor): the switch, the marks of the last batch (device / host),
     // the replay's per-LP lists (the counters of the last solve call or explicit refactor: last.rfx)
     bool refactor_on = false;
@@ -2956,7 +3034,7 @@ struct bslv_lpq {
     int *lb_nst_d = nullptr; double *lb_xv_d = nullptr; size_t lb_cap = 0;
     long last_rebuild[4] = {0, 0, 0, 0};
     // dynamic LDS (candidate sort of the bound flipping ratio test; revised form: rho) that each selection kernel may use so far, indexed as select_kernel is
-    size_t select_lds_max[3][4] = {{64 * 1024, 64 * 1024, 64 * 1024, 64 * 1024}, {64 * 1024, 64 * 1024, 64 * 1024, 64 * 1024}, {64 * 1024, 64 * 1024, 64 * 1024, 64 * 1024}};
+    size_t select_lds_max[3][5] = {{64 * 1024, 64 * 1024, 64 * 1024, 64 * 1024, 64 * 1024}, {64 * 1024, 64 * 1024, 64 * 1024, 64 * 1024, 64 * 1024}, {64 * 1024, 64 * 1024, 64 * 1024, 64 * 1024, 64 * 1024}};
     size_t price_lds_max = 64 * 1024;  // ... of k_rev_price (revised form, new objective: y)
     int obj_batches = 0;               // solve_batch_obj calls so far (BSLV_LP_OBJ_UNDEFINED counts them)
     bool has_boxed = false;            // some variable outside the per-LP range has two finite, non-artificial bounds
@@ -3271,7 +3349,7 @@ void bslv_lpq_destroy(bslv_lpq *h)
     fr(h->raykind_d); fr(h->raystat_d); fr(h->ray_d); fr(h->lb_nst_d); fr(h->lb_xv_d);
     fr(h->age_d); fr(h->age0_d); fr(h->cert_d);
     for (const DevexNorms *r : {&h->dvx, &h->pdv}) { fr(r->norm_d); fr(r->stat_d); }
-    for (const TiePhase *r : {&h->tie, &h->tie_obj}) { fr(r->dir_d); fr(r->g_d); fr(r->state_d); fr(r->iters_d); fr(r->stat_d); }
+    for (const TiePhase *r : {&h->tie, &h->tie_obj, &h->tie_call}) { fr(r->dir_d); fr(r->g_d); fr(r->state_d); fr(r->iters_d); fr(r->stat_d); }
     fr(h->L.T); fr(h->L.beta); fr(h->L.xN); fr(h->L.bh); fr(h->L.nh); fr(h->L.nstat); fr(h->L.pos);
     fr(h->Tstd); fr(h->lb_d); fr(h->ub_d); fr(h->art_d);
     fr(h->dbg_d); fr(h->list_d); fr(h->cptr_d); fr(h->cidx_d); fr(h->rptr_d); fr(h->ridx_d); fr(h->cval_d); fr(h->rval_d); fr(h->cost_d); fr(h->dsl_d); fr(h->trow_d); fr(h->uvec_d); fr(h->xfull_d); fr(h->hmail_d);
@@ -3652,13 +3730,14 @@ struct SelectPlan {
 // The selection kernels by rule (0: the default one, RULE_DVX, RULE_PDV) and shape; bslv_lpq::select_lds_max has the same indices
 // k_select<false>; the extended selection k_select<true>; ... with phase 1 in its primal steps, the PRIMAL and REPAIR methods: k_select_p1
 // in the tableau form, k_select_p1_rev in the revised form (the default rule only: plan_select gives such a batch no other)
-enum { SHAPE_PLAIN, SHAPE_EXT, SHAPE_P1, SHAPE_P1_REV };
+// (SHAPE_TIE_REV: k_select_tie_rev, the tie phase of the revised form -- no selection of a plan, listed here for its LDS limit)
+enum { SHAPE_PLAIN, SHAPE_EXT, SHAPE_P1, SHAPE_P1_REV, SHAPE_TIE_REV };
 static const void *select_kernel(int rule, int shape)
 {
-    static const void *const k[3][4] = {
-        {(const void *)k_select<false>, (const void *)k_select<true>, (const void *)k_select_p1, (const void *)k_select_p1_rev},
-        {(const void *)k_select_priced<RULE_DVX, false, false>, (const void *)k_select_priced<RULE_DVX, false, true>, (const void *)k_select_priced<RULE_DVX, true, true>, nullptr},
-        {nullptr, (const void *)k_select_priced<RULE_PDV, false, true>, (const void *)k_select_priced<RULE_PDV, true, true>, nullptr}};      // (primal steps live in the extended selection: without one the batch is refused, plan_select)
+    static const void *const k[3][5] = {
+        {(const void *)k_select<false>, (const void *)k_select<true>, (const void *)k_select_p1, (const void *)k_select_p1_rev, (const void *)k_select_tie_rev},
+        {(const void *)k_select_priced<RULE_DVX, false, false>, (const void *)k_select_priced<RULE_DVX, false, true>, (const void *)k_select_priced<RULE_DVX, true, true>, nullptr, nullptr},
+        {nullptr, (const void *)k_select_priced<RULE_PDV, false, true>, (const void *)k_select_priced<RULE_PDV, true, true>, nullptr, nullptr}};      // (primal steps live in the extended selection: without one the batch is refused, plan_select)
     return k[rule][shape];
 }
 // the kernel of (rule, shape) may be launched with `want` bytes of dynamic LDS, its limit raised if need be
@@ -3723,18 +3802,20 @@ static int plan_select(bslv_lpq *h, int B, const double *vlo, const double *vup,
     plan->cpt = (cache && !dvx && !bfrt && !L.rev && plan->nt == NT && L.N <= 6 * NT) ? (L.N <= 2 * NT ? 2 : (L.N <= 4 * NT ? 4 : 6)) : 0;
     return 0;
 }
+// revised form: helper workgroups for the sparse products of a tableau row (rev_helper), as many per LP as the chip holds beside the
+// `running` LPs' own workgroups (of nt threads) without anyone waiting for a place
+static int rev_helper_count(const LpView &L, int nt, int running)
+{
+    if (!L.rev || nt != NT_BIG) return 1;
+    static const int hmax = getenv("BSLV_REV_HELPERS") ? std::max(1, atoi(getenv("BSLV_REV_HELPERS"))) : 32;
+    return std::max(1, std::min(std::min(hmax, (L.ld + 2047) / 2048), 256 / std::max(1, running)));
+}
 // the KP selections of one round for the `running` LPs of the active list
 static void launch_select(bslv_lpq *h, const SelectPlan &p, const BatchView &bv, int running)
 {
     LpView &L = h->L; hipStream_t s = h->stream;
     for (int lev = 0; lev < KP; lev += p.per_launch) {
-        // revised form: helper workgroups for the sparse products of a tableau row (rev_helper), as many per LP as the chip holds
-        // beside the LPs' own workgroups without anyone waiting for a place
-        int helpers = 1;
-        if (L.rev && p.nt == NT_BIG) {
-            static const int hmax = getenv("BSLV_REV_HELPERS") ? std::max(1, atoi(getenv("BSLV_REV_HELPERS"))) : 32;
-            helpers = std::max(1, std::min(std::min(hmax, (L.ld + 2047) / 2048), 256 / std::max(1, running)));
-        }
+        const int helpers = rev_helper_count(L, p.nt, running);
         L.helpers = helpers; L.launch_id = (++h->launch_seq) & 0x3FFFFF;
         if (p.cpt == 2) hipLaunchKernelGGL(k_select_cached<2>, dim3(running), dim3(NT), 0, s, L, bv, h->active_d, running, p.per_launch);
         else if (p.cpt == 4) hipLaunchKernelGGL(k_select_cached<4>, dim3(running), dim3(NT), 0, s, L, bv, h->active_d, running, p.per_launch);
@@ -4171,7 +4252,7 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
     }
     if (const char *e = getenv("BSLV_UPD_GRID")) h->upd_grid = std::max(64, atoi(e));
     {   // one work-list length per lock-step iteration, zeroed here: no reset between iterations
-        const int need = L.maxit + 64 + ((h->tie.on || h->tie_obj.on) ? tie_rounds_max(L) : 0);      // (the rounds of a tie phase count on behind the others')
+        const int need = L.maxit + 64 + ((h->tie.on || h->tie_obj.on || h->tie_call.on) ? tie_rounds_max(L) : 0);      // (the rounds of a tie phase count on behind the others')
         if ((rc = ensure_nwork(h, need, need))) return rc;
     }
     HIP_TRY(hipMemsetAsync(h->xstat_d, 0, 8 * sizeof(int), s));
@@ -4342,13 +4423,30 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
         for (int k = 0; k < nt; k++) { const int b = h->active_h[k]; if (h->status_h[b] == ST_RUNNING) { h->status_h[b] = BSLV_LP_OPTIMAL; r.last[3]++; HIP_TRY(hipMemcpy(h->status_d + b, h->status_h + b, sizeof(int), hipMemcpyHostToDevice)); } }
         return 0;
     };
+    long tie_before[4] = {0, 0, 0, 0};
+    if (resolve && h->tie_call.on) for (int k = 0; k < 4; k++) tie_before[k] = h->tie.last[k];      // (bslv_lpq_solve_batch_canonical: the rescue's solves count with the call)
     for (int k = 0; k < 4; k++) h->tie.last[k] = 0;
     if (L.objmode) for (int k = 0; k < 4; k++) h->tie_obj.last[k] = 0;
-    if (h->tie.on && !L.objmode && !L.rev && L.vcnt > 0 && !max_rounds) {
+    // (the engine's switch is the tableau form's alone: bslv_lpq_set_canonical; the call's own direction holds in both forms)
+    if ((h->tie.on || h->tie_call.on) && !L.objmode && L.vcnt > 0 && !max_rounds) {
         if ((rc = ensure_tie(h, h->tie, L.Mp1p))) return rc;
-        const TieView tv = h->tie.view(tie_cap(L));
-        if ((rc = tie_phase(h->tie, [&](int nt) { hipLaunchKernelGGL(k_select_tie, dim3(nt), dim3(plan.nt), 0, s, L, bv, tv, h->active_d, nt, KP); }))) return rc;
+        TieView tv = h->tie.view(tie_cap(L));
+        if (h->tie_call.on) tv.dir = h->tie_call.dir_d;
+        if (!L.rev) {
+            if ((rc = tie_phase(h->tie, [&](int nt) { hipLaunchKernelGGL(k_select_tie, dim3(nt), dim3(plan.nt), 0, s, L, bv, tv, h->active_d, nt, KP); }))) return rc;
+        } else {
+            // revised form: the dynamic LDS is rho alone; helpers and the launch number per launch, as launch_select sets them
+            const size_t want = (size_t)L.ldt * sizeof(double);
+            L.rho_off = select_lds_fits(h, 0, SHAPE_TIE_REV, want) ? 0 : -1;
+            const size_t lds = L.rho_off == 0 ? want : 0;
+            if ((rc = tie_phase(h->tie, [&](int nt) {
+                    const int helpers = rev_helper_count(L, plan.nt, nt);
+                    L.helpers = helpers; L.launch_id = (++h->launch_seq) & 0x3FFFFF;
+                    hipLaunchKernelGGL(k_select_tie_rev, dim3(nt, helpers), dim3(plan.nt), lds, s, L, bv, tv, h->active_d, nt, KP);
+                }))) return rc;
+        }
     }
+    for (int k = 0; k < 4; k++) h->tie.last[k] += tie_before[k];
     if (h->tie_obj.on && L.objmode && !L.rev && !max_rounds) {
         if ((rc = ensure_tie(h, h->tie_obj, L.ld))) return rc;
         const TieView tv = h->tie_obj.view(tie_cap(L));
@@ -4441,6 +4539,7 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
     {
         static const bool tm = getenv("BSLV_LP_TIMING") != nullptr;
         if (tm) fprintf(stderr, "lp solve_batch: %s form %d x %d, B %d, %d lock-step rounds, %ld pivots, %ld passes, %.1f ms; %d parents, largest family %d, %s\n", L.rev ? "revised" : "tableau", L.M, L.N, B, it, st.pivots, st.passes, st.total_ms, h->last_init_parents, h->last_init_family, h->last_init_chunks ? "k_init_grouped" : "k_init");
+        if (tm && (h->tie.on || h->tie_call.on) && !L.objmode) fprintf(stderr, "lp tie phase%s: %ld LPs entered, %ld tie pivots, %ld without an entering candidate, %ld gave up, %d rounds\n", h->tie_call.on ? " (per call)" : "", h->tie.last[0], h->tie.last[1], h->tie.last[2], h->tie.last[3], tie_rounds);
         if (tm && period > 0) fprintf(stderr, "lp period %d: %ld refactorisations at the start, %ld during the rounds, %ld replay pivots, largest age at a selection %ld, %ld replay passes, %.1f ms in refactorisations\n", period, h->last.per[0], h->last.per[1], h->last.per[2], h->last.per[3], h->per.passes, h->per.ms);
         if (tm && h->park.cap) fprintf(stderr, "lp park (totals): %ld parked, %ld unparked for a child, %ld because their source was about to be overwritten, %ld dropped unused, %zu live\n", h->park.stats[0], h->park.stats[1], h->park.stats[2], h->park.stats[3], h->park.live.size());
     }
@@ -4887,6 +4986,22 @@ int bslv_lpq_set_canonical(bslv_lpq *h, int on, const double *dir)
     return 0;
 }
 int bslv_lpq_get_canonical(const bslv_lpq *h) { return h && h->tie.on; }
+// ... for this call only, towards the canonical basis for `dir`: see bslv_hip.h.  The engine's own switch and direction are neither read
+// nor changed (the phase runs with the call's direction, in `tie`'s per-LP state and counters); in the revised form this is the way to
+// the tie phase (k_select_tie_rev), which bslv_lpq_set_canonical refuses there.
+int bslv_lpq_solve_batch_canonical(bslv_lpq *h, const double *dir, int B, const int *src, const int *dst, const double *vlo,
+                                   const double *vup, int *status, int *iters)
+{
+    if (!h || (!dir && h->L.vcnt > 0)) { set_error("bslv_lpq_solve_batch_canonical: bad argument"); return BSLV_E_ARG; }
+    const int vc = h->L.vcnt;
+    for (int j = 0; j < vc; j++) if (!std::isfinite(dir[j])) { set_error("bslv_lpq_solve_batch_canonical: dir[%d] is not finite", j); return BSLV_E_ARG; }
+    if (vc > 0) { if (const int rc = tie_upload_dir(h, h->tie_call, dir, vc)) return rc; }
+    h->call_method = h->method;
+    h->tie_call.on = vc > 0;
+    const int rc = solve_batch_rescue(h, B, src, dst, vlo, vup, 0, 0, nullptr, status, iters);
+    h->tie_call.on = false;
+    return rc;
+}
 int bslv_lpq_last_canonical_stats(const bslv_lpq *h, long out[4])
 {
     if (!h || !out) return BSLV_E_ARG;

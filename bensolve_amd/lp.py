@@ -184,6 +184,24 @@ class LpEngine:
                                                    vup.ctypes.data, status.ctypes.data, iters.ctypes.data))
         return status, iters
 
+    def solve_batch_canonical(self, dir, src, dst, vlo, vup):
+        """solve_batch followed by the tie phase towards the canonical optimal basis for `dir` (var_cnt values), for this call only; the
+        engine's own switch and direction stay what they are.  Works in both forms; in the revised form the only way to the tie phase
+        (bslv_lpq_solve_batch_canonical).  dir=None hands the library a null pointer (its BSLV_E_ARG raises BslvError, like a NaN)."""
+        src = np.ascontiguousarray(src, np.int32)
+        dst = np.ascontiguousarray(dst, np.int32)
+        B = len(src)
+        d = None if dir is None else np.ascontiguousarray(dir, np.float64).reshape(self.vcnt)
+        vlo = np.ascontiguousarray(vlo, np.float64).reshape(B, self.vcnt)
+        vup = np.ascontiguousarray(vup, np.float64).reshape(B, self.vcnt)
+        status = np.empty(B, np.int32)
+        iters = np.empty(B, np.int32)
+        self.lib.bslv_lpq_solve_batch_canonical.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 6
+        self.lib.bslv_lpq_solve_batch_canonical.restype = ctypes.c_int
+        check(self.lib.bslv_lpq_solve_batch_canonical(self.h, None if d is None else d.ctypes.data, B, src.ctypes.data, dst.ctypes.data,
+                                                      vlo.ctypes.data, vup.ctypes.data, status.ctypes.data, iters.ctypes.data))
+        return status, iters
+
     def solve_batch_obj(self, src, dst, cost_first, costs, vlo=None, vup=None):
         """LPs that differ in the objective: costs[b, t] on variable cost_first + t (bslv_lpq_solve_batch_obj)."""
         src = np.ascontiguousarray(src, np.int32)

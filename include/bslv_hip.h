@@ -505,6 +505,22 @@ int  bslv_lpq_last_primal_pricing_norms(bslv_lpq *h, int b, double *t /* M + N *
 int  bslv_lpq_set_canonical(bslv_lpq *h, int on, const double *dir /* var_cnt, NULL with on = 0 */);
 int  bslv_lpq_get_canonical(const bslv_lpq *h);
 int  bslv_lpq_last_canonical_stats(const bslv_lpq *h, long out[4]);
+/* ... PER CALL, in both forms: one solve_batch under the engine's own method, followed by the tie phase towards the canonical basis for
+ * dir, with the meaning documented at bslv_lpq_set_canonical, for THIS batch only.  The engine's own switch and its stored direction are
+ * neither read nor changed (bslv_lpq_get_canonical answers what it did; a later solve_batch runs as if the call had not been made).  In
+ * the tableau form the call is set_canonical(1, dir); solve_batch(..); <the old switch and direction back>, bit for bit.  In the
+ * REVISED form, where bslv_lpq_set_canonical answers BSLV_E_ARG, this call is the way to the tie phase (lp_engine.hip,
+ * k_select_tie_rev): g comes from one product with B^-1, the pivot row and the entering column from the sparse products of a
+ * selection (helper workgroups included), and the pivot element is cross-checked between the two as in every selection of that form.
+ * A tie pivot is a rank-1 step on B^-1 and counts in iters[] and in the slot's age (bslv_lpq_slot_age); no periodic refactorisation
+ * runs inside the phase.  With bslv_lpq_set_refactor the rescue re-solves before the tie phase of the LPs it takes, as in any
+ * solve_batch; only LPs that end OPTIMAL enter the phase.
+ * h == NULL, dir == NULL with var_cnt > 0 or a non-finite dir[j]: BSLV_E_ARG, nothing changed.  var_cnt == 0: the call is solve_batch.
+ * bslv_lpq_last_canonical_stats covers the call (the rescue's solves included); for this call [3] reads "gave up: at the cap, or
+ * (revised form) on a drifted inverse" -- an LP whose cross-check fails commits nothing, keeps the optimal basis it had reached with
+ * the status OPTIMAL and is not marked for the rescue: the optimum is already known. */
+int  bslv_lpq_solve_batch_canonical(bslv_lpq *h, const double *dir /* var_cnt */, int B, const int *src, const int *dst,
+                                    const double *vlo, const double *vup, int *status, int *iters);
 /* CANONICAL OPTIMAL POINTS of objective batches.  The dual variant builds the cut of the lower image from the optimal point y = P x of
  * P1(w) (phase2_dual takes it from lp_primal_solution_cols, bslv_algs.c:1479-1486).  Where w is the normal of a face of the upper
  * image of dimension >= 1 the LP is dual degenerate: every y of that face is optimal and the pivoting ends in P x of whichever vertex x
