@@ -107,15 +107,25 @@ CONFIGS = {
 
 def write_vlp(prob, path):
     """Write `prob` in the reference's .vlp format (bslv_vlp.c:275-588, ex/prob2vlp.m:105-182)
-    with %.17g numbers so that file and in-memory data are bit-identical."""
+    with %.17g numbers so that file and in-memory data are bit-identical.  Optional keys cone_kind (1 'cone', 2 'dualcone'), gen
+    (q x K, generators as columns) and c (q) become the 'cone K nz' / 'dualcone K nz' header fields and the 'k i j v' lines
+    (j = 0: c), as read_vlp reads them; without cone_kind the file has no cone data (the standard cone, c = 1)."""
     A, P = prob["A"], prob["P"]
     m, n, q = prob["m"], prob["n"], prob["q"]
     ai, aj = np.nonzero(A)
     pi, pj = np.nonzero(P)
+    kind = int(prob.get("cone_kind") or 0)
+    gen = np.asarray(prob["gen"], np.float64).reshape(q, -1) if kind and prob.get("gen") is not None else np.zeros((q, 0))
+    c = np.asarray(prob["c"], np.float64) if kind and prob.get("c") is not None else np.zeros(q)
+    gi, gj = np.nonzero(gen)
+    ci = np.flatnonzero(c)
+    cone = " %s %d %d" % ("dualcone" if kind == 2 else "cone", gen.shape[1], len(gi) + len(ci)) if kind else ""
     with open(path, "w") as f:
-        f.write("p vlp %s %d %d %d %d %d\n" % ("min" if prob["optdir"] == 1 else "max", m, n, len(ai), q, len(pi)))
+        f.write("p vlp %s %d %d %d %d %d%s\n" % ("min" if prob["optdir"] == 1 else "max", m, n, len(ai), q, len(pi), cone))
         f.write("".join("a %d %d %.17g\n" % (i + 1, j + 1, A[i, j]) for i, j in zip(ai, aj)))
         f.write("".join("o %d %d %.17g\n" % (i + 1, j + 1, P[i, j]) for i, j in zip(pi, pj)))
+        f.write("".join("k %d %d %.17g\n" % (i + 1, j + 1, gen[i, j]) for i, j in zip(gi, gj)))
+        f.write("".join("k %d 0 %.17g\n" % (i + 1, c[i]) for i in ci))
         for kind, types, lb, ub, cnt in (("i", prob["rtype"], prob["rlb"], prob["rub"], m),
                                          ("j", prob["ctype"], prob["clb"], prob["cub"], n)):
             for k in range(cnt):

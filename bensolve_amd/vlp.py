@@ -42,7 +42,12 @@ def solve_primal(prob, cone_kind=0, gen=None, c=None, bounded=False, eps_phase0=
     dump = slot-indexed dump of the result polyhedron with the sign changes of poly_trans_primal applied).  alg_phase2 = "dual":
     phase2_dual; the dump is then given with the sides swapped back, so that X / pi are the upper image in both cases.
     canonical (with alg_phase2 = "dual"): every P1(w) ends in its canonical optimal point (BSLV_VLP_CANONICAL, include/bslv_hip.h);
-    out["canonical_obj"] then holds the tie phase's counters summed over phase 2 (all zero with the flag off)."""
+    out["canonical_obj"] then holds the tie phase's counters summed over phase 2 (all zero with the flag off).
+    preimages (option -s): out["pre_p"] maps an element of the upper image (row of dump["X"]) to its x (n values), out["pre_d"] a
+    vertex of the lower image (row of dump["Y"]) to its (u, w) (m + q values), both as the engine stores them: the writers of the
+    _pre_img_ files multiply u by optdir and w by c_dir.  Elements without a stored pre-image (directions of the lower image) have no
+    key.  With alg_phase2 = "dual" the store of the dual algorithm is freed here (bslv_dual_preimages_free) and
+    out["lower_image_handle"] is the address it was kept under: a key for bslv_dual_preimage_x / _uw, no longer an object."""
     dual2 = alg_phase2 == "dual"
     lib = load_library()
     vp = ctypes.c_void_p
@@ -92,6 +97,31 @@ def solve_primal(prob, cone_kind=0, gen=None, c=None, bounded=False, eps_phase0=
         if info.negate_dual_last:
             d["Y"][:, -1] = -d["Y"][:, -1]
         out["dump"] = d
+        if preimages:
+            m, n = prob["m"], prob["n"]
+            get_p, get_d = (lib.bslv_dual_preimage_x, lib.bslv_dual_preimage_uw) if dual2 else (lib.bslv_benson_preimage_p, lib.bslv_benson_preimage_d)
+            for f in (get_p, get_d):
+                f.argtypes = [vp, ctypes.c_int, vp]
+                f.restype = ctypes.c_int
+            x, uw = np.zeros(n), np.zeros(m + q)
+            out["pre_p"], out["pre_d"] = {}, {}
+            for i in np.flatnonzero(d["pu"]):
+                rc = get_p(h, int(i), x.ctypes.data)
+                if rc == 0:
+                    out["pre_p"][int(i)] = x.copy()
+                elif rc != 1:
+                    check(rc)
+            for k in np.flatnonzero(d["du"]):
+                rc = get_d(h, int(k), uw.ctypes.data)
+                if rc == 0:
+                    out["pre_d"][int(k)] = uw.copy()
+                elif rc != 1:
+                    check(rc)
+            if dual2:
+                lib.bslv_dual_preimages_free.argtypes = [vp]
+                lib.bslv_dual_preimages_free.restype = None
+                lib.bslv_dual_preimages_free(h)
+                out["lower_image_handle"] = h.value
         lib.bslv_benson_destroy.argtypes = [vp]
         lib.bslv_benson_destroy.restype = None
         lib.bslv_poly_destroy.argtypes = [vp]

@@ -11,6 +11,9 @@ expected outputs, no reference text.
                  the reference's own LP solver, GLPK, is not installed: parity unpinned by the reference)
   hybrid_*.npz   outputs of oracle/_ref/bensolve_hybrid (reference driver + reference polyhedron
                  engine + oracle LP) on the ex/*.vlp suite and on small synthetic problems
+  solutions.npz / .json  (`make_golden.py solutions`) the hybrid's -s runs on the general cases of tests/vlp_general_cases.py:
+                 images and c in the .npz; return code, counts, input digest and the residuals of tests/solution_certificate.py
+                 on the hybrid's own files in the .json
 """
 import itertools
 import json
@@ -393,7 +396,50 @@ def make_hybrid():
     json.dump(status, open(os.path.join(HERE, "hybrid_status.json"), "w"), indent=1)
 
 
+def run_hybrid_solution(prob, extra=()):
+    """bensolve_hybrid <case>.vlp -s -m 0 [-b] (primal algorithm: the hybrid's LP shim has no column duals for -a dual -s):
+    (return code, the five files as tests/solution_certificate.load_run reads them, or None)"""
+    import solution_certificate as sc
+    exe = os.path.join(ROOT, "oracle", "_ref", "bensolve_hybrid")
+    with tempfile.TemporaryDirectory() as td:
+        path, base = os.path.join(td, "case.vlp"), os.path.join(td, "out")
+        synth.write_vlp(prob, path)
+        p = subprocess.run([exe, path, "-s", "-m", "0", "-o", base] + list(extra), capture_output=True, text=True, timeout=600)
+        return p.returncode, (sc.load_run(base) if p.returncode == 0 else None)
+
+
+def solution_runs():
+    """(key in the golden files, case, extra options)"""
+    import vlp_general_cases as gc
+    for name in gc.CASES:
+        yield name, name, []
+        if name in gc.BOUNDED:
+            yield name + "+b", name, ["-b"]
+
+
+def make_solutions():
+    import solution_certificate as sc
+    import vlp_general_cases as gc
+    out, meta = {}, {}
+    for key, name, extra in solution_runs():
+        prob = gc.CASES[name]()
+        rc, run = run_hybrid_solution(prob, extra)
+        meta[key] = dict(rc=rc, digest=gc.digest(prob))
+        if rc == 0:
+            meta[key].update(sc.reference_record(prob, run))
+            out[key + "/p_type"] = run["img_p"][:, 0].astype(np.int8); out[key + "/p"] = run["img_p"][:, 1:]
+            out[key + "/d_type"] = run["img_d"][:, 0].astype(np.int8); out[key + "/d"] = run["img_d"][:, 1:]
+            out[key + "/c"] = run["c"]
+        print("solutions", key, {k: v for k, v in meta[key].items() if k not in ("residuals", "digest")},
+              "worst residual / scale %.2g" % max(v["value"] / meta[key]["scale"] for v in meta[key]["residuals"].values()) if rc == 0 else "")
+    np.savez_compressed(os.path.join(HERE, "solutions.npz"), **out)
+    json.dump(meta, open(os.path.join(HERE, "solutions.json"), "w"), indent=1)
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "solutions":
+        make_solutions()
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "large":
         make_poly_large()
         sys.exit(0)
@@ -413,3 +459,4 @@ if __name__ == "__main__":
     make_poly_dims()
     make_lp()
     make_hybrid()
+    make_solutions()

@@ -35,6 +35,32 @@ def test_vlp_roundtrip(tmp_path):
     assert sum(1 for l in lines if l.startswith("i ")) == 7 and sum(1 for l in lines if l.startswith("j ")) == 5
 
 
+def test_vlp_roundtrip_with_cone_data(tmp_path):
+    """write_vlp's 'cone K nz' / 'dualcone K nz' header fields and 'k i j v' lines (j = 0: c) read back bit for bit, by read_vlp
+    and by the product's C reader; a problem without cone_kind is written as before"""
+    import test_vlp_parser as tp
+    base = synth.covering_vlp(6, 4, 3, 2)
+    gen = np.array([[1.0, 0.0, 0.0, 1.0], [0.0, 1.0, 0.0, 1.0], [0.0, 0.0, 1.0, -0.5]])
+    for kind, word, c in ((1, "cone", np.array([1.0, 1.0, 2.0])), (2, "dualcone", None)):
+        prob = dict(base, cone_kind=kind, gen=gen, c=c)
+        path = os.path.join(tmp_path, word + ".vlp")
+        synth.write_vlp(prob, path)
+        nz = np.count_nonzero(gen) + (0 if c is None else 3)
+        assert open(path).readline().split()[8:] == [word, "4", str(nz)]
+        back = synth.read_vlp(path)
+        assert back["cone_kind"] == kind
+        np.testing.assert_array_equal(back["gen"], gen)
+        np.testing.assert_array_equal(back["c"], np.zeros(3) if c is None else c)
+        for k in ("A", "P", "rlb", "rub", "clb", "cub", "rtype", "ctype"):
+            np.testing.assert_array_equal(back[k], base[k])
+        cr = tp.c_read(path)
+        np.testing.assert_array_equal(cr["gen"], gen)
+        np.testing.assert_array_equal(cr["A"], base["A"])
+    plain = os.path.join(tmp_path, "plain.vlp")
+    synth.write_vlp(base, plain)
+    assert len(open(plain).readline().split()) == 8 and not any(l.startswith("k ") for l in open(plain))
+
+
 def test_read_vlp_helper_matches_the_c_reader():
     """bensolve_amd.synth.read_vlp (scripts, tests) against the product's C reader on the committed example files"""
     import ctypes
