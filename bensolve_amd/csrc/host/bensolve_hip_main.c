@@ -29,6 +29,9 @@ static void usage(void)
            "                           against the edge test over all pairs) and print one line: polyhedron check: ... ok, or the counts\n"
            "  -k/-L/-l METHOD, -M N, -f FORMAT, -p   accepted as in the reference's command line; the LP method is recorded in the\n"
            "                           .log (every LP is solved by the engine's dual simplex), no graphics file is written\n"
+           "Environment (with -a dual; both off by default):\n"
+           "  BSLV_CANONICAL_OBJ=1       every P1(w) ends in its canonical optimal point, by the LP engine's switch (tableau form only)\n"
+           "  BSLV_CANONICAL_OBJ_CALL=1  the same, handed to the LP engine with every solve: also under BSLV_LP_REV=1 (revised form)\n"
            );
 }
 

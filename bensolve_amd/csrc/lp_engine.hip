@@ -2229,7 +2229,17 @@ __device__ __forceinline__ bool tie_obj_finish(const BatchView &Bv, const TieVie
 }
 // One tie iteration of LP b by the calling workgroup; false when the LP cannot select again before the next pass (finished, waiting for
 // a refresh, KP pivots pending).  sv, si, p_d: LDS of the kernel (see SelShared for why it is handed down).
-__device__ __forceinline__ bool tie_obj_once(const LpView &L, const BatchView &Bv, const TieView &Tv, const int b, double *sv, int *si, PivDesc *p_d)
+// REV (k_select_tie_obj_rev: a slot holds B^-1 and no tableau row to walk): with T[r][j] = -rho_r . K[nh_j] the row g on entry is ONE
+// tableau row, the one of the synthesised y = sum over the basic variables of the cost range of ddir_t rho_pos(cfirst + t), in ascending
+// t (what rev_price_y does with the costs of the batch, here through the pending pivots): g_j = ddir_{nh[j]} - y . K[nh_j].  y lies
+// where a pivot row's rho would (rev_form_rho) and its products take the pivot rows' path, helpers included (rev_row_of_rho); they
+// write the LP's scratch row (c.row, free until a step fetches its pivot row), from which g is copied.  The entering column and the
+// pivot row come from fetch_col / fetch_row's revised variants (xr, xdyn: the LDS of the row fetch, see fetch_row_revised), with
+// select_once's cross-check of the pivot element between the two -- an LP that fails it commits nothing and leaves the phase OPTIMAL
+// on the basis it had reached (Tv.stat[3]): every step of the phase keeps optimality.  A bound switch fetches no row and has no
+// check.  Everything else is the one text of both forms.
+template <bool REV = false>
+__device__ __forceinline__ bool tie_obj_once(const LpView &L, const BatchView &Bv, const TieView &Tv, const int b, double *sv, int *si, PivDesc *p_d, int *xr = nullptr, unsigned char *xdyn = nullptr)
 {
     const int tid = threadIdx.x, NT = (int)blockDim.x;
     const int state = Tv.state[b], np = Bv.npend[b], titer = Tv.iters[b], mode = Bv.mode[b];
@@ -2242,6 +2252,33 @@ __device__ __forceinline__ bool tie_obj_once(const LpView &L, const BatchView &B
     __syncthreads();                           // (everyone has read the LP's state before thread 0 changes it)
     if (state == TIE_NEW) {
         // entry: g through the pending pivots, at most ccnt tableau rows
+        if constexpr (REV) {
+            const int ldt = L.ldt;
+            double *y_g = c.prow0 + (size_t)np * ldt;
+            double *sy = L.rho_off >= 0 ? reinterpret_cast<double *>(xdyn + L.rho_off) : nullptr;
+            for (int col = tid; col < ldt; col += NT) {      // (a thread owns columns of B^-1 and adds the rows in ascending t: a fixed order)
+                double acc = 0.0;
+                if (col < M)
+                    for (int t = 0; t < L.ccnt; t++) {
+                        const int pr = c.pos[L.cfirst + t];
+                        if (pr >= 0) acc = fma(Tv.dir[t], virt_entry_b(c.T0[(size_t)pr * ldt + col], pr, col, np, c.pd, c.prow0, c.pcol0, ldt, L.Mp1p), acc);
+                    }
+                y_g[col] = acc;
+                if (sy) sy[col] = acc;
+            }
+            __syncthreads();
+            rev_row_of_rho<true>(L, Bv, c, sy ? sy : y_g, xr);
+            __syncthreads();
+            for (int j = tid; j < ld; j += NT) {
+                double v = 0.0;
+                if (j < N) {
+                    v = row[j];
+                    const int kj = c.nh[j] - L.cfirst;
+                    if (kj >= 0 && kj < L.ccnt) v += Tv.dir[kj];      // (as k_rev_price adds the costs)
+                }
+                g[j] = v;
+            }
+        } else
         for (int j = tid; j < ld; j += NT) {
             double v = 0.0;
             if (j < N) {
@@ -2277,7 +2314,7 @@ __device__ __forceinline__ bool tie_obj_once(const LpView &L, const BatchView &B
     const int stq = c.nstat[q], kq = c.nh[q];
     const double gq = g[q], dq = drow[q];
     const double dir = (stq == NS_U || (stq == NS_F && gq > 0.0)) ? -1.0 : 1.0;
-    fetch_col<true>(L, c, q);
+    if constexpr (REV) fetch_col(L, c, q); else fetch_col<true>(L, c, q);
     // primal_step's ratio test (phase 2), on the entering column
     double cmax = 0.0;
     for (int i = tid; i < M; i += NT) cmax = fmax(cmax, fabs(pc[i]));
@@ -2327,15 +2364,22 @@ __device__ __forceinline__ bool tie_obj_once(const LpView &L, const BatchView &B
     }
     const int r = lv.i >> 1;
     const bool below = !(lv.i & 1);          // the leaving variable goes to its lower bound
-    fetch_row<true>(L, Bv, c, r);
+    if constexpr (REV) fetch_row<false, true>(L, Bv, c, r, xr, xdyn); else fetch_row<true>(L, Bv, c, r);
     // the descriptor, the basis heads
     if (tid == 0) {
+        // (revised form: select_once's cross-check of the pivot element, the row's against the column's, with its test hook)
+        if (REV && (!(fabs(row[q] - pc[r]) <= 1e-8 * (1.0 + fabs(row[q]))) || (b == L.drift_b && Bv.iters[b] + 1 == L.drift_p))) {
+            if (L.trace == b) printf("lp %d it %d (tie phase of an objective batch): pivot element from the row %.17g, from the column %.17g: B^-1 has drifted\n", b, Bv.iters[b], row[q], pc[r]);
+            p_d->r = -1;
+        } else {
         *p_d = commit_pivot(L, Bv, c, r, q, below, bland, Bv.iters[b], Bv.verified[b], MODE_PIVOT, g, true, 0, false);
         Tv.iters[b] = titer + 1;
         atomicAdd(&Tv.stat[1], 1);
+        }
     }
     __syncthreads();
     const PivDesc d = *p_d;
+    if constexpr (REV) if (d.r < 0) { tie_obj_finish(Bv, Tv, b, 3); return false; }      // (given up: the optimum is known, the basis reached stays)
     // the multipliers of all rows, beta; the reduced-cost row and g follow the pivot (select_once, Phase D)
     for (int i = tid; i <= M; i += NT) {
         if (i == r) { pc[i] = 0.0; beta[i] = d.enter_val; continue; }
@@ -2366,6 +2410,27 @@ __global__ __launch_bounds__(NT_BIG) void k_select_tie_obj(LpView L, BatchView B
     for (int sdx = 0; sdx < nsel; sdx++) {
         if (sdx) __syncthreads();
         if (!tie_obj_once(L, Bv, Tv, b, sv, si, &s_d)) break;
+    }
+}
+// k_select_tie_obj for the revised form: what bslv_lpq_solve_batch_obj_canonical launches there (tie_obj_once<true>), with helper
+// workgroups for the sparse products of g and of the pivot rows as in k_select.  Like k_select_tie_rev it declares its LDS itself -- the
+// words of the revised form's row fetch with it -- and hands it down, under a dynamic-LDS name of its own (rho alone): the kernels above
+// compile to what they always did.  A tie pivot is a rank-1 step on B^-1 like any other and counts in the slot's age; no periodic
+// refactorisation runs inside the phase.  A slot of this form has no row M: the reduced costs reach it by k_rev_store_d, as after any solve.
+extern __shared__ unsigned char dyn_tie_obj_rev[];
+__global__ __launch_bounds__(NT_BIG) void k_select_tie_obj_rev(LpView L, BatchView Bv, TieView Tv, const int *active, int nact, int nsel)
+{
+    __shared__ SelSharedDvx xs;
+    if ((int)blockIdx.x >= nact) return;
+    const int b = active[blockIdx.x];
+    if (blockIdx.y > 0) { rev_helper<true>(L, Bv, b, xs.rv, dyn_tie_obj_rev); return; }
+    for (int sdx = 0; sdx < nsel; sdx++) {
+        if (sdx) __syncthreads();
+        if (!tie_obj_once<true>(L, Bv, Tv, b, xs.sv, xs.si, &xs.d, xs.rv, dyn_tie_obj_rev)) break;
+    }
+    if (L.helpers > 1) {                       // every path of the LP's own workgroup ends here: the helpers may go
+        __syncthreads();
+        if (threadIdx.x == 0) __hip_atomic_store(&Bv.hmail[(size_t)b * 8], (L.launch_id << 8) | 0xFF, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
 
@@ -3008,8 +3073,9 @@ struct bslv_lpq {
     TiePhase tie, tie_obj;
     int cobj_first = 0, cobj_cnt = 0;
     // bslv_lpq_solve_batch_canonical: the direction of the call (device; on while the call runs).  The per-LP state and the counters of
-    // its phase are `tie`'s, whose switch and direction the call leaves alone
-    TiePhase tie_call;
+    // its phase are `tie`'s, whose switch and direction the call leaves alone.  tie_call_obj: the same for
+    // bslv_lpq_solve_batch_obj_canonical and `tie_obj` (the call's cost range is the batch's own, L.cfirst / L.ccnt)
+    TiePhase tie_call, tie_call_obj;
     // refactorisation of the revised form (bslv_lpq_refactor, bslv_lpq_set_refactor): the switch, the marks of the last batch (device / host),
     // the replay's per-LP lists (the counters of the last solve call or explicit refactor: last.rfx)
     bool refactor_on = false;
@@ -3034,7 +3100,7 @@ struct bslv_lpq {
     int *lb_nst_d = nullptr; double *lb_xv_d = nullptr; size_t lb_cap = 0;
     long last_rebuild[4] = {0, 0, 0, 0};
     // dynamic LDS (candidate sort of the bound flipping ratio test; revised form: rho) that each selection kernel may use so far, indexed as select_kernel is
-    size_t select_lds_max[3][5] = {{64 * 1024, 64 * 1024, 64 * 1024, 64 * 1024, 64 * 1024}, {64 * 1024, 64 * 1024, 64 * 1024, 64 * 1024, 64 * 1024}, {64 * 1024, 64 * 1024, 64 * 1024, 64 * 1024, 64 * 1024}};
+    size_t select_lds_max[3][6] = {{64 * 1024, 64 * 1024, 64 * 1024, 64 * 1024, 64 * 1024, 64 * 1024}, {64 * 1024, 64 * 1024, 64 * 1024, 64 * 1024, 64 * 1024, 64 * 1024}, {64 * 1024, 64 * 1024, 64 * 1024, 64 * 1024, 64 * 1024, 64 * 1024}};
     size_t price_lds_max = 64 * 1024;  // ... of k_rev_price (revised form, new objective: y)
     int obj_batches = 0;               // solve_batch_obj calls so far (BSLV_LP_OBJ_UNDEFINED counts them)
     bool has_boxed = false;            // some variable outside the per-LP range has two finite, non-artificial bounds
@@ -3349,7 +3415,7 @@ void bslv_lpq_destroy(bslv_lpq *h)
     fr(h->raykind_d); fr(h->raystat_d); fr(h->ray_d); fr(h->lb_nst_d); fr(h->lb_xv_d);
     fr(h->age_d); fr(h->age0_d); fr(h->cert_d);
     for (const DevexNorms *r : {&h->dvx, &h->pdv}) { fr(r->norm_d); fr(r->stat_d); }
-    for (const TiePhase *r : {&h->tie, &h->tie_obj, &h->tie_call}) { fr(r->dir_d); fr(r->g_d); fr(r->state_d); fr(r->iters_d); fr(r->stat_d); }
+    for (const TiePhase *r : {&h->tie, &h->tie_obj, &h->tie_call, &h->tie_call_obj}) { fr(r->dir_d); fr(r->g_d); fr(r->state_d); fr(r->iters_d); fr(r->stat_d); }
     fr(h->L.T); fr(h->L.beta); fr(h->L.xN); fr(h->L.bh); fr(h->L.nh); fr(h->L.nstat); fr(h->L.pos);
     fr(h->Tstd); fr(h->lb_d); fr(h->ub_d); fr(h->art_d);
     fr(h->dbg_d); fr(h->list_d); fr(h->cptr_d); fr(h->cidx_d); fr(h->rptr_d); fr(h->ridx_d); fr(h->cval_d); fr(h->rval_d); fr(h->cost_d); fr(h->dsl_d); fr(h->trow_d); fr(h->uvec_d); fr(h->xfull_d); fr(h->hmail_d);
@@ -3730,14 +3796,15 @@ struct SelectPlan {
 // The selection kernels by rule (0: the default one, RULE_DVX, RULE_PDV) and shape; bslv_lpq::select_lds_max has the same indices
 // k_select<false>; the extended selection k_select<true>; ... with phase 1 in its primal steps, the PRIMAL and REPAIR methods: k_select_p1
 // in the tableau form, k_select_p1_rev in the revised form (the default rule only: plan_select gives such a batch no other)
-// (SHAPE_TIE_REV: k_select_tie_rev, the tie phase of the revised form -- no selection of a plan, listed here for its LDS limit)
-enum { SHAPE_PLAIN, SHAPE_EXT, SHAPE_P1, SHAPE_P1_REV, SHAPE_TIE_REV };
+// (SHAPE_TIE_REV, SHAPE_TIE_OBJ_REV: k_select_tie_rev and k_select_tie_obj_rev, the tie phases of the revised form -- no selections
+// of a plan, listed here for their LDS limits)
+enum { SHAPE_PLAIN, SHAPE_EXT, SHAPE_P1, SHAPE_P1_REV, SHAPE_TIE_REV, SHAPE_TIE_OBJ_REV };
 static const void *select_kernel(int rule, int shape)
 {
-    static const void *const k[3][5] = {
-        {(const void *)k_select<false>, (const void *)k_select<true>, (const void *)k_select_p1, (const void *)k_select_p1_rev, (const void *)k_select_tie_rev},
-        {(const void *)k_select_priced<RULE_DVX, false, false>, (const void *)k_select_priced<RULE_DVX, false, true>, (const void *)k_select_priced<RULE_DVX, true, true>, nullptr, nullptr},
-        {nullptr, (const void *)k_select_priced<RULE_PDV, false, true>, (const void *)k_select_priced<RULE_PDV, true, true>, nullptr, nullptr}};      // (primal steps live in the extended selection: without one the batch is refused, plan_select)
+    static const void *const k[3][6] = {
+        {(const void *)k_select<false>, (const void *)k_select<true>, (const void *)k_select_p1, (const void *)k_select_p1_rev, (const void *)k_select_tie_rev, (const void *)k_select_tie_obj_rev},
+        {(const void *)k_select_priced<RULE_DVX, false, false>, (const void *)k_select_priced<RULE_DVX, false, true>, (const void *)k_select_priced<RULE_DVX, true, true>, nullptr, nullptr, nullptr},
+        {nullptr, (const void *)k_select_priced<RULE_PDV, false, true>, (const void *)k_select_priced<RULE_PDV, true, true>, nullptr, nullptr, nullptr}};      // (primal steps live in the extended selection: without one the batch is refused, plan_select)
     return k[rule][shape];
 }
 // the kernel of (rule, shape) may be launched with `want` bytes of dynamic LDS, its limit raised if need be
@@ -4177,11 +4244,12 @@ int bslv_lpq_solve_batch_method(bslv_lpq *h, int method, int B, const int *src, 
 // own cost vector must be zero).  Bounds: those of the last solve_batch / set_bounds for the per-LP range (vlo/vup may be
 // NULL when the engine has no such range).  LP b starts from the basis of slot src[b], which must be primal feasible for
 // these bounds (an optimal slot of any objective is), and runs primal simplex steps.
-int bslv_lpq_solve_batch_obj(bslv_lpq *h, int B, const int *src, const int *dst, const double *vlo, const double *vup,
-                             int cost_first, int cost_cnt, const double *costs, int *status, int *iters)
+// (own_range: bslv_lpq_solve_batch_obj_canonical, whose tie phase takes the range of the call and not the one the engine's switch was set for)
+static int solve_batch_obj_ranged(bslv_lpq *h, int B, const int *src, const int *dst, const double *vlo, const double *vup,
+                                  int cost_first, int cost_cnt, const double *costs, int *status, int *iters, bool own_range)
 {
     if (!h || cost_cnt < 1 || cost_first < 0 || cost_first + cost_cnt > h->ps.M0 + h->ps.N0 || !costs) { set_error("bslv_lpq_solve_batch_obj: bad argument"); return BSLV_E_ARG; }
-    if (h->tie_obj.on && (cost_first != h->cobj_first || cost_cnt != h->cobj_cnt)) { set_error("bslv_lpq_solve_batch_obj: the cost range (%d, %d) is not the one bslv_lpq_set_canonical_obj was set for (%d, %d)", cost_first, cost_cnt, h->cobj_first, h->cobj_cnt); return BSLV_E_ARG; }
+    if (!own_range && h->tie_obj.on && (cost_first != h->cobj_first || cost_cnt != h->cobj_cnt)) { set_error("bslv_lpq_solve_batch_obj: the cost range (%d, %d) is not the one bslv_lpq_set_canonical_obj was set for (%d, %d)", cost_first, cost_cnt, h->cobj_first, h->cobj_cnt); return BSLV_E_ARG; }
     if (h->ps.nfold) {      // indices of the model as given -> the engine's (a cost on a folded row would be a cost on its column: not asked for by any caller)
         for (int t = 0; t < cost_cnt; t++) if (h->ps.map_var(cost_first + t) != h->ps.map_var(cost_first) + t) { set_error("bslv_lpq_solve_batch_obj: the cost range covers rows the presolve folded into column bounds"); return BSLV_E_ARG; }
         cost_first = h->ps.map_var(cost_first);
@@ -4197,6 +4265,11 @@ int bslv_lpq_solve_batch_obj(bslv_lpq *h, int B, const int *src, const int *dst,
         if (!rc && status && sscanf(e, "%d:%d", &k, &lp) >= 1 && k == h->obj_batches && lp >= 0 && lp < B) status[lp] = BSLV_LP_UNDEFINED;
     }
     return rc;
+}
+int bslv_lpq_solve_batch_obj(bslv_lpq *h, int B, const int *src, const int *dst, const double *vlo, const double *vup,
+                             int cost_first, int cost_cnt, const double *costs, int *status, int *iters)
+{
+    return solve_batch_obj_ranged(h, B, src, dst, vlo, vup, cost_first, cost_cnt, costs, status, iters, false);
 }
 // One batch.  Its counters (BatchStats) are gathered in a record of its own and become the call's (h->last) when the batch is over:
 // stored, or added for a re-solve of the rescue (resolve)
@@ -4252,7 +4325,7 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
     }
     if (const char *e = getenv("BSLV_UPD_GRID")) h->upd_grid = std::max(64, atoi(e));
     {   // one work-list length per lock-step iteration, zeroed here: no reset between iterations
-        const int need = L.maxit + 64 + ((h->tie.on || h->tie_obj.on || h->tie_call.on) ? tie_rounds_max(L) : 0);      // (the rounds of a tie phase count on behind the others')
+        const int need = L.maxit + 64 + ((h->tie.on || h->tie_obj.on || h->tie_call.on || h->tie_call_obj.on) ? tie_rounds_max(L) : 0);      // (the rounds of a tie phase count on behind the others')
         if ((rc = ensure_nwork(h, need, need))) return rc;
     }
     HIP_TRY(hipMemsetAsync(h->xstat_d, 0, 8 * sizeof(int), s));
@@ -4425,6 +4498,8 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
     };
     long tie_before[4] = {0, 0, 0, 0};
     if (resolve && h->tie_call.on) for (int k = 0; k < 4; k++) tie_before[k] = h->tie.last[k];      // (bslv_lpq_solve_batch_canonical: the rescue's solves count with the call)
+    long tie_obj_before[4] = {0, 0, 0, 0};
+    if (resolve && h->tie_call_obj.on) for (int k = 0; k < 4; k++) tie_obj_before[k] = h->tie_obj.last[k];      // (bslv_lpq_solve_batch_obj_canonical: likewise)
     for (int k = 0; k < 4; k++) h->tie.last[k] = 0;
     if (L.objmode) for (int k = 0; k < 4; k++) h->tie_obj.last[k] = 0;
     // (the engine's switch is the tableau form's alone: bslv_lpq_set_canonical; the call's own direction holds in both forms)
@@ -4447,11 +4522,25 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
         }
     }
     for (int k = 0; k < 4; k++) h->tie.last[k] += tie_before[k];
-    if (h->tie_obj.on && L.objmode && !L.rev && !max_rounds) {
+    // (again the engine's switch is the tableau form's alone, bslv_lpq_set_canonical_obj, and the call's own direction holds in both forms)
+    if ((h->tie_obj.on || h->tie_call_obj.on) && L.objmode && !max_rounds) {
         if ((rc = ensure_tie(h, h->tie_obj, L.ld))) return rc;
-        const TieView tv = h->tie_obj.view(tie_cap(L));
-        if ((rc = tie_phase(h->tie_obj, [&](int nt) { hipLaunchKernelGGL(k_select_tie_obj, dim3(nt), dim3(plan.nt), 0, s, L, bv, tv, h->active_d, nt, KP); }))) return rc;
+        TieView tv = h->tie_obj.view(tie_cap(L));
+        if (h->tie_call_obj.on) tv.dir = h->tie_call_obj.dir_d;
+        if (!L.rev) {
+            if ((rc = tie_phase(h->tie_obj, [&](int nt) { hipLaunchKernelGGL(k_select_tie_obj, dim3(nt), dim3(plan.nt), 0, s, L, bv, tv, h->active_d, nt, KP); }))) return rc;
+        } else {
+            const size_t want = (size_t)L.ldt * sizeof(double);
+            L.rho_off = select_lds_fits(h, 0, SHAPE_TIE_OBJ_REV, want) ? 0 : -1;
+            const size_t lds = L.rho_off == 0 ? want : 0;
+            if ((rc = tie_phase(h->tie_obj, [&](int nt) {
+                    const int helpers = rev_helper_count(L, plan.nt, nt);
+                    L.helpers = helpers; L.launch_id = (++h->launch_seq) & 0x3FFFFF;
+                    hipLaunchKernelGGL(k_select_tie_obj_rev, dim3(nt, helpers), dim3(plan.nt), lds, s, L, bv, tv, h->active_d, nt, KP);
+                }))) return rc;
+        }
     }
+    if (L.objmode) for (int k = 0; k < 4; k++) h->tie_obj.last[k] += tie_obj_before[k];
     {   // tableau passes of this batch: sum of the work-list lengths of the rounds
         std::vector<int> nw(std::max(it, 1), 0);
         if (it > 0) HIP_TRY(hipMemcpy(nw.data(), h->nwork_d, (size_t)it * sizeof(int), hipMemcpyDeviceToHost));
@@ -4540,6 +4629,7 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
         static const bool tm = getenv("BSLV_LP_TIMING") != nullptr;
         if (tm) fprintf(stderr, "lp solve_batch: %s form %d x %d, B %d, %d lock-step rounds, %ld pivots, %ld passes, %.1f ms; %d parents, largest family %d, %s\n", L.rev ? "revised" : "tableau", L.M, L.N, B, it, st.pivots, st.passes, st.total_ms, h->last_init_parents, h->last_init_family, h->last_init_chunks ? "k_init_grouped" : "k_init");
         if (tm && (h->tie.on || h->tie_call.on) && !L.objmode) fprintf(stderr, "lp tie phase%s: %ld LPs entered, %ld tie pivots, %ld without an entering candidate, %ld gave up, %d rounds\n", h->tie_call.on ? " (per call)" : "", h->tie.last[0], h->tie.last[1], h->tie.last[2], h->tie.last[3], tie_rounds);
+        if (tm && h->tie_call_obj.on && L.objmode) fprintf(stderr, "lp tie phase of an objective batch (per call): %ld LPs entered, %ld tie iterations, %ld on a column without a blocking row, %ld gave up, %d rounds\n", h->tie_obj.last[0], h->tie_obj.last[1], h->tie_obj.last[2], h->tie_obj.last[3], tie_rounds);
         if (tm && period > 0) fprintf(stderr, "lp period %d: %ld refactorisations at the start, %ld during the rounds, %ld replay pivots, largest age at a selection %ld, %ld replay passes, %.1f ms in refactorisations\n", period, h->last.per[0], h->last.per[1], h->last.per[2], h->last.per[3], h->per.passes, h->per.ms);
         if (tm && h->park.cap) fprintf(stderr, "lp park (totals): %ld parked, %ld unparked for a child, %ld because their source was about to be overwritten, %ld dropped unused, %zu live\n", h->park.stats[0], h->park.stats[1], h->park.stats[2], h->park.stats[3], h->park.live.size());
     }
@@ -5022,6 +5112,21 @@ int bslv_lpq_set_canonical_obj(bslv_lpq *h, int on, int cost_first, int cost_cnt
     return 0;
 }
 int bslv_lpq_get_canonical_obj(const bslv_lpq *h) { return h && h->tie_obj.on; }
+// ... for this call only, towards the canonical optimal point for `ddir` on the call's own cost range: see bslv_hip.h.  The engine's own
+// switch, range and direction are neither read nor changed (the phase runs with the call's direction, in `tie_obj`'s per-LP state and
+// counters); in the revised form this is the way to the phase (k_select_tie_obj_rev), which bslv_lpq_set_canonical_obj refuses there.
+int bslv_lpq_solve_batch_obj_canonical(bslv_lpq *h, const double *ddir, int B, const int *src, const int *dst, const double *vlo,
+                                       const double *vup, int cost_first, int cost_cnt, const double *costs, int *status, int *iters)
+{
+    if (!h || !ddir) { set_error("bslv_lpq_solve_batch_obj_canonical: bad argument"); return BSLV_E_ARG; }
+    if (cost_cnt < 1 || cost_first < 0 || cost_first + cost_cnt > h->ps.M0 + h->ps.N0) { set_error("bslv_lpq_solve_batch_obj_canonical: bad cost range (%d, %d)", cost_first, cost_cnt); return BSLV_E_ARG; }
+    for (int j = 0; j < cost_cnt; j++) if (!std::isfinite(ddir[j])) { set_error("bslv_lpq_solve_batch_obj_canonical: ddir[%d] is not finite", j); return BSLV_E_ARG; }
+    if (const int rc = tie_upload_dir(h, h->tie_call_obj, ddir, cost_cnt)) return rc;
+    h->tie_call_obj.on = true;
+    const int rc = solve_batch_obj_ranged(h, B, src, dst, vlo, vup, cost_first, cost_cnt, costs, status, iters, true);
+    h->tie_call_obj.on = false;
+    return rc;
+}
 int bslv_lpq_last_canonical_obj_stats(const bslv_lpq *h, long out[4])
 {
     if (!h || !out) return BSLV_E_ARG;

@@ -309,10 +309,12 @@ struct DualPreimg {
 static std::mutex g_dpre_mu;
 static std::unordered_map<const bslv_poly *, DualPreimg *> g_dpre;
 
-// canonical: the P1(w) LPs end in their canonical optimal point (bslv_lpq_set_canonical_obj; hom == 0 only); cstats: its four counters, summed
+// canonical: the P1(w) LPs end in their canonical optimal point (hom == 0 only) -- CANON_SWITCH: by the LP engine's switch,
+// bslv_lpq_set_canonical_obj (tableau form only); CANON_CALL: per call, bslv_lpq_solve_batch_obj_canonical (both forms); cstats: its four counters, summed
+enum { CANON_SWITCH = 1, CANON_CALL = 2 };
 static thread_local long g_canon_obj[4] = {0, 0, 0, 0};      // of phase 2 of this thread's last bslv_vlp_solve_dual2
 static int dual_benson(const Problem &pb, const Sol &S, int hom, double eps, int batch, bslv_poly **poly_out, int *status, long *lps, long *steps,
-                       DualPreimg *store = nullptr, bool canonical = false, long *cstats = nullptr)
+                       DualPreimg *store = nullptr, int canonical = 0, long *cstats = nullptr)
 {
     *status = 0; *poly_out = nullptr;
     const int m = pb.m, n = pb.n, q = pb.q, M = m + q + (hom ? 1 : 0), N = n + q;
@@ -349,17 +351,24 @@ static int dual_benson(const Problem &pb, const Sol &S, int hom, double eps, int
     if (st == BSLV_LP_INFEASIBLE) { report_ray(lp, "phase 2 (dual), feasibility LP", st, 0, nullptr, nullptr, 0, 0, nullptr); *status = 1; bslv_poly_destroy(poly); poly = nullptr; return done(0); }
     if (st != BSLV_LP_OPTIMAL) { set_error("phase 2 (dual): the feasibility LP has status %d", st); return done(BSLV_E_STATE); }
     auto count_canonical = [&]() { long cs[4]; if (cstats && bslv_lpq_last_canonical_obj_stats(lp, cs) == 0) for (int k = 0; k < 4; k++) cstats[k] += cs[k]; };
+    std::vector<double> ddir;
     if (canonical && !hom) {
         // canonical optimal points: ddir = sum_j (1 + hash01(j)) R_j, a generic interior point of the cone the weights live in -- ddir . y is
         // bounded below on every optimal face (the default cone: ddir_k = 1 + hash01(k), the primal driver's direction)
-        std::vector<double> ddir(q, 0.0);
+        ddir.assign(q, 0.0);
         for (int i = 0; i < q; i++) for (int j = 0; j < S.r; j++) ddir[i] += (1.0 + hash01(j)) * S.R[(size_t)i * S.r + j];
-        if ((rc = bslv_lpq_set_canonical_obj(lp, 1, M + n, q, ddir.data()))) return done(rc);      // (the revised form: the LP engine's message, no fallback)
+        if ((canonical & CANON_SWITCH) && (rc = bslv_lpq_set_canonical_obj(lp, 1, M + n, q, ddir.data()))) return done(rc);      // (the revised form: the LP engine's message, no fallback)
     }
+    // every P1(w) solve below -- PART 1, the batches, their retries: with CANON_CALL the direction goes with the call
+    const bool canon_call = (canonical & CANON_CALL) && !hom;
+    auto solve_obj = [&](int nb, const int *sv, const int *dv, const double *Wv, int *stat, int *iter) {
+        return canon_call ? bslv_lpq_solve_batch_obj_canonical(lp, ddir.data(), nb, sv, dv, nullptr, nullptr, M + n, q, Wv, stat, iter)
+                          : bslv_lpq_solve_batch_obj(lp, nb, sv, dv, nullptr, nullptr, M + n, q, Wv, stat, iter);
+    };
     // ... then PART 1 (:1397-1443): w = mean of the columns of R
     std::vector<double> w(q, 0.0), y(q), val(q);
     for (int i = 0; i < q; i++) { for (int j = 0; j < nw0; j++) w[i] += W0[(size_t)i * nw0 + j]; w[i] /= nw0; }
-    if ((rc = bslv_lpq_solve_batch_obj(lp, 1, &zero, &zero, nullptr, nullptr, M + n, q, w.data(), &st, &it))) return done(rc);
+    if ((rc = solve_obj(1, &zero, &zero, w.data(), &st, &it))) return done(rc);
     count_canonical();
     if (st != BSLV_LP_OPTIMAL) { report_ray(lp, "phase 2 (dual), first LP", st, 0, nullptr, nullptr, M + n, q, w.data()); *status = st == BSLV_LP_INFEASIBLE ? 1 : 2; bslv_poly_destroy(poly); poly = nullptr; return done(0); }
     ++*lps;
@@ -436,7 +445,7 @@ static int dual_benson(const Problem &pb, const Sol &S, int hom, double eps, int
             gen[dst[t]] = gen[src[t]] + 1;
         }
         if (np > 0) {
-            if ((rc = bslv_lpq_solve_batch_obj(lp, np, src.data(), dst.data(), nullptr, nullptr, M + n, q, W.data(), stv.data(), itv.data()))) return done(rc);
+            if ((rc = solve_obj(np, src.data(), dst.data(), W.data(), stv.data(), itv.data()))) return done(rc);
             count_canonical();
             {   // an LP given up (UNDEFINED: in the revised form the pivot cross-check found B^-1 drifted; nothing refactorises it) is solved
                 // once more from slot 0, the first optimal basis -- primal feasible, as every optimal slot -- as the reference retries lp_solve
@@ -448,7 +457,7 @@ static int dual_benson(const Problem &pb, const Sol &S, int hom, double eps, int
                 const int nr = (int)rt.size();
                 if (nr > 0) {
                     rst.resize(nr); rit.resize(nr);
-                    if ((rc = bslv_lpq_solve_batch_obj(lp, nr, rsrc.data(), rdst.data(), nullptr, nullptr, M + n, q, rW.data(), rst.data(), rit.data()))) return done(rc);
+                    if ((rc = solve_obj(nr, rsrc.data(), rdst.data(), rW.data(), rst.data(), rit.data()))) return done(rc);
                     count_canonical();
                     for (int k = 0; k < nr; k++) { stv[rt[k]] = rst[k]; itv[rt[k]] += rit[k]; }
                 }
@@ -511,7 +520,7 @@ static int dual_benson(const Problem &pb, const Sol &S, int hom, double eps, int
     return done(0);
 }
 
-static int phase2_dual(const Problem &pb, const Sol &S, double eps, int batch, bslv_poly **poly_out, int *status, long *lps, long *steps, DualPreimg *store = nullptr, bool canonical = false)
+static int phase2_dual(const Problem &pb, const Sol &S, double eps, int batch, bslv_poly **poly_out, int *status, long *lps, long *steps, DualPreimg *store = nullptr, int canonical = 0)
 {
     return dual_benson(pb, S, 0, eps, batch, poly_out, status, lps, steps, store, canonical, g_canon_obj);
 }
@@ -713,6 +722,7 @@ int bslv_vlp_solve_dual2(int m, int n, int q, const double *A, const double *P,
     *lower_image_out = nullptr;
     for (int k = 0; k < 4; k++) g_canon_obj[k] = 0;
     if (const char *e = getenv("BSLV_CANONICAL_OBJ")) if (atoi(e) != 0) flags |= BSLV_VLP_CANONICAL;
+    if (const char *e = getenv("BSLV_CANONICAL_OBJ_CALL")) if (atoi(e) != 0) flags |= BSLV_VLP_CANONICAL_CALL;
     Sol S;
     std::vector<double> Pn;
     long lps = 0, steps = 0;
@@ -725,7 +735,7 @@ int bslv_vlp_solve_dual2(int m, int n, int q, const double *A, const double *P,
     bslv_poly *poly = nullptr;
     DualPreimg *store = (flags & BSLV_VLP_PREIMAGES) ? new DualPreimg() : nullptr;
     if (store) { store->m = m; store->n = n; store->q = q; }
-    if ((rc = phase2_dual(pb, S, eps_benson_phase2, batch, &poly, &vst, &lps, &steps, store, (flags & BSLV_VLP_CANONICAL) != 0))) { delete store; return rc; }
+    if ((rc = phase2_dual(pb, S, eps_benson_phase2, batch, &poly, &vst, &lps, &steps, store, ((flags & BSLV_VLP_CANONICAL) ? CANON_SWITCH : 0) | ((flags & BSLV_VLP_CANONICAL_CALL) ? CANON_CALL : 0)))) { delete store; return rc; }
     if (vst) { delete store; *vlp_status = vst; phase2_failure(info, vst, bounded, lps); return 0; }
     if (store) {
         // pre-images of the extreme DIRECTIONS of the upper image (dual slots that are directions; bslv_algs.c:1508-1535): x of

@@ -217,6 +217,27 @@ class LpEngine:
                                                 cost_first, costs.shape[1], costs.ctypes.data, status.ctypes.data, iters.ctypes.data))
         return status, iters
 
+    def solve_batch_obj_canonical(self, ddir, src, dst, cost_first, costs, vlo=None, vup=None):
+        """solve_batch_obj followed by the tie phase towards the canonical optimal point for `ddir` (one value per variable of the cost
+        range cost_first .. cost_first + costs.shape[1] - 1), for this call only; the engine's own switch, range and direction stay what
+        they are.  Works in both forms; in the revised form the only way to the phase (bslv_lpq_solve_batch_obj_canonical).  ddir=None
+        hands the library a null pointer (its BSLV_E_ARG raises BslvError, like a NaN or a bad range)."""
+        src = np.ascontiguousarray(src, np.int32)
+        dst = np.ascontiguousarray(dst, np.int32)
+        B = len(src)
+        costs = np.ascontiguousarray(costs, np.float64).reshape(B, -1)
+        d = None if ddir is None else np.ascontiguousarray(ddir, np.float64).reshape(costs.shape[1])
+        vlo = np.ascontiguousarray(np.zeros((B, self.vcnt)) if vlo is None else vlo, np.float64).reshape(B, self.vcnt)
+        vup = np.ascontiguousarray(np.zeros((B, self.vcnt)) if vup is None else vup, np.float64).reshape(B, self.vcnt)
+        status = np.empty(B, np.int32)
+        iters = np.empty(B, np.int32)
+        self.lib.bslv_lpq_solve_batch_obj_canonical.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 4 + [ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 3
+        self.lib.bslv_lpq_solve_batch_obj_canonical.restype = ctypes.c_int
+        check(self.lib.bslv_lpq_solve_batch_obj_canonical(self.h, None if d is None else d.ctypes.data, B, src.ctypes.data, dst.ctypes.data,
+                                                          vlo.ctypes.data, vup.ctypes.data, int(cost_first), costs.shape[1], costs.ctypes.data,
+                                                          status.ctypes.data, iters.ctypes.data))
+        return status, iters
+
     def _get(self, fn, slots, first, cnt):
         slots = np.ascontiguousarray(slots, np.int32)
         out = np.empty((len(slots), cnt), np.float64)

@@ -42,7 +42,8 @@ def solve_primal(prob, cone_kind=0, gen=None, c=None, bounded=False, eps_phase0=
     dump = slot-indexed dump of the result polyhedron with the sign changes of poly_trans_primal applied).  alg_phase2 = "dual":
     phase2_dual; the dump is then given with the sides swapped back, so that X / pi are the upper image in both cases.
     canonical (with alg_phase2 = "dual"): every P1(w) ends in its canonical optimal point (BSLV_VLP_CANONICAL, include/bslv_hip.h);
-    out["canonical_obj"] then holds the tie phase's counters summed over phase 2 (all zero with the flag off).
+    out["canonical_obj"] then holds the tie phase's counters summed over phase 2 (all zero with the flag off).  canonical = "call": the
+    same direction handed to every P1(w) solve per call (BSLV_VLP_CANONICAL_CALL), which an LP engine in the revised form takes too.
     preimages (option -s): out["pre_p"] maps an element of the upper image (row of dump["X"]) to its x (n values), out["pre_d"] a
     vertex of the lower image (row of dump["Y"]) to its (u, w) (m + q values), both as the engine stores them: the writers of the
     _pre_img_ files multiply u by optdir and w by c_dir.  Elements without a stored pre-image (directions of the lower image) have no
@@ -66,7 +67,7 @@ def solve_primal(prob, cone_kind=0, gen=None, c=None, bounded=False, eps_phase0=
     check((lib.bslv_vlp_solve_dual2 if dual2 else lib.bslv_vlp_solve_primal)(prob["m"], prob["n"], prob["q"], A.ctypes.data, P.ctypes.data, rt.ctypes.data, arrs[0].ctypes.data, arrs[1].ctypes.data,
                                     ct.ctypes.data, arrs[2].ctypes.data, arrs[3].ctypes.data, int(prob.get("optdir", 1)), cone_kind,
                                     None if g is None else g.ctypes.data, 0 if g is None else g.shape[1], None if cc is None else cc.ctypes.data,
-                                    int(bounded), (1 if alg_phase1 == "dual" else 0) | (2 if preimages else 0) | (4 if (canonical and dual2) else 0), eps_phase0, eps_phase1, eps_benson_phase1, eps_benson_phase2, batch,
+                                    int(bounded), (1 if alg_phase1 == "dual" else 0) | (2 if preimages else 0) | ((8 if isinstance(canonical, str) and canonical == "call" else 4) if (canonical and dual2) else 0), eps_phase0, eps_phase1, eps_benson_phase1, eps_benson_phase2, batch,
                                     ctypes.byref(h), ctypes.byref(st), ctypes.byref(info)))
     q = prob["q"]
     out = dict(status=STATUS.get(st.value, st.value), message=info.message.decode(), lps=info.lps, steps=info.steps, c_dir=info.c_dir)

@@ -535,7 +535,7 @@ int  bslv_lpq_solve_batch_canonical(bslv_lpq *h, const double *dir /* var_cnt */
  * unbounded on the optimal face: the basis reached stays), or the cap of 1000 + 2 (M + N) iterations; its iterations are counted in
  * iters[].  A solve_batch_obj with another cost range answers BSLV_E_ARG while the switch is on; solve_batch ignores the switch; it
  * is independent of bslv_lpq_set_canonical.  A non-finite ddir, a bad range or on with ddir == NULL is BSLV_E_ARG, and so is on for an
- * engine in the revised form (its tie phase needs g from B^-1: not built).  With on = 0 the engine computes what it always did, bit
+ * engine in the revised form (there the phase is reached per call: bslv_lpq_solve_batch_obj_canonical, below).  With on = 0 the engine computes what it always did, bit
  * for bit.
  * bslv_lpq_last_canonical_obj_stats, of the last solve_batch_obj: [0] LPs that entered the phase (all that ended OPTIMAL), [1] tie
  * iterations (pivots + bound switches), [2] LPs that ended on a column without a blocking row, [3] LPs that gave up at the cap; all
@@ -543,6 +543,27 @@ int  bslv_lpq_solve_batch_canonical(bslv_lpq *h, const double *dir /* var_cnt */
 int  bslv_lpq_set_canonical_obj(bslv_lpq *h, int on, int cost_first, int cost_cnt, const double *ddir /* cost_cnt; NULL with on = 0 */);
 int  bslv_lpq_get_canonical_obj(const bslv_lpq *h);
 int  bslv_lpq_last_canonical_obj_stats(const bslv_lpq *h, long out[4]);
+/* ... PER CALL, in both forms: one solve_batch_obj, followed by the tie phase towards the canonical optimal point for ddir on the cost
+ * range of the call, with the meaning documented at bslv_lpq_set_canonical_obj, for THIS batch only.  The engine's own switch, its cost
+ * range and its stored direction are neither read nor changed (bslv_lpq_get_canonical_obj answers what it did; a later solve_batch_obj
+ * runs as if the call had not been made), and the call takes its own range: solve_batch_obj's refusal of a range other than the
+ * switch's does not apply to it.  In the tableau form the call is set_canonical_obj(1, cost_first, cost_cnt, ddir);
+ * solve_batch_obj(..); <the old switch, range and direction back>, bit for bit.  In the REVISED form, where
+ * bslv_lpq_set_canonical_obj answers BSLV_E_ARG, this call is the way to the phase (lp_engine.hip, k_select_tie_obj_rev): a slot holds
+ * B^-1 and T[r][j] = -rho_r . K[nh_j], so g on entry is one tableau row, the one of the synthesised y = sum_t ddir_t rho_pos(cost_first + t)
+ * over the basic variables of the range, g_j = ddir_{nh[j]} - y . K[nh_j], through the sparse products of a selection (helper workgroups
+ * included); the entering column and the pivot row come from those products too, and the pivot element is cross-checked between the
+ * two as in every selection of that form (a bound switch fetches no row and has no check).  A tie pivot is a rank-1 step on B^-1 and
+ * counts in iters[] and in the slot's age (bslv_lpq_slot_age); no periodic refactorisation runs inside the phase, and neither Devex
+ * switch reaches it.  With bslv_lpq_set_refactor the rescue re-solves before the tie phase of the LPs it takes, as in any
+ * solve_batch_obj; only LPs that end OPTIMAL enter the phase.
+ * h == NULL, ddir == NULL, a non-finite ddir[t] or a bad range: BSLV_E_ARG, nothing changed; whatever solve_batch_obj refuses stays
+ * refused with its own code.  bslv_lpq_last_canonical_obj_stats covers the call (the rescue's solves included); for this call [3]
+ * reads "gave up: at the cap, or (revised form) on a drifted inverse" -- an LP whose cross-check fails commits nothing, keeps the
+ * optimal basis it had reached (every step of the phase keeps optimality) with the status OPTIMAL and is not marked for the rescue. */
+int  bslv_lpq_solve_batch_obj_canonical(bslv_lpq *h, const double *ddir /* cost_cnt */, int B, const int *src, const int *dst,
+                                        const double *vlo, const double *vup, int cost_first, int cost_cnt, const double *costs,
+                                        int *status, int *iters);
 
 /* ------------------------------------------------------------------------------------------
  * 2. Polyhedron engine  (replaces bslv_poly.h:90-118)
@@ -909,8 +930,12 @@ typedef struct bslv_vlp_info {
  * over the generators R_j of the cone the weights live in (a generic interior point of it, so ddir . y is bounded below on every
  * optimal face; the default cone: ddir_k = 1 + hash01(k), the direction of bslv_benson_set_canonical): every cut of the lower image is
  * then built from a VERTEX of the upper image (bslv_algs.c:1479-1486) and is a facet.  The homogeneous engine of phase1_dual is left
- * alone.  An LP engine that comes up in the revised form makes the call fail with that engine's message. */
-enum { BSLV_VLP_PHASE1_DUAL = 1, BSLV_VLP_PREIMAGES = 2, BSLV_VLP_CANONICAL = 4 };
+ * alone.  An LP engine that comes up in the revised form makes the call fail with that engine's message;
+ * CANONICAL_CALL (bslv_vlp_solve_dual2 only; BSLV_CANONICAL_OBJ_CALL=1 in the environment sets it there): the same ddir, handed to
+ * every P1(w) solve -- PART 1, the batches and their retries -- per call, through bslv_lpq_solve_batch_obj_canonical, in both forms
+ * of the LP engine: the way to the canonical points on an engine in the revised form.  The engine's switch stays off.  Neither flag
+ * is a default. */
+enum { BSLV_VLP_PHASE1_DUAL = 1, BSLV_VLP_PREIMAGES = 2, BSLV_VLP_CANONICAL = 4, BSLV_VLP_CANONICAL_CALL = 8 };
 /* cone_kind 0 default (R^q_+), 1 `gen` generates C, 2 `gen` generates C* (vlp->cone_gen); c_in: q or NULL (vlp->c).
  * vlp_status (sol->status, bslv_main.h:103): 1 infeasible, 2 unbounded, 3 no vertex, 4 optimal, 5 input error.
  * With status 4 *engine_out is the finished phase-2 engine (bslv_benson_poly(engine) is the result; destroy it). */
@@ -930,7 +955,7 @@ int  bslv_vlp_solve_dual2(int m, int n, int q, const double *A, const double *P,
                           int bounded, int flags, double eps_phase0, double eps_phase1, double eps_benson_phase1, double eps_benson_phase2,
                           int batch, bslv_poly **lower_image_out, int *vlp_status, bslv_vlp_info *info /* may be NULL */);
 /* the four counters of bslv_lpq_last_canonical_obj_stats summed over the objective solves of phase 2 of the calling thread's last
- * bslv_vlp_solve_dual2 (all zero without BSLV_VLP_CANONICAL) */
+ * bslv_vlp_solve_dual2 (all zero without BSLV_VLP_CANONICAL or BSLV_VLP_CANONICAL_CALL) */
 int  bslv_vlp_last_canonical_obj_stats(long out[4]);
 /* option -s with the dual algorithm (flags & BSLV_VLP_PREIMAGES in bslv_vlp_solve_dual2; phase2_dual with PRE_IMG_ON,
  * bslv_algs.c:1388-1389, 1431-1432, 1484-1497, 1508-1546): x (n values) of an element of the UPPER image = dual slot `facet` of the
