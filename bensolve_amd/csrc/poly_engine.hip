@@ -1737,7 +1737,7 @@ __device__ __forceinline__ void k2_for_entries(const int *pool, int nm, const un
 // NWC = compile-time bound of the row length in words, so the accumulator stays in registers.
 template <int NWC>
 __device__ __forceinline__ void k2_pairs(int nm, int d, int W, int NW, const unsigned long long *bits, const unsigned long long *rows, unsigned *adj_bits,
-                                         int (*queue)[128], const unsigned long long *later = nullptr)
+                                         int (*queue)[128], const unsigned long long *later = nullptr, int part = 0, int nparts = 1)
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     // the row intersection of one candidate
@@ -1765,9 +1765,10 @@ __device__ __forceinline__ void k2_pairs(int nm, int d, int W, int NW, const uns
     // the wave idle, so each wave queues its candidates (LDS) and sweeps 64 at a time.
     // Pairs are visited row by row (wave w takes rows w, w+16, ...; lanes run over j): column i is one broadcast
     // read per row and no pair index has to be decoded -- the one workgroup is instruction-bound here.
+    // A prune worked in nparts parts (K2V2): the rows are dealt over the waves of all parts, row i to wave i mod (16 nparts).
     int qn = 0;                                    // wave-uniform
     int *q = queue[wave];
-    for (int i = wave; i < nm - 1; i += K2T / WAVE) {
+    for (int i = part * (K2T / WAVE) + wave; i < nm - 1; i += nparts * (K2T / WAVE)) {
         const int rowbase = i * (2 * nm - i - 1) / 2 - (i + 1);          // pair index of (i, j) = rowbase + j
         for (int j0 = i + 1; j0 < nm; j0 += WAVE) {
             const int j = j0 + lane;
@@ -1805,7 +1806,13 @@ struct K2V2 {
     // thousands of facets) count in global memory, as the single-cut pipeline does -- each in a slice of its own, handed out by a
     // ticket per round (fc_ticket[round & 1]; workgroup 0 clears the other one for the next round)
     int *fc2, *fl2, *fc_ticket; int fc_slices, fc_stride;
+    // a large prune in parts (k2v2_assign): the workgroups behind the S prunes of the launch are `helpers` more, each of which may take the
+    // rows of one part of a prune of split_min members or more, at most split_parts parts per prune (helpers = 0: no prune is split).
+    // npart_g[s]: the parts prune s was worked in; cntx_g[s * (K2_MAXPARTS - 1) + p - 1]: the adjacent pairs part p >= 1 found
+    int *npart_g, *cntx_g; int helpers, split_min, split_parts;
+    int *split_stat;                  // [0] prunes that were worked in parts, [1] helpers that took a part (bslv_poly_split_stats)
 };
+constexpr int K2_MAXPARTS = 4, K2_SPLIT_MAXS = 1024, K2_DBG_SLOTS = 32, K2_DBG_LARGE = 192;
 __device__ __forceinline__ int k2v2_round(const RState *st);
 __device__ __forceinline__ int k2v2_rank_base(const RState *st);
 // is element v (owner code co = cutof[v]) a member of the new facet of rank `want`?  A shared on-plane element (co = -1 - k) carries the
@@ -1819,21 +1826,56 @@ __device__ __forceinline__ bool k2v2_member(const PolyView &P, int v, int co, in
     for (int t = 0; t < k; t++) mine |= tail[t] == want;
     return mine;
 }
+// element v counts as a member of each of its owners among the S selected cuts, as k2v2_member reads them (hist: LDS, S counters)
+__device__ __forceinline__ void k2v2_count_owners(const PolyView &P, int v, int co, int rank_base, int S, int *hist)
+{
+    if (co >= -1) { if (co >= 0 && co < S) atomicAdd(&hist[co], 1); return; }
+    const int k = -1 - co;
+    const int *tail = P.pool + P.inc_off[v] + P.inc_len[v] - k;
+    for (int t = 0; t < k; t++) { const int s = tail[t] - rank_base; if (s >= 0 && s < S) atomicAdd(&hist[s], 1); }
+}
+// A large prune in parts.  The pair phase of a prune (k2_pairs) is quadratic in its members and bound by the instructions of its one
+// workgroup, and a launch ends with its largest prune.  So a prune of split_min members or more is worked by up to split_parts
+// workgroups: its own and helpers from the pool behind the prunes.  Every part builds the prune's state itself (P0-P3 are
+// deterministic functions of device state), takes its share of the rows of the pair phase and gives its result through atomics on
+// global memory that nothing reads before k_r2_k2emit: no workgroup waits for another.  Who takes what is a function of the
+// member counts nm[0..S) alone, which every workgroup of the launch has counted for itself: the prunes in the order of their
+// size (largest first, ties by s) take helpers 0, 1, .. until the pool is empty.
+__device__ __forceinline__ int k2v2_parts(const K2V2 &V, int n)
+{
+    return n >= V.split_min && n <= K2_MAXNM ? min(min(V.split_parts, K2_MAXPARTS), 1 + n / max(V.split_min, 2)) : 1;
+}
+// out[2] = the parts of prune vs (its own workgroup, helper < 0); a helper: out[0] = its prune (left alone: none), out[1] = its part, out[2] = of how many
+__device__ __forceinline__ void k2v2_assign(const K2V2 &V, const int *nm, int S, int vs, int helper, int *out)
+{
+    for (int s = threadIdx.x; s < S; s += K2T) {
+        const int n = nm[s], want = k2v2_parts(V, n) - 1;
+        if (want <= 0 || (helper < 0 && s != vs)) continue;
+        int off = 0;                                    // helpers that go to the prunes served before s
+        for (int k = 0; k < S; k++) { const int nk = nm[k]; if (nk > n || (nk == n && k < s)) off += k2v2_parts(V, nk) - 1; }
+        const int got = max(0, min(want, V.helpers - off));
+        if (helper < 0) out[2] = 1 + got;
+        else if (helper >= off && helper < off + got) { out[0] = s; out[1] = 1 + helper - off; out[2] = 1 + got; }
+    }
+}
 __device__ __forceinline__ void k2v2_sizes(const RState *st, int &S, int &go, int &nzero, int &nv0, int &ncross);
 __device__ void k2v2_check_members(const K2V2 &V, int vs, const int *s_mem, int nm, const int *members, int nzero);
 // (a device function: the kernels of the single-cut pipeline, k2_fused_t<false>, and of a round's prunes, k2_fused_t<true>, call it)
 template <bool V2>
 __device__ void k2_fused_body(PolyView P, int *members, int nzero, int nv0, int ncross, int *fcount, int *flocal,
                               int lds_words, int2 *E, int ebase, int *ne_dev, Tri *totals, Mail *mail, int seq, unsigned long long *dbg,
-                              const CutDev *cd, int *abort_flag, int *EP, const Hp &hn, int *counters_n, int *zlist_n, const K2V2 &V)
+                              const CutDev *cd, int *abort_flag, int *EP, const Hp &hn, int *counters_n, int *zlist_n, const K2V2 &V, int helper = -1)
 {
     extern __shared__ unsigned long long k2_dyn[];
+    int S = 0;
     if (V2) {
-        int S, go;
+        int go;
         k2v2_sizes(V.st, S, go, nzero, nv0, ncross);
         if (blockIdx.x == 0 && threadIdx.x == 0 && V.fc_ticket) V.fc_ticket[(k2v2_round(V.st) + 1) & 1] = 0;
-        if (!go || (int)blockIdx.x >= S) return;
-        cd = nullptr; ne_dev = nullptr;      // (dbg, BSLV_K2_DEBUG: every prune workgroup of a round adds its phases)
+        // helper >= 0: workgroup `helper` of the pool behind the prunes; it learns below (k2v2_assign) which part of which prune is its
+        if (!go || S <= 0 || (helper < 0 && (int)blockIdx.x >= S)) return;
+        cd = nullptr; ne_dev = nullptr;      // (dbg, BSLV_K2_DEBUG: every prune workgroup of a round adds its phases; a helper adds none)
+        if (helper >= 0) dbg = nullptr;
     }
     if (!V2 && blockIdx.x > 0) {
         // workgroups 1.. ride along: they classify the elements against the NEXT halfspace (the prune reads no
@@ -1858,6 +1900,7 @@ __device__ void k2_fused_body(PolyView P, int *members, int nzero, int nv0, int 
         }
     }
     unsigned long long t_prev = dbg ? wall_clock64() : 0ull;
+    const unsigned long long t_start = t_prev;
 #define K2_PHASE(k) do { if (dbg && threadIdx.x == 0) { unsigned long long t_now = wall_clock64(); if (V2) atomicAdd(&dbg[k], t_now - t_prev); else dbg[k] += t_now - t_prev; t_prev = t_now; } } while (0)
     __shared__ Tri lds[16];
     __shared__ unsigned s_off[K2_MAXNM];
@@ -1867,19 +1910,51 @@ __device__ void k2_fused_body(PolyView P, int *members, int nzero, int nv0, int 
     __shared__ int s_queue[K2T / WAVE][128];      // candidate pairs per wave (k2_pairs)
     const int tid = threadIdx.x, d = P.d;
     int nm = nzero + ncross;
-    const int vs = (int)blockIdx.x;                 // V2: the selected cut of this workgroup
-    const int myrank = V2 ? k2v2_rank_base(V.st) + vs : 0x7FFFFFFF;      // ... and the rank of its facet
-    // V2: fallback request / empty result of cut vs (uniform callers)
-    auto v2_result = [&](int cnt, int n) { if (tid == 0) { V.cnt_g[vs] = cnt; V.nm_g[vs] = n; } };
+    int vs = (int)blockIdx.x;                       // V2: the selected cut of this workgroup (a helper: of the prune it was dealt to)
+    int part = 0, nparts = 1;                       // V2: this workgroup takes the rows of part `part` of nparts of the pair phase (k2_pairs)
+    int myrank = V2 ? k2v2_rank_base(V.st) + vs : 0x7FFFFFFF;      // ... and the rank of its facet
+    // V2: fallback request / empty result of cut vs (uniform callers); part 0 reports for the prune, a part >= 1 has only the
+    // number of adjacent pairs among its rows to add
+    auto v2_result = [&](int cnt, int n) {
+        if (tid != 0) return;
+        if (part == 0) { V.cnt_g[vs] = cnt; V.nm_g[vs] = n; V.npart_g[vs] = nparts; }
+        else if (cnt >= 0) V.cntx_g[vs * (K2_MAXPARTS - 1) + part - 1] = cnt;
+    };
     if (V2) {
         // P0a: the members of cut vs among the on-plane elements (members[0..nzero), slot order) and the new vertices
-        __shared__ int s_base;
-        if (tid == 0) s_base = 0;
+        __shared__ int s_base, s_asg[3];
+        __shared__ int s_hist[K2_SPLIT_MAXS];
+        // Prunes in parts: while it scans the candidates every workgroup also counts the members of ALL S prunes (s_hist), and from those
+        // counts alone works out which prunes are split and which helper takes which part (k2v2_assign) -- the same in every workgroup.
+        const bool split = V.helpers > 0 && V.split_parts > 1 && S <= K2_SPLIT_MAXS;      // (uniform over the launch)
+        if (helper >= 0 && !split) return;
+        if (split) for (int k = tid; k < S; k += K2T) s_hist[k] = 0;
+        if (tid == 0) { s_base = 0; s_asg[0] = -1; s_asg[1] = 0; s_asg[2] = 1; }
         __syncthreads();
-        const int ncand = nzero + ncross;
+        const int ncand = nzero + ncross, rank_base = k2v2_rank_base(V.st);
         // every thread takes CPT CONSECUTIVE candidates (so one scan per CPT * K2T candidates keeps them in order) and has the loads of
         // all of them in flight together: a round has 3-4 thousand candidates, which used to be four dependent load-scan-barrier trips
         constexpr int CPT = 8;
+        // A prune's own workgroup counts while it scans for its members.  A helper does not know its prune before it has counted: when
+        // the candidates take one trip (the usual case) it counts, learns its prune and tests the candidates it still holds in
+        // registers; otherwise it counts in a pass of its own first.
+        const bool one_trip = ncand <= K2T * CPT;
+        auto learn = [&]() {              // (uniform) the parts of prune vs; a helper: its prune and part, false when nothing was dealt to it
+            __syncthreads();
+            k2v2_assign(V, s_hist, S, vs, helper, s_asg);
+            __syncthreads();
+            nparts = s_asg[2];
+            if (helper < 0) return true;
+            vs = s_asg[0]; part = s_asg[1]; myrank = rank_base + vs;
+            return vs >= 0;
+        };
+        if (helper >= 0 && !one_trip)
+            for (int c0 = 0; c0 < ncand; c0 += K2T * CPT)
+#pragma unroll
+                for (int u = 0; u < CPT; u++) {
+                    const int c = c0 + tid * CPT + u;
+                    if (c < ncand) { const int v = c < nzero ? members[c] : nv0 + (c - nzero); k2v2_count_owners(P, v, V.cutof[v], rank_base, S, s_hist); }
+                }
         for (int c0 = 0; c0 < ncand; c0 += K2T * CPT) {
             const int cb = c0 + tid * CPT;
             int vv[CPT], co[CPT], cnt = 0;
@@ -1887,6 +1962,11 @@ __device__ void k2_fused_body(PolyView P, int *members, int nzero, int nv0, int 
             for (int u = 0; u < CPT; u++) { const int c = cb + u; vv[u] = c < ncand ? (c < nzero ? members[c] : nv0 + (c - nzero)) : -1; }
 #pragma unroll
             for (int u = 0; u < CPT; u++) co[u] = vv[u] >= 0 ? V.cutof[vv[u]] : 0;
+            if (split && (helper < 0 || one_trip)) {
+#pragma unroll
+                for (int u = 0; u < CPT; u++) if (vv[u] >= 0) k2v2_count_owners(P, vv[u], co[u], rank_base, S, s_hist);
+            }
+            if (helper >= 0 && c0 == 0 && !learn()) return;         // nothing dealt to this helper
 #pragma unroll
             for (int u = 0; u < CPT; u++) { if (vv[u] >= 0 && !k2v2_member(P, vv[u], co[u], vs, myrank)) vv[u] = -1; cnt += vv[u] >= 0; }
             Tri t{cnt, 0, 0};
@@ -1899,13 +1979,15 @@ __device__ void k2_fused_body(PolyView P, int *members, int nzero, int nv0, int 
             if (tid == 0) s_base += tot.a;
             __syncthreads();
         }
+        if (helper >= 0 && ncand == 0) return;
+        if (helper < 0 && split) learn();
         nm = s_base;
         K2_PHASE(10);
         if (nm > K2_MAXNM) { v2_result(-1, nm); return; }          // too large for one workgroup: multi-kernel prune (the negative count says why: -1 members, -2 pair bitmap, -3 hash table, -4 bit matrix)
 #ifdef BSLV_R2_CHECK_MEMBERS
         k2v2_check_members(V, vs, s_mem, nm, members, nzero);          // debugging aid, O(nm^2): a member list never holds an element twice
 #endif
-        if (tid == 0 && nm >= 2) atomicAdd((unsigned long long *)V.pair_tests, (unsigned long long)((long long)nm * (nm - 1) / 2));
+        if (tid == 0 && part == 0 && nm >= 2) atomicAdd((unsigned long long *)V.pair_tests, (unsigned long long)((long long)nm * (nm - 1) / 2));
         if (nm < 2) { v2_result(0, nm); return; }
     }
     const long long npairs = (long long)nm * (nm - 1) / 2;
@@ -1949,6 +2031,10 @@ __device__ void k2_fused_body(PolyView P, int *members, int nzero, int nv0, int 
     }
     __syncthreads();
     const bool use_hash = 2 * s_total <= K2_HASH && (long long)K2_HASH <= bits_cap;        // load factor <= 1/2 (uniform)
+    if (V2 && !use_hash && nparts > 1) {        // only a prune that counts in its LDS hash table is worked in parts (every part sees the same numbers):
+        if (part > 0) return;                   // its own workgroup takes all rows, as for an unsplit prune
+        nparts = 1;
+    }
     if (V2 && !use_hash) {
         __shared__ int s_slice;
         if (tid == 0) s_slice = V.fc_slices > 0 ? atomicAdd(&V.fc_ticket[k2v2_round(V.st) & 1], 1) : V.fc_slices;
@@ -2023,24 +2109,35 @@ __device__ void k2_fused_body(PolyView P, int *members, int nzero, int nv0, int 
     K2_PHASE(3);
     // P4+P5 (k2_pairs)
     const unsigned long long *lat = V2 ? later : nullptr;
-    if (NW <= 1) k2_pairs<1>(nm, d, W, NW, bits, rows, adj_bits, s_queue, lat);
-    else if (NW <= 2) k2_pairs<2>(nm, d, W, NW, bits, rows, adj_bits, s_queue, lat);
-    else if (NW <= 4) k2_pairs<4>(nm, d, W, NW, bits, rows, adj_bits, s_queue, lat);
-    else k2_pairs<K2_MAXNM / 64>(nm, d, W, NW, bits, rows, adj_bits, s_queue, lat);
+    const unsigned long long t_p4 = t_prev;
+    if (NW <= 1) k2_pairs<1>(nm, d, W, NW, bits, rows, adj_bits, s_queue, lat, part, nparts);
+    else if (NW <= 2) k2_pairs<2>(nm, d, W, NW, bits, rows, adj_bits, s_queue, lat, part, nparts);
+    else if (NW <= 4) k2_pairs<4>(nm, d, W, NW, bits, rows, adj_bits, s_queue, lat, part, nparts);
+    else k2_pairs<K2_MAXNM / 64>(nm, d, W, NW, bits, rows, adj_bits, s_queue, lat, part, nparts);
     __syncthreads();
     K2_PHASE(4);
+    const unsigned long long p4_ticks = t_prev - t_p4;
     K2_PHASE(5);
     if (V2) {
-        // the bitmap, the members and the number of adjacent pairs go to global memory; k_r2_k2emit writes the edges
+        // the bitmap, the members and the number of adjacent pairs go to global memory; k_r2_k2emit writes the edges.
+        // A prune in parts: every part ORs the words of its rows into the bitmap, which k_r2_k2emit left zero when it last read it
         unsigned *ag = V.adj_g + (size_t)vs * V.adjw_cap;
         int *mg = V.mem_g + (size_t)vs * K2_MAXNM;
-        int part = 0;
-        for (int w = tid; w < nadjw; w += K2T) { const unsigned x = adj_bits[w]; ag[w] = x; part += __popc(x); }
-        for (int m = tid; m < nm; m += K2T) mg[m] = s_mem[m];
-        const Tri tt = block_sum(Tri{part, 0, 0}, lds);
+        int npairs_mine = 0;
+        if (nparts == 1) for (int w = tid; w < nadjw; w += K2T) { const unsigned x = adj_bits[w]; ag[w] = x; npairs_mine += __popc(x); }
+        else for (int w = tid; w < nadjw; w += K2T) { const unsigned x = adj_bits[w]; if (x) atomicOr(&ag[w], x); npairs_mine += __popc(x); }
+        if (part == 0) for (int m = tid; m < nm; m += K2T) mg[m] = s_mem[m];
+        const Tri tt = block_sum(Tri{npairs_mine, 0, 0}, lds);
         v2_result(tt.a, nm);
+        if (tid == 0 && nparts > 1) atomicAdd(&V.split_stat[part == 0 ? 0 : 1], 1);
         K2_PHASE(6);
-        if (dbg && tid == 0) { atomicAdd(&dbg[7], 1ull); atomicAdd(&dbg[8], (unsigned long long)W); atomicAdd(&dbg[9], (unsigned long long)s_nloc); atomicAdd(&dbg[11], (unsigned long long)nm); atomicMax(&dbg[12], (unsigned long long)nm); }
+        if (dbg && tid == 0) {
+            atomicAdd(&dbg[7], 1ull); atomicAdd(&dbg[8], (unsigned long long)W); atomicAdd(&dbg[9], (unsigned long long)s_nloc); atomicAdd(&dbg[11], (unsigned long long)nm); atomicMax(&dbg[12], (unsigned long long)nm);
+            // the large prunes (K2_DBG_LARGE members or more), which a launch waits for: how many, their pair phase, their whole time
+            const unsigned long long whole = t_prev - t_start;
+            atomicMax(&dbg[13], p4_ticks); atomicMax(&dbg[17], whole);
+            if (nm >= K2_DBG_LARGE) { atomicAdd(&dbg[14], 1ull); atomicAdd(&dbg[15], p4_ticks); atomicAdd(&dbg[16], whole); atomicAdd(&dbg[18], (unsigned long long)nm); }
+        }
         return;
     }
     // P6: adjacent pairs in lexicographic order; the 32 pairs of a bitmap word are consecutive, so (i, j) is
@@ -2381,6 +2478,11 @@ struct bslv_poly {
     bool r2_mis = true;               // rounds take a MAXIMAL independent set from a conflict matrix of the chunk (round 3); BSLV_R2_MIS=0 / debug_set key 11: the local minima of one random order (round 2)
     bool r2_ride = true;              // a round's new vertices are classified by workgroups of the launch of its prunes (k_r2_prune_classify); BSLV_R2_RIDE=0 / debug_set key 18: two launches
     int r2_ride_gmax = 240;           // ... by at most this many workgroups (the CUs but 16 for the prunes; BSLV_R2_RIDE_G / debug_set key 19, a test hook: 1 exercises the stride)
+    bool r2_ride_lds = true;          // ... which read the chunk's halfspaces from an image in their LDS when it fits (r2_stage_hps); BSLV_R2_RIDE_LDS=0 / debug_set key 22: from global memory
+    bool r2_split = true;             // a round's large prunes are worked in parts by helper workgroups of the same launch (k2v2_assign); BSLV_R2_SPLIT=0 / debug_set key 23: one workgroup per prune
+    int r2_split_min = 64;            // ... prunes of this many members or more, in 1 + members / r2_split_min parts (BSLV_R2_SPLIT_MIN / debug_set key 24)
+    int r2_split_parts = 4;           // ... in at most this many parts, 2 .. K2_MAXPARTS (BSLV_R2_SPLIT_PARTS / debug_set key 25)
+    int r2_split_helpers = 32;        // ... from a pool of this many helper workgroups per launch (BSLV_R2_SPLIT_H / debug_set key 26)
     int r2_ride_threads = 256;        // ... in each of which this many threads work (a power of two, 64 .. K2T; BSLV_R2_RIDE_T / debug_set key 20)
     int chunk_cuts = 1024;             // cuts classified and applied together (bslv_poly_debug_set(h, 7, n); at most 4096)
     int r2_defer = 0;                 // rounds of a chunk stop when one holds fewer cuts than this; what is left is handed BACK to the caller (rc 2) -- see bslv_poly_set_defer
@@ -3419,13 +3521,18 @@ int bslv_poly_create(bslv_poly **out, int dim, int v2h, const double *c)
     if (const char *e = getenv("BSLV_R2_RIDE")) h->r2_ride = atoi(e) != 0;
     if (const char *e = getenv("BSLV_R2_RIDE_G")) h->r2_ride_gmax = std::max(1, atoi(e));
     if (const char *e = getenv("BSLV_R2_RIDE_T")) bslv_poly_debug_set(h, 20, atol(e));
+    if (const char *e = getenv("BSLV_R2_RIDE_LDS")) bslv_poly_debug_set(h, 22, atol(e));
+    if (const char *e = getenv("BSLV_R2_SPLIT")) bslv_poly_debug_set(h, 23, atol(e));
+    if (const char *e = getenv("BSLV_R2_SPLIT_MIN")) bslv_poly_debug_set(h, 24, atol(e));
+    if (const char *e = getenv("BSLV_R2_SPLIT_PARTS")) bslv_poly_debug_set(h, 25, atol(e));
+    if (const char *e = getenv("BSLV_R2_SPLIT_H")) bslv_poly_debug_set(h, 26, atol(e));
     if (const char *e = getenv("BSLV_CHUNK_CUTS")) h->chunk_cuts = std::min(4096, std::max(32, atoi(e)));
     if (const char *e = getenv("BSLV_R2_MIN_CUTS")) h->r2_min_cuts = std::max(-1, atoi(e));
     if (const char *e = getenv("BSLV_POLY_SNAP")) h->snap = atoi(e) != 0;
     if (const char *e = getenv("BSLV_CROSS_UB")) h->cross_ub = std::max(0, atoi(e));
     if (const char *e = getenv("BSLV_K2_LDS")) h->k2_lds = (size_t)std::max(64, atoi(e));      // test hook: a small value forces the multi-kernel prune
     if (const char *e = getenv("BSLV_K2_WINDOW")) { const long long v = atoll(e); if (v > 0) h->window_blocks = std::min(v, PAIR_WINDOW_DEFAULT); }
-    if (getenv("BSLV_K2_DEBUG") && malloc0(&h->k2dbg, 16 * sizeof(unsigned long long)) == hipSuccess) (void)hipMemset(h->k2dbg, 0, 16 * sizeof(unsigned long long));
+    if (getenv("BSLV_K2_DEBUG") && malloc0(&h->k2dbg, K2_DBG_SLOTS * sizeof(unsigned long long)) == hipSuccess) (void)hipMemset(h->k2dbg, 0, K2_DBG_SLOTS * sizeof(unsigned long long));
     h->rounds = new RoundsBuf();
     // dual slot 0: "facet at infinity", ideal point (0,..,0,-1)  (bslv_poly.c:83-92)
     std::vector<double> z(dim, 0.0);
@@ -3453,8 +3560,12 @@ void bslv_poly_destroy(bslv_poly *h)
                 h->tm_launch[2] / std::max(1L, h->n_single), h->tm_launch[3] / std::max(1L, h->n_single));
     if (h->cutlog) fclose(h->cutlog);
     if (h->k2dbg) {
-        unsigned long long t[16];
-        if (hipMemcpy(t, h->k2dbg, sizeof(t), hipMemcpyDeviceToHost) == hipSuccess && t[7])
+        unsigned long long t[K2_DBG_SLOTS] = {0};
+        if (hipMemcpy(t, h->k2dbg, sizeof(t), hipMemcpyDeviceToHost) != hipSuccess) t[7] = 0;
+        if (t[7] && t[17])
+            fprintf(stderr, "k2_fused, rounds: prunes of >= %d members: %llu of %llu, members mean %.0f, P4 mean %.2f us, whole prune mean %.2f us | over all prunes: P4 max %.2f us, whole prune max %.2f us\n", K2_DBG_LARGE, t[14], t[7],
+                    t[14] ? (double)t[18] / t[14] : 0.0, t[14] ? t[15] * 0.01 / t[14] : 0.0, t[14] ? t[16] * 0.01 / t[14] : 0.0, t[13] * 0.01, t[17] * 0.01);
+        if (t[7])
             fprintf(stderr, "k2_fused phases (us/launch over %llu launches; rounds: per prune workgroup): P0a %.2f P0 %.2f P1 %.2f P2 %.2f P3 %.2f P4 %.2f P5 %.2f P6 %.2f | W %.1f nloc %.0f | members mean %.0f max %llu\n", t[7],
                     t[10] * 0.01 / t[7], t[0] * 0.01 / t[7], t[1] * 0.01 / t[7], t[2] * 0.01 / t[7], t[3] * 0.01 / t[7], t[4] * 0.01 / t[7], t[5] * 0.01 / t[7], t[6] * 0.01 / t[7], (double)t[8] / t[7], (double)t[9] / t[7],
                     (double)t[11] / t[7], t[12]);
@@ -3922,6 +4033,11 @@ int bslv_poly_debug_set(bslv_poly *h, int key, long value)
     case 18: h->r2_ride = value != 0; return 0;                           /* rounds: the new vertices classified inside the launch of the prunes (1) / a launch of their own (0) */
     case 19: h->r2_ride_gmax = (int)std::max(1L, std::min(4096L, value)); return 0;     /* ... by at most this many workgroups (test hook) */
     case 20: { int t = 64; while (t < K2T && t < value) t <<= 1; h->r2_ride_threads = t; return 0; }      /* ... threads of each that work: a power of two, 64 .. 1024 */
+    case 22: h->r2_ride_lds = value != 0; return 0;                       /* ... halfspaces from an LDS image (1) / from global memory (0) */
+    case 23: h->r2_split = value != 0; return 0;                          /* rounds: large prunes worked in parts by helper workgroups (1) / one workgroup per prune (0) */
+    case 24: h->r2_split_min = (int)std::max(2L, std::min((long)K2_MAXNM + 1, value)); return 0;      /* ... prunes of this many members or more */
+    case 25: h->r2_split_parts = (int)std::max(2L, std::min((long)K2_MAXPARTS, value)); return 0;     /* ... in at most this many parts */
+    case 26: h->r2_split_helpers = (int)std::max(1L, std::min(256L, value)); return 0;                /* ... from a pool of this many helpers per launch */
     case 16: h->k2_noflags = value != 0; return 0;                       /* multi-kernel prune of large facets without a flag byte per pair (forced; by itself from 4 GiB of flags on) */
     case 11: h->r2_mis = value != 0; return 0;                            /* rounds: maximal independent set from the conflict matrix (1) / local minima of one order (0) */
     case 14: h->r2_defer = (int)std::max(0L, value); return 0;           /* see bslv_poly_set_defer */
@@ -4095,6 +4211,12 @@ int bslv_poly_rounds2_stats(const bslv_poly *h, long out[5])
     if (!h || !out) return BSLV_E_ARG;
     out[0] = h->r2_rounds; out[1] = h->r2_cuts; out[2] = h->r2_chunks; out[3] = h->r2_fallback_prunes; out[4] = h->r2_declined;
     return 0;
+}
+// a round's large prunes worked in parts (K2V2, k2v2_assign): out[0] prunes that were split, [1] helper workgroups that took a part of one
+int bslv_poly_split_stats(bslv_poly *h, long out[2])
+{
+    if (!h || !out) return BSLV_E_ARG;
+    return rounds2_split_stats(h, out);
 }
 // MEASUREMENT ONLY (bench / profiles): turns the engine into nv synthetic live points so that the
 // batched incidence kernel can be timed at sizes beyond the caches.  The polyhedron is destroyed.

@@ -12,6 +12,7 @@ struct Rounds2Buf {
     int *own = nullptr; int vcap = 0;
     unsigned long long *hw = nullptr; size_t hwcap = 0;     // element-major class words (hot elements and what the chunk creates)
     int *cnt_g = nullptr, *nm_g = nullptr, *mem_g = nullptr; unsigned *adj_g = nullptr; int scap = 0;
+    int *npart_g = nullptr, *cntx_g = nullptr, *split_stat = nullptr;      // prunes worked in parts (K2V2)
     int *gout = nullptr, *gout_h = nullptr;
     int seq = 0;
     unsigned chunk_seed = 0;
@@ -28,12 +29,22 @@ static void rounds2_free(Rounds2Buf &V)
 {
     auto fr = [](void *p) { if (p) (void)hipFree(p); };
     fr(V.st_d); fr(V.alive); fr(V.alive_prev); fr(V.anym); fr(V.bad); fr(V.selmap); fr(V.sel); fr(V.order); fr(V.rcflag); fr(V.own);
-    fr(V.cnt_g); fr(V.nm_g); fr(V.mem_g); fr(V.adj_g); fr(V.gout); fr(V.hw); fr(V.M); fr(V.selw); fr(V.wm); fr(V.mcnt); fr(V.fc2); fr(V.fl2); fr(V.fc_ticket);
+    fr(V.cnt_g); fr(V.nm_g); fr(V.npart_g); fr(V.cntx_g); fr(V.split_stat); fr(V.mem_g); fr(V.adj_g); fr(V.gout); fr(V.hw); fr(V.M); fr(V.selw); fr(V.wm); fr(V.mcnt); fr(V.fc2); fr(V.fl2); fr(V.fc_ticket);
     if (V.mail_h) (void)hipHostFree(V.mail_h);
     if (V.gout_h) (void)hipHostFree(V.gout_h);
     V = Rounds2Buf();
 }
 static hipError_t r2_prune_classify_grant(int d, int lds);
+static int rounds2_split_stats(bslv_poly *h, long out[2])
+{
+    int c[2] = {0, 0};
+    if (h->rounds2 && h->rounds2->split_stat) {
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        HIP_TRY(hipMemcpy(c, h->rounds2->split_stat, sizeof c, hipMemcpyDeviceToHost));
+    }
+    out[0] = c[0]; out[1] = c[1];
+    return 0;
+}
 static int rounds2_ensure(bslv_poly *h, Rounds2Buf &V, int Bc)
 {
     hipStream_t s = h->stream;
@@ -44,6 +55,8 @@ static int rounds2_ensure(bslv_poly *h, Rounds2Buf &V, int Bc)
         HIP_TRY(hipHostGetDevicePointer((void **)&V.mail_d, V.mail_h, 0));
         memset(V.mail_h, 0, R2_MAILS * sizeof(RState));
         HIP_TRY(malloc0(&V.gout, 4 * sizeof(int)));
+        HIP_TRY(malloc0(&V.split_stat, 2 * sizeof(int)));
+        HIP_TRY(hipMemsetAsync(V.split_stat, 0, 2 * sizeof(int), s));
         HIP_TRY(hipHostMalloc(&V.gout_h, 4 * sizeof(int)));
         HIP_TRY(malloc0(&V.M, (size_t)R2_MAXC * (R2_MAXC / 32) * sizeof(unsigned)));
         HIP_TRY(malloc0(&V.selw, 64 * sizeof(unsigned)));
@@ -70,7 +83,9 @@ static int rounds2_ensure(bslv_poly *h, Rounds2Buf &V, int Bc)
         if ((rc = grow(&V.cnt_g, 0, (size_t)nc, s))) return rc;
         if ((rc = grow(&V.nm_g, 0, (size_t)nc, s))) return rc;
         if ((rc = grow(&V.mem_g, 0, (size_t)nc * K2_MAXNM, s))) return rc;
-        if ((rc = grow(&V.adj_g, 0, (size_t)nc * R2_ADJW, s))) return rc;
+        if ((rc = grow(&V.adj_g, 0, (size_t)nc * R2_ADJW, s, true))) return rc;         // (zero: what the parts of a split prune rely on, k_r2_k2emit keeps it so)
+        if ((rc = grow(&V.npart_g, 0, (size_t)nc, s, true))) return rc;
+        if ((rc = grow(&V.cntx_g, 0, (size_t)nc * (K2_MAXPARTS - 1), s, true))) return rc;
         V.bcap = nc; V.scap = nc;
     }
     if (h->P.cap > V.vcap) { if ((rc = grow(&V.own, 0, (size_t)h->P.cap, s))) return rc; V.vcap = h->P.cap; }
@@ -366,7 +381,8 @@ static int run_rounds2(bslv_poly *h, RoundsBuf &R, const std::vector<int> &todo,
                        (const int *)h->EP[cur], h->EP[1 - cur], Z, (const unsigned long long *)V.hw, (const unsigned *)V.wm, nw, (int *)nullptr,
                        (const unsigned *)V.selw, (const int *)V.selmap);
         const int S_ub = std::max(1, std::min(Bc - napplied - nredundant, V.scap));
-        const K2V2 KV{V.st_d, R.cutof, V.mem_g, V.adj_g, V.cnt_g, V.nm_g, R2_ADJW, &V.st_d->pair_tests, V.fc2, V.fl2, V.fc_ticket, V.fc2 ? V.fc_slices : 0, V.fc_stride};
+        const K2V2 KV{V.st_d, R.cutof, V.mem_g, V.adj_g, V.cnt_g, V.nm_g, R2_ADJW, &V.st_d->pair_tests, V.fc2, V.fl2, V.fc_ticket, V.fc2 ? V.fc_slices : 0, V.fc_stride,
+                      V.npart_g, V.cntx_g, 0, h->r2_split_min, h->r2_split_parts, V.split_stat};
         const int seq = ++V.seq;
         // the new vertices of the round against the cuts that are still alive: workgroups that stride over whatever the round made.  Nothing
         // reads these class words before the next round's k_r2_minit, and the prunes read none: the classification rides along in
@@ -377,8 +393,12 @@ static int run_rounds2(bslv_poly *h, RoundsBuf &R, const std::vector<int> &todo,
             // vertices in one pass, at most r2_ride_gmax: each holds the LDS of a CU like a prune does; the prunes are dispatched first
             const int nthr = std::max(h->r2_ride_threads, std::min(nwp, K2T));
             const int vpb = std::max(1, nthr / nwp), G = std::max(1, std::min(h->r2_ride_gmax, (want + vpb - 1) / vpb));
-            launch_r2_prune_classify(d, dim3(S_ub + G), h->k2_lds, s, h->P, h->members, h->fcount, h->flocal, (int)(h->k2_lds / 8), Enew, h->totals + 2, h->k2mail_d, h->k2dbg, h->abort_d,
-                                     Hp{}, KV, (const double *)h->hps_d, Bc, nw, nwp, (const unsigned *)V.alive, V.hw, V.wm, G, nthr, mis ? 1 : 0);
+            // ... and behind the prunes a pool of helper workgroups, which take parts of the round's large prunes (k2v2_assign); a helper
+            // with nothing dealt to it returns after its scan of the candidates
+            K2V2 KH = KV;
+            KH.helpers = h->r2_split ? h->r2_split_helpers : 0;
+            launch_r2_prune_classify(d, dim3(S_ub + KH.helpers + G), h->k2_lds, s, h->P, h->members, h->fcount, h->flocal, (int)(h->k2_lds / 8), Enew, h->totals + 2, h->k2mail_d, h->k2dbg, h->abort_d,
+                                     Hp{}, KH, (const double *)h->hps_d, Bc, nw, nwp, (const unsigned *)V.alive, V.hw, V.wm, G, nthr, mis ? 1 : 0, h->r2_ride_lds ? 1 : 0);
         } else {
             launch_r2_classify3(d, dim3(std::max(1, std::min(4096, (want + PB / nwp - 1) / (PB / nwp)))), s, h->P, (const double *)h->hps_d, Bc, nw, nwp, (const RState *)V.st_d,
                                 (const unsigned *)V.alive, V.hw, V.wm, (int *)nullptr, mis ? 1 : 0);
@@ -386,8 +406,8 @@ static int run_rounds2(bslv_poly *h, RoundsBuf &R, const std::vector<int> &todo,
                                (int *)nullptr, h->totals + 2, h->k2mail_d, 0, h->k2dbg, (const CutDev *)nullptr, h->abort_d, (int *)nullptr, Hp{}, (int *)nullptr,
                                (int *)nullptr, KV);
         }
-        hipLaunchKernelGGL(k_r2_k2emit, dim3(S_ub), dim3(K2T), 0, s, V.st_d, (const int *)V.cnt_g, (const int *)V.nm_g, (const unsigned *)V.adj_g, (const int *)V.mem_g,
-                           R2_ADJW, Enew, h->EP[1 - cur], h->ecap, V.mail_d + (seq % R2_MAILS), seq);
+        hipLaunchKernelGGL(k_r2_k2emit, dim3(S_ub), dim3(K2T), 0, s, V.st_d, (const int *)V.cnt_g, (const int *)V.nm_g, V.adj_g, (const int *)V.npart_g, (const int *)V.cntx_g,
+                           (const int *)V.mem_g, R2_ADJW, Enew, h->EP[1 - cur], h->ecap, V.mail_d + (seq % R2_MAILS), seq);
         HIP_TRY(hipGetLastError());
         cur = 1 - cur;
         *seq_out = seq; *sub_out = S_ub;
@@ -531,7 +551,7 @@ static int run_rounds2(bslv_poly *h, RoundsBuf &R, const std::vector<int> &todo,
             // the adjacent pairs did not fit behind the edges: grow (copies the new list) and emit again (the bitmaps are still there)
             if ((rc = ensure_ecap(h, m.ne_next + m.epairs + 1))) return rc;
             seq = ++V.seq;
-            hipLaunchKernelGGL(k_r2_k2emit, dim3(S_ub), dim3(K2T), 0, s, V.st_d, (const int *)V.cnt_g, (const int *)V.nm_g, (const unsigned *)V.adj_g,
+            hipLaunchKernelGGL(k_r2_k2emit, dim3(S_ub), dim3(K2T), 0, s, V.st_d, (const int *)V.cnt_g, (const int *)V.nm_g, V.adj_g, (const int *)V.npart_g, (const int *)V.cntx_g,
                                (const int *)V.mem_g, R2_ADJW, h->E[h->ecur], h->EP[h->ecur], h->ecap, V.mail_d + (seq % R2_MAILS), seq);
             HIP_TRY(hipGetLastError());
             if ((rc = r2_wait(h, V, seq, &m))) return rc;

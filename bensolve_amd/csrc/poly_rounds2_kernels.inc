@@ -995,11 +995,24 @@ __global__ __launch_bounds__(PB) void k_r2_assign3(PolyView P, const unsigned lo
 // The next round's k_r2_minit is the first to read these words (k_r2_k2emit reads none).
 // block / nblocks: this workgroup's number among those that classify; nthr: its threads (PB in k_r2_classify3, K2T when it rides along
 // with the prunes in k_r2_prune_classify).  No barrier in here: workgroups of another kernel call it from a role branch.
-template <int D>
+// LDSH: `hps` is the LDS image of the chunk's halfspaces that r2_stage_hps made (component-major, the class word fastest: the lanes
+// of a vertex read consecutive doubles); the operands, the order of the fma over k and the thresholds are those of the global-memory
+// path, so the class words are bit-identical.
+__device__ __forceinline__ int r2_hps_lds_stride(int nw) { return nw | 1; }      // odd: the staging stores of a wave spread over the banks
+__device__ __forceinline__ void r2_stage_hps(const double *__restrict__ hps, int B, int nw, int d, double *lh)
+{
+    const int nwl = r2_hps_lds_stride(nw), n = B * (d + 3);
+    for (int e = threadIdx.x; e < n; e += blockDim.x) {
+        const int c = e / (d + 3), k = e - c * (d + 3);
+        lh[((c & 31) * (d + 3) + k) * nwl + (c >> 5)] = hps[e];
+    }
+}
+template <int D, bool LDSH = false>
 __device__ __forceinline__ void r2_classify3_body(const PolyView &P, const double *__restrict__ hps, int B, int nw, int nwp, const RState *st, const unsigned *__restrict__ alive,
                                                   unsigned long long *__restrict__ hw, unsigned *__restrict__ wm, int *mcnt, int block, int nblocks, int nthr, int packed = 1)
 {
     if (!st->go || r2_halted(st)) return;
+    const int hstride = LDSH ? r2_hps_lds_stride(nw) : 1;
     const int vpb = nthr / nwp, w = threadIdx.x & (nwp - 1), lv = threadIdx.x / nwp, lane = threadIdx.x & 63;
     const int ncross = st->ncross, first = st->nv_next - ncross;
     const int d = D > 0 ? D : P.d;
@@ -1016,11 +1029,12 @@ __device__ __forceinline__ void r2_classify3_body(const PolyView &P, const doubl
             const int bend = min(32, B - w * 32);
             unsigned plus = 0, notminus = 0;
             for (int bb = 0; bb < bend; bb++) {
-                const double *h = hps + (size_t)(w * 32 + bb) * (d + 3);
+                // component k of halfspace w * 32 + bb is h[k * hstride]
+                const double *h = LDSH ? hps + (size_t)bb * (d + 3) * hstride + w : hps + (size_t)(w * 32 + bb) * (d + 3);
                 double s = 0.0;
 #pragma unroll
-                for (int k = 0; k < (D > 0 ? D : MAXD); k++) if (k < d) s = fma(h[k], x[k], s);
-                const double hi = ideal ? 0.0 + POLY_EPS : h[d + 1], lo = ideal ? 0.0 - POLY_EPS : h[d + 2];
+                for (int k = 0; k < (D > 0 ? D : MAXD); k++) if (k < d) s = fma(h[k * hstride], x[k], s);
+                const double hi = ideal ? 0.0 + POLY_EPS : h[(d + 1) * hstride], lo = ideal ? 0.0 - POLY_EPS : h[(d + 2) * hstride];
                 plus |= (unsigned)(s > hi) << bb;
                 notminus |= (unsigned)(s > lo) << bb;
             }
@@ -1057,18 +1071,35 @@ __global__ __launch_bounds__(PB) void k_r2_classify3(PolyView P, const double *_
 template <int D>
 __global__ __launch_bounds__(K2T) void k_r2_prune_classify(PolyView P, int *members, int *fcount, int *flocal, int lds_words, int2 *E, Tri *totals, Mail *mail, unsigned long long *dbg,
                                                            int *abort_flag, Hp hn, K2V2 V, const double *__restrict__ hps, int B, int nw, int nwp, const unsigned *__restrict__ alive,
-                                                           unsigned long long *__restrict__ hw, unsigned *__restrict__ wm, int G, int nthr, int packed)
+                                                           unsigned long long *__restrict__ hw, unsigned *__restrict__ wm, int G, int nthr, int packed, int hps_lds)
 {
-    const int S = max(V.st->S, 0), b = (int)blockIdx.x;
-    if (b >= S) {
-        // only the first nthr threads (whole waves) of a classifying workgroup work: the classification is bound by the loads of the
-        // halfspaces per CU (every lane of a wave reads another halfspace), so it wants few waves on MANY CUs, and a workgroup of this launch
-        // has a CU to itself -- with all K2T threads at work a round's new vertices sat on 57 CUs, 16 waves each, and took twice the prunes' time
-        if (b < S + G && (int)threadIdx.x < nthr) r2_classify3_body<D>(P, hps, B, nw, nwp, V.st, alive, hw, wm, (int *)nullptr, b - S, G, nthr, packed);
+    extern __shared__ unsigned long long k2_dyn[];
+    const int S = max(V.st->S, 0), H = V.helpers, b = (int)blockIdx.x;
+    if (b >= S + H) {
+        if (b < S + H + G) {
+            // hps_lds: the workgroup has a CU's LDS to itself (the dynamic LDS of the prunes), so when the chunk's halfspaces fit there
+            // (uniform over the launch) it stages them once with coalesced loads and classifies from the image -- read from global
+            // memory, every load of a wave touches 32 cache lines for 8 bytes each.  All threads stage, and meet at the one barrier
+            // (the conditions are those under which r2_classify3_body returns at once: uniform).
+            const int d = D > 0 ? D : P.d;
+            const bool staged = hps_lds && (long long)r2_hps_lds_stride(nw) * 32 * (d + 3) <= (long long)lds_words && V.st->go && !r2_halted(V.st);
+            if (staged) {
+                r2_stage_hps(hps, B, nw, d, (double *)k2_dyn);
+                __syncthreads();
+            }
+            // only the first nthr threads (whole waves) of a classifying workgroup work: the classification is bound by the loads of the
+            // halfspaces per CU (every lane of a wave reads another halfspace), so it wants few waves on MANY CUs, and a workgroup of this launch
+            // has a CU to itself -- with all K2T threads at work a round's new vertices sat on 57 CUs, 16 waves each, and took twice the prunes' time
+            if ((int)threadIdx.x < nthr) {
+                if (staged) r2_classify3_body<D, true>(P, (const double *)k2_dyn, B, nw, nwp, V.st, alive, hw, wm, (int *)nullptr, b - S - H, G, nthr, packed);
+                else r2_classify3_body<D>(P, hps, B, nw, nwp, V.st, alive, hw, wm, (int *)nullptr, b - S - H, G, nthr, packed);
+            }
+        }
         if (b > 0) return;
     }
+    // b < S: prune b; S <= b < S + H: helper b - S of the pool (k2v2_assign).  Workgroup 0 is never a helper: with S = 0 it enters as a prune
     k2_fused_body<true>(P, members, 0, 0, 0, fcount, flocal, lds_words, E, 0, (int *)nullptr, totals, mail, 0, dbg, (const CutDev *)nullptr, abort_flag, (int *)nullptr, hn, (int *)nullptr,
-                        (int *)nullptr, V);
+                        (int *)nullptr, V, b >= S && b > 0 ? b - S : -1);
 }
 
 // The cuts still alive when a chunk hands them back (bslv_poly_set_defer) WILL be applied, with a later batch: every element that is
@@ -1105,8 +1136,8 @@ __global__ __launch_bounds__(PB) void k_r2_words(PolyView P, const unsigned long
 
 // ordered emission of the adjacent pairs of every selected cut (cut by cut in selection order, pairs in lexicographic order
 // of the member positions: what a sequence of k2_fused launches appends), commit of the round, mailbox
-__global__ __launch_bounds__(K2T) void k_r2_k2emit(RState *st, const int *__restrict__ cnt_g, const int *__restrict__ nm_g, const unsigned *__restrict__ adj_g,
-                                                   const int *__restrict__ mem_g, int adjw_cap, int2 *E, int *EP, int ecap, RState *mail, int seq)
+__global__ __launch_bounds__(K2T) void k_r2_k2emit(RState *st, const int *__restrict__ cnt_g, const int *__restrict__ nm_g, unsigned *__restrict__ adj_g,
+                                                   const int *__restrict__ npart_g, const int *__restrict__ cntx_g, const int *__restrict__ mem_g, int adjw_cap, int2 *E, int *EP, int ecap, RState *mail, int seq)
 {
     __shared__ Tri lds[16];
     __shared__ int s_carry;
@@ -1119,7 +1150,9 @@ __global__ __launch_bounds__(K2T) void k_r2_k2emit(RState *st, const int *__rest
     }
     // pairs of the cuts before this one, of all cuts; prunes that asked for their fallback count nothing here
     Tri part{0, 0, 0};
-    for (int k = tid; k < S; k += K2T) { const int c = cnt_g[k]; if (c > 0) { part.b += c; if (k < s) part.a += c; } if (c < 0) part.c += 1; }
+    // (a prune worked in parts: its own workgroup's pairs and, beside them, those of each further part)
+    auto pairs_of = [&](int k) { int c = cnt_g[k]; if (c >= 0) for (int p = 1; p < npart_g[k]; p++) c += cntx_g[k * (K2_MAXPARTS - 1) + p - 1]; return c; };
+    for (int k = tid; k < S; k += K2T) { const int c = pairs_of(k); if (c > 0) { part.b += c; if (k < s) part.a += c; } if (c < 0) part.c += 1; }
     part = block_sum(part, lds);
     const int ebase = st->ne_next, before = part.a, total = part.b;
     const bool over = (long long)ebase + total > ecap;
@@ -1130,17 +1163,20 @@ __global__ __launch_bounds__(K2T) void k_r2_k2emit(RState *st, const int *__rest
         rstate_publish(st, mail, seq);
     }
     if (over || s >= S) return;
-    const int cnt = cnt_g[s];
+    const int cnt = pairs_of(s);
     if (cnt <= 0) return;
     const int nm = nm_g[s];
     const int nadjw = (int)(((long long)nm * (nm - 1) / 2 + 31) / 32);
-    const unsigned *adj = adj_g + (size_t)s * adjw_cap;
+    // The parts of a split prune OR their words into a bitmap that must be zero: the words go back to zero here, where they are read
+    // for the last time (when the pairs did not fit, `over`, this kernel runs again on the same bitmaps and clears them then)
+    unsigned *adj = adj_g + (size_t)s * adjw_cap;
     const int *mem = mem_g + (size_t)s * K2_MAXNM;
     if (tid == 0) s_carry = 0;
     __syncthreads();
     for (int w0 = 0; w0 < nadjw; w0 += K2T) {
         const int ww = w0 + tid;
         unsigned word = ww < nadjw ? adj[ww] : 0u;
+        if (word) adj[ww] = 0u;
         Tri t{(int)__popc(word), 0, 0};
         Tri tot;
         const Tri ex = block_exscan(t, &tot, lds);

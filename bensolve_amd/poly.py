@@ -104,6 +104,13 @@ class PolyEngine:
         check(self.lib.bslv_poly_rounds2_stats(self.h, out))
         return dict(rounds=out[0], cuts=out[1], chunks=out[2], fallback_prunes=out[3], declined=out[4])
 
+    def split_stats(self):
+        """rounds: prunes that were worked in parts by several workgroups of their launch, helper workgroups that took a part"""
+        out = (ctypes.c_long * 2)()
+        self.lib.bslv_poly_split_stats.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        check(self.lib.bslv_poly_split_stats(self.h, out))
+        return dict(split_prunes=out[0], helper_parts=out[1])
+
     def rounds2_health(self):
         """(cuts handed back late, mailbox reads repeated because the sequence number arrived before the state)"""
         for f in ("bslv_poly_rounds2_late_left", "bslv_poly_rounds2_torn_reads"):

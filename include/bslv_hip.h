@@ -629,7 +629,7 @@ long bslv_poly_rounds2_torn_reads(const bslv_poly *h);
 /* test hook, same switches as the BSLV_* environment variables but at run time: key 0 dynamic LDS bytes of the one-workgroup
  * prune (64 forces the multi-kernel prune), 1 speculative launch on/off, 2 hot mode on/off, 3 CROSS_UB, 4 size of a new facet
  * from which the multi-kernel prune builds facet-major member lists (default 4096), 5 member lists on/off, 6 device-selected
- * rounds of independent cuts inside a hot chunk on/off, 7 cuts per chunk (32..4096, default 512); keys 8, 10-12, 14, 16 and 18-20:
+ * rounds of independent cuts inside a hot chunk on/off, 7 cuts per chunk (32..4096, default 512); keys 8, 10-12, 14, 16 and 18-26:
  * bslv_poly_debug_set in poly_engine.hip; any other key is BSLV_E_ARG */
 /* bslv_poly_add_cuts may hand cuts BACK (rc 2: not applied, dual slot left unused) when the rounds of a chunk get thinner than
  * min_cuts cuts -- the tail of a chunk is its cliques, one cut each per pass over the polyhedron; the caller hands the same
@@ -641,6 +641,9 @@ int  bslv_poly_debug_set(bslv_poly *h, int key, long value);
  * the number of cuts classified and applied together): out[0] rounds, [1] cuts applied in them, [2] chunks, [3] prunes that took
  * the multi-kernel path, [4] rounds taken back for want of capacity */
 int  bslv_poly_rounds2_stats(const bslv_poly *h, long out[5]);
+/* rounds: prunes of a round that were worked in parts by several workgroups of the launch (debug_set keys 23-26; BSLV_R2_SPLIT,
+ * _MIN, _PARTS, _H): out[0] prunes that were split, [1] helper workgroups that took a part of one */
+int  bslv_poly_split_stats(bslv_poly *h, long out[2]);
 int  bslv_poly_init(bslv_poly *h, int *rc_out);               /* poly__intl_apprx :153 */
 int  bslv_poly_next(bslv_poly *h, double *val, int *ideal, int *idx, int *rc_out); /* poly__get_vrtx :210 */
 int  bslv_poly_unprocessed(bslv_poly *h, int max_out, int *idx, double *val, int *ideal, int *count);
