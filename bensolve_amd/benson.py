@@ -158,6 +158,23 @@ class BensonEngine:
         self.lib.bslv_benson_get_canonical.argtypes = [ctypes.c_void_p]
         return int(self.lib.bslv_benson_get_canonical(self.h))
 
+    def set_lp_method(self, method):
+        """the simplex method of the driver's LPs: 0 dual, 1 primal, 2 repair, -1 unset = the calls as they always were
+        (bslv_benson_set_lp_method, include/bslv_hip.h).  Returns the library's code."""
+        self.lib.bslv_benson_set_lp_method.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        return int(self.lib.bslv_benson_set_lp_method(self.h, int(method)))
+
+    def get_lp_method(self):
+        self.lib.bslv_benson_get_lp_method.argtypes = [ctypes.c_void_p]
+        return int(self.lib.bslv_benson_get_lp_method(self.h))
+
+    def lp_method_stats(self):
+        """LPs solved so far under DUAL, PRIMAL, REPAIR by the driver's method calls (bslv_benson_lp_method_stats)"""
+        out = (ctypes.c_long * 3)()
+        self.lib.bslv_benson_lp_method_stats.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        check(self.lib.bslv_benson_lp_method_stats(self.h, out))
+        return [int(v) for v in out]
+
     def canonical_stats(self):
         """tie phase of the LPs of the last solve_local and of all so far (bslv_benson_canonical_stats)"""
         last, tot = (ctypes.c_long * 4)(), (ctypes.c_long * 4)()

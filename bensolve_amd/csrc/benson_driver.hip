@@ -33,6 +33,11 @@ struct bslv_benson {
     int rows_folded = 0;                              // singleton rows of A turned into column bounds
     bool hom = false;                                 // homogeneous problem (phases 0 and 1)
     long tot_retries = 0;                             // LPs solved again from the root tableau / the standard basis
+    // bslv_benson_set_lp_method: -1 = unset (the engine's own method, the calls as they always were); else the start LPs, every P2(v)
+    // batch and both stages of its retry go through bslv_lpq_solve_batch_method.  lp_method_lps: LPs solved so far under DUAL / PRIMAL /
+    // REPAIR by such calls (bslv_benson_lp_method_stats)
+    int lp_method = -1;
+    long lp_method_lps[3] = {0, 0, 0};
     long tot_root_starts = 0, tot_nearest_starts = 0; // LPs whose parent's tableau was not resident here: started from the root tableau / from the nearest resident one
     bool nearest_start = true;
     // option -s (opt->solution == PRE_IMG_ON): x of every confirmed vertex, (u, w) of every cut (bslv_algs.c:1064-1079)
@@ -271,6 +276,11 @@ int bslv_benson_create_ex(bslv_benson **out, int m, int n, int q, const double *
     if (const char *e = getenv("BSLV_CANONICAL_DUAL")) {
         if (atoi(e) != 0 && !h->hom && (rc = bslv_benson_set_canonical(h, 1))) { bslv_benson_destroy(h); return rc; }
     }
+    // BSLV_BENSON_LP_METHOD=dual|primal|repair: bslv_benson_set_lp_method (any other value leaves it unset, like the other variables)
+    if (const char *e = getenv("BSLV_BENSON_LP_METHOD")) {
+        const int m = !strcmp(e, "dual") ? BSLV_LP_METHOD_DUAL : !strcmp(e, "primal") ? BSLV_LP_METHOD_PRIMAL : !strcmp(e, "repair") ? BSLV_LP_METHOD_REPAIR : -1;
+        if (m >= 0) h->lp_method = m;
+    }
     *out = h;
     return 0;
 }
@@ -290,6 +300,26 @@ int bslv_benson_set_canonical(bslv_benson *h, int on)
     return 0;
 }
 int bslv_benson_get_canonical(const bslv_benson *h) { return h && h->canonical; }
+// The simplex method of the driver's LPs: see bslv_hip.h.  One batch of the driver under it (the start LPs, solve_local and its retry)
+int bslv_benson_set_lp_method(bslv_benson *h, int method)
+{
+    if (!h || method < -1 || method > BSLV_LP_METHOD_REPAIR) { set_error("bslv_benson_set_lp_method: bad argument (method %d)", method); return BSLV_E_ARG; }
+    h->lp_method = method;
+    return 0;
+}
+int bslv_benson_get_lp_method(const bslv_benson *h) { return h ? h->lp_method : -1; }
+int bslv_benson_lp_method_stats(const bslv_benson *h, long out[3])
+{
+    if (!h || !out) return BSLV_E_ARG;
+    for (int k = 0; k < 3; k++) out[k] = h->lp_method_lps[k];
+    return 0;
+}
+static int solve_under_method(bslv_benson *h, int n, const int *s, const int *d, const double *lo, const double *up, int *stat, int *iter)
+{
+    if (h->lp_method < 0) return bslv_lpq_solve_batch(h->lp, n, s, d, lo, up, stat, iter);
+    h->lp_method_lps[h->lp_method] += n;
+    return bslv_lpq_solve_batch_method(h->lp, h->lp_method, n, s, d, lo, up, stat, iter);
+}
 // The LP certificate of every solve_local (bslv_lpq_certify): see bslv_hip.h.  The P1(w) batches of the dual variant (vlp_phases.hip) do
 // not go through solve_local: the LP-level call serves them.
 int bslv_benson_set_certify(bslv_benson *h, int on)
@@ -375,7 +405,7 @@ int bslv_benson_start(bslv_benson *h, int *vlp_status)
         // each weighted-sum LP starts cold: freeing row j-1 leaves the previous basis dual infeasible,
         // which the dual-only engine reports as UNDEFINED (GLPK would switch to its primal phase)
         if (j > 0 && (rc = bslv_lpq_reset_slot(h->lp, 0))) return rc;
-        if ((rc = bslv_lpq_solve_batch(h->lp, 1, &zero, &zero, vlo.data(), vup.data(), &st, &it))) return rc;
+        if ((rc = solve_under_method(h, 1, &zero, &zero, vlo.data(), vup.data(), &st, &it))) return rc;
         h->tot_pivots += it;
         if (st != BSLV_LP_OPTIMAL) { report_ray(h->lp, "phase 2 (primal), weighted-sum LP", st, 0, vlo.data(), vup.data(), 0, 0, nullptr); *vlp_status = (st == BSLV_LP_INFEASIBLE) ? 1 : 2; return 0; }
         h->tot_lps++;
@@ -837,8 +867,15 @@ int bslv_benson_solve_local_ctx(bslv_benson *h, int ctx, double *records, int *p
     auto count_canonical = [h]() { long cs[4]; if (bslv_lpq_last_canonical_stats(h->lp, cs) == 0) for (int k = 0; k < 4; k++) { h->last_canon[k] += cs[k]; h->tot_canon[k] += cs[k]; } };
     // (a revised LP engine has no switch: there the batch and its retries get the direction per call, bslv_lpq_solve_batch_canonical)
     const bool canon_call = h->canonical && bslv_lpq_is_revised(h->lp);
+    // (bslv_benson_set_lp_method: the tableau form keeps its tie phase, the engine's switch holds under every method of a call; the
+    //  canonical call of the revised form solves under the engine's own method, DUAL, and no other)
+    if (canon_call && h->lp_method > BSLV_LP_METHOD_DUAL) {
+        set_error("bslv_benson_solve_local: bslv_benson_set_lp_method(%d) together with bslv_benson_set_canonical on a revised LP engine: bslv_lpq_solve_batch_canonical solves under DUAL only", h->lp_method);
+        return BSLV_E_ARG;
+    }
     auto solve = [h, canon_call](int n, const int *s, const int *d, const double *lo, const double *up, int *stat, int *iter) {
-        return canon_call ? bslv_lpq_solve_batch_canonical(h->lp, h->canon_dir.data(), n, s, d, lo, up, stat, iter) : bslv_lpq_solve_batch(h->lp, n, s, d, lo, up, stat, iter);
+        if (canon_call) { if (h->lp_method >= 0) h->lp_method_lps[h->lp_method] += n; return bslv_lpq_solve_batch_canonical(h->lp, h->canon_dir.data(), n, s, d, lo, up, stat, iter); }
+        return solve_under_method(h, n, s, d, lo, up, stat, iter);
     };
     if (h->canonical && !canon_call && !bslv_lpq_get_canonical(h->lp) && (rc = bslv_lpq_set_canonical(h->lp, 1, h->canon_dir.data()))) return rc;      // (stays on: the retries below solve with it too)
     if ((rc = solve(nl, src.data(), dst.data(), vlo.data(), vup.data(), st.data(), it.data()))) return rc;

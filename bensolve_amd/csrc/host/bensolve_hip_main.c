@@ -28,7 +28,9 @@ static void usage(void)
            "  -t, --test               audit the result polyhedron on the device after phase 2 (incidences, feasibility, the edge list\n"
            "                           against the edge test over all pairs) and print one line: polyhedron check: ... ok, or the counts\n"
            "  -k/-L/-l METHOD, -M N, -f FORMAT, -p   accepted as in the reference's command line; the LP method is recorded in the\n"
-           "                           .log (every LP is solved by the engine's dual simplex), no graphics file is written\n"
+           "                           .log; with BSLV_LP_METHOD_OPTIONS=1 in the environment -k / -L / -l are handed to the LPs of\n"
+           "                           their phase (the .log then counts them per phase), without it every LP is solved as before;\n"
+           "                           no graphics file is written\n"
            "Environment (with -a dual; both off by default):\n"
            "  BSLV_CANONICAL_OBJ=1       every P1(w) ends in its canonical optimal point, by the LP engine's switch (tableau form only)\n"
            "  BSLV_CANONICAL_OBJ_CALL=1  the same, handed to the LP engine with every solve: also under BSLV_LP_REV=1 (revised form)\n"
@@ -172,12 +174,22 @@ int main(int argc, char **argv)
     int st = 0;
     if (msg >= 1) printf("running ... \n");
     bslv_poly *lower = NULL;
-    const int vflags = (dual1 ? BSLV_VLP_PHASE1_DUAL : 0) | (presol ? BSLV_VLP_PREIMAGES : 0);
+    int vflags = (dual1 ? BSLV_VLP_PHASE1_DUAL : 0) | (presol ? BSLV_VLP_PREIMAGES : 0);
+    /* -k / -L / -l are handed on only with BSLV_LP_METHOD_OPTIONS=1 in the environment (off as shipped: without it the run is what it
+     * always was).  A phase whose option was not given, or given as auto, hands nothing on. */
+    const char *const mopt = getenv("BSLV_LP_METHOD_OPTIONS");
+    const int methods_on = mopt && atoi(mopt) != 0;
+    if (methods_on) {
+        static const int engine_method[4] = {-1, BSLV_LP_METHOD_PRIMAL, BSLV_LP_METHOD_DUAL, BSLV_LP_METHOD_REPAIR};
+        for (int ph = 0; ph < 3; ph++) if (lp_method[ph]) vflags |= BSLV_VLP_LP_METHOD(ph, engine_method[lp_method[ph]]);
+    }
     int rc = dual2 ? bslv_vlp_solve_dual2(v->m, v->n, q, v->A, v->P, v->rtype, v->rlb, v->rub, v->ctype, v->clb, v->cub,
                                           v->optdir, v->cone_gen, v->gen, v->n_gen, v->c, bounded, vflags, 1e-8, 1e-8, eps1, eps, batch, &lower, &st, &info)
                    : bslv_vlp_solve_primal(v->m, v->n, q, v->A, v->P, v->rtype, v->rlb, v->rub, v->ctype, v->clb, v->cub,
                                            v->optdir, v->cone_gen, v->gen, v->n_gen, v->c, bounded, vflags, 1e-8, 1e-8, eps1, eps, batch, &h, &st, &info);
     if (rc) { printf("engine error %d: %s\n", rc, bslv_last_error()); return 3; }
+    long lpm[5][3];
+    (void)bslv_vlp_last_lp_method_stats(lpm);
     char cfile[1100];
     if (info.c) {                                                         /* bslv_vlp.c:833-842 */
         snprintf(cfile, sizeof cfile, "%s_c.sol", base);
@@ -229,6 +241,10 @@ int main(int argc, char **argv)
             fprintf(lf, "  lp_method_phase0:   %s\n", m0);
             fprintf(lf, "  lp_method_phase1:   %s\n", m1);
             fprintf(lf, "  lp_method_phase2:   %s\n", m2);
+        }
+        if (methods_on) {      /* LPs handed to a method call, per phase_type: dual / primal / repair */
+            static const char *const pname[5] = {"phase0", "phase1_primal", "phase1_dual", "phase2_primal", "phase2_dual"};
+            for (int p = 0; p < 5; p++) fprintf(lf, "  lp_method_lps_%s: %ld dual, %ld primal, %ld repair\n", pname[p], lpm[p][0], lpm[p][1], lpm[p][2]);
         }
         fprintf(lf, "  message_level:      %d\n", msg);
         fprintf(lf, "  lp_message_level:   %d\n", 0);

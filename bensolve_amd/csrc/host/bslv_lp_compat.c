@@ -19,6 +19,8 @@ static struct {
     int bounds_dirty;
     int num;                 /* optimal solves */
     int last_status;
+    int method;              /* lp_set_options: the engine's method of the phase at hand (BSLV_LP_METHOD_*); starts as PRIMAL, GLPK's own default */
+    int method_set;          /* lp_set_options has been called since lp_init */
 } G;
 
 static void die(const char *what)
@@ -60,7 +62,44 @@ void lp_update_extra_coeffs(lp_idx n_rows, lp_idx n_cols)
     G.extra_rows = n_rows; G.extra_cols = n_cols;
 }
 
-void lp_set_options(const struct lp_opt *opt, phase_type phase) { (void)opt; (void)phase; }
+/* The reference's mapping (lp_set_options, bslv_lp.c:153-217) in the engine's numbering.  A phase has a method of its own -- the dual
+ * simplex for the primal Benson phases, the primal simplex for the dual ones, none for phase 0, which keeps whatever was set before
+ * (`prev`; GLPK starts with its primal simplex) -- and the option of the phase replaces it unless it is LP_METHOD_AUTO.  -1 for a phase
+ * or a method outside the enums (the reference asserts). */
+int bslv_lp_compat_method(const struct lp_opt *opt, phase_type phase, int prev)
+{
+    static const int of_option[3] = {BSLV_LP_METHOD_PRIMAL, BSLV_LP_METHOD_DUAL, BSLV_LP_METHOD_REPAIR};      /* PRIMAL_SIMPLEX, DUAL_SIMPLEX, DUAL_PRIMAL_SIMPLEX */
+    int own, option;
+    if (!opt) return -1;
+    switch (phase) {
+    case PHASE0: own = prev; option = (int)opt->method_phase0; break;
+    case PHASE1_PRIMAL: own = BSLV_LP_METHOD_DUAL; option = (int)opt->method_phase1; break;
+    case PHASE1_DUAL: own = BSLV_LP_METHOD_PRIMAL; option = (int)opt->method_phase1; break;
+    case PHASE2_PRIMAL: own = BSLV_LP_METHOD_DUAL; option = (int)opt->method_phase2; break;
+    case PHASE2_DUAL: own = BSLV_LP_METHOD_PRIMAL; option = (int)opt->method_phase2; break;
+    default: return -1;
+    }
+    if (option == (int)LP_METHOD_AUTO) return own;
+    if (option < 0 || option > (int)DUAL_PRIMAL_SIMPLEX) return -1;
+    return of_option[option];
+}
+/* Recorded per call; lp_solve uses it only with BSLV_LP_METHOD_OPTIONS=1 in the environment (off as shipped: the reference's driver
+ * always hands PRIMAL_SIMPLEX over for phase 0, and honouring that by default would change every existing run). */
+void lp_set_options(const struct lp_opt *opt, phase_type phase)
+{
+    const int m = bslv_lp_compat_method(opt, phase, G.method_set ? G.method : BSLV_LP_METHOD_PRIMAL);
+    if (m < 0) { fprintf(stderr, "bslv_lp_compat: lp_set_options: phase %d or its method is outside the enums\n", (int)phase); exit(3); }
+    G.method = m;
+    G.method_set = 1;
+}
+/* one solve in slot 0: under the recorded method when the switch is on, else the engine's own call */
+static void solve_slot0(int *st, int *it)
+{
+    const int zero = 0;
+    const char *e = getenv("BSLV_LP_METHOD_OPTIONS");
+    if (e && atoi(e) != 0 && G.method_set) { if (bslv_lpq_solve_batch_method(G.eng, G.method, 1, &zero, &zero, NULL, NULL, st, it)) die("bslv_lpq_solve_batch_method"); }
+    else if (bslv_lpq_solve_batch(G.eng, 1, &zero, &zero, NULL, NULL, st, it)) die("bslv_lpq_solve_batch");
+}
 
 static void set_bnd(char *types, double *lb, double *ub, const boundlist *L, int hom)
 {
@@ -129,13 +168,12 @@ lp_status_type lp_solve(size_t i)
     }
     G.bounds_dirty = 0;
     free(lo); free(up);
-    const int zero = 0;
     int st = BSLV_LP_UNDEFINED, it = 0;
     if (!G.have_basis) { if (bslv_lpq_reset_slot(G.eng, 0)) die("bslv_lpq_reset_slot"); G.have_basis = 1; }
-    if (bslv_lpq_solve_batch(G.eng, 1, &zero, &zero, NULL, NULL, &st, &it)) die("bslv_lpq_solve_batch");
-    if (st == BSLV_LP_UNDEFINED) {           /* bslv_lp.c:222-227: try again with the standard basis */
+    solve_slot0(&st, &it);
+    if (st == BSLV_LP_UNDEFINED) {           /* bslv_lp.c:222-227: try again with the standard basis (under the same method) */
         if (bslv_lpq_reset_slot(G.eng, 0)) die("bslv_lpq_reset_slot");
-        if (bslv_lpq_solve_batch(G.eng, 1, &zero, &zero, NULL, NULL, &st, &it)) die("bslv_lpq_solve_batch");
+        solve_slot0(&st, &it);
     }
     G.last_status = st;
     if (st == BSLV_LP_OPTIMAL) { G.num++; return LP_OPTIMAL; }

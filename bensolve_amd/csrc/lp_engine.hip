@@ -700,6 +700,81 @@ __global__ __launch_bounds__(NT) void k_rev_price(LpView L, BatchView Bv, int B,
     }
 }
 constexpr int REV_PRICE_SLICE = 2 * NT;             // columns per slice of k_rev_price (two per thread, one round of rev_row_slice)
+// ---- an OBJECTIVE batch under a method (bslv_lpq_solve_batch_obj_method, DUAL and REPAIR), both forms: the dual start.  When these
+//      kernels run the LP has the start of solve_batch_obj -- k_prep's objective mode: every nonbasic variable on its NATURAL side (the
+//      parent's, sanitised against the bounds), PF_PRIMAL -- and its new reduced-cost row d in dcur (tableau form: k_prep; revised form:
+//      k_rev_price, which is why the sides can only be chosen now).  The basis is made dual feasible for d: every nonbasic variable goes to
+//      the side d_j wants, and the LP runs dual simplex steps (pflags 0); k_init (revised form: k_rev_u first) forms beta from the values
+//      left here.
+//      ARTIFICIAL BOUNDS of the call (oracle/lp_dense.c olp_solve does the same per LP): the engine of an objective batch has a zero cost
+//      and none of its own.  k_obj_art gives a variable outside the per-LP range -+BIG on the side some LP of the batch needs and the
+//      variable lacks (d_j > TOL_DJ without a lower, d_j < -TOL_DJ without an upper bound), in the call's own copy of lb / ub / art, which
+//      every later kernel of the call sees in place of the engine's (solve_batch_impl).  They count as bounds as the engine's own do in
+//      solve_batch: a start on one sets bit 1 of `verified`, a conclusion on one is UNBOUNDED (conclude_optimal).  An LP that needs none
+//      never meets one: no natural side is artificial, and only a variable that needed the bound is put there.
+//      An LP with a variable no side makes dual feasible (a variable of the per-LP range without the bound its d_j wants): UNDEFINED
+//      under DUAL; under REPAIR its primal start stands, per LP.
+//      xstat[8..10]: LPs started dual, nonbasic variables moved off their natural side, LPs REPAIR left to the primal start. ----
+__device__ __forceinline__ int obj_dual_side(int natural, double lo, double up, double dj)
+{
+    if (natural == NS_S) return NS_S;
+    if (dj > TOL_DJ && !isinf(lo)) return NS_L;
+    if (dj < -TOL_DJ && !isinf(up)) return NS_U;
+    return natural;
+}
+// art: the call's copy as 32-bit words (M + N bytes, rounded up), lb / ub: the call's copies
+__global__ __launch_bounds__(NT) void k_obj_art(LpView L, BatchView Bv, int B, unsigned *art, double *lb, double *ub)
+{
+    const int b = blockIdx.x;
+    if (b >= B) return;
+    const int *nh = L.nh + (size_t)Bv.dst[b] * L.N;
+    const double *dc = Bv.dcur + (size_t)b * L.ld;
+    for (int j = threadIdx.x; j < L.N; j += NT) {
+        const int k = nh[j];
+        if (k >= L.vfirst && k < L.vfirst + L.vcnt) continue;
+        const double lo = L.lb[k], up = L.ub[k], v = dc[j];
+        if (lo == up) continue;
+        if (v > TOL_DJ && isinf(lo)) { atomicOr(art + (k >> 2), 1u << (8 * (k & 3))); lb[k] = -BIG; }
+        if (v < -TOL_DJ && isinf(up)) { atomicOr(art + (k >> 2), 2u << (8 * (k & 3))); ub[k] = BIG; }
+    }
+}
+template <int METHOD>
+__global__ __launch_bounds__(NT) void k_obj_start(LpView L, BatchView Bv, int B)
+{
+    const int b = blockIdx.x;
+    if (b >= B) return;
+    const int dst = Bv.dst[b];
+    const int *nh = L.nh + (size_t)dst * L.N;
+    int *ns = L.nstat + (size_t)dst * L.N;
+    double *xN = L.xN + (size_t)dst * L.ld;
+    const double *dc = Bv.dcur + (size_t)b * L.ld;
+    int bad = 0;
+    for (int j = threadIdx.x; j < L.N; j += NT) {
+        const int k = nh[j];
+        const double v = dc[j];
+        if (dual_start_infeasible(obj_dual_side(ns[j], LO(L, Bv, b, k), UP(L, Bv, b, k), v), v)) bad = 1;
+    }
+    bad = __syncthreads_or(bad);
+    if (bad) {      // (REPAIR: the primal start stands)
+        if (threadIdx.x == 0) { if (METHOD == BSLV_LP_METHOD_DUAL) Bv.status[b] = BSLV_LP_UNDEFINED; else atomicAdd(&Bv.xstat[10], 1); }
+        return;
+    }
+    int bigm = 0, moved = 0;
+    for (int j = threadIdx.x; j < L.N; j += NT) {
+        const int k = nh[j], natural = ns[j];
+        const double lo = LO(L, Bv, b, k), up = UP(L, Bv, b, k);
+        const unsigned char a = L.art[k];
+        const int st = obj_dual_side(natural, lo, up, dc[j]);
+        if (st == natural) continue;
+        moved++;
+        if ((st == NS_L && (a & 1)) || (st == NS_U && (a & 2))) bigm = 1;
+        ns[j] = st;
+        xN[j] = st == NS_U ? up : lo;
+    }
+    if (moved) atomicAdd(&Bv.xstat[9], moved);
+    bigm = __syncthreads_or(bigm);
+    if (threadIdx.x == 0) { Bv.pflags[b] = 0; Bv.verified[b] = 1 | (bigm ? 2 : 0); atomicAdd(&Bv.xstat[8], 1); }
+}
 
 // The slices of a row are dealt by a ticket (hmail[3]) to whoever asks: the LP's own workgroup and its helpers -- workgroups of the same
 // k_select launch (blockIdx.y > 0) that do nothing but wait for a request.  ONE workgroup per LP is what a selection is, and on ex09 the
@@ -2997,8 +3072,10 @@ struct BatchStats {
     long pivots = 0, passes = 0, launches = 0;
     double update_ms = 0, total_ms = 0;
     long ext[5] = {0, 0, 0, 0, 0}, p1[3] = {0, 0, 0};
+    long objm[4] = {0, 0, 0, 0};      // an objective batch under DUAL / REPAIR: LPs started dual, variables moved at the start, LPs handed to the primal start, dual pivots
     void add(const BatchStats &o)
     {
+        for (int k = 0; k < 4; k++) objm[k] += o.objm[k];
         iters += o.iters; pivots += o.pivots; passes += o.passes; launches += o.launches; update_ms += o.update_ms; total_ms += o.total_ms;
         for (int k = 0; k < 5; k++) ext[k] += o.ext[k];
         for (int k = 0; k < 3; k++) p1[k] += o.p1[k];
@@ -3059,6 +3136,11 @@ struct bslv_lpq {
     int *npend_d = nullptr, *flushed_d = nullptr; double *pcol_d = nullptr, *dcur_d = nullptr;     // delayed update (see BatchView)
     double *dper_d = nullptr; int *pflags_d = nullptr, *stall_d = nullptr, *xstat_d = nullptr;
     double *cvals_d = nullptr; size_t cvals_cap = 0;     // objective coefficients of solve_batch_obj
+    // bslv_lpq_solve_batch_obj_method: the method of the objective batch in flight (PRIMAL: solve_batch_obj as it always was; the rescue's
+    // re-solves included), and the call's own copy of the bounds, artificial ones added (k_obj_art)
+    int call_obj_method = BSLV_LP_METHOD_PRIMAL;
+    bool obj_call_dual = false;        // a DUAL / REPAIR call of bslv_lpq_solve_batch_obj_method is in flight (its polish, a PRIMAL batch, included)
+    double *clb_d = nullptr, *cub_d = nullptr; unsigned char *cart_d = nullptr;
     CallStats last;                    // the counters of the last solve call (bslv_lpq_last_stats and the getters beside it)
     int method = BSLV_LP_METHOD_DUAL;  // bslv_lpq_set_method (BSLV_LP_METHOD at create)
     int call_method = BSLV_LP_METHOD_DUAL;  // the method of the solve call in flight: `method`, or what bslv_lpq_solve_batch_method was given (the rescue's re-solves included)
@@ -3191,7 +3273,7 @@ static int ensure_batch(bslv_lpq *h, int B)
     HIP_TRY(malloc0(&h->dper_d, (size_t)cap * h->L.ld * sizeof(double)));
     HIP_TRY(malloc0(&h->pflags_d, cap * sizeof(int)));
     HIP_TRY(malloc0(&h->stall_d, cap * sizeof(int)));
-    if (!h->xstat_d) HIP_TRY(malloc0(&h->xstat_d, 8 * sizeof(int)));
+    if (!h->xstat_d) HIP_TRY(malloc0(&h->xstat_d, 12 * sizeof(int)));      // (8: the selections'; 3 more: the start of an objective batch under a method)
     if (!h->dbg_d) HIP_TRY(malloc0(&h->dbg_d, 16 * sizeof(unsigned long long)));
     HIP_TRY(malloc0(&h->npend_d, (size_t)2 * cap * sizeof(int)));      // (npend and flushed in one piece: bslv_lpq_park's copy of both is one readback)
     h->flushed_d = h->npend_d + cap;
@@ -3421,7 +3503,7 @@ void bslv_lpq_destroy(bslv_lpq *h)
     fr(h->dbg_d); fr(h->list_d); fr(h->cptr_d); fr(h->cidx_d); fr(h->rptr_d); fr(h->ridx_d); fr(h->cval_d); fr(h->rval_d); fr(h->cost_d); fr(h->dsl_d); fr(h->trow_d); fr(h->uvec_d); fr(h->xfull_d); fr(h->hmail_d);
     fr(h->src_d); fr(h->dst_d); fr(h->status_d); fr(h->iters_d); fr(h->mode_d); fr(h->ver_d); fr(h->qslot_d); fr(h->init_d);
     fr(h->rmark_d); fr(h->rfx_i_d); fr(h->rfx_c_d);
-    fr(h->vlo_d); fr(h->vup_d); fr(h->prow_d); fr(h->desc_d); fr(h->out_d); fr(h->active_d); fr(h->work_d); fr(h->nwork_d); fr(h->npend_d); fr(h->pcol_d); fr(h->dcur_d); fr(h->dper_d); fr(h->pflags_d); fr(h->stall_d); fr(h->xstat_d); fr(h->cvals_d);
+    fr(h->vlo_d); fr(h->vup_d); fr(h->prow_d); fr(h->desc_d); fr(h->out_d); fr(h->active_d); fr(h->work_d); fr(h->nwork_d); fr(h->npend_d); fr(h->pcol_d); fr(h->dcur_d); fr(h->dper_d); fr(h->pflags_d); fr(h->stall_d); fr(h->xstat_d); fr(h->cvals_d); fr(h->clb_d); fr(h->cub_d); fr(h->cart_d);
     if (h->status_h) (void)hipHostFree(h->status_h);
     if (h->active_h) (void)hipHostFree(h->active_h);
     if (h->init_h) (void)hipHostFree(h->init_h);
@@ -3823,14 +3905,17 @@ static bool pdv_batch(const bslv_lpq *h)
 {
     const LpView &L = h->L;
     if (h->ppricing != BSLV_LP_PRICING_DEVEX) return false;
-    if (L.objmode) return true;
+    // (an objective batch under a method, bslv_lpq_solve_batch_obj_method: PRIMAL is the objective batch it always was; DUAL makes dual
+    //  steps, its clean-up steps stay as they are; REPAIR is a PRIMAL / REPAIR batch: the primal rule unless the dual one is on)
+    if (L.objmode) return h->call_obj_method == BSLV_LP_METHOD_PRIMAL || (h->call_obj_method == BSLV_LP_METHOD_REPAIR && h->pricing != BSLV_LP_PRICING_DEVEX);
     return h->call_method != BSLV_LP_METHOD_DUAL && !L.rev && h->pricing != BSLV_LP_PRICING_DEVEX;
 }
 // A PRIMAL / REPAIR batch of the revised form (bslv_lpq_solve_batch_method): k_select_p1_rev, the instance of the default rule, whatever
 // the two pricing switches say -- neither Devex rule has an instance for the revised form's phase 1, and both counter triples read 0
 static bool rev_p1_batch(const bslv_lpq *h) { return h->L.rev && !h->L.objmode && h->call_method != BSLV_LP_METHOD_DUAL; }
-// ... and the batches under dual Devex pricing (objective batches make primal steps only: they keep the kernels they had)
-static bool dvx_batch(const bslv_lpq *h) { return h->pricing == BSLV_LP_PRICING_DEVEX && !h->L.objmode && !rev_p1_batch(h); }
+// ... and the batches under dual Devex pricing (objective batches make primal steps only: they keep the kernels they had -- unless the
+// call gave them the method DUAL or REPAIR, bslv_lpq_solve_batch_obj_method: then their steps are a DUAL solve_batch's)
+static bool dvx_batch(const bslv_lpq *h) { return h->pricing == BSLV_LP_PRICING_DEVEX && (!h->L.objmode || h->call_obj_method != BSLV_LP_METHOD_PRIMAL) && !rev_p1_batch(h); }
 static int plan_select(bslv_lpq *h, int B, const double *vlo, const double *vup, SelectPlan *plan)
 {
     LpView &L = h->L;
@@ -4271,6 +4356,26 @@ int bslv_lpq_solve_batch_obj(bslv_lpq *h, int B, const int *src, const int *dst,
 {
     return solve_batch_obj_ranged(h, B, src, dst, vlo, vup, cost_first, cost_cnt, costs, status, iters, false);
 }
+// ... under `method` for this call only: see bslv_hip.h.  PRIMAL is bslv_lpq_solve_batch_obj; DUAL and REPAIR make the parent's basis dual
+// feasible for the new objective (k_obj_art, k_obj_start) and run dual simplex steps
+int bslv_lpq_solve_batch_obj_method(bslv_lpq *h, int method, int B, const int *src, const int *dst, const double *vlo, const double *vup,
+                                    int cost_first, int cost_cnt, const double *costs, int *status, int *iters)
+{
+    if (!h || method < BSLV_LP_METHOD_DUAL || method > BSLV_LP_METHOD_REPAIR) { set_error("bslv_lpq_solve_batch_obj_method: bad argument (method %d)", method); return BSLV_E_ARG; }
+    if (method != BSLV_LP_METHOD_PRIMAL && h->tie_obj.on) { set_error("bslv_lpq_solve_batch_obj_method: the tie phase of bslv_lpq_set_canonical_obj follows a PRIMAL objective solve only (method %d)", method); return BSLV_E_ARG; }
+    h->call_obj_method = method;
+    h->obj_call_dual = method != BSLV_LP_METHOD_PRIMAL;
+    const int rc = solve_batch_obj_ranged(h, B, src, dst, vlo, vup, cost_first, cost_cnt, costs, status, iters, false);
+    h->call_obj_method = BSLV_LP_METHOD_PRIMAL;
+    h->obj_call_dual = false;
+    return rc;
+}
+int bslv_lpq_last_obj_method_stats(const bslv_lpq *h, long out[4])
+{
+    if (!h || !out) return BSLV_E_ARG;
+    for (int k = 0; k < 4; k++) out[k] = h->last.objm[k];
+    return 0;
+}
 // One batch.  Its counters (BatchStats) are gathered in a record of its own and become the call's (h->last) when the batch is over:
 // stored, or added for a re-solve of the rescue (resolve)
 static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, const double *vlo, const double *vup,
@@ -4311,6 +4416,17 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
     LpView &L = h->L;
     auto t0 = std::chrono::steady_clock::now();
     hipStream_t s = h->stream;
+    // An objective batch under DUAL / REPAIR (bslv_lpq_solve_batch_obj_method): the kernels of the call see the call's own copy of the
+    // bounds, to which k_obj_art adds its artificial ones; the engine's are put back when the call returns, on every path
+    const int objm = cvals ? h->call_obj_method : BSLV_LP_METHOD_PRIMAL;
+    struct BoundsBack { LpView &L; const double *lb, *ub; const unsigned char *art; ~BoundsBack() { L.lb = lb; L.ub = ub; L.art = art; } } bounds_back{L, L.lb, L.ub, L.art};
+    if (objm != BSLV_LP_METHOD_PRIMAL) {
+        const size_t n = (size_t)L.M + L.N, na = (n + 3) / 4 * 4;
+        if (!h->clb_d) { HIP_TRY(malloc0s(&h->clb_d, n * sizeof(double), s)); HIP_TRY(malloc0s(&h->cub_d, n * sizeof(double), s)); HIP_TRY(malloc0s(&h->cart_d, na, s)); }
+        HIP_TRY(hipMemcpyAsync(h->clb_d, h->lb_d, n * sizeof(double), hipMemcpyDeviceToDevice, s));
+        HIP_TRY(hipMemcpyAsync(h->cub_d, h->ub_d, n * sizeof(double), hipMemcpyDeviceToDevice, s));
+        HIP_TRY(hipMemcpyAsync(h->cart_d, h->art_d, n, hipMemcpyDeviceToDevice, s));
+    }
     HIP_TRY(hipMemcpyAsync(h->src_d, src, B * sizeof(int), hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(h->dst_d, dst, B * sizeof(int), hipMemcpyHostToDevice, s));
     if (L.vcnt > 0) {
@@ -4328,7 +4444,7 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
         const int need = L.maxit + 64 + ((h->tie.on || h->tie_obj.on || h->tie_call.on || h->tie_call_obj.on) ? tie_rounds_max(L) : 0);      // (the rounds of a tie phase count on behind the others')
         if ((rc = ensure_nwork(h, need, need))) return rc;
     }
-    HIP_TRY(hipMemsetAsync(h->xstat_d, 0, 8 * sizeof(int), s));
+    HIP_TRY(hipMemsetAsync(h->xstat_d, 0, 12 * sizeof(int), s));
     if (L.rfx) HIP_TRY(hipMemsetAsync(h->rmark_d, 0, (size_t)B * sizeof(int), s));
     // Devex pricing: the reference norms of the batch start at 1
     const bool dvx = dvx_batch(h);
@@ -4354,6 +4470,12 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
         if (const char *e = getenv("BSLV_REV_PRICE_LDS")) in_lds = in_lds && atoi(e) != 0;      // test hook: 0 = y from global scratch (k_rev_y), as for M > ~18 000
         if (!in_lds) hipLaunchKernelGGL(k_rev_y, dim3(B), dim3(NT), 0, s, L, bv, B);
         hipLaunchKernelGGL(k_rev_price, dim3((L.ld + REV_PRICE_SLICE - 1) / REV_PRICE_SLICE, B), dim3(NT), in_lds ? ylds : 0, s, L, bv, B, in_lds ? 1 : 0);
+    }
+    if (objm != BSLV_LP_METHOD_PRIMAL) {      // the dual start: row first (k_prep / k_rev_price above), then the call's artificial bounds, then the sides; beta follows from them (k_rev_u, k_init)
+        hipLaunchKernelGGL(k_obj_art, dim3(B), dim3(NT), 0, s, L, bv, B, reinterpret_cast<unsigned *>(h->cart_d), h->clb_d, h->cub_d);
+        L.lb = h->clb_d; L.ub = h->cub_d; L.art = h->cart_d;
+        if (objm == BSLV_LP_METHOD_DUAL) hipLaunchKernelGGL(k_obj_start<BSLV_LP_METHOD_DUAL>, dim3(B), dim3(NT), 0, s, L, bv, B);
+        else hipLaunchKernelGGL(k_obj_start<BSLV_LP_METHOD_REPAIR>, dim3(B), dim3(NT), 0, s, L, bv, B);
     }
     if (L.rev) hipLaunchKernelGGL(k_rev_u, dim3(B), dim3(NT), 0, s, L, bv, B, (const int *)nullptr, 0);      // beta = B^-1 uvec (k_init)
     if (L.objmode && !L.rev) {      // new objective: the tableau rows are copied up front (the reduced-cost row is rebuilt by k_prep, not streamed from the parent)
@@ -4600,6 +4722,19 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
         P.list_inflight = false; P.pairs_inflight = false;      // (the readbacks above have waited for the stream)
     }
     { int xs[8]; HIP_TRY(hipMemcpy(xs, h->xstat_d, sizeof xs, hipMemcpyDeviceToHost)); for (int k = 0; k < 5; k++) st.ext[k] = xs[k]; for (int k = 0; k < 3; k++) st.p1[k] = xs[5 + k]; }
+    if (objm != BSLV_LP_METHOD_PRIMAL) {      // (every iteration counts in iters[]; the primal ones, pivots and bound switches, in ext[2] as well)
+        int xs[3];
+        HIP_TRY(hipMemcpy(xs, h->xstat_d + 8, sizeof xs, hipMemcpyDeviceToHost));
+        for (int k = 0; k < 3; k++) st.objm[k] = xs[k];
+    }
+    if (cvals && h->obj_call_dual) st.objm[3] = st.pivots - st.ext[2];      // (the polish below, a PRIMAL batch of the same call, counts its dual steps here too)
+    // ... and which of its LPs started on an artificial bound and ended OPTIMAL (bit 1 of `verified` stays through a solve): the polish
+    std::vector<int> polish;
+    if (objm != BSLV_LP_METHOD_PRIMAL) {
+        std::vector<int> ver(B);
+        HIP_TRY(hipMemcpy(ver.data(), h->ver_d, (size_t)B * sizeof(int), hipMemcpyDeviceToHost));
+        for (int b = 0; b < B; b++) if (h->status_h[b] == BSLV_LP_OPTIMAL && (ver[b] & 2)) polish.push_back(b);
+    }
     if ((rc = devex_collect(h, h->dvx)) || (rc = devex_collect(h, h->pdv))) return rc;
     if (pdv) h->pdv_dst.assign(dst, dst + B);
     if (h->profile) {
@@ -4615,6 +4750,33 @@ static int solve_batch_impl(bslv_lpq *h, int B, const int *src, const int *dst, 
     h->park.pre_ev.clear();
     st.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     if (resolve) h->last.add(st); else static_cast<BatchStats &>(h->last) = st;
+    // THE POLISH of a dual start on artificial bounds.  A variable that was put on one and never entered the basis -- a free column
+    // ends with d_j = 0 wherever it stands -- is still there: an optimal point of the LP, 1e7 away on its optimal face, and everything
+    // computed from such values carries 1e7 x 1e-16 x the row length (measured: row residuals of 1e-8 .. 2e-5).  Those LPs are solved
+    // once more in their own slots as the PRIMAL objective batch they would have been, under the engine's own bounds: k_prep takes the
+    // variables back to their natural side, beta is formed anew, and the few steps that follow (0 .. 7 measured) end in a basis of the
+    // LP as given.  Their iterations and counters count with the call.
+    if (!polish.empty()) {
+        L.lb = bounds_back.lb; L.ub = bounds_back.ub; L.art = bounds_back.art;
+        const int m = (int)polish.size(), vc = L.vcnt;
+        std::vector<int> sl(m), st2(m), it2(m);
+        std::vector<double> lo2((size_t)m * std::max(vc, 1)), up2((size_t)m * std::max(vc, 1)), cv2((size_t)m * ccnt);
+        for (int k = 0; k < m; k++) {
+            sl[k] = dst[polish[k]];
+            if (vc > 0) { memcpy(&lo2[(size_t)k * vc], vlo + (size_t)polish[k] * vc, vc * sizeof(double)); memcpy(&up2[(size_t)k * vc], vup + (size_t)polish[k] * vc, vc * sizeof(double)); }
+            memcpy(&cv2[(size_t)k * ccnt], cvals + (size_t)polish[k] * ccnt, ccnt * sizeof(double));
+        }
+        const std::vector<int> marks = h->rmark_h; const bool marks_valid = h->rmark_valid;      // (of THIS batch: the rescue reads them)
+        h->call_obj_method = BSLV_LP_METHOD_PRIMAL;
+        rc = solve_batch_impl(h, m, sl.data(), sl.data(), vc > 0 ? lo2.data() : nullptr, vc > 0 ? up2.data() : nullptr, cfirst, ccnt, cv2.data(), st2.data(), it2.data(), true);
+        h->call_obj_method = objm;
+        h->rmark_h = marks; h->rmark_valid = marks_valid;
+        if (rc) return rc;
+        // (a polish that does not end OPTIMAL -- the basis the dual steps reached was not primal feasible once the variables were back on
+        //  their natural sides, and the primal steps did not mend it -- leaves no certified optimum in the slot: UNDEFINED, never the
+        //  OPTIMAL of before and never the polish's own verdict on an LP the dual steps had found an optimum for)
+        for (int k = 0; k < m; k++) { if (status) status[polish[k]] = st2[k] == BSLV_LP_OPTIMAL ? BSLV_LP_OPTIMAL : BSLV_LP_UNDEFINED; if (iters) iters[polish[k]] += it2[k]; }
+    }
     if (L.probe & 8) {
         unsigned long long dg[16];
         HIP_TRY(hipMemcpy(dg, h->dbg_d, sizeof dg, hipMemcpyDeviceToHost));

@@ -137,23 +137,45 @@ static void sol_normalise(Sol &S, int optdir)
 
 struct Problem { int m, n, q; const double *A, *P; const char *rtype; const double *rlb, *rub; const char *ctype; const double *clb, *cub; };
 
-// one LP in slot 0, in place, with the reference's retry (bslv_lp.c:222-227: undefined -> standard basis -> again)
-static int solve0(bslv_lpq *lp, int p, const double *ub, int *st)
+// THE LP METHOD PER PHASE (flags of bslv_vlp_solve_primal / _dual2, BSLV_VLP_LP_METHOD): of this thread's solve in flight, by the
+// option's phase (0, 1, 2), -1 = not given: the calls as they always were.  g_lpm_stats: LPs handed to a method call, by the
+// reference's phase_type (PHASE0, PHASE1_PRIMAL, PHASE1_DUAL, PHASE2_PRIMAL, PHASE2_DUAL) and method (bslv_vlp_last_lp_method_stats)
+enum { PT_PHASE0 = 0, PT_PHASE1_PRIMAL, PT_PHASE1_DUAL, PT_PHASE2_PRIMAL, PT_PHASE2_DUAL };
+static thread_local int g_lpm[3] = {-1, -1, -1};
+static thread_local long g_lpm_stats[5][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
+static void lpm_decode(int flags)
+{
+    for (int ph = 0; ph < 3; ph++) g_lpm[ph] = ((flags >> (4 + 2 * ph)) & 3) - 1;
+    for (auto &row : g_lpm_stats) for (long &v : row) v = 0;
+}
+// one solve_batch of a phase's own LPs (phase 0's, the feasibility LP of the dual variant) under the method of its phase
+static int solve_m(bslv_lpq *lp, int method, int pt, int n, const int *s, const int *d, const double *lo, const double *up, int *st, int *it)
+{
+    if (method < 0) return bslv_lpq_solve_batch(lp, n, s, d, lo, up, st, it);
+    g_lpm_stats[pt][method] += n;
+    return bslv_lpq_solve_batch_method(lp, method, n, s, d, lo, up, st, it);
+}
+// a Benson engine of a phase: the method goes to the driver; when the phase is over its counts are taken
+static int engine_method(bslv_benson *h, int method) { return method < 0 ? 0 : bslv_benson_set_lp_method(h, method); }
+static void engine_counts(const bslv_benson *h, int pt) { long c[3]; if (bslv_benson_lp_method_stats(h, c) == 0) for (int k = 0; k < 3; k++) g_lpm_stats[pt][k] += c[k]; }
+
+// one LP in slot 0, in place, with the reference's retry (bslv_lp.c:222-227: undefined -> standard basis -> again); the method: phase 0's
+static int solve0(bslv_lpq *lp, int p, const double *ub, int *st, int meth = -1, int pt = PT_PHASE0)
 {
     const int zero = 0;
     std::vector<double> vlo(p, -INFINITY);
     int it, rc;
-    if ((rc = bslv_lpq_solve_batch(lp, 1, &zero, &zero, vlo.data(), ub, st, &it))) return rc;
+    if ((rc = solve_m(lp, meth, pt, 1, &zero, &zero, vlo.data(), ub, st, &it))) return rc;
     if (*st == BSLV_LP_UNDEFINED) {
         if ((rc = bslv_lpq_reset_slot(lp, 0))) return rc;
-        if ((rc = bslv_lpq_solve_batch(lp, 1, &zero, &zero, vlo.data(), ub, st, &it))) return rc;
+        if ((rc = solve_m(lp, meth, pt, 1, &zero, &zero, vlo.data(), ub, st, &it))) return rc;
     }
     if (*st == BSLV_LP_UNDEFINED && !bslv_lpq_get_extended(lp)) {
         // still nothing from the standard basis: a dual simplex stalling in degenerate pivots.  The extended selection (cost
         // perturbation, primal clean-up) from here on, for every LP of this engine
         if ((rc = bslv_lpq_set_extended(lp, 1))) return rc;
         if ((rc = bslv_lpq_reset_slot(lp, 0))) return rc;
-        if ((rc = bslv_lpq_solve_batch(lp, 1, &zero, &zero, vlo.data(), ub, st, &it))) return rc;
+        if ((rc = solve_m(lp, meth, pt, 1, &zero, &zero, vlo.data(), ub, st, &it))) return rc;
     }
     return 0;
 }
@@ -198,7 +220,7 @@ static int phase0(const Problem &pb, Sol &S, double eps_phase0, int *status, lon
     if ((rc = bslv_lpq_reset_slot(lp, 0))) return done(rc);
     std::vector<double> ub(p, 0.0), z(d), wred(d), V((size_t)d * d, 0.0), C((size_t)d * d, 0.0);
     int st;
-    if ((rc = solve0(lp, p, ub.data(), &st))) return done(rc);                                          // :689-698
+    if ((rc = solve0(lp, p, ub.data(), &st, g_lpm[0], PT_PHASE0))) return done(rc);                                          // :689-698
     if (st == BSLV_LP_UNBOUNDED) { const std::vector<double> vlo(p, -INFINITY); report_ray(lp, "phase 0, first LP", st, 0, vlo.data(), ub.data(), 0, 0, nullptr); *status = 2; return done(0); }
     if (st != BSLV_LP_OPTIMAL) { set_error("phase 0: first LP has status %d (the reference asserts optimality, bslv_algs.c:697)", st); return done(BSLV_E_STATE); }
     ++*lps;
@@ -209,7 +231,7 @@ static int phase0(const Problem &pb, Sol &S, double eps_phase0, int *status, lon
             for (int k = 0; k < d; k++) s += S.Z[(size_t)k * p + j] * C[(size_t)k * d + i];
             ub[j] = sign * s;
         }
-        int r2 = solve0(lp, p, ub.data(), &st);
+        int r2 = solve0(lp, p, ub.data(), &st, g_lpm[0], PT_PHASE0);
         if (r2) return r2;
         if (st != BSLV_LP_OPTIMAL) { set_error("phase 0: LP %d has status %d (the reference asserts optimality, bslv_algs.c:712)", i, st); return BSLV_E_STATE; }
         ++*lps;
@@ -265,7 +287,8 @@ static int phase1_primal(const Problem &pb, Sol &S, double eps_phase1, double ep
     int rc = bslv_benson_create_ex(&h, pb.m, pb.n, q, pb.A, pb.P, pb.rtype, pb.rlb, pb.rub, pb.ctype, pb.clb, pb.cub,
                                    S.Z.data(), S.p, S.c.data(), S.eta.data(), 1, 0, eps_benson, std::max(4 * batch + 64, 64));
     if (rc) return rc;
-    auto done = [&](int r) { bslv_benson_destroy(h); return r; };
+    auto done = [&](int r) { engine_counts(h, PT_PHASE1_PRIMAL); bslv_benson_destroy(h); return r; };
+    if ((rc = engine_method(h, g_lpm[1]))) return done(rc);
     int vst = 0;
     if ((rc = bslv_benson_start(h, &vst))) return done(rc);                                             // PART 1 (:829-851)
     if (vst) { set_error("phase 1: an initialisation LP is not optimal (the reference asserts, bslv_algs.c:844)"); return done(BSLV_E_STATE); }
@@ -346,8 +369,13 @@ static int dual_benson(const Problem &pb, const Sol &S, int hom, double eps, int
     const int zero = 0;
     int st, it;
     // a primal feasible basis first (zero objective: every basis is dual feasible, the dual simplex repairs the bounds) ...
+    const int meth = g_lpm[hom ? 1 : 2], pt = hom ? PT_PHASE1_DUAL : PT_PHASE2_DUAL;      // (-L for the homogeneous run of phase 1, -l for phase 2)
+    if (meth >= 0 && meth != BSLV_LP_METHOD_PRIMAL && canonical && !hom) {
+        set_error("bslv_vlp_solve_dual2: an LP method other than primal for phase 2 together with BSLV_VLP_CANONICAL / BSLV_VLP_CANONICAL_CALL: the tie phase of objective batches follows a PRIMAL solve only");
+        return done(BSLV_E_ARG);
+    }
     if ((rc = bslv_lpq_reset_slot(lp, 0))) return done(rc);
-    if ((rc = bslv_lpq_solve_batch(lp, 1, &zero, &zero, nullptr, nullptr, &st, &it))) return done(rc);
+    if ((rc = solve_m(lp, meth, pt, 1, &zero, &zero, nullptr, nullptr, &st, &it))) return done(rc);
     if (st == BSLV_LP_INFEASIBLE) { report_ray(lp, "phase 2 (dual), feasibility LP", st, 0, nullptr, nullptr, 0, 0, nullptr); *status = 1; bslv_poly_destroy(poly); poly = nullptr; return done(0); }
     if (st != BSLV_LP_OPTIMAL) { set_error("phase 2 (dual): the feasibility LP has status %d", st); return done(BSLV_E_STATE); }
     auto count_canonical = [&]() { long cs[4]; if (cstats && bslv_lpq_last_canonical_obj_stats(lp, cs) == 0) for (int k = 0; k < 4; k++) cstats[k] += cs[k]; };
@@ -362,6 +390,8 @@ static int dual_benson(const Problem &pb, const Sol &S, int hom, double eps, int
     // every P1(w) solve below -- PART 1, the batches, their retries: with CANON_CALL the direction goes with the call
     const bool canon_call = (canonical & CANON_CALL) && !hom;
     auto solve_obj = [&](int nb, const int *sv, const int *dv, const double *Wv, int *stat, int *iter) {
+        if (meth >= 0) g_lpm_stats[pt][meth] += nb;
+        if (meth >= 0 && !canon_call) return bslv_lpq_solve_batch_obj_method(lp, meth, nb, sv, dv, nullptr, nullptr, M + n, q, Wv, stat, iter);
         return canon_call ? bslv_lpq_solve_batch_obj_canonical(lp, ddir.data(), nb, sv, dv, nullptr, nullptr, M + n, q, Wv, stat, iter)
                           : bslv_lpq_solve_batch_obj(lp, nb, sv, dv, nullptr, nullptr, M + n, q, Wv, stat, iter);
     };
@@ -676,6 +706,7 @@ int bslv_vlp_solve_primal(int m, int n, int q, const double *A, const double *P,
         return BSLV_E_ARG;
     }
     *engine_out = nullptr;
+    lpm_decode(flags);
     Sol S;
     std::vector<double> Pn;
     long lps = 0, steps = 0;
@@ -686,15 +717,18 @@ int bslv_vlp_solve_primal(int m, int n, int q, const double *A, const double *P,
     bslv_benson *h = nullptr;
     if ((rc = bslv_benson_create_ex(&h, m, n, q, A, Pn.data(), rtype, rlb, rub, ctype, clb, cub, S.R.data(), S.r, S.c.data(), S.eta.data(), 0, (flags & BSLV_VLP_PREIMAGES) ? BSLV_BENSON_PREIMAGES : 0,
                                     eps_benson_phase2, std::max(4 * batch + 64, 64)))) return rc;
+    if ((rc = engine_method(h, g_lpm[2]))) { bslv_benson_destroy(h); return rc; }
     int vst = 0;
     if ((rc = bslv_benson_start(h, &vst))) { bslv_benson_destroy(h); return rc; }
     if (vst) {
+        engine_counts(h, PT_PHASE2_PRIMAL);
         bslv_benson_destroy(h);
         *vlp_status = vst;                                                           // 1 VLP_INFEASIBLE, 2 VLP_UNBOUNDED
         phase2_failure(info, vst, bounded, lps);
         return 0;
     }
     if ((rc = run_engine(h, batch, &lps, &steps))) { bslv_benson_destroy(h); return rc; }
+    engine_counts(h, PT_PHASE2_PRIMAL);
     if (flags & BSLV_VLP_PREIMAGES) {
         Problem pb{m, n, q, A, Pn.data(), rtype, rlb, rub, ctype, clb, cub};
         if ((rc = direction_preimages(pb, S, h, &lps))) { bslv_benson_destroy(h); return rc; }
@@ -720,6 +754,7 @@ int bslv_vlp_solve_dual2(int m, int n, int q, const double *A, const double *P,
         return BSLV_E_ARG;
     }
     *lower_image_out = nullptr;
+    lpm_decode(flags);
     for (int k = 0; k < 4; k++) g_canon_obj[k] = 0;
     if (const char *e = getenv("BSLV_CANONICAL_OBJ")) if (atoi(e) != 0) flags |= BSLV_VLP_CANONICAL;
     if (const char *e = getenv("BSLV_CANONICAL_OBJ_CALL")) if (atoi(e) != 0) flags |= BSLV_VLP_CANONICAL_CALL;
@@ -776,6 +811,12 @@ int bslv_vlp_solve_dual2(int m, int n, int q, const double *A, const double *P,
     return 0;
 }
 
+int bslv_vlp_last_lp_method_stats(long out[5][3])
+{
+    if (!out) return BSLV_E_ARG;
+    for (int p = 0; p < 5; p++) for (int k = 0; k < 3; k++) out[p][k] = g_lpm_stats[p][k];
+    return 0;
+}
 int bslv_vlp_last_canonical_obj_stats(long out[4])
 {
     if (!out) return BSLV_E_ARG;

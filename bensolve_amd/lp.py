@@ -217,6 +217,33 @@ class LpEngine:
                                                 cost_first, costs.shape[1], costs.ctypes.data, status.ctypes.data, iters.ctypes.data))
         return status, iters
 
+    def solve_batch_obj_method(self, method, src, dst, cost_first, costs, vlo=None, vup=None):
+        """solve_batch_obj under a simplex method for this call only (bslv_lpq_solve_batch_obj_method): method 1 (primal) is solve_batch_obj,
+        0 (dual) makes the parent's basis dual feasible for the new objective and runs dual simplex steps, 2 (repair) does so for
+        the LPs where that is possible and starts the others as PRIMAL does.  Both forms; the engine's own method stays what it is."""
+        src = np.ascontiguousarray(src, np.int32)
+        dst = np.ascontiguousarray(dst, np.int32)
+        B = len(src)
+        costs = np.ascontiguousarray(costs, np.float64).reshape(B, -1)
+        vlo = np.ascontiguousarray(np.zeros((B, self.vcnt)) if vlo is None else vlo, np.float64).reshape(B, self.vcnt)
+        vup = np.ascontiguousarray(np.zeros((B, self.vcnt)) if vup is None else vup, np.float64).reshape(B, self.vcnt)
+        status = np.empty(B, np.int32)
+        iters = np.empty(B, np.int32)
+        self.lib.bslv_lpq_solve_batch_obj_method.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 4 + [ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 3
+        self.lib.bslv_lpq_solve_batch_obj_method.restype = ctypes.c_int
+        check(self.lib.bslv_lpq_solve_batch_obj_method(self.h, int(method), B, src.ctypes.data, dst.ctypes.data, vlo.ctypes.data, vup.ctypes.data,
+                                                       int(cost_first), costs.shape[1], costs.ctypes.data, status.ctypes.data, iters.ctypes.data))
+        return status, iters
+
+    def last_obj_method_stats(self):
+        """of the last solve call (bslv_lpq_last_obj_method_stats): LPs that started dual, nonbasic variables moved at the start, LPs
+        REPAIR handed to the primal start, dual pivots"""
+        out = (ctypes.c_long * 4)()
+        self.lib.bslv_lpq_last_obj_method_stats.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        self.lib.bslv_lpq_last_obj_method_stats.restype = ctypes.c_int
+        check(self.lib.bslv_lpq_last_obj_method_stats(self.h, out))
+        return [int(v) for v in out]
+
     def solve_batch_obj_canonical(self, ddir, src, dst, cost_first, costs, vlo=None, vup=None):
         """solve_batch_obj followed by the tie phase towards the canonical optimal point for `ddir` (one value per variable of the cost
         range cost_first .. cost_first + costs.shape[1] - 1), for this call only; the engine's own switch, range and direction stay what

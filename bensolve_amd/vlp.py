@@ -36,9 +36,24 @@ def cone_vertenum(gen):
     return a, b
 
 
+LP_METHODS = {"dual": 0, "primal": 1, "repair": 2}
+
+
+def lp_method_flags(lp_methods):
+    """the flag bits of BSLV_VLP_LP_METHOD(phase, m) for lp_methods = (k, L, l); None or "auto" in a place: nothing given for that phase"""
+    flags = 0
+    for phase, m in enumerate(lp_methods or ()):
+        if m is not None and m != "auto":
+            flags |= (LP_METHODS[m] + 1) << (4 + 2 * phase)
+    return flags
+
+
 def solve_primal(prob, cone_kind=0, gen=None, c=None, bounded=False, eps_phase0=1e-8, eps_phase1=1e-8, eps_benson_phase1=1e-7,
-                 eps_benson_phase2=1e-7, batch=256, alg_phase2="primal", alg_phase1="primal", preimages=False, canonical=False):
-    """prob: dict as bensolve_amd.synth builds them (P as in the file: not negated).  Returns dict(status, message, info...,
+                 eps_benson_phase2=1e-7, batch=256, alg_phase2="primal", alg_phase1="primal", preimages=False, canonical=False, lp_methods=None):
+    """lp_methods = (k, L, l): the simplex method of the LPs of phase 0, 1, 2 -- "dual", "primal", "repair" or None / "auto" = not
+    given, the calls as they always were (BSLV_VLP_LP_METHOD, include/bslv_hip.h); out["lp_method_stats"] = the 5 x 3 counts of
+    bslv_vlp_last_lp_method_stats (phase_type x method).
+    prob: dict as bensolve_amd.synth builds them (P as in the file: not negated).  Returns dict(status, message, info...,
     dump = slot-indexed dump of the result polyhedron with the sign changes of poly_trans_primal applied).  alg_phase2 = "dual":
     phase2_dual; the dump is then given with the sides swapped back, so that X / pi are the upper image in both cases.
     canonical (with alg_phase2 = "dual"): every P1(w) ends in its canonical optimal point (BSLV_VLP_CANONICAL, include/bslv_hip.h);
@@ -67,11 +82,15 @@ def solve_primal(prob, cone_kind=0, gen=None, c=None, bounded=False, eps_phase0=
     check((lib.bslv_vlp_solve_dual2 if dual2 else lib.bslv_vlp_solve_primal)(prob["m"], prob["n"], prob["q"], A.ctypes.data, P.ctypes.data, rt.ctypes.data, arrs[0].ctypes.data, arrs[1].ctypes.data,
                                     ct.ctypes.data, arrs[2].ctypes.data, arrs[3].ctypes.data, int(prob.get("optdir", 1)), cone_kind,
                                     None if g is None else g.ctypes.data, 0 if g is None else g.shape[1], None if cc is None else cc.ctypes.data,
-                                    int(bounded), (1 if alg_phase1 == "dual" else 0) | (2 if preimages else 0) | ((8 if isinstance(canonical, str) and canonical == "call" else 4) if (canonical and dual2) else 0), eps_phase0, eps_phase1, eps_benson_phase1, eps_benson_phase2, batch,
+                                    int(bounded), (1 if alg_phase1 == "dual" else 0) | (2 if preimages else 0) | ((8 if isinstance(canonical, str) and canonical == "call" else 4) if (canonical and dual2) else 0) | lp_method_flags(lp_methods), eps_phase0, eps_phase1, eps_benson_phase1, eps_benson_phase2, batch,
                                     ctypes.byref(h), ctypes.byref(st), ctypes.byref(info)))
     q = prob["q"]
     out = dict(status=STATUS.get(st.value, st.value), message=info.message.decode(), lps=info.lps, steps=info.steps, c_dir=info.c_dir)
 
+    ms = (ctypes.c_long * 15)()
+    lib.bslv_vlp_last_lp_method_stats.argtypes = [vp]
+    check(lib.bslv_vlp_last_lp_method_stats(ms))
+    out["lp_method_stats"] = [[int(ms[3 * p + k]) for k in range(3)] for p in range(5)]
     if dual2:
         cs = (ctypes.c_long * 4)()
         lib.bslv_vlp_last_canonical_obj_stats.argtypes = [vp]

@@ -406,10 +406,12 @@ int  bslv_lpq_get_extended(const bslv_lpq *h);
  *           simplex steps are the ones that conclude a primal clean-up today (rounding left a bound violated).
  *   REPAIR  the dual simplex, except that an LP whose start is dual infeasible is started as under PRIMAL instead of coming back
  *           UNDEFINED (GLP_DUALP: "dual, and primal if it fails").
- * Both imply the extended selection (the primal steps live there).  Objective batches (solve_batch_obj) keep their own start.
+ * Both imply the extended selection (the primal steps live there).  Objective batches (solve_batch_obj) keep their own start -- primal
+ * steps from the parent's basis -- whatever this method is; they take a method per call: bslv_lpq_solve_batch_obj_method, below.
  * Not for the revised form: there a method other than DUAL is BSLV_E_ARG here, and the engine-wide method stays DUAL.  The revised
  * form does have PRIMAL and REPAIR, per call: bslv_lpq_solve_batch_method, in both forms, solves one batch under a method of its own
- * and leaves this one alone.  (Still open: an engine-wide PRIMAL / REPAIR default for the revised form, here and through BSLV_LP_METHOD.)
+ * and leaves this one alone.  (Still open: an engine-wide PRIMAL / REPAIR default for the revised form, here and through BSLV_LP_METHOD.
+ * The callers above the engine carry a method of their own: bslv_benson_set_lp_method.)
  * BSLV_LP_METHOD=dual|primal|repair sets the method an engine is created with (ignored by an engine that comes up in the revised form).
  * bslv_lpq_last_phase1_stats, of the last solve_batch: [0] LPs that entered phase 1, [1] phase-1 iterations (pivots + bound
  * switches), [2] rebuilds of the phase-1 pricing vector from the tableau rows (it is otherwise updated with every pivot). */
@@ -564,6 +566,57 @@ int  bslv_lpq_last_canonical_obj_stats(const bslv_lpq *h, long out[4]);
 int  bslv_lpq_solve_batch_obj_canonical(bslv_lpq *h, const double *ddir /* cost_cnt */, int B, const int *src, const int *dst,
                                         const double *vlo, const double *vup, int cost_first, int cost_cnt, const double *costs,
                                         int *status, int *iters);
+/* AN OBJECTIVE BATCH UNDER A METHOD, per call and in both forms (the reference runs the P1(w) LPs of -a dual / -A dual under whatever
+ * -l / -L asks for: lp_set_options, bslv_lp.c:153-217).  The engine's own method (bslv_lpq_set_method) is neither read nor changed.
+ *   PRIMAL  bslv_lpq_solve_batch_obj, bit for bit: statuses, iters, slots, getters and every last_* record.
+ *   DUAL    the basis of src[b] is made dual feasible for the NEW objective and the LP runs dual simplex steps.  The new reduced-cost
+ *           row d is built as for solve_batch_obj (tableau form: k_prep's sum over the parent's tableau rows; revised form: k_rev_price,
+ *           one tableau row of y = sum c_t rho_t -- the dense row stays on the device).  Every nonbasic variable then takes the side d_j
+ *           wants where it has a bound there: the lower one for d_j > 1e-9, the upper one for d_j < -1e-9; otherwise it keeps the side
+ *           solve_batch_obj gives it (the parent's, sanitised against the bounds).  This is the rule of a DUAL solve_batch fed the new
+ *           d_j.  beta is formed from the nonbasic values so chosen, by the kernels that form it in every solve (k_init; revised form:
+ *           k_rev_u, k_init); the order of the start is k_prep, (revised form: k_rev_price,) k_obj_art, k_obj_start, (k_rev_u,) k_init
+ *           in both forms: in the revised form the row exists only after k_prep.
+ *           The LP then runs the selection of a DUAL solve_batch with the extended selection on (an objective batch always has it) --
+ *           bound flipping, cost perturbation, primal clean-up, Bland fallback as there -- under the dual Devex instance where
+ *           bslv_lpq_set_pricing is DEVEX; the primal Devex switch does not reach a DUAL call.
+ *           ARTIFICIAL BOUNDS.  An engine that solves objective batches has a zero cost vector and so no artificial bounds of its own.
+ *           The call makes its own by the engine's rule, applied to the reduced costs it starts from (oracle/lp_dense.c olp_solve, the
+ *           "artificial-bounds start of the dual simplex"): a nonbasic variable outside the per-LP range whose d_j in SOME LP of the
+ *           batch points where it has no bound (d_j > 1e-9 without a lower, d_j < -1e-9 without an upper bound) has -+1e7 there for
+ *           every LP of the batch, for this call only.  They count as bounds exactly as the engine's own do in solve_batch: a variable
+ *           starts on one where its d_j wants it, and an LP that ends with a non-zero reduced cost on one comes back BSLV_LP_UNBOUNDED
+ *           -- it is unbounded in the direction the PRIMAL path reports as a ray; with bslv_lpq_set_rays this conclusion stores NO ray
+ *           (kind NONE, counted in last_ray_stats[2]), as for solve_batch: re-solve under PRIMAL for the DIRECTION.  THE POLISH: a variable put on an
+ *           artificial bound that never enters the basis -- a free column ends with d_j = 0 wherever it stands -- would stay 1e7 away
+ *           on the optimal face, and values of that size leave 1e-8 .. 1e-5 in the rows.  So every LP that started on an artificial
+ *           bound and ended OPTIMAL is solved once more in its own slot as the PRIMAL objective batch it would have been, under the
+ *           engine's own bounds, inside the same call (0 .. 7 iterations measured): what comes back is a basis and a point of the LP as
+ *           given.  These iterations count in iters[] and in every last_* record of the call.  Nothing guarantees that the
+ *           basis the dual steps reached is primal feasible once the variables are back on their natural sides; the primal steps mend
+ *           what rounding left, and a polish that does not end OPTIMAL makes the LP BSLV_LP_UNDEFINED (never OPTIMAL, never the
+ *           polish's own verdict).  The artificial bounds are the BATCH's, not the LP's: a variable one
+ *           LP needs bounded is bounded at -+1e7 for every LP of the call.  An LP that does not need it never STARTS on it (no natural
+ *           side is an artificial bound), but it sees the variable as bounded -- in the ratio tests, and a basic variable could in
+ *           principle leave towards it -- so what an LP computes may depend on the other LPs of its batch; only a PRIMAL call keeps
+ *           "an LP of a batch is that LP alone" bit for bit.
+ *           An LP with a nonbasic variable that no side makes dual feasible -- a variable of the per-LP range (its bounds come per LP,
+ *           it gets no artificial one) that is free with |d_j| > 1e-7 or bounded on the wrong side only -- comes back BSLV_LP_UNDEFINED
+ *           with 0 iterations and leaves slot dst[b] unusable, as a solve_batch with a dual infeasible start does.
+ *   REPAIR  DUAL, except that an LP whose start cannot be made dual feasible takes the start of PRIMAL instead of coming back UNDEFINED
+ *           (primal steps from the parent's basis, which must be primal feasible as for solve_batch_obj).  Decided per LP, inside one
+ *           call.  Pricing: the dual Devex instance where that switch is on, else the primal Devex instance where that one is.
+ * method outside 0..2 or h == NULL: BSLV_E_ARG, nothing changed; whatever solve_batch_obj refuses stays refused with its own code.  The
+ * in-call rescue (bslv_lpq_set_refactor) re-solves under the call's method.  The tie phase of objective batches follows a PRIMAL solve
+ * only: with bslv_lpq_set_canonical_obj on, DUAL and REPAIR are BSLV_E_ARG; bslv_lpq_solve_batch_obj_canonical keeps its signature and
+ * its PRIMAL solve.
+ * bslv_lpq_last_obj_method_stats, of the last solve call: [0] LPs that started dual, [1] nonbasic variables moved off the side
+ * solve_batch_obj would have given them at the start, [2] LPs REPAIR handed to the primal start, [3] dual pivots (all iterations less
+ * the primal ones).  All zero after any other call and after a PRIMAL one. */
+int  bslv_lpq_solve_batch_obj_method(bslv_lpq *h, int method, int B, const int *src, const int *dst,
+                                     const double *vlo, const double *vup,
+                                     int cost_first, int cost_cnt, const double *costs, int *status, int *iters);
+int  bslv_lpq_last_obj_method_stats(const bslv_lpq *h, long out[4]);
 
 /* ------------------------------------------------------------------------------------------
  * 2. Polyhedron engine  (replaces bslv_poly.h:90-118)
@@ -812,6 +865,18 @@ int  bslv_benson_unprocessed_left(const bslv_benson *h);
 int  bslv_benson_set_canonical(bslv_benson *h, int on);
 int  bslv_benson_get_canonical(const bslv_benson *h);
 int  bslv_benson_canonical_stats(const bslv_benson *h, long last[4], long total[4]);
+/* THE SIMPLEX METHOD of the driver's LPs (the reference: lp_set_options per phase, -k / -L / -l).  method = BSLV_LP_METHOD_DUAL /
+ * _PRIMAL / _REPAIR, or -1 = unset, the default: the calls as they always were, bit for bit (the LP engine's own method).  Set, the
+ * weighted-sum LPs of the start, every P2(v) batch of bslv_benson_solve_local (and its _ctx twin) and every stage of its retry -- from
+ * the root tableau, from the standard basis, with the extended selection -- go through bslv_lpq_solve_batch_method, in both forms of
+ * the LP engine.  With bslv_benson_set_canonical on, the tableau form keeps its tie phase (the engine's switch holds under every method
+ * of a call); a revised engine, whose tie phase is bslv_lpq_solve_batch_canonical under the engine's own method, accepts DUAL and answers
+ * BSLV_E_ARG to PRIMAL and REPAIR from solve_local, with a message that names both.  BSLV_BENSON_LP_METHOD=dual|primal|repair sets it
+ * when an engine is created.  Anything else: BSLV_E_ARG.  bslv_benson_lp_method_stats: LPs handed to such calls so far under DUAL,
+ * PRIMAL, REPAIR (retries count again; all 0 while unset). */
+int  bslv_benson_set_lp_method(bslv_benson *h, int method);
+int  bslv_benson_get_lp_method(const bslv_benson *h);
+int  bslv_benson_lp_method_stats(const bslv_benson *h, long out[3]);
 /* LP CERTIFICATE: with on != 0 bslv_benson_solve_local and its _ctx twin certify the LPs of the batch that ended BSLV_LP_OPTIMAL with
  * bslv_lpq_certify, after the retries and before the getters, with the slots and bounds of the solve.  The first LP that is not certified
  * is printed on stderr (batch number, slot, the five residuals and where they were met), a summary line when the engine is destroyed;
@@ -939,6 +1004,21 @@ typedef struct bslv_vlp_info {
  * of the LP engine: the way to the canonical points on an engine in the revised form.  The engine's switch stays off.  Neither flag
  * is a default. */
 enum { BSLV_VLP_PHASE1_DUAL = 1, BSLV_VLP_PREIMAGES = 2, BSLV_VLP_CANONICAL = 4, BSLV_VLP_CANONICAL_CALL = 8 };
+/* THE LP METHOD PER PHASE (the reference: -k / -L / -l, lp_set_options per phase_type).  Two bits per phase above the four flags:
+ * BSLV_VLP_LP_METHOD(phase, m) with phase 0, 1, 2 and m = BSLV_LP_METHOD_DUAL / _PRIMAL / _REPAIR; nothing given for a phase = "auto"
+ * = the calls as they always were, NOT the reference's default of that phase (making phase 0 primal because the reference does would
+ * change every existing run).  A given method reaches: phase 0's LPs (bslv_lpq_solve_batch_method, their retry from the standard basis
+ * included); the homogeneous Benson engine of phase 1 (bslv_benson_set_lp_method) or, with PHASE1_DUAL, the feasibility LP and the
+ * objective batches of the homogeneous dual variant (bslv_lpq_solve_batch_obj_method); in phase 2 the Benson engine of
+ * bslv_vlp_solve_primal or the feasibility LP and the P1(w) batches of bslv_vlp_solve_dual2, PART 1 and retries included.  The LPs of the
+ * pre-images of directions (PREIMAGES) take none.  bslv_vlp_solve_dual2 with CANONICAL or CANONICAL_CALL and a phase-2 method other
+ * than primal: BSLV_E_ARG (the tie phase of objective batches follows a PRIMAL solve only).
+ * bslv_vlp_last_lp_method_stats, of the calling thread's last solve: out[phase_type][method] = LPs handed to a call under that
+ * method, phase_type as the reference's enum (PHASE0, PHASE1_PRIMAL, PHASE1_DUAL, PHASE2_PRIMAL, PHASE2_DUAL); retries count again;
+ * all 0 where no method was given. */
+#define BSLV_VLP_LP_METHOD(phase, m) (((m) + 1) << (4 + 2 * (phase)))
+#define BSLV_VLP_LP_METHOD_OF(flags, phase) ((((flags) >> (4 + 2 * (phase))) & 3) - 1)      /* -1: not given */
+int  bslv_vlp_last_lp_method_stats(long out[5][3]);
 /* cone_kind 0 default (R^q_+), 1 `gen` generates C, 2 `gen` generates C* (vlp->cone_gen); c_in: q or NULL (vlp->c).
  * vlp_status (sol->status, bslv_main.h:103): 1 infeasible, 2 unbounded, 3 no vertex, 4 optimal, 5 input error.
  * With status 4 *engine_out is the finished phase-2 engine (bslv_benson_poly(engine) is the result; destroy it). */

@@ -33,6 +33,12 @@ struct lp_opt { lp_method_type method_phase0, method_phase1, method_phase2; int 
 
 void lp_init(int rows, int cols, int nnz, lp_idx *row_idx, lp_idx *col_idx, double *data);    /* bslv_lp.c:60 */
 void lp_set_options(const struct lp_opt *opt, phase_type phase);                               /* :153 */
+/* lp_set_options records the method of the phase with the reference's mapping (PRIMAL_SIMPLEX / DUAL_SIMPLEX / DUAL_PRIMAL_SIMPLEX ->
+ * BSLV_LP_METHOD_PRIMAL / _DUAL / _REPAIR, LP_METHOD_AUTO -> the phase's own: dual for the primal Benson phases, primal for the dual
+ * ones, phase 0 keeps what was set before).  lp_solve uses it -- bslv_lpq_solve_batch_method, the retry from the standard basis
+ * included -- only with BSLV_LP_METHOD_OPTIONS=1 in the environment; without it nothing changes.  bslv_lp_compat_method is the
+ * mapping alone (prev: the method in force before the call; -1: a phase or method outside the enums). */
+int bslv_lp_compat_method(const struct lp_opt *opt, phase_type phase, int prev);
 void lp_update_extra_coeffs(lp_idx n_rows, lp_idx n_cols);                                     /* :73 */
 void lp_set_rows(size_t i, boundlist const *rows);                                             /* :112 */
 void lp_set_rows_hom(size_t i, boundlist const *rows);                                         /* :118 */
