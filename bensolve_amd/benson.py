@@ -168,6 +168,19 @@ class BensonEngine:
         self.lib.bslv_benson_get_lp_method.argtypes = [ctypes.c_void_p]
         return int(self.lib.bslv_benson_get_lp_method(self.h))
 
+    def set_lp_pricing(self, dual_rule, primal_rule):
+        """the pricing rules (0 dantzig, 1 devex; -1, -1 = unset) of the LP calls the driver makes under its method
+        (bslv_benson_set_lp_pricing, include/bslv_hip.h).  Returns the library's code."""
+        self.lib.bslv_benson_set_lp_pricing.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]
+        return int(self.lib.bslv_benson_set_lp_pricing(self.h, int(dual_rule), int(primal_rule)))
+
+    def get_lp_pricing(self):
+        """(dual_rule, primal_rule) as set, (-1, -1) while unset (bslv_benson_get_lp_pricing)"""
+        d, p = ctypes.c_int(-1), ctypes.c_int(-1)
+        self.lib.bslv_benson_get_lp_pricing.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        check(self.lib.bslv_benson_get_lp_pricing(self.h, ctypes.byref(d), ctypes.byref(p)))
+        return int(d.value), int(p.value)
+
     def lp_method_stats(self):
         """LPs solved so far under DUAL, PRIMAL, REPAIR by the driver's method calls (bslv_benson_lp_method_stats)"""
         out = (ctypes.c_long * 3)()

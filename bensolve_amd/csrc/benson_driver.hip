@@ -37,6 +37,8 @@ struct bslv_benson {
     // batch and both stages of its retry go through bslv_lpq_solve_batch_method.  lp_method_lps: LPs solved so far under DUAL / PRIMAL /
     // REPAIR by such calls (bslv_benson_lp_method_stats)
     int lp_method = -1;
+    // bslv_benson_set_lp_pricing: -1 / -1 = unset; else, while lp_method is set, those calls are bslv_lpq_solve_batch_method_priced under these rules
+    int lp_dual_rule = -1, lp_primal_rule = -1;
     long lp_method_lps[3] = {0, 0, 0};
     long tot_root_starts = 0, tot_nearest_starts = 0; // LPs whose parent's tableau was not resident here: started from the root tableau / from the nearest resident one
     bool nearest_start = true;
@@ -281,6 +283,13 @@ int bslv_benson_create_ex(bslv_benson **out, int m, int n, int q, const double *
         const int m = !strcmp(e, "dual") ? BSLV_LP_METHOD_DUAL : !strcmp(e, "primal") ? BSLV_LP_METHOD_PRIMAL : !strcmp(e, "repair") ? BSLV_LP_METHOD_REPAIR : -1;
         if (m >= 0) h->lp_method = m;
     }
+    // BSLV_BENSON_LP_PRICING=<dantzig|devex>[:<dantzig|devex>]: bslv_benson_set_lp_pricing, dual[:primal] (the primal rule defaults to dantzig)
+    if (const char *e = getenv("BSLV_BENSON_LP_PRICING")) {
+        const auto rule = [](const char *p, size_t n) { return (n == 7 && !strncmp(p, "dantzig", 7)) ? BSLV_LP_PRICING_DANTZIG : (n == 5 && !strncmp(p, "devex", 5)) ? BSLV_LP_PRICING_DEVEX : -1; };
+        const char *c = strchr(e, ':');
+        const int dr = rule(e, c ? (size_t)(c - e) : strlen(e)), pr = c ? rule(c + 1, strlen(c + 1)) : BSLV_LP_PRICING_DANTZIG;
+        if (dr >= 0 && pr >= 0) { h->lp_dual_rule = dr; h->lp_primal_rule = pr; }
+    }
     *out = h;
     return 0;
 }
@@ -308,6 +317,21 @@ int bslv_benson_set_lp_method(bslv_benson *h, int method)
     return 0;
 }
 int bslv_benson_get_lp_method(const bslv_benson *h) { return h ? h->lp_method : -1; }
+// The pricing rules of those calls: see bslv_hip.h (bslv_lpq_solve_batch_method_priced; the LP engine's own switches stay what they are)
+int bslv_benson_set_lp_pricing(bslv_benson *h, int dual_rule, int primal_rule)
+{
+    const auto ok = [](int r) { return r == BSLV_LP_PRICING_DANTZIG || r == BSLV_LP_PRICING_DEVEX; };
+    if (!h || !((dual_rule == -1 && primal_rule == -1) || (ok(dual_rule) && ok(primal_rule)))) { set_error("bslv_benson_set_lp_pricing: bad argument (dual rule %d, primal rule %d)", dual_rule, primal_rule); return BSLV_E_ARG; }
+    h->lp_dual_rule = dual_rule; h->lp_primal_rule = primal_rule;
+    return 0;
+}
+int bslv_benson_get_lp_pricing(const bslv_benson *h, int *dual_rule, int *primal_rule)
+{
+    if (!h) return BSLV_E_ARG;
+    if (dual_rule) *dual_rule = h->lp_dual_rule;
+    if (primal_rule) *primal_rule = h->lp_primal_rule;
+    return 0;
+}
 int bslv_benson_lp_method_stats(const bslv_benson *h, long out[3])
 {
     if (!h || !out) return BSLV_E_ARG;
@@ -318,6 +342,7 @@ static int solve_under_method(bslv_benson *h, int n, const int *s, const int *d,
 {
     if (h->lp_method < 0) return bslv_lpq_solve_batch(h->lp, n, s, d, lo, up, stat, iter);
     h->lp_method_lps[h->lp_method] += n;
+    if (h->lp_dual_rule >= 0) return bslv_lpq_solve_batch_method_priced(h->lp, h->lp_method, h->lp_dual_rule, h->lp_primal_rule, n, s, d, lo, up, stat, iter);
     return bslv_lpq_solve_batch_method(h->lp, h->lp_method, n, s, d, lo, up, stat, iter);
 }
 // The LP certificate of every solve_local (bslv_lpq_certify): see bslv_hip.h.  The P1(w) batches of the dual variant (vlp_phases.hip) do

@@ -1481,14 +1481,15 @@ struct SelSharedDvx : SelShared { int rv[3 + REV_HQ + 1]; };      // rv: request
 // phase 2 share them.  A dual pivot of the LP here, a refactorisation replay on the host side, start a new framework (all t_j = 1); bound
 // switches change nothing.  Instances of their own again (k_select_priced<RULE_PDV, ..>), which take the LDS of the DVX ones; no
 // instance carries both rules.
-// P1R (with P1 and the default rule): phase 1 in the revised form (bslv_lpq_solve_batch_method; k_select_p1_rev).  P1 alone stays the tableau
-// form's instance, with the revised form's code left out (TAB below).
+// P1R (with P1): phase 1 in the revised form (bslv_lpq_solve_batch_method; k_select_p1_rev) -- and, with DVX or PDV, under the rule of one
+// call (bslv_lpq_solve_batch_method_priced; k_select_priced_p1_rev<RULE>).  P1 alone stays the tableau form's instance, with the revised
+// form's code left out (TAB below).
 template <bool EXT, bool P1 = false, bool DVX = false, bool PDV = false, bool P1R = false>
 __device__ __forceinline__ bool select_once(const LpView &L, const BatchView &Bv, const int b, const int cap2, SelShared *xs = nullptr, const NormView *nv = nullptr)
 {
     static_assert(EXT || !P1, "phase 1 lives in the extended selection");
     static_assert(!(DVX && PDV) && (EXT || !PDV), "one rule per instance; primal steps live in the extended selection");
-    static_assert(!P1R || (P1 && !DVX && !PDV), "the revised form's phase 1 is an instance of the default rule");
+    static_assert(!P1R || P1, "the revised form's phase 1 is a phase-1 instance, under at most one rule (above)");
     constexpr bool XS = P1 || DVX || PDV;     // the LDS comes from the kernel
     constexpr bool TAB = P1 && !P1R;          // an instance that never sees the revised form
     double *sv; int *si; PivDesc *p_d; unsigned char *dyn;
@@ -2034,6 +2035,39 @@ __global__ __launch_bounds__(NT_BIG) void k_select_priced(LpView L, BatchView Bv
         if (!(EXT ? select_once_priced<RULE, P1>(L, Bv, b, cap2, &xs, &Nv) : select_once<false, false, true>(L, Bv, b, cap2, &xs, &Nv))) break;
     }
     if constexpr (!P1) if (L.helpers > 1) {
+        __syncthreads();
+        if (threadIdx.x == 0) __hip_atomic_store(&Bv.hmail[(size_t)b * 8], (L.launch_id << 8) | 0xFF, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+#pragma clang diagnostic pop
+
+// k_select_p1_rev under Devex pricing: what a PRIMAL or REPAIR call of bslv_lpq_solve_batch_method_priced launches in the revised form
+// (select_once<true, true, DVX, PDV, true>; the rule of the CALL -- the engine's two switches do not reach such a batch).  Rows, columns
+// and the phase-1 pricing vector as in k_select_p1_rev, helper workgroups included; under RULE_PDV the norms follow a primal pivot in one
+// more pass over the pivot row rev_row_of_rho has just completed (the helpers' slices are in: fetch_row ends behind its barrier), and
+// phase 1 weights its own pricing vector by them; under RULE_DVX they follow a dual pivot with the multipliers of Phase D.  Kernels of
+// their own again, LDS declared here and handed down, the dynamic LDS under a name per instance (see k_select_priced).
+template <int RULE>
+__device__ __noinline__ bool select_once_priced_p1_rev(const LpView &L, const BatchView &Bv, const int b, const int cap2, SelShared *xs, const NormView *nv) { return select_once<true, true, RULE == RULE_DVX, RULE == RULE_PDV, true>(L, Bv, b, cap2, xs, nv); }
+template <int RULE> extern __shared__ unsigned char dyn_priced_p1_rev[];
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wundefined-var-template"      // (dynamic LDS has no definition)
+template <int RULE>
+__global__ __launch_bounds__(NT_BIG) void k_select_priced_p1_rev(LpView L, BatchView Bv, NormView Nv, const int *active, int nact, int cap2, int nsel)
+{
+    static_assert(RULE == RULE_DVX || RULE == RULE_PDV, "the two instances: one rule each");
+    __shared__ SelSharedDvx xs;
+    unsigned char *const dyn = dyn_priced_p1_rev<RULE>;
+    if ((int)blockIdx.x >= nact) return;
+    const int b = active[blockIdx.x];
+    if (blockIdx.y > 0) { rev_helper<true>(L, Bv, b, xs.rv, dyn); return; }
+    if (threadIdx.x == 0) xs.dyn = dyn;
+    __syncthreads();
+    for (int sdx = 0; sdx < nsel; sdx++) {
+        if (sdx) __syncthreads();
+        if (!select_once_priced_p1_rev<RULE>(L, Bv, b, cap2, &xs, &Nv)) break;
+    }
+    if (L.helpers > 1) {                       // every path of the LP's own workgroup ends here: the helpers may go
         __syncthreads();
         if (threadIdx.x == 0) __hip_atomic_store(&Bv.hmail[(size_t)b * 8], (L.launch_id << 8) | 0xFF, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
     }
@@ -3143,6 +3177,7 @@ struct bslv_lpq {
     double *clb_d = nullptr, *cub_d = nullptr; unsigned char *cart_d = nullptr;
     CallStats last;                    // the counters of the last solve call (bslv_lpq_last_stats and the getters beside it)
     int method = BSLV_LP_METHOD_DUAL;  // bslv_lpq_set_method (BSLV_LP_METHOD at create)
+    bool call_priced = false;               // the solve call in flight is bslv_lpq_solve_batch_method_priced: pricing / ppricing hold ITS rules until it returns
     int call_method = BSLV_LP_METHOD_DUAL;  // the method of the solve call in flight: `method`, or what bslv_lpq_solve_batch_method was given (the rescue's re-solves included)
     // dual Devex pricing (bslv_lpq_set_pricing, BSLV_LP_PRICING at create) and primal Devex pricing (bslv_lpq_set_primal_pricing,
     // BSLV_LP_PRIMAL_PRICING at create): the rule and what the engine keeps for it (DevexNorms); pdv_dst: the slots of the LPs of the
@@ -3877,7 +3912,8 @@ struct SelectPlan {
 };
 // The selection kernels by rule (0: the default one, RULE_DVX, RULE_PDV) and shape; bslv_lpq::select_lds_max has the same indices
 // k_select<false>; the extended selection k_select<true>; ... with phase 1 in its primal steps, the PRIMAL and REPAIR methods: k_select_p1
-// in the tableau form, k_select_p1_rev in the revised form (the default rule only: plan_select gives such a batch no other)
+// in the tableau form, k_select_p1_rev in the revised form (k_select_priced_p1_rev<RULE> under the rule of a call: plan_select gives such a
+// batch no other rule than the one bslv_lpq_solve_batch_method_priced came with)
 // (SHAPE_TIE_REV, SHAPE_TIE_OBJ_REV: k_select_tie_rev and k_select_tie_obj_rev, the tie phases of the revised form -- no selections
 // of a plan, listed here for their LDS limits)
 enum { SHAPE_PLAIN, SHAPE_EXT, SHAPE_P1, SHAPE_P1_REV, SHAPE_TIE_REV, SHAPE_TIE_OBJ_REV };
@@ -3885,8 +3921,8 @@ static const void *select_kernel(int rule, int shape)
 {
     static const void *const k[3][6] = {
         {(const void *)k_select<false>, (const void *)k_select<true>, (const void *)k_select_p1, (const void *)k_select_p1_rev, (const void *)k_select_tie_rev, (const void *)k_select_tie_obj_rev},
-        {(const void *)k_select_priced<RULE_DVX, false, false>, (const void *)k_select_priced<RULE_DVX, false, true>, (const void *)k_select_priced<RULE_DVX, true, true>, nullptr, nullptr, nullptr},
-        {nullptr, (const void *)k_select_priced<RULE_PDV, false, true>, (const void *)k_select_priced<RULE_PDV, true, true>, nullptr, nullptr, nullptr}};      // (primal steps live in the extended selection: without one the batch is refused, plan_select)
+        {(const void *)k_select_priced<RULE_DVX, false, false>, (const void *)k_select_priced<RULE_DVX, false, true>, (const void *)k_select_priced<RULE_DVX, true, true>, (const void *)k_select_priced_p1_rev<RULE_DVX>, nullptr, nullptr},
+        {nullptr, (const void *)k_select_priced<RULE_PDV, false, true>, (const void *)k_select_priced<RULE_PDV, true, true>, (const void *)k_select_priced_p1_rev<RULE_PDV>, nullptr, nullptr}};      // (primal steps live in the extended selection: without one the batch is refused, plan_select)
     return k[rule][shape];
 }
 // the kernel of (rule, shape) may be launched with `want` bytes of dynamic LDS, its limit raised if need be
@@ -3908,14 +3944,16 @@ static bool pdv_batch(const bslv_lpq *h)
     // (an objective batch under a method, bslv_lpq_solve_batch_obj_method: PRIMAL is the objective batch it always was; DUAL makes dual
     //  steps, its clean-up steps stay as they are; REPAIR is a PRIMAL / REPAIR batch: the primal rule unless the dual one is on)
     if (L.objmode) return h->call_obj_method == BSLV_LP_METHOD_PRIMAL || (h->call_obj_method == BSLV_LP_METHOD_REPAIR && h->pricing != BSLV_LP_PRICING_DEVEX);
-    return h->call_method != BSLV_LP_METHOD_DUAL && !L.rev && h->pricing != BSLV_LP_PRICING_DEVEX;
+    return h->call_method != BSLV_LP_METHOD_DUAL && (!L.rev || h->call_priced) && h->pricing != BSLV_LP_PRICING_DEVEX;
 }
 // A PRIMAL / REPAIR batch of the revised form (bslv_lpq_solve_batch_method): k_select_p1_rev, the instance of the default rule, whatever
-// the two pricing switches say -- neither Devex rule has an instance for the revised form's phase 1, and both counter triples read 0
+// the ENGINE's two pricing switches say, and both counter triples read 0.  The Devex instances of the revised form's phase 1
+// (k_select_priced_p1_rev) are reached per call only: under bslv_lpq_solve_batch_method_priced `pricing` and `ppricing` hold the rules
+// of the call (call_priced), and the mapping is the tableau form's.
 static bool rev_p1_batch(const bslv_lpq *h) { return h->L.rev && !h->L.objmode && h->call_method != BSLV_LP_METHOD_DUAL; }
 // ... and the batches under dual Devex pricing (objective batches make primal steps only: they keep the kernels they had -- unless the
 // call gave them the method DUAL or REPAIR, bslv_lpq_solve_batch_obj_method: then their steps are a DUAL solve_batch's)
-static bool dvx_batch(const bslv_lpq *h) { return h->pricing == BSLV_LP_PRICING_DEVEX && (!h->L.objmode || h->call_obj_method != BSLV_LP_METHOD_PRIMAL) && !rev_p1_batch(h); }
+static bool dvx_batch(const bslv_lpq *h) { return h->pricing == BSLV_LP_PRICING_DEVEX && (!h->L.objmode || h->call_obj_method != BSLV_LP_METHOD_PRIMAL) && (!rev_p1_batch(h) || h->call_priced); }
 static int plan_select(bslv_lpq *h, int B, const double *vlo, const double *vup, SelectPlan *plan)
 {
     LpView &L = h->L;
@@ -4323,6 +4361,24 @@ int bslv_lpq_solve_batch_method(bslv_lpq *h, int method, int B, const int *src, 
     if (!h || method < BSLV_LP_METHOD_DUAL || method > BSLV_LP_METHOD_REPAIR) { set_error("bslv_lpq_solve_batch_method: bad argument (method %d)", method); return BSLV_E_ARG; }
     h->call_method = method;
     return solve_batch_rescue(h, B, src, dst, vlo, vup, 0, 0, nullptr, status, iters);
+}
+// ... under `method` AND the two pricing rules of this call only: see bslv_hip.h.  The engine's method and switches are what they were
+// when the call returns; while it runs `pricing` / `ppricing` hold the call's rules, so every batch of the call -- the rescue's re-solves
+// included -- is planned under them (dvx_batch, pdv_batch), and call_priced lets them reach a PRIMAL / REPAIR batch of the revised form.
+int bslv_lpq_solve_batch_method_priced(bslv_lpq *h, int method, int dual_rule, int primal_rule, int B, const int *src, const int *dst,
+                                       const double *vlo, const double *vup, int *status, int *iters)
+{
+    const auto rule_ok = [](int r) { return r == BSLV_LP_PRICING_DANTZIG || r == BSLV_LP_PRICING_DEVEX; };
+    if (!h || method < BSLV_LP_METHOD_DUAL || method > BSLV_LP_METHOD_REPAIR || !rule_ok(dual_rule) || !rule_ok(primal_rule)) {
+        set_error("bslv_lpq_solve_batch_method_priced: bad argument (method %d, dual rule %d, primal rule %d)", method, dual_rule, primal_rule);
+        return BSLV_E_ARG;
+    }
+    const int pricing0 = h->pricing, ppricing0 = h->ppricing;
+    h->pricing = dual_rule; h->ppricing = primal_rule; h->call_priced = true;
+    h->call_method = method;
+    const int rc = solve_batch_rescue(h, B, src, dst, vlo, vup, 0, 0, nullptr, status, iters);
+    h->pricing = pricing0; h->ppricing = ppricing0; h->call_priced = false;
+    return rc;
 }
 // The LPs of the batch differ in their OBJECTIVE (lp_set_obj_coeffs + lp_solve, bslv_lp.c:141-151,219: what phase2_dual
 // does per vertex, bslv_algs.c:1469-1477): cost costs[b*cost_cnt + t] on variable cost_first + t, 0 elsewhere (the engine's

@@ -184,6 +184,24 @@ class LpEngine:
                                                    vup.ctypes.data, status.ctypes.data, iters.ctypes.data))
         return status, iters
 
+    def solve_batch_method_priced(self, method, dual_rule, primal_rule, src, dst, vlo, vup):
+        """solve_batch under `method` (0 dual, 1 primal, 2 repair), the dual pricing rule `dual_rule` and the primal pricing rule
+        `primal_rule` (0 dantzig, 1 devex) for this call only; the engine's method and its two pricing switches stay what they are.  In
+        the revised form the only way to Devex pricing for a PRIMAL / REPAIR batch (bslv_lpq_solve_batch_method_priced)."""
+        src = np.ascontiguousarray(src, np.int32)
+        dst = np.ascontiguousarray(dst, np.int32)
+        B = len(src)
+        vlo = np.ascontiguousarray(vlo, np.float64).reshape(B, self.vcnt)
+        vup = np.ascontiguousarray(vup, np.float64).reshape(B, self.vcnt)
+        status = np.empty(B, np.int32)
+        iters = np.empty(B, np.int32)
+        self.lib.bslv_lpq_solve_batch_method_priced.argtypes = [ctypes.c_void_p] + [ctypes.c_int] * 4 + [ctypes.c_void_p] * 6
+        self.lib.bslv_lpq_solve_batch_method_priced.restype = ctypes.c_int
+        check(self.lib.bslv_lpq_solve_batch_method_priced(self.h, int(method), int(dual_rule), int(primal_rule), B, src.ctypes.data,
+                                                          dst.ctypes.data, vlo.ctypes.data, vup.ctypes.data, status.ctypes.data,
+                                                          iters.ctypes.data))
+        return status, iters
+
     def solve_batch_canonical(self, dir, src, dst, vlo, vup):
         """solve_batch followed by the tie phase towards the canonical optimal basis for `dir` (var_cnt values), for this call only; the
         engine's own switch and direction stay what they are.  Works in both forms; in the revised form the only way to the tie phase

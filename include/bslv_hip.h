@@ -246,12 +246,32 @@ int  bslv_lpq_solve_batch(bslv_lpq *h, int B, const int *src, const int *dst,
  *                 there: set_method and BSLV_LP_METHOD stay what they were.  The phase-1 pricing vector of a slot that holds B^-1 is the
  *                 tableau row of a synthesised rho, y1 = sum of +-(row i of B^-1) over the infeasible rows, rebuilt when the tableau
  *                 form rebuilds its own (last_phase1_stats[2]) and after a periodic refactorisation of an LP in phase 1.  Such a batch
- *                 runs the kernel instance of the DEFAULT pricing rule (k_select_p1_rev) whatever the two pricing switches say.
+ *                 runs the kernel instance of the DEFAULT pricing rule (k_select_p1_rev) whatever the two pricing switches say; Devex
+ *                 pricing reaches it per call, bslv_lpq_solve_batch_method_priced below.
  * method outside 0..2, or h == NULL: BSLV_E_ARG, nothing changed.  bslv_lpq_last_phase1_stats, last_stats, last_ext_stats, last_passes,
  * last_period_stats and the ages cover the call as they cover a solve_batch; the in-call rescue (bslv_lpq_set_refactor) re-solves under
  * the call's method. */
 int  bslv_lpq_solve_batch_method(bslv_lpq *h, int method, int B, const int *src, const int *dst,
                                  const double *vlo, const double *vup, int *status, int *iters);
+/* ... under `method` AND under the two pricing rules of THIS call: dual_rule for the dual simplex steps, primal_rule for the primal ones
+ * (BSLV_LP_PRICING_DANTZIG / _DEVEX, with the meaning documented at bslv_lpq_set_pricing and bslv_lpq_set_primal_pricing).  The engine's
+ * method and its two pricing switches are neither read nor changed: the getters answer what they did and a later solve runs as if the call
+ * had not been made.
+ *   Tableau form  the call IS set_pricing(dual_rule); set_primal_pricing(primal_rule); solve_batch_method(method, ..); <both old switches
+ *                 back>, bit for bit: statuses, iters, slots, getters, every last_* statistic and both norm read-outs.
+ *   Revised form  DUAL is set_pricing(dual_rule); solve_batch(..); <the old switch back>, bit for bit (the primal rule does not reach a
+ *                 DUAL batch, in either form).  PRIMAL and REPAIR: this call is the only way to Devex pricing for such a batch there
+ *                 (k_select_priced_p1_rev<RULE>).  Which rule runs is decided as in the tableau form: dual_rule DEVEX runs the dual-Devex
+ *                 instance and the primal counters read 0 (no instance carries both rules); otherwise primal_rule DEVEX runs the
+ *                 primal-Devex instance; both DANTZIG is bslv_lpq_solve_batch_method, bit for bit.  New reference frameworks start where
+ *                 the two rules say: under the primal rule with a dual pivot of the LP, under the dual rule with a primal or phase-1
+ *                 pivot, under both with a refactorisation replay (the in-call rescue's re-solve, the resume after a periodic
+ *                 refactorisation).  Phase 1 weights its own pricing vector by the same norms; nothing is reset when it ends.
+ * A method or a rule out of range, or h == NULL: BSLV_E_ARG, nothing changed.  bslv_lpq_last_pricing_stats, _last_primal_pricing_stats and
+ * both _norms read-outs answer for this call as for a batch under the switches; last_phase1_stats, last_stats, last_period_stats and the
+ * ages cover it; the in-call rescue (bslv_lpq_set_refactor) re-solves under the call's method AND the call's rules. */
+int  bslv_lpq_solve_batch_method_priced(bslv_lpq *h, int method, int dual_rule, int primal_rule, int B, const int *src, const int *dst,
+                                        const double *vlo, const double *vup, int *status, int *iters);
 /* The LPs of the batch differ in their OBJECTIVE (lp_set_obj_coeffs + lp_solve, bslv_lp.c:141-151, 219-259, as phase2_dual
  * drives them, bslv_algs.c:1469-1477): cost costs[b*cost_cnt + t] on variable cost_first + t, zero elsewhere (the engine must
  * have been created with a zero cost vector).  LP b starts from the basis of slot src[b], which has to be primal feasible
@@ -439,8 +459,9 @@ int  bslv_lpq_last_phase1_stats(const bslv_lpq *h, long out[3]);
  * bslv_lpq_last_pricing_stats, of the last solve call: [0] dual selections made under the weighted rule, [1] of those, selections whose
  * row is not the row of the largest violation, [2] new reference frameworks after the start (one per primal or phase-1 pivot, one per
  * LP and refactorisation replay during the rounds).  All 0 with the switch off.
- * REVISED FORM, PRIMAL / REPAIR (bslv_lpq_solve_batch_method): no Devex instance carries the revised form's phase 1.  Such a batch runs
- * the instance of the default rule whatever this switch says -- the bits of the switch off -- and the counters read 0.
+ * REVISED FORM, PRIMAL / REPAIR (bslv_lpq_solve_batch_method): the rule reaches such a batch only through
+ * bslv_lpq_solve_batch_method_priced.  Under this switch it runs the instance of the default rule -- the bits of the switch off -- and
+ * the counters read 0.
  * bslv_lpq_last_pricing_norms (for tests): s_0 .. s_(M-1) of LP b of the last batch, M rows of the engine's OWN model (the given rows
  * less bslv_lpq_rows_folded); BSLV_E_STATE if the last solve call did not run under DEVEX, BSLV_E_ARG for b outside the batch. */
 enum { BSLV_LP_PRICING_DANTZIG = 0, BSLV_LP_PRICING_DEVEX = 1 };
@@ -470,8 +491,9 @@ int  bslv_lpq_last_pricing_norms(bslv_lpq *h, int b, double *s);
  *     such a batch keeps the dual-Devex instance: its primal steps are priced as before and the counters below read 0 -- no instance
  *     carries both rules;
  *   - DUAL-method batches never: their primal clean-up steps stay as they are;
- *   - PRIMAL / REPAIR batches of the REVISED form (bslv_lpq_solve_batch_method) never, under either switch: no Devex instance carries
- *     the revised form's phase 1, the batch runs the instance of the default rule and both counter triples read 0.
+ *   - PRIMAL / REPAIR batches of the REVISED form (bslv_lpq_solve_batch_method) never, under either switch: the rules reach them only
+ *     through bslv_lpq_solve_batch_method_priced; under the switches the batch runs the instance of the default rule and both counter
+ *     triples read 0.
  * The tie phases of the canonical switches and the replay's own selection never read or write the norms.  With the switch off nothing
  * is allocated, nothing launched and no bit differs.  Any other rule is BSLV_E_ARG; both forms accept the call.
  * BSLV_LP_PRIMAL_PRICING=dantzig|devex sets the rule an engine is created with (so the Benson and VLP drivers and bensolve_hip get it
@@ -877,6 +899,17 @@ int  bslv_benson_canonical_stats(const bslv_benson *h, long last[4], long total[
 int  bslv_benson_set_lp_method(bslv_benson *h, int method);
 int  bslv_benson_get_lp_method(const bslv_benson *h);
 int  bslv_benson_lp_method_stats(const bslv_benson *h, long out[3]);
+/* THE PRICING RULES of the driver's LPs, per call (bslv_lpq_solve_batch_method_priced): dual_rule and primal_rule are
+ * BSLV_LP_PRICING_DANTZIG / _DEVEX, or -1 / -1 = unset, the default.  Set, and only while the driver carries a method
+ * (bslv_benson_set_lp_method), the batches that went through bslv_lpq_solve_batch_method -- the start LPs, the P2(v) batches and both
+ * stages of the retry -- go through bslv_lpq_solve_batch_method_priced with these rules; without a method, or unset, the calls are what
+ * they were, bit for bit.  The LP engine's own switches are not touched.  This is how Devex pricing reaches the PRIMAL / REPAIR batches
+ * of a revised LP engine.  One rule -1 and the other not, or any other value: BSLV_E_ARG, nothing changed.
+ * BSLV_BENSON_LP_PRICING=<dantzig|devex>[:<dantzig|devex>] (dual[:primal], primal defaulting to dantzig) sets them when an engine is
+ * created, next to BSLV_BENSON_LP_METHOD (so bensolve_hip -l primal_simplex gets the rule without an option of its own); a malformed
+ * value leaves them unset.  bslv_benson_get_lp_pricing: the two rules as set (either pointer may be NULL); BSLV_E_ARG for h == NULL. */
+int  bslv_benson_set_lp_pricing(bslv_benson *h, int dual_rule, int primal_rule);
+int  bslv_benson_get_lp_pricing(const bslv_benson *h, int *dual_rule, int *primal_rule);
 /* LP CERTIFICATE: with on != 0 bslv_benson_solve_local and its _ctx twin certify the LPs of the batch that ended BSLV_LP_OPTIMAL with
  * bslv_lpq_certify, after the retries and before the getters, with the slots and bounds of the solve.  The first LP that is not certified
  * is printed on stderr (batch number, slot, the five residuals and where they were met), a summary line when the engine is destroyed;
